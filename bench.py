@@ -7,14 +7,15 @@ action / next-state tail) for every agent this process owns, closed loop: the en
 
 `value` is the metric as SURVEY.md 8(d) / BASELINE.md define it: 1 / MEDIAN wall time of one `MPCPolicy.act(obs, t)`
 -- NumPy observation in, all optimizer iterations on the GPU, NumPy action / next observation / reward out, the same
-bracket as the reference's utils/rollouts.py:92-101 -- times the agents the job owns, with p10 / p90.  The
-device-resident rate of the same closed loop (state never leaves HBM, launches never synchronised) is reported next
-to it as `device_resident_control_steps_per_sec`, and the dominant kernel's roofline is measured on that loop with HIP
-events on the launch stream.
+bracket as the reference's utils/rollouts.py:92-101 -- times the agents the job owns, with p10 / p90.  A plain run
+measures that and nothing else.  With --full the device-resident rate of the same closed loop (state never leaves
+HBM, launches never synchronised) is reported next to it as `device_resident_control_steps_per_sec`, and the dominant
+kernel's roofline is measured on that loop with HIP events on the launch stream.  --dump-outputs DIR writes what the
+last timed call returned (action, next observation, reward) as DIR/<name>.npy.
 
 Default workload = BASELINE.json configs[1]: Pendulum-v0 true dynamics, CEM, num_agents=1 per GPU, N=500, H=30,
-5 iterations, k=50.  At one GPU the same JSON line carries a `secondary` block for the north star's second target --
-HalfCheetah learned MLP (26-200-200-20), PI2, N=1000, H=30 -- with its own MFMA roofline and CPU baseline.
+5 iterations, k=50.  With --full at one GPU the same JSON line carries a `secondary` block for the north star's second
+target -- HalfCheetah learned MLP (26-200-200-20), PI2, N=1000, H=30 -- with its own MFMA roofline and CPU baseline.
 
 With --gpus N every rank owns its own agents (weak scaling, independent agents, RNG keyed by global agent id); the
 only exchange the path has is one RCCL all-gather of the packed (action | next_state | reward) records per control
@@ -207,6 +208,7 @@ class Workload:
             if self.use_dist:
                 self._torch_gather_host(b, a, n, r)
         self.obs = n                      # closed loop: the model is the environment
+        self.last_outputs = (a, n, r)
         self.last_host_record[b] = np.concatenate([a, n, np.asarray(r, np.float32).reshape(-1, 1)], axis=1)
 
     def _torch_gather_host(self, b, a, n, r):
@@ -341,6 +343,7 @@ class StubWorkload:
         rec[:, self.U:self.U + self.S] = self.obs * 0.5
         rec[:, -1] = -ga
         self.obs = rec[:, self.U:self.U + self.S].copy()
+        self.last_outputs = (rec[:, :self.U], self.obs, rec[:, -1])
         self.records[b] = self.torch.from_numpy(rec)
         self.last_host_record[b] = rec
         if self.use_dist:
@@ -378,7 +381,7 @@ class StubWorkload:
 def measure(W, steps, warmup, dist, use_dist, red_dev, act_only=False):
     """Times `steps` control steps twice: through MPCPolicy.act (the metric) and device-resident (the roofline).
     Both regions are bracketed by barrier + synchronize on both sides; elapsed = MAX over ranks.
-    act_only: just the MPCPolicy.act region (the launch-per-call repeat of the headline)."""
+    act_only: just the MPCPolicy.act region (the headline of a plain run, the launch-per-call repeat of --full)."""
     torch = W.torch
 
     def reduce_max(x):
@@ -402,6 +405,7 @@ def measure(W, steps, warmup, dist, use_dist, red_dev, act_only=False):
         walls[i] = time.perf_counter() - s0
     W.fence()
     t1 = time.perf_counter()
+    outputs = W.last_outputs                    # what the last timed call handed its caller (--dump-outputs)
     for i in range(steps, n_samples):
         s0 = time.perf_counter()
         W.act_step(warmup + i)
@@ -413,7 +417,7 @@ def measure(W, steps, warmup, dist, use_dist, red_dev, act_only=False):
     med, p10, p90 = (reduce_max(_pct(walls, q)) for q in (50, 10, 90))
     if act_only:
         return dict(walls=walls, act_elapsed=act_elapsed, median=med, p10=p10, p90=p90, n_samples=n_samples,
-                    gather_rows_checked=rows_act)
+                    gather_rows_checked=rows_act, outputs=outputs)
 
     # ---- (2) device-resident closed loop + HIP events around the dominant kernel ----------------------------------
     for _ in range(max(2, min(warmup, 20))):
@@ -442,7 +446,7 @@ def measure(W, steps, warmup, dist, use_dist, red_dev, act_only=False):
     dev_elapsed = reduce_max(t5 - t4)
     return dict(walls=walls, act_elapsed=act_elapsed, median=med, p10=p10, p90=p90, dev_elapsed=dev_elapsed,
                 dev_elapsed_instrumented=reduce_max(t3 - t2), roll_ms=roll_ms, roll_n=roll_n, kname=kname, kinst=kinst,
-                prof_every=every, gather_rows_checked=rows_act + rows_dev, n_samples=n_samples)
+                prof_every=every, gather_rows_checked=rows_act + rows_dev, n_samples=n_samples, outputs=outputs)
 
 
 SHAPE_KEYS = ("env", "opt", "N", "A", "H", "iters")
@@ -585,9 +589,8 @@ def result_block(name, W, m, world, steps, warmup):
     c = W.c
     total_agents = world * c["A"]
     value = total_agents / m["median"]
-    dev_rate = steps * total_agents / m["dev_elapsed"]
     traj = c["N"] * c["iters"] * (2 if c["opt"] == "SPSA" else 1)
-    return {
+    blk = {
         "metric": "MPC control-steps/sec (agent-control-steps; %s, %s N=%d H=%d)"
                   % (("HalfCheetah learned MLP %s" % "-".join(map(str, mlp_dims(c)))) if W.mlp else "Pendulum true model", c["opt"], c["N"], c["H"]),
         "value": value,
@@ -607,11 +610,23 @@ def result_block(name, W, m, world, steps, warmup):
         "ms_per_step": m["act_elapsed"] / steps * 1e3,
         "candidate_trajectories_per_sec": value * traj,
         "dyn_steps_per_sec": value * traj * c["H"],
-        "device_resident_control_steps_per_sec": dev_rate,
-        "device_resident_ms_per_step": m["dev_elapsed"] / steps * 1e3,
-        "device_resident_ms_per_step_with_events": m["dev_elapsed_instrumented"] / steps * 1e3,
-        "roofline": roofline(W, m, name, world),
     }
+    if "dev_elapsed" in m:                         # --full: the device-resident loop and the roofline measured on it
+        blk.update({
+            "device_resident_control_steps_per_sec": steps * total_agents / m["dev_elapsed"],
+            "device_resident_ms_per_step": m["dev_elapsed"] / steps * 1e3,
+            "device_resident_ms_per_step_with_events": m["dev_elapsed_instrumented"] / steps * 1e3,
+            "roofline": roofline(W, m, name, world),
+        })
+    return blk
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: what one MPCPolicy.act call returns -- action [A,U], next observation [A,S], reward [A] -- as
+    float32 .npy files, so that two builds run with the same arguments can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    for name, x in zip(("action", "next_observation", "reward"), outputs):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(x, np.float32))
 
 
 def _self_launch(n):
@@ -636,8 +651,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed control steps (default: per config, ~0.1-2 s of GPU time)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the MLP (north-star target 2) block at --gpus 1")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the device-resident loop and its roofline, the launch-per-call and strict-math "
+                         "repeats, the secondary / tutorial_two / config3 blocks and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the secondary / tutorial_two / config3 blocks of --config cfg2")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the action / next observation / reward the last timed step returned (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = DEFAULT_STEPS.get(args.config, 200)
@@ -696,11 +717,14 @@ def main():
     launch = "bench.py --gpus N started its own ranks (torch.distributed.run)" if os.environ.get("BBMPC_BENCH_SELF_LAUNCHED") \
         else ("external launcher (torch.distributed.run)" if "WORLD_SIZE" in os.environ else "single process")
 
-    def run_block(name, steps, warmup, agents=None, scaling="weak", launch_per_call=True):
-        """One configuration on all ranks: the MPCPolicy.act region, the device-resident region, and (launch_per_call)
-        the act region once more on a second handle created with BBMPC_LINGER_US=0.  Returns rank 0's block."""
+    def run_block(name, steps, warmup, agents=None, scaling="weak", launch_per_call=True, full=True, dump_dir=None):
+        """One configuration on all ranks: the MPCPolicy.act region; with `full` the device-resident region too, and
+        (launch_per_call) the act region once more on a second handle created with BBMPC_LINGER_US=0.  Returns rank 0's
+        block; rank 0 writes the outputs of the last timed act call to `dump_dir`."""
         W = cls(name, rank, world, local, dev, use_dist, backend, gather_mode, agents=agents)
-        m = measure(W, steps, warmup, dist, use_dist, red_dev)
+        m = measure(W, steps, warmup, dist, use_dist, red_dev, act_only=not full)
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, m["outputs"])
         blk = None
         if rank == 0:
             blk = result_block(name, W, m, world, steps, warmup)
@@ -721,7 +745,7 @@ def main():
         # kernel of a host-in / host-out call stays resident for BBMPC_LINGER_US and serves the next call from a mailbox
         # when the caller comes back in time, which this loop does; value_launch_per_call is the same >= 30 calls on a
         # handle created with BBMPC_LINGER_US=0 (one launch per call, whatever the caller's cadence)
-        if launch_per_call:
+        if full and launch_per_call:
             saved = os.environ.get("BBMPC_LINGER_US")
             os.environ["BBMPC_LINGER_US"] = "0"
             try:
@@ -765,9 +789,10 @@ def main():
                     blk["strict_math_median_ms"] = ms["median"] * 1e3
         return blk
 
-    out = run_block(args.config, args.steps, args.warmup)
+    # a plain run times the headline alone; --full adds everything else the line has carried
+    out = run_block(args.config, args.steps, args.warmup, full=args.full, dump_dir=args.dump_outputs)
 
-    if args.config == "cfg2" and not args.no_secondary:
+    if args.full and args.config == "cfg2" and not args.no_secondary:
         if world == 1 and not use_dist and not stub:
             # ---- north star target 2 in the same line: HalfCheetah learned MLP, PI2, N=1000, H=30 (MFMA path) ---------
             s_steps = max(200, min(DEFAULT_STEPS[SECONDARY], args.steps))
@@ -797,7 +822,7 @@ def main():
 
     if rank == 0:
         c = CONFIGS[args.config]
-        if not args.no_cpu_baseline and world == 1 and not stub and c["opt"] in ("RandomSearch", "CEM", "PI2"):
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub and c["opt"] in ("RandomSearch", "CEM", "PI2"):
             out["cpu_baseline"] = cpu_baseline(c)
         # RCCL prints its version banner through C stdio, which is block-buffered on a pipe and would otherwise
         # come out after this line at exit: push it out first so that the JSON line is the last line of stdout

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +23,7 @@ def _free_port():
     return p
 
 
-def _run(nproc, extra_env=None, args=()):
+def _run(nproc, extra_env=None, args=("--full",)):
     env = dict(os.environ, BBMPC_BENCH_BACKEND="gloo", BBMPC_BENCH_STUB="1", OMP_NUM_THREADS="1")
     env.update(extra_env or {})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
@@ -37,7 +38,7 @@ def _run(nproc, extra_env=None, args=()):
 
 @pytest.mark.parametrize("nproc,config", [(2, "cfg3"), (3, "cfg5pso")])
 def test_multi_rank_launch_line(nproc, config):
-    out = _run(nproc, args=("--config", config))
+    out = _run(nproc, args=("--full", "--config", config))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "median_ms", "p10_ms", "p90_ms",
                 "device_resident_control_steps_per_sec", "multi_gpu"):
@@ -60,7 +61,7 @@ def test_plain_launch_starts_its_own_ranks():
     env = dict(os.environ, BBMPC_BENCH_BACKEND="gloo", BBMPC_BENCH_STUB="1", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3",
-                          "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
     assert res.returncode == 0, res.stdout + res.stderr
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout
@@ -73,6 +74,27 @@ def test_plain_launch_starts_its_own_ranks():
     assert sec["scaling"] == "strong" and sec["n_gpus"] == 2 and "64 agents in total, 32 per GPU" in sec["note"]
     assert sec["multi_gpu"]["ranks"] == 2 and sec["multi_gpu"]["gathered_rows_checked"] == 2 * 2 * 64
     assert "PI2" in sec["metric"] and sec["value"] > 0
+
+
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline alone (one act region: its gathered rows are checked once), and
+    --dump-outputs writes what the last timed call returned; two runs with the same arguments write the same arrays."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        out = _run(2, args=("--config", "cfg5pso", "--dump-outputs", str(d)))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "multi_gpu"):
+            assert key in out, key
+        for key in ("roofline", "device_resident_control_steps_per_sec", "value_launch_per_call", "secondary",
+                    "cpu_baseline"):
+            assert key not in out, key
+        assert out["steps"] == 12 and out["multi_gpu"]["gathered_rows_checked"] == 2 * 2 * 4
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("action", "next_observation", "reward")})
+    a, n, r = (dumps[0][k] for k in ("action", "next_observation", "reward"))
+    assert a.shape == (4, 6) and n.shape == (4, 20) and r.shape == (4,)
+    assert all(x.dtype == np.float32 for x in (a, n, r))
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
 
 
 def test_world_size_mismatch_is_an_error_message():

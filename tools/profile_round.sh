@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="--no-cpu-baseline --no-secondary"
+B="--full --no-cpu-baseline --no-secondary"
 for CFG in $CFGS; do
   STEPS=200; W=5
   case $CFG in cfg4|cfg4pi2) STEPS=40;; cfg5cem|cfg5pso) STEPS=10;; cfg5cma) STEPS=6;; cfg2cma|cfg_tut2) STEPS=40;; esac
