@@ -9,13 +9,13 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BBMPC_LIB") or os.path.join(HERE, "libbbmpc.so")   # BBMPC_LIB: a debug build (tools/)
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # enums (bbmpc.h)
 OPT_NONE, OPT_RANDOM_SEARCH, OPT_CEM, OPT_PI2, OPT_PSO, OPT_CMAES, OPT_SPSA = range(7)
 DYN_PENDULUM, DYN_MLP, DYN_USER = 1, 2, 3
 REW_PENDULUM, REW_CHEETAH, REW_USER = 1, 2, 3
-USER_KIND_REWARD, USER_KIND_DYNAMICS = 1, 2
+USER_KIND_REWARD, USER_KIND_DYNAMICS, USER_KIND_INVERSE_TRANSFORM, USER_KIND_TRANSFORM = 1, 2, 3, 4
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 FIX_Q1_REWARD_ARG_ORDER = 1 << 0
 FIX_Q2_CEM_WARM_START = 1 << 1
@@ -71,6 +71,7 @@ SYMBOLS = [
     "bbmpc_set_reward_source", "bbmpc_set_dynamics_source", "bbmpc_check_user_source", "bbmpc_mlp_forward",
     "bbmpc_set_reward_callback", "bbmpc_set_dynamics_callback",
     "bbmpc_process_input", "bbmpc_process_output", "bbmpc_check_user_rollout",
+    "bbmpc_set_inverse_transform_source", "bbmpc_set_transform_source", "bbmpc_transform_rows", "bbmpc_check_xform_rollout",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -141,6 +142,10 @@ def _load():
     lib.bbmpc_check_user_source.argtypes = [i32, ctypes.c_char_p, i32, i32]
     lib.bbmpc_mlp_forward.argtypes = [vp, vp, i32, vp]
     lib.bbmpc_check_user_rollout.argtypes = [i32, i32, ctypes.c_char_p, ctypes.c_char_p, i32, i32]
+    lib.bbmpc_set_inverse_transform_source.argtypes = [vp, ctypes.c_char_p]
+    lib.bbmpc_set_transform_source.argtypes = [vp, ctypes.c_char_p]
+    lib.bbmpc_transform_rows.argtypes = [vp, i32, vp, vp, i32, vp]
+    lib.bbmpc_check_xform_rollout.argtypes = [i32, ctypes.c_char_p, ctypes.c_char_p, i32, i32]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

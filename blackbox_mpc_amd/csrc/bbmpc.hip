@@ -288,6 +288,9 @@ Engine::~Engine() {
     user_reward.release();
     user_dynamics.release();
     user_rollout.release();
+    user_xform.release();
+    user_fwd_xform.release();
+    user_xform_rollout.release();
     if (h_pin) (void)hipHostFree(h_pin);
     for (auto*& hs : h_record_stage) { if (hs) (void)hipHostFree(hs); hs = nullptr; }
     if (host_done) (void)hipHostFree(host_done);
@@ -533,7 +536,7 @@ void Engine::set_user_source(int kind, const char* src) {
     else REQUIRE(cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_STATE, "handle was not created with BBMPC_DYN_USER");
     std::vector<char> code;
     try {
-        code = compile_user_program(src, kind, S, U);
+        code = compile_user_program(src, kind, S, U, kind == USER_KIND_DYNAMICS ? user_xform.source : std::string());
     } catch (const std::exception& ex) {
         throw HipError(BBMPC_E_INVALID, ex.what());
     }
@@ -546,17 +549,72 @@ void Engine::set_user_source(int kind, const char* src) {
     f.source = src;
     f.cb = nullptr; f.cb_user = nullptr;
     user_rollout_stale = true;
+    user_xform_rollout_stale = true;
 }
 
 void Engine::set_user_callback(int kind, bbmpc_rows_callback fn, void* user) {
     if (kind == USER_KIND_REWARD) REQUIRE(cfg.reward == BBMPC_REW_USER, BBMPC_E_STATE, "handle was not created with BBMPC_REW_USER");
     else REQUIRE(cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_STATE, "handle was not created with BBMPC_DYN_USER");
+    REQUIRE(!(fn && kind == USER_KIND_DYNAMICS && has_xform()), BBMPC_E_UNSUPPORTED,
+            "a dynamics callback returns absolute next states: apply the inverse target transform inside it (clear the transform first)");
     HIP_CHECK(hipStreamSynchronize(stream));
     UserFunction& f = kind == USER_KIND_REWARD ? user_reward : user_dynamics;
     if (fn) { f.release(); f.source.clear(); }
     f.cb = fn;
     f.cb_user = fn ? user : nullptr;
     user_rollout_stale = true;
+    user_xform_rollout_stale = true;
+}
+
+// Target transforms (rtc.hpp): the inverse one on a learned-model or BBMPC_DYN_USER handle replaces next = dev + state
+// in every rollout, step and row call of the handle; src NULL / empty clears it.  The forward one only serves
+// transform_rows (training targets).  Compiled here, so a compiler error comes back from this call.
+void Engine::set_transform_source(int kind, const char* src) {
+    const bool clear = !src || !*src;
+    const bool inverse = kind == USER_KIND_INVERSE_TRANSFORM;
+    if (inverse && !clear) {
+        REQUIRE(cfg.dynamics == BBMPC_DYN_MLP || cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
+                "an inverse target transform needs a learned-model (BBMPC_DYN_MLP) or BBMPC_DYN_USER handle; the built-in pendulum "
+                "model keeps next = dev + state");
+        REQUIRE(!user_dynamics.cb, BBMPC_E_UNSUPPORTED,
+                "inverse target transform: this handle's dynamics is a callback, which returns absolute next states itself");
+    }
+    const bool rebuild_dyn = inverse && cfg.dynamics == BBMPC_DYN_USER && !user_dynamics.source.empty();
+    std::vector<char> code, dyn_code;
+    try {
+        if (!clear) code = compile_user_program(src, kind, S, U);
+        if (rebuild_dyn) dyn_code = compile_user_program(user_dynamics.source, USER_KIND_DYNAMICS, S, U, clear ? std::string() : std::string(src));
+    } catch (const std::exception& ex) {
+        throw HipError(BBMPC_E_INVALID, ex.what());
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    UserFunction& f = inverse ? user_xform : user_fwd_xform;
+    f.release();
+    f.source.clear();
+    if (!clear) {
+        HIP_CHECK(hipModuleLoadData(&f.module, code.data()));
+        HIP_CHECK(hipModuleGetFunction(&f.fn, f.module, inverse ? "bbmpc_user_inverse_transform_rows" : "bbmpc_user_transform_rows"));
+        f.source = src;
+    }
+    if (rebuild_dyn) {
+        user_dynamics.release();
+        HIP_CHECK(hipModuleLoadData(&user_dynamics.module, dyn_code.data()));
+        HIP_CHECK(hipModuleGetFunction(&user_dynamics.fn, user_dynamics.module, "bbmpc_user_dynamics_rows"));
+    }
+    if (inverse) {
+        user_rollout_stale = true;
+        user_xform_rollout_stale = true;
+        user_xform_rollout.release();
+    }
+}
+
+// out = transform(d_a, d_b) on [batch] rows: inverse (cur, dev) -> next, forward (cur, next) -> target
+void Engine::transform_rows(int kind, const float* d_a, const float* d_b, int batch, float* d_out) {
+    const UserFunction& f = kind == USER_KIND_INVERSE_TRANSFORM ? user_xform : user_fwd_xform;
+    REQUIRE(f.fn, BBMPC_E_STATE, kind == USER_KIND_INVERSE_TRANSFORM ? "no inverse target transform set (bbmpc_set_inverse_transform_source)"
+                                                                    : "no target transform set (bbmpc_set_transform_source)");
+    void* args[] = {(void*)&d_a, (void*)&d_b, (void*)&batch, (void*)&d_out};
+    HIP_CHECK(hipModuleLaunchKernel(f.fn, (unsigned)((batch + 255) / 256), 1, 1, 256, 1, 1, 0, stream, args, nullptr));
 }
 
 // total (+)= the rewards a callback wrote for one batch of rows
@@ -589,6 +647,10 @@ void Engine::dynamics_rows(const float* d_states, const float* d_actions, int as
         hipLaunchKernelGGL(k_step_pendulum, dim3((batch + 63) / 64), dim3(64), 0, stream, d_states, d_actions, astride, batch,
                            (int)fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER), d_next, (float*)nullptr);
         HIP_CHECK(hipGetLastError());
+        return;
+    }
+    if (has_xform()) {                                                    // learned model + inverse target transform
+        mlp_xform_rows(d_states, d_actions, astride, batch, d_next);
         return;
     }
     step_dev(d_states, d_actions, astride, batch, d_next, nullptr);        // learned model (its built-in reward kind is REW_NONE here)
@@ -675,7 +737,8 @@ void Engine::rollout_user_fused(int mode, bool pen, RolloutArgs& ra) {
         std::vector<char> code;
         try {
             code = compile_user_rollout(cfg.reward == BBMPC_REW_USER ? user_reward.source : std::string(),
-                                        cfg.dynamics == BBMPC_DYN_USER ? user_dynamics.source : std::string(), cfg.dynamics, cfg.reward, S, U);
+                                        cfg.dynamics == BBMPC_DYN_USER ? user_dynamics.source : std::string(), cfg.dynamics, cfg.reward, S, U,
+                                        user_xform.source);
         } catch (const std::exception& ex) {
             throw HipError(BBMPC_E_INVALID, ex.what());
         }
@@ -746,6 +809,86 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_rows_mlp_raw(RowMlp net, const
     for (int i = tid; i < M; i += nthr) out[(size_t)b * M + i] = raw[i];
 }
 
+// Learned model + inverse target transform on rows, the step-wise twin of bbmpc_mlp_xform_rollout and the one-step path
+// (predict_next_state, the next state act() returns): process_input, the Dense stack (k_rows_mlp_raw, k_tail_mlp's
+// per-row code), de-normalise, then the user's transform rows (system_dynamics_handler.py:97-161).
+void Engine::mlp_xform_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next) {
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    const float* acts_c = d_actions;
+    if (astride != U) {
+        if (d_step_act.n < (size_t)batch * U) d_step_act.alloc((size_t)batch * U);
+        HIP_CHECK(hipMemcpy2DAsync(d_step_act.p, (size_t)U * 4, d_actions, (size_t)astride * 4, (size_t)U * 4, batch,
+                                   hipMemcpyDeviceToDevice, stream));
+        acts_c = d_step_act.p;
+    }
+    if (u_xin.n < (size_t)batch * (S + U)) u_xin.alloc((size_t)batch * (S + U));
+    if (u_xraw.n < (size_t)batch * S) u_xraw.alloc((size_t)batch * S);
+    const float* stats = mlp.normalized ? d_stats.p : nullptr;
+    hipLaunchKernelGGL(k_process_input, dim3((batch * (S + U) + 255) / 256), dim3(256), 0, stream, d_states, acts_c, batch, S, U, stats, u_xin.p);
+    hipLaunchKernelGGL(k_rows_mlp_raw, dim3(batch), dim3(TAIL_THREADS), 0, stream, row_mlp(), (const float*)u_xin.p, u_xraw.p);
+    if (stats) hipLaunchKernelGGL(k_denormalize_rows, dim3((batch * S + 255) / 256), dim3(256), 0, stream, batch, S, U, stats, u_xraw.p);
+    HIP_CHECK(hipGetLastError());
+    transform_rows(USER_KIND_INVERSE_TRANSFORM, d_states, u_xraw.p, batch, d_next);
+}
+
+// The learned-model rollout with the inverse target transform (and a user reward, if any) inlined: kernels_mlp_xform.hpp,
+// compiled through hiprtc on first use after the sources change.  Candidates of RandomSearch / CEM / PI2 are drawn into the
+// sample buffer first (k_gen_candidates), as for the other user-function rollouts.
+void Engine::rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra) {
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    if (cfg.reward == BBMPC_REW_USER) REQUIRE(user_reward.fn, BBMPC_E_STATE, "user reward: call bbmpc_set_reward_source before computing");
+    const XformLds lay = xform_lds_layout(mlp.tiles, mlp.n_layers, ra.H, S, U, mlp_nw);
+    const size_t lds = (size_t)lay.total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "learned-model rollout with an inverse target transform: a 16-particle tile's action block plus the activation / "
+            "partial-sum buffers of this network do not fit one CU's LDS (shorten the horizon or narrow the network)");
+    if (user_xform_rollout_stale || !user_xform_rollout.fn) {
+        std::vector<char> code;
+        try {
+            code = compile_mlp_xform_rollout(user_xform.source, cfg.reward == BBMPC_REW_USER ? user_reward.source : std::string(),
+                                             cfg.reward, S, U);
+        } catch (const std::exception& ex) {
+            throw HipError(BBMPC_E_INVALID, ex.what());
+        }
+        user_xform_rollout.release();
+        HIP_CHECK(hipModuleLoadData(&user_xform_rollout.module, code.data()));
+        HIP_CHECK(hipModuleGetFunction(&user_xform_rollout.fn, user_xform_rollout.module, "bbmpc_mlp_xform_rollout"));
+        user_xform_rollout_stale = false;
+    }
+    if (mode == SRC_UNIFORM || mode == SRC_TRUNC) {
+        REQUIRE(ra.samples, BBMPC_E_STATE, "learned-model transform rollout: no sample buffer");
+        dim3 ggrid((ra.n_pop + 255) / 256, A), gblock(256);
+        if (mode == SRC_UNIFORM) hipLaunchKernelGGL(k_gen_candidates<SRC_UNIFORM>, ggrid, gblock, 0, stream, ra);
+        else hipLaunchKernelGGL(k_gen_candidates<SRC_TRUNC>, ggrid, gblock, (size_t)2 * ra.HU * sizeof(float), stream, ra);
+        HIP_CHECK(hipGetLastError());
+    }
+    XformArgs x;
+    memset(&x, 0, sizeof(x));
+    x.n_pop = ra.n_pop; x.A = A; x.H = ra.H; x.Nst = ra.Nst;
+    x.from_ref = mode == SRC_REF ? 1 : 0;
+    x.pen = pen ? 1 : 0;
+    x.fix_q1 = (int)fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER);
+    x.nw = mlp_nw;
+    x.n_layers = mlp.n_layers;
+    x.normalized = mlp.normalized;
+    for (int l = 0; l <= mlp.n_layers; ++l) x.tiles[l] = mlp.tiles[l];
+    for (int l = 0; l < mlp.n_layers; ++l) { x.act[l] = mlp.act[l]; x.wp4[l] = d_wpack4[l].p; x.bpack[l] = mlp.bpack[l]; }
+    x.mean_s = mlp.mean_s; x.std_s = mlp.std_s; x.mean_a = mlp.mean_a; x.std_a = mlp.std_a; x.mean_t = mlp.mean_t; x.std_t = mlp.std_t;
+    x.state = ra.state;
+    x.seq = ra.seq;
+    x.cand = mode == SRC_BUF ? ra.cand : ra.samples;
+    x.samples = (pen && mode != SRC_REF) ? ra.samples : nullptr;          // the feasible candidates go back
+    x.lo = ra.lo; x.hi = ra.hi;
+    x.rewards = ra.rewards;
+    x.penalty_out = ra.penalty_out;
+    if (mode != SRC_REF) REQUIRE(x.cand, BBMPC_E_STATE, "learned-model transform rollout: no candidate buffer");
+    void* args[] = {&x};
+    prof_begin();
+    HIP_CHECK(hipModuleLaunchKernel(user_xform_rollout.fn, (unsigned)((ra.n_pop + XF_TP - 1) / XF_TP), (unsigned)A, 1, (unsigned)(mlp_nw * 64),
+                                    1, 1, (unsigned)lds, stream, args, nullptr));
+    prof_end();
+}
+
 void Engine::mlp_forward_rows(const float* d_x, int batch, float* d_out) {
     REQUIRE(cfg.dynamics == BBMPC_DYN_MLP && mlp_ready, BBMPC_E_STATE, "bbmpc_mlp_forward: needs a learned-dynamics handle with weights set");
     hipLaunchKernelGGL(k_rows_mlp_raw, dim3(batch), dim3(TAIL_THREADS), 0, stream, row_mlp(), d_x, d_out);
@@ -760,6 +903,9 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
         } else if (cfg.dynamics != BBMPC_DYN_MLP && !user_stepwise_only) {
             dominant_kernel = "bbmpc_user_rollout(hiprtc)";
             rollout_user_fused(mode, pen, ra);
+        } else if (cfg.dynamics == BBMPC_DYN_MLP && !user_stepwise_only && has_xform()) {
+            dominant_kernel = "bbmpc_mlp_xform_rollout(hiprtc)";
+            rollout_mlp_xform(mode, pen, ra);
         } else if (cfg.dynamics == BBMPC_DYN_MLP && !user_stepwise_only) {
             dominant_kernel = "k_rollout_mlp";
             rollout_mlp_user_reward(mode, pen, ra);
@@ -1363,14 +1509,15 @@ void Engine::evaluate_dev(const float* d_state_in, const float* d_seq, int n_pop
 
 void Engine::step_dev(const float* d_states, const float* d_actions, int astride, int batch, float* d_next, float* d_rew) {
     REQUIRE(batch >= 1, BBMPC_E_INVALID, "batch must be >= 1");
-    if (user_path() && (cfg.dynamics == BBMPC_DYN_USER || d_rew)) {
-        // user dynamics, or a reward the built-in step kernels cannot evaluate: dynamics rows, then reward rows
+    if (user_path() && (cfg.dynamics == BBMPC_DYN_USER || has_xform() || d_rew)) {
+        // user dynamics / an inverse target transform, or a reward the built-in step kernels cannot evaluate: dynamics rows,
+        // then reward rows
         float* nx = d_next;
         if (!nx) {
             if (u_next.n < (size_t)batch * S) u_next.alloc((size_t)batch * S);
             nx = u_next.p;
         }
-        if (cfg.dynamics == BBMPC_DYN_USER) dynamics_rows(d_states, d_actions, astride, batch, nx);
+        if (cfg.dynamics == BBMPC_DYN_USER || has_xform()) dynamics_rows(d_states, d_actions, astride, batch, nx);
         else step_dev(d_states, d_actions, astride, batch, nx, nullptr);
         if (d_rew) reward_rows(d_states, nx, d_actions, astride, batch, d_rew, 0);
         return;
@@ -1833,7 +1980,8 @@ int bbmpc_set_dynamics_source(bbmpc_handle h, const char* src) {
 int bbmpc_check_user_source(int32_t kind, const char* src, int32_t dim_s, int32_t dim_u) {
     API_BEGIN
     CHECK_PTR(src);
-    if (kind != bbmpc::USER_KIND_REWARD && kind != bbmpc::USER_KIND_DYNAMICS) throw HipError(BBMPC_E_INVALID, "kind must be 1 (reward) or 2 (dynamics)");
+    if (kind < bbmpc::USER_KIND_REWARD || kind > bbmpc::USER_KIND_TRANSFORM)
+        throw HipError(BBMPC_E_INVALID, "kind must be 1 (reward), 2 (dynamics), 3 (inverse target transform) or 4 (target transform)");
     if (dim_s < 1 || dim_u < 1 || dim_s > 256 || dim_u > 256) throw HipError(BBMPC_E_INVALID, "dim_s / dim_u must be in [1, 256]");
     try {
         (void)bbmpc::compile_user_program(src, kind, dim_s, dim_u);
@@ -1851,6 +1999,58 @@ int bbmpc_check_user_rollout(int32_t dynamics, int32_t reward, const char* dyn_s
     if (dim_s < 1 || dim_u < 1 || dim_s > 256 || dim_u > 256) throw HipError(BBMPC_E_INVALID, "dim_s / dim_u must be in [1, 256]");
     try {
         (void)bbmpc::compile_user_rollout(reward == BBMPC_REW_USER ? rew_src : "", dynamics == BBMPC_DYN_USER ? dyn_src : "", dynamics, reward, dim_s, dim_u);
+    } catch (const std::exception& ex) {
+        throw HipError(BBMPC_E_INVALID, ex.what());
+    }
+    API_END
+}
+
+int bbmpc_set_inverse_transform_source(bbmpc_handle h, const char* src) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->invalidate_step_graph();
+    h->e->set_transform_source(bbmpc::USER_KIND_INVERSE_TRANSFORM, src);
+    API_END
+}
+
+int bbmpc_set_transform_source(bbmpc_handle h, const char* src) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->invalidate_step_graph();
+    h->e->set_transform_source(bbmpc::USER_KIND_TRANSFORM, src);
+    API_END
+}
+
+int bbmpc_transform_rows(bbmpc_handle h, int32_t kind, const float* a, const float* b, int32_t batch, float* out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(a);
+    CHECK_PTR(b);
+    CHECK_PTR(out);
+    Engine& e = *h->e;
+    if (kind != bbmpc::USER_KIND_INVERSE_TRANSFORM && kind != bbmpc::USER_KIND_TRANSFORM)
+        throw HipError(BBMPC_E_INVALID, "kind must be 3 (inverse target transform) or 4 (target transform)");
+    if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
+    const size_t n = (size_t)batch * e.S;
+    if (e.d_step_b.n < 3 * n) e.d_step_b.alloc(3 * n);
+    float* da = e.d_step_b.p; float* db = da + n; float* dout = db + n;
+    HIP_CHECK(hipMemcpyAsync(da, a, n * 4, hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(db, b, n * 4, hipMemcpyHostToDevice, e.stream));
+    e.transform_rows(kind, da, db, batch, dout);
+    HIP_CHECK(hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
+
+int bbmpc_check_xform_rollout(int32_t reward, const char* xform_src, const char* rew_src, int32_t dim_s, int32_t dim_u) {
+    API_BEGIN
+    CHECK_PTR(xform_src);
+    if (reward < BBMPC_REW_PENDULUM || reward > BBMPC_REW_USER) throw HipError(BBMPC_E_INVALID, "unknown reward kind");
+    if (reward == BBMPC_REW_USER && !rew_src) throw HipError(BBMPC_E_INVALID, "missing reward source");
+    // the learned model's limits (bbmpc_set_mlp)
+    if (dim_s < 1 || dim_u < 1 || dim_s > 64 || dim_s + dim_u > 128) throw HipError(BBMPC_E_UNSUPPORTED, "dim_s <= 64 and dim_s + dim_u <= 128");
+    try {
+        (void)bbmpc::compile_mlp_xform_rollout(xform_src, reward == BBMPC_REW_USER ? rew_src : "", reward, dim_s, dim_u);
     } catch (const std::exception& ex) {
         throw HipError(BBMPC_E_INVALID, ex.what());
     }

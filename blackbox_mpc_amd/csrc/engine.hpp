@@ -23,6 +23,7 @@
 #include "kernels_fused_cma.hpp"
 #include "kernels_fused_pso.hpp"
 #include "kernels_mlp.hpp"
+#include "kernels_mlp_xform.hpp"
 #include "kernels_mlp_q4s.hpp"
 #include "kernels_mlp_w4.hpp"
 #include "kernels_mlp_wave.hpp"
@@ -286,7 +287,17 @@ struct Engine {
     bool cem_sigma0_ready = false;     // d_sigma0 holds cem_sigma(prev_mean, var0): constant while CEM restarts from the constructor distribution
     DevBuf<float> d_sigma0;
     DevBuf<float> u_rows, u_x0, u_x1, u_total, u_pen, u_next;
-    bool user_path() const { return cfg.reward == BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_USER; }
+    // target transforms (rtc.hpp USER_KIND_*TRANSFORM): the inverse one replaces next = dev + state in every dynamics step of
+    // the handle, so a handle with one takes the user-function paths; the forward one only serves bbmpc_transform_rows
+    UserFunction user_xform, user_fwd_xform, user_xform_rollout;   // user_xform_rollout: kernels_mlp_xform.hpp, built lazily
+    bool user_xform_rollout_stale = true;
+    bool has_xform() const { return !user_xform.source.empty(); }
+    void set_transform_source(int kind, const char* src);
+    void transform_rows(int kind, const float* d_a, const float* d_b, int batch, float* d_out);
+    void rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra);
+    void mlp_xform_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next);
+    DevBuf<float> u_xin, u_xraw;       // learned model + transform, step-wise: processed inputs / de-normalised outputs
+    bool user_path() const { return cfg.reward == BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_USER || has_xform(); }
     int builtin_reward_kind() const { return cfg.reward == BBMPC_REW_USER ? REW_NONE : cfg.reward; }
     void set_user_source(int kind, const char* src);
     void set_user_callback(int kind, bbmpc_rows_callback fn, void* user);

@@ -126,4 +126,13 @@ static __global__ void k_process_output(const float* states, const float* raw, i
     out[i] = dev + states[i];                                                // transforms.py:34
 }
 
+// process_output's de-normalisation alone, in place: dev = mean_t + raw * (std_t + 1e-7) (:152-155) -- what an inverse target
+// transform receives
+static __global__ void k_denormalize_rows(int batch, int S, int U, const float* stats, float* raw) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * S) return;
+    const int f = i % S;
+    raw[i] = stats[2 * S + 2 * U + f] + raw[i] * (stats[3 * S + 2 * U + f] + 1e-7f);
+}
+
 }  // namespace bbmpc

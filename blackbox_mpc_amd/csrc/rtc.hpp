@@ -71,13 +71,24 @@ private:
 };
 
 constexpr int USER_KIND_REWARD = 1, USER_KIND_DYNAMICS = 2;
+// target transforms (SystemDynamicsHandler's transform_targets_func / inverse_transform_targets_func, reference
+// dynamics_handlers/system_dynamics_handler.py:15-17, 128-161, 314):
+//     __device__ void bbmpc_user_inverse_transform_targets(const float* cur, const float* dev, float* next, int S);
+//     __device__ void bbmpc_user_transform_targets(const float* cur, const float* next, float* target, int S);
+constexpr int USER_KIND_INVERSE_TRANSFORM = 3, USER_KIND_TRANSFORM = 4;
 
 // The row kernels the engine launches around the user's function.  BBMPC_S / BBMPC_U are compile-time so the per-row
-// arrays live in registers; rows are [batch, S] / [batch, astride] row-major.
-inline std::string user_program_source(const std::string& user_src, int kind) {
+// arrays live in registers; rows are [batch, S] / [batch, astride] row-major.  `xform_src` (dynamics only, may be empty):
+// the handle's inverse target transform, which then replaces next = delta + state (BBMPC_XFORM).
+inline std::string user_program_source(const std::string& user_src, int kind, const std::string& xform_src = std::string()) {
     std::string s;
     s += "// ---- user source ------------------------------------------------------------------\n";
     s += user_src;
+    if (kind == USER_KIND_DYNAMICS && !xform_src.empty()) {
+        s += "\n// ---- user inverse target transform ----------------------------------------------------\n";
+        s += xform_src;
+        s += "\n#define BBMPC_XFORM 1\n";
+    }
     s += "\n// ---- row kernels (blackbox_mpc_amd/csrc/rtc.hpp) ------------------------------------\n";
     if (kind == USER_KIND_REWARD) {
         s += R"RTC(
@@ -121,6 +132,32 @@ extern "C" __global__ void bbmpc_user_reward_traj(int n_pop, int A, int H, int N
     rewards[(size_t)a * Nst + n] = total + rewards[(size_t)a * Nst + n];
 }
 )RTC";
+    } else if (kind == USER_KIND_INVERSE_TRANSFORM) {
+        s += R"RTC(
+// next = inverse_transform_targets_func(cur, dev) on rows (system_dynamics_handler.py:157-161)
+extern "C" __global__ void bbmpc_user_inverse_transform_rows(const float* __restrict__ cur, const float* __restrict__ dev,
+                                                             int batch, float* __restrict__ next) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    float c[BBMPC_S], d[BBMPC_S], nx[BBMPC_S];
+    for (int i = 0; i < BBMPC_S; ++i) { c[i] = cur[(size_t)b * BBMPC_S + i]; d[i] = dev[(size_t)b * BBMPC_S + i]; }
+    bbmpc_user_inverse_transform_targets(c, d, nx, BBMPC_S);
+    for (int i = 0; i < BBMPC_S; ++i) next[(size_t)b * BBMPC_S + i] = nx[i];
+}
+)RTC";
+    } else if (kind == USER_KIND_TRANSFORM) {
+        s += R"RTC(
+// target = transform_targets_func(cur, next) on rows (system_dynamics_handler.py:314)
+extern "C" __global__ void bbmpc_user_transform_rows(const float* __restrict__ cur, const float* __restrict__ next,
+                                                     int batch, float* __restrict__ target) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    float c[BBMPC_S], nx[BBMPC_S], tg[BBMPC_S];
+    for (int i = 0; i < BBMPC_S; ++i) { c[i] = cur[(size_t)b * BBMPC_S + i]; nx[i] = next[(size_t)b * BBMPC_S + i]; }
+    bbmpc_user_transform_targets(c, nx, tg, BBMPC_S);
+    for (int i = 0; i < BBMPC_S; ++i) target[(size_t)b * BBMPC_S + i] = tg[i];
+}
+)RTC";
     } else {
         s += R"RTC(
 extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ states, const float* __restrict__ act,
@@ -131,14 +168,20 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
     for (int i = 0; i < BBMPC_S; ++i) x[i] = states[(size_t)b * BBMPC_S + i];                    // process_input: concat
     for (int i = 0; i < BBMPC_U; ++i) x[BBMPC_S + i] = act[(size_t)b * astride + i];
     bbmpc_user_dynamics(x, d, BBMPC_S, BBMPC_U);                                                // f(x, train=False) -> delta
+#ifdef BBMPC_XFORM
+    float nx[BBMPC_S];
+    bbmpc_user_inverse_transform_targets(x, d, nx, BBMPC_S);                                    // the raw output (:148-151)
+    for (int i = 0; i < BBMPC_S; ++i) next_states[(size_t)b * BBMPC_S + i] = nx[i];
+#else
     for (int i = 0; i < BBMPC_S; ++i) next_states[(size_t)b * BBMPC_S + i] = d[i] + x[i];        // transforms.py:34
+#endif
 }
 )RTC";
     }
     return s;
 }
 
-#include "_embed.inc"      // k_embed_fastmath, k_embed_models: the leaf-math headers as text (generated by _build.py)
+#include "_embed.inc"      // k_embed_fastmath, k_embed_models, k_embed_kernels_mlp_xform: headers as text (generated by _build.py)
 
 // The FUSED form: one lane per candidate trajectory, the whole H-step recurrence in registers, with the user's
 // function(s) inlined next to the built-in model / rewards (the engine's own models.hpp, compiled from the same text
@@ -146,10 +189,14 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
 // the step-wise evaluator (kernels_user.hpp) stays for MLP + user reward.
 //   BBMPC_DYN_KIND 1 = PendulumTrueModel (op-for-op form), 3 = bbmpc_user_dynamics
 //   BBMPC_REW_KIND 1 / 2 = built-in pendulum / cheetah reward, 3 = bbmpc_user_reward
-inline std::string user_rollout_source(const std::string& reward_src, const std::string& dynamics_src) {
+//   xform_src (user dynamics only, may be empty): the inverse target transform, inlined in place of next = delta + state
+inline std::string user_rollout_source(const std::string& reward_src, const std::string& dynamics_src,
+                                       const std::string& xform_src = std::string()) {
     std::string s = "#include \"models.hpp\"\n";
     s += "// ---- user reward --------------------------------------------------------------------\n" + reward_src + "\n";
     s += "// ---- user dynamics ------------------------------------------------------------------\n" + dynamics_src + "\n";
+    if (!xform_src.empty())
+        s += "// ---- user inverse target transform ---------------------------------------------------\n" + xform_src + "\n#define BBMPC_XFORM 1\n";
     s += R"RTC(
 extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, int from_ref, int pen, int fix_q1,
                                               const float* __restrict__ state, const float* __restrict__ seq,
@@ -180,7 +227,11 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
         {
             float d[S];
             bbmpc_user_dynamics(x, d, S, U);                                   // f(x, train=False) -> delta
+#ifdef BBMPC_XFORM
+            bbmpc_user_inverse_transform_targets(x, d, nx, S);                 // the raw output (:148-151)
+#else
             for (int i = 0; i < S; ++i) nx[i] = d[i] + x[i];                     // transforms.py:34
+#endif
         }
 #else
         {
@@ -216,9 +267,9 @@ inline std::vector<char> compile_rtc(const std::string& src, const char* name, c
                                      bool with_engine_headers) {
     const Hiprtc& r = Hiprtc::get();
     Hiprtc::Program prog = nullptr;
-    const char* hdr_text[] = {k_embed_fastmath, k_embed_models};
-    const char* hdr_name[] = {"fastmath.hpp", "models.hpp"};
-    int rc = r.CreateProgram(&prog, src.c_str(), name, with_engine_headers ? 2 : 0, with_engine_headers ? hdr_text : nullptr,
+    const char* hdr_text[] = {k_embed_fastmath, k_embed_models, k_embed_kernels_mlp_xform};
+    const char* hdr_name[] = {"fastmath.hpp", "models.hpp", "kernels_mlp_xform.hpp"};
+    int rc = r.CreateProgram(&prog, src.c_str(), name, with_engine_headers ? 3 : 0, with_engine_headers ? hdr_text : nullptr,
                              with_engine_headers ? hdr_name : nullptr);
     if (rc != 0) throw std::runtime_error(std::string("hiprtcCreateProgram: ") + r.GetErrorString(rc));
     // one rounding per source operation, as everywhere in the engine (and as the reference's TF ops round)
@@ -247,16 +298,35 @@ inline std::vector<char> compile_rtc(const std::string& src, const char* name, c
     return code;
 }
 
-inline std::vector<char> compile_user_program(const std::string& user_src, int kind, int S, int U) {
-    return compile_rtc(user_program_source(user_src, kind), kind == USER_KIND_REWARD ? "bbmpc_user_reward.hip" : "bbmpc_user_dynamics.hip",
+inline std::vector<char> compile_user_program(const std::string& user_src, int kind, int S, int U,
+                                             const std::string& xform_src = std::string()) {
+    static const char* const names[] = {"", "bbmpc_user_reward.hip", "bbmpc_user_dynamics.hip", "bbmpc_user_inverse_transform.hip",
+                                        "bbmpc_user_transform.hip"};
+    return compile_rtc(user_program_source(user_src, kind, xform_src), names[kind],
                        {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U)}, false);
 }
 
 inline std::vector<char> compile_user_rollout(const std::string& reward_src, const std::string& dynamics_src, int dyn_kind, int rew_kind,
-                                              int S, int U) {
-    return compile_rtc(user_rollout_source(reward_src, dynamics_src), "bbmpc_user_rollout.hip",
+                                              int S, int U, const std::string& xform_src = std::string()) {
+    return compile_rtc(user_rollout_source(reward_src, dynamics_src, xform_src), "bbmpc_user_rollout.hip",
                        {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U), "-DBBMPC_DYN_KIND=" + std::to_string(dyn_kind),
                         "-DBBMPC_REW_KIND=" + std::to_string(rew_kind)}, true);
+}
+
+// The learned-model rollout with the inverse target transform inlined (kernels_mlp_xform.hpp); reward_src is the user
+// reward when rew_kind == 3 (BBMPC_REW_USER), else empty and a built-in reward kind.
+inline std::string mlp_xform_rollout_source(const std::string& xform_src, const std::string& reward_src) {
+    std::string s = "#include \"models.hpp\"\n";
+    s += "// ---- user reward --------------------------------------------------------------------\n" + reward_src + "\n";
+    s += "// ---- user inverse target transform ---------------------------------------------------\n" + xform_src + "\n";
+    s += "#define BBMPC_XFORM_KERNEL 1\n#include \"kernels_mlp_xform.hpp\"\n";
+    return s;
+}
+
+inline std::vector<char> compile_mlp_xform_rollout(const std::string& xform_src, const std::string& reward_src, int rew_kind, int S, int U) {
+    return compile_rtc(mlp_xform_rollout_source(xform_src, reward_src), "bbmpc_mlp_xform_rollout.hip",
+                       {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U), "-DBBMPC_REW_KIND=" + std::to_string(rew_kind)},
+                       true);
 }
 
 struct UserFunction {

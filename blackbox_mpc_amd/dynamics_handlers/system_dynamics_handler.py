@@ -16,9 +16,10 @@ class SystemDynamicsHandler:
     def __init__(self, env_action_space, env_observation_space, dynamics_function=None, true_model=False,
                  is_normalized=True, log_dir=None, tf_writer=None, save_model_frequency=1, saved_model_dir=None,
                  transform_targets_func=None, inverse_transform_targets_func=None):
-        # custom target transforms (reference :128-161 applies inverse_transform_targets_func(states, raw)): honoured on the
-        # torch-callable path, where process_output runs in torch (utils/device_functions.py); the built-in and HIP-source
-        # models fuse the default delta transform and refuse a custom one (trajectory_evaluators/deterministic.py)
+        # custom target transforms (reference :128-161 applies inverse_transform_targets_func(states, dev), :314
+        # transform_targets_func(states, next_states)).  The inverse one runs in torch on the torch-callable path
+        # (utils/device_functions.py) and is inlined into the kernels of DeterministicMLP / HipDynamicsFunction when it is a
+        # HipInverseTargetTransform (trajectory_evaluators/deterministic.py); train() applies the forward one per episode
         self._transform_targets_func = transform_targets_func
         self._inverse_transform_targets_func = inverse_transform_targets_func
         self._is_true_model = bool(true_model)
@@ -107,7 +108,8 @@ class SystemDynamicsHandler:
                                     validation_split=0.2, split_mask=None):
         """:292-331.  Episodes: observations [T+1, A, S], actions [T, A, U]; rows are (s_t, a_t) -> s_{t+1} - s_t,
         episode-major, then agent, then t.  Each row goes to the training set with probability 1 - validation_split
-        (np.random.choice, :311-313); `split_mask` injects that draw (True = training row)."""
+        (np.random.choice, :311-313); `split_mask` injects that draw (True = training row).  With a transform_targets_func
+        the targets are transform(states[T,S], next_states[T,S]) per episode and agent (:314)."""
         acs_all = np.array(actions_trajectories)
         num_agents = acs_all.shape[2]
         d_in, d_out = [], []
@@ -116,7 +118,10 @@ class SystemDynamicsHandler:
             for agent in range(num_agents):
                 states = obs[:-1, agent]
                 d_in.append(np.concatenate([states, acs[:, agent]], axis=-1))
-                d_out.append(obs[1:, agent] - states)                      # default_transform_targets
+                if self._transform_targets_func is None:
+                    d_out.append(obs[1:, agent] - states)                  # default_transform_targets
+                else:
+                    d_out.append(self._transform_targets(states, obs[1:, agent]))
         d_in = np.array(d_in, dtype=np.float32).reshape(-1, self._dim_U + self._dim_S)
         d_out = np.array(d_out, dtype=np.float32).reshape(-1, self._dim_S)
         if split_mask is None:
@@ -128,6 +133,16 @@ class SystemDynamicsHandler:
         self._model_training_out = np.concatenate([self._model_training_out, d_out[split_mask]], axis=0)
         self._model_validation_in = np.concatenate([self._model_validation_in, d_in[~split_mask]], axis=0)
         self._model_validation_out = np.concatenate([self._model_validation_out, d_out[~split_mask]], axis=0)
+
+    def _transform_targets(self, states, next_states):
+        """transform_targets_func(states[T,S], next_states[T,S]) -> [T,S] on float32 arrays: any NumPy callable, or a
+        HipTargetTransform (run on the GPU)."""
+        s = np.ascontiguousarray(states, np.float32)
+        n = np.ascontiguousarray(next_states, np.float32)
+        out = np.asarray(self._transform_targets_func(s, n), np.float32)
+        if out.shape != s.shape:
+            raise ValueError("transform_targets_func returned shape %s for states of shape %s" % (out.shape, s.shape))
+        return out
 
     def _recompute_normalization(self):
         """:340-349 -- statistics of the TRAINING rows (population std)."""
@@ -155,8 +170,6 @@ class SystemDynamicsHandler:
         (the reference's callers only ever pass tf.keras.optimizers.Adam).  Keyword-only extras: `device` (default: the GPU -- training on the
         host has to be asked for explicitly with device="cpu"), and the injected random draws `split_mask`,
         `permutations` (one per epoch) / `seed` for reproducible runs."""
-        if self._transform_targets_func is not None:
-            raise NotImplementedError("training with a custom transform_targets_func is not built (default: next - state)")
         if self._is_true_model:
             raise Exception("the true model has nothing to train")
         # the reference instantiates `nn_optimizer(learning_rate=learning_rate)` (:261): a Keras optimizer CLASS (or its

@@ -107,6 +107,26 @@ class Engine:
         """HIP source defining `__device__ void bbmpc_user_dynamics(x, delta, S, U)` (include/bbmpc.h)."""
         L.check(L.lib.bbmpc_set_dynamics_source(self._h, hip_source.encode()))
 
+    def set_inverse_transform_source(self, hip_source):
+        """HIP source defining `__device__ void bbmpc_user_inverse_transform_targets(cur, dev, next, S)`, or None to clear
+        (include/bbmpc.h): replaces next = dev + state on a learned-model / user-dynamics handle."""
+        L.check(L.lib.bbmpc_set_inverse_transform_source(self._h, hip_source.encode() if hip_source else None))
+
+    def set_transform_source(self, hip_source):
+        """HIP source defining `__device__ void bbmpc_user_transform_targets(cur, next, target, S)`, or None to clear."""
+        L.check(L.lib.bbmpc_set_transform_source(self._h, hip_source.encode() if hip_source else None))
+
+    def transform_rows(self, kind, states, other):
+        """kind USER_KIND_INVERSE_TRANSFORM: (states, dev) -> next; USER_KIND_TRANSFORM: (states, next) -> targets."""
+        states, other = L.f32c(states), L.f32c(other)
+        b = states.shape[0] if states.ndim == 2 else -1
+        if states.shape != (b, self.S) or other.shape != (b, self.S):
+            raise ValueError("two [B,%d] arrays expected, got %s, %s" % (self.S, states.shape, other.shape))
+        out = np.empty((b, self.S), np.float32)
+        if b:
+            L.check(L.lib.bbmpc_transform_rows(self._h, int(kind), L.ptr(states), L.ptr(other), b, L.ptr(out)))
+        return out
+
     def set_reward_callback(self, fn):
         """fn(d_cur, d_actions, d_next, batch, d_out, hip_stream) -> status, all device pointers (include/bbmpc.h
         bbmpc_rows_callback); `fn` is an _lib.ROWS_CALLBACK the caller keeps alive; None clears it."""

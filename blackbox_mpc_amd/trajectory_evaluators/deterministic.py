@@ -44,9 +44,16 @@ def dynamics_plugin(handler):
     from ..utils import device_functions as DF
     dyn = handler._dynamics_function
     if getattr(dyn, "_bbmpc_dynamics_kind", None) is not None or isinstance(getattr(dyn, "hip_source", None), str):
-        if getattr(handler, "_inverse_transform_targets_func", None) is not None:
-            raise NotImplementedError("a custom inverse_transform_targets_func needs a dynamics_function that runs on PyTorch "
-                                      "CUDA tensors (the built-in models and HIP-source models fuse the default delta transform)")
+        inverse = getattr(handler, "_inverse_transform_targets_func", None)
+        if inverse is not None:
+            if not isinstance(inverse, DF.HipInverseTargetTransform):
+                raise NotImplementedError(
+                    "inverse_transform_targets_func %r cannot run inside the built-in / HIP-source models' kernels: give it as "
+                    "HIP source wrapped in blackbox_mpc_amd.utils.device_functions.HipInverseTargetTransform, or use a "
+                    "dynamics_function that runs on PyTorch CUDA tensors" % (inverse,))
+            if getattr(dyn, "_bbmpc_dynamics_kind", None) == L.DYN_PENDULUM:
+                raise NotImplementedError("inverse_transform_targets_func: PendulumTrueModel keeps the default next = delta + "
+                                          "state (HipInverseTargetTransform works with DeterministicMLP and HipDynamicsFunction)")
         return dyn
     if not callable(dyn):
         raise NotImplementedError(_DYNAMICS_HELP % (dyn, "it is not callable"))
@@ -79,9 +86,21 @@ def plugin_kinds(reward_function, handler):
     return dk, rk
 
 
+def configure_transform(engine, handler, dyn):
+    """Attach the handler's HipInverseTargetTransform (built-in learned model / HIP-source true model), once per engine."""
+    if getattr(dyn, "_bbmpc_dynamics_kind", None) != L.DYN_MLP and not isinstance(getattr(dyn, "hip_source", None), str):
+        return
+    inverse = getattr(handler, "_inverse_transform_targets_func", None)
+    src = getattr(inverse, "hip_source", None)
+    if getattr(engine, "_xform_source", None) is not src:
+        engine.set_inverse_transform_source(src)
+        engine._xform_source = src
+
+
 def configure_dynamics(engine, handler):
     """Upload MLP weights + normalisation statistics when the dynamics are learned; attach user dynamics."""
     dyn = dynamics_plugin(handler)
+    configure_transform(engine, handler, dyn)
     if getattr(dyn, "_bbmpc_dynamics_kind", None) == L.DYN_MLP:
         engine.set_mlp(dyn.weights, dyn.biases, dyn.activation_codes, handler.normalization_stats())
     elif engine.cfg.dynamics == L.DYN_USER and isinstance(getattr(dyn, "hip_source", None), str):

@@ -96,6 +96,45 @@ class HipDynamicsFunction(_HipFunction):
         return self._engine(dim_s, dim_u).predict_next_state(s, a) - s
 
 
+class HipInverseTargetTransform(_HipFunction):
+    """inverse_transform_targets_func given as HIP source (`bbmpc_user_inverse_transform_targets(cur, dev, next, S)`):
+    next = g(state, dev), where dev is the de-normalised model output (the raw output of a true / un-normalised model) --
+    the reference's process_output order (system_dynamics_handler.py:128-161).  Inlined into the learned-model rollout
+    kernel and the HIP-source true model's kernels; callable on NumPy batches: (states[B,S], dev[B,S]) -> next[B,S]."""
+    _bbmpc_transform_kind = L.USER_KIND_INVERSE_TRANSFORM
+
+    def _make(self, Engine, dim_s, lo, hi):
+        eng = Engine(L.OPT_NONE, L.DYN_USER, L.REW_USER, lo, hi, dim_s=dim_s, num_agents=1, planning_horizon=1)
+        eng.set_inverse_transform_source(self.hip_source)
+        return eng
+
+    def __call__(self, states, dev):
+        s, d = np.asarray(states, np.float32), np.asarray(dev, np.float32)
+        return self._engine(s.shape[1], 1).transform_rows(L.USER_KIND_INVERSE_TRANSFORM, s, d)
+
+
+class HipTargetTransform(_HipFunction):
+    """transform_targets_func given as HIP source (`bbmpc_user_transform_targets(cur, next, target, S)`): what a learned
+    model is trained to predict (system_dynamics_handler.py:314).  Callable on NumPy batches:
+    (states[T,S], next_states[T,S]) -> targets[T,S], on the GPU."""
+    _bbmpc_transform_kind = L.USER_KIND_TRANSFORM
+
+    def _make(self, Engine, dim_s, lo, hi):
+        eng = Engine(L.OPT_NONE, L.DYN_USER, L.REW_USER, lo, hi, dim_s=dim_s, num_agents=1, planning_horizon=1)
+        eng.set_transform_source(self.hip_source)
+        return eng
+
+    def __call__(self, states, next_states):
+        s, n = np.asarray(states, np.float32), np.asarray(next_states, np.float32)
+        return self._engine(s.shape[1], 1).transform_rows(L.USER_KIND_TRANSFORM, s, n)
+
+
+def check_transform_rollout(hip_source, dim_s, dim_u, reward_kind=L.REW_CHEETAH, reward_source=None):
+    """Compile only (no GPU needed) the learned-model rollout with this inverse target transform (and reward) inlined."""
+    rew = reward_source.encode() if reward_source is not None else None
+    L.check(L.lib.bbmpc_check_xform_rollout(int(reward_kind), hip_source.encode(), rew, int(dim_s), int(dim_u)))
+
+
 # ---- plain callables on torch CUDA tensors --------------------------------------------------------------------------------
 class _DeviceBlock:
     """A float32 block of the engine's device memory as an object torch.as_tensor aliases without a copy."""

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BBMPC_ABI_VERSION 2
+#define BBMPC_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------- */
 #define BBMPC_OK              0
@@ -205,6 +205,24 @@ int bbmpc_set_dynamics_callback(bbmpc_handle h, bbmpc_rows_callback fn, void* us
  * BBMPC_REW_* kinds, sources NULL for built-ins.  Needs no GPU. */
 int bbmpc_check_user_rollout(int32_t dynamics, int32_t reward, const char* dynamics_source, const char* reward_source,
                              int32_t dim_s, int32_t dim_u);
+/* Target transforms: SystemDynamicsHandler's transform_targets_func / inverse_transform_targets_func (reference
+ * dynamics_handlers/system_dynamics_handler.py:15-17, 128-161, 314) as HIP source (hiprtc, gfx950) defining per row
+ *     __device__ void bbmpc_user_inverse_transform_targets(const float* cur, const float* dev, float* next, int S);
+ *     __device__ void bbmpc_user_transform_targets(const float* cur, const float* next, float* target, int S);
+ * `dev` is the de-normalised model output (mean_t + raw * (std_t + 1e-7) for a normalised learned model, the raw
+ * output otherwise).  bbmpc_set_inverse_transform_source puts it in place of next = dev + state everywhere on a
+ * BBMPC_DYN_MLP or BBMPC_DYN_USER handle: rollouts (learned model: one MFMA kernel compiled with the transform and a
+ * user reward inlined; BBMPC_USER_STEPWISE=1: the step-wise evaluator), predict_next_state and the control step's next
+ * state.  NULL / "" clears it.  bbmpc_set_transform_source sets the forward transform, which only
+ * bbmpc_transform_rows uses (training targets).  bbmpc_transform_rows: kind 3 -> out = inverse(a = cur, b = dev),
+ * kind 4 -> out = forward(a = cur, b = next); host arrays [batch, S].  bbmpc_check_user_source takes kinds 3 / 4;
+ * bbmpc_check_xform_rollout compiles the fused learned-model rollout (reward: BBMPC_REW_*, reward_source for
+ * BBMPC_REW_USER).  Neither check needs a GPU. */
+int bbmpc_set_inverse_transform_source(bbmpc_handle h, const char* hip_source);
+int bbmpc_set_transform_source(bbmpc_handle h, const char* hip_source);
+int bbmpc_transform_rows(bbmpc_handle h, int32_t kind, const float* a, const float* b, int32_t batch, float* out);
+int bbmpc_check_xform_rollout(int32_t reward, const char* transform_source, const char* reward_source, int32_t dim_s,
+                              int32_t dim_u);
 /* DeterministicMLP.__call__(x[B, S+U], train) -> [B, S]: the raw Dense stack on already-processed inputs
  * (dynamics_functions/deterministic_mlp.py:27-51), no normalisation, no residual. */
 int bbmpc_mlp_forward(bbmpc_handle h, const float* x, int32_t batch, float* out);
