@@ -122,7 +122,7 @@ def needs_build():
 
 
 EMBED = os.path.join(CSRC, "_embed.inc")
-EMBEDDED_HEADERS = ["fastmath.hpp", "models.hpp", "kernels_mlp_xform.hpp"]
+EMBEDDED_HEADERS = ["fastmath.hpp", "models.hpp", "activations.hpp", "kernels_mlp_xform.hpp"]
 
 
 def write_embedded_sources():

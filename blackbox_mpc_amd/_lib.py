@@ -9,7 +9,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BBMPC_LIB") or os.path.join(HERE, "libbbmpc.so")   # BBMPC_LIB: a debug build (tools/)
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # enums (bbmpc.h)
 OPT_NONE, OPT_RANDOM_SEARCH, OPT_CEM, OPT_PI2, OPT_PSO, OPT_CMAES, OPT_SPSA = range(7)
@@ -17,6 +17,8 @@ DYN_PENDULUM, DYN_MLP, DYN_USER = 1, 2, 3
 REW_PENDULUM, REW_CHEETAH, REW_USER = 1, 2, 3
 USER_KIND_REWARD, USER_KIND_DYNAMICS, USER_KIND_INVERSE_TRANSFORM, USER_KIND_TRANSFORM = 1, 2, 3, 4
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
+(ACT_ELU, ACT_SELU, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_EXPONENTIAL, ACT_HARD_SIGMOID, ACT_SWISH, ACT_LEAKY_RELU,
+ ACT_RELU6) = range(4, 13)
 FIX_Q1_REWARD_ARG_ORDER = 1 << 0
 FIX_Q2_CEM_WARM_START = 1 << 1
 FIX_Q7_EXPL_NOISE_ZERO_MEAN = 1 << 2

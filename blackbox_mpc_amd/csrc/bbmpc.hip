@@ -842,11 +842,13 @@ void Engine::rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra) {
     REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED,
             "learned-model rollout with an inverse target transform: a 16-particle tile's action block plus the activation / "
             "partial-sum buffers of this network do not fit one CU's LDS (shorten the horizon or narrow the network)");
-    if (user_xform_rollout_stale || !user_xform_rollout.fn) {
+    bool act_ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) act_ext = act_ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    if (user_xform_rollout_stale || !user_xform_rollout.fn || act_ext != user_xform_rollout_ext) {
         std::vector<char> code;
         try {
             code = compile_mlp_xform_rollout(user_xform.source, cfg.reward == BBMPC_REW_USER ? user_reward.source : std::string(),
-                                             cfg.reward, S, U);
+                                             cfg.reward, S, U, act_ext);
         } catch (const std::exception& ex) {
             throw HipError(BBMPC_E_INVALID, ex.what());
         }
@@ -854,6 +856,7 @@ void Engine::rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra) {
         HIP_CHECK(hipModuleLoadData(&user_xform_rollout.module, code.data()));
         HIP_CHECK(hipModuleGetFunction(&user_xform_rollout.fn, user_xform_rollout.module, "bbmpc_mlp_xform_rollout"));
         user_xform_rollout_stale = false;
+        user_xform_rollout_ext = act_ext;
     }
     if (mode == SRC_UNIFORM || mode == SRC_TRUNC) {
         REQUIRE(ra.samples, BBMPC_E_STATE, "learned-model transform rollout: no sample buffer");

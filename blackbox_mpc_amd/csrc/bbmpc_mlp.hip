@@ -9,6 +9,9 @@ namespace bbmpc {
 
 void bbmpc_tu_mlp_upload_tnq(const float2* table) { tnq_upload(table); }
 
+static_assert(ACT_SIGMOID == BBMPC_ACT_SIGMOID && ACT_ELU == BBMPC_ACT_ELU && ACT_SWISH == BBMPC_ACT_SWISH &&
+                  ACT_RELU6 == BBMPC_ACT_RELU6, "activations.hpp and bbmpc.h disagree on the activation codes");
+
 // ------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------
@@ -36,7 +39,7 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
         mlp.half_tail[l] = (tail <= 8 && !sw.mlp_no_half_tail) ? 1 : 0;
     }
     for (int l = 0; l < n_layers; ++l) {
-        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_SIGMOID, BBMPC_E_INVALID, "unknown activation");
+        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
         REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
         mlp.act[l] = acts[l];
         const int K = dims[l], M = dims[l + 1], IT = mlp.tiles[l], OT = mlp.tiles[l + 1];
@@ -188,6 +191,10 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
     if (sw.mlp_generic) spec = 0;
     const bool single_step = per_particle_state && ra.H == 1;
     if (single_step) spec = 3;
+    // an activation after sigmoid (activations.hpp): the *_ext instantiations, which dispatch over every code; networks of
+    // none / tanh / relu / sigmoid keep the kernels they always ran
+    bool ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
     if (sw.mlp_bf16 && spec == 1 && !per_particle_state && !final_state && !record) {
         // opt-in reduced-precision mode (kernels_mlp.hpp): never selected automatically
         dim3 bgrid((ra.n_pop + MLP_TP - 1) / MLP_TP, A), bblock(mlp_nw * 64);
@@ -212,11 +219,13 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
             using KFn = void (*)(MlpRolloutArgs);
             static const KFn table[2][3] = {{k_rollout_mlp_w4<2, false>, k_rollout_mlp_w4<3, false>, k_rollout_mlp_w4<4, false>},
                                             {k_rollout_mlp_w4<2, true>, k_rollout_mlp_w4<3, true>, k_rollout_mlp_w4<4, true>}};
-            const KFn wfn = table[tanh_net ? 1 : 0][mlp.n_layers - 2];
+            static const KFn table_ext[3] = {k_rollout_mlp_w4_ext<2>, k_rollout_mlp_w4_ext<3>, k_rollout_mlp_w4_ext<4>};
+            const KFn wfn = ext ? table_ext[mlp.n_layers - 2] : table[tanh_net ? 1 : 0][mlp.n_layers - 2];
             if (wlds > 64 * 1024) ensure_max_lds((const void*)wfn, 159 * 1024);
             dim3 wgrid((ra.n_pop + W4_TP - 1) / W4_TP, per_particle_state ? 1 : A), wblock(256);
             dominant_kernel = "k_rollout_mlp_w4";
-            snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_w4<%d, %s>", mlp.n_layers, tanh_net ? "true" : "false");
+            if (ext) snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_w4_ext<%d>", mlp.n_layers);
+            else snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_w4<%d, %s>", mlp.n_layers, tanh_net ? "true" : "false");
             prof_begin();
             hipLaunchKernelGGL(wfn, wgrid, wblock, wlds, stream, q);
             HIP_CHECK(hipGetLastError());
@@ -239,7 +248,11 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
                  {k_rollout_mlp_wave<3, 1, true>, k_rollout_mlp_wave<3, 2, true>, k_rollout_mlp_wave<3, 3, true>, k_rollout_mlp_wave<3, 4, true>}}};
             bool tanh_net = mlp.act[mlp.n_layers - 1] == BBMPC_ACT_NONE;
             for (int l = 0; l + 1 < mlp.n_layers; ++l) tanh_net = tanh_net && mlp.act[l] == BBMPC_ACT_TANH;
-            const KFn wfn = table[tanh_net ? 1 : 0][mlp.n_layers - 2][mlp.tiles[1] - 1];
+            static const KFn table_ext[3][4] = {
+                {k_rollout_mlp_wave<1, 1, false, true>, k_rollout_mlp_wave<1, 2, false, true>, k_rollout_mlp_wave<1, 3, false, true>, k_rollout_mlp_wave<1, 4, false, true>},
+                {k_rollout_mlp_wave<2, 1, false, true>, k_rollout_mlp_wave<2, 2, false, true>, k_rollout_mlp_wave<2, 3, false, true>, k_rollout_mlp_wave<2, 4, false, true>},
+                {k_rollout_mlp_wave<3, 1, false, true>, k_rollout_mlp_wave<3, 2, false, true>, k_rollout_mlp_wave<3, 3, false, true>, k_rollout_mlp_wave<3, 4, false, true>}};
+            const KFn wfn = ext ? table_ext[mlp.n_layers - 2][mlp.tiles[1] - 1] : table[tanh_net ? 1 : 0][mlp.n_layers - 2][mlp.tiles[1] - 1];
             const int wht = mlp.tiles[1];
             const size_t wlds = (size_t)mlp_wave_lds_layout(ra.H, U, S, mlp.n_layers - 1, wht).total * sizeof(float);
             if (wlds <= 159 * 1024) {
@@ -254,7 +267,8 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
             }
         }
     }
-    const void* fn = spec == 3 ? (const void*)k_step_mlp : spec == 1 ? (const void*)k_rollout_mlp<1> : (spec == 2 ? (const void*)k_rollout_mlp<2> : (const void*)k_rollout_mlp<0>);
+    const void* fn = ext ? (spec == 3 ? (const void*)k_step_mlp_ext : spec == 1 ? (const void*)k_rollout_mlp_ext<1> : (spec == 2 ? (const void*)k_rollout_mlp_ext<2> : (const void*)k_rollout_mlp_ext<0>))
+                         : (spec == 3 ? (const void*)k_step_mlp : spec == 1 ? (const void*)k_rollout_mlp<1> : (spec == 2 ? (const void*)k_rollout_mlp<2> : (const void*)k_rollout_mlp<0>));
     if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
     // pair mode (two tiles per workgroup, software-pipelined) when there are more tiles than CUs can hold one each
     const long tiles_total = (long)((ra.n_pop + MLP_TP - 1) / MLP_TP) * A;
@@ -288,7 +302,9 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
                 const bool ne1 = qpairs <= 256;
                 const bool tanh_net = mlp.act[0] == BBMPC_ACT_TANH && mlp.act[1] == BBMPC_ACT_TANH && mlp.act[2] == BBMPC_ACT_NONE;
                 const bool relu_net = mlp.act[0] == BBMPC_ACT_RELU && mlp.act[1] == BBMPC_ACT_RELU && mlp.act[2] == BBMPC_ACT_NONE;
-                const KFn fn = wide     ? (tanh_net ? (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1> : k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>)
+                const KFn fn = ext      ? (wide ? (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_RTX, ACT_RTX, ACT_RTX, 1> : k_rollout_mlp_q4s<64, 7, ACT_RTX, ACT_RTX, ACT_RTX, 2>)
+                                                : (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_RTX, ACT_RTX, ACT_RTX, 1> : k_rollout_mlp_q4s<50, 7, ACT_RTX, ACT_RTX, ACT_RTX, 2>))
+                             : wide     ? (tanh_net ? (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1> : k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>)
                                                     : (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_RT, ACT_RT, ACT_RT, 1> : k_rollout_mlp_q4s<64, 7, ACT_RT, ACT_RT, ACT_RT, 2>))
                              : tanh_net ? (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1> : k_rollout_mlp_q4s<50, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>)
                              : relu_net ? (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_RELU, ACT_RELU, ACT_NONE, 1> : k_rollout_mlp_q4s<50, 7, ACT_RELU, ACT_RELU, ACT_NONE, 2>)
@@ -297,7 +313,7 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
                 dim3 qgrid((ra.n_pop + 3) / 4, A), qblock(256);
                 dominant_kernel = "k_rollout_mlp_q4s";
                 {   // the instantiation as rocprofv3 prints it (bbmpc_profile_instantiation): HG, K0G, three activations, NE
-                    const int rt = -1;
+                    const int rt = ext ? ACT_RTX : ACT_RT;
                     const int a0 = (tanh_net || (!wide && relu_net)) ? mlp.act[0] : rt, a1 = (tanh_net || (!wide && relu_net)) ? mlp.act[1] : rt,
                               a2 = (tanh_net || (!wide && relu_net)) ? mlp.act[2] : rt;
                     snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_q4s<%d, 7, %d, %d, %d, %d>", wide ? 64 : 50, a0, a1, a2, ne1 ? 1 : 2);
@@ -359,7 +375,12 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
     }
     dim3 grid((ra.n_pop + MLP_TP - 1) / MLP_TP, per_particle_state ? 1 : A), block(mlp_nw * 64);
     prof_begin();
-    if (spec == 3) hipLaunchKernelGGL(k_step_mlp, grid, block, lds, stream, q);
+    if (ext) {
+        if (spec == 3) hipLaunchKernelGGL(k_step_mlp_ext, grid, block, lds, stream, q);
+        else if (spec == 1) hipLaunchKernelGGL(k_rollout_mlp_ext<1>, grid, block, lds, stream, q);
+        else if (spec == 2) hipLaunchKernelGGL(k_rollout_mlp_ext<2>, grid, block, lds, stream, q);
+        else hipLaunchKernelGGL(k_rollout_mlp_ext<0>, grid, block, lds, stream, q);
+    } else if (spec == 3) hipLaunchKernelGGL(k_step_mlp, grid, block, lds, stream, q);
     else if (spec == 1) hipLaunchKernelGGL(k_rollout_mlp<1>, grid, block, lds, stream, q);
     else if (spec == 2) hipLaunchKernelGGL(k_rollout_mlp<2>, grid, block, lds, stream, q);
     else hipLaunchKernelGGL(k_rollout_mlp<0>, grid, block, lds, stream, q);

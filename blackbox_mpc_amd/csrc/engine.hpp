@@ -291,6 +291,7 @@ struct Engine {
     // the handle, so a handle with one takes the user-function paths; the forward one only serves bbmpc_transform_rows
     UserFunction user_xform, user_fwd_xform, user_xform_rollout;   // user_xform_rollout: kernels_mlp_xform.hpp, built lazily
     bool user_xform_rollout_stale = true;
+    bool user_xform_rollout_ext = false;     // the program was compiled for a network with an activation after sigmoid
     bool has_xform() const { return !user_xform.source.empty(); }
     void set_transform_source(int kind, const char* src);
     void transform_rows(int kind, const float* d_a, const float* d_b, int batch, float* d_out);

@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "activations.hpp"
 #include "kernels_refit.hpp"
 #include "kernels_rollout.hpp"
 #include "models.hpp"
@@ -35,7 +36,7 @@ constexpr int MLP_MAX_LAYERS = 8;      // Dense layers (the generic kernel walks
 constexpr int MLP_TP = 16;          // particles per workgroup tile
 constexpr int MLP_TMAX = 2;         // output tiles per wave per layer
 
-constexpr int ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3;
+// ACT_* codes: activations.hpp
 
 struct MlpDesc {
     int n_layers;
@@ -75,29 +76,7 @@ struct MlpRolloutArgs {
                               // an agent's row stores the state here for the later launches and the tail
 };
 
-// tanh on the hardware exp/rcp units: sign(x) * (1 - 2 / (2^{c|x|} + 1)), c = 2 log2(e): six instructions
-// (v_mul with |x|, v_exp_f32, v_add, v_rcp_f32, v_fma, v_bfi).  Absolute error <= ~2.5e-7 over the whole range (v_exp_f32 /
-// v_rcp_f32 are ~1 ulp); near zero the RELATIVE error grows (cancellation) but an activation feeds a dot product, where
-// only absolute error matters -- it is the size of one fp32 rounding of an O(1) pre-activation.  fp32-input MFMA
-// executes at the vector rate on the same datapath as VALU work (measured: step time = MFMA time + VALU time, not the
-// max), so every VALU instruction shaved off the activations is matrix time gained: this form replaced
-// exp(2|x|) -> 1 - 2r spelled as (|x|+|x|) * log2e, exp2, +1, rcp, r+r, 1-  (eight instructions).
-__device__ __forceinline__ float bb_tanhf(float x) {
-    // tanh x = 1 - 2 / (1 + e^(2x)) holds for either sign: +inf for large x -> 1 - 0, 0 for large -x -> 1 - 2; round 5 dropped the
-    // |x| / copysign pair around it (one v_bfi per value: five instructions instead of six, same absolute error bound -- the
-    // reciprocal's argument lies in [1, 2) for x < 0 and the cancellation near zero is the positive side's mirrored).
-    const float e = __builtin_amdgcn_exp2f(2.8853900817779268f * x);
-    // v_rcp_f32 (1 ulp).  __frcp_rn is the correctly rounded reciprocal, i.e. a full IEEE division: ten instructions
-    // (v_div_scale x2, v_rcp, four fmas, v_div_fmas, v_div_fixup) per activation value, on the MFMAs' issue port.
-    return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);   // NaN stays NaN (exp2(NaN) = NaN)
-}
-
-__device__ __forceinline__ float apply_act(float x, int act) {
-    if (act == ACT_TANH) return bb_tanhf(x);
-    if (act == ACT_RELU) return fmaxf(x, 0.0f);
-    if (act == ACT_SIGMOID) return 1.0f / (1.0f + expf(-x));
-    return x;
-}
+// bb_tanhf, apply_act (run-time code) and apply_act_ct (compile-time code): activations.hpp
 
 // LDS carve, in floats (all pieces multiples of 4 floats = 16 B):
 //   xs   [IT0][64][4]        normalised layer-0 input tiles
@@ -138,6 +117,7 @@ __host__ __device__ inline MlpLds mlp_lds_layout(const MlpDesc& m, int H, int U,
 #ifndef MLP_GEN_PF
 #define MLP_GEN_PF 2
 #endif
+template <bool EXT>
 __device__ __forceinline__ void mlp_layer_out_split(const MlpDesc& m, const float* wp4, int l, int in_off, int out_off, int wave,
                                                     int lane, int nw) {
     // The activation tiles are addressed as OFFSETS into the dynamic LDS array (round 6): through the `float*` the layer loop
@@ -192,8 +172,8 @@ __device__ __forceinline__ void mlp_layer_out_split(const MlpDesc& m, const floa
                     }
                 }
             }
-            acc0.x = apply_act(acc0.x, a); acc0.y = apply_act(acc0.y, a); acc0.z = apply_act(acc0.z, a); acc0.w = apply_act(acc0.w, a);
-            acc1.x = apply_act(acc1.x, a); acc1.y = apply_act(acc1.y, a); acc1.z = apply_act(acc1.z, a); acc1.w = apply_act(acc1.w, a);
+            acc0 = apply_act4<EXT>(acc0, a);
+            acc1 = apply_act4<EXT>(acc1, a);
             *reinterpret_cast<f32x4*>(out + ((size_t)ot0 * 64 + lane) * 4) = acc0;
             *reinterpret_cast<f32x4*>(out + ((size_t)ot1 * 64 + lane) * 4) = acc1;
         } else {
@@ -208,7 +188,7 @@ __device__ __forceinline__ void mlp_layer_out_split(const MlpDesc& m, const floa
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b.z, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b.w, acc, 0, 0, 0);
             }
-            acc.x = apply_act(acc.x, a); acc.y = apply_act(acc.y, a); acc.z = apply_act(acc.z, a); acc.w = apply_act(acc.w, a);
+            acc = apply_act4<EXT>(acc, a);
             *reinterpret_cast<f32x4*>(out + ((size_t)ot0 * 64 + lane) * 4) = acc;
         }
     }
@@ -333,7 +313,7 @@ __device__ __forceinline__ void mlp_fill_actions(const MlpRolloutArgs& q, int a,
     }
 }
 
-template <int SPEC>
+template <int SPEC, bool EXT = false>
 __device__ __forceinline__ void rollout_mlp_body(const MlpRolloutArgs& q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const RolloutArgs& p = q.r;
@@ -429,7 +409,7 @@ __device__ __forceinline__ void rollout_mlp_body(const MlpRolloutArgs& q) {
             int in_off = lay.xs;
             for (int l = 0; l < L - 1; ++l) {
                 const int out_off = (l & 1) ? lay.actB : lay.actA;
-                mlp_layer_out_split(m, q.wp4[l], l, in_off, out_off, wave, lane, nw);
+                mlp_layer_out_split<EXT>(m, q.wp4[l], l, in_off, out_off, wave, lane, nw);
                 __syncthreads();
                 in_off = out_off;
             }
@@ -447,8 +427,7 @@ __device__ __forceinline__ void rollout_mlp_body(const MlpRolloutArgs& q) {
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wr_in[it * 4 + 3], b.w, acc, 0, 0, 0);
                 }
             }
-            acc.x = apply_act(acc.x, m.act[0]); acc.y = apply_act(acc.y, m.act[0]);
-            acc.z = apply_act(acc.z, m.act[0]); acc.w = apply_act(acc.w, m.act[0]);
+            acc = apply_act4<EXT>(acc, m.act[0]);
 #pragma unroll
             for (int h = 1; h < NH; ++h) {
                 float* out = actbuf[(h - 1) & 1];
@@ -465,8 +444,7 @@ __device__ __forceinline__ void rollout_mlp_body(const MlpRolloutArgs& q) {
                         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wr_hid[((h - 1) * HTM + it) * 4 + 3], b.w, acc, 0, 0, 0);
                     }
                 }
-                acc.x = apply_act(acc.x, m.act[h]); acc.y = apply_act(acc.y, m.act[h]);
-                acc.z = apply_act(acc.z, m.act[h]); acc.w = apply_act(acc.w, m.act[h]);
+                acc = apply_act4<EXT>(acc, m.act[h]);
             }
             // last layer, K split: my own last-hidden tile (still in `acc`) times my slab of W_last
 #pragma unroll
@@ -493,7 +471,7 @@ __device__ __forceinline__ void rollout_mlp_body(const MlpRolloutArgs& q) {
                 float acc = lbias[f];
 #pragma unroll 4
                 for (int w = 0; w < nwp; ++w) acc = acc + pp0[(size_t)w * OTl * 256];
-                acc = apply_act(acc, m.act[L - 1]);
+                acc = apply_act_rt<EXT>(acc, m.act[L - 1]);
                 const float dev = normd ? tmean[f] + acc * tstd[f] : acc;       // system_dynamics_handler.py:152-155
                 const float ns = dev + cur[pp * Sp + f];                        // transforms.py:34
                 nxt[pp * Sp + f] = ns;
@@ -550,6 +528,14 @@ __global__ void k_rollout_mlp(MlpRolloutArgs q) {
 static __global__ void k_step_mlp(MlpRolloutArgs q) {
     rollout_mlp_body<0>(q);
 }
+// the two above for networks with an activation after sigmoid (activations.hpp: the run-time dispatch over every code)
+template <int SPEC>
+__global__ void k_rollout_mlp_ext(MlpRolloutArgs q) {
+    rollout_mlp_body<SPEC, true>(q);
+}
+static __global__ void k_step_mlp_ext(MlpRolloutArgs q) {
+    rollout_mlp_body<0, true>(q);
+}
 
 // ---- small helpers for the OptimizerBase.__call__ tail on the learned-dynamics path ----------------
 
@@ -591,14 +577,6 @@ static __global__ void k_pack_record(int A, int U, int S, const float* action, c
 // (same three barriers per step, but for two tiles), weights are shared in VGPRs.  Tile counts are
 // compile-time so that each interval is straight-line code the scheduler can interleave.
 // Restricted to 2 hidden layers of HT tiles each, S+U <= 32, S <= 32 (BASELINE configs 4-5: HT = 13).
-template <int ACT>
-__device__ __forceinline__ float apply_act_ct(float x) {
-    if constexpr (ACT == ACT_TANH) return bb_tanhf(x);
-    else if constexpr (ACT == ACT_RELU) return fmaxf(x, 0.0f);
-    else if constexpr (ACT == ACT_SIGMOID) return 1.0f / (1.0f + expf(-x));
-    else return x;
-}
-
 // Two-tile mode runs HT - 1 waves (12 for 200 hidden units: three per SIMD, 168 registers each -- fourteen waves had
 // 128 and spilled).  Waves land on SIMD (wave & 3).  Feature tile HT-1 (the 13th, half-empty one) has no wave of its
 // own: its layer-1 job is one more dependent chain of 50 MFMAs, and whichever SIMD carries it whole runs 4 jobs against
@@ -1778,8 +1756,7 @@ __global__ void k_rollout_mlp_bf16(MlpRolloutArgs q) {
 #pragma unroll
         for (int it = 0; it < IT0M; ++it)
             if (it < IT0) acc = bf_mma<NPROD>(w_in[it], bf_from_u4(xs[(size_t)it * 64 + lane]), acc);
-        acc.x = apply_act(acc.x, m.act[0]); acc.y = apply_act(acc.y, m.act[0]);
-        acc.z = apply_act(acc.z, m.act[0]); acc.w = apply_act(acc.w, m.act[0]);
+        acc = apply_act4<true>(acc, m.act[0]);
         hbuf[(size_t)wave * 64 + lane] = bf_to_u4(bf_split4(acc));               // all-gather through LDS
         __syncthreads();
         // ---- layer 1
@@ -1787,8 +1764,7 @@ __global__ void k_rollout_mlp_bf16(MlpRolloutArgs q) {
 #pragma unroll
         for (int it = 0; it < HTM; ++it)
             if (it < HT) acc = bf_mma<NPROD>(w_hid[it], bf_from_u4(hbuf[(size_t)it * 64 + lane]), acc);
-        acc.x = apply_act(acc.x, m.act[1]); acc.y = apply_act(acc.y, m.act[1]);
-        acc.z = apply_act(acc.z, m.act[1]); acc.w = apply_act(acc.w, m.act[1]);
+        acc = apply_act4<true>(acc, m.act[1]);
         // ---- last layer, K split: my own hidden tile (converted in registers) times my slab of W_last
         {
             const BfSplit hb = bf_split4(acc);

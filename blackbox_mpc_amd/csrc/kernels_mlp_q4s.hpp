@@ -163,9 +163,11 @@ __device__ __forceinline__ void mfma4_a_round4_first(f32x4& c0, f32x4& c1, f32x4
 }
 
 constexpr int ACT_RT = -1;                                // activation taken from MlpDesc::act at run time (a scalar branch per use)
+constexpr int ACT_RTX = -2;                               // the same, for networks with a code after sigmoid (activations.hpp)
 template <int ACT>
 __device__ __forceinline__ float apply_act_q4s(float x, int rt) {
-    if constexpr (ACT == ACT_RT) return apply_act(x, rt);
+    if constexpr (ACT == ACT_RT) return apply_act_base(x, rt);
+    else if constexpr (ACT == ACT_RTX) return apply_act(x, rt);
     else return apply_act_ct<ACT>(x);
 }
 

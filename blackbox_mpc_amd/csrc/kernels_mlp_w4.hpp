@@ -72,8 +72,9 @@ __host__ __device__ inline MlpW4Lds mlp_w4_lds_layout(int H, int U, int S) {
 // NL Dense layers (2..4) of at most 32 inputs / outputs each (the first: dim_S <= 20 state + dim_U <= 8 action inputs).
 // TANH: every hidden activation is tanh and the output layer is linear (the tutorials' networks): no run-time dispatch.
 // grid (ceil(n_pop / 16), A or 1), block 256.
-template <int NL, bool TANH>
-__global__ __launch_bounds__(256) void k_rollout_mlp_w4(MlpRolloutArgs q) {
+// EXT: some activation is one of the codes after sigmoid (activations.hpp apply_act_rt).
+template <int NL, bool TANH, bool EXT>
+__device__ __forceinline__ void rollout_mlp_w4_body(MlpRolloutArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const RolloutArgs& p = q.r;
     const MlpDesc& m = q.m;
@@ -203,11 +204,11 @@ __global__ __launch_bounds__(256) void k_rollout_mlp_w4(MlpRolloutArgs q) {
             if (l + 1 < NL) {
                 const int act = TANH ? ACT_TANH : m.act[l];
                 if (TANH) { v0 = bb_tanhf(s0); v1 = bb_tanhf(s1); }
-                else { v0 = apply_act(s0, act); v1 = apply_act(s1, act); }
+                else { v0 = apply_act_rt<EXT>(s0, act); v1 = apply_act_rt<EXT>(s1, act); }
             } else {
                 // ---- epilogue on my two slots: last activation, de-normalise, residual (system_dynamics_handler.py:152-155,
                 //      transforms.py:34), the ring, the next step's input (process_input)
-                if (!TANH) { s0 = apply_act(s0, m.act[NL - 1]); s1 = apply_act(s1, m.act[NL - 1]); }
+                if (!TANH) { s0 = apply_act_rt<EXT>(s0, m.act[NL - 1]); s1 = apply_act_rt<EXT>(s1, m.act[NL - 1]); }
                 curA = sa ? (tmA + s0 * tsA) + curA : 0.0f;
                 curB = sb ? (tmB + s1 * tsB) + curB : 0.0f;
                 if (sa) ringA[(t + 1) * W4_TP * Sp] = curA;
@@ -264,6 +265,15 @@ __global__ __launch_bounds__(256) void k_rollout_mlp_w4(MlpRolloutArgs q) {
                H, dbg_t[1] - dbg_t[0], dbg_t[2] - dbg_t[1], dbg_t[3] - dbg_t[2], dbg_t[4] - dbg_t[3], dbg_t[5] - dbg_t[4], dbg_t[6] - dbg_t[5]);
 #endif
 #undef W4_MARK
+}
+
+template <int NL, bool TANH>
+__global__ __launch_bounds__(256) void k_rollout_mlp_w4(MlpRolloutArgs q) {
+    rollout_mlp_w4_body<NL, TANH, false>(q);
+}
+template <int NL>
+__global__ __launch_bounds__(256) void k_rollout_mlp_w4_ext(MlpRolloutArgs q) {
+    rollout_mlp_w4_body<NL, false, true>(q);
 }
 
 }  // namespace bbmpc

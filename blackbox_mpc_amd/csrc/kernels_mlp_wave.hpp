@@ -50,9 +50,10 @@ __host__ __device__ inline MlpWaveLds mlp_wave_lds_layout(int H, int U, int S, i
     return l;
 }
 
+template <bool EXT>
 __device__ __forceinline__ f32x4 act4(f32x4 v, int a) {
     if (a == ACT_TANH) { v.x = bb_tanhf(v.x); v.y = bb_tanhf(v.y); v.z = bb_tanhf(v.z); v.w = bb_tanhf(v.w); }
-    else if (a != ACT_NONE) { v.x = apply_act(v.x, a); v.y = apply_act(v.y, a); v.z = apply_act(v.z, a); v.w = apply_act(v.w, a); }
+    else if (a != ACT_NONE) v = apply_act4<EXT>(v, a);
     return v;
 }
 
@@ -61,7 +62,8 @@ __host__ __device__ constexpr int mlp_wave_waves(int HT) { return HT + 1; }
 
 // NH hidden layers of exactly HT 16-feature tiles each; S+U <= 32, S <= 32.  grid (ceil(n_pop/16), A), block 64*waves.
 // TANH: every hidden activation is tanh and the output layer is linear (the tutorials' networks): no run-time dispatch
-template <int NH, int HT, bool TANH>
+// EXT: some activation is one of the codes after sigmoid (activations.hpp apply_act4; the dispatcher sets it).
+template <int NH, int HT, bool TANH, bool EXT = false>
 __global__ __launch_bounds__(64 * mlp_wave_waves(HT)) void k_rollout_mlp_wave(MlpRolloutArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const RolloutArgs& p = q.r;
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(64 * mlp_wave_waves(HT)) void k_rollout_mlp_wave(Ml
 #pragma unroll
             for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w_in[1][s], xin[1][s], acc, 0, 0, 0);
         }
-        acc = act4(acc, TANH ? ACT_TANH : m.act[0]);
+        acc = act4<EXT>(acc, TANH ? ACT_TANH : m.act[0]);
         // ---- hidden -> hidden: all-gather the HT tiles through LDS (a buffer per layer: reused a whole step later)
 #pragma unroll
         for (int h = 1; h < NH; ++h) {
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(64 * mlp_wave_waves(HT)) void k_rollout_mlp_wave(Ml
 #pragma unroll
                 for (int s = 0; s < 4; ++s) nx = __builtin_amdgcn_mfma_f32_16x16x4f32(w_hid[h - 1][it][s], b[s], nx, 0, 0, 0);
             }
-            acc = act4(nx, TANH ? ACT_TANH : m.act[h]);
+            acc = act4<EXT>(nx, TANH ? ACT_TANH : m.act[h]);
         }
         // ---- last layer, K split: my last-hidden tile (still in `acc`) times my slab of W_last
         f32x4 o[OTLM];
@@ -258,7 +260,7 @@ __global__ __launch_bounds__(64 * mlp_wave_waves(HT)) void k_rollout_mlp_wave(Ml
 #pragma unroll
         for (int it = 0; it < OTLM; ++it) {
             if (it < OTL) {
-                const f32x4 ov = act4(o[it], TANH ? ACT_NONE : m.act[L - 1]);
+                const f32x4 ov = act4<EXT>(o[it], TANH ? ACT_NONE : m.act[L - 1]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int f = 16 * it + 4 * g + r;

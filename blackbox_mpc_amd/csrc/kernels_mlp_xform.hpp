@@ -19,11 +19,12 @@
 // Candidates come from the caller's sequences (SRC_REF) or from the sample buffer the engine filled (SRC_BUF); clip and
 // penalty as bbmpc_user_rollout (rtc.hpp) applies them.
 //
-// Only leaf headers that hiprtc receives (models.hpp, fastmath.hpp) are included: the host side includes this file for
+// Only leaf headers that hiprtc receives (activations.hpp, models.hpp, fastmath.hpp) are included: the host side includes this file for
 // XformArgs and the LDS layout; the kernel itself is compiled only where BBMPC_XFORM_KERNEL is defined (hiprtc).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "activations.hpp"   // apply_act: the generic kernel's activations, the same text
 #include "models.hpp"
 
 namespace bbmpc {
@@ -88,19 +89,14 @@ __host__ __device__ inline XformLds xform_lds_layout(const int* tiles, int n_lay
 #ifdef BBMPC_XFORM_KERNEL
 typedef float xf_f32x4 __attribute__((ext_vector_type(4)));
 
+// BBMPC_ACT_EXT=1: the network has an activation after sigmoid (activations.hpp); the program is compiled for the network
+#ifndef BBMPC_ACT_EXT
+#define BBMPC_ACT_EXT 1
+#endif
+constexpr bool XF_EXT = BBMPC_ACT_EXT != 0;
+
 // the dynamic LDS array, declared once at namespace scope (the kernel has C linkage, the helpers do not)
 extern __shared__ __attribute__((aligned(16))) float xf_smem[];
-
-// the generic kernel's activations, instruction for instruction (kernels_mlp.hpp bb_tanhf / apply_act)
-__device__ __forceinline__ float xf_act(float x, int act) {
-    if (act == 1) {
-        const float e = __builtin_amdgcn_exp2f(2.8853900817779268f * x);
-        return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
-    }
-    if (act == 2) return fmaxf(x, 0.0f);
-    if (act == 3) return 1.0f / (1.0f + expf(-x));
-    return x;
-}
 
 // feature f of particle p inside a tile array [T][64][4]
 __device__ __forceinline__ int xf_tile_addr(int f, int p) {
@@ -126,7 +122,7 @@ __device__ __forceinline__ void xf_layer_out_split(const XformArgs& q, int l, in
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, b.z, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, b.w, acc, 0, 0, 0);
         }
-        acc.x = xf_act(acc.x, a); acc.y = xf_act(acc.y, a); acc.z = xf_act(acc.z, a); acc.w = xf_act(acc.w, a);
+        acc = apply_act4<XF_EXT>(acc, a);
         *reinterpret_cast<xf_f32x4*>(out + ((size_t)ot * 64 + lane) * 4) = acc;
     }
 }
@@ -243,7 +239,7 @@ extern "C" __global__ void bbmpc_mlp_xform_rollout(XformArgs q) {
             const float* p0 = part + ((size_t)ot * 64 + ln) * 4 + rg;
             float acc = lbias[f];
             for (int w = 0; w < nwp; ++w) acc = acc + p0[(size_t)w * OTl * 256];
-            acc = xf_act(acc, q.act[L - 1]);
+            acc = apply_act_rt<XF_EXT>(acc, q.act[L - 1]);
             devb[pp * Sp + f] = normd ? tmean[f] + acc * tstd[f] : acc;       // system_dynamics_handler.py:152-155
         }
         __syncthreads();

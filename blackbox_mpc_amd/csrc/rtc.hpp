@@ -181,7 +181,7 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
     return s;
 }
 
-#include "_embed.inc"      // k_embed_fastmath, k_embed_models, k_embed_kernels_mlp_xform: headers as text (generated by _build.py)
+#include "_embed.inc"      // k_embed_fastmath, k_embed_models, k_embed_activations, k_embed_kernels_mlp_xform: headers as text (generated by _build.py)
 
 // The FUSED form: one lane per candidate trajectory, the whole H-step recurrence in registers, with the user's
 // function(s) inlined next to the built-in model / rewards (the engine's own models.hpp, compiled from the same text
@@ -267,9 +267,9 @@ inline std::vector<char> compile_rtc(const std::string& src, const char* name, c
                                      bool with_engine_headers) {
     const Hiprtc& r = Hiprtc::get();
     Hiprtc::Program prog = nullptr;
-    const char* hdr_text[] = {k_embed_fastmath, k_embed_models, k_embed_kernels_mlp_xform};
-    const char* hdr_name[] = {"fastmath.hpp", "models.hpp", "kernels_mlp_xform.hpp"};
-    int rc = r.CreateProgram(&prog, src.c_str(), name, with_engine_headers ? 3 : 0, with_engine_headers ? hdr_text : nullptr,
+    const char* hdr_text[] = {k_embed_fastmath, k_embed_models, k_embed_activations, k_embed_kernels_mlp_xform};
+    const char* hdr_name[] = {"fastmath.hpp", "models.hpp", "activations.hpp", "kernels_mlp_xform.hpp"};
+    int rc = r.CreateProgram(&prog, src.c_str(), name, with_engine_headers ? 4 : 0, with_engine_headers ? hdr_text : nullptr,
                              with_engine_headers ? hdr_name : nullptr);
     if (rc != 0) throw std::runtime_error(std::string("hiprtcCreateProgram: ") + r.GetErrorString(rc));
     // one rounding per source operation, as everywhere in the engine (and as the reference's TF ops round)
@@ -323,9 +323,12 @@ inline std::string mlp_xform_rollout_source(const std::string& xform_src, const 
     return s;
 }
 
-inline std::vector<char> compile_mlp_xform_rollout(const std::string& xform_src, const std::string& reward_src, int rew_kind, int S, int U) {
+// act_ext: the network has an activation after sigmoid (activations.hpp), so the program dispatches over every code
+inline std::vector<char> compile_mlp_xform_rollout(const std::string& xform_src, const std::string& reward_src, int rew_kind, int S, int U,
+                                                   bool act_ext = true) {
     return compile_rtc(mlp_xform_rollout_source(xform_src, reward_src), "bbmpc_mlp_xform_rollout.hip",
-                       {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U), "-DBBMPC_REW_KIND=" + std::to_string(rew_kind)},
+                       {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U), "-DBBMPC_REW_KIND=" + std::to_string(rew_kind),
+                        std::string("-DBBMPC_ACT_EXT=") + (act_ext ? "1" : "0")},
                        true);
 }
 

@@ -15,24 +15,71 @@ import numpy as np
 from .. import _lib as L
 
 
+_SELU_ALPHA, _SELU_SCALE = 1.6732632423543772, 1.0507009873554805
+
+
 def _act(code, x):
     import torch
+    F = torch.nn.functional
     if code == L.ACT_TANH:
         return torch.tanh(x)
     if code == L.ACT_RELU:
         return torch.relu(x)
     if code == L.ACT_SIGMOID:
         return torch.sigmoid(x)
+    if code == L.ACT_ELU:
+        return F.elu(x)
+    if code == L.ACT_SELU:
+        return F.selu(x)
+    if code == L.ACT_SOFTPLUS:
+        return F.softplus(x)
+    if code == L.ACT_SOFTSIGN:
+        return F.softsign(x)
+    if code == L.ACT_EXPONENTIAL:
+        return torch.exp(x)
+    if code == L.ACT_HARD_SIGMOID:
+        return torch.clamp(0.2 * x + 0.5, 0.0, 1.0)           # Keras 2.0's, not torch's hardsigmoid
+    if code == L.ACT_SWISH:
+        return F.silu(x)
+    if code == L.ACT_LEAKY_RELU:
+        return F.leaky_relu(x, 0.2)                            # tf.nn.leaky_relu's slope
+    if code == L.ACT_RELU6:
+        return F.relu6(x)
     return x
 
 
-def _act_grad(code, y, g):
+# activations whose derivative is not a function of the layer output alone: the forward pass keeps their pre-activation
+_NEEDS_PRE = (L.ACT_SWISH,)
+
+
+def _act_grad(code, y, g, z=None):
+    """g * f'(x) rebuilt from the layer output y = f(x) (z = x, only for the codes in _NEEDS_PRE)."""
+    import torch
     if code == L.ACT_TANH:
         return g * (1.0 - y * y)
     if code == L.ACT_RELU:
         return g * (y > 0).to(g.dtype)
     if code == L.ACT_SIGMOID:
         return g * (y * (1.0 - y))
+    if code == L.ACT_ELU:                                      # x > 0 <=> y > 0; e^x = y + 1
+        return g * torch.where(y > 0, torch.ones_like(y), y + 1.0)
+    if code == L.ACT_SELU:                                     # lambda alpha e^x = y + lambda alpha
+        return g * torch.where(y > 0, torch.full_like(y, _SELU_SCALE), y + _SELU_SCALE * _SELU_ALPHA)
+    if code == L.ACT_SOFTPLUS:                                 # sigma(x) = 1 - e^-y
+        return g * -torch.expm1(-y)
+    if code == L.ACT_SOFTSIGN:                                 # 1 / (1 + |x|)^2 = (1 - |y|)^2
+        return g * (1.0 - y.abs()).square()
+    if code == L.ACT_EXPONENTIAL:
+        return g * y
+    if code == L.ACT_HARD_SIGMOID:
+        return g * (0.2 * ((y > 0) & (y < 1)).to(g.dtype))
+    if code == L.ACT_SWISH:                                    # sigma(x) (1 + x (1 - sigma(x))) = s + y (1 - s)
+        s = torch.sigmoid(z)
+        return g * (s + y * (1.0 - s))
+    if code == L.ACT_LEAKY_RELU:
+        return g * torch.where(y > 0, torch.ones_like(y), torch.full_like(y, 0.2))
+    if code == L.ACT_RELU6:
+        return g * ((y > 0) & (y < 6)).to(g.dtype)
     return g
 
 
@@ -63,22 +110,28 @@ class DenseTrainer:
         self._graph = None
 
     # -- one step on (x, y): forward, MSE, backward, Keras-Adam ---------------------------------------------------
-    def forward(self, x):
+    def forward(self, x, pre=None):
+        """The layer outputs [x, y1, ..., yL]; `pre`, when given, collects the pre-activations the backward pass needs
+        (None for the layers whose derivative follows from y)."""
         ys = [x]
         for w, b, a in zip(self.w, self.b, self.acts):
-            ys.append(_act(a, self.torch.addmm(b, ys[-1], w)))
+            z = self.torch.addmm(b, ys[-1], w)
+            if pre is not None:
+                pre.append(z if a in _NEEDS_PRE else None)
+            ys.append(_act(a, z))
         return ys
 
     def _step(self, x, y):
         torch = self.torch
-        ys = self.forward(x)
+        zs = []
+        ys = self.forward(x, zs)
         diff = ys[-1] - y
         self.loss_acc += (diff * diff).mean()
         g = diff * (2.0 / diff.numel())
         n = len(self.w)
         grads = [None] * (2 * n)
         for l in reversed(range(n)):
-            g = _act_grad(self.acts[l], ys[l + 1], g)
+            g = _act_grad(self.acts[l], ys[l + 1], g, zs[l])
             grads[l] = ys[l].t() @ g
             grads[n + l] = g.sum(dim=0)
             if l:

@@ -9,16 +9,36 @@ import numpy as np
 from .. import _lib as L
 
 _ACT = {None: L.ACT_NONE, "linear": L.ACT_NONE, "none": L.ACT_NONE, "tanh": L.ACT_TANH, "relu": L.ACT_RELU,
-        "sigmoid": L.ACT_SIGMOID}
+        "sigmoid": L.ACT_SIGMOID, "elu": L.ACT_ELU, "selu": L.ACT_SELU, "softplus": L.ACT_SOFTPLUS,
+        "softsign": L.ACT_SOFTSIGN, "exponential": L.ACT_EXPONENTIAL, "exp": L.ACT_EXPONENTIAL,
+        "hard_sigmoid": L.ACT_HARD_SIGMOID, "swish": L.ACT_SWISH, "silu": L.ACT_SWISH, "leaky_relu": L.ACT_LEAKY_RELU,
+        "relu6": L.ACT_RELU6}
+# code -> the name save() / load() and messages use
+_ACT_NAME = {L.ACT_NONE: None, L.ACT_TANH: "tanh", L.ACT_RELU: "relu", L.ACT_SIGMOID: "sigmoid", L.ACT_ELU: "elu",
+             L.ACT_SELU: "selu", L.ACT_SOFTPLUS: "softplus", L.ACT_SOFTSIGN: "softsign",
+             L.ACT_EXPONENTIAL: "exponential", L.ACT_HARD_SIGMOID: "hard_sigmoid", L.ACT_SWISH: "swish",
+             L.ACT_LEAKY_RELU: "leaky_relu", L.ACT_RELU6: "relu6"}
+_SUPPORTED = ("tanh, relu, sigmoid, elu, selu, softplus, softsign, exponential, hard_sigmoid (Keras: clip(0.2 x + 0.5, "
+              "0, 1)), swish / silu, leaky_relu (slope 0.2), relu6, None / linear")
 
 
 def _act_code(a):
+    """The BBMPC_ACT_* code of one entry of `activation_functions`: a Keras activation name (as Dense(activation=...)
+    takes it in the reference) or an elementwise callable (tf.nn.*, torch.*, np.*), resolved by its __name__."""
     if a is None or isinstance(a, str):
         key = a.lower() if isinstance(a, str) else None
     else:  # a callable such as np.tanh / torch.tanh / tf.math.tanh: resolve by name
         key = getattr(a, "__name__", str(a)).lower()
+        if key == "leaky_relu" and str(getattr(a, "__module__", "") or "").startswith("torch"):
+            raise ValueError("unsupported activation %r: torch's leaky_relu defaults to slope 0.01, tf.nn.leaky_relu (the "
+                             "supported one, also the string 'leaky_relu') to 0.2 (supported: %s)" % (a, _SUPPORTED))
+    if key == "softmax":
+        raise ValueError("unsupported activation %r: softmax is not elementwise (supported: %s)" % (a, _SUPPORTED))
+    if key == "hardsigmoid":
+        raise ValueError("unsupported activation %r: torch's hardsigmoid is x / 6 + 0.5, not Keras' hard_sigmoid "
+                         "clip(0.2 x + 0.5, 0, 1) (supported: %s)" % (a, _SUPPORTED))
     if key not in _ACT:
-        raise ValueError("unsupported activation %r (supported: tanh, relu, sigmoid, None)" % (a,))
+        raise ValueError("unsupported activation %r (supported: %s)" % (a, _SUPPORTED))
     return _ACT[key]
 
 
@@ -60,8 +80,7 @@ class DeterministicMLP:
     @classmethod
     def load(cls, path):
         z = np.load(path)
-        inv = {v: k for k, v in _ACT.items() if k in (None, "tanh", "relu", "sigmoid")}
-        m = cls(list(z["layers"]), [inv[int(c)] for c in z["activations"]])
+        m = cls(list(z["layers"]), [_ACT_NAME[int(c)] for c in z["activations"]])
         n = int(z["n_layers"])
         m.set_weights([z["W%d" % i] for i in range(n)], [z["b%d" % i] for i in range(n)])
         return m

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BBMPC_ABI_VERSION 3
+#define BBMPC_ABI_VERSION 4
 
 /* ---- status codes ------------------------------------------------------- */
 #define BBMPC_OK              0
@@ -61,11 +61,20 @@ extern "C" {
 #define BBMPC_REW_CHEETAH  2
 #define BBMPC_REW_USER     3   /* caller-supplied: HIP source (bbmpc_set_reward_source) or a device-memory callback */
 
-/* Dense activations (tutorials use tf.math.tanh and None) */
-#define BBMPC_ACT_NONE    0
-#define BBMPC_ACT_TANH    1
-#define BBMPC_ACT_RELU    2
-#define BBMPC_ACT_SIGMOID 3
+/* Dense activations (tutorials use tf.math.tanh and None); the TF 2.0 definitions, fixed slopes and constants */
+#define BBMPC_ACT_NONE         0
+#define BBMPC_ACT_TANH         1
+#define BBMPC_ACT_RELU         2
+#define BBMPC_ACT_SIGMOID      3
+#define BBMPC_ACT_ELU          4   /* x > 0 ? x : e^x - 1 (alpha 1) */
+#define BBMPC_ACT_SELU         5   /* lambda * (x > 0 ? x : alpha (e^x - 1)) */
+#define BBMPC_ACT_SOFTPLUS     6   /* log(1 + e^x) */
+#define BBMPC_ACT_SOFTSIGN     7   /* x / (1 + |x|) */
+#define BBMPC_ACT_EXPONENTIAL  8   /* e^x */
+#define BBMPC_ACT_HARD_SIGMOID 9   /* clip(0.2 x + 0.5, 0, 1) (Keras 2.0) */
+#define BBMPC_ACT_SWISH        10  /* x * sigmoid(x) (= silu) */
+#define BBMPC_ACT_LEAKY_RELU   11  /* x >= 0 ? x : 0.2 x (tf.nn.leaky_relu's default slope) */
+#define BBMPC_ACT_RELU6        12  /* min(max(x, 0), 6) */
 
 /* quirk switches; a set bit OPTS OUT of the reference's as-executed behaviour
  * (SURVEY.md section 8 quirk register).  Default 0 = bug-compatible. */
