@@ -16,6 +16,7 @@ OPT_NONE, OPT_RANDOM_SEARCH, OPT_CEM, OPT_PI2, OPT_PSO, OPT_CMAES, OPT_SPSA = ra
 DYN_PENDULUM, DYN_MLP, DYN_USER = 1, 2, 3
 REW_PENDULUM, REW_CHEETAH, REW_USER = 1, 2, 3
 USER_KIND_REWARD, USER_KIND_DYNAMICS, USER_KIND_INVERSE_TRANSFORM, USER_KIND_TRANSFORM = 1, 2, 3, 4
+MAX_USER_PARAMS = 4096                                  # BBMPC_MAX_USER_PARAMS: runtime parameters per agent
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
 (ACT_ELU, ACT_SELU, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_EXPONENTIAL, ACT_HARD_SIGMOID, ACT_SWISH, ACT_LEAKY_RELU,
  ACT_RELU6) = range(4, 13)
@@ -74,6 +75,8 @@ SYMBOLS = [
     "bbmpc_set_reward_callback", "bbmpc_set_dynamics_callback",
     "bbmpc_process_input", "bbmpc_process_output", "bbmpc_check_user_rollout",
     "bbmpc_set_inverse_transform_source", "bbmpc_set_transform_source", "bbmpc_transform_rows", "bbmpc_check_xform_rollout",
+    "bbmpc_set_reward_source_params", "bbmpc_set_dynamics_source_params", "bbmpc_set_user_params", "bbmpc_compile_stats",
+    "bbmpc_check_user_params",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -148,6 +151,11 @@ def _load():
     lib.bbmpc_set_transform_source.argtypes = [vp, ctypes.c_char_p]
     lib.bbmpc_transform_rows.argtypes = [vp, i32, vp, vp, i32, vp]
     lib.bbmpc_check_xform_rollout.argtypes = [i32, ctypes.c_char_p, ctypes.c_char_p, i32, i32]
+    lib.bbmpc_set_reward_source_params.argtypes = [vp, ctypes.c_char_p, i32]
+    lib.bbmpc_set_dynamics_source_params.argtypes = [vp, ctypes.c_char_p, i32]
+    lib.bbmpc_set_user_params.argtypes = [vp, i32, vp, i64]
+    lib.bbmpc_compile_stats.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.bbmpc_check_user_params.argtypes = [ctypes.c_char_p, i32, ctypes.c_char_p, i32, i32, i32]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

@@ -530,13 +530,14 @@ void Engine::get_profile(double* ms, int64_t* launches) {
 // ------------------------------------------------------------------------------------------------
 // user device functions (rtc.hpp) + the step-wise evaluator (kernels_user.hpp)
 // ------------------------------------------------------------------------------------------------
-void Engine::set_user_source(int kind, const char* src) {
+void Engine::set_user_source(int kind, const char* src, int nparams) {
     REQUIRE(src && *src, BBMPC_E_INVALID, "empty HIP source");
     if (kind == USER_KIND_REWARD) REQUIRE(cfg.reward == BBMPC_REW_USER, BBMPC_E_STATE, "handle was not created with BBMPC_REW_USER");
     else REQUIRE(cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_STATE, "handle was not created with BBMPC_DYN_USER");
     std::vector<char> code;
     try {
-        code = compile_user_program(src, kind, S, U, kind == USER_KIND_DYNAMICS ? user_xform.source : std::string());
+        ++rtc_compiles;
+        code = compile_user_program(src, kind, S, U, kind == USER_KIND_DYNAMICS ? user_xform.source : std::string(), nparams);
     } catch (const std::exception& ex) {
         throw HipError(BBMPC_E_INVALID, ex.what());
     }
@@ -547,6 +548,8 @@ void Engine::set_user_source(int kind, const char* src) {
     HIP_CHECK(hipModuleGetFunction(&f.fn, f.module, kind == USER_KIND_REWARD ? "bbmpc_user_reward_rows" : "bbmpc_user_dynamics_rows"));
     if (kind == USER_KIND_REWARD) HIP_CHECK(hipModuleGetFunction(&f.fn_traj, f.module, "bbmpc_user_reward_traj"));
     f.source = src;
+    f.nparams = nparams;
+    (kind == USER_KIND_REWARD ? rew_params : dyn_params).set = false;       // a new source starts without parameters
     f.cb = nullptr; f.cb_user = nullptr;
     user_rollout_stale = true;
     user_xform_rollout_stale = true;
@@ -559,11 +562,58 @@ void Engine::set_user_callback(int kind, bbmpc_rows_callback fn, void* user) {
             "a dynamics callback returns absolute next states: apply the inverse target transform inside it (clear the transform first)");
     HIP_CHECK(hipStreamSynchronize(stream));
     UserFunction& f = kind == USER_KIND_REWARD ? user_reward : user_dynamics;
-    if (fn) { f.release(); f.source.clear(); }
+    if (fn) { f.release(); f.source.clear(); f.nparams = 0; }
     f.cb = fn;
     f.cb_user = fn ? user : nullptr;
     user_rollout_stale = true;
     user_xform_rollout_stale = true;
+}
+
+// Runtime parameters of a parameterised reward / dynamics: count = P (shared by every agent) or A * P (per local agent).
+// Only uploads, never compiles.  Resident and graph-replayed control steps never run a user path (use_fused*() wants
+// built-in plug-ins, graph_ok wants !user_path()), so the copy only has to be ordered on the handle's stream ahead of the
+// next launch: it goes there, after whatever still reads the old rows, and is waited for, so `data` may go on return.
+void Engine::set_user_params(int kind, const float* data, int64_t count) {
+    REQUIRE(kind == USER_KIND_REWARD || kind == USER_KIND_DYNAMICS, BBMPC_E_INVALID, "kind must be 1 (reward) or 2 (dynamics)");
+    const UserFunction& f = kind == USER_KIND_REWARD ? user_reward : user_dynamics;
+    REQUIRE(f.nparams > 0, BBMPC_E_STATE,
+            kind == USER_KIND_REWARD ? "user reward: no parameterised source set (bbmpc_set_reward_source_params)"
+                                     : "user dynamics: no parameterised source set (bbmpc_set_dynamics_source_params)");
+    const int64_t P = f.nparams;
+    REQUIRE(count == P || count == (int64_t)A * P, BBMPC_E_INVALID,
+            "runtime parameters: count must be num_params (shared) or num_agents * num_params (per agent)");
+    REQUIRE(data, BBMPC_E_INVALID, "runtime parameters: null data");
+    std::vector<float> rows((size_t)A * P);
+    for (int a = 0; a < A; ++a) memcpy(rows.data() + (size_t)a * P, data + (count == P ? 0 : (size_t)a * P), (size_t)P * 4);
+    UserParams& pp = kind == USER_KIND_REWARD ? rew_params : dyn_params;
+    if (pp.d.n < rows.size()) {
+        HIP_CHECK(hipStreamSynchronize(stream));       // the old buffer may still be read
+        pp.d.alloc(rows.size());
+    }
+    HIP_CHECK(hipMemcpyAsync(pp.d.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    pp.set = true;
+    pp.per_agent = count != P;
+}
+
+// the device rows of a parameterised function (nullptr for a classic one); refuses to compute before they were set
+const float* Engine::user_params_dev(int kind) const {
+    const UserFunction& f = kind == USER_KIND_REWARD ? user_reward : user_dynamics;
+    if (f.nparams == 0) return nullptr;
+    const UserParams& pp = kind == USER_KIND_REWARD ? rew_params : dyn_params;
+    REQUIRE(pp.set, BBMPC_E_STATE, kind == USER_KIND_REWARD ? "user reward: runtime parameters not set (bbmpc_set_user_params)"
+                                                           : "user dynamics: runtime parameters not set (bbmpc_set_user_params)");
+    return pp.d.p;
+}
+
+// rows of one agent in a batch of rows (the evaluator's layout b = a * rows + n): per-agent parameters need a multiple of A
+// rows; shared ones any batch (every row then reads agent 0's copy)
+int Engine::rows_per_agent(int kind, int batch) const {
+    const UserParams& pp = kind == USER_KIND_REWARD ? rew_params : dyn_params;
+    if (!pp.per_agent) return batch;
+    REQUIRE(batch % A == 0, BBMPC_E_INVALID,
+            "per-agent runtime parameters: a call on B rows needs B to be a multiple of num_agents (B / A consecutive rows per agent)");
+    return batch / A;
 }
 
 // Target transforms (rtc.hpp): the inverse one on a learned-model or BBMPC_DYN_USER handle replaces next = dev + state
@@ -582,8 +632,12 @@ void Engine::set_transform_source(int kind, const char* src) {
     const bool rebuild_dyn = inverse && cfg.dynamics == BBMPC_DYN_USER && !user_dynamics.source.empty();
     std::vector<char> code, dyn_code;
     try {
-        if (!clear) code = compile_user_program(src, kind, S, U);
-        if (rebuild_dyn) dyn_code = compile_user_program(user_dynamics.source, USER_KIND_DYNAMICS, S, U, clear ? std::string() : std::string(src));
+        if (!clear) { ++rtc_compiles; code = compile_user_program(src, kind, S, U); }
+        if (rebuild_dyn) {
+            ++rtc_compiles;
+            dyn_code = compile_user_program(user_dynamics.source, USER_KIND_DYNAMICS, S, U, clear ? std::string() : std::string(src),
+                                            user_dynamics.nparams);
+        }
     } catch (const std::exception& ex) {
         throw HipError(BBMPC_E_INVALID, ex.what());
     }
@@ -624,7 +678,7 @@ __global__ void k_rows_accumulate(const float* __restrict__ r, int batch, float*
 }
 
 // next = process_output(state, dynamics(process_input(state, action)))  on [batch] rows   deterministic.py:79-103
-void Engine::dynamics_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next) {
+void Engine::dynamics_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next, int t) {
     if (cfg.dynamics == BBMPC_DYN_USER && user_dynamics.cb) {
         const float* acts_c = d_actions;
         if (astride != U) {                               // the callback sees a dense [batch, U] block
@@ -639,6 +693,12 @@ void Engine::dynamics_rows(const float* d_states, const float* d_actions, int as
     }
     if (cfg.dynamics == BBMPC_DYN_USER) {
         REQUIRE(user_dynamics.fn, BBMPC_E_STATE, "user dynamics: call bbmpc_set_dynamics_source (or bbmpc_set_dynamics_callback) before computing");
+        if (const float* params = user_params_dev(USER_KIND_DYNAMICS)) {
+            int rpa = rows_per_agent(USER_KIND_DYNAMICS, batch);
+            void* args[] = {(void*)&d_states, (void*)&d_actions, (void*)&astride, (void*)&batch, (void*)&d_next, (void*)&params, (void*)&rpa, (void*)&t};
+            HIP_CHECK(hipModuleLaunchKernel(user_dynamics.fn, (unsigned)((batch + 255) / 256), 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+            return;
+        }
         void* args[] = {(void*)&d_states, (void*)&d_actions, (void*)&astride, (void*)&batch, (void*)&d_next};
         HIP_CHECK(hipModuleLaunchKernel(user_dynamics.fn, (unsigned)((batch + 255) / 256), 1, 1, 256, 1, 1, 0, stream, args, nullptr));
         return;
@@ -658,7 +718,7 @@ void Engine::dynamics_rows(const float* d_states, const float* d_actions, int as
 
 // total (+)= reward_function(cur, actions, next) on [batch] rows   deterministic.py:65-66, 105-127
 void Engine::reward_rows(const float* d_cur, const float* d_next, const float* d_actions, int astride, int batch, float* d_total,
-                         int accumulate) {
+                         int accumulate, int t) {
     if (cfg.reward == BBMPC_REW_USER && user_reward.cb) {
         const float* acts_c = d_actions;
         if (astride != U) {
@@ -676,6 +736,13 @@ void Engine::reward_rows(const float* d_cur, const float* d_next, const float* d
     }
     if (cfg.reward == BBMPC_REW_USER) {
         REQUIRE(user_reward.fn, BBMPC_E_STATE, "user reward: call bbmpc_set_reward_source (or bbmpc_set_reward_callback) before computing");
+        if (const float* params = user_params_dev(USER_KIND_REWARD)) {
+            int rpa = rows_per_agent(USER_KIND_REWARD, batch);
+            void* args[] = {(void*)&d_cur,   (void*)&d_next,     (void*)&d_actions, (void*)&astride, (void*)&batch,
+                            (void*)&d_total, (void*)&accumulate, (void*)&params,    (void*)&rpa,     (void*)&t};
+            HIP_CHECK(hipModuleLaunchKernel(user_reward.fn, (unsigned)((batch + 255) / 256), 1, 1, 256, 1, 1, 0, stream, args, nullptr));
+            return;
+        }
         void* args[] = {(void*)&d_cur, (void*)&d_next, (void*)&d_actions, (void*)&astride, (void*)&batch, (void*)&d_total, (void*)&accumulate};
         HIP_CHECK(hipModuleLaunchKernel(user_reward.fn, (unsigned)((batch + 255) / 256), 1, 1, 256, 1, 1, 0, stream, args, nullptr));
         return;
@@ -719,8 +786,8 @@ void Engine::rollout_stepwise(int mode, bool pen, RolloutArgs& ra) {
     float* nxt = u_x1.p;
     for (int t = 0; t < Hh; ++t) {
         const float* acts = u_rows.p + (size_t)t * B * U;
-        dynamics_rows(cur, acts, U, (int)B, nxt);
-        reward_rows(cur, nxt, acts, U, (int)B, u_total.p, t > 0 ? 1 : 0);
+        dynamics_rows(cur, acts, U, (int)B, nxt, t);
+        reward_rows(cur, nxt, acts, U, (int)B, u_total.p, t > 0 ? 1 : 0, t);
         std::swap(cur, nxt);
     }
     hipLaunchKernelGGL(k_rows_finish, grid, block, 0, stream, n_pop, A, ra.Nst, pen ? 1 : 0, u_total.p, u_pen.p, ra.rewards, ra.penalty_out);
@@ -736,9 +803,10 @@ void Engine::rollout_user_fused(int mode, bool pen, RolloutArgs& ra) {
         if (cfg.dynamics == BBMPC_DYN_USER) REQUIRE(user_dynamics.fn, BBMPC_E_STATE, "user dynamics: call bbmpc_set_dynamics_source before computing");
         std::vector<char> code;
         try {
+            ++rtc_compiles;
             code = compile_user_rollout(cfg.reward == BBMPC_REW_USER ? user_reward.source : std::string(),
                                         cfg.dynamics == BBMPC_DYN_USER ? user_dynamics.source : std::string(), cfg.dynamics, cfg.reward, S, U,
-                                        user_xform.source);
+                                        user_xform.source, user_reward.nparams, user_dynamics.nparams);
         } catch (const std::exception& ex) {
             throw HipError(BBMPC_E_INVALID, ex.what());
         }
@@ -764,7 +832,12 @@ void Engine::rollout_user_fused(int mode, bool pen, RolloutArgs& ra) {
     const float* hi_ = ra.hi;
     float* rewards = ra.rewards;
     float* penalty_out = ra.penalty_out;
-    void* args[] = {&n_pop, &Aa, &Hh, &Nst_, &from_ref, &ipen, &fq1, &state, &seq, &cand, &samples, &lo_, &hi_, &rewards, &penalty_out};
+    // parameterised sides only (else null); a classic program's kernel has 15 arguments and the launch reads no more
+    // entries of args[] than the kernel has
+    const float* rew_p = user_params_dev(USER_KIND_REWARD);
+    const float* dyn_p = user_params_dev(USER_KIND_DYNAMICS);
+    void* args[] = {&n_pop, &Aa, &Hh, &Nst_, &from_ref, &ipen, &fq1, &state, &seq, &cand, &samples, &lo_, &hi_, &rewards, &penalty_out,
+                    &rew_p, &dyn_p};
     // few trajectories -> one wave per workgroup (latency); many -> 256-thread workgroups
     const unsigned bs = ((long)n_pop * A <= 16384) ? 64 : 256;
     prof_begin();
@@ -793,7 +866,8 @@ void Engine::rollout_mlp_user_reward(int mode, bool pen, RolloutArgs& ra) {
     const float* cand = mode == SRC_BUF ? ra.cand : ra.samples;
     float* rewards = ra.rewards;
     if (mode != SRC_REF) REQUIRE(cand, BBMPC_E_STATE, "user reward over the learned model: no candidate buffer");
-    void* args[] = {&n_pop, &Aa, &Hh, &Nst_, &from_ref, &state, &traj, &seq, &cand, &rewards};
+    const float* params = user_params_dev(USER_KIND_REWARD);                  // a parameterised reward only
+    void* args[] = {&n_pop, &Aa, &Hh, &Nst_, &from_ref, &state, &traj, &seq, &cand, &rewards, &params};
     HIP_CHECK(hipModuleLaunchKernel(user_reward.fn_traj, (unsigned)((n_pop + 255) / 256), (unsigned)A, 1, 256, 1, 1, 0, stream, args, nullptr));
 }
 
@@ -847,8 +921,9 @@ void Engine::rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra) {
     if (user_xform_rollout_stale || !user_xform_rollout.fn || act_ext != user_xform_rollout_ext) {
         std::vector<char> code;
         try {
+            ++rtc_compiles;
             code = compile_mlp_xform_rollout(user_xform.source, cfg.reward == BBMPC_REW_USER ? user_reward.source : std::string(),
-                                             cfg.reward, S, U, act_ext);
+                                             cfg.reward, S, U, act_ext, cfg.reward == BBMPC_REW_USER ? user_reward.nparams : 0);
         } catch (const std::exception& ex) {
             throw HipError(BBMPC_E_INVALID, ex.what());
         }
@@ -885,7 +960,8 @@ void Engine::rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra) {
     x.rewards = ra.rewards;
     x.penalty_out = ra.penalty_out;
     if (mode != SRC_REF) REQUIRE(x.cand, BBMPC_E_STATE, "learned-model transform rollout: no candidate buffer");
-    void* args[] = {&x};
+    const float* rew_p = cfg.reward == BBMPC_REW_USER ? user_params_dev(USER_KIND_REWARD) : nullptr;
+    void* args[] = {&x, &rew_p};                                               // the second one only for a parameterised reward
     prof_begin();
     HIP_CHECK(hipModuleLaunchKernel(user_xform_rollout.fn, (unsigned)((ra.n_pop + XF_TP - 1) / XF_TP), (unsigned)A, 1, (unsigned)(mlp_nw * 64),
                                     1, 1, (unsigned)lds, stream, args, nullptr));
@@ -1977,6 +2053,83 @@ int bbmpc_set_dynamics_source(bbmpc_handle h, const char* src) {
     h->e->invalidate_step_graph();
     CHECK_PTR(src);
     h->e->set_user_source(bbmpc::USER_KIND_DYNAMICS, src);
+    API_END
+}
+
+static void check_num_params(int32_t num_params) {
+    if (num_params < 1) throw HipError(BBMPC_E_INVALID, "num_params must be >= 1 (a source without parameters: bbmpc_set_*_source)");
+    if (num_params > BBMPC_MAX_USER_PARAMS)
+        throw HipError(BBMPC_E_UNSUPPORTED, "num_params > " + std::to_string(BBMPC_MAX_USER_PARAMS) + " floats per agent");
+}
+
+int bbmpc_set_reward_source_params(bbmpc_handle h, const char* src, int32_t num_params) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->invalidate_step_graph();
+    CHECK_PTR(src);
+    check_num_params(num_params);
+    h->e->set_user_source(bbmpc::USER_KIND_REWARD, src, num_params);
+    API_END
+}
+
+int bbmpc_set_dynamics_source_params(bbmpc_handle h, const char* src, int32_t num_params) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->invalidate_step_graph();
+    CHECK_PTR(src);
+    check_num_params(num_params);
+    h->e->set_user_source(bbmpc::USER_KIND_DYNAMICS, src, num_params);
+    API_END
+}
+
+// no invalidate_step_graph(): a captured step never covers a user path (optimize_host's graph_ok wants !user_path())
+int bbmpc_set_user_params(bbmpc_handle h, int32_t kind, const float* data, int64_t count) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_user_params(kind, data, count);
+    API_END
+}
+
+int bbmpc_compile_stats(bbmpc_handle h, int64_t* compiles) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    if (compiles) *compiles = h->e->rtc_compiles;
+    API_END
+}
+
+// Every program a parameterised source takes part in, compiled (no GPU).  The partner a side lacks is a classic stub.
+int bbmpc_check_user_params(const char* rew_src, int32_t rew_np, const char* dyn_src, int32_t dyn_np, int32_t dim_s, int32_t dim_u) {
+    API_BEGIN
+    if (!rew_src && !dyn_src) throw HipError(BBMPC_E_INVALID, "no source given");
+    if (rew_src) check_num_params(rew_np);
+    if (dyn_src) check_num_params(dyn_np);
+    if (dim_s < 1 || dim_u < 1 || dim_s > 256 || dim_u > 256) throw HipError(BBMPC_E_INVALID, "dim_s / dim_u must be in [1, 256]");
+    static const char* const k_stub_reward =
+        "__device__ float bbmpc_user_reward(const float* c, const float* a, const float* n, int S, int U) { return -n[0] * n[0]; }\n";
+    static const char* const k_stub_dynamics =
+        "__device__ void bbmpc_user_dynamics(const float* x, float* d, int S, int U) { for (int i = 0; i < S; ++i) d[i] = 0.01f * x[i]; }\n";
+    static const char* const k_stub_xform =
+        "__device__ void bbmpc_user_inverse_transform_targets(const float* c, const float* d, float* n, int S) "
+        "{ for (int i = 0; i < S; ++i) n[i] = c[i] + d[i]; }\n";
+    const std::string rs = rew_src ? rew_src : k_stub_reward, ds = dyn_src ? dyn_src : k_stub_dynamics;
+    const int rn = rew_src ? rew_np : 0, dn = dyn_src ? dyn_np : 0;
+    try {
+        if (rew_src) {
+            (void)bbmpc::compile_user_program(rs, bbmpc::USER_KIND_REWARD, dim_s, dim_u, std::string(), rn);      // rows + traj scorer
+            (void)bbmpc::compile_user_rollout(rs, "", BBMPC_DYN_PENDULUM, BBMPC_REW_USER, dim_s, dim_u, std::string(), rn, 0);
+            if (dim_s <= 64 && dim_s + dim_u <= 128)                                                     // the learned model's limits
+                (void)bbmpc::compile_mlp_xform_rollout(k_stub_xform, rs, BBMPC_REW_USER, dim_s, dim_u, true, rn);
+        }
+        if (dyn_src) {
+            (void)bbmpc::compile_user_program(ds, bbmpc::USER_KIND_DYNAMICS, dim_s, dim_u, std::string(), dn);
+            (void)bbmpc::compile_user_program(ds, bbmpc::USER_KIND_DYNAMICS, dim_s, dim_u, k_stub_xform, dn);
+            for (int rk : {BBMPC_REW_PENDULUM, BBMPC_REW_CHEETAH})
+                (void)bbmpc::compile_user_rollout("", ds, BBMPC_DYN_USER, rk, dim_s, dim_u, std::string(), 0, dn);
+        }
+        (void)bbmpc::compile_user_rollout(rs, ds, BBMPC_DYN_USER, BBMPC_REW_USER, dim_s, dim_u, std::string(), rn, dn);
+    } catch (const std::exception& ex) {
+        throw HipError(BBMPC_E_INVALID, ex.what());
+    }
     API_END
 }
 

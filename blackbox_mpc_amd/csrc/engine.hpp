@@ -300,13 +300,26 @@ struct Engine {
     DevBuf<float> u_xin, u_xraw;       // learned model + transform, step-wise: processed inputs / de-normalised outputs
     bool user_path() const { return cfg.reward == BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_USER || has_xform(); }
     int builtin_reward_kind() const { return cfg.reward == BBMPC_REW_USER ? REW_NONE : cfg.reward; }
-    void set_user_source(int kind, const char* src);
+    void set_user_source(int kind, const char* src, int nparams = 0);
     void set_user_callback(int kind, bbmpc_rows_callback fn, void* user);
+    // runtime parameters of a parameterised user reward / dynamics (bbmpc_set_user_params): [A][P] on the device -- a
+    // shared row is stored once per agent, so every kernel reads the row of its own agent
+    struct UserParams {
+        bool set = false, per_agent = false;
+        DevBuf<float> d;
+    };
+    UserParams rew_params, dyn_params;
+    int64_t rtc_compiles = 0;          // hiprtc compilations of this handle (bbmpc_compile_stats)
+    void set_user_params(int kind, const float* data, int64_t count);
+    const float* user_params_dev(int kind) const;
+    int rows_per_agent(int kind, int batch) const;
     bool user_callbacks() const { return user_reward.cb != nullptr || user_dynamics.cb != nullptr; }
     DevBuf<float> u_cb_rew;            // rewards of one planning step as a callback wrote them
     void rollout_stepwise(int mode, bool pen, RolloutArgs& ra);
-    void dynamics_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next);
-    void reward_rows(const float* d_cur, const float* d_next, const float* d_actions, int astride, int batch, float* d_total, int accumulate);
+    // t: the planning step a parameterised function sees (0 on one-step calls)
+    void dynamics_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next, int t = 0);
+    void reward_rows(const float* d_cur, const float* d_next, const float* d_actions, int astride, int batch, float* d_total, int accumulate,
+                     int t = 0);
     void mlp_forward_rows(const float* d_x, int batch, float* d_out);
     // population sharding (PI2): per-iteration partials of this rank and the gathered partials of all ranks
     DevBuf<float> ps_part, ps_all;

@@ -148,8 +148,13 @@ __device__ __forceinline__ void xf_layer_k_split(const XformArgs& q, int l, int 
     }
 }
 
-// grid (ceil(n_pop / 16), A), block nw * 64, dynamic LDS xform_lds_layout(...).total floats
+// grid (ceil(n_pop / 16), A), block nw * 64, dynamic LDS xform_lds_layout(...).total floats.  A parameterised user reward
+// (BBMPC_REW_NPARAMS, rtc.hpp) takes rew_params [A][P] as a second argument and reads the row of agent blockIdx.y.
+#ifdef BBMPC_REW_NPARAMS
+extern "C" __global__ void bbmpc_mlp_xform_rollout(XformArgs q, const float* __restrict__ rew_params) {
+#else
 extern "C" __global__ void bbmpc_mlp_xform_rollout(XformArgs q) {
+#endif
     constexpr int S = BBMPC_S, U = BBMPC_U, TP = XF_TP, Sp = (S + 3) & ~3;
     float* const smem = xf_smem;
     const int a = blockIdx.y, n0 = blockIdx.x * TP;
@@ -264,7 +269,9 @@ extern "C" __global__ void bbmpc_mlp_xform_rollout(XformArgs q) {
             const float* c = cur + tid * Sp;
             const float* ac = acts + (t * TP + tid) * U;
             const float* nx = nxt + tid * Sp;
-#if BBMPC_REW_KIND == 3
+#if BBMPC_REW_KIND == 3 && defined(BBMPC_REW_NPARAMS)
+            total = total + bbmpc_user_reward_params(c, ac, nx, S, U, rew_params + (size_t)a * BBMPC_REW_NPARAMS, t);
+#elif BBMPC_REW_KIND == 3
             total = total + bbmpc_user_reward(c, ac, nx, S, U);                // (current_state, actions, next_state)
 #else
             total = total + reward_generic(BBMPC_REW_KIND, q.fix_q1 != 0, c, ac, nx, S, U);

@@ -10,6 +10,15 @@
 // per row.  bbmpc_set_reward_source / bbmpc_set_dynamics_source compile it together with the two row kernels below and
 // the engine calls them once per planning step from its step-wise evaluator (kernels_user.hpp).  libhiprtc is bound at
 // run time, next to the HIP runtime the process already uses; compiling needs no GPU.
+//
+// Runtime parameters (bbmpc_set_*_source_params): a source declared with P > 0 parameters defines instead
+//     __device__ float bbmpc_user_reward_params(const float* cur, const float* act, const float* nxt, int S, int U,
+//                                               const float* params, int t);
+//     __device__ void  bbmpc_user_dynamics_params(const float* x, float* delta, int S, int U, const float* params, int t);
+// where `params` is the P-float row of the agent that owns the row (read only) and t the planning step (0 on one-step
+// calls).  The programs are then compiled with BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS = P and the kernel texts below get
+// the parameterised call and the extra kernel arguments filled in; a source without parameters gets exactly the classic
+// text, so its kernels are the ones it always had.
 #pragma once
 #include <dlfcn.h>
 #include "../../include/bbmpc.h"   // bbmpc_rows_callback
@@ -77,10 +86,27 @@ constexpr int USER_KIND_REWARD = 1, USER_KIND_DYNAMICS = 2;
 //     __device__ void bbmpc_user_transform_targets(const float* cur, const float* next, float* target, int S);
 constexpr int USER_KIND_INVERSE_TRANSFORM = 3, USER_KIND_TRANSFORM = 4;
 
+// The kernel texts below carry @@NAME@@ slots where the classic and the parameterised programs differ; fill_slots puts
+// one of the two in (every slot must be there: a missing one is a bug in this file, not in the user's source).
+inline std::string fill_slots(std::string text, const std::vector<std::pair<std::string, std::string>>& slots) {
+    for (const auto& kv : slots) {
+        const std::string key = "@@" + kv.first + "@@";
+        size_t at = text.find(key);
+        if (at == std::string::npos) throw std::logic_error("rtc.hpp: kernel text without slot " + key);
+        for (; at != std::string::npos; at = text.find(key, at + kv.second.size())) text.replace(at, key.size(), kv.second);
+    }
+    return text;
+}
+
 // The row kernels the engine launches around the user's function.  BBMPC_S / BBMPC_U are compile-time so the per-row
 // arrays live in registers; rows are [batch, S] / [batch, astride] row-major.  `xform_src` (dynamics only, may be empty):
-// the handle's inverse target transform, which then replaces next = delta + state (BBMPC_XFORM).
-inline std::string user_program_source(const std::string& user_src, int kind, const std::string& xform_src = std::string()) {
+// the handle's inverse target transform, which then replaces next = delta + state (BBMPC_XFORM).  nparams > 0 (reward /
+// dynamics): the parameterised entry point; the row kernels take (params [A][P], rows_per_agent, t) -- row b belongs to
+// agent b / rows_per_agent -- and the traj scorer takes params and reads the row of agent blockIdx.y.
+inline std::string user_program_source(const std::string& user_src, int kind, const std::string& xform_src = std::string(),
+                                       int nparams = 0) {
+    const bool par = nparams > 0;
+    const char* const rows_args = par ? ",\n        const float* __restrict__ params, int rows_per_agent, int t" : "";
     std::string s;
     s += "// ---- user source ------------------------------------------------------------------\n";
     s += user_src;
@@ -91,17 +117,17 @@ inline std::string user_program_source(const std::string& user_src, int kind, co
     }
     s += "\n// ---- row kernels (blackbox_mpc_amd/csrc/rtc.hpp) ------------------------------------\n";
     if (kind == USER_KIND_REWARD) {
-        s += R"RTC(
+        s += fill_slots(R"RTC(
 extern "C" __global__ void bbmpc_user_reward_rows(const float* __restrict__ cur, const float* __restrict__ nxt,
                                                   const float* __restrict__ act, int astride, int batch,
-                                                  float* __restrict__ total, int accumulate) {
+                                                  float* __restrict__ total, int accumulate@@ROWS_ARGS@@) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     float c[BBMPC_S], n[BBMPC_S], a[BBMPC_U];
     for (int i = 0; i < BBMPC_S; ++i) { c[i] = cur[(size_t)b * BBMPC_S + i]; n[i] = nxt[(size_t)b * BBMPC_S + i]; }
     for (int i = 0; i < BBMPC_U; ++i) a[i] = act[(size_t)b * astride + i];
     // reward_function(current_state, actions, next_state): the argument order of the CALL (deterministic.py:65-66)
-    const float r = bbmpc_user_reward(c, a, n, BBMPC_S, BBMPC_U);
+    const float r = @@REWARD_ROW@@;
     total[b] = accumulate ? total[b] + r : r;
 }
 
@@ -111,7 +137,7 @@ extern "C" __global__ void bbmpc_user_reward_rows(const float* __restrict__ cur,
 extern "C" __global__ void bbmpc_user_reward_traj(int n_pop, int A, int H, int Nst, int from_ref,
                                                   const float* __restrict__ state, const float* __restrict__ traj,
                                                   const float* __restrict__ seq, const float* __restrict__ cand,
-                                                  float* __restrict__ rewards) {
+                                                  float* __restrict__ rewards@@TRAJ_ARGS@@) {
     const int a = blockIdx.y, n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_pop) return;
     const int HU = H * BBMPC_U;
@@ -125,13 +151,20 @@ extern "C" __global__ void bbmpc_user_reward_traj(int n_pop, int A, int H, int N
             const int j = t * BBMPC_U + u;
             ac[u] = from_ref ? seq[((size_t)n * A + a) * HU + j] : cand[((size_t)a * HU + j) * Nst + n];
         }
-        total = total + bbmpc_user_reward(c, ac, nx, BBMPC_S, BBMPC_U);
+        total = total + @@REWARD_TRAJ@@;
         for (int i = 0; i < BBMPC_S; ++i) c[i] = nx[i];
     }
     if (total != total) total = -1.0e6f;
     rewards[(size_t)a * Nst + n] = total + rewards[(size_t)a * Nst + n];
 }
-)RTC";
+)RTC",
+                        {{"ROWS_ARGS", rows_args},
+                         {"REWARD_ROW", par ? "bbmpc_user_reward_params(c, a, n, BBMPC_S, BBMPC_U, params + (size_t)(b / rows_per_agent) * "
+                                              "BBMPC_REW_NPARAMS, t)"
+                                            : "bbmpc_user_reward(c, a, n, BBMPC_S, BBMPC_U)"},
+                         {"TRAJ_ARGS", par ? ", const float* __restrict__ params" : ""},
+                         {"REWARD_TRAJ", par ? "bbmpc_user_reward_params(c, ac, nx, BBMPC_S, BBMPC_U, params + (size_t)a * BBMPC_REW_NPARAMS, t)"
+                                             : "bbmpc_user_reward(c, ac, nx, BBMPC_S, BBMPC_U)"}});
     } else if (kind == USER_KIND_INVERSE_TRANSFORM) {
         s += R"RTC(
 // next = inverse_transform_targets_func(cur, dev) on rows (system_dynamics_handler.py:157-161)
@@ -159,15 +192,15 @@ extern "C" __global__ void bbmpc_user_transform_rows(const float* __restrict__ c
 }
 )RTC";
     } else {
-        s += R"RTC(
+        s += fill_slots(R"RTC(
 extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ states, const float* __restrict__ act,
-                                                    int astride, int batch, float* __restrict__ next_states) {
+                                                    int astride, int batch, float* __restrict__ next_states@@ROWS_ARGS@@) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     float x[BBMPC_S + BBMPC_U], d[BBMPC_S];
     for (int i = 0; i < BBMPC_S; ++i) x[i] = states[(size_t)b * BBMPC_S + i];                    // process_input: concat
     for (int i = 0; i < BBMPC_U; ++i) x[BBMPC_S + i] = act[(size_t)b * astride + i];
-    bbmpc_user_dynamics(x, d, BBMPC_S, BBMPC_U);                                                // f(x, train=False) -> delta
+    @@DYNAMICS_ROW@@;                                                // f(x, train=False) -> delta
 #ifdef BBMPC_XFORM
     float nx[BBMPC_S];
     bbmpc_user_inverse_transform_targets(x, d, nx, BBMPC_S);                                    // the raw output (:148-151)
@@ -176,7 +209,11 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
     for (int i = 0; i < BBMPC_S; ++i) next_states[(size_t)b * BBMPC_S + i] = d[i] + x[i];        // transforms.py:34
 #endif
 }
-)RTC";
+)RTC",
+                        {{"ROWS_ARGS", rows_args},
+                         {"DYNAMICS_ROW", par ? "bbmpc_user_dynamics_params(x, d, BBMPC_S, BBMPC_U, params + (size_t)(b / rows_per_agent) * "
+                                                "BBMPC_DYN_NPARAMS, t)"
+                                              : "bbmpc_user_dynamics(x, d, BBMPC_S, BBMPC_U)"}});
     }
     return s;
 }
@@ -190,19 +227,22 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
 //   BBMPC_DYN_KIND 1 = PendulumTrueModel (op-for-op form), 3 = bbmpc_user_dynamics
 //   BBMPC_REW_KIND 1 / 2 = built-in pendulum / cheetah reward, 3 = bbmpc_user_reward
 //   xform_src (user dynamics only, may be empty): the inverse target transform, inlined in place of next = delta + state
+//   rew_np / dyn_np > 0: that side is parameterised (BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS); the kernel then takes
+//   rew_params / dyn_params [A][P] after its classic arguments and hands the function the row of agent blockIdx.y --
+//   uniform over the workgroup, so the reads are scalar loads -- and the horizon step t
 inline std::string user_rollout_source(const std::string& reward_src, const std::string& dynamics_src,
-                                       const std::string& xform_src = std::string()) {
+                                       const std::string& xform_src = std::string(), int rew_np = 0, int dyn_np = 0) {
     std::string s = "#include \"models.hpp\"\n";
     s += "// ---- user reward --------------------------------------------------------------------\n" + reward_src + "\n";
     s += "// ---- user dynamics ------------------------------------------------------------------\n" + dynamics_src + "\n";
     if (!xform_src.empty())
         s += "// ---- user inverse target transform ---------------------------------------------------\n" + xform_src + "\n#define BBMPC_XFORM 1\n";
-    s += R"RTC(
+    s += fill_slots(R"RTC(
 extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, int from_ref, int pen, int fix_q1,
                                               const float* __restrict__ state, const float* __restrict__ seq,
                                               const float* cand, float* samples, const float* __restrict__ lo,
                                               const float* __restrict__ hi, float* __restrict__ rewards,
-                                              float* __restrict__ penalty_out) {
+                                              float* __restrict__ penalty_out@@PARAM_ARGS@@) {
     constexpr int S = BBMPC_S, U = BBMPC_U;
     const int a = blockIdx.y, n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_pop) return;
@@ -226,7 +266,7 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
 #if BBMPC_DYN_KIND == 3
         {
             float d[S];
-            bbmpc_user_dynamics(x, d, S, U);                                   // f(x, train=False) -> delta
+            @@DYNAMICS_STEP@@;                                   // f(x, train=False) -> delta
 #ifdef BBMPC_XFORM
             bbmpc_user_inverse_transform_targets(x, d, nx, S);                 // the raw output (:148-151)
 #else
@@ -243,7 +283,7 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
         }
 #endif
 #if BBMPC_REW_KIND == 3
-        total = total + bbmpc_user_reward(x, x + S, nx, S, U);                   // (current_state, actions, next_state)
+        total = total + @@REWARD_STEP@@;                   // (current_state, actions, next_state)
 #else
         total = total + bbmpc::reward_generic(BBMPC_REW_KIND, fix_q1 != 0, x, x + S, nx, S, U);
 #endif
@@ -258,7 +298,12 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
     }
     rewards[(size_t)a * Nst + n] = total;
 }
-)RTC";
+)RTC",
+                    {{"PARAM_ARGS", rew_np > 0 || dyn_np > 0 ? ",\n        const float* __restrict__ rew_params, const float* __restrict__ dyn_params" : ""},
+                     {"DYNAMICS_STEP", dyn_np > 0 ? "bbmpc_user_dynamics_params(x, d, S, U, dyn_params + (size_t)a * BBMPC_DYN_NPARAMS, t)"
+                                                  : "bbmpc_user_dynamics(x, d, S, U)"},
+                     {"REWARD_STEP", rew_np > 0 ? "bbmpc_user_reward_params(x, x + S, nx, S, U, rew_params + (size_t)a * BBMPC_REW_NPARAMS, t)"
+                                                : "bbmpc_user_reward(x, x + S, nx, S, U)"}});
     return s;
 }
 
@@ -298,19 +343,27 @@ inline std::vector<char> compile_rtc(const std::string& src, const char* name, c
     return code;
 }
 
+// the -D flags of a parameterised side (none for a classic source)
+inline void add_nparams_defines(std::vector<std::string>& defs, int rew_np, int dyn_np) {
+    if (rew_np > 0) defs.push_back("-DBBMPC_REW_NPARAMS=" + std::to_string(rew_np));
+    if (dyn_np > 0) defs.push_back("-DBBMPC_DYN_NPARAMS=" + std::to_string(dyn_np));
+}
+
 inline std::vector<char> compile_user_program(const std::string& user_src, int kind, int S, int U,
-                                             const std::string& xform_src = std::string()) {
+                                             const std::string& xform_src = std::string(), int nparams = 0) {
     static const char* const names[] = {"", "bbmpc_user_reward.hip", "bbmpc_user_dynamics.hip", "bbmpc_user_inverse_transform.hip",
                                         "bbmpc_user_transform.hip"};
-    return compile_rtc(user_program_source(user_src, kind, xform_src), names[kind],
-                       {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U)}, false);
+    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U)};
+    add_nparams_defines(defs, kind == USER_KIND_REWARD ? nparams : 0, kind == USER_KIND_DYNAMICS ? nparams : 0);
+    return compile_rtc(user_program_source(user_src, kind, xform_src, nparams), names[kind], defs, false);
 }
 
 inline std::vector<char> compile_user_rollout(const std::string& reward_src, const std::string& dynamics_src, int dyn_kind, int rew_kind,
-                                              int S, int U, const std::string& xform_src = std::string()) {
-    return compile_rtc(user_rollout_source(reward_src, dynamics_src, xform_src), "bbmpc_user_rollout.hip",
-                       {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U), "-DBBMPC_DYN_KIND=" + std::to_string(dyn_kind),
-                        "-DBBMPC_REW_KIND=" + std::to_string(rew_kind)}, true);
+                                              int S, int U, const std::string& xform_src = std::string(), int rew_np = 0, int dyn_np = 0) {
+    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U),
+                                     "-DBBMPC_DYN_KIND=" + std::to_string(dyn_kind), "-DBBMPC_REW_KIND=" + std::to_string(rew_kind)};
+    add_nparams_defines(defs, rew_np, dyn_np);
+    return compile_rtc(user_rollout_source(reward_src, dynamics_src, xform_src, rew_np, dyn_np), "bbmpc_user_rollout.hip", defs, true);
 }
 
 // The learned-model rollout with the inverse target transform inlined (kernels_mlp_xform.hpp); reward_src is the user
@@ -323,17 +376,19 @@ inline std::string mlp_xform_rollout_source(const std::string& xform_src, const 
     return s;
 }
 
-// act_ext: the network has an activation after sigmoid (activations.hpp), so the program dispatches over every code
+// act_ext: the network has an activation after sigmoid (activations.hpp), so the program dispatches over every code.
+// rew_np > 0: a parameterised user reward (the kernel then takes rew_params [A][P] after XformArgs).
 inline std::vector<char> compile_mlp_xform_rollout(const std::string& xform_src, const std::string& reward_src, int rew_kind, int S, int U,
-                                                   bool act_ext = true) {
-    return compile_rtc(mlp_xform_rollout_source(xform_src, reward_src), "bbmpc_mlp_xform_rollout.hip",
-                       {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U), "-DBBMPC_REW_KIND=" + std::to_string(rew_kind),
-                        std::string("-DBBMPC_ACT_EXT=") + (act_ext ? "1" : "0")},
-                       true);
+                                                   bool act_ext = true, int rew_np = 0) {
+    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U),
+                                     "-DBBMPC_REW_KIND=" + std::to_string(rew_kind), std::string("-DBBMPC_ACT_EXT=") + (act_ext ? "1" : "0")};
+    add_nparams_defines(defs, rew_np, 0);
+    return compile_rtc(mlp_xform_rollout_source(xform_src, reward_src), "bbmpc_mlp_xform_rollout.hip", defs, true);
 }
 
 struct UserFunction {
     std::string source;
+    int nparams = 0;                       // > 0: the source defines the parameterised entry point (bbmpc_set_*_source_params)
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
     hipFunction_t fn_traj = nullptr;       // reward module only: bbmpc_user_reward_traj

@@ -47,6 +47,7 @@ class Engine:
         dev = ctypes.c_int32(-1)
         L.check(L.lib.bbmpc_handle_device(self._h, ctypes.byref(dev)))             # where the handle lives, fixed at creation: the
         self._device = int(dev.value)                                               # library's answer, not a guess from torch's state
+        self._param_fns, self._params_uploaded = {}, {}     # parameterised user functions: kind -> function / uploaded version
 
     @property
     def device(self):
@@ -99,13 +100,33 @@ class Engine:
         else:
             L.check(L.lib.bbmpc_set_mlp(self._h, n, dims_a, acts_a, wp, bp, 0, None))
 
-    def set_reward_source(self, hip_source):
-        """HIP source defining `__device__ float bbmpc_user_reward(cur, act, nxt, S, U)` (include/bbmpc.h)."""
-        L.check(L.lib.bbmpc_set_reward_source(self._h, hip_source.encode()))
+    def set_reward_source(self, hip_source, num_params=0):
+        """HIP source defining `__device__ float bbmpc_user_reward(cur, act, nxt, S, U)`, or with num_params > 0
+        `bbmpc_user_reward_params(cur, act, nxt, S, U, params, t)` (include/bbmpc.h)."""
+        if num_params:
+            L.check(L.lib.bbmpc_set_reward_source_params(self._h, hip_source.encode(), int(num_params)))
+        else:
+            L.check(L.lib.bbmpc_set_reward_source(self._h, hip_source.encode()))
 
-    def set_dynamics_source(self, hip_source):
-        """HIP source defining `__device__ void bbmpc_user_dynamics(x, delta, S, U)` (include/bbmpc.h)."""
-        L.check(L.lib.bbmpc_set_dynamics_source(self._h, hip_source.encode()))
+    def set_dynamics_source(self, hip_source, num_params=0):
+        """HIP source defining `__device__ void bbmpc_user_dynamics(x, delta, S, U)`, or with num_params > 0
+        `bbmpc_user_dynamics_params(x, delta, S, U, params, t)` (include/bbmpc.h)."""
+        if num_params:
+            L.check(L.lib.bbmpc_set_dynamics_source_params(self._h, hip_source.encode(), int(num_params)))
+        else:
+            L.check(L.lib.bbmpc_set_dynamics_source(self._h, hip_source.encode()))
+
+    def set_user_params(self, kind, values):
+        """Upload runtime parameters (kind USER_KIND_REWARD / USER_KIND_DYNAMICS): [P] shared or [num_agents, P] (local
+        agents).  Never compiles."""
+        v = L.f32c(values).reshape(-1)
+        L.check(L.lib.bbmpc_set_user_params(self._h, int(kind), L.ptr(v), int(v.size)))
+
+    def compile_count(self):
+        """hiprtc compilations this handle has run (bbmpc_compile_stats)."""
+        n = ctypes.c_int64(0)
+        L.check(L.lib.bbmpc_compile_stats(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def set_inverse_transform_source(self, hip_source):
         """HIP source defining `__device__ void bbmpc_user_inverse_transform_targets(cur, dev, next, S)`, or None to clear

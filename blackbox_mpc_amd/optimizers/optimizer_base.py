@@ -53,6 +53,14 @@ class OptimizerBase:
             configure_dynamics(eng, h)
         return eng
 
+    def _require_engine_and_params(self):
+        # what _require_engine is on an optimizer whose reward / dynamics has runtime parameters: they are uploaded when
+        # they changed since the last computation (set_trajectory_evaluator picks it, so built-ins skip the test)
+        from ..utils.device_functions import sync_user_params
+        eng = OptimizerBase._require_engine(self)
+        sync_user_params(eng)
+        return eng
+
     def __call__(self, current_state, time_step=0, add_exploration_noise=False):
         """(current_state[A,S], time_step, add_exploration_noise) ->
         (action[A,U], next_state[A,S], rewards_of_next_state[A])   optimizer_base.py:55-95"""
@@ -82,4 +90,8 @@ class OptimizerBase:
                               population_global=self._population_global, **self._engine_kwargs())
         configure_dynamics(self._engine, h)
         configure_reward(self._engine, trajectory_evaluator._reward_function)
+        if self._engine._param_fns:
+            self._require_engine = self._require_engine_and_params
+        else:
+            self.__dict__.pop("_require_engine", None)
         return

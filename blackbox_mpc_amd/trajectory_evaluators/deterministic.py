@@ -99,14 +99,17 @@ def configure_transform(engine, handler, dyn):
 
 def configure_dynamics(engine, handler):
     """Upload MLP weights + normalisation statistics when the dynamics are learned; attach user dynamics."""
+    from ..utils import device_functions as DF
     dyn = dynamics_plugin(handler)
     configure_transform(engine, handler, dyn)
     if getattr(dyn, "_bbmpc_dynamics_kind", None) == L.DYN_MLP:
         engine.set_mlp(dyn.weights, dyn.biases, dyn.activation_codes, handler.normalization_stats())
     elif engine.cfg.dynamics == L.DYN_USER and isinstance(getattr(dyn, "hip_source", None), str):
-        if getattr(engine, "_dyn_source", None) is not dyn.hip_source:
-            engine.set_dynamics_source(dyn.hip_source)
-            engine._dyn_source = dyn.hip_source
+        np_ = getattr(dyn, "num_params", 0)
+        if getattr(engine, "_dyn_source", None) is not dyn.hip_source or getattr(engine, "_dyn_nparams", 0) != np_:
+            engine.set_dynamics_source(dyn.hip_source, np_)
+            engine._dyn_source, engine._dyn_nparams = dyn.hip_source, np_
+            DF.attach_params(engine, L.USER_KIND_DYNAMICS, dyn)
     elif engine.cfg.dynamics == L.DYN_USER:
         # a callable on torch CUDA tensors: rebuilt whenever the handler's statistics change (they are baked into it)
         engine.set_dynamics_callback(dyn.make_callback(handler, engine.device))
@@ -117,12 +120,14 @@ def configure_reward(engine, reward_function, handler=None):
     """Compile + attach the user's reward device function (or its torch callback), once per engine."""
     if engine.cfg.reward != L.REW_USER:
         return
-    if isinstance(getattr(reward_function, "hip_source", None), str):
-        if getattr(engine, "_rew_source", None) is not reward_function.hip_source:
-            engine.set_reward_source(reward_function.hip_source)
-            engine._rew_source = reward_function.hip_source
-        return
     from ..utils import device_functions as DF
+    if isinstance(getattr(reward_function, "hip_source", None), str):
+        np_ = getattr(reward_function, "num_params", 0)
+        if getattr(engine, "_rew_source", None) is not reward_function.hip_source or getattr(engine, "_rew_nparams", 0) != np_:
+            engine.set_reward_source(reward_function.hip_source, np_)
+            engine._rew_source, engine._rew_nparams = reward_function.hip_source, np_
+            DF.attach_params(engine, L.USER_KIND_REWARD, reward_function)
+        return
     plug = reward_function if isinstance(reward_function, DF.TorchRewardFunction) else DF.torch_plugin(reward_function, DF.TorchRewardFunction)
     if getattr(engine, "_rew_plugin", None) is not plug:
         engine.set_reward_callback(plug.make_callback(engine.S, engine.U, engine.device))
@@ -153,7 +158,19 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
             self._engines[key] = eng
         if dynamics_stale(eng, h):
             configure_dynamics(eng, h)
+        if eng._param_fns:
+            from ..utils.device_functions import sync_user_params
+            sync_user_params(eng)
         return eng
+
+    def _one_step_agents(self):
+        """Agents of the one-step calls' engine: the rows of per-agent runtime parameters (B / A consecutive rows of a
+        call belong to one agent), else 1."""
+        for fn in (self._reward_function, self._system_dynamics_handler._dynamics_function):
+            p = getattr(fn, "_params", None)
+            if p is not None and p.ndim == 2:
+                return p.shape[0]
+        return 1
 
     def __call__(self, current_states, action_sequences, time_step=0):
         """current_states [A,S], action_sequences [N,A,H,U] -> rewards [N,A] (NaN -> -1e6)."""
@@ -164,7 +181,7 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
 
     def predict_next_state(self, current_states, current_actions):
         s = np.asarray(current_states, np.float32)
-        return self._engine(1, 1).predict_next_state(s, np.asarray(current_actions, np.float32))
+        return self._engine(self._one_step_agents(), 1).predict_next_state(s, np.asarray(current_actions, np.float32))
 
     def evaluate_next_reward(self, current_states, next_states, current_actions):
-        return self._engine(1, 1).evaluate_next_reward(current_states, next_states, current_actions)
+        return self._engine(self._one_step_agents(), 1).evaluate_next_reward(current_states, next_states, current_actions)

@@ -29,7 +29,22 @@ The engine then evaluates step by step (SURVEY.md H5's unfused fallback) and cal
 the row batches of its own HBM buffers aliased as torch tensors (TorchRewardFunction / TorchDynamicsFunction below,
 bbmpc_set_*_callback in include/bbmpc.h); the torch work is enqueued on the engine's stream, nothing is copied to the
 host.  Slower than device code (2 * H + 2 launches plus the framework's per-op overhead) but never on the CPU.  A callable
-that cannot take CUDA tensors is refused (NotImplementedError), as before."""
+that cannot take CUDA tensors is refused (NotImplementedError), as before.
+
+RUNTIME PARAMETERS (goals, setpoints, reference trajectories, estimated plant constants) change between control steps
+without a recompile.  A function declared with num_params=P defines the parameterised entry point instead
+(include/bbmpc.h):
+
+    reward = HipRewardFunction('''
+        __device__ float bbmpc_user_reward_params(const float* cur, const float* act, const float* nxt, int S, int U,
+                                                  const float* params, int t) {       // params: this agent's P floats
+            const float d = nxt[0] - params[0];                                        // t: planning step (0 one-step)
+            return -d * d - 0.1f * act[0] * act[0];
+        }''', num_params=1)
+    reward.set_params([0.5])                        # [P]: every agent; [num_agents_global, P]: one row per agent
+
+Every engine built on the function uploads the parameters before its next computation when they changed (an engine of
+a sharded policy takes the rows of its own agents); set_params never compiles."""
 import numpy as np
 
 from .. import _lib as L
@@ -40,12 +55,50 @@ def check_source(kind, hip_source, dim_s, dim_u):
     L.check(L.lib.bbmpc_check_user_source(int(kind), hip_source.encode(), int(dim_s), int(dim_u)))
 
 
+def check_params_source(dim_s, dim_u, reward_source=None, reward_params=0, dynamics_source=None, dynamics_params=0):
+    """Compile only (no GPU needed) every program a parameterised reward and / or dynamics takes part in."""
+    rew = reward_source.encode() if reward_source is not None else None
+    dyn = dynamics_source.encode() if dynamics_source is not None else None
+    L.check(L.lib.bbmpc_check_user_params(rew, int(reward_params), dyn, int(dynamics_params), int(dim_s), int(dim_u)))
+
+
 class _HipFunction:
+    num_params = 0
+    _params = None                    # float32 [P] (shared) or [num_agents_global, P] (per agent), set_params' copy
+    _params_version = 0
+
     def __init__(self, hip_source):
         if not isinstance(hip_source, str) or not hip_source.strip():
             raise ValueError("hip_source must be a non-empty string of HIP device code")
         self.hip_source = hip_source
         self._engines = {}
+
+    def _init_params(self, num_params):
+        if isinstance(num_params, bool) or not isinstance(num_params, (int, np.integer)):
+            raise TypeError("num_params must be an int, got %r" % (num_params,))
+        if not 0 <= int(num_params) <= L.MAX_USER_PARAMS:
+            raise ValueError("num_params must be in [0, %d], got %d" % (L.MAX_USER_PARAMS, num_params))
+        self.num_params = int(num_params)
+
+    def set_params(self, values):
+        """values [P] (shared by every agent) or [num_agents_global, P] (one row per agent): stored as a float32 copy;
+        engines upload it before their next computation."""
+        if not self.num_params:
+            raise ValueError("set_params: %s was declared without runtime parameters (num_params=0)" % type(self).__name__)
+        v = np.array(values, dtype=np.float32, copy=True)
+        P = self.num_params
+        if not ((v.ndim == 1 and v.shape[0] == P) or (v.ndim == 2 and v.shape[0] >= 1 and v.shape[1] == P)):
+            raise ValueError("set_params: expected [%d] or [num_agents_global, %d], got shape %s" % (P, P, v.shape))
+        self._params = v
+        self._params_version += 1
+
+    def _direct_engine(self, dim_s, dim_u):
+        """The engine of a direct NumPy call: shared parameters only."""
+        if self._params is not None and self._params.ndim == 2:
+            raise ValueError("calling %s directly uses shared parameters, but per-agent ones are set" % type(self).__name__)
+        eng = self._engine(dim_s, dim_u)
+        sync_user_params(eng)
+        return eng
 
     def _engine(self, dim_s, dim_u, low=None, high=None):
         from ..engine import Engine
@@ -60,31 +113,39 @@ class _HipFunction:
 
 
 class HipRewardFunction(_HipFunction):
-    """reward_function given as HIP source (`bbmpc_user_reward`)."""
+    """reward_function given as HIP source (`bbmpc_user_reward`, or `bbmpc_user_reward_params` with num_params > 0)."""
     _bbmpc_reward_kind = L.REW_USER
+
+    def __init__(self, hip_source, num_params=0):
+        super().__init__(hip_source)
+        self._init_params(num_params)
 
     def _make(self, Engine, dim_s, lo, hi):
         # the dynamics kind is irrelevant for evaluate_next_reward; a user-dynamics handle needs no weights
         eng = Engine(L.OPT_NONE, L.DYN_USER, L.REW_USER, lo, hi, dim_s=dim_s, num_agents=1, planning_horizon=1)
-        eng.set_reward_source(self.hip_source)
+        eng.set_reward_source(self.hip_source, self.num_params)
+        attach_params(eng, L.USER_KIND_REWARD, self)
         return eng
 
     def __call__(self, current_state, actions, next_state):
         cur, act, nxt = (np.asarray(v, np.float32) for v in (current_state, actions, next_state))
-        return self._engine(cur.shape[1], act.shape[1]).evaluate_next_reward(cur, nxt, act)
+        return self._direct_engine(cur.shape[1], act.shape[1]).evaluate_next_reward(cur, nxt, act)
 
 
 class HipDynamicsFunction(_HipFunction):
-    """dynamics_function given as HIP source (`bbmpc_user_dynamics`); f(x[B,S+U], train) -> delta[B,S]."""
+    """dynamics_function given as HIP source (`bbmpc_user_dynamics`, or `bbmpc_user_dynamics_params` with
+    num_params > 0); f(x[B,S+U], train) -> delta[B,S]."""
     _bbmpc_dynamics_kind = L.DYN_USER
 
-    def __init__(self, hip_source, dim_s=None, dim_u=None):
+    def __init__(self, hip_source, dim_s=None, dim_u=None, num_params=0):
         super().__init__(hip_source)
         self._dims = (dim_s, dim_u)
+        self._init_params(num_params)
 
     def _make(self, Engine, dim_s, lo, hi):
         eng = Engine(L.OPT_NONE, L.DYN_USER, L.REW_USER, lo, hi, dim_s=dim_s, num_agents=1, planning_horizon=1)
-        eng.set_dynamics_source(self.hip_source)
+        eng.set_dynamics_source(self.hip_source, self.num_params)
+        attach_params(eng, L.USER_KIND_DYNAMICS, self)
         return eng
 
     def __call__(self, x, train=False):
@@ -93,7 +154,7 @@ class HipDynamicsFunction(_HipFunction):
         if dim_s is None or dim_u is None:
             raise ValueError("calling a HipDynamicsFunction directly needs dim_s / dim_u (constructor) to split x")
         s, a = x[:, :dim_s], x[:, dim_s:dim_s + dim_u]
-        return self._engine(dim_s, dim_u).predict_next_state(s, a) - s
+        return self._direct_engine(dim_s, dim_u).predict_next_state(s, a) - s
 
 
 class HipInverseTargetTransform(_HipFunction):
@@ -127,6 +188,31 @@ class HipTargetTransform(_HipFunction):
     def __call__(self, states, next_states):
         s, n = np.asarray(states, np.float32), np.asarray(next_states, np.float32)
         return self._engine(s.shape[1], 1).transform_rows(L.USER_KIND_TRANSFORM, s, n)
+
+
+def attach_params(engine, kind, fn):
+    """Register a parameterised function with the engine it was just set on (the handle has no parameters yet)."""
+    engine._params_uploaded.pop(kind, None)
+    if fn.num_params:
+        engine._param_fns[kind] = fn
+    else:
+        engine._param_fns.pop(kind, None)
+
+
+def sync_user_params(engine):
+    """Upload the parameters of the engine's parameterised functions whose copy on the engine is behind: a shared row,
+    or the rows [agent_offset, agent_offset + num_agents) of per-agent ones.  Never set: left to the engine to refuse."""
+    for kind, fn in engine._param_fns.items():
+        p = fn._params
+        if p is None or engine._params_uploaded.get(kind) == fn._params_version:
+            continue
+        if p.ndim == 2:
+            if p.shape[0] != engine.cfg.num_agents_global:
+                raise ValueError("%s: per-agent parameters have %d rows, the engine plans for %d agents"
+                                 % (type(fn).__name__, p.shape[0], engine.cfg.num_agents_global))
+            p = p[engine.cfg.agent_offset:engine.cfg.agent_offset + engine.A]
+        engine.set_user_params(kind, p)
+        engine._params_uploaded[kind] = fn._params_version
 
 
 def check_transform_rollout(hip_source, dim_s, dim_u, reward_kind=L.REW_CHEETAH, reward_source=None):

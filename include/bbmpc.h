@@ -214,6 +214,38 @@ int bbmpc_set_dynamics_callback(bbmpc_handle h, bbmpc_rows_callback fn, void* us
  * BBMPC_REW_* kinds, sources NULL for built-ins.  Needs no GPU. */
 int bbmpc_check_user_rollout(int32_t dynamics, int32_t reward, const char* dynamics_source, const char* reward_source,
                              int32_t dim_s, int32_t dim_u);
+/* Runtime parameters of HIP-source plug-ins: goals, setpoints, reference trajectories or estimated plant constants that
+ * change between control steps without a recompile.  A source set with bbmpc_set_*_source_params(h, src, P) defines
+ * the parameterised entry point instead of the classic one:
+ *     __device__ float bbmpc_user_reward_params(const float* cur, const float* act, const float* nxt, int S, int U,
+ *                                               const float* params, int t);
+ *     __device__ void  bbmpc_user_dynamics_params(const float* x, float* delta, int S, int U, const float* params, int t);
+ * `params` is the P-float row of the agent that owns the row being scored (read only); t is the planning step inside
+ * the horizon, 0 for the one-step calls (the control step's next state and reward, bbmpc_predict_next_state,
+ * bbmpc_evaluate_next_reward, bbmpc_step_dev).  Every kernel that calls the function gets the row: the fused
+ * analytic rollout, the step-wise evaluator, the learned model's trajectory scorer and its transform rollout.  The
+ * program is compiled with BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS = P (a source without parameters compiles exactly
+ * as before).  Limits: 1 <= P <= BBMPC_MAX_USER_PARAMS floats per agent (BBMPC_E_INVALID below, BBMPC_E_UNSUPPORTED
+ * above).
+ * bbmpc_set_user_params(h, kind, data, count): kind 1 = reward, 2 = dynamics; host data of count = P floats (shared by
+ * every agent) or num_agents * P (one row per LOCAL agent, agent-major).  It only uploads, on the handle's stream
+ * behind the work already queued, and returns once the copy is done.  BBMPC_E_STATE when the handle's function of that
+ * kind has no parameters, BBMPC_E_INVALID for any other count.  Computing with a parameterised function whose
+ * parameters were never set fails with BBMPC_E_STATE; a one-step call on B rows with per-agent parameters needs B to be
+ * a multiple of num_agents (B / A consecutive rows per agent) and fails with BBMPC_E_INVALID otherwise.
+ * bbmpc_compile_stats: the number of hiprtc compilations this handle has run (sources, transforms and the fused
+ * rollouts it builds lazily) -- a parameter update never adds one.
+ * bbmpc_check_user_params compiles (no GPU) every program a parameterised reward and/or dynamics takes part in: the
+ * row kernels (and the trajectory scorer), the fused rollouts with each built-in and user partner, and the learned
+ * model's transform rollout with the reward inlined; a missing partner source is a classic stub.  A NULL source skips
+ * that side. */
+#define BBMPC_MAX_USER_PARAMS 4096
+int bbmpc_set_reward_source_params(bbmpc_handle h, const char* hip_source, int32_t num_params);
+int bbmpc_set_dynamics_source_params(bbmpc_handle h, const char* hip_source, int32_t num_params);
+int bbmpc_set_user_params(bbmpc_handle h, int32_t kind, const float* data, int64_t count);
+int bbmpc_compile_stats(bbmpc_handle h, int64_t* compiles);
+int bbmpc_check_user_params(const char* reward_source, int32_t reward_params, const char* dynamics_source,
+                            int32_t dynamics_params, int32_t dim_s, int32_t dim_u);
 /* Target transforms: SystemDynamicsHandler's transform_targets_func / inverse_transform_targets_func (reference
  * dynamics_handlers/system_dynamics_handler.py:15-17, 128-161, 314) as HIP source (hiprtc, gfx950) defining per row
  *     __device__ void bbmpc_user_inverse_transform_targets(const float* cur, const float* dev, float* next, int S);
