@@ -32,7 +32,6 @@
 #include "kernels_rollout.hpp"
 #include "kernels_tail.hpp"
 #include "kernels_user.hpp"
-#include "rtc.hpp"
 
 namespace bbmpc {
 
@@ -78,6 +77,25 @@ struct DevBuf {
 };
 
 hipStream_t masked_stream_from_env(const char* name, int cu_count);
+
+// A user-supplied function as the handle holds it: a program compiled at run time (rtc.hpp, loaded by bbmpc_user.hip) or
+// a host callback.
+struct UserProgram;
+struct UserFunction {
+    std::string source;
+    int nparams = 0;                       // > 0: the source defines the parameterised entry point (bbmpc_set_*_source_params)
+    hipModule_t module = nullptr;
+    hipFunction_t fn = nullptr;
+    hipFunction_t fn_traj = nullptr;       // reward module only: bbmpc_user_reward_traj
+    bbmpc_rows_callback cb = nullptr;      // or: a host callback working on device memory (bbmpc_set_*_callback)
+    void* cb_user = nullptr;
+    void release() {
+        if (module) (void)hipModuleUnload(module);
+        module = nullptr;
+        fn = nullptr;
+        fn_traj = nullptr;
+    }
+};
 
 struct Engine {
     bbmpc_config cfg;
@@ -271,7 +289,8 @@ struct Engine {
         return kk;
     }
     bool fix(uint32_t bit) const { return (cfg.quirks & bit) != 0; }
-    // user-supplied reward / dynamics device functions (rtc.hpp) and the step-wise evaluator that calls them
+    // user-supplied reward / dynamics device functions and the step-wise evaluator that calls them (bbmpc_user.hip; kind =
+    // rtc.hpp's USER_KIND_*)
     UserFunction user_reward, user_dynamics, user_rollout;   // user_rollout: the fused lane-per-trajectory kernel (rtc.hpp), built lazily
     bool user_rollout_stale = true;
     bool user_stepwise_only = false;   // BBMPC_USER_STEPWISE: never fuse (test / comparison hook)
@@ -311,8 +330,15 @@ struct Engine {
     UserParams rew_params, dyn_params;
     int64_t rtc_compiles = 0;          // hiprtc compilations of this handle (bbmpc_compile_stats)
     void set_user_params(int kind, const float* data, int64_t count);
-    const float* user_params_dev(int kind) const;
-    int rows_per_agent(int kind, int batch) const;
+    const float* user_params_dev(int kind);
+    int rows_per_agent(int kind, int batch);
+    UserFunction& user_fn(int kind);            // the reward / dynamics side: its function, its parameters, ...
+    UserParams& user_pp(int kind);
+    void require_user_side(int kind) const;     // ... and the handle created for a user function on that side
+    UserProgram user_program() const;           // what the handle's programs are compiled from (rtc.hpp)
+    void launch_rows(hipFunction_t fn, int batch, void** args);
+    void draw_candidates(int mode, RolloutArgs& ra);
+    const float* dense_actions(const float* d_actions, int astride, int batch);
     bool user_callbacks() const { return user_reward.cb != nullptr || user_dynamics.cb != nullptr; }
     DevBuf<float> u_cb_rew;            // rewards of one planning step as a callback wrote them
     void rollout_stepwise(int mode, bool pen, RolloutArgs& ra);

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the engine's translation units (bbmpc.hip, bbmpc_cma.hip, bbmpc_mlp.hip).
+// Host-side helpers shared by the engine's translation units (bbmpc.hip, bbmpc_cma.hip, bbmpc_mlp.hip, bbmpc_fused.hip).
 #pragma once
 #include <mutex>
 #include <set>

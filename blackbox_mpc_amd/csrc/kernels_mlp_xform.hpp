@@ -4,7 +4,7 @@
 // the model output and hands it to inverse_transform_targets_func(states, dev) -- by default `dev + states`
 // (utils/transforms.py:34).  A custom transform is HIP source defining
 //     __device__ void bbmpc_user_inverse_transform_targets(const float* cur, const float* dev, float* next, int S);
-// and this kernel is compiled at run time with it (rtc.hpp mlp_xform_rollout_source), so the Dense stack stays on the matrix
+// and this kernel is compiled at run time with it (rtc.hpp program_source), so the Dense stack stays on the matrix
 // cores and the transform costs one inlined call per particle and step.
 //
 // Mapping: the generic kernel's (kernels_mlp.hpp:1-20).  One workgroup owns a 16-particle tile of one agent for the whole
@@ -269,10 +269,8 @@ extern "C" __global__ void bbmpc_mlp_xform_rollout(XformArgs q) {
             const float* c = cur + tid * Sp;
             const float* ac = acts + (t * TP + tid) * U;
             const float* nx = nxt + tid * Sp;
-#if BBMPC_REW_KIND == 3 && defined(BBMPC_REW_NPARAMS)
-            total = total + bbmpc_user_reward_params(c, ac, nx, S, U, rew_params + (size_t)a * BBMPC_REW_NPARAMS, t);
-#elif BBMPC_REW_KIND == 3
-            total = total + bbmpc_user_reward(c, ac, nx, S, U);                // (current_state, actions, next_state)
+#if BBMPC_REW_KIND == 3
+            total = total + BBMPC_CALL_REWARD(c, ac, nx, rew_params, a, t);    // (current_state, actions, next_state); rtc.hpp k_user_calls
 #else
             total = total + reward_generic(BBMPC_REW_KIND, q.fix_q1 != 0, c, ac, nx, S, U);
 #endif

@@ -1,6 +1,6 @@
 // Step-wise trajectory evaluator: the un-fused form of DeterministicTrajectoryEvaluator.__call__
 // (trajectory_evaluators/deterministic.py:26-77) used whenever the reward or the dynamics is a user-supplied device
-// function (rtc.hpp).  It is the reference's own structure -- one batched dynamics call and one batched reward call
+// function (rtc.hpp; launched by Engine::rollout_stepwise in bbmpc_user.hip).  It is the reference's own structure -- one batched dynamics call and one batched reward call
 // per planning step over B = n_pop * A rows -- instead of the fused whole-horizon kernels the built-in pairs get:
 //
 //   k_rows_prepare      candidates (internal layout [A][H*U][Nst], or the caller's [n,A,H,U]) -> action rows [H][B][U],
@@ -10,8 +10,8 @@
 //                       reward rows    (user function | k_reward_rows_acc), accumulated   :65-67
 //   k_rows_finish       NaN -> -1e6 (:75-77), minus the penalty, into rewards [A][Nst]
 //
-// Row b = a * n_pop + n.  Sampling for RandomSearch / CEM / PI2 is a separate kernel here (k_gen_candidates), the
-// refits are the ordinary ones.
+// Row b = a * n_pop + n.  Sampling for RandomSearch / CEM / PI2 is a separate kernel here (k_gen_candidates, launched by
+// the core's Engine::draw_candidates for every user-function rollout), the refits are the ordinary ones.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -16,9 +16,10 @@
 //                                               const float* params, int t);
 //     __device__ void  bbmpc_user_dynamics_params(const float* x, float* delta, int S, int U, const float* params, int t);
 // where `params` is the P-float row of the agent that owns the row (read only) and t the planning step (0 on one-step
-// calls).  The programs are then compiled with BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS = P and the kernel texts below get
-// the parameterised call and the extra kernel arguments filled in; a source without parameters gets exactly the classic
-// text, so its kernels are the ones it always had.
+// calls).  The programs are then compiled with BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS = P, on which the kernel texts below
+// select the parameterised call and the extra kernel arguments with the preprocessor (k_user_calls); without the define a
+// kernel is exactly the classic one.  This header is the hiprtc side only; bbmpc_user.hip, the one unit that includes it,
+// holds the Engine members that compile, load and launch the programs, and their C ABI entry points.
 #pragma once
 #include <dlfcn.h>
 #include "../../include/bbmpc.h"   // bbmpc_rows_callback
@@ -86,48 +87,41 @@ constexpr int USER_KIND_REWARD = 1, USER_KIND_DYNAMICS = 2;
 //     __device__ void bbmpc_user_transform_targets(const float* cur, const float* next, float* target, int S);
 constexpr int USER_KIND_INVERSE_TRANSFORM = 3, USER_KIND_TRANSFORM = 4;
 
-// The kernel texts below carry @@NAME@@ slots where the classic and the parameterised programs differ; fill_slots puts
-// one of the two in (every slot must be there: a missing one is a bug in this file, not in the user's source).
-inline std::string fill_slots(std::string text, const std::vector<std::pair<std::string, std::string>>& slots) {
-    for (const auto& kv : slots) {
-        const std::string key = "@@" + kv.first + "@@";
-        size_t at = text.find(key);
-        if (at == std::string::npos) throw std::logic_error("rtc.hpp: kernel text without slot " + key);
-        for (; at != std::string::npos; at = text.find(key, at + kv.second.size())) text.replace(at, key.size(), kv.second);
-    }
-    return text;
-}
+// The two calls of a user function, for every program below and kernels_mlp_xform.hpp: the classic entry point, or with
+// BBMPC_*_NPARAMS the parameterised one on row `agent` of `params` [A][P] (an argument only the parameterised kernel has).
+static const char* const k_user_calls = R"RTC(
+#ifdef BBMPC_REW_NPARAMS
+#define BBMPC_CALL_REWARD(c, a, n, params, agent, t) bbmpc_user_reward_params(c, a, n, BBMPC_S, BBMPC_U, (params) + (size_t)(agent) * BBMPC_REW_NPARAMS, t)
+#else
+#define BBMPC_CALL_REWARD(c, a, n, params, agent, t) bbmpc_user_reward(c, a, n, BBMPC_S, BBMPC_U)
+#endif
+#ifdef BBMPC_DYN_NPARAMS
+#define BBMPC_CALL_DYNAMICS(x, d, params, agent, t) bbmpc_user_dynamics_params(x, d, BBMPC_S, BBMPC_U, (params) + (size_t)(agent) * BBMPC_DYN_NPARAMS, t)
+#else
+#define BBMPC_CALL_DYNAMICS(x, d, params, agent, t) bbmpc_user_dynamics(x, d, BBMPC_S, BBMPC_U)
+#endif
+)RTC";
 
 // The row kernels the engine launches around the user's function.  BBMPC_S / BBMPC_U are compile-time so the per-row
-// arrays live in registers; rows are [batch, S] / [batch, astride] row-major.  `xform_src` (dynamics only, may be empty):
-// the handle's inverse target transform, which then replaces next = delta + state (BBMPC_XFORM).  nparams > 0 (reward /
-// dynamics): the parameterised entry point; the row kernels take (params [A][P], rows_per_agent, t) -- row b belongs to
-// agent b / rows_per_agent -- and the traj scorer takes params and reads the row of agent blockIdx.y.
-inline std::string user_program_source(const std::string& user_src, int kind, const std::string& xform_src = std::string(),
-                                       int nparams = 0) {
-    const bool par = nparams > 0;
-    const char* const rows_args = par ? ",\n        const float* __restrict__ params, int rows_per_agent, int t" : "";
-    std::string s;
-    s += "// ---- user source ------------------------------------------------------------------\n";
-    s += user_src;
-    if (kind == USER_KIND_DYNAMICS && !xform_src.empty()) {
-        s += "\n// ---- user inverse target transform ----------------------------------------------------\n";
-        s += xform_src;
-        s += "\n#define BBMPC_XFORM 1\n";
-    }
-    s += "\n// ---- row kernels (blackbox_mpc_amd/csrc/rtc.hpp) ------------------------------------\n";
-    if (kind == USER_KIND_REWARD) {
-        s += fill_slots(R"RTC(
+// arrays live in registers; rows are [batch, S] / [batch, astride] row-major.  A dynamics program with an inverse target
+// transform (BBMPC_XFORM) applies it in place of next = delta + state.  A parameterised reward / dynamics: the row kernels
+// take (params [A][P], rows_per_agent, t) -- row b belongs to agent b / rows_per_agent -- and the traj scorer takes params
+// and reads the row of agent blockIdx.y.
+static const char* const k_reward_rows_text = R"RTC(
 extern "C" __global__ void bbmpc_user_reward_rows(const float* __restrict__ cur, const float* __restrict__ nxt,
                                                   const float* __restrict__ act, int astride, int batch,
-                                                  float* __restrict__ total, int accumulate@@ROWS_ARGS@@) {
+                                                  float* __restrict__ total, int accumulate
+#ifdef BBMPC_REW_NPARAMS
+                                                  , const float* __restrict__ params, int rows_per_agent, int t
+#endif
+                                                  ) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     float c[BBMPC_S], n[BBMPC_S], a[BBMPC_U];
     for (int i = 0; i < BBMPC_S; ++i) { c[i] = cur[(size_t)b * BBMPC_S + i]; n[i] = nxt[(size_t)b * BBMPC_S + i]; }
     for (int i = 0; i < BBMPC_U; ++i) a[i] = act[(size_t)b * astride + i];
     // reward_function(current_state, actions, next_state): the argument order of the CALL (deterministic.py:65-66)
-    const float r = @@REWARD_ROW@@;
+    const float r = BBMPC_CALL_REWARD(c, a, n, params, b / rows_per_agent, t);
     total[b] = accumulate ? total[b] + r : r;
 }
 
@@ -137,7 +131,11 @@ extern "C" __global__ void bbmpc_user_reward_rows(const float* __restrict__ cur,
 extern "C" __global__ void bbmpc_user_reward_traj(int n_pop, int A, int H, int Nst, int from_ref,
                                                   const float* __restrict__ state, const float* __restrict__ traj,
                                                   const float* __restrict__ seq, const float* __restrict__ cand,
-                                                  float* __restrict__ rewards@@TRAJ_ARGS@@) {
+                                                  float* __restrict__ rewards
+#ifdef BBMPC_REW_NPARAMS
+                                                  , const float* __restrict__ params
+#endif
+                                                  ) {
     const int a = blockIdx.y, n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_pop) return;
     const int HU = H * BBMPC_U;
@@ -151,22 +149,15 @@ extern "C" __global__ void bbmpc_user_reward_traj(int n_pop, int A, int H, int N
             const int j = t * BBMPC_U + u;
             ac[u] = from_ref ? seq[((size_t)n * A + a) * HU + j] : cand[((size_t)a * HU + j) * Nst + n];
         }
-        total = total + @@REWARD_TRAJ@@;
+        total = total + BBMPC_CALL_REWARD(c, ac, nx, params, a, t);
         for (int i = 0; i < BBMPC_S; ++i) c[i] = nx[i];
     }
     if (total != total) total = -1.0e6f;
     rewards[(size_t)a * Nst + n] = total + rewards[(size_t)a * Nst + n];
 }
-)RTC",
-                        {{"ROWS_ARGS", rows_args},
-                         {"REWARD_ROW", par ? "bbmpc_user_reward_params(c, a, n, BBMPC_S, BBMPC_U, params + (size_t)(b / rows_per_agent) * "
-                                              "BBMPC_REW_NPARAMS, t)"
-                                            : "bbmpc_user_reward(c, a, n, BBMPC_S, BBMPC_U)"},
-                         {"TRAJ_ARGS", par ? ", const float* __restrict__ params" : ""},
-                         {"REWARD_TRAJ", par ? "bbmpc_user_reward_params(c, ac, nx, BBMPC_S, BBMPC_U, params + (size_t)a * BBMPC_REW_NPARAMS, t)"
-                                             : "bbmpc_user_reward(c, ac, nx, BBMPC_S, BBMPC_U)"}});
-    } else if (kind == USER_KIND_INVERSE_TRANSFORM) {
-        s += R"RTC(
+)RTC";
+
+static const char* const k_inverse_transform_rows_text = R"RTC(
 // next = inverse_transform_targets_func(cur, dev) on rows (system_dynamics_handler.py:157-161)
 extern "C" __global__ void bbmpc_user_inverse_transform_rows(const float* __restrict__ cur, const float* __restrict__ dev,
                                                              int batch, float* __restrict__ next) {
@@ -178,8 +169,8 @@ extern "C" __global__ void bbmpc_user_inverse_transform_rows(const float* __rest
     for (int i = 0; i < BBMPC_S; ++i) next[(size_t)b * BBMPC_S + i] = nx[i];
 }
 )RTC";
-    } else if (kind == USER_KIND_TRANSFORM) {
-        s += R"RTC(
+
+static const char* const k_transform_rows_text = R"RTC(
 // target = transform_targets_func(cur, next) on rows (system_dynamics_handler.py:314)
 extern "C" __global__ void bbmpc_user_transform_rows(const float* __restrict__ cur, const float* __restrict__ next,
                                                      int batch, float* __restrict__ target) {
@@ -191,16 +182,20 @@ extern "C" __global__ void bbmpc_user_transform_rows(const float* __restrict__ c
     for (int i = 0; i < BBMPC_S; ++i) target[(size_t)b * BBMPC_S + i] = tg[i];
 }
 )RTC";
-    } else {
-        s += fill_slots(R"RTC(
+
+static const char* const k_dynamics_rows_text = R"RTC(
 extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ states, const float* __restrict__ act,
-                                                    int astride, int batch, float* __restrict__ next_states@@ROWS_ARGS@@) {
+                                                    int astride, int batch, float* __restrict__ next_states
+#ifdef BBMPC_DYN_NPARAMS
+                                                    , const float* __restrict__ params, int rows_per_agent, int t
+#endif
+                                                    ) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     float x[BBMPC_S + BBMPC_U], d[BBMPC_S];
     for (int i = 0; i < BBMPC_S; ++i) x[i] = states[(size_t)b * BBMPC_S + i];                    // process_input: concat
     for (int i = 0; i < BBMPC_U; ++i) x[BBMPC_S + i] = act[(size_t)b * astride + i];
-    @@DYNAMICS_ROW@@;                                                // f(x, train=False) -> delta
+    BBMPC_CALL_DYNAMICS(x, d, params, b / rows_per_agent, t);                                   // f(x, train=False) -> delta
 #ifdef BBMPC_XFORM
     float nx[BBMPC_S];
     bbmpc_user_inverse_transform_targets(x, d, nx, BBMPC_S);                                    // the raw output (:148-151)
@@ -209,14 +204,7 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
     for (int i = 0; i < BBMPC_S; ++i) next_states[(size_t)b * BBMPC_S + i] = d[i] + x[i];        // transforms.py:34
 #endif
 }
-)RTC",
-                        {{"ROWS_ARGS", rows_args},
-                         {"DYNAMICS_ROW", par ? "bbmpc_user_dynamics_params(x, d, BBMPC_S, BBMPC_U, params + (size_t)(b / rows_per_agent) * "
-                                                "BBMPC_DYN_NPARAMS, t)"
-                                              : "bbmpc_user_dynamics(x, d, BBMPC_S, BBMPC_U)"}});
-    }
-    return s;
-}
+)RTC";
 
 #include "_embed.inc"      // k_embed_fastmath, k_embed_models, k_embed_activations, k_embed_kernels_mlp_xform: headers as text (generated by _build.py)
 
@@ -227,22 +215,19 @@ extern "C" __global__ void bbmpc_user_dynamics_rows(const float* __restrict__ st
 //   BBMPC_DYN_KIND 1 = PendulumTrueModel (op-for-op form), 3 = bbmpc_user_dynamics
 //   BBMPC_REW_KIND 1 / 2 = built-in pendulum / cheetah reward, 3 = bbmpc_user_reward
 //   xform_src (user dynamics only, may be empty): the inverse target transform, inlined in place of next = delta + state
-//   rew_np / dyn_np > 0: that side is parameterised (BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS); the kernel then takes
-//   rew_params / dyn_params [A][P] after its classic arguments and hands the function the row of agent blockIdx.y --
-//   uniform over the workgroup, so the reads are scalar loads -- and the horizon step t
-inline std::string user_rollout_source(const std::string& reward_src, const std::string& dynamics_src,
-                                       const std::string& xform_src = std::string(), int rew_np = 0, int dyn_np = 0) {
-    std::string s = "#include \"models.hpp\"\n";
-    s += "// ---- user reward --------------------------------------------------------------------\n" + reward_src + "\n";
-    s += "// ---- user dynamics ------------------------------------------------------------------\n" + dynamics_src + "\n";
-    if (!xform_src.empty())
-        s += "// ---- user inverse target transform ---------------------------------------------------\n" + xform_src + "\n#define BBMPC_XFORM 1\n";
-    s += fill_slots(R"RTC(
+//   a parameterised side (BBMPC_REW_NPARAMS / BBMPC_DYN_NPARAMS): the kernel then takes rew_params / dyn_params [A][P]
+//   after its classic arguments and hands the function the row of agent blockIdx.y -- uniform over the workgroup, so the
+//   reads are scalar loads -- and the horizon step t
+static const char* const k_rollout_text = R"RTC(
 extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, int from_ref, int pen, int fix_q1,
                                               const float* __restrict__ state, const float* __restrict__ seq,
                                               const float* cand, float* samples, const float* __restrict__ lo,
                                               const float* __restrict__ hi, float* __restrict__ rewards,
-                                              float* __restrict__ penalty_out@@PARAM_ARGS@@) {
+                                              float* __restrict__ penalty_out
+#if defined(BBMPC_REW_NPARAMS) || defined(BBMPC_DYN_NPARAMS)
+                                              , const float* __restrict__ rew_params, const float* __restrict__ dyn_params
+#endif
+                                              ) {
     constexpr int S = BBMPC_S, U = BBMPC_U;
     const int a = blockIdx.y, n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_pop) return;
@@ -266,7 +251,7 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
 #if BBMPC_DYN_KIND == 3
         {
             float d[S];
-            @@DYNAMICS_STEP@@;                                   // f(x, train=False) -> delta
+            BBMPC_CALL_DYNAMICS(x, d, dyn_params, a, t);                       // f(x, train=False) -> delta
 #ifdef BBMPC_XFORM
             bbmpc_user_inverse_transform_targets(x, d, nx, S);                 // the raw output (:148-151)
 #else
@@ -283,7 +268,7 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
         }
 #endif
 #if BBMPC_REW_KIND == 3
-        total = total + @@REWARD_STEP@@;                   // (current_state, actions, next_state)
+        total = total + BBMPC_CALL_REWARD(x, x + S, nx, rew_params, a, t);      // (current_state, actions, next_state)
 #else
         total = total + bbmpc::reward_generic(BBMPC_REW_KIND, fix_q1 != 0, x, x + S, nx, S, U);
 #endif
@@ -298,14 +283,7 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
     }
     rewards[(size_t)a * Nst + n] = total;
 }
-)RTC",
-                    {{"PARAM_ARGS", rew_np > 0 || dyn_np > 0 ? ",\n        const float* __restrict__ rew_params, const float* __restrict__ dyn_params" : ""},
-                     {"DYNAMICS_STEP", dyn_np > 0 ? "bbmpc_user_dynamics_params(x, d, S, U, dyn_params + (size_t)a * BBMPC_DYN_NPARAMS, t)"
-                                                  : "bbmpc_user_dynamics(x, d, S, U)"},
-                     {"REWARD_STEP", rew_np > 0 ? "bbmpc_user_reward_params(x, x + S, nx, S, U, rew_params + (size_t)a * BBMPC_REW_NPARAMS, t)"
-                                                : "bbmpc_user_reward(x, x + S, nx, S, U)"}});
-    return s;
-}
+)RTC";
 
 // Compile for gfx950; returns the code object.  Throws std::runtime_error with the compiler log on failure.
 inline std::vector<char> compile_rtc(const std::string& src, const char* name, const std::vector<std::string>& defines,
@@ -343,64 +321,66 @@ inline std::vector<char> compile_rtc(const std::string& src, const char* name, c
     return code;
 }
 
-// the -D flags of a parameterised side (none for a classic source)
-inline void add_nparams_defines(std::vector<std::string>& defs, int rew_np, int dyn_np) {
-    if (rew_np > 0) defs.push_back("-DBBMPC_REW_NPARAMS=" + std::to_string(rew_np));
-    if (dyn_np > 0) defs.push_back("-DBBMPC_DYN_NPARAMS=" + std::to_string(dyn_np));
+// The programs, numbered so that the four row programs keep their USER_KIND_* value.
+constexpr int PROG_ROLLOUT = 5, PROG_MLP_XFORM_ROLLOUT = 6;
+
+// What a program is built from; each form reads the fields it needs (a row program: its own source and side; dynamics rows
+// and the fused rollout: xform_src too; the learned-model transform rollout: xform_src, the reward side and act_ext).
+struct UserProgram {
+    int S = 0, U = 0;
+    int dyn_kind = 0, rew_kind = 0;              // BBMPC_DYN_* / BBMPC_REW_* (3 = the user's function)
+    std::string reward_src, dynamics_src;        // empty where that side is built in
+    std::string xform_src;                       // the inverse target transform, or empty
+    int rew_np = 0, dyn_np = 0;                  // > 0: that side is parameterised
+    bool act_ext = true;                         // the network has an activation after sigmoid (activations.hpp): dispatch over every code
+    // the source a row program (USER_KIND_*) is named after
+    std::string& own_source(int kind) { return kind == USER_KIND_REWARD ? reward_src : kind == USER_KIND_DYNAMICS ? dynamics_src : xform_src; }
+};
+
+// the kernel a loaded program is entered by (the reward rows program also has bbmpc_user_reward_traj)
+inline const char* program_kernel(int form) {
+    static const char* const names[] = {"", "bbmpc_user_reward_rows", "bbmpc_user_dynamics_rows", "bbmpc_user_inverse_transform_rows",
+                                        "bbmpc_user_transform_rows", "bbmpc_user_rollout", "bbmpc_mlp_xform_rollout"};
+    return names[form];
 }
 
-inline std::vector<char> compile_user_program(const std::string& user_src, int kind, int S, int U,
-                                             const std::string& xform_src = std::string(), int nparams = 0) {
-    static const char* const names[] = {"", "bbmpc_user_reward.hip", "bbmpc_user_dynamics.hip", "bbmpc_user_inverse_transform.hip",
-                                        "bbmpc_user_transform.hip"};
-    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U)};
-    add_nparams_defines(defs, kind == USER_KIND_REWARD ? nparams : 0, kind == USER_KIND_DYNAMICS ? nparams : 0);
-    return compile_rtc(user_program_source(user_src, kind, xform_src, nparams), names[kind], defs, false);
+inline std::vector<std::string> program_defines(int form, const UserProgram& d) {
+    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(d.S), "-DBBMPC_U=" + std::to_string(d.U)};
+    if (form == PROG_ROLLOUT) defs.push_back("-DBBMPC_DYN_KIND=" + std::to_string(d.dyn_kind));
+    if (form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT) defs.push_back("-DBBMPC_REW_KIND=" + std::to_string(d.rew_kind));
+    if (form == PROG_MLP_XFORM_ROLLOUT) defs.push_back(std::string("-DBBMPC_ACT_EXT=") + (d.act_ext ? "1" : "0"));
+    const bool rew = form == USER_KIND_REWARD || form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT;
+    const bool dyn = form == USER_KIND_DYNAMICS || form == PROG_ROLLOUT;
+    if (rew && d.rew_np > 0) defs.push_back("-DBBMPC_REW_NPARAMS=" + std::to_string(d.rew_np));
+    if (dyn && d.dyn_np > 0) defs.push_back("-DBBMPC_DYN_NPARAMS=" + std::to_string(d.dyn_np));
+    return defs;
 }
 
-inline std::vector<char> compile_user_rollout(const std::string& reward_src, const std::string& dynamics_src, int dyn_kind, int rew_kind,
-                                              int S, int U, const std::string& xform_src = std::string(), int rew_np = 0, int dyn_np = 0) {
-    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U),
-                                     "-DBBMPC_DYN_KIND=" + std::to_string(dyn_kind), "-DBBMPC_REW_KIND=" + std::to_string(rew_kind)};
-    add_nparams_defines(defs, rew_np, dyn_np);
-    return compile_rtc(user_rollout_source(reward_src, dynamics_src, xform_src, rew_np, dyn_np), "bbmpc_user_rollout.hip", defs, true);
-}
-
-// The learned-model rollout with the inverse target transform inlined (kernels_mlp_xform.hpp); reward_src is the user
-// reward when rew_kind == 3 (BBMPC_REW_USER), else empty and a built-in reward kind.
-inline std::string mlp_xform_rollout_source(const std::string& xform_src, const std::string& reward_src) {
-    std::string s = "#include \"models.hpp\"\n";
-    s += "// ---- user reward --------------------------------------------------------------------\n" + reward_src + "\n";
-    s += "// ---- user inverse target transform ---------------------------------------------------\n" + xform_src + "\n";
-    s += "#define BBMPC_XFORM_KERNEL 1\n#include \"kernels_mlp_xform.hpp\"\n";
+inline std::string program_source(int form, const UserProgram& d) {
+    const std::string xform = d.xform_src.empty() ? std::string()
+        : "// ---- user inverse target transform ---------------------------------------------------\n" + d.xform_src + "\n#define BBMPC_XFORM 1\n";
+    if (form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT) {
+        std::string s = "#include \"models.hpp\"\n";
+        s += "// ---- user reward --------------------------------------------------------------------\n" + d.reward_src + "\n";
+        if (form == PROG_MLP_XFORM_ROLLOUT) return s + xform + k_user_calls + "#define BBMPC_XFORM_KERNEL 1\n#include \"kernels_mlp_xform.hpp\"\n";
+        s += "// ---- user dynamics ------------------------------------------------------------------\n" + d.dynamics_src + "\n";
+        return s + xform + k_user_calls + k_rollout_text;
+    }
+    std::string s = "// ---- user source ------------------------------------------------------------------\n";
+    s += UserProgram(d).own_source(form) + "\n";
+    if (form == USER_KIND_DYNAMICS) s += xform;
+    s += "// ---- row kernels (blackbox_mpc_amd/csrc/rtc.hpp) ------------------------------------\n";
+    s += k_user_calls;
+    s += form == USER_KIND_REWARD ? k_reward_rows_text : form == USER_KIND_DYNAMICS ? k_dynamics_rows_text
+         : form == USER_KIND_INVERSE_TRANSFORM ? k_inverse_transform_rows_text : k_transform_rows_text;
     return s;
 }
 
-// act_ext: the network has an activation after sigmoid (activations.hpp), so the program dispatches over every code.
-// rew_np > 0: a parameterised user reward (the kernel then takes rew_params [A][P] after XformArgs).
-inline std::vector<char> compile_mlp_xform_rollout(const std::string& xform_src, const std::string& reward_src, int rew_kind, int S, int U,
-                                                   bool act_ext = true, int rew_np = 0) {
-    std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(S), "-DBBMPC_U=" + std::to_string(U),
-                                     "-DBBMPC_REW_KIND=" + std::to_string(rew_kind), std::string("-DBBMPC_ACT_EXT=") + (act_ext ? "1" : "0")};
-    add_nparams_defines(defs, rew_np, 0);
-    return compile_rtc(mlp_xform_rollout_source(xform_src, reward_src), "bbmpc_mlp_xform_rollout.hip", defs, true);
+// the code object of one program; only the two rollouts see the engine's headers (models.hpp, kernels_mlp_xform.hpp, ...)
+inline std::vector<char> compile_program(int form, const UserProgram& d) {
+    static const char* const names[] = {"", "bbmpc_user_reward.hip", "bbmpc_user_dynamics.hip", "bbmpc_user_inverse_transform.hip",
+                                        "bbmpc_user_transform.hip", "bbmpc_user_rollout.hip", "bbmpc_mlp_xform_rollout.hip"};
+    return compile_rtc(program_source(form, d), names[form], program_defines(form, d), form >= PROG_ROLLOUT);
 }
-
-struct UserFunction {
-    std::string source;
-    int nparams = 0;                       // > 0: the source defines the parameterised entry point (bbmpc_set_*_source_params)
-    hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;
-    hipFunction_t fn_traj = nullptr;       // reward module only: bbmpc_user_reward_traj
-    bbmpc_rows_callback cb = nullptr;      // or: a host callback working on device memory (bbmpc_set_*_callback)
-    void* cb_user = nullptr;
-    bool ready() const { return fn != nullptr || cb != nullptr; }
-    void release() {
-        if (module) (void)hipModuleUnload(module);
-        module = nullptr;
-        fn = nullptr;
-        fn_traj = nullptr;
-    }
-};
 
 }  // namespace bbmpc
