@@ -77,6 +77,8 @@ SYMBOLS = [
     "bbmpc_set_inverse_transform_source", "bbmpc_set_transform_source", "bbmpc_transform_rows", "bbmpc_check_xform_rollout",
     "bbmpc_set_reward_source_params", "bbmpc_set_dynamics_source_params", "bbmpc_set_user_params", "bbmpc_compile_stats",
     "bbmpc_check_user_params",
+    "bbmpc_predict_trajectories", "bbmpc_predict_trajectories_dev", "bbmpc_trajectory_sq_error_dev",
+    "bbmpc_set_keep_plan", "bbmpc_get_plan",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -156,6 +158,11 @@ def _load():
     lib.bbmpc_set_user_params.argtypes = [vp, i32, vp, i64]
     lib.bbmpc_compile_stats.argtypes = [vp, ctypes.POINTER(i64)]
     lib.bbmpc_check_user_params.argtypes = [ctypes.c_char_p, i32, ctypes.c_char_p, i32, i32, i32]
+    lib.bbmpc_predict_trajectories.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.bbmpc_predict_trajectories_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.bbmpc_trajectory_sq_error_dev.argtypes = [vp, vp, vp, i32, i32, vp]
+    lib.bbmpc_set_keep_plan.argtypes = [vp, i32]
+    lib.bbmpc_get_plan.argtypes = [vp, vp]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

@@ -698,6 +698,7 @@ RowMlp Engine::row_mlp() const {
 void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_record_out, float* d_next_out) {
     REQUIRE(cfg.optimizer != BBMPC_OPT_NONE, BBMPC_E_STATE, "handle was created without an optimizer");
     const uint32_t step = step_counter++;
+    if (keep_plan) plan_ready = true;
     pending_cma_update.set = false;
     if (use_fused()) {
         dominant_kernel = "k_fused_pendulum";

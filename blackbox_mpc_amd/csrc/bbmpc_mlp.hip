@@ -4,6 +4,7 @@
 #define BBMPC_TU_MLP
 #include "engine.hpp"
 #include "engine_util.hpp"
+#include "kernels_mlp_traj.hpp"
 
 namespace bbmpc {
 
@@ -386,6 +387,34 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
     else hipLaunchKernelGGL(k_rollout_mlp<0>, grid, block, lds, stream, q);
     HIP_CHECK(hipGetLastError());
     prof_end();
+}
+
+// bbmpc_predict_trajectories on a learned model with a built-in reward: one launch of k_traj_mlp (kernels_mlp_traj.hpp),
+// 16 rows per workgroup whatever the network -- the generic kernel's coverage (<= 8 layers, width <= 512)
+void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out) {
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    MlpTrajArgs q;
+    memset(&q, 0, sizeof(q));
+    q.m = mlp;
+    for (int l = 0; l < mlp.n_layers; ++l) q.wp4[l] = d_wpack4[l].p;
+    q.nw = mlp_nw;
+    q.B = batch; q.Hq = horizon; q.S = S; q.U = U;
+    q.reward_kind = builtin_reward_kind();
+    q.fix_q1 = fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER) ? 1 : 0;
+    q.states = d_states;
+    q.seq = d_seq;
+    q.states_out = d_states_out;
+    q.rewards_out = d_rewards_out;
+    const size_t lds = (size_t)mlp_traj_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "trajectory prediction: the activation / partial-sum buffers of this network do not fit one CU's LDS");
+    bool ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    const void* fn = ext ? (const void*)k_traj_mlp<true> : (const void*)k_traj_mlp<false>;
+    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+    dim3 grid((batch + MLP_TP - 1) / MLP_TP), block(mlp_nw * 64);
+    if (ext) hipLaunchKernelGGL(k_traj_mlp<true>, grid, block, lds, stream, q);
+    else hipLaunchKernelGGL(k_traj_mlp<false>, grid, block, lds, stream, q);
+    HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace bbmpc

@@ -63,6 +63,7 @@ void Engine::set_user_source(int kind, const char* src, int nparams) {
     user_pp(kind).set = false;       // a new source starts without parameters
     f.cb = nullptr; f.cb_user = nullptr;
     user_rollout_stale = true;
+    user_traj_stale = true;
     user_xform_rollout_stale = true;
 }
 
@@ -76,6 +77,7 @@ void Engine::set_user_callback(int kind, bbmpc_rows_callback fn, void* user) {
     f.cb = fn;
     f.cb_user = fn ? user : nullptr;
     user_rollout_stale = true;
+    user_traj_stale = true;
     user_xform_rollout_stale = true;
 }
 
@@ -153,6 +155,7 @@ void Engine::set_transform_source(int kind, const char* src) {
     if (rebuild_dyn) load_program(user_dynamics, USER_KIND_DYNAMICS, dyn_code);
     if (inverse) {
         user_rollout_stale = true;
+    user_traj_stale = true;
         user_xform_rollout_stale = true;
         user_xform_rollout.release();
     }
@@ -329,6 +332,26 @@ void Engine::rollout_user_fused(int mode, bool pen, RolloutArgs& ra) {
     prof_begin();
     HIP_CHECK(hipModuleLaunchKernel(user_rollout.fn, (unsigned)((n_pop + bs - 1) / bs), (unsigned)A, 1, bs, 1, 1, 0, stream, args, nullptr));
     prof_end();
+}
+
+// bbmpc_predict_trajectories for analytic models with a HIP-source function on either side: rtc.hpp's bbmpc_user_traj, one
+// launch for all Hq steps.  Compiled on the handle's first prediction after the sources changed (one hiprtc run), so a
+// handle that never predicts compiles what it always did; parameter updates never recompile.
+void Engine::traj_user_fused(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out) {
+    if (cfg.reward == BBMPC_REW_USER) REQUIRE(user_reward.fn, BBMPC_E_STATE, "user reward: call bbmpc_set_reward_source before computing");
+    if (cfg.dynamics == BBMPC_DYN_USER) REQUIRE(user_dynamics.fn, BBMPC_E_STATE, "user dynamics: call bbmpc_set_dynamics_source before computing");
+    const float* rew_p = user_params_dev(USER_KIND_REWARD);
+    const float* dyn_p = user_params_dev(USER_KIND_DYNAMICS);
+    int rew_rpa = rew_p ? rows_per_agent(USER_KIND_REWARD, batch) : batch;      // (refuses B % A != 0 before anything is launched)
+    int dyn_rpa = dyn_p ? rows_per_agent(USER_KIND_DYNAMICS, batch) : batch;
+    if (user_traj_stale || !user_traj.fn) {
+        load_program(user_traj, PROG_TRAJ, compile_checked(PROG_TRAJ, user_program(), &rtc_compiles));
+        user_traj_stale = false;
+    }
+    int fq1 = (int)fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER);
+    void* args[] = {&batch, &horizon, &fq1, &d_states, &d_seq, &d_states_out, &d_rewards_out, &rew_p, &dyn_p, &rew_rpa, &dyn_rpa};
+    const unsigned bs = batch <= 16384 ? 64 : 256;
+    HIP_CHECK(hipModuleLaunchKernel(user_traj.fn, (unsigned)((batch + bs - 1) / bs), 1, 1, bs, 1, 1, 0, stream, args, nullptr));
 }
 
 // Learned MLP + user reward: the whole-horizon MFMA rollout (16-particle tiles) records the state after every step,
@@ -528,6 +551,9 @@ int bbmpc_check_user_params(const char* rew_src, int32_t rew_np, const char* dyn
         }
     }
     (void)bbmpc::compile_checked(bbmpc::PROG_ROLLOUT, d);
+    (void)bbmpc::compile_checked(bbmpc::PROG_TRAJ, d);                       // trajectory prediction, both sides the user's
+    if (rew_src) (void)bbmpc::compile_checked(bbmpc::PROG_TRAJ, r);
+    if (dyn_src) (void)bbmpc::compile_checked(bbmpc::PROG_TRAJ, b);
     API_END
 }
 
@@ -552,6 +578,7 @@ int bbmpc_check_user_rollout(int32_t dynamics, int32_t reward, const char* dyn_s
     if (reward == BBMPC_REW_USER) d.reward_src = rew_src;
     if (dynamics == BBMPC_DYN_USER) d.dynamics_src = dyn_src;
     (void)bbmpc::compile_checked(bbmpc::PROG_ROLLOUT, d);
+    (void)bbmpc::compile_checked(bbmpc::PROG_TRAJ, d);                       // ... and its trajectory-prediction twin
     API_END
 }
 

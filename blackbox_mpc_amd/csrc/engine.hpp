@@ -392,6 +392,22 @@ struct Engine {
     void evaluate_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_rew_out);
     void step_dev(const float* d_states, const float* d_actions, int astride, int batch, float* d_next, float* d_rew);
     void reward_dev(const float* d_cur, const float* d_next, const float* d_act, int batch, float* d_rew);
+    // open-loop trajectory prediction (bbmpc_traj.hip; the learned model's MFMA kernel is launched from bbmpc_mlp.hip):
+    // states [B,S], sequences [B,Hq,U] -> states_out [B,Hq,S], rewards_out [B,Hq] (either may be null)
+    void predict_trajectories_dev(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
+    void traj_mlp(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
+    void traj_user_fused(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);   // bbmpc_user.hip
+    UserFunction user_traj;            // rtc.hpp bbmpc_user_traj, built on the first prediction
+    bool user_traj_stale = true;
+    // plan readback (bbmpc_set_keep_plan / bbmpc_get_plan): the switch routes control steps as bbmpc_set_trace does, so the
+    // solution of every iteration stays in HBM
+    bool keep_plan = false;
+    bool plan_ready = false;           // a control step ran since the switch went on
+    void get_plan(float* actions_out);
+    void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
+    void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
+    DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging
+    DevBuf<double> tj_part;                          // squared-error partials [row blocks][Hq*S]
 
     void inject(int kind, const float* data, int64_t count);
     void dump_noise(int kind, int control_step, int iteration, float* out, int64_t count);

@@ -285,6 +285,60 @@ extern "C" __global__ void bbmpc_user_rollout(int n_pop, int A, int H, int Nst, 
 }
 )RTC";
 
+// Open-loop trajectory prediction (bbmpc_predict_trajectories) for analytic models with a user function on either side:
+// one lane per ROW of the batch, the Hq-step recurrence in registers as in bbmpc_user_rollout, but every row starts from
+// its own state, every next state goes to states_out [B,Hq,S] and every step reward to rewards_out [B,Hq] (either may be
+// null); no clip, no penalty, no NaN rule.  Row b belongs to agent b / rows_per_agent (parameterised sides), t is the step
+// inside the sequence.  Same defines as the rollout.  Compiled on the handle's first prediction, never before.
+static const char* const k_traj_text = R"RTC(
+extern "C" __global__ void bbmpc_user_traj(int batch, int Hq, int fix_q1, const float* __restrict__ states,
+                                           const float* __restrict__ seq, float* __restrict__ states_out,
+                                           float* __restrict__ rewards_out
+#if defined(BBMPC_REW_NPARAMS) || defined(BBMPC_DYN_NPARAMS)
+                                           , const float* __restrict__ rew_params, const float* __restrict__ dyn_params,
+                                           int rew_rows_per_agent, int dyn_rows_per_agent
+#endif
+                                           ) {
+    constexpr int S = BBMPC_S, U = BBMPC_U;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    float x[S + U], nx[S];
+    for (int i = 0; i < S; ++i) x[i] = states[(size_t)b * S + i];
+    for (int t = 0; t < Hq; ++t) {
+        for (int u = 0; u < U; ++u) x[S + u] = seq[((size_t)b * Hq + t) * U + u];
+#if BBMPC_DYN_KIND == 3
+        {
+            float d[S];
+            BBMPC_CALL_DYNAMICS(x, d, dyn_params, b / dyn_rows_per_agent, t);  // f(x, train=False) -> delta
+#ifdef BBMPC_XFORM
+            bbmpc_user_inverse_transform_targets(x, d, nx, S);                 // the raw output (:148-151)
+#else
+            for (int i = 0; i < S; ++i) nx[i] = d[i] + x[i];                     // transforms.py:34
+#endif
+        }
+#else
+        {
+            float ss[3] = {x[0], x[1], x[2]};
+            const float ac[1] = {x[3]};
+            const bbmpc::PendulumModel model{fix_q1 != 0};
+            (void)model.step(ss, ac);
+            nx[0] = ss[0]; nx[1] = ss[1]; nx[2] = ss[2];
+        }
+#endif
+        if (rewards_out) {
+#if BBMPC_REW_KIND == 3
+            rewards_out[(size_t)b * Hq + t] = BBMPC_CALL_REWARD(x, x + S, nx, rew_params, b / rew_rows_per_agent, t);
+#else
+            rewards_out[(size_t)b * Hq + t] = bbmpc::reward_generic(BBMPC_REW_KIND, fix_q1 != 0, x, x + S, nx, S, U);
+#endif
+        }
+        if (states_out)
+            for (int i = 0; i < S; ++i) states_out[((size_t)b * Hq + t) * S + i] = nx[i];
+        for (int i = 0; i < S; ++i) x[i] = nx[i];
+    }
+}
+)RTC";
+
 // Compile for gfx950; returns the code object.  Throws std::runtime_error with the compiler log on failure.
 inline std::vector<char> compile_rtc(const std::string& src, const char* name, const std::vector<std::string>& defines,
                                      bool with_engine_headers) {
@@ -322,7 +376,7 @@ inline std::vector<char> compile_rtc(const std::string& src, const char* name, c
 }
 
 // The programs, numbered so that the four row programs keep their USER_KIND_* value.
-constexpr int PROG_ROLLOUT = 5, PROG_MLP_XFORM_ROLLOUT = 6;
+constexpr int PROG_ROLLOUT = 5, PROG_MLP_XFORM_ROLLOUT = 6, PROG_TRAJ = 7;
 
 // What a program is built from; each form reads the fields it needs (a row program: its own source and side; dynamics rows
 // and the fused rollout: xform_src too; the learned-model transform rollout: xform_src, the reward side and act_ext).
@@ -340,17 +394,17 @@ struct UserProgram {
 // the kernel a loaded program is entered by (the reward rows program also has bbmpc_user_reward_traj)
 inline const char* program_kernel(int form) {
     static const char* const names[] = {"", "bbmpc_user_reward_rows", "bbmpc_user_dynamics_rows", "bbmpc_user_inverse_transform_rows",
-                                        "bbmpc_user_transform_rows", "bbmpc_user_rollout", "bbmpc_mlp_xform_rollout"};
+                                        "bbmpc_user_transform_rows", "bbmpc_user_rollout", "bbmpc_mlp_xform_rollout", "bbmpc_user_traj"};
     return names[form];
 }
 
 inline std::vector<std::string> program_defines(int form, const UserProgram& d) {
     std::vector<std::string> defs = {"-DBBMPC_S=" + std::to_string(d.S), "-DBBMPC_U=" + std::to_string(d.U)};
-    if (form == PROG_ROLLOUT) defs.push_back("-DBBMPC_DYN_KIND=" + std::to_string(d.dyn_kind));
-    if (form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT) defs.push_back("-DBBMPC_REW_KIND=" + std::to_string(d.rew_kind));
+    if (form == PROG_ROLLOUT || form == PROG_TRAJ) defs.push_back("-DBBMPC_DYN_KIND=" + std::to_string(d.dyn_kind));
+    if (form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT || form == PROG_TRAJ) defs.push_back("-DBBMPC_REW_KIND=" + std::to_string(d.rew_kind));
     if (form == PROG_MLP_XFORM_ROLLOUT) defs.push_back(std::string("-DBBMPC_ACT_EXT=") + (d.act_ext ? "1" : "0"));
-    const bool rew = form == USER_KIND_REWARD || form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT;
-    const bool dyn = form == USER_KIND_DYNAMICS || form == PROG_ROLLOUT;
+    const bool rew = form == USER_KIND_REWARD || form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT || form == PROG_TRAJ;
+    const bool dyn = form == USER_KIND_DYNAMICS || form == PROG_ROLLOUT || form == PROG_TRAJ;
     if (rew && d.rew_np > 0) defs.push_back("-DBBMPC_REW_NPARAMS=" + std::to_string(d.rew_np));
     if (dyn && d.dyn_np > 0) defs.push_back("-DBBMPC_DYN_NPARAMS=" + std::to_string(d.dyn_np));
     return defs;
@@ -359,12 +413,12 @@ inline std::vector<std::string> program_defines(int form, const UserProgram& d) 
 inline std::string program_source(int form, const UserProgram& d) {
     const std::string xform = d.xform_src.empty() ? std::string()
         : "// ---- user inverse target transform ---------------------------------------------------\n" + d.xform_src + "\n#define BBMPC_XFORM 1\n";
-    if (form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT) {
+    if (form == PROG_ROLLOUT || form == PROG_MLP_XFORM_ROLLOUT || form == PROG_TRAJ) {
         std::string s = "#include \"models.hpp\"\n";
         s += "// ---- user reward --------------------------------------------------------------------\n" + d.reward_src + "\n";
         if (form == PROG_MLP_XFORM_ROLLOUT) return s + xform + k_user_calls + "#define BBMPC_XFORM_KERNEL 1\n#include \"kernels_mlp_xform.hpp\"\n";
         s += "// ---- user dynamics ------------------------------------------------------------------\n" + d.dynamics_src + "\n";
-        return s + xform + k_user_calls + k_rollout_text;
+        return s + xform + k_user_calls + (form == PROG_TRAJ ? k_traj_text : k_rollout_text);
     }
     std::string s = "// ---- user source ------------------------------------------------------------------\n";
     s += UserProgram(d).own_source(form) + "\n";
@@ -379,7 +433,7 @@ inline std::string program_source(int form, const UserProgram& d) {
 // the code object of one program; only the two rollouts see the engine's headers (models.hpp, kernels_mlp_xform.hpp, ...)
 inline std::vector<char> compile_program(int form, const UserProgram& d) {
     static const char* const names[] = {"", "bbmpc_user_reward.hip", "bbmpc_user_dynamics.hip", "bbmpc_user_inverse_transform.hip",
-                                        "bbmpc_user_transform.hip", "bbmpc_user_rollout.hip", "bbmpc_mlp_xform_rollout.hip"};
+                                        "bbmpc_user_transform.hip", "bbmpc_user_rollout.hip", "bbmpc_mlp_xform_rollout.hip", "bbmpc_user_traj.hip"};
     return compile_rtc(program_source(form, d), names[form], program_defines(form, d), form >= PROG_ROLLOUT);
 }
 

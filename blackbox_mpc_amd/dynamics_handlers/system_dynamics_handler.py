@@ -12,6 +12,38 @@ import numpy as np
 _STATS = ("mean_states", "std_states", "mean_actions", "std_actions", "mean_targets", "std_targets")
 
 
+def multistep_windows(observations_trajectories, actions_trajectories, horizon, stride=1):
+    """Cut every window of `horizon` steps out of episodes in train()'s layout (observations [T+1, A, S], actions
+    [T, A, U] per episode): episode-major, then agent, then start t0 = 0, stride, 2 stride, ...; a window that would run
+    past the end of its episode is dropped (an episode shorter than the horizon gives none).  Returns
+    (start_states [B,S], actions [B,horizon,U], observed [B,horizon,S]) with observed[b, t] the recorded state t + 1 steps
+    after the window's start."""
+    horizon, stride = int(horizon), int(stride)
+    if horizon < 1 or stride < 1:
+        raise ValueError("horizon and stride must be >= 1")
+    starts, acts, obs_w = [], [], []
+    dim_s = dim_u = None
+    for obs, acs in zip(observations_trajectories, actions_trajectories):
+        obs, acs = np.asarray(obs, np.float32), np.asarray(acs, np.float32)
+        if obs.ndim != 3 or acs.ndim != 3 or obs.shape[0] != acs.shape[0] + 1 or obs.shape[1] != acs.shape[1]:
+            raise ValueError("an episode is observations [T+1, A, S] with actions [T, A, U], got %s and %s" % (obs.shape, acs.shape))
+        dim_s, dim_u = obs.shape[2], acs.shape[2]
+        steps = acs.shape[0]
+        t0 = np.arange(0, steps - horizon + 1, stride)
+        if t0.size == 0:
+            continue
+        idx = t0[:, None] + np.arange(horizon)[None, :]                 # [W, horizon]
+        for agent in range(acs.shape[1]):
+            starts.append(obs[t0, agent])
+            acts.append(acs[idx, agent])
+            obs_w.append(obs[idx + 1, agent])
+    if not starts:
+        return (np.zeros((0, dim_s or 0), np.float32), np.zeros((0, horizon, dim_u or 0), np.float32),
+                np.zeros((0, horizon, dim_s or 0), np.float32))
+    return (np.ascontiguousarray(np.concatenate(starts, axis=0)), np.ascontiguousarray(np.concatenate(acts, axis=0)),
+            np.ascontiguousarray(np.concatenate(obs_w, axis=0)))
+
+
 class SystemDynamicsHandler:
     def __init__(self, env_action_space, env_observation_space, dynamics_function=None, true_model=False,
                  is_normalized=True, log_dir=None, tf_writer=None, save_model_frequency=1, saved_model_dir=None,
@@ -43,6 +75,8 @@ class SystemDynamicsHandler:
         self._first_time = True
         self.training_loss = None
         self.validation_loss = None
+        self.multistep_rmse = None                       # (rmse [horizon, S], windows) of the last multistep_error call, on
+                                                         # whatever episodes it was given (the learning loops: the ones just trained on)
         if saved_model_dir is not None:
             self.load(saved_model_dir)
             self._first_time = False                     # :61 a loaded model keeps its statistics
@@ -205,3 +239,63 @@ class SystemDynamicsHandler:
         if self._training_iter % self._save_model_frequency == 0 and self._log_dir is not None:   # :212-241
             self.save(os.path.join(self._log_dir, "saved_model_%d" % self._refining_model_iter))
         return
+
+    # -- multi-step (open-loop) model error ---------------------------------------------------------------------------
+    def _multistep_engine(self):
+        """An evaluator-only engine of this handler's model, one per GPU, for states-only trajectory prediction.  A handle
+        has to be created with some reward kind: the pendulum's where dim_S allows it, else BBMPC_REW_USER without a
+        source.  Neither is ever evaluated -- multistep_error passes rewards_out = NULL, and for that the engine rolls a
+        learned model through its MFMA trajectory kernel whatever the reward kind is (bbmpc_traj.hip)."""
+        from .. import _lib as L
+        from ..engine import Engine
+        from ..trajectory_evaluators import deterministic as D
+        import torch
+        engines = self.__dict__.setdefault("_ms_engines", {})
+        device = torch.cuda.current_device()
+        eng = engines.get(device)
+        if eng is None:
+            dyn = D.dynamics_plugin(self)
+            dk = getattr(dyn, "_bbmpc_dynamics_kind", None)
+            eng = engines[device] = Engine(L.OPT_NONE, L.DYN_USER if dk is None else dk,
+                                           L.REW_PENDULUM if self._dim_S >= 3 else L.REW_USER, self._env_action_space.low,
+                                           self._env_action_space.high, dim_s=self._dim_S, num_agents=1, planning_horizon=1,
+                                           device=device)
+        if D.dynamics_stale(eng, self):
+            D.configure_dynamics(eng, self)
+        if eng._param_fns:
+            from ..utils.device_functions import sync_user_params
+            sync_user_params(eng)
+        return eng
+
+    def multistep_error(self, observations_trajectories, actions_trajectories, horizon, stride=1, max_rows=262144):
+        """Open-loop error of the model over `horizon` steps on episodes in train()'s layout: every window
+        (multistep_windows) is rolled out from its first observation under the recorded actions on the GPU
+        (bbmpc_predict_trajectories_dev) and compared with the recorded states there (bbmpc_trajectory_sq_error_dev, a
+        deterministic reduction).  Returns (rmse [horizon, dim_S] in state units, number of windows) and keeps it in
+        `multistep_rmse`.  A true model on its own data gives ~0."""
+        import torch
+        starts, acts, observed = multistep_windows(observations_trajectories, actions_trajectories, horizon, stride)
+        n, horizon = starts.shape[0], int(horizon)
+        if n == 0:
+            raise ValueError("multistep_error: no episode is %d steps long" % horizon)
+        if starts.shape[1] != self._dim_S or acts.shape[2] != self._dim_U:
+            raise ValueError("multistep_error: episodes of dim_S %d / dim_U %d for a handler of %d / %d"
+                             % (starts.shape[1], acts.shape[2], self._dim_S, self._dim_U))
+        eng = self._multistep_engine()
+        dev = torch.device("cuda", eng.device)
+        total = np.zeros(horizon * self._dim_S, np.float64)
+        for r0 in range(0, n, int(max_rows)):
+            r1 = min(n, r0 + int(max_rows))
+            d_s = torch.from_numpy(starts[r0:r1]).to(dev)
+            d_a = torch.from_numpy(acts[r0:r1]).to(dev)
+            d_o = torch.from_numpy(observed[r0:r1]).to(dev)
+            d_p = torch.empty_like(d_o)
+            d_e = torch.empty(horizon * self._dim_S, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)                                    # the copies above ran on torch's stream
+            eng.predict_trajectories_dev(d_s.data_ptr(), d_a.data_ptr(), r1 - r0, horizon, d_p.data_ptr(), 0)
+            eng.trajectory_sq_error_dev(d_p.data_ptr(), d_o.data_ptr(), r1 - r0, horizon, d_e.data_ptr())
+            eng.synchronize()
+            total += d_e.cpu().numpy()
+        rmse = np.sqrt(total / n).reshape(horizon, self._dim_S)
+        self.multistep_rmse = (rmse, n)
+        return rmse, n

@@ -344,6 +344,44 @@ class Engine:
                                      int(action_stride), int(batch), ctypes.c_void_p(d_next_states),
                                      ctypes.c_void_p(d_rewards or 0)))
 
+    def predict_trajectories(self, states, action_sequences, want_states=True, want_rewards=True):
+        """Open-loop prediction (bbmpc_predict_trajectories): states [B,S], action_sequences [B,Hq,U] ->
+        (states [B,Hq,S], rewards [B,Hq]); s_{t+1} = predict_next_state(s_t, a_t) from each row's own start, every state
+        and reward kept.  Hq is free of the handle's planning horizon.  An output that is not wanted comes back None."""
+        states, seq = L.f32c(states), L.f32c(action_sequences)
+        b = states.shape[0] if states.ndim == 2 else -1
+        # the C side copies b*S and b*Hq*U floats from these buffers: a wrong shape must not become an out-of-bounds read
+        if states.shape != (b, self.S) or seq.ndim != 3 or seq.shape[0] != b or seq.shape[2] != self.U:
+            raise ValueError("states [B,%d] and action_sequences [B,Hq,%d] expected, got %s, %s"
+                             % (self.S, self.U, states.shape, seq.shape))
+        hq = seq.shape[1]
+        out_s = np.empty((b, hq, self.S), np.float32) if want_states else None
+        out_r = np.empty((b, hq), np.float32) if want_rewards else None
+        L.check(L.lib.bbmpc_predict_trajectories(self._h, L.ptr(states), L.ptr(seq), b, hq, L.ptr(out_s), L.ptr(out_r)))
+        return out_s, out_r
+
+    def predict_trajectories_dev(self, d_states, d_action_sequences, batch, horizon, d_states_out=0, d_rewards_out=0):
+        """The same on device addresses, enqueued on the handle's stream (either output may be 0, not both)."""
+        L.check(L.lib.bbmpc_predict_trajectories_dev(self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_action_sequences),
+                                                     int(batch), int(horizon), ctypes.c_void_p(d_states_out or 0),
+                                                     ctypes.c_void_p(d_rewards_out or 0)))
+
+    def set_keep_plan(self, enabled=True):
+        """Opt-in switch of plan readback (bbmpc_set_keep_plan): the control steps that follow keep their solution in HBM
+        (the routing of set_trace: same results, slower paths).  Off by default."""
+        L.check(L.lib.bbmpc_set_keep_plan(self._h, int(bool(enabled))))
+
+    def get_plan(self):
+        """The action sequence [A,H,U] the last control step took its action from (bbmpc_get_plan)."""
+        out = np.empty((self.A, self.H, self.U), np.float32)
+        L.check(L.lib.bbmpc_get_plan(self._h, L.ptr(out)))
+        return out
+
+    def trajectory_sq_error_dev(self, d_predicted, d_observed, batch, horizon, d_sum_sq):
+        """d_sum_sq (float64 [Hq*S]) = sum over rows of (predicted - observed)^2, device arrays [B,Hq,S]; deterministic."""
+        L.check(L.lib.bbmpc_trajectory_sq_error_dev(self._h, ctypes.c_void_p(d_predicted), ctypes.c_void_p(d_observed),
+                                                    int(batch), int(horizon), ctypes.c_void_p(d_sum_sq)))
+
     # -- parity hooks ----------------------------------------------------------------------
     def inject_noise(self, kind, data):
         if data is None:

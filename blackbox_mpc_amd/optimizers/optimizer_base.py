@@ -66,6 +66,26 @@ class OptimizerBase:
         (action[A,U], next_state[A,S], rewards_of_next_state[A])   optimizer_base.py:55-95"""
         return self._require_engine().optimize(current_state, time_step, add_exploration_noise)
 
+    def keep_plan(self, enabled=True):
+        """Switch plan readback on (off): control steps then take the paths that keep their solution in HBM -- same
+        results, slower -- so that `plan` can read it.  Off by default."""
+        self._require_engine().set_keep_plan(enabled)
+
+    def plan(self, current_state):
+        """(actions [A,H,U], states [A,H,S], rewards [A,H]): the solution the LAST __call__ took its action from (the final
+        mean of CEM / PI2 / SPSA / CMA-ES, the best particle of RandomSearch / PSO), rolled out open loop from
+        `current_state` through the model.  Needs keep_plan(True) before that call."""
+        eng = self._require_engine()
+        try:
+            actions = eng.get_plan()
+        except L.BBMPCError as ex:
+            if ex.code == L.E_STATE:
+                raise RuntimeError("plan(): plan readback was not on during the last call -- switch it on with "
+                                   "optimizer.keep_plan(True) (MPCPolicy.keep_plan(True)) before calling the optimizer") from ex
+            raise
+        states, rewards = eng.predict_trajectories(np.asarray(current_state, np.float32), actions)
+        return actions, states, rewards
+
     def reset(self):
         if type(self)._engine_optimizer == L.OPT_NONE:
             raise Exception("reset function is not implemented yet")

@@ -55,6 +55,22 @@ class MPCPolicy(ModelBasedBasePolicy):
             return action[0], next_observations[0], rewards[0]
         return action, next_observations, rewards
 
+    def keep_plan(self, enabled=True):
+        """Switch plan readback on (off) for the `act` calls that follow (OptimizerBase.keep_plan)."""
+        self._optimizer.keep_plan(enabled)
+
+    def plan(self, observations):
+        """The plan the last `act` took its action from, rolled out from `observations`: (actions [A,H,U], states [A,H,S],
+        rewards [A,H]); a 1-D observation is un-batched as in `act` ([H,U], [H,S], [H])."""
+        observations = np.asarray(observations)
+        batched = observations
+        if observations.ndim == 1:
+            batched = np.tile(observations[None], (self._optimizer._num_agents, 1))
+        actions, states, rewards = self._optimizer.plan(batched)
+        if observations.ndim == 1:
+            return actions[0], states[0], rewards[0]
+        return actions, states, rewards
+
     def reset(self):
         self._optimizer.reset()
 

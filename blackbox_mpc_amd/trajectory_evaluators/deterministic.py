@@ -183,5 +183,12 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
         s = np.asarray(current_states, np.float32)
         return self._engine(self._one_step_agents(), 1).predict_next_state(s, np.asarray(current_actions, np.float32))
 
+    def predict_trajectories(self, current_states, action_sequences):
+        """current_states [B,S], action_sequences [B,Hq,U] -> (states [B,Hq,S], rewards [B,Hq]): predict_next_state and
+        evaluate_next_reward composed Hq times from each row's own start state (open loop, actions as given).  Served by
+        the one-step calls' engine -- the call's horizon is free of any planning horizon -- through the same staleness /
+        parameter-sync logic as __call__."""
+        return self._engine(self._one_step_agents(), 1).predict_trajectories(current_states, action_sequences)
+
     def evaluate_next_reward(self, current_states, next_states, current_actions):
         return self._engine(self._one_step_agents(), 1).evaluate_next_reward(current_states, next_states, current_actions)

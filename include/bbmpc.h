@@ -328,6 +328,40 @@ int bbmpc_evaluate_next_reward(bbmpc_handle h, const float* states, const float*
 int bbmpc_step_dev(bbmpc_handle h, const float* d_states, const float* d_actions, int32_t action_stride,
                    int32_t batch, float* d_next_states, float* d_rewards);
 
+/* Open-loop trajectory prediction: predict_next_state and evaluate_next_reward (deterministic.py:79-127) composed
+ * `horizon` times from every row's own start state, all of it kept.  states [B,S], action_sequences [B,Hq,U] ->
+ * states_out [B,Hq,S], rewards_out [B,Hq] (row major, row b first; either output may be NULL, not both).  With
+ * s_0 = states[b], for t = 0 .. Hq-1: s_{t+1} = predict_next_state(s_t, a_t) (process_input -> model -> process_output,
+ * an inverse target transform included), states_out[b,t] = s_{t+1}, rewards_out[b,t] = reward(s_t, a_t, s_{t+1}).
+ * Actions are used as given (no clip, no penalty, as bbmpc_evaluate) and per-step values are returned as computed: the
+ * evaluator's NaN -> -1e6 rule belongs to its sum.  Hq is independent of the handle's planning_horizon (1 <= Hq <=
+ * 4096); any handle serves, evaluator-only ones included.  Built-in pendulum and learned model + built-in reward: one
+ * kernel for all Hq steps; HIP-source dynamics / rewards on an analytic model: one run-time compiled kernel, built on the
+ * handle's first prediction (one hiprtc run, counted by bbmpc_compile_stats; never on a handle that does not predict);
+ * torch callbacks, and a learned model with an inverse target transform or a HIP-source reward, run their row kernels /
+ * callbacks step by step, compiling nothing.  Runtime parameters: row b belongs to agent b / (B / A)
+ * (B % A != 0 with per-agent parameters: BBMPC_E_INVALID) and the function sees t = the step inside the sequence.
+ * BBMPC_E_INVALID: batch < 1, horizon outside [1, 4096], both outputs NULL; BBMPC_E_STATE: weights, sources or
+ * parameters not set.  The host variant is synchronous; _dev enqueues on the handle's stream. */
+int bbmpc_predict_trajectories(bbmpc_handle h, const float* states, const float* action_sequences, int32_t batch,
+                               int32_t horizon, float* states_out, float* rewards_out);
+int bbmpc_predict_trajectories_dev(bbmpc_handle h, const float* d_states, const float* d_action_sequences, int32_t batch,
+                                   int32_t horizon, float* d_states_out, float* d_rewards_out);
+/* Plan readback.  bbmpc_set_keep_plan(h, 1) makes the control steps that follow keep their solution in HBM: it routes
+ * them as bbmpc_set_trace does (one launch per iteration instead of the resident / fused / graph-replayed forms, which
+ * keep it in registers or LDS; same results, slower) -- off by default, and with it off nothing changes.
+ * bbmpc_get_plan writes the action sequence [A,H,U] the LAST control step took its action from: the final mean (CEM, PI2,
+ * SPSA, CMA-ES; before the warm-start shift), PSO's global best, RandomSearch's best particle; actions[a,0] is the action
+ * that step returned without exploration noise.  BBMPC_E_STATE when the switch was not on during that step.  Roll it out
+ * with bbmpc_predict_trajectories for the predicted states and rewards (OptimizerBase.plan / MPCPolicy.plan do). */
+int bbmpc_set_keep_plan(bbmpc_handle h, int32_t enabled);
+int bbmpc_get_plan(bbmpc_handle h, float* actions);
+/* Multi-step model error: d_sum_sq[t * S + s] = sum over the B rows of (predicted[b,t,s] - observed[b,t,s])^2, device
+ * arrays [B,Hq,S], the sums in float64 [Hq * S].  Two-stage reduction in a fixed order, no atomics: equal inputs give
+ * equal bits.  On the handle's stream.  No counterpart in the reference (its train() reports a one-step loss only). */
+int bbmpc_trajectory_sq_error_dev(bbmpc_handle h, const float* d_predicted, const float* d_observed, int32_t batch,
+                                  int32_t horizon, double* d_sum_sq);
+
 /* Closed-loop episode on the device -- counterpart of utils/rollouts.py:60-139 (_sample) with the engine's own
  * model as the environment: T control steps, each feeding its predicted next state back as the next observation;
  * nothing leaves HBM until the end.  records_out is [T][A][U+S+1] (action | next_state | reward) on the host.
