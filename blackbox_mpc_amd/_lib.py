@@ -28,6 +28,8 @@ STRICT_MATH = 1 << 9
 NOISE_TRUNC_NORMAL, NOISE_UNIFORM, NOISE_RADEMACHER, NOISE_NORMAL, NOISE_PSO_SCALARS = 1, 2, 3, 4, 5
 NOISE_PSO_RESEED_TRUNC, NOISE_PSO_RESEED_UNIFORM, NOISE_PSO_RESET_POS, NOISE_PSO_RESET_VEL = 6, 7, 8, 9
 NOISE_EXPLORATION = 10
+NOISE_PROCESS = 11                                      # [iters][A,P,H,S] N(0,1): the particle evaluator's process noise
+MAX_PARTICLES = 64
 TRACE_REWARDS, TRACE_MEAN, TRACE_VAR, TRACE_ELITES, TRACE_SAMPLES = 1, 2, 3, 4, 5
 TRACE_CMA_B, TRACE_CMA_C, TRACE_CMA_D, TRACE_CMA_SVD_STATS = 6, 7, 8, 9
 
@@ -79,6 +81,7 @@ SYMBOLS = [
     "bbmpc_check_user_params",
     "bbmpc_predict_trajectories", "bbmpc_predict_trajectories_dev", "bbmpc_trajectory_sq_error_dev",
     "bbmpc_set_keep_plan", "bbmpc_get_plan",
+    "bbmpc_set_particles", "bbmpc_evaluate_particles", "bbmpc_evaluate_particles_dev",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -163,6 +166,9 @@ def _load():
     lib.bbmpc_trajectory_sq_error_dev.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.bbmpc_set_keep_plan.argtypes = [vp, i32]
     lib.bbmpc_get_plan.argtypes = [vp, vp]
+    lib.bbmpc_set_particles.argtypes = [vp, i32, vp, ctypes.c_float]
+    lib.bbmpc_evaluate_particles.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.bbmpc_evaluate_particles_dev.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

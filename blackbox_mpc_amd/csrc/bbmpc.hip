@@ -548,6 +548,10 @@ const float* Engine::dense_actions(const float* d_actions, int astride, int batc
 }
 
 void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
+    if (particles_on()) {                                 // bbmpc_set_particles: noisy rollouts + aggregate (bbmpc_particles.hip)
+        rollout_particles(mode, pen, ra, nullptr, 0);
+        return;
+    }
     if (user_path()) {
         if (user_callbacks()) {                           // a host callback per planning step: step-wise only
             dominant_kernel = "stepwise(user callback)";
@@ -788,7 +792,7 @@ void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_recor
             // (no BBMPC_FIX_Q2_CEM_WARM_START): prev_mean, var0 and the sigma they give are constants, so from the second
             // control step on k_dist_init is skipped as for PI2 below -- the first rollout samples from (prev_mean, sigma0)
             // and reads the state from the pinned buffer, the first refit smooths against (prev_mean, var0)
-            const bool cem_skip = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on &&
+            const bool cem_skip = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() &&
                                   iters >= 1 && k <= 64 && !sw.refit_v1 && !fix(BBMPC_FIX_Q2_CEM_WARM_START) && cem_sigma0_ready &&
                                   pi2_copy_seen && stage_state_src != nullptr;
             const float* cem_pinned = nullptr;
@@ -901,7 +905,7 @@ void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_recor
             // launch of its own in front of a 360 us control step) has nothing left to do -- PI2 never changes sigma, the
             // first rollout samples around prev_mean directly, the refit writes every element of the mean, and the first
             // rollout reads the state from the pinned buffer itself (its workgroup 0 stores it for the later launches).
-            const bool skip_init = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on &&
+            const bool skip_init = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() &&
                                    iters >= 1 && pi2_dist_ready && pi2_copy_seen && stage_state_src != nullptr;
             const float* pinned_state = nullptr;
             last_step_steady = skip_init;
@@ -1014,6 +1018,7 @@ void Engine::optimize_spsa(RolloutArgs& ra, uint32_t step) {
         const float ak = cfg.spsa_a / (float)pow((double)((tf + 1.0f) + big_a), (double)cfg.spsa_alpha);   // :69
         const float ck = cfg.spsa_c / (float)pow((double)(tf + 1.0f), (double)cfg.spsa_gamma);             // :70
         OptArgs oa = opt_args(step, (uint32_t)it);
+        if (particles_on()) ra.iter = (uint32_t)it;       // the process noise is drawn per iteration
         want_lds((const void*)k_refit_spsa, (size_t)Nst * 4);
         // candidates -> the two rollouts -> row sums of this handle's perturbation pairs (part != null: sharded population)
         auto shard_pass = [&](float* part) {
@@ -1092,6 +1097,7 @@ void Engine::optimize_pso(RolloutArgs& ra, uint32_t step) {
     }
     for (int it = 0; it < iters; ++it) {
         OptArgs oa = opt_args(step, (uint32_t)it);
+        if (particles_on()) ra.iter = (uint32_t)it;       // the process noise is drawn per iteration
         for (int r = 0; r < shards_here; ++r) {
             const PsoState pr = pso_state(r);
             if (ps_loopback > 1) oa.pop_offset = r * N;
@@ -1141,6 +1147,10 @@ void Engine::evaluate_dev(const float* d_state_in, const float* d_seq, int n_pop
     // rewards come back in the reference layout [n_pop, A]; the kernel writes [A][stride] so use a scratch
     // and a strided 2D copy (A is small).
     REQUIRE(n_pop >= 1, BBMPC_E_INVALID, "n_pop must be >= 1");
+    if (particles_on()) {                                 // bbmpc_set_particles: the scores
+        evaluate_particles_dev(d_state_in, d_seq, n_pop, d_rew_out, nullptr);
+        return;
+    }
     const int st = ((n_pop + 63) / 64) * 64;
     if (d_eval_rew.n < (size_t)A * st) d_eval_rew.alloc((size_t)A * st);
     RolloutArgs ra;
@@ -1260,6 +1270,14 @@ void Engine::inject(int kind, const float* data, int64_t count) {
             HIP_CHECK(hipMemcpy(b.p, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
             break;
         }
+        case BBMPC_NOISE_PROCESS: {
+            REQUIRE(particles_on(), BBMPC_E_STATE, "process noise: call bbmpc_set_particles first (the layout depends on num_particles)");
+            REQUIRE(count == (int64_t)A * part_P * H * S * std::max(iters, 1), BBMPC_E_INVALID, "process noise must be [iters][A,P,H,S]");
+            auto& b = inj[kind];
+            b.alloc((size_t)count);
+            HIP_CHECK(hipMemcpy(b.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
+            break;
+        }
         case BBMPC_NOISE_EXPLORATION: {
             REQUIRE(count == (int64_t)A * U, BBMPC_E_INVALID, "exploration noise must be [A,U]");
             auto& b = inj[kind];
@@ -1302,6 +1320,10 @@ __global__ void k_dump_pso_scalars(OptArgs p, float* out) {
 
 void Engine::dump_noise(int kind, int control_step, int iteration, float* out, int64_t count) {
     int n = auto_split > 1 ? N * auto_split : N, a = A, hu = HU;       // (draws are keyed by the global particle)
+    if (kind == BBMPC_NOISE_PROCESS) {
+        dump_process_noise(control_step, iteration, out, count);
+        return;
+    }
     RngKey kk = key((uint32_t)control_step);
     if (kind == BBMPC_NOISE_PSO_SCALARS) {
         REQUIRE(count == 2, BBMPC_E_INVALID, "dump_noise: PSO scalars are [2] per (control step, iteration)");
@@ -1675,7 +1697,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                 // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
                 // replayed as a graph (engine.hpp: step_graph)
                 const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&
-                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && e.stream == e.own_stream && !e.any_injected();
+                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && e.stream == e.own_stream && !e.any_injected();
                 const uint64_t sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
                 bool replayed = false;
                 if (graph_ok && e.step_graph && e.step_graph_sig == sig) {

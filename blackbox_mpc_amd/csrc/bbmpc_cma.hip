@@ -146,13 +146,14 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
     const size_t gnn = (size_t)G * n * n;
     for (int it = 0; it < iters; ++it) {
         CmaArgs q = cma_args(step, (uint32_t)it);
+        if (particles_on()) ra.iter = (uint32_t)it;       // the process noise is drawn per iteration
         q.inj = inj_n ? inj_n + inj_stride * it : nullptr;
         const int kp = (k + 3) & ~3;
         const size_t lds = (size_t)(Nst + TOPK_HIST_WORDS + 2 * kp) * 4;
         const bool small3 = sw.cma_small3 && cma_use_eigh_small() && !pop_sharded();
         if (small3) {
             // n <= 32: sample | roll out | update, three launches per iteration (kernels_eigh_small.hpp)
-            const bool write_back = trace_on || user_path();
+            const bool write_back = trace_on || user_path() || particles_on();
             // the analytic pendulum, one agent per instance: the rollouts ride on the sampling launch
             const bool roll_in = !write_back && cfg.dynamics == BBMPC_DYN_PENDULUM && cfg.reward == BBMPC_REW_PENDULUM && cma_G == A && U == 1 && S == 3;
             if (roll_in) {
@@ -193,7 +194,7 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
             // the clipped candidates go back to the buffer only where somebody reads them whole (the parity trace, the sharded
             // selection, user functions): the path update clips the k elites it reads itself, and the write-back is 9.6 MB of
             // strided stores per launch at config 5's shape
-            const bool write_back = trace_on || pop_sharded() || user_path();
+            const bool write_back = trace_on || pop_sharded() || user_path() || particles_on();
             ra.cand = d_cand_a.p; ra.samples = write_back ? d_cand_a.p : nullptr; ra.rewards = d_rewards.p; ra.penalty_out = nullptr;
             launch_rollout(SRC_BUF, true, ra);                          // clip + penalty (cma_es.py:147-157)
             if (part || !merge_sp) hipLaunchKernelGGL(k_cma_select, dim3(G), dim3(REFIT_THREADS), lds, stream, q, part);
@@ -376,7 +377,7 @@ void Engine::launch_pending_cma_update(const FinalArgs& fa) {
 bool Engine::use_fused_cma() const {
     if (cfg.optimizer != BBMPC_OPT_CMAES || cfg.dynamics != BBMPC_DYN_PENDULUM || cfg.reward != BBMPC_REW_PENDULUM) return false;
     // opt-in: measured no faster than the per-iteration kernels (both are bound by the Jacobi sweeps)
-    if (!sw.cma_fused || fused_mode == 0 || trace_on || pop_sharded()) return false;      // the parity trace is captured between the per-iteration kernels
+    if (!sw.cma_fused || fused_mode == 0 || trace_on || pop_sharded() || particles_on()) return false;      // the parity trace is captured between the per-iteration kernels
     if (sw.cma_svd_v1 || sw.cma_svd_rounds || sw.cma_svd_general) return false;
     return cma_G == A && cma_n <= 64 && N <= 1024 && k <= 1024;
 }

@@ -15,6 +15,7 @@ void bbmpc_tu_fused_upload_tnq(const float2* table) { tnq_upload(table); }
 bool Engine::use_fused() const {
     if (cfg.dynamics != BBMPC_DYN_PENDULUM || cfg.reward != BBMPC_REW_PENDULUM) return false;
     if (pop_sharded()) return false;            // the refit is split around a collective: per-iteration kernels
+    if (particles_on()) return false;           // bbmpc_set_particles: the noisy rollouts are kernels of their own
     if (cfg.optimizer == BBMPC_OPT_SPSA) {
         if (iters > FUSED_MAX_SPSA_ITERS) return false;
     } else if (cfg.optimizer != BBMPC_OPT_RANDOM_SEARCH && cfg.optimizer != BBMPC_OPT_CEM && cfg.optimizer != BBMPC_OPT_PI2) {
@@ -289,7 +290,7 @@ static size_t fused_pso_lds(int H, int Nst) { return ((size_t)2 * H * Nst + ((H 
 
 bool Engine::use_fused_pso() const {
     if (cfg.dynamics != BBMPC_DYN_PENDULUM || cfg.reward != BBMPC_REW_PENDULUM || cfg.optimizer != BBMPC_OPT_PSO || U != 1) return false;
-    if (fused_mode == 0 || pop_sharded()) return false;           // a sharded swarm exchanges its bests every iteration
+    if (fused_mode == 0 || pop_sharded() || particles_on()) return false;           // a sharded swarm exchanges its bests every iteration
     return N <= 1024 && fused_pso_lds(H, Nst) <= 160 * 1024;
 }
 

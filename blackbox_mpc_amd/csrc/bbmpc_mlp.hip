@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "engine_util.hpp"
 #include "kernels_mlp_traj.hpp"
+#include "kernels_mlp_particles.hpp"
 
 namespace bbmpc {
 
@@ -414,6 +415,33 @@ void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int 
     dim3 grid((batch + MLP_TP - 1) / MLP_TP), block(mlp_nw * 64);
     if (ext) hipLaunchKernelGGL(k_traj_mlp<true>, grid, block, lds, stream, q);
     else hipLaunchKernelGGL(k_traj_mlp<false>, grid, block, lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
+// Particle rollouts of a learned model with a built-in reward (bbmpc_set_particles): one launch of k_rollout_mlp_particles,
+// 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp, always fp32
+void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    MlpParticleArgs q;
+    memset(&q, 0, sizeof(q));
+    q.m = mlp;
+    for (int l = 0; l < mlp.n_layers; ++l) q.wp4[l] = d_wpack4[l].p;
+    q.nw = mlp_nw;
+    q.p = pa;
+    const size_t lds = (size_t)mlp_traj_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the activation / partial-sum buffers of this network do not fit one CU's LDS");
+    bool ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    const void* fn = ext ? (const void*)k_rollout_mlp_particles<true> : (const void*)k_rollout_mlp_particles<false>;
+    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+    const long rows = (long)pa.n_pop * pa.P;
+    // (the kernel addresses its action source and the noise with 32-bit offsets)
+    const long act_elems = pa.from_ref ? (long)pa.n_pop * A * pa.HU : (long)A * pa.HU * pa.Nst;
+    REQUIRE(act_elems < (1L << 31) && (long)A * pa.P * pa.H * S < (1L << 31), BBMPC_E_UNSUPPORTED,
+            "particle rollout: more than 2^31 action or noise elements per launch");
+    dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), A), block(mlp_nw * 64);
+    if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles<true>, grid, block, lds, stream, q);
+    else hipLaunchKernelGGL(k_rollout_mlp_particles<false>, grid, block, lds, stream, q);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -1,0 +1,196 @@
+// Particle trajectory evaluator (bbmpc_set_particles, bbmpc_evaluate_particles; kernels_particles.hpp): the switch, the
+// process-noise buffer, the launch sequence  candidates -> noisy rollouts -> aggregate  that Engine::launch_rollout takes
+// while the switch is on, and the ABI.  The learned model's rollout kernel is launched from bbmpc_mlp.hip.
+#include <cmath>
+
+#include "abi_util.hpp"
+#include "kernels_particles.hpp"
+
+namespace bbmpc {
+
+void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
+    REQUIRE(num_particles >= 0 && num_particles <= PARTICLES_MAX, BBMPC_E_INVALID, "num_particles must be in [0, 64]");
+    invalidate_step_graph();
+    if (num_particles == 0) {
+        part_P = 0;
+        pnoise_valid = false;
+        return;
+    }
+    REQUIRE(sigma != nullptr, BBMPC_E_INVALID, "null pointer argument: sigma");
+    for (int s = 0; s < S; ++s)
+        REQUIRE(std::isfinite(sigma[s]) && sigma[s] >= 0.0f, BBMPC_E_INVALID, "process noise sigma must be finite and >= 0");
+    REQUIRE(std::isfinite(kappa), BBMPC_E_INVALID, "risk_kappa must be finite");
+    REQUIRE(cfg.reward != BBMPC_REW_USER && cfg.dynamics != BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
+            "particles with a HIP-source or callback reward / dynamics: the noisy rollouts are built for the built-in models and rewards");
+    REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED, "particles with an inverse target transform: the noise is added to next = dev + state");
+    REQUIRE(!pop_sharded() && cfg.population_global <= N, BBMPC_E_UNSUPPORTED,
+            "particles with a sharded population: the shards would have to exchange per-particle returns");
+    REQUIRE((long)N * num_particles <= 32768, BBMPC_E_UNSUPPORTED, "particles: population_size * num_particles must not exceed 32768");
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (num_particles != part_P) inj.erase(BBMPC_NOISE_PROCESS);       // (its layout depends on P)
+    if (d_psigma.n < (size_t)S) d_psigma.alloc((size_t)S);
+    HIP_CHECK(hipMemcpy(d_psigma.p, sigma, (size_t)S * 4, hipMemcpyHostToDevice));
+    const size_t ne = (size_t)A * num_particles * H * S;
+    if (d_pnoise.n < ne) d_pnoise.alloc(ne);
+    part_P = num_particles;
+    part_kappa = kappa;
+    pnoise_valid = false;
+}
+
+// eps [A][P][H][S] of (control step, iteration): the injected tensor, or the handle's own draws, generated once per
+// (step, iteration) however many rollouts share them (SPSA's plus and minus candidates do).
+const float* Engine::process_noise(uint32_t step, uint32_t iter) {
+    const size_t ne = (size_t)A * part_P * H * S;
+    if (const float* in = injected(BBMPC_NOISE_PROCESS)) return in + ne * std::min<size_t>(iter, (size_t)std::max(iters, 1) - 1);
+    if (pnoise_valid && pnoise_step == step && pnoise_iter == iter) return d_pnoise.p;
+    RngKey kk = key(step);
+    kk.q_per_agent = (uint32_t)((H * S + 3) / 4);
+    kk.step_src = nullptr;
+    const int blocks = A * part_P * (int)kk.q_per_agent;
+    hipLaunchKernelGGL(k_gen_process_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, iter, A, part_P, H * S, cfg.agent_offset,
+                       d_pnoise.p);
+    HIP_CHECK(hipGetLastError());
+    pnoise_valid = true; pnoise_step = step; pnoise_iter = iter;
+    return d_pnoise.p;
+}
+
+void Engine::dump_process_noise(int control_step, int iteration, float* out, int64_t count) {
+    REQUIRE(particles_on(), BBMPC_E_STATE, "dump_noise: process noise needs bbmpc_set_particles first");
+    const int64_t total = (int64_t)A * part_P * H * S;
+    REQUIRE(count == total, BBMPC_E_INVALID, "dump_noise: process noise is [A, P, H, S]");
+    RngKey kk = key((uint32_t)control_step);
+    kk.q_per_agent = (uint32_t)((H * S + 3) / 4);
+    kk.step_src = nullptr;
+    DevBuf<float> tmp;
+    tmp.alloc((size_t)total);
+    const int blocks = A * part_P * (int)kk.q_per_agent;
+    hipLaunchKernelGGL(k_gen_process_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, (uint32_t)iteration, A, part_P, H * S,
+                       cfg.agent_offset, tmp.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, tmp.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// launch_rollout with particles on: the candidates into the sample buffer (as the user-function paths draw them), the
+// noisy rollouts of every (candidate, particle) row, the aggregate into ra.rewards.  d_returns: where the per-particle
+// returns [A][returns_stride] go (null: the handle's own buffer).
+void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_returns, int returns_stride) {
+    REQUIRE(!user_path(), BBMPC_E_UNSUPPORTED, "particles with user-supplied functions or an inverse target transform");
+    const int P = part_P;
+    if (!d_returns) {
+        returns_stride = ra.Nst * P;
+        if (d_preturns.n < (size_t)A * returns_stride) d_preturns.alloc((size_t)A * returns_stride);
+        d_returns = d_preturns.p;
+    }
+    REQUIRE(returns_stride >= ra.n_pop * P, BBMPC_E_INVALID, "internal: particle returns stride");
+    draw_candidates(mode, ra);
+    ParticleArgs q;
+    memset(&q, 0, sizeof(q));
+    q.n_pop = ra.n_pop; q.P = P; q.A = A; q.H = ra.H; q.U = U; q.S = S; q.HU = ra.HU; q.Nst = ra.Nst; q.RS = returns_stride;
+    q.from_ref = mode == SRC_REF ? 1 : 0;
+    q.pen = pen ? 1 : 0;
+    q.fix_q1 = ra.fix_q1; q.reward_kind = ra.reward_kind;
+    q.state = ra.state; q.seq = ra.seq;
+    q.cand = mode == SRC_BUF ? ra.cand : ra.samples;
+    q.lo = ra.lo; q.hi = ra.hi;
+    q.sigma = d_psigma.p;
+    q.pnoise = process_noise(ra.key.step, ra.iter);
+    q.returns = d_returns;
+    q.samples = (pen && mode != SRC_REF) ? ra.samples : nullptr;          // the feasible candidates go back
+    q.rewards = ra.rewards;
+    q.penalty_out = ra.penalty_out;
+    REQUIRE(ra.H == H, BBMPC_E_INVALID, "internal: particle rollout horizon");
+    const long rows = (long)ra.n_pop * P;
+    dominant_inst[0] = 0;
+    prof_begin();
+    if (cfg.dynamics == BBMPC_DYN_MLP) {
+        dominant_kernel = "k_rollout_mlp_particles";
+        launch_rollout_mlp_particles(q);
+    } else {
+        dominant_kernel = "k_rollout_pendulum_particles";
+        // few rows -> one wave per workgroup so every wave gets its own SIMD; many -> 256-thread workgroups
+        const int bs = (rows * A <= 16384) ? 64 : 256;
+        hipLaunchKernelGGL(k_rollout_pendulum_particles, dim3((unsigned)((rows + bs - 1) / bs), A), dim3(bs), 0, stream, q);
+        HIP_CHECK(hipGetLastError());
+    }
+    prof_end();
+    hipLaunchKernelGGL(k_particle_aggregate, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, q, part_kappa);
+    HIP_CHECK(hipGetLastError());
+}
+
+// scores [n_pop, A] and (optional) returns [n_pop, P, A] in the reference's layouts, from the caller's sequences
+void Engine::evaluate_particles_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_scores, float* d_ret_out) {
+    REQUIRE(particles_on(), BBMPC_E_STATE, "particles are off: call bbmpc_set_particles first");
+    REQUIRE(n_pop >= 1, BBMPC_E_INVALID, "n_pop must be >= 1");
+    REQUIRE((long)n_pop * part_P <= (1L << 24), BBMPC_E_UNSUPPORTED, "particles: n_pop * num_particles must not exceed 2^24 per call");
+    const int P = part_P;
+    const int st = ((n_pop + 63) / 64) * 64;
+    if (d_eval_rew.n < (size_t)A * st) d_eval_rew.alloc((size_t)A * st);
+    RolloutArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.n_pop = n_pop; ra.A = A; ra.H = H; ra.U = U; ra.S = S; ra.HU = HU; ra.Nst = st;
+    ra.agent_offset = cfg.agent_offset;
+    ra.fix_q1 = fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER);
+    ra.reward_kind = builtin_reward_kind();
+    ra.state = d_state_in;
+    ra.seq = d_seq;
+    ra.lo = d_lo.p; ra.hi = d_hi.p;
+    ra.rewards = d_eval_rew.p;
+    ra.key = key(step_counter);                   // the handle's current control step, iteration 0
+    ra.iter = 0;
+    rollout_particles(SRC_REF, false, ra, nullptr, 0);
+    for (int a = 0; a < A; ++a) {
+        // [A][st] -> [n_pop][A] and [A][st * P] (row n * P + p) -> [n_pop][P][A]: strided copies per agent (A is small)
+        HIP_CHECK(hipMemcpy2DAsync(d_scores + a, (size_t)A * 4, d_eval_rew.p + (size_t)a * st, 4, 4, n_pop, hipMemcpyDeviceToDevice, stream));
+        if (d_ret_out)
+            HIP_CHECK(hipMemcpy2DAsync(d_ret_out + a, (size_t)A * 4, d_preturns.p + (size_t)a * st * P, 4, 4, (size_t)n_pop * P,
+                                       hipMemcpyDeviceToDevice, stream));
+    }
+}
+
+}  // namespace bbmpc
+
+extern "C" {
+
+int bbmpc_set_particles(bbmpc_handle h, int32_t num_particles, const float* sigma, float risk_kappa) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_particles(num_particles, sigma, risk_kappa);
+    API_END
+}
+
+int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const float* d_seq, int32_t n_pop, float* d_scores,
+                                 float* d_returns) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_state);
+    CHECK_PTR(d_seq);
+    CHECK_PTR(d_scores);
+    h->e->evaluate_particles_dev(d_state, d_seq, n_pop, d_scores, d_returns);
+    API_END
+}
+
+int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* seq, int32_t n_pop, float* scores, float* returns) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(state);
+    CHECK_PTR(seq);
+    CHECK_PTR(scores);
+    Engine& e = *h->e;
+    if (!e.particles_on()) throw HipError(BBMPC_E_STATE, "particles are off: call bbmpc_set_particles first");
+    if (n_pop < 1) throw HipError(BBMPC_E_INVALID, "n_pop must be >= 1");
+    const size_t nseq = (size_t)n_pop * e.A * e.HU, nsc = (size_t)n_pop * e.A, nret = returns ? nsc * e.part_P : 0;
+    if (e.d_pe_io.n < nseq + nsc + nret) e.d_pe_io.alloc(nseq + nsc + nret);
+    float* dseq = e.d_pe_io.p;
+    float* dsc = dseq + nseq;
+    float* dret = returns ? dsc + nsc : nullptr;
+    HIP_CHECK(hipMemcpyAsync(e.d_state.p, state, (size_t)e.A * e.S * 4, hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(dseq, seq, nseq * 4, hipMemcpyHostToDevice, e.stream));
+    e.evaluate_particles_dev(e.d_state.p, dseq, n_pop, dsc, dret);
+    HIP_CHECK(hipMemcpyAsync(scores, dsc, nsc * 4, hipMemcpyDeviceToHost, e.stream));
+    if (returns) HIP_CHECK(hipMemcpyAsync(returns, dret, nret * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
+
+}  // extern "C"

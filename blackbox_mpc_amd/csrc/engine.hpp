@@ -35,6 +35,8 @@
 
 namespace bbmpc {
 
+struct ParticleArgs;       // kernels_particles.hpp
+
 struct HipError : std::runtime_error {
     int code;
     HipError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
@@ -404,6 +406,21 @@ struct Engine {
     bool keep_plan = false;
     bool plan_ready = false;           // a control step ran since the switch went on
     void get_plan(float* actions_out);
+    // particle trajectory evaluator (bbmpc_set_particles; bbmpc_particles.hip, kernels_particles.hpp): P noisy rollouts per
+    // candidate reduced to mean - kappa * std.  While it is on, control steps are routed as bbmpc_set_trace routes them
+    // (one launch sequence per iteration: no resident, fused or graph-replayed form) and launch_rollout scores through it.
+    int part_P = 0;
+    float part_kappa = 0.0f;
+    DevBuf<float> d_psigma, d_pnoise, d_preturns, d_pe_io;   // sigma [S] | eps [A][P][H][S] | returns [A][Nst * P] | host-call staging
+    bool pnoise_valid = false;         // d_pnoise holds the draws of (pnoise_step, pnoise_iter)
+    uint32_t pnoise_step = 0, pnoise_iter = 0;
+    bool particles_on() const { return part_P > 0; }
+    void set_particles(int num_particles, const float* sigma, float kappa);
+    const float* process_noise(uint32_t step, uint32_t iter);
+    void dump_process_noise(int control_step, int iteration, float* out, int64_t count);
+    void rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_returns, int returns_stride);
+    void launch_rollout_mlp_particles(const ParticleArgs& pa);                 // bbmpc_mlp.hip
+    void evaluate_particles_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_scores, float* d_returns);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
     DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging

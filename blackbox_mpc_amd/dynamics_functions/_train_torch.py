@@ -225,5 +225,16 @@ class DenseTrainer:
                 vl[e] = float((d * d).mean(dim=1).mean().item())    # mean of per-batch MSEs (:276-284)
         return tl, vl
 
+    def residual_rms(self, val_in, val_out):
+        """Per-output RMS of (target - prediction) on the given rows, on the training device; None without rows."""
+        torch = self.torch
+        if len(val_in) == 0:
+            return None
+        vin = torch.as_tensor(np.ascontiguousarray(val_in, np.float32)).to(self.dev)
+        vout = torch.as_tensor(np.ascontiguousarray(val_out, np.float32)).to(self.dev)
+        with torch.no_grad():
+            d = vout - self.forward(vin)[-1]
+            return torch.sqrt((d * d).mean(dim=0)).cpu().numpy().astype(np.float32)
+
     def numpy_params(self):
         return [w.detach().cpu().numpy() for w in self.w], [b.detach().cpu().numpy() for b in self.b]

@@ -232,6 +232,8 @@ class SystemDynamicsHandler:
         trainer = DenseTrainer(fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule)  # fresh optimizer per call (:258)
         self.training_loss, self.validation_loss = trainer.fit(tin, tout, vin, vout, epochs, batch_size,
                                                                permutations=permutations, generator_seed=seed)
+        self._residual_rms = trainer.residual_rms(vin, vout)              # normalised target units; residual_std() scales it
+        self._trained = True
         fn.set_weights(*trainer.numpy_params())                            # bumps the version: evaluators re-upload
         self._version += 1
         self._refining_model_iter += 1                                     # :290
@@ -239,6 +241,19 @@ class SystemDynamicsHandler:
         if self._training_iter % self._save_model_frequency == 0 and self._log_dir is not None:   # :212-241
             self.save(os.path.join(self._log_dir, "saved_model_%d" % self._refining_model_iter))
         return
+
+    def residual_std(self):
+        """Per-dimension RMS of (target - prediction) in state units on the held-out validation rows of the last train():
+        the one-step residual of the fitted model, the natural `process_noise_std` of a ParticleTrajectoryEvaluator.
+        Computed by train() on the device it trains on."""
+        if not getattr(self, "_trained", False):
+            raise Exception("residual_std() needs a train() call first")
+        if self._residual_rms is None:
+            raise Exception("residual_std(): the last train() held no validation rows out (validation_split / split_mask)")
+        r = np.asarray(self._residual_rms, np.float32)
+        if self._is_normalized:
+            r = r * (np.asarray(self._stats[5], np.float32) + np.float32(1e-7))     # targets were (t - mean_t) / (std_t + 1e-7)
+        return r.astype(np.float32)
 
     # -- multi-step (open-loop) model error ---------------------------------------------------------------------------
     def _multistep_engine(self):

@@ -316,6 +316,46 @@ class Engine:
         L.check(L.lib.bbmpc_evaluate_dev(self._h, ctypes.c_void_p(d_state), ctypes.c_void_p(d_seq), int(n_pop),
                                          ctypes.c_void_p(d_rewards)))
 
+    def set_particles(self, num_particles, process_noise_std=None, risk_kappa=0.0):
+        """Particle trajectory evaluation (bbmpc_set_particles): every candidate is rolled out `num_particles` times with
+        additive N(0, process_noise_std^2) noise on the predicted next state ([dim_S] or a scalar) and scored
+        mean - risk_kappa * std of the returns.  0 switches back to the deterministic paths."""
+        p = int(num_particles)
+        if p == 0:
+            L.check(L.lib.bbmpc_set_particles(self._h, 0, None, ctypes.c_float(0.0)))
+            self.P = 0
+            return
+        if process_noise_std is None:
+            raise ValueError("process_noise_std is required with num_particles > 0")
+        sg = np.asarray(process_noise_std, np.float32)
+        sg = L.f32c(np.full((self.S,), sg, np.float32) if sg.ndim == 0 else sg.reshape(-1))
+        if sg.shape != (self.S,):
+            raise ValueError("process_noise_std must be a scalar or [dim_S] = [%d], got %s" % (self.S, sg.shape))
+        L.check(L.lib.bbmpc_set_particles(self._h, p, L.ptr(sg), ctypes.c_float(float(risk_kappa))))
+        self.P = p
+
+    def evaluate_particles(self, state, action_sequences, want_returns=True):
+        """(scores [n, A], per-particle returns [n, P, A] or None) -- bbmpc_evaluate_particles."""
+        state = L.f32c(state)
+        seq = L.f32c(action_sequences)
+        if state.shape != (self.A, self.S):
+            raise ValueError("current_states must be [%d, %d], got %s" % (self.A, self.S, state.shape))
+        if seq.ndim != 4 or seq.shape[1:] != (self.A, self.H, self.U):
+            raise ValueError("action_sequences must be [n, %d, %d, %d], got %s" % (self.A, self.H, self.U, seq.shape))
+        p = getattr(self, "P", 0)
+        if p <= 0:
+            raise ValueError("particles are off: call set_particles first")
+        n = seq.shape[0]
+        scores = np.empty((n, self.A), np.float32)
+        returns = np.empty((n, p, self.A), np.float32) if want_returns else None
+        if n:
+            L.check(L.lib.bbmpc_evaluate_particles(self._h, L.ptr(state), L.ptr(seq), n, L.ptr(scores), L.ptr(returns)))
+        return scores, returns
+
+    def evaluate_particles_dev(self, d_state, d_seq, n_pop, d_scores, d_returns=0):
+        L.check(L.lib.bbmpc_evaluate_particles_dev(self._h, ctypes.c_void_p(d_state), ctypes.c_void_p(d_seq), int(n_pop),
+                                                   ctypes.c_void_p(d_scores), ctypes.c_void_p(d_returns or 0)))
+
     def predict_next_state(self, states, actions):
         states, actions = L.f32c(states), L.f32c(actions)
         b = states.shape[0]

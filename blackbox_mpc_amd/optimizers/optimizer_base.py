@@ -110,6 +110,9 @@ class OptimizerBase:
                               population_global=self._population_global, **self._engine_kwargs())
         configure_dynamics(self._engine, h)
         configure_reward(self._engine, trajectory_evaluator._reward_function)
+        particles = getattr(trajectory_evaluator, "particle_settings", None)
+        if particles is not None:                     # a ParticleTrajectoryEvaluator: (num_particles, process_noise_std, risk_kappa)
+            self._engine.set_particles(*particles)
         if self._engine._param_fns:
             self._require_engine = self._require_engine_and_params
         else:

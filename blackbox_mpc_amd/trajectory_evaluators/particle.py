@@ -1,0 +1,52 @@
+"""ParticleTrajectoryEvaluator -- the "different trajectory evaluators to propagate uncertainties" the reference's
+README leaves open (its EvaluatorBase / set_trajectory_evaluator layout was made for them): every candidate is rolled out
+`num_particles` times through the ONE model with additive Gaussian process noise on the predicted next state, and the
+returns are reduced to  mean - risk_kappa * std  (include/bbmpc.h: bbmpc_set_particles).  The noise does not depend on
+the candidate (common random numbers), so candidates of an agent are ranked on the same noise paths."""
+import numpy as np
+
+from .deterministic import DeterministicTrajectoryEvaluator
+
+
+class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
+    def __init__(self, reward_function, system_dynamics_handler, num_particles, process_noise_std, risk_kappa=0.0,
+                 quirks=0):
+        """process_noise_std: a scalar or [dim_S], >= 0 -- for a learned model SystemDynamicsHandler.residual_std() is
+        the natural choice.  risk_kappa > 0 prefers candidates whose return varies little over the particles."""
+        super().__init__(reward_function, system_dynamics_handler, quirks=quirks)
+        p = int(num_particles)
+        if not 1 <= p <= 64:
+            raise ValueError("num_particles must be in [1, 64], got %r" % (num_particles,))
+        dim_s = system_dynamics_handler._dim_S
+        sg = np.asarray(process_noise_std, np.float32)
+        sg = np.full((dim_s,), sg, np.float32) if sg.ndim == 0 else sg.reshape(-1).astype(np.float32)
+        if sg.shape != (dim_s,) or not np.all(np.isfinite(sg)) or np.any(sg < 0):
+            raise ValueError("process_noise_std must be a finite scalar or [dim_S] = [%d] vector >= 0" % dim_s)
+        if not np.isfinite(risk_kappa):
+            raise ValueError("risk_kappa must be finite")
+        self._num_particles, self._process_noise_std, self._risk_kappa = p, sg, float(risk_kappa)
+
+    @property
+    def particle_settings(self):
+        """(num_particles, process_noise_std [dim_S], risk_kappa): what OptimizerBase.set_trajectory_evaluator hands to
+        Engine.set_particles."""
+        return self._num_particles, self._process_noise_std, self._risk_kappa
+
+    def _particle_engine(self, seq):
+        if seq.ndim != 4:
+            raise ValueError("action_sequences must be [population, num_agents, planning_horizon, dim_U]")
+        eng = self._engine(seq.shape[1], seq.shape[2])
+        if getattr(eng, "P", 0) != self._num_particles or getattr(eng, "_particle_settings", None) is not self:
+            eng.set_particles(*self.particle_settings)
+            eng._particle_settings = self
+        return eng
+
+    def __call__(self, current_states, action_sequences, time_step=0):
+        """current_states [A,S], action_sequences [N,A,H,U] -> scores [N,A]."""
+        seq = np.asarray(action_sequences, np.float32)
+        return self._particle_engine(seq).evaluate(current_states, seq)
+
+    def particle_returns(self, current_states, action_sequences):
+        """The per-particle returns [N, P, A] behind the scores (NaN -> -1e6 per particle)."""
+        seq = np.asarray(action_sequences, np.float32)
+        return self._particle_engine(seq).evaluate_particles(current_states, seq)[1]

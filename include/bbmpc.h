@@ -96,6 +96,7 @@ extern "C" {
 #define BBMPC_NOISE_PSO_RESET_POS      8  /* [N,A,H,U]: pso.py:147-149 */
 #define BBMPC_NOISE_PSO_RESET_VEL      9  /* [N,A,H,U]: pso.py:151-152 */
 #define BBMPC_NOISE_EXPLORATION       10  /* [A,U] unit trunc normal: optimizer_base.py:83-86 */
+#define BBMPC_NOISE_PROCESS           11  /* [iters][A,P,H,S] N(0,1) ([A,P,H,S] on evaluator-only handles): bbmpc_set_particles */
 
 /* trace items for bbmpc_get_trace (per-iteration parity data) */
 #define BBMPC_TRACE_REWARDS 1   /* [N,A]  (SPSA: [2N,A], plus then minus)   */
@@ -316,6 +317,32 @@ int bbmpc_evaluate(bbmpc_handle h, const float* state, const float* action_seque
                    float* rewards);
 int bbmpc_evaluate_dev(bbmpc_handle h, const float* d_state, const float* d_action_sequences, int32_t n_pop,
                        float* d_rewards);
+
+/* Particle trajectory evaluator: the "different trajectory evaluators to propagate uncertainties" the reference's README
+ * leaves open (its EvaluatorBase / set_trajectory_evaluator layout was made for them).  Every candidate is rolled out
+ * num_particles times through the handle's ONE model with additive Gaussian process noise, for agent a, candidate n,
+ * particle p:   s_0 = state[a];   nxt = predict_next_state(s_t, a_t) + sigma (.) eps[a, p, t, :];
+ *               R += reward(s_t, a_t, nxt) (the reference's call order, quirk Q1 as configured);   s_{t+1} = nxt
+ * r[n,p,a] = R (NaN -> -1e6 per particle);  mean = (sum_p r) / P and var = (sum_p (r - mean)^2) / P in index order, fp32;
+ * score[n,a] = mean - risk_kappa * sqrt(var)  (risk_kappa == 0: the mean).  eps does not depend on the candidate
+ * (common random numbers); it is drawn per optimizer iteration from stream BBMPC_NOISE_PROCESS -- Philox counter
+ * (p, ga * Qp + (j >> 2), control_step, (11 << 16) | iter), ga the global agent id, j = t * S + s, Qp = ceil(H * S / 4),
+ * element j from word j & 3, Box-Muller on word pairs as BBMPC_NOISE_NORMAL -- or injected (bbmpc_inject_noise).
+ * With particles on, every optimizer scores its candidates this way (bound penalties are subtracted from the score),
+ * bbmpc_evaluate[_dev] returns the scores (iter = 0, the handle's current control step: equal calls give equal bits) and
+ * control steps take one launch sequence per iteration, as with bbmpc_set_trace.  The control step's record stays the
+ * noise-free one-step prediction.  On the analytic pendulum the noise lands on (cos, sin, thdot), so the rollouts use the
+ * op-for-op model step whatever BBMPC_STRICT_MATH says.  num_particles = 0 switches back to the deterministic paths, bit
+ * for bit.  BBMPC_E_INVALID: num_particles outside [0, 64], sigma NULL / negative / not finite, risk_kappa not finite.
+ * BBMPC_E_UNSUPPORTED: HIP-source or callback reward / dynamics, an inverse target transform, a sharded population,
+ * population_size * num_particles > 32768.
+ * bbmpc_evaluate_particles: scores [n_pop, A] and, when `returns` is not NULL, the per-particle returns [n_pop, P, A]
+ * (BBMPC_E_STATE with particles off).  The host variant is synchronous; _dev enqueues on the handle's stream. */
+int bbmpc_set_particles(bbmpc_handle h, int32_t num_particles, const float* sigma, float risk_kappa);
+int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* action_sequences, int32_t n_pop,
+                             float* scores, float* returns);
+int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const float* d_action_sequences, int32_t n_pop,
+                                 float* d_scores, float* d_returns);
 
 /* .predict_next_state(states[B,S], actions[B,U]) -> [B,S]      deterministic.py:79-103 */
 int bbmpc_predict_next_state(bbmpc_handle h, const float* states, const float* actions, int32_t batch,
