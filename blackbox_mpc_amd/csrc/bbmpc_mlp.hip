@@ -6,6 +6,7 @@
 #include "engine_util.hpp"
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
+#include "kernels_mlp_ensemble.hpp"
 
 namespace bbmpc {
 
@@ -13,6 +14,51 @@ void bbmpc_tu_mlp_upload_tnq(const float2* table) { tnq_upload(table); }
 
 static_assert(ACT_SIGMOID == BBMPC_ACT_SIGMOID && ACT_ELU == BBMPC_ACT_ELU && ACT_SWISH == BBMPC_ACT_SWISH &&
                   ACT_RELU6 == BBMPC_ACT_RELU6, "activations.hpp and bbmpc.h disagree on the activation codes");
+
+// ------------------------------------------------------------------------------------------------
+// operand packing (bbmpc_set_mlp for the handle's model, bbmpc_set_mlp_ensemble per member)
+// ------------------------------------------------------------------------------------------------
+// Hidden features are internal, so their order inside a tile is free.  When the last tile of a hidden layer
+// holds <= 8 features (200 units = 12 tiles + 8) they are put into the slots 4g + {0, 1}: as the next layer's
+// K tile that leaves MFMAs 2 and 3 (k = 4g + 2, 4g + 3) with nothing but zeros, and the pipelined kernel
+// skips them.  slot -> feature (or -1 = padding); inputs (layer 0) and outputs (last layer) keep their order.
+static int mlp_feature_of_slot(const MlpDesc& d, int layer_of_feature, int slot) {
+    const int width = d.dims[layer_of_feature], tiles = (width + 15) / 16, t = slot >> 4, q = slot & 15;
+    if (layer_of_feature >= 1 && layer_of_feature < d.n_layers && t == tiles - 1 && d.half_tail[layer_of_feature]) {
+        if ((q & 3) >= 2) return -1;
+        const int f = 16 * t + 2 * (q >> 2) + (q & 3);
+        return f < width ? f : -1;
+    }
+    return slot < width ? slot : -1;
+}
+
+// Dense layer l of a network of d's shape (dims, tiles, half_tail): kernel w [in][out] and bias b [out] ->
+//   wp [OT][IT][4][64]    MFMA operand order (MlpDesc::wpack)
+//   w4 [OT][IT][64][4]    the same operands with a lane's four A operands of a k tile side by side (generic kernel)
+//   bp [OT][64][4]        biases in accumulator order (MlpDesc::bpack)
+static void mlp_pack_layer(const MlpDesc& d, int l, const float* w, const float* b, std::vector<float>& wp, std::vector<float>& w4,
+                           std::vector<float>& bp) {
+    const int M = d.dims[l + 1], IT = d.tiles[l], OT = d.tiles[l + 1];
+    wp.assign((size_t)OT * IT * 256, 0.0f);
+    bp.assign((size_t)OT * 256, 0.0f);
+    for (int ot = 0; ot < OT; ++ot) {
+        for (int it = 0; it < IT; ++it)
+            for (int s = 0; s < 4; ++s)
+                for (int ln = 0; ln < 64; ++ln) {
+                    const int k = mlp_feature_of_slot(d, l, it * 16 + 4 * (ln >> 4) + s), o = mlp_feature_of_slot(d, l + 1, ot * 16 + (ln & 15));
+                    if (k >= 0 && o >= 0) wp[(((size_t)ot * IT + it) * 4 + s) * 64 + ln] = w[(size_t)k * M + o];
+                }
+        for (int ln = 0; ln < 64; ++ln)
+            for (int r = 0; r < 4; ++r) {
+                const int o = mlp_feature_of_slot(d, l + 1, ot * 16 + (ln >> 4) * 4 + r);
+                if (o >= 0) bp[((size_t)ot * 64 + ln) * 4 + r] = b[o];
+            }
+    }
+    w4.resize(wp.size());
+    for (size_t t = 0; t < (size_t)OT * IT; ++t)
+        for (int s = 0; s < 4; ++s)
+            for (int ln = 0; ln < 64; ++ln) w4[(t * 64 + ln) * 4 + s] = wp[(t * 4 + s) * 64 + ln];
+}
 
 // ------------------------------------------------------------------------------------------------
 // launches
@@ -25,6 +71,7 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
     REQUIRE(dims[0] == S + U && dims[n_layers] == S, BBMPC_E_INVALID, "MLP must map dim_S+dim_U -> dim_S");
     HIP_CHECK(hipStreamSynchronize(stream));
     memset(&mlp, 0, sizeof(mlp));
+    ens_E = 0;                                  // (the shape may change: bbmpc_set_mlp_ensemble installs the members again)
     mlp.n_layers = n_layers;
     int hidden_tiles = 1;
     for (int l = 0; l <= n_layers; ++l) {
@@ -44,42 +91,11 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
         REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
         REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
         mlp.act[l] = acts[l];
-        const int K = dims[l], M = dims[l + 1], IT = mlp.tiles[l], OT = mlp.tiles[l + 1];
-        std::vector<float> wp((size_t)OT * IT * 256, 0.0f), bp((size_t)OT * 256, 0.0f);
-        // Hidden features are internal, so their order inside a tile is free.  When the last tile of a hidden layer
-        // holds <= 8 features (200 units = 12 tiles + 8) they are put into the slots 4g + {0, 1}: as the next layer's
-        // K tile that leaves MFMAs 2 and 3 (k = 4g + 2, 4g + 3) with nothing but zeros, and the pipelined kernel
-        // skips them.  slot -> feature (or -1 = padding); inputs (layer 0) and outputs (last layer) keep their order.
-        auto feature_of_slot = [&](int layer_of_feature, int slot) -> int {
-            const int width = dims[layer_of_feature], tiles = (width + 15) / 16, t = slot >> 4, q = slot & 15;
-            if (layer_of_feature >= 1 && layer_of_feature < n_layers && t == tiles - 1 && mlp.half_tail[layer_of_feature]) {
-                if ((q & 3) >= 2) return -1;
-                const int f = 16 * t + 2 * (q >> 2) + (q & 3);
-                return f < width ? f : -1;
-            }
-            return slot < width ? slot : -1;
-        };
-        for (int ot = 0; ot < OT; ++ot) {
-            for (int it = 0; it < IT; ++it)
-                for (int s = 0; s < 4; ++s)
-                    for (int ln = 0; ln < 64; ++ln) {
-                        const int k = feature_of_slot(l, it * 16 + 4 * (ln >> 4) + s), o = feature_of_slot(l + 1, ot * 16 + (ln & 15));
-                        if (k >= 0 && o >= 0) wp[(((size_t)ot * IT + it) * 4 + s) * 64 + ln] = w[l][(size_t)k * M + o];
-                    }
-            for (int ln = 0; ln < 64; ++ln)
-                for (int r = 0; r < 4; ++r) {
-                    const int o = feature_of_slot(l + 1, ot * 16 + (ln >> 4) * 4 + r);
-                    if (o >= 0) bp[((size_t)ot * 64 + ln) * 4 + r] = b[l][o];
-                }
-        }
+        const int K = dims[l], M = dims[l + 1];
+        std::vector<float> wp, w4, bp;
+        mlp_pack_layer(mlp, l, w[l], b[l], wp, w4, bp);
         upload(d_wpack[l], wp);
-        {   // the same operands with a lane's four A operands of a k tile side by side: [OT][IT][lane][s] (generic kernel)
-            std::vector<float> w4(wp.size());
-            for (size_t t = 0; t < (size_t)OT * IT; ++t)
-                for (int s = 0; s < 4; ++s)
-                    for (int ln = 0; ln < 64; ++ln) w4[(t * 64 + ln) * 4 + s] = wp[(t * 4 + s) * 64 + ln];
-            upload(d_wpack4[l], w4);
-        }
+        upload(d_wpack4[l], w4);
         upload(d_bpack[l], bp);
         upload(d_wraw[l], std::vector<float>(w[l], w[l] + (size_t)K * M));
         upload(d_braw[l], std::vector<float>(b[l], b[l] + M));
@@ -115,7 +131,7 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
                     for (int ln = 0; ln < 64; ++ln)
                         for (int r = 0; r < 4; ++r) {
                             // same slot -> feature map as the fp32 operands (the biases come from bpack)
-                            const int kk = feature_of_slot(l, 16 * it + 4 * (ln >> 4) + r), o = feature_of_slot(l + 1, 16 * ot + (ln & 15));
+                            const int kk = mlp_feature_of_slot(mlp, l, 16 * it + 4 * (ln >> 4) + r), o = mlp_feature_of_slot(mlp, l + 1, 16 * ot + (ln & 15));
                             const float v = (kk >= 0 && o >= 0) ? w[l][(size_t)kk * M + o] : 0.0f;
                             const uint16_t h = bf16_rne(v), lo = bf16_rne(v - bf16_f(h));
                             uint16_t* d = hw + (((size_t)ot * IT + it) * 64 + ln) * 8;
@@ -161,6 +177,43 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
         mlp.std_t = q;
     }
     mlp_ready = true;
+}
+
+// bbmpc_set_mlp_ensemble: E networks of the installed model's shape for the particle rollouts (kernels_mlp_ensemble.hpp).
+// w, b: [E][n_layers] pointers, member-major, in bbmpc_set_mlp's layouts.  Every member is packed on the host before the
+// handle is touched, so a refusal leaves it as it was.
+void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* b) {
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_STATE, "handle was not created with BBMPC_DYN_MLP");
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "model ensemble: call bbmpc_set_mlp first (the members share its shape and statistics)");
+    REQUIRE(E >= 0 && E <= MLP_ENS_MAX, BBMPC_E_UNSUPPORTED, "model ensemble: 0..8 members are supported");
+    if (E == 0) {
+        invalidate_step_graph();
+        ens_E = 0;
+        return;
+    }
+    REQUIRE(w && b, BBMPC_E_INVALID, "null argument");
+    const int L = mlp.n_layers;
+    for (int i = 0; i < E * L; ++i) REQUIRE(w[i] && b[i], BBMPC_E_INVALID, "null weight/bias pointer");
+    REQUIRE(part_P == 0 || part_P % E == 0, BBMPC_E_INVALID,
+            "model ensemble: num_particles = " + std::to_string(part_P) + " is no multiple of num_members = " + std::to_string(E) +
+                " (the members must carry equal weight in the mean)");
+    std::vector<float> ew[MLP_MAX_LAYERS], eb[MLP_MAX_LAYERS];
+    for (int l = 0; l < L; ++l) {
+        std::vector<float> wp, w4, bp;
+        for (int e = 0; e < E; ++e) {
+            mlp_pack_layer(mlp, l, w[e * L + l], b[e * L + l], wp, w4, bp);
+            ew[l].insert(ew[l].end(), w4.begin(), w4.end());
+            eb[l].insert(eb[l].end(), bp.begin(), bp.end());
+        }
+    }
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));
+    ens_E = 0;
+    for (int l = 0; l < L; ++l) {
+        upload(d_ens_wp4[l], ew[l]);
+        upload(d_ens_bp[l], eb[l]);
+    }
+    ens_E = E;
 }
 
 void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_particle_state, float* final_state) {
@@ -419,7 +472,8 @@ void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int 
 }
 
 // Particle rollouts of a learned model with a built-in reward (bbmpc_set_particles): one launch of k_rollout_mlp_particles,
-// 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp, always fp32
+// 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp, always fp32; with an ensemble
+// installed (bbmpc_set_mlp_ensemble), one launch of k_rollout_mlp_particles_ens instead
 void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
     MlpParticleArgs q;
@@ -439,6 +493,30 @@ void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     const long act_elems = pa.from_ref ? (long)pa.n_pop * A * pa.HU : (long)A * pa.HU * pa.Nst;
     REQUIRE(act_elems < (1L << 31) && (long)A * pa.P * pa.H * S < (1L << 31), BBMPC_E_UNSUPPORTED,
             "particle rollout: more than 2^31 action or noise elements per launch");
+    if (ens_E > 0) {
+        // trajectory sampling: rows grouped by member, grid.z = member (kernels_mlp_ensemble.hpp)
+        REQUIRE(pa.P % ens_E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");
+        MlpEnsParticleArgs qe;
+        memset(&qe, 0, sizeof(qe));
+        qe.m = mlp;
+        for (int l = 0; l < mlp.n_layers; ++l) {
+            qe.wp4[l] = d_ens_wp4[l].p;
+            qe.m.bpack[l] = d_ens_bp[l].p;
+            qe.wstride[l] = mlp.tiles[l + 1] * mlp.tiles[l] * 256;
+            qe.bstride[l] = mlp.tiles[l + 1] * 256;
+        }
+        qe.nw = mlp_nw;
+        qe.E = ens_E;
+        qe.p = pa;
+        const void* fe = ext ? (const void*)k_rollout_mlp_particles_ens<true> : (const void*)k_rollout_mlp_particles_ens<false>;
+        if (lds > 64 * 1024) ensure_max_lds(fe, 159 * 1024);
+        const long rows_e = (long)pa.n_pop * (pa.P / ens_E);
+        dim3 egrid((unsigned)((rows_e + MLP_TP - 1) / MLP_TP), A, ens_E), eblock(mlp_nw * 64);
+        if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles_ens<true>, egrid, eblock, lds, stream, qe);
+        else hipLaunchKernelGGL(k_rollout_mlp_particles_ens<false>, egrid, eblock, lds, stream, qe);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
     dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), A), block(mlp_nw * 64);
     if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles<true>, grid, block, lds, stream, q);
     else hipLaunchKernelGGL(k_rollout_mlp_particles<false>, grid, block, lds, stream, q);

@@ -26,6 +26,9 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     REQUIRE(!pop_sharded() && cfg.population_global <= N, BBMPC_E_UNSUPPORTED,
             "particles with a sharded population: the shards would have to exchange per-particle returns");
     REQUIRE((long)N * num_particles <= 32768, BBMPC_E_UNSUPPORTED, "particles: population_size * num_particles must not exceed 32768");
+    REQUIRE(ens_E == 0 || num_particles % ens_E == 0, BBMPC_E_INVALID,
+            "particles: num_particles = " + std::to_string(num_particles) + " is no multiple of the model ensemble's num_members = " +
+                std::to_string(ens_E) + " (the members must carry equal weight in the mean)");
     HIP_CHECK(hipStreamSynchronize(stream));
     if (num_particles != part_P) inj.erase(BBMPC_NOISE_PROCESS);       // (its layout depends on P)
     if (d_psigma.n < (size_t)S) d_psigma.alloc((size_t)S);
@@ -104,7 +107,7 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
     dominant_inst[0] = 0;
     prof_begin();
     if (cfg.dynamics == BBMPC_DYN_MLP) {
-        dominant_kernel = "k_rollout_mlp_particles";
+        dominant_kernel = ens_E > 0 ? "k_rollout_mlp_particles_ens" : "k_rollout_mlp_particles";
         launch_rollout_mlp_particles(q);
     } else {
         dominant_kernel = "k_rollout_pendulum_particles";

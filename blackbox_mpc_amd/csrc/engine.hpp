@@ -420,6 +420,11 @@ struct Engine {
     void dump_process_noise(int control_step, int iteration, float* out, int64_t count);
     void rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_returns, int returns_stride);
     void launch_rollout_mlp_particles(const ParticleArgs& pa);                 // bbmpc_mlp.hip
+    // model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble; bbmpc_mlp.hip, kernels_mlp_ensemble.hpp): particle p
+    // follows member p % ens_E.  Every deterministic path keeps the model of bbmpc_set_mlp.
+    int ens_E = 0;
+    DevBuf<float> d_ens_wp4[MLP_MAX_LAYERS], d_ens_bp[MLP_MAX_LAYERS];   // per layer [E][OT][IT][64][4] | [E][OT][64][4]
+    void set_mlp_ensemble(int E, const float* const* w, const float* const* b);
     void evaluate_particles_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_scores, float* d_returns);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);

@@ -125,7 +125,11 @@ class SystemDynamicsHandler:
         from ..dynamics_functions.deterministic_mlp import DeterministicMLP
         mlp = os.path.join(saved_model_dir, "mlp.npz")
         if os.path.exists(mlp):
-            self._dynamics_function = DeterministicMLP.load(mlp)
+            if os.path.exists(os.path.join(saved_model_dir, "mlp_member1.npz")):      # EnsembleMLP.save
+                from ..dynamics_functions.ensemble_mlp import EnsembleMLP
+                self._dynamics_function = EnsembleMLP.load(mlp)
+            else:
+                self._dynamics_function = DeterministicMLP.load(mlp)
         if self._is_normalized and all(os.path.exists(os.path.join(saved_model_dir, n + ".npy")) for n in _STATS):
             self.set_normalization_stats(*[np.load(os.path.join(saved_model_dir, n + ".npy")) for n in _STATS])
 
@@ -199,11 +203,12 @@ class SystemDynamicsHandler:
 
     def train(self, observations_trajectories, actions_trajectories, rewards_trajectories, validation_split=0.2,
               batch_size=128, learning_rate=1e-3, epochs=30, nn_optimizer=None, *, device=None, seed=None,
-              split_mask=None, permutations=None):
+              split_mask=None, permutations=None, bootstrap_indices=None):
         """Reference signature (:163-166); `nn_optimizer`: None / "Adam" / "SGD" / "RMSprop" or a class of that name
         (the reference's callers only ever pass tf.keras.optimizers.Adam).  Keyword-only extras: `device` (default: the GPU -- training on the
         host has to be asked for explicitly with device="cpu"), and the injected random draws `split_mask`,
-        `permutations` (one per epoch) / `seed` for reproducible runs."""
+        `permutations` (one per epoch) / `seed` for reproducible runs.  With an EnsembleMLP every member is fitted on
+        its own bootstrap resample of the training rows (`_train_ensemble`; `bootstrap_indices` injects the resamples)."""
         if self._is_true_model:
             raise Exception("the true model has nothing to train")
         # the reference instantiates `nn_optimizer(learning_rate=learning_rate)` (:261): a Keras optimizer CLASS (or its
@@ -229,18 +234,67 @@ class SystemDynamicsHandler:
         tin, tout = self._normalize_data(self._model_training_in, self._model_training_out)
         vin, vout = self._normalize_data(self._model_validation_in, self._model_validation_out)
         from ..dynamics_functions._train_torch import DenseTrainer
+        if hasattr(fn, "members"):
+            self._train_ensemble(fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
+                                 bootstrap_indices)
+            return self._after_training()
+        if bootstrap_indices is not None:
+            raise ValueError("bootstrap_indices are the resamples of an EnsembleMLP's members")
         trainer = DenseTrainer(fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule)  # fresh optimizer per call (:258)
         self.training_loss, self.validation_loss = trainer.fit(tin, tout, vin, vout, epochs, batch_size,
                                                                permutations=permutations, generator_seed=seed)
         self._residual_rms = trainer.residual_rms(vin, vout)              # normalised target units; residual_std() scales it
         self._trained = True
         fn.set_weights(*trainer.numpy_params())                            # bumps the version: evaluators re-upload
+        return self._after_training()
+
+    def _after_training(self):
         self._version += 1
         self._refining_model_iter += 1                                     # :290
         self._training_iter += 1
         if self._training_iter % self._save_model_frequency == 0 and self._log_dir is not None:   # :212-241
             self.save(os.path.join(self._log_dir, "saved_model_%d" % self._refining_model_iter))
         return
+
+    def _train_ensemble(self, fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
+                        bootstrap_indices):
+        """The members of an EnsembleMLP on the (normalised) rows train() prepared -- statistics, split and the
+        freeze-after-first rule are shared.  Member e is fitted by a fresh DenseTrainer on a bootstrap resample of the
+        training rows: n_train indices drawn with replacement, `bootstrap_indices[e]` when given, else from
+        np.random.default_rng([seed, e]) -- which then also draws the member's epoch permutations.  Injected
+        `permutations` are [E][epochs] (one list per member) or [epochs] (shared by the members).
+        training_loss / validation_loss stay member 0's; the per-member lists go to member_training_loss /
+        member_validation_loss, and residual_std() becomes the RMS over members of the members' validation residuals."""
+        from ..dynamics_functions._train_torch import DenseTrainer
+        n, members = tin.shape[0], fn.members
+        if bootstrap_indices is not None:
+            if len(bootstrap_indices) != len(members):
+                raise ValueError("bootstrap_indices needs one row of indices per member (%d)" % len(members))
+            bootstrap_indices = [np.asarray(ix, np.int64).reshape(-1) for ix in bootstrap_indices]
+            for ix in bootstrap_indices:
+                if ix.shape[0] != n or (n and (ix.min() < 0 or ix.max() >= n)):
+                    raise ValueError("bootstrap_indices: %d indices into the %d training rows per member" % (n, n))
+        per_member = permutations is not None and len(permutations) > 0 and np.ndim(permutations[0]) >= 2
+        if per_member and len(permutations) != len(members):
+            raise ValueError("permutations needs one list per member (%d)" % len(members))
+        self.member_training_loss, self.member_validation_loss, rms = [], [], []
+        for e, member in enumerate(members):
+            rng = np.random.default_rng([int(seed), e] if seed is not None else None)
+            idx = bootstrap_indices[e] if bootstrap_indices is not None else rng.integers(0, n, size=n)
+            if permutations is None:
+                perms = [rng.permutation(n) for _ in range(epochs)]
+            else:
+                perms = permutations[e] if per_member else permutations
+            trainer = DenseTrainer(member.weights, member.biases, member.activation_codes, device, learning_rate=learning_rate,
+                                   rule=rule)
+            tl, vl = trainer.fit(tin[idx], tout[idx], vin, vout, epochs, batch_size, permutations=perms, generator_seed=seed)
+            self.member_training_loss.append(tl)
+            self.member_validation_loss.append(vl)
+            rms.append(trainer.residual_rms(vin, vout))
+            member.set_weights(*trainer.numpy_params())                    # bumps the version: evaluators re-upload
+        self.training_loss, self.validation_loss = self.member_training_loss[0], self.member_validation_loss[0]
+        self._residual_rms = None if rms[0] is None else np.sqrt(np.mean(np.square(np.asarray(rms, np.float64)), axis=0)).astype(np.float32)
+        self._trained = True
 
     def residual_std(self):
         """Per-dimension RMS of (target - prediction) in state units on the held-out validation rows of the last train():

@@ -100,6 +100,29 @@ class Engine:
         else:
             L.check(L.lib.bbmpc_set_mlp(self._h, n, dims_a, acts_a, wp, bp, 0, None))
 
+    def set_mlp_ensemble(self, members):
+        """Model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble): `members` is a list of (weights, biases)
+        pairs or of objects with `.weights` / `.biases`, each of the shape of the model set_mlp installed; particle p
+        follows member p % len(members).  An empty list / None removes the ensemble."""
+        members = list(members or [])
+        if not members:
+            L.check(L.lib.bbmpc_set_mlp_ensemble(self._h, 0, None, None))
+            return
+        pairs = [(m.weights, m.biases) if hasattr(m, "weights") else m for m in members]
+        ws = [[L.f32c(w) for w in p[0]] for p in pairs]
+        bs = [[L.f32c(b) for b in p[1]] for p in pairs]
+        n = len(ws[0])
+        for e, (w_e, b_e) in enumerate(zip(ws, bs)):
+            if len(w_e) != n or len(b_e) != n:
+                raise ValueError("member %d: %d layers expected" % (e, n))
+            for i, (w, b) in enumerate(zip(w_e, b_e)):
+                if w.shape != ws[0][i].shape or b.shape != (w.shape[1],):
+                    raise ValueError("member %d, layer %d: kernel %s / bias %s do not match member 0's %s"
+                                     % (e, i, w.shape, b.shape, ws[0][i].shape))
+        wp = (ctypes.c_void_p * (len(ws) * n))(*[w.ctypes.data for w_e in ws for w in w_e])
+        bp = (ctypes.c_void_p * (len(bs) * n))(*[b.ctypes.data for b_e in bs for b in b_e])
+        L.check(L.lib.bbmpc_set_mlp_ensemble(self._h, len(ws), wp, bp))
+
     def set_reward_source(self, hip_source, num_params=0):
         """HIP source defining `__device__ float bbmpc_user_reward(cur, act, nxt, S, U)`, or with num_params > 0
         `bbmpc_user_reward_params(cur, act, nxt, S, U, params, t)` (include/bbmpc.h)."""

@@ -2,7 +2,9 @@
 README leaves open (its EvaluatorBase / set_trajectory_evaluator layout was made for them): every candidate is rolled out
 `num_particles` times through the ONE model with additive Gaussian process noise on the predicted next state, and the
 returns are reduced to  mean - risk_kappa * std  (include/bbmpc.h: bbmpc_set_particles).  The noise does not depend on
-the candidate (common random numbers), so candidates of an agent are ranked on the same noise paths."""
+the candidate (common random numbers), so candidates of an agent are ranked on the same noise paths.  When the handler's
+dynamics function is an EnsembleMLP, particle p follows member p % num_members for the whole horizon (trajectory
+sampling, bbmpc_set_mlp_ensemble): the spread of the returns then carries the members' disagreement as well."""
 import numpy as np
 
 from .deterministic import DeterministicTrajectoryEvaluator
@@ -24,6 +26,10 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
             raise ValueError("process_noise_std must be a finite scalar or [dim_S] = [%d] vector >= 0" % dim_s)
         if not np.isfinite(risk_kappa):
             raise ValueError("risk_kappa must be finite")
+        members = getattr(system_dynamics_handler._dynamics_function, "members", None)
+        if members is not None and p % len(members) != 0:
+            raise ValueError("num_particles = %d is no multiple of the EnsembleMLP's num_members = %d (particle p follows "
+                             "member p %% num_members: the members must carry equal weight)" % (p, len(members)))
         self._num_particles, self._process_noise_std, self._risk_kappa = p, sg, float(risk_kappa)
 
     @property

@@ -344,6 +344,24 @@ int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* ac
 int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const float* d_action_sequences, int32_t n_pop,
                                  float* d_scores, float* d_returns);
 
+/* Model ensemble with trajectory sampling for the particle evaluator (PETS, TS-infinity): num_members networks of the shape,
+ * activations and six normalisation statistics of the model that bbmpc_set_mlp installed, e.g. fitted on bootstrap
+ * resamples of the training rows.  weights / biases: num_members x n_layers pointers, member-major (entry e * n_layers + l),
+ * each in bbmpc_set_mlp's layout.  With particles on, particle p of every candidate and agent is rolled through member
+ * p % num_members for the whole horizon, so member disagreement shows as spread of the per-particle returns and
+ * risk_kappa > 0 penalises candidates the members disagree about.  Everything else of bbmpc_set_particles' recurrence is
+ * unchanged: sigma (.) eps[a, p, t, :] on the next state (sigma = 0 leaves pure model disagreement), the reward's call
+ * order, NaN -> -1e6 per particle, the noise keying and injection, the aggregate, the bound penalties; r[n, p, a] of
+ * bbmpc_evaluate_particles belongs to member p % num_members.  Every deterministic path -- the control step's record,
+ * bbmpc_predict_next_state, bbmpc_predict_trajectories, everything with particles off -- keeps the model of bbmpc_set_mlp,
+ * and a handle without an ensemble launches what it launched before.  num_members = 0 removes the ensemble (weights and
+ * biases are not read); so does a later bbmpc_set_mlp.
+ * BBMPC_E_STATE: not a BBMPC_DYN_MLP handle, or bbmpc_set_mlp has not been called.  BBMPC_E_UNSUPPORTED: num_members
+ * outside [0, 8].  BBMPC_E_INVALID: NULL pointers; num_particles % num_members != 0 -- from whichever of
+ * bbmpc_set_particles / bbmpc_set_mlp_ensemble comes second (the members carry equal weight in the mean).  A refused call
+ * leaves the handle as it was. */
+int bbmpc_set_mlp_ensemble(bbmpc_handle h, int32_t num_members, const float* const* weights, const float* const* biases);
+
 /* .predict_next_state(states[B,S], actions[B,U]) -> [B,S]      deterministic.py:79-103 */
 int bbmpc_predict_next_state(bbmpc_handle h, const float* states, const float* actions, int32_t batch,
                              float* next_states);
