@@ -31,6 +31,7 @@ NOISE_EXPLORATION = 10
 NOISE_PROCESS = 11                                      # [iters][A,P,H,S] N(0,1): the particle evaluator's process noise
 MAX_PARTICLES = 64
 MAX_ENSEMBLE_MEMBERS = 8                                # bbmpc_set_mlp_ensemble
+LOGVAR_ABS_MAX = 40.0                                   # bbmpc_set_mlp_logvar_head: |min_logvar|, |max_logvar| <= 40
 TRACE_REWARDS, TRACE_MEAN, TRACE_VAR, TRACE_ELITES, TRACE_SAMPLES = 1, 2, 3, 4, 5
 TRACE_CMA_B, TRACE_CMA_C, TRACE_CMA_D, TRACE_CMA_SVD_STATS = 6, 7, 8, 9
 
@@ -83,7 +84,7 @@ SYMBOLS = [
     "bbmpc_predict_trajectories", "bbmpc_predict_trajectories_dev", "bbmpc_trajectory_sq_error_dev",
     "bbmpc_set_keep_plan", "bbmpc_get_plan",
     "bbmpc_set_particles", "bbmpc_evaluate_particles", "bbmpc_evaluate_particles_dev",
-    "bbmpc_set_mlp_ensemble",
+    "bbmpc_set_mlp_ensemble", "bbmpc_set_mlp_logvar_head",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -172,6 +173,7 @@ def _load():
     lib.bbmpc_evaluate_particles.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.bbmpc_evaluate_particles_dev.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.bbmpc_set_mlp_ensemble.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.bbmpc_set_mlp_logvar_head.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

@@ -1571,6 +1571,14 @@ int bbmpc_set_mlp_ensemble(bbmpc_handle h, int32_t num_members, const float* con
     API_END
 }
 
+int bbmpc_set_mlp_logvar_head(bbmpc_handle h, int32_t num_heads, const float* const* w, const float* const* b, const float* min_logvar,
+                              const float* max_logvar) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_mlp_logvar_head(num_heads, w, b, min_logvar, max_logvar);
+    API_END
+}
+
 // which = 0: process_input(states[B,S], actions[B,U]) -> [B,S+U];  1: process_output(states[B,S], raw[B,S]) -> [B,S]
 static void process_io(Engine& e, int which, const float* a, const float* b, int batch, const float* const* stats, float* out) {
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");

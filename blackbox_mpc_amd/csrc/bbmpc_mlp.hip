@@ -2,11 +2,14 @@
 // SystemDynamicsHandler.process_input / process_output): weight packing and the choice + launch of the MFMA rollout
 // kernels (kernels_mlp*.hpp).  A translation unit of its own: the template kernels are instantiated here only.
 #define BBMPC_TU_MLP
+#include <cmath>
+
 #include "engine.hpp"
 #include "engine_util.hpp"
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
 #include "kernels_mlp_ensemble.hpp"
+#include "kernels_mlp_gaussian.hpp"
 
 namespace bbmpc {
 
@@ -72,6 +75,7 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
     HIP_CHECK(hipStreamSynchronize(stream));
     memset(&mlp, 0, sizeof(mlp));
     ens_E = 0;                                  // (the shape may change: bbmpc_set_mlp_ensemble installs the members again)
+    lv_heads = 0;                               // (... and bbmpc_set_mlp_logvar_head the heads)
     mlp.n_layers = n_layers;
     int hidden_tiles = 1;
     for (int l = 0; l <= n_layers; ++l) {
@@ -189,6 +193,7 @@ void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* 
     if (E == 0) {
         invalidate_step_graph();
         ens_E = 0;
+        lv_heads = 0;                           // (one head per member: bbmpc_set_mlp_logvar_head comes after this call)
         return;
     }
     REQUIRE(w && b, BBMPC_E_INVALID, "null argument");
@@ -209,11 +214,56 @@ void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* 
     invalidate_step_graph();
     HIP_CHECK(hipStreamSynchronize(stream));
     ens_E = 0;
+    lv_heads = 0;
     for (int l = 0; l < L; ++l) {
         upload(d_ens_wp4[l], ew[l]);
         upload(d_ens_bp[l], eb[l]);
     }
     ens_E = E;
+}
+
+// bbmpc_set_mlp_logvar_head: one log-variance head per model of the particle rollouts (kernels_mlp_gaussian.hpp) -- the
+// handle's model, or each member of its ensemble.  w [num_heads] pointers to [dims[L-1]][S] kernels, b to [S] biases: the last
+// layer's layouts.  Packed on the host before the handle is touched, so a refusal leaves it as it was.
+void Engine::set_mlp_logvar_head(int num_heads, const float* const* w, const float* const* b, const float* min_logvar,
+                                 const float* max_logvar) {
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_STATE, "handle was not created with BBMPC_DYN_MLP");
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "log-variance head: call bbmpc_set_mlp first (the head shares the model's last hidden layer)");
+    if (num_heads == 0) {
+        invalidate_step_graph();
+        lv_heads = 0;
+        return;
+    }
+    REQUIRE(w && b && min_logvar && max_logvar, BBMPC_E_INVALID, "null argument");
+    const int want = std::max(1, ens_E);
+    REQUIRE(num_heads == want, BBMPC_E_INVALID,
+            "log-variance head: num_heads = " + std::to_string(num_heads) + " but the handle rolls " + std::to_string(want) +
+                " model(s) (one head per ensemble member, one for the model without an ensemble)");
+    for (int e = 0; e < num_heads; ++e) REQUIRE(w[e] && b[e], BBMPC_E_INVALID, "null weight/bias pointer");
+    for (int s = 0; s < S; ++s)
+        REQUIRE(std::isfinite(min_logvar[s]) && std::isfinite(max_logvar[s]) && std::fabs(min_logvar[s]) <= MLP_LOGVAR_ABS_MAX &&
+                    std::fabs(max_logvar[s]) <= MLP_LOGVAR_ABS_MAX && min_logvar[s] <= max_logvar[s],
+                BBMPC_E_INVALID, "log-variance head: the bounds must be finite, within [-40, 40], with min_logvar <= max_logvar");
+    REQUIRE((size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "log-variance head: the partial-sum buffers of the doubled last layer do not fit one CU's LDS next to this network's activations");
+    const int L = mlp.n_layers;
+    std::vector<float> hw, hb, bounds(min_logvar, min_logvar + S);
+    bounds.insert(bounds.end(), max_logvar, max_logvar + S);
+    {
+        std::vector<float> wp, w4, bp;
+        for (int e = 0; e < num_heads; ++e) {
+            mlp_pack_layer(mlp, L - 1, w[e], b[e], wp, w4, bp);
+            hw.insert(hw.end(), w4.begin(), w4.end());
+            hb.insert(hb.end(), bp.begin(), bp.end());
+        }
+    }
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));
+    lv_heads = 0;
+    upload(d_lv_wp4, hw);
+    upload(d_lv_bp, hb);
+    upload(d_lv_bounds, bounds);
+    lv_heads = num_heads;
 }
 
 void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_particle_state, float* final_state) {
@@ -473,7 +523,8 @@ void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int 
 
 // Particle rollouts of a learned model with a built-in reward (bbmpc_set_particles): one launch of k_rollout_mlp_particles,
 // 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp, always fp32; with an ensemble
-// installed (bbmpc_set_mlp_ensemble), one launch of k_rollout_mlp_particles_ens instead
+// installed (bbmpc_set_mlp_ensemble), one launch of k_rollout_mlp_particles_ens instead; with log-variance heads
+// (bbmpc_set_mlp_logvar_head), with or without an ensemble, one launch of k_rollout_mlp_particles_gauss
 void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
     MlpParticleArgs q;
@@ -493,6 +544,41 @@ void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     const long act_elems = pa.from_ref ? (long)pa.n_pop * A * pa.HU : (long)A * pa.HU * pa.Nst;
     REQUIRE(act_elems < (1L << 31) && (long)A * pa.P * pa.H * S < (1L << 31), BBMPC_E_UNSUPPORTED,
             "particle rollout: more than 2^31 action or noise elements per launch");
+    if (lv_heads > 0) {
+        // probabilistic models: the ensemble kernel's frame with the head behind the last layer (kernels_mlp_gaussian.hpp);
+        // without an ensemble one "member", the primary's operands at stride 0
+        const int E = std::max(1, ens_E);
+        REQUIRE(lv_heads == E && pa.P % E == 0, BBMPC_E_INVALID, "internal: log-variance heads per model");
+        MlpGaussParticleArgs qg;
+        memset(&qg, 0, sizeof(qg));
+        qg.m = mlp;
+        for (int l = 0; l < mlp.n_layers; ++l) {
+            qg.wp4[l] = ens_E > 0 ? d_ens_wp4[l].p : d_wpack4[l].p;
+            qg.m.bpack[l] = ens_E > 0 ? d_ens_bp[l].p : d_bpack[l].p;
+            qg.wstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * mlp.tiles[l] * 256 : 0;
+            qg.bstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * 256 : 0;
+        }
+        const int Ll = mlp.n_layers - 1;
+        qg.hp4 = d_lv_wp4.p;
+        qg.hbp = d_lv_bp.p;
+        qg.hwstride = mlp.tiles[Ll + 1] * mlp.tiles[Ll] * 256;
+        qg.hbstride = mlp.tiles[Ll + 1] * 256;
+        qg.min_logvar = d_lv_bounds.p;
+        qg.max_logvar = d_lv_bounds.p + S;
+        qg.nw = mlp_nw;
+        qg.E = E;
+        qg.p = pa;
+        const size_t glds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+        REQUIRE(glds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
+        const void* fg = ext ? (const void*)k_rollout_mlp_particles_gauss<true> : (const void*)k_rollout_mlp_particles_gauss<false>;
+        if (glds > 64 * 1024) ensure_max_lds(fg, 159 * 1024);
+        const long rows_e = (long)pa.n_pop * (pa.P / E);
+        dim3 ggrid((unsigned)((rows_e + MLP_TP - 1) / MLP_TP), A, E), gblock(mlp_nw * 64);
+        if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles_gauss<true>, ggrid, gblock, glds, stream, qg);
+        else hipLaunchKernelGGL(k_rollout_mlp_particles_gauss<false>, ggrid, gblock, glds, stream, qg);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
     if (ens_E > 0) {
         // trajectory sampling: rows grouped by member, grid.z = member (kernels_mlp_ensemble.hpp)
         REQUIRE(pa.P % ens_E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");

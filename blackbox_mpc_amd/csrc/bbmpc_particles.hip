@@ -107,7 +107,7 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
     dominant_inst[0] = 0;
     prof_begin();
     if (cfg.dynamics == BBMPC_DYN_MLP) {
-        dominant_kernel = ens_E > 0 ? "k_rollout_mlp_particles_ens" : "k_rollout_mlp_particles";
+        dominant_kernel = lv_heads > 0 ? "k_rollout_mlp_particles_gauss" : ens_E > 0 ? "k_rollout_mlp_particles_ens" : "k_rollout_mlp_particles";
         launch_rollout_mlp_particles(q);
     } else {
         dominant_kernel = "k_rollout_pendulum_particles";

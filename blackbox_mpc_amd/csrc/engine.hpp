@@ -425,6 +425,12 @@ struct Engine {
     int ens_E = 0;
     DevBuf<float> d_ens_wp4[MLP_MAX_LAYERS], d_ens_bp[MLP_MAX_LAYERS];   // per layer [E][OT][IT][64][4] | [E][OT][64][4]
     void set_mlp_ensemble(int E, const float* const* w, const float* const* b);
+    // log-variance heads of the model / of every member (bbmpc_set_mlp_logvar_head; bbmpc_mlp.hip, kernels_mlp_gaussian.hpp):
+    // the particle rollouts add (sigma + sd(s, a)) * eps.  lv_heads = max(1, ens_E) while installed, else 0; removed by
+    // bbmpc_set_mlp and bbmpc_set_mlp_ensemble.  No deterministic path reads them.
+    int lv_heads = 0;
+    DevBuf<float> d_lv_wp4, d_lv_bp, d_lv_bounds;                        // [heads][OT][IT][64][4] | [heads][OT][64][4] | min [S], max [S]
+    void set_mlp_logvar_head(int num_heads, const float* const* w, const float* const* b, const float* min_logvar, const float* max_logvar);
     void evaluate_particles_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_scores, float* d_returns);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);

@@ -85,11 +85,17 @@ def _act_grad(code, y, g, z=None):
 
 class DenseTrainer:
     def __init__(self, weights, biases, act_codes, device, learning_rate=1e-3, beta_1=0.9, beta_2=0.999,
-                 epsilon=1e-7, rule="adam", rho=0.9):
+                 epsilon=1e-7, rule="adam", rho=0.9, logvar_head=None):
         """rule: "adam" | "sgd" | "rmsprop" -- tf.keras.optimizers.{Adam, SGD, RMSprop}(learning_rate=lr) with their
         TF-2.0 defaults, which is how the reference instantiates `nn_optimizer` (system_dynamics_handler.py:261):
           sgd      w -= lr * g                                              (momentum 0)
-          rmsprop  v = rho*v + (1-rho)*g^2 ;  w -= lr * g / (sqrt(v) + eps)   (rho 0.9, momentum 0, eps 1e-7, not centered)"""
+          rmsprop  v = rho*v + (1-rho)*g^2 ;  w -= lr * g / (sqrt(v) + eps)   (rho 0.9, momentum 0, eps 1e-7, not centered)
+        logvar_head: None, or (W_v [hidden, out], b_v [out], min_logvar, max_logvar) of a ProbabilisticMLP -- a second last
+        Dense layer on the last hidden activation.  The loss is then the Gaussian negative log-likelihood
+          z = h W_v + b_v;  lv1 = max_lv - softplus(max_lv - z);  lv = min_lv + softplus(lv1 - min_lv)
+          loss = mean over the batch's B * out elements of (mu - y)^2 exp(-lv) + lv
+        with the backward pass written out like the Dense stack's (dlv/dz = sigmoid(lv1 - min_lv) sigmoid(max_lv - z));
+        W_v and b_v join `params`, so every update rule and the captured step cover them.  The bounds are fixed."""
         if rule not in ("adam", "sgd", "rmsprop"):
             raise ValueError("unknown optimizer rule %r" % (rule,))
         self.rule, self.rho = rule, float(rho)
@@ -100,6 +106,18 @@ class DenseTrainer:
         self.w = [torch.tensor(np.asarray(w, np.float32), device=self.dev) for w in weights]
         self.b = [torch.tensor(np.asarray(b, np.float32), device=self.dev) for b in biases]
         self.params = self.w + self.b
+        self.has_logvar_head = logvar_head is not None
+        if self.has_logvar_head:
+            wv, bv, lo, hi = logvar_head
+            self.wv = torch.tensor(np.asarray(wv, np.float32), device=self.dev)
+            self.bv = torch.tensor(np.asarray(bv, np.float32), device=self.dev)
+            out = self.bv.shape[0]
+            self.min_lv = torch.tensor(np.broadcast_to(np.asarray(lo, np.float32), (out,)).copy(), device=self.dev)
+            self.max_lv = torch.tensor(np.broadcast_to(np.asarray(hi, np.float32), (out,)).copy(), device=self.dev)
+            if self.wv.shape != (self.w[-1].shape[0], out) or out != self.w[-1].shape[1]:
+                raise ValueError("logvar_head: kernel %s does not sit on the last hidden layer %s"
+                                 % (tuple(self.wv.shape), tuple(self.w[-1].shape)))
+            self.params = self.params + [self.wv, self.bv]
         self.m = [torch.zeros_like(p) for p in self.params]
         self.v = [torch.zeros_like(p) for p in self.params]
         self.lr, self.b1, self.b2, self.eps = float(learning_rate), float(beta_1), float(beta_2), float(epsilon)
@@ -121,14 +139,44 @@ class DenseTrainer:
             ys.append(_act(a, z))
         return ys
 
+    @staticmethod
+    def _softplus(x):
+        """max(x, 0) + log(1 + e^-|x|): csrc/activations.hpp's form, no threshold."""
+        return x.clamp(min=0.0) + (-x.abs()).exp().log1p()
+
+    def logvar(self, h):
+        """The clamped log-variance of the head on the last hidden activation h, with what the backward pass needs:
+        (lv, dlv/dz)."""
+        torch = self.torch
+        z = torch.addmm(self.bv, h, self.wv)
+        lv1 = self.max_lv - self._softplus(self.max_lv - z)
+        lv = self.min_lv + self._softplus(lv1 - self.min_lv)
+        return lv, torch.sigmoid(lv1 - self.min_lv) * torch.sigmoid(self.max_lv - z)
+
+    def nll(self, x, y):
+        """Per-element (mu - y)^2 exp(-lv) + lv of the rows (x, y): [B, out]."""
+        ys = self.forward(x)
+        lv, _ = self.logvar(ys[-2])
+        d = ys[-1] - y
+        return d * d * (-lv).exp() + lv
+
     def _step(self, x, y):
         torch = self.torch
         zs = []
         ys = self.forward(x, zs)
         diff = ys[-1] - y
-        self.loss_acc += (diff * diff).mean()
-        g = diff * (2.0 / diff.numel())
         n = len(self.w)
+        gz = None
+        if self.has_logvar_head:
+            lv, dlv_dz = self.logvar(ys[n - 1])
+            inv = (-lv).exp()
+            wsq = diff * diff * inv
+            self.loss_acc += (wsq + lv).mean()
+            g = diff * inv * (2.0 / diff.numel())
+            gz = (1.0 - wsq) * dlv_dz * (1.0 / diff.numel())              # d loss / d z through the soft clamp
+        else:
+            self.loss_acc += (diff * diff).mean()
+            g = diff * (2.0 / diff.numel())
         grads = [None] * (2 * n)
         for l in reversed(range(n)):
             g = _act_grad(self.acts[l], ys[l + 1], g, zs[l])
@@ -136,6 +184,10 @@ class DenseTrainer:
             grads[n + l] = g.sum(dim=0)
             if l:
                 g = g @ self.w[l].t()
+                if gz is not None and l == n - 1:                          # the head reads the same hidden activation
+                    g = g + gz @ self.wv.t()
+        if gz is not None:
+            grads = grads + [ys[n - 1].t() @ gz, gz.sum(dim=0)]
         if self.rule == "sgd":
             torch._foreach_add_(self.params, grads, alpha=-self.lr)
             return
@@ -220,6 +272,11 @@ class DenseTrainer:
                 tl[e] = float(self.loss_acc.item()) / nb
             nvb = vin.shape[0] // batch_size
             if nvb:
+                if self.has_logvar_head:
+                    with torch.no_grad():
+                        d = self.nll(vin[:nvb * batch_size], vout[:nvb * batch_size]).reshape(nvb, -1)
+                    vl[e] = float(d.mean(dim=1).mean().item())      # mean of per-batch NLLs
+                    continue
                 pv = self.forward(vin[:nvb * batch_size])[-1]
                 d = (pv - vout[:nvb * batch_size]).reshape(nvb, -1)
                 vl[e] = float((d * d).mean(dim=1).mean().item())    # mean of per-batch MSEs (:276-284)
@@ -235,6 +292,9 @@ class DenseTrainer:
         with torch.no_grad():
             d = vout - self.forward(vin)[-1]
             return torch.sqrt((d * d).mean(dim=0)).cpu().numpy().astype(np.float32)
+
+    def numpy_logvar_head(self):
+        return self.wv.detach().cpu().numpy(), self.bv.detach().cpu().numpy()
 
     def numpy_params(self):
         return [w.detach().cpu().numpy() for w in self.w], [b.detach().cpu().numpy() for b in self.b]

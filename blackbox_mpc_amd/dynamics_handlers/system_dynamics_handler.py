@@ -44,6 +44,13 @@ def multistep_windows(observations_trajectories, actions_trajectories, horizon, 
             np.ascontiguousarray(np.concatenate(obs_w, axis=0)))
 
 
+def _logvar_head(fn):
+    """DenseTrainer's `logvar_head` of a (member) model: (W_v, b_v, min_logvar, max_logvar), None for a plain model."""
+    if not hasattr(fn, "logvar_weights"):
+        return None
+    return fn.logvar_weights, fn.logvar_bias, fn.min_logvar, fn.max_logvar
+
+
 class SystemDynamicsHandler:
     def __init__(self, env_action_space, env_observation_space, dynamics_function=None, true_model=False,
                  is_normalized=True, log_dir=None, tf_writer=None, save_model_frequency=1, saved_model_dir=None,
@@ -128,6 +135,9 @@ class SystemDynamicsHandler:
             if os.path.exists(os.path.join(saved_model_dir, "mlp_member1.npz")):      # EnsembleMLP.save
                 from ..dynamics_functions.ensemble_mlp import EnsembleMLP
                 self._dynamics_function = EnsembleMLP.load(mlp)
+            elif os.path.exists(os.path.join(saved_model_dir, "mlp_logvar.npz")):   # ProbabilisticMLP.save
+                from ..dynamics_functions.probabilistic_mlp import ProbabilisticMLP
+                self._dynamics_function = ProbabilisticMLP.load(mlp)
             else:
                 self._dynamics_function = DeterministicMLP.load(mlp)
         if self._is_normalized and all(os.path.exists(os.path.join(saved_model_dir, n + ".npy")) for n in _STATS):
@@ -137,6 +147,9 @@ class SystemDynamicsHandler:
         os.makedirs(log_dir, exist_ok=True)
         if hasattr(self._dynamics_function, "save"):
             self._dynamics_function.save(os.path.join(log_dir, "mlp.npz"))
+            stale = os.path.join(log_dir, "mlp_logvar.npz")                # a probabilistic model saved here before
+            if not getattr(self._dynamics_function, "logvar_heads", None) and os.path.exists(stale):
+                os.remove(stale)
         if self._stats is not None:
             for n, v in zip(_STATS, self._stats):
                 np.save(os.path.join(log_dir, n + ".npy"), v)
@@ -208,7 +221,10 @@ class SystemDynamicsHandler:
         (the reference's callers only ever pass tf.keras.optimizers.Adam).  Keyword-only extras: `device` (default: the GPU -- training on the
         host has to be asked for explicitly with device="cpu"), and the injected random draws `split_mask`,
         `permutations` (one per epoch) / `seed` for reproducible runs.  With an EnsembleMLP every member is fitted on
-        its own bootstrap resample of the training rows (`_train_ensemble`; `bootstrap_indices` injects the resamples)."""
+        its own bootstrap resample of the training rows (`_train_ensemble`; `bootstrap_indices` injects the resamples).
+        A ProbabilisticMLP (or an ensemble of them) is fitted, mean and log-variance head together, on the Gaussian
+        negative log-likelihood: training_loss / validation_loss (and the member lists) then hold the NLL, while
+        residual_std() stays the mean network's residual."""
         if self._is_true_model:
             raise Exception("the true model has nothing to train")
         # the reference instantiates `nn_optimizer(learning_rate=learning_rate)` (:261): a Keras optimizer CLASS (or its
@@ -240,12 +256,15 @@ class SystemDynamicsHandler:
             return self._after_training()
         if bootstrap_indices is not None:
             raise ValueError("bootstrap_indices are the resamples of an EnsembleMLP's members")
-        trainer = DenseTrainer(fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule)  # fresh optimizer per call (:258)
+        trainer = DenseTrainer(fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule,
+                               logvar_head=_logvar_head(fn))               # fresh optimizer per call (:258)
         self.training_loss, self.validation_loss = trainer.fit(tin, tout, vin, vout, epochs, batch_size,
                                                                permutations=permutations, generator_seed=seed)
         self._residual_rms = trainer.residual_rms(vin, vout)              # normalised target units; residual_std() scales it
         self._trained = True
         fn.set_weights(*trainer.numpy_params())                            # bumps the version: evaluators re-upload
+        if trainer.has_logvar_head:
+            fn.set_logvar_head(*trainer.numpy_logvar_head())
         return self._after_training()
 
     def _after_training(self):
@@ -286,12 +305,14 @@ class SystemDynamicsHandler:
             else:
                 perms = permutations[e] if per_member else permutations
             trainer = DenseTrainer(member.weights, member.biases, member.activation_codes, device, learning_rate=learning_rate,
-                                   rule=rule)
+                                   rule=rule, logvar_head=_logvar_head(member))
             tl, vl = trainer.fit(tin[idx], tout[idx], vin, vout, epochs, batch_size, permutations=perms, generator_seed=seed)
             self.member_training_loss.append(tl)
             self.member_validation_loss.append(vl)
             rms.append(trainer.residual_rms(vin, vout))
             member.set_weights(*trainer.numpy_params())                    # bumps the version: evaluators re-upload
+            if trainer.has_logvar_head:
+                member.set_logvar_head(*trainer.numpy_logvar_head())
         self.training_loss, self.validation_loss = self.member_training_loss[0], self.member_validation_loss[0]
         self._residual_rms = None if rms[0] is None else np.sqrt(np.mean(np.square(np.asarray(rms, np.float64)), axis=0)).astype(np.float32)
         self._trained = True

@@ -99,6 +99,7 @@ class Engine:
             L.check(L.lib.bbmpc_set_mlp(self._h, n, dims_a, acts_a, wp, bp, 1, sp))
         else:
             L.check(L.lib.bbmpc_set_mlp(self._h, n, dims_a, acts_a, wp, bp, 0, None))
+        self._mlp_last_hidden = dims[-2]                 # rows of a log-variance head's kernel (set_mlp_logvar_head)
 
     def set_mlp_ensemble(self, members):
         """Model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble): `members` is a list of (weights, biases)
@@ -122,6 +123,30 @@ class Engine:
         wp = (ctypes.c_void_p * (len(ws) * n))(*[w.ctypes.data for w_e in ws for w in w_e])
         bp = (ctypes.c_void_p * (len(bs) * n))(*[b.ctypes.data for b_e in bs for b in b_e])
         L.check(L.lib.bbmpc_set_mlp_ensemble(self._h, len(ws), wp, bp))
+
+    def set_mlp_logvar_head(self, heads, min_logvar=None, max_logvar=None):
+        """Log-variance heads for the particle rollouts (bbmpc_set_mlp_logvar_head): `heads` is a list of (W_v, b_v) pairs
+        or of objects with `.logvar_weights` / `.logvar_bias`, one per model the handle rolls -- one per ensemble member,
+        else one; min_logvar / max_logvar are scalars or [dim_S].  Call it after set_mlp / set_mlp_ensemble.  An empty
+        list / None removes the heads."""
+        heads = list(heads or [])
+        if not heads:
+            L.check(L.lib.bbmpc_set_mlp_logvar_head(self._h, 0, None, None, None, None))
+            return
+        pairs = [(m.logvar_weights, m.logvar_bias) if hasattr(m, "logvar_weights") else m for m in heads]
+        ws = [L.f32c(p[0]) for p in pairs]
+        bs = [L.f32c(p[1]) for p in pairs]
+        for e, (w, b) in enumerate(zip(ws, bs)):
+            hid = getattr(self, "_mlp_last_hidden", w.shape[0] if w.ndim == 2 else -1)    # (no model yet: the ABI refuses)
+            if w.shape != (hid, self.S) or b.shape != (self.S,):
+                raise ValueError("head %d: kernel %s / bias %s, expected [%d, %d] / [%d]" % (e, w.shape, b.shape, hid, self.S, self.S))
+        if min_logvar is None or max_logvar is None:
+            raise ValueError("min_logvar and max_logvar are required with heads")
+        lo = L.f32c(np.broadcast_to(np.asarray(min_logvar, np.float32), (self.S,)))
+        hi = L.f32c(np.broadcast_to(np.asarray(max_logvar, np.float32), (self.S,)))
+        wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * len(bs))(*[b.ctypes.data for b in bs])
+        L.check(L.lib.bbmpc_set_mlp_logvar_head(self._h, len(ws), wp, bp, lo.ctypes.data, hi.ctypes.data))
 
     def set_reward_source(self, hip_source, num_params=0):
         """HIP source defining `__device__ float bbmpc_user_reward(cur, act, nxt, S, U)`, or with num_params > 0

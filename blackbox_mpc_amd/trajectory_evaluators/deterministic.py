@@ -106,6 +106,8 @@ def configure_dynamics(engine, handler):
         engine.set_mlp(dyn.weights, dyn.biases, dyn.activation_codes, handler.normalization_stats())
         if hasattr(dyn, "members"):                   # an EnsembleMLP: member 0 above, all members for the particle rollouts
             engine.set_mlp_ensemble(dyn.members)
+        if getattr(dyn, "logvar_heads", None):        # a ProbabilisticMLP / probabilistic EnsembleMLP: the heads come last
+            engine.set_mlp_logvar_head(dyn.logvar_heads, dyn.min_logvar, dyn.max_logvar)
     elif engine.cfg.dynamics == L.DYN_USER and isinstance(getattr(dyn, "hip_source", None), str):
         np_ = getattr(dyn, "num_params", 0)
         if getattr(engine, "_dyn_source", None) is not dyn.hip_source or getattr(engine, "_dyn_nparams", 0) != np_:

@@ -4,7 +4,10 @@ README leaves open (its EvaluatorBase / set_trajectory_evaluator layout was made
 returns are reduced to  mean - risk_kappa * std  (include/bbmpc.h: bbmpc_set_particles).  The noise does not depend on
 the candidate (common random numbers), so candidates of an agent are ranked on the same noise paths.  When the handler's
 dynamics function is an EnsembleMLP, particle p follows member p % num_members for the whole horizon (trajectory
-sampling, bbmpc_set_mlp_ensemble): the spread of the returns then carries the members' disagreement as well."""
+sampling, bbmpc_set_mlp_ensemble): the spread of the returns then carries the members' disagreement as well.  When it is
+a ProbabilisticMLP, or an ensemble of them, the noise scale of a step is process_noise_std plus the standard deviation
+the model's log-variance head predicts at that state and action (bbmpc_set_mlp_logvar_head), and process_noise_std = 0
+-- the learned noise alone -- is a sensible setting."""
 import numpy as np
 
 from .deterministic import DeterministicTrajectoryEvaluator

@@ -362,6 +362,27 @@ int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const flo
  * leaves the handle as it was. */
 int bbmpc_set_mlp_ensemble(bbmpc_handle h, int32_t num_members, const float* const* weights, const float* const* biases);
 
+/* Probabilistic models for the particle evaluator (PETS' Gaussian heads): every model of the particle rollouts -- the model of
+ * bbmpc_set_mlp, or each member of bbmpc_set_mlp_ensemble -- gets a log-variance head, a second last Dense layer on the same
+ * last hidden activation h with no activation of its own, in the target space of the mean (normalised when is_normalized).
+ * weights / biases: num_heads pointers to kernels [dims[n_layers - 1], dim_S] and biases [dim_S]; min_logvar / max_logvar
+ * [dim_S].  With z = h W_v + b_v and softplus(x) = max(x, 0) + log(1 + exp(-|x|)):
+ *     lv1 = max_logvar - softplus(max_logvar - z);   lv = min_logvar + softplus(lv1 - min_logvar)
+ *     sd[f] = tstd[f] * exp(lv[f] / 2)                (tstd = std_targets + 1e-7, or 1 when not normalised)
+ * and the particle recurrence of bbmpc_set_particles changes in one term:
+ *     nxt = predict_next_state_member(s_t, a_t) + (sigma[f] + sd_f(s_t, a_t)) * eps[a, p, t, f]
+ * on the same eps (keying, injection), reward order, NaN rule, aggregate and returns layout; sigma = 0 leaves the learned
+ * noise alone.  Every deterministic path -- the record, bbmpc_predict_next_state, bbmpc_predict_trajectories, everything
+ * with particles off -- keeps the mean network and launches what it launched before, as does a handle without heads.
+ * Call order: bbmpc_set_mlp, optionally bbmpc_set_mlp_ensemble, then this call with num_heads = max(1, num_members): head e
+ * belongs to member e, head 0 to the model when there is no ensemble.  num_heads = 0 (nothing else is read), a later
+ * bbmpc_set_mlp or a later bbmpc_set_mlp_ensemble removes the heads.
+ * BBMPC_E_STATE: not a BBMPC_DYN_MLP handle, or bbmpc_set_mlp has not been called.  BBMPC_E_INVALID: NULL pointers; a wrong
+ * num_heads; bounds that are not finite, lie outside [-40, 40] or have min > max.  BBMPC_E_UNSUPPORTED: the doubled last
+ * layer's partial sums no longer fit the kernel's LDS layout.  A refused call leaves the handle as it was. */
+int bbmpc_set_mlp_logvar_head(bbmpc_handle h, int32_t num_heads, const float* const* weights, const float* const* biases,
+                              const float* min_logvar, const float* max_logvar);
+
 /* .predict_next_state(states[B,S], actions[B,U]) -> [B,S]      deterministic.py:79-103 */
 int bbmpc_predict_next_state(bbmpc_handle h, const float* states, const float* actions, int32_t batch,
                              float* next_states);

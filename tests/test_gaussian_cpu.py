@@ -1,0 +1,406 @@
+"""Learned-variance (Gaussian) heads without a GPU: the NumPy statement the GPU tests compare against
+(tests/gaussian_util.py) against tests/particle_util.py, the cases of the GPU test (built here once, so that the CPU check of
+the cheetah margin rule and the GPU test see the same numbers), the hand-written NLL backward pass against autograd in
+float64, a fit on heteroscedastic data, save / load, the refusal of mixed members, the ABI's declaration and ensemble
+training with heads against DenseTrainer.fit called directly."""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from oracle import oracle_np as O
+from tests import gaussian_util as GU
+from tests import particle_util as PU
+from tests import test_ensemble_cpu as TE
+
+F = np.float32
+SIGMA = TE.SIGMA
+MARGIN_TOL = TE.MARGIN_TOL
+# (network, N, A, P, E, H, seed, normalized) of tests/test_gpu_gaussian.py::test_returns_match_the_helper; E = 1: no ensemble
+CASES = [("PEND_MLP", 33, 2, 3, 1, 9, 42, True), ("PEND_MLP", 33, 2, 16, 8, 9, 42, True), ("CHEETAH", 5, 1, 6, 3, 2, 42, True),
+         ("CHEETAH", 37, 3, 4, 2, 12, 42, True), ("SWISH", 5, 1, 6, 3, 2, 42, True), ("PEND_MLP", 33, 2, 4, 2, 9, 42, False)]
+# the seeds of the cases' inputs, chosen on the helper alone so that the cheetah cases meet the margin condition below
+INPUT_SEEDS = [3000, 3001, 3002, 3003, 3005, 3006]
+# gaussian case -> test_ensemble_cpu.CASES' case of the same (network family, N, A, H)
+_ENSEMBLE_CASE = {2: 0, 3: 1, 4: 4}
+
+
+def head_params(dims, seed, e):
+    """Member e's head: a Glorot-uniform kernel on the last hidden layer and biases around -6, so that z = h W_v + b_v
+    straddles the lower bound and comes near the upper one; bounds that differ per state dimension."""
+    hidden, S = dims[-2], dims[-1]
+    rng = np.random.default_rng(seed + 10 * e + 5)
+    lim = np.sqrt(6.0 / (hidden + S))
+    return rng.uniform(-lim, lim, (hidden, S)).astype(F), rng.normal(-6.0, 1.5, S).astype(F)
+
+
+def logvar_bounds(S):
+    return np.linspace(-8.0, -7.0, S).astype(F), np.linspace(-3.5, -3.0, S).astype(F)
+
+
+def member_heads(spec, evs, seed=42):
+    dims, S = spec[0], spec[2]
+    lo, hi = logvar_bounds(S)
+    raw = [head_params(dims, seed, e) for e in range(len(evs))]
+    return raw, (lo, hi), [GU.Head(ev, w, b, lo, hi) for ev, (w, b) in zip(evs, raw)]
+
+
+@functools.lru_cache(maxsize=None)
+def gaussian_case(case):
+    """Everything test_returns_match_the_helper needs, computed once per process: members, heads, inputs, the helper's
+    returns and the states it visited."""
+    name, N, A, P, E, H, seed, normalized = CASES[case]
+    spec = TE.network(name)
+    dims, acts, S, U, reward = spec
+    params, stats, evs = TE.member_evaluators(spec, E, seed, normalized)
+    raw, bounds, heads = member_heads(spec, evs, seed)
+    rng = np.random.default_rng(INPUT_SEEDS[case])
+    states = (O.cheetah_start_states(A, S) if reward == "cheetah" else O.pendulum_start_states(A)).astype(F)
+    seq = rng.uniform(-1, 1, (N, A, H, U)).astype(F)
+    eps = rng.standard_normal((A, P, H, S)).astype(F)
+    sigma = np.full(S, SIGMA, F)
+    want, visited = GU.gaussian_particle_returns(evs, heads, states, seq, eps, sigma, P, keep_states=True)
+    for arr in (states, seq, eps, sigma, want):
+        arr.setflags(write=False)
+    return dict(spec=spec, params=params, stats=stats, evs=evs, raw_heads=raw, bounds=bounds, heads=heads, states=states,
+                seq=seq, eps=eps, sigma=sigma, want=want, visited=visited, shape=(N, A, P, E, H))
+
+
+def gaussian_margin(case):
+    """particle_util.cheetah_noisy_margin on the helper's visited states, in the returns' layout [N, P, A]."""
+    c = gaussian_case(case)
+    N, A, P, E, H = c["shape"]
+    out = np.empty((N, P, A))
+    for e in range(E):
+        out[:, e::E, :] = PU.cheetah_noisy_margin(c["visited"][e]).reshape(N, P // E, A)
+    return out
+
+
+# ---- 1. the helper ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("normalized", [True, False])
+def test_helper_with_a_constant_sd_is_the_particle_helper_at_sigma_plus_sd(normalized):
+    from tests.test_gpu_mlp import _stats
+    ws, bs = O.make_mlp_params([4, 16, 3], seed=1)
+    ev = O.Evaluator("pendulum", O.Handler(O.MLP(ws, bs, ["tanh", None]), False, normalized, _stats(3, 1, 7) if normalized else None))
+    N, A, P, H = 9, 2, 6, 5
+    rng = np.random.default_rng(0)
+    states = O.pendulum_start_states(A)
+    seq = rng.uniform(-2, 2, (N, A, H, 1)).astype(F)
+    eps = rng.standard_normal((A, P, H, 3)).astype(F)
+    sigma = np.array([0.01, 0.0, 0.05], F)
+    # zero W_v: z = b_v whatever the state, so sd is one constant per dimension -- one of them clamped from below, one from above
+    head = GU.Head(ev, np.zeros((16, 3), F), np.array([-5.0, -30.0, 4.0], F), np.full(3, -9.0, F), np.array([-1.0, -1.0, -2.0], F))
+    c = head.sd32(states[:1], seq[0, :1, 0])[0]
+    np.testing.assert_allclose(c, head.sd64(states[:1], seq[0, :1, 0])[0], rtol=1e-6)
+    lv = np.log(c.astype(np.float64) / head.tstd) * 2.0
+    np.testing.assert_allclose(lv, [-5.0, -9.0, -2.0], atol=0.05)          # inside: z itself; outside: the bound
+    assert np.all(lv >= -9.0 - 1e-5) and np.all(lv <= np.array([-1.0, -1.0, -2.0]) + 1e-5)     # (lv recovered from a float32 sd)
+    got = GU.gaussian_particle_returns([ev], [head], states, seq, eps, sigma, P)
+    np.testing.assert_array_equal(got, PU.particle_returns(ev, states, seq, eps, (sigma + c).astype(F), P))
+    assert not np.array_equal(got, PU.particle_returns(ev, states, seq, eps, sigma, P))
+    # eps = 0: the noise scale is multiplied by zero, the returns are the particle helper's at any sigma, bit for bit
+    zero = np.zeros_like(eps)
+    g0 = GU.gaussian_particle_returns([ev, ev], [head, head], states, seq, zero, sigma, P)
+    np.testing.assert_array_equal(g0, PU.particle_returns(ev, states, seq, zero, sigma, P))
+    np.testing.assert_array_equal(g0, PU.particle_returns(ev, states, seq, zero, np.full(3, 7.0, F), P))
+    # the evaluator's scores are the base class's on those returns
+    pe = GU.GaussianParticleEvaluator([ev], [head], P, sigma, 1.5, eps)
+    np.testing.assert_array_equal(pe(states, seq), PU.aggregate32(got, 1.5))
+
+
+def test_sd_depends_on_the_state_and_head_e_follows_member_e():
+    c = gaussian_case(1)
+    N, A, P, E, H = c["shape"]
+    s = np.tile(c["states"], (3, 1))
+    a = c["seq"][:3].reshape(3 * A, H, -1)[:, 0]
+    sds = [h.sd32(s, a) for h in c["heads"]]
+    assert np.ptp(sds[0], axis=0).min() > 0                                 # state dependent
+    assert not np.allclose(sds[0], sds[1])
+    for h, sd in zip(c["heads"], sds):
+        np.testing.assert_allclose(sd, h.sd64(s, a), rtol=2e-6)
+        lo, hi = h.tstd * np.exp(0.5 * h.min_lv.astype(np.float64)), h.tstd * np.exp(0.5 * h.max_lv.astype(np.float64))
+        assert np.all(sd >= lo * (1 - 1e-6)) and np.all(sd <= hi * (1 + 1e-6))
+    # particle p carries (member, head) p % E
+    r = c["want"]
+    for e in (0, 5):
+        one = GU.gaussian_returns_one_model(c["evs"][e], c["heads"][e], c["states"], c["seq"], c["eps"][:, e::E], c["sigma"], P // E)
+        np.testing.assert_array_equal(r[:, e::E], one)
+
+
+# ---- 2. the GPU cases ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", sorted(_ENSEMBLE_CASE))
+def test_gpu_cases_leave_no_more_rows_to_the_margin_rule_than_the_ensemble_test(case):
+    """A condition on the inputs (see tests/test_ensemble_cpu.py): the share of rows whose noisy trajectory comes within
+    margin_tol per step of an indicator threshold -- the only rows assert_cheetah_rewards lets miss the tolerance -- is no
+    larger than in the ensemble test's case of the same N, A, H."""
+    c = gaussian_case(case)
+    assert np.all(np.isfinite(c["want"]))
+    margin = gaussian_margin(case)
+    share = float((margin <= MARGIN_TOL).mean())
+    cap = float((TE.ensemble_margin(_ENSEMBLE_CASE[case]) <= MARGIN_TOL).mean())
+    print("[gaussian case %d] smallest margin %.3e, rows within margin_tol: %.3f (ensemble test: %.3f)" % (case, margin.min(), share, cap))
+    assert share <= cap
+    assert np.all(c["want"][:, 0] != c["want"][:, 1])
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_gpu_cases_are_finite_and_the_learned_noise_matters(case):
+    c = gaussian_case(case)
+    N, A, P, E, H = c["shape"]
+    assert c["want"].shape == (N, P, A) and np.all(np.isfinite(c["want"]))
+    from tests import ensemble_util as EU
+    plain = EU.ensemble_particle_returns(c["evs"], c["states"], c["seq"], c["eps"], c["sigma"], P)
+    assert np.abs(plain - c["want"]).max() > 1e-2 * H                       # far above the GPU test's tolerance
+
+
+# ---- 3. the hand-written backward pass -------------------------------------------------------------------------------
+@pytest.mark.parametrize("acts", [("tanh", "tanh", None), ("swish", "swish", None)])
+def test_nll_step_is_minus_lr_times_the_autograd_gradient(acts):
+    """One SGD step at learning rate 1, so that the parameter deltas ARE the negated gradients and the absolute tolerance
+    tests/test_train_cpu.py puts on trained parameters (atol 2e-4) applies to them directly.  On top of it the bound the
+    arithmetic gives: the float32 pass differs from float64 by the rounding of dot products of at most 32 (batch) / 16
+    (width) terms through five stages, a few 1e-6 of the largest gradient entry -- 2e-5 of it is asserted per tensor."""
+    import torch
+    from blackbox_mpc_amd.dynamics_functions import _train_torch as TT
+    from blackbox_mpc_amd.dynamics_functions.deterministic_mlp import _act_code
+    codes = [_act_code(a) for a in acts]
+    assert (codes[0] in TT._NEEDS_PRE) == (acts[0] == "swish")
+    rng = np.random.default_rng(11)
+    ws, bs = O.make_mlp_params([4, 16, 16, 3], seed=4, last_scale=1.0)
+    bs = [rng.normal(0, 0.1, b.shape).astype(F) for b in bs]
+    wv, bv = rng.normal(0, 0.8, (16, 3)).astype(F), np.array([-1.0, 0.3, -6.0], F)
+    lo, hi = np.array([-4.0, -3.0, -5.0], F), np.array([0.5, 0.0, 1.0], F)     # z lands inside, above and below the bounds
+    x = rng.normal(0, 1, (32, 4)).astype(F)
+    y = rng.normal(0, 0.5, (32, 3)).astype(F)
+    tr = TT.DenseTrainer(ws, bs, codes, "cpu", learning_rate=1.0, rule="sgd", logvar_head=(wv, bv, lo, hi))
+    assert len(tr.params) == 8
+    tr._step(torch.as_tensor(x), torch.as_tensor(y))
+    got = [p.numpy().astype(np.float64) for p in tr.params]
+    # the loss written from the formulas, float64, autograd
+    p64 = [torch.tensor(np.asarray(v, np.float64), requires_grad=True) for v in ws + bs + [wv, bv]]
+    w64, b64, wv64, bv64 = p64[:3], p64[3:6], p64[6], p64[7]
+    h = torch.tensor(x.astype(np.float64))
+    for i in range(3):
+        if i == 2:
+            z = h @ wv64 + bv64
+        h = TT._act(codes[i], h @ w64[i] + b64[i])
+    sp = torch.nn.functional.softplus
+    lo64, hi64 = torch.tensor(lo.astype(np.float64)), torch.tensor(hi.astype(np.float64))
+    lv = lo64 + sp(hi64 - sp(hi64 - z, threshold=1e9) - lo64, threshold=1e9)
+    loss = ((h - torch.tensor(y.astype(np.float64))) ** 2 * torch.exp(-lv) + lv).mean()
+    loss.backward()
+    np.testing.assert_allclose(float(tr.loss_acc), float(loss.detach()), rtol=1e-5)
+    frac = ((z.detach().numpy() > hi).mean(), (z.detach().numpy() < lo).mean())
+    assert 0.02 < frac[0] < 0.9 and 0.02 < frac[1] < 0.9, frac                # the clamp's three regimes all occur
+    for name, g, p0, p in zip(["W0", "W1", "W2", "b0", "b1", "b2", "Wv", "bv"], got, ws + bs + [wv, bv], p64):
+        delta, grad = g - np.asarray(p0, np.float64), p.grad.numpy()
+        assert np.abs(grad).max() > 1e-3, name
+        print("[%s %s] max |delta + grad| = %.2e, max |grad| = %.2e" % (acts[0], name, np.abs(delta + grad).max(), np.abs(grad).max()))
+        np.testing.assert_allclose(delta, -grad, rtol=0, atol=2e-4)
+        assert np.abs(delta + grad).max() <= 2e-5 * np.abs(grad).max() + 1e-7, name   # 1e-7: float32 spacing of an O(1) parameter
+
+
+# ---- 4. a fit on heteroscedastic data --------------------------------------------------------------------------------
+def test_nll_fit_learns_where_the_noise_is():
+    import torch
+    from blackbox_mpc_amd.dynamics_functions import ProbabilisticMLP
+    from blackbox_mpc_amd.dynamics_functions._train_torch import DenseTrainer
+    torch.manual_seed(0)
+    rng = np.random.default_rng(5)
+    n, epochs, B = 4096, 40, 64
+    x = rng.uniform(-1, 1, (n, 2)).astype(F)
+    noisy = x[:, 0] > 0
+    std = np.where(noisy, 0.5, 0.1)                                          # 5 x on one half of the input range
+    y = (np.sin(2.0 * x[:, :1]) + 0.3 * x[:, 1:] + (std * rng.standard_normal(n))[:, None]).astype(F)
+    fn = ProbabilisticMLP([2, 32, 32, 1], ["tanh", "tanh", None], seed=2)
+    tr = DenseTrainer(fn.weights, fn.biases, fn.activation_codes, "cpu", learning_rate=2e-3,
+                      logvar_head=(fn.logvar_weights, fn.logvar_bias, fn.min_logvar, fn.max_logvar))
+    perms = [rng.permutation(n - 512) for _ in range(epochs)]
+    tl, vl = tr.fit(x[512:], y[512:], x[:512], y[:512], epochs, B, permutations=perms)
+    print("NLL per epoch, training:", np.round(tl, 3), "validation:", np.round(vl, 3))
+    assert tl[-1] < tl[0] and vl[-1] < vl[0] and tl[-1] < np.min(tl[:3])
+    with torch.no_grad():
+        xs = torch.as_tensor(x)
+        lv, _ = tr.logvar(tr.forward(xs)[-2])
+        sd = torch.exp(0.5 * lv).numpy()[:, 0]
+    ratio = sd[noisy].mean() / sd[~noisy].mean()
+    print("mean predicted sd: noisy half %.3f, quiet half %.3f, ratio %.2f (truth 5)" % (sd[noisy].mean(), sd[~noisy].mean(), ratio))
+    assert ratio > 2.0
+    # back into the model: the head's version bump is what makes the evaluators upload it again
+    v = fn._version
+    fn.set_weights(*tr.numpy_params())
+    fn.set_logvar_head(*tr.numpy_logvar_head())
+    assert fn._version == v + 2
+
+
+# ---- 5. classes, files, ABI, training glue ---------------------------------------------------------------------------
+def _spaces():
+    from blackbox_mpc_amd import Box
+    return Box(low=[-2.0], high=[2.0]), Box(low=[-1, -1, -8], high=[1, 1, 8])
+
+
+def test_probabilistic_mlp_round_trips_and_its_mean_loads_as_a_plain_model(tmp_path):
+    from blackbox_mpc_amd.dynamics_functions import DeterministicMLP, ProbabilisticMLP
+    from blackbox_mpc_amd.dynamics_handlers.system_dynamics_handler import SystemDynamicsHandler
+    fn = ProbabilisticMLP([4, 16, 16, 3], ["tanh", "swish", None], min_logvar=[-9, -8, -7], max_logvar=0.25, seed=5)
+    assert isinstance(fn, DeterministicMLP) and fn.logvar_weights.shape == (16, 3) and fn.logvar_bias.shape == (3,)
+    assert fn.min_logvar.dtype == np.float32 and list(fn.min_logvar) == [-9, -8, -7] and list(fn.max_logvar) == [0.25] * 3
+    assert fn.logvar_heads == [fn]
+    plain = DeterministicMLP([4, 16, 16, 3], ["tanh", "swish", None], seed=5)
+    for x, y in zip(fn.weights, plain.weights):
+        np.testing.assert_array_equal(x, y)                                  # the head draws from a stream of its own
+    d = ProbabilisticMLP([4, 16, 16, 3], ["tanh", "swish", None])
+    assert list(d.min_logvar) == [-10.0] * 3 and list(d.max_logvar) == [0.5] * 3
+    v = fn._version
+    fn.set_logvar_head(fn.logvar_weights * F(2), fn.logvar_bias - F(1))
+    assert fn._version == v + 1 and fn.logvar_bias[0] == F(-1)
+    with pytest.raises(ValueError):
+        fn.set_logvar_head(np.zeros((15, 3), F), np.zeros(3, F))
+    for lo, hi in ((1.0, 0.0), (-41.0, 0.0), (0.0, 41.0), (np.nan, 0.0), (0.0, np.inf)):
+        with pytest.raises(ValueError, match="logvar"):
+            ProbabilisticMLP([4, 8, 3], ["tanh", None], min_logvar=lo, max_logvar=hi)
+    path = str(tmp_path / "mlp.npz")
+    fn.save(path)
+    assert sorted(os.listdir(tmp_path)) == ["mlp.npz", "mlp_logvar.npz"]
+    back = ProbabilisticMLP.load(path)
+    assert back.activation_codes == fn.activation_codes and back.layer_sizes == fn.layer_sizes
+    for x, y in zip(fn.weights + fn.biases + [fn.logvar_weights, fn.logvar_bias, fn.min_logvar, fn.max_logvar],
+                    back.weights + back.biases + [back.logvar_weights, back.logvar_bias, back.min_logvar, back.max_logvar]):
+        np.testing.assert_array_equal(x, y)
+    mean = DeterministicMLP.load(path)                                       # mlp.npz alone is a plain model
+    assert type(mean) is DeterministicMLP and not hasattr(mean, "logvar_weights")
+    for x, y in zip(mean.weights + mean.biases, fn.weights + fn.biases):
+        np.testing.assert_array_equal(x, y)
+    # through the handler
+    h = SystemDynamicsHandler(*_spaces(), dynamics_function=fn, is_normalized=True)
+    h.set_normalization_stats(*[np.full(n, 0.5 + i, F) for i, n in enumerate((3, 3, 1, 1, 3, 3))])
+    h.save(str(tmp_path / "h"))
+    got = SystemDynamicsHandler(*_spaces(), saved_model_dir=str(tmp_path / "h"))._dynamics_function
+    assert isinstance(got, ProbabilisticMLP)
+    np.testing.assert_array_equal(got.logvar_weights, fn.logvar_weights)
+    os.remove(str(tmp_path / "h" / "mlp_logvar.npz"))
+    assert type(SystemDynamicsHandler(*_spaces(), saved_model_dir=str(tmp_path / "h"))._dynamics_function) is DeterministicMLP
+
+
+def test_probabilistic_ensemble_round_trips_and_refuses_mixed_members(tmp_path):
+    from blackbox_mpc_amd.dynamics_functions import DeterministicMLP, EnsembleMLP, ProbabilisticMLP
+    from blackbox_mpc_amd.dynamics_handlers.system_dynamics_handler import SystemDynamicsHandler
+    ens = EnsembleMLP([4, 16, 16, 3], ["tanh", "relu", None], num_members=3, seed=5, probabilistic=True, min_logvar=-8.0, max_logvar=-1.0)
+    assert ens.probabilistic and all(isinstance(m, ProbabilisticMLP) for m in ens.members) and ens.logvar_heads == ens.members
+    assert list(ens.min_logvar) == [-8.0] * 3 and list(ens.max_logvar) == [-1.0] * 3
+    assert not np.array_equal(ens.members[0].logvar_weights, ens.members[1].logvar_weights)
+    plain = EnsembleMLP([4, 16, 16, 3], ["tanh", "relu", None], num_members=3, seed=5)
+    assert not plain.probabilistic and plain.logvar_heads == []
+    for m, n in zip(ens.members, plain.members):
+        np.testing.assert_array_equal(m.weights[0], n.weights[0])
+    v = ens._version
+    ens.members[2].set_logvar_head(ens.members[2].logvar_weights, ens.members[2].logvar_bias + F(1))
+    assert ens._version == v + 1
+    with pytest.raises(ValueError, match="all ProbabilisticMLP or all plain"):
+        EnsembleMLP.from_members([ens.members[0], plain.members[1]])
+    other = ProbabilisticMLP([4, 16, 16, 3], ["tanh", "relu", None], min_logvar=-7.0, max_logvar=-1.0)
+    with pytest.raises(ValueError, match="share min_logvar"):
+        EnsembleMLP.from_members([ens.members[0], other])
+    h = SystemDynamicsHandler(*_spaces(), dynamics_function=ens, is_normalized=False)
+    h.save(str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == ["mlp.npz", "mlp_logvar.npz", "mlp_member1.npz", "mlp_member1_logvar.npz",
+                                            "mlp_member2.npz", "mlp_member2_logvar.npz"]
+    back = SystemDynamicsHandler(*_spaces(), saved_model_dir=str(tmp_path), is_normalized=False)._dynamics_function
+    assert isinstance(back, EnsembleMLP) and back.probabilistic and back.num_members == 3
+    for m, n in zip(ens.members, back.members):
+        for x, y in zip(m.weights + m.biases + [m.logvar_weights, m.logvar_bias, m.min_logvar, m.max_logvar],
+                        n.weights + n.biases + [n.logvar_weights, n.logvar_bias, n.min_logvar, n.max_logvar]):
+            np.testing.assert_array_equal(x, y)
+    assert type(DeterministicMLP.load(str(tmp_path / "mlp_member1.npz"))) is DeterministicMLP
+    EnsembleMLP.from_members(ens.members[:2]).save(str(tmp_path))            # a smaller ensemble over a larger one
+    assert sorted(os.listdir(tmp_path)) == ["mlp.npz", "mlp_logvar.npz", "mlp_member1.npz", "mlp_member1_logvar.npz"]
+    plain.save(str(tmp_path))                                                # plain members over probabilistic ones
+    assert sorted(os.listdir(tmp_path)) == ["mlp.npz", "mlp_member1.npz", "mlp_member2.npz"]
+    assert not EnsembleMLP.load(str(tmp_path)).probabilistic
+
+
+def test_header_declares_and_the_binding_names_the_setter():
+    from blackbox_mpc_amd import _build
+    _build.build()
+    from blackbox_mpc_amd import _lib as L
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "bbmpc.h")).read()
+    assert "int bbmpc_set_mlp_logvar_head(" in header and "bbmpc_set_mlp_logvar_head" in L.SYMBOLS
+    assert hasattr(L.lib, "bbmpc_set_mlp_logvar_head") and L.LOGVAR_ABS_MAX == 40.0
+    assert L.lib.bbmpc_set_mlp_logvar_head(None, 1, None, None, None, None) == L.E_INVALID and b"null handle" in L.lib.bbmpc_last_error()
+    from blackbox_mpc_amd.engine import Engine
+    assert callable(Engine.set_mlp_logvar_head)
+
+
+@pytest.mark.parametrize("normalized", [True, False])
+def test_ensemble_training_with_heads_is_dense_trainer_fit_on_the_bootstrap_rows(normalized):
+    from blackbox_mpc_amd.dynamics_functions import EnsembleMLP
+    from blackbox_mpc_amd.dynamics_functions._train_torch import DenseTrainer
+    from blackbox_mpc_amd.dynamics_handlers.system_dynamics_handler import SystemDynamicsHandler
+    from tests.test_train_cpu import _episodes
+    obs, acs, rews = _episodes(4, 40, 2, 2)
+    E, epochs, batch, lr = 2, 3, 32, 2e-3
+    fn = EnsembleMLP([4, 16, 16, 3], ["tanh", "relu", None], num_members=E, seed=3, probabilistic=True)
+    h = SystemDynamicsHandler(*_spaces(), dynamics_function=fn, is_normalized=normalized)
+    start = [([w.copy() for w in m.weights], [b.copy() for b in m.biases], m.logvar_weights.copy(), m.logvar_bias.copy()) for m in fn.members]
+    rng = np.random.default_rng(4)
+    mask = rng.random(4 * 2 * 40) > 0.25
+    n = int(mask.sum())
+    boot = rng.integers(0, n, size=(E, n))
+    perms = [[rng.permutation(n) for _ in range(epochs)] for _ in range(E)]
+    h.train(obs, acs, rews, batch_size=batch, learning_rate=lr, epochs=epochs, device="cpu", seed=7, split_mask=mask,
+            permutations=perms, bootstrap_indices=boot)
+    tin, tout = h._normalize_data(h._model_training_in, h._model_training_out)
+    vin, vout = h._normalize_data(h._model_validation_in, h._model_validation_out)
+    rms = []
+    for e in range(E):
+        m = fn.members[e]
+        tr = DenseTrainer(start[e][0], start[e][1], fn.activation_codes, "cpu", learning_rate=lr, rule="adam",
+                          logvar_head=(start[e][2], start[e][3], m.min_logvar, m.max_logvar))
+        tl, vl = tr.fit(tin[boot[e]], tout[boot[e]], vin, vout, epochs, batch, permutations=perms[e], generator_seed=7)
+        ws, bs = tr.numpy_params()
+        wv, bv = tr.numpy_logvar_head()
+        for x, y in zip(ws + bs + [wv, bv], m.weights + m.biases + [m.logvar_weights, m.logvar_bias]):
+            np.testing.assert_array_equal(x, y)
+        np.testing.assert_array_equal(h.member_training_loss[e], tl)
+        np.testing.assert_array_equal(h.member_validation_loss[e], vl)
+        assert not np.array_equal(wv, start[e][2]) and not np.array_equal(ws[0], start[e][0][0])       # both trained
+        # the losses are the NLL, not the MSE: the NLL of the fitted model on the validation batches, from the formulas
+        nvb = vin.shape[0] // batch
+        import torch
+        with torch.no_grad():
+            d = tr.nll(torch.as_tensor(vin[:nvb * batch]), torch.as_tensor(vout[:nvb * batch])).reshape(nvb, -1).mean(dim=1).mean()
+        assert vl[-1] == float(d)
+        rms.append(tr.residual_rms(vin, vout).astype(np.float64))
+    np.testing.assert_array_equal(h.training_loss, h.member_training_loss[0])
+    # residual_std stays the mean networks' residual
+    want = np.sqrt(np.mean(np.square(np.array(rms)), axis=0))
+    if normalized:
+        want = want * (h.normalization_stats()[5].astype(np.float64) + 1e-7)
+    np.testing.assert_allclose(h.residual_std(), want, rtol=1e-6)
+
+
+def test_single_model_training_passes_the_head():
+    from blackbox_mpc_amd.dynamics_functions import ProbabilisticMLP
+    from blackbox_mpc_amd.dynamics_functions._train_torch import DenseTrainer
+    from blackbox_mpc_amd.dynamics_handlers.system_dynamics_handler import SystemDynamicsHandler
+    from tests.test_train_cpu import _episodes
+    obs, acs, rews = _episodes(2, 40, 2, 2)
+    fn = ProbabilisticMLP([4, 16, 16, 3], ["tanh", "relu", None], seed=3)
+    h = SystemDynamicsHandler(*_spaces(), dynamics_function=fn, is_normalized=True)
+    w0, b0, wv0, bv0 = [w.copy() for w in fn.weights], [b.copy() for b in fn.biases], fn.logvar_weights.copy(), fn.logvar_bias.copy()
+    rng = np.random.default_rng(1)
+    mask = rng.random(2 * 2 * 40) > 0.25
+    perms = [rng.permutation(int(mask.sum())) for _ in range(2)]
+    v = fn._version
+    h.train(obs, acs, rews, batch_size=32, epochs=2, device="cpu", split_mask=mask, permutations=perms)
+    assert fn._version == v + 2
+    tin, tout = h._normalize_data(h._model_training_in, h._model_training_out)
+    vin, vout = h._normalize_data(h._model_validation_in, h._model_validation_out)
+    tr = DenseTrainer(w0, b0, fn.activation_codes, "cpu", logvar_head=(wv0, bv0, fn.min_logvar, fn.max_logvar))
+    tl, vl = tr.fit(tin, tout, vin, vout, 2, 32, permutations=perms)
+    np.testing.assert_array_equal(h.training_loss, tl)
+    np.testing.assert_array_equal(h.validation_loss, vl)
+    np.testing.assert_array_equal(fn.logvar_weights, tr.numpy_logvar_head()[0])
+    np.testing.assert_array_equal(fn.weights[0], tr.numpy_params()[0][0])
+    np.testing.assert_allclose(h.residual_std(), tr.residual_rms(vin, vout) * (h.normalization_stats()[5] + F(1e-7)), rtol=1e-6)
