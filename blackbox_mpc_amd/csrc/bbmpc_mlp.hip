@@ -8,8 +8,6 @@
 #include "engine_util.hpp"
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
-#include "kernels_mlp_ensemble.hpp"
-#include "kernels_mlp_gaussian.hpp"
 
 namespace bbmpc {
 
@@ -183,7 +181,7 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
     mlp_ready = true;
 }
 
-// bbmpc_set_mlp_ensemble: E networks of the installed model's shape for the particle rollouts (kernels_mlp_ensemble.hpp).
+// bbmpc_set_mlp_ensemble: E networks of the installed model's shape for the particle rollouts (kernels_mlp_particles.hpp).
 // w, b: [E][n_layers] pointers, member-major, in bbmpc_set_mlp's layouts.  Every member is packed on the host before the
 // handle is touched, so a refusal leaves it as it was.
 void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* b) {
@@ -222,7 +220,7 @@ void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* 
     ens_E = E;
 }
 
-// bbmpc_set_mlp_logvar_head: one log-variance head per model of the particle rollouts (kernels_mlp_gaussian.hpp) -- the
+// bbmpc_set_mlp_logvar_head: one log-variance head per model of the particle rollouts (kernels_mlp_particles.hpp) -- the
 // handle's model, or each member of its ensemble.  w [num_heads] pointers to [dims[L-1]][S] kernels, b to [S] biases: the last
 // layer's layouts.  Packed on the host before the handle is touched, so a refusal leaves it as it was.
 void Engine::set_mlp_logvar_head(int num_heads, const float* const* w, const float* const* b, const float* min_logvar,
@@ -521,92 +519,63 @@ void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int 
     HIP_CHECK(hipGetLastError());
 }
 
-// Particle rollouts of a learned model with a built-in reward (bbmpc_set_particles): one launch of k_rollout_mlp_particles,
-// 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp, always fp32; with an ensemble
-// installed (bbmpc_set_mlp_ensemble), one launch of k_rollout_mlp_particles_ens instead; with log-variance heads
-// (bbmpc_set_mlp_logvar_head), with or without an ensemble, one launch of k_rollout_mlp_particles_gauss
+// Particle rollouts of a learned model with a built-in reward (bbmpc_set_particles): one launch of the frame of
+// kernels_mlp_particles.hpp, 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp,
+// always fp32.  Kind MLP_PART_PLAIN; with an ensemble installed (bbmpc_set_mlp_ensemble) MLP_PART_ENS, rows grouped by
+// member and grid.z = member; with log-variance heads (bbmpc_set_mlp_logvar_head), with or without an ensemble,
+// MLP_PART_GAUSS (without an ensemble one "member", the primary's operands at stride 0)
 void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
-    MlpParticleArgs q;
-    memset(&q, 0, sizeof(q));
-    q.m = mlp;
-    for (int l = 0; l < mlp.n_layers; ++l) q.wp4[l] = d_wpack4[l].p;
-    q.nw = mlp_nw;
-    q.p = pa;
-    const size_t lds = (size_t)mlp_traj_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+    size_t lds = (size_t)mlp_traj_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
     REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the activation / partial-sum buffers of this network do not fit one CU's LDS");
-    bool ext = false;
-    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
-    const void* fn = ext ? (const void*)k_rollout_mlp_particles<true> : (const void*)k_rollout_mlp_particles<false>;
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-    const long rows = (long)pa.n_pop * pa.P;
     // (the kernel addresses its action source and the noise with 32-bit offsets)
     const long act_elems = pa.from_ref ? (long)pa.n_pop * A * pa.HU : (long)A * pa.HU * pa.Nst;
     REQUIRE(act_elems < (1L << 31) && (long)A * pa.P * pa.H * S < (1L << 31), BBMPC_E_UNSUPPORTED,
             "particle rollout: more than 2^31 action or noise elements per launch");
-    if (lv_heads > 0) {
-        // probabilistic models: the ensemble kernel's frame with the head behind the last layer (kernels_mlp_gaussian.hpp);
-        // without an ensemble one "member", the primary's operands at stride 0
-        const int E = std::max(1, ens_E);
-        REQUIRE(lv_heads == E && pa.P % E == 0, BBMPC_E_INVALID, "internal: log-variance heads per model");
-        MlpGaussParticleArgs qg;
-        memset(&qg, 0, sizeof(qg));
-        qg.m = mlp;
+    const int kind = lv_heads > 0 ? MLP_PART_GAUSS : ens_E > 0 ? MLP_PART_ENS : MLP_PART_PLAIN;
+    const int E = std::max(1, ens_E);
+    if (kind == MLP_PART_GAUSS) REQUIRE(lv_heads == E && pa.P % E == 0, BBMPC_E_INVALID, "internal: log-variance heads per model");
+    if (kind == MLP_PART_ENS) REQUIRE(pa.P % E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");
+    const long rows = (long)pa.n_pop * (pa.P / E);            // per (agent, member)
+    dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), A, E), block(mlp_nw * 64);
+    bool ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    // the arguments of kind ARGS::KIND and its launch (the kernel takes exactly this one struct by value)
+    auto launch = [&](auto q) {
+        using ARGS = decltype(q);
+        memset(&q, 0, sizeof(q));
+        q.m = mlp;
+        q.nw = mlp_nw;
+        q.p = pa;
         for (int l = 0; l < mlp.n_layers; ++l) {
-            qg.wp4[l] = ens_E > 0 ? d_ens_wp4[l].p : d_wpack4[l].p;
-            qg.m.bpack[l] = ens_E > 0 ? d_ens_bp[l].p : d_bpack[l].p;
-            qg.wstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * mlp.tiles[l] * 256 : 0;
-            qg.bstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * 256 : 0;
+            q.wp4[l] = ens_E > 0 ? d_ens_wp4[l].p : d_wpack4[l].p;
+            q.m.bpack[l] = ens_E > 0 ? d_ens_bp[l].p : d_bpack[l].p;
+            if constexpr (ARGS::KIND != MLP_PART_PLAIN) {
+                q.wstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * mlp.tiles[l] * 256 : 0;
+                q.bstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * 256 : 0;
+            }
         }
-        const int Ll = mlp.n_layers - 1;
-        qg.hp4 = d_lv_wp4.p;
-        qg.hbp = d_lv_bp.p;
-        qg.hwstride = mlp.tiles[Ll + 1] * mlp.tiles[Ll] * 256;
-        qg.hbstride = mlp.tiles[Ll + 1] * 256;
-        qg.min_logvar = d_lv_bounds.p;
-        qg.max_logvar = d_lv_bounds.p + S;
-        qg.nw = mlp_nw;
-        qg.E = E;
-        qg.p = pa;
-        const size_t glds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
-        REQUIRE(glds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
-        const void* fg = ext ? (const void*)k_rollout_mlp_particles_gauss<true> : (const void*)k_rollout_mlp_particles_gauss<false>;
-        if (glds > 64 * 1024) ensure_max_lds(fg, 159 * 1024);
-        const long rows_e = (long)pa.n_pop * (pa.P / E);
-        dim3 ggrid((unsigned)((rows_e + MLP_TP - 1) / MLP_TP), A, E), gblock(mlp_nw * 64);
-        if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles_gauss<true>, ggrid, gblock, glds, stream, qg);
-        else hipLaunchKernelGGL(k_rollout_mlp_particles_gauss<false>, ggrid, gblock, glds, stream, qg);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (ens_E > 0) {
-        // trajectory sampling: rows grouped by member, grid.z = member (kernels_mlp_ensemble.hpp)
-        REQUIRE(pa.P % ens_E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");
-        MlpEnsParticleArgs qe;
-        memset(&qe, 0, sizeof(qe));
-        qe.m = mlp;
-        for (int l = 0; l < mlp.n_layers; ++l) {
-            qe.wp4[l] = d_ens_wp4[l].p;
-            qe.m.bpack[l] = d_ens_bp[l].p;
-            qe.wstride[l] = mlp.tiles[l + 1] * mlp.tiles[l] * 256;
-            qe.bstride[l] = mlp.tiles[l + 1] * 256;
+        if constexpr (ARGS::KIND != MLP_PART_PLAIN) q.E = E;
+        if constexpr (ARGS::KIND == MLP_PART_GAUSS) {
+            const int Ll = mlp.n_layers - 1;
+            q.hp4 = d_lv_wp4.p;
+            q.hbp = d_lv_bp.p;
+            q.hwstride = mlp.tiles[Ll + 1] * mlp.tiles[Ll] * 256;
+            q.hbstride = mlp.tiles[Ll + 1] * 256;
+            q.min_logvar = d_lv_bounds.p;
+            q.max_logvar = d_lv_bounds.p + S;
+            lds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+            REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
         }
-        qe.nw = mlp_nw;
-        qe.E = ens_E;
-        qe.p = pa;
-        const void* fe = ext ? (const void*)k_rollout_mlp_particles_ens<true> : (const void*)k_rollout_mlp_particles_ens<false>;
-        if (lds > 64 * 1024) ensure_max_lds(fe, 159 * 1024);
-        const long rows_e = (long)pa.n_pop * (pa.P / ens_E);
-        dim3 egrid((unsigned)((rows_e + MLP_TP - 1) / MLP_TP), A, ens_E), eblock(mlp_nw * 64);
-        if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles_ens<true>, egrid, eblock, lds, stream, qe);
-        else hipLaunchKernelGGL(k_rollout_mlp_particles_ens<false>, egrid, eblock, lds, stream, qe);
+        const void* fn = ext ? (const void*)k_rollout_mlp_particles_kind<ARGS, true> : (const void*)k_rollout_mlp_particles_kind<ARGS, false>;
+        if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+        if (ext) hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, true>), grid, block, lds, stream, q);
+        else hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, false>), grid, block, lds, stream, q);
         HIP_CHECK(hipGetLastError());
-        return;
-    }
-    dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), A), block(mlp_nw * 64);
-    if (ext) hipLaunchKernelGGL(k_rollout_mlp_particles<true>, grid, block, lds, stream, q);
-    else hipLaunchKernelGGL(k_rollout_mlp_particles<false>, grid, block, lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    };
+    if (kind == MLP_PART_GAUSS) launch(MlpGaussParticleArgs());
+    else if (kind == MLP_PART_ENS) launch(MlpEnsParticleArgs());
+    else launch(MlpParticleArgs());
 }
 
 }  // namespace bbmpc

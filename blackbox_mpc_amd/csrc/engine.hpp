@@ -420,12 +420,12 @@ struct Engine {
     void dump_process_noise(int control_step, int iteration, float* out, int64_t count);
     void rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_returns, int returns_stride);
     void launch_rollout_mlp_particles(const ParticleArgs& pa);                 // bbmpc_mlp.hip
-    // model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble; bbmpc_mlp.hip, kernels_mlp_ensemble.hpp): particle p
+    // model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble; bbmpc_mlp.hip, kernels_mlp_particles.hpp): particle p
     // follows member p % ens_E.  Every deterministic path keeps the model of bbmpc_set_mlp.
     int ens_E = 0;
     DevBuf<float> d_ens_wp4[MLP_MAX_LAYERS], d_ens_bp[MLP_MAX_LAYERS];   // per layer [E][OT][IT][64][4] | [E][OT][64][4]
     void set_mlp_ensemble(int E, const float* const* w, const float* const* b);
-    // log-variance heads of the model / of every member (bbmpc_set_mlp_logvar_head; bbmpc_mlp.hip, kernels_mlp_gaussian.hpp):
+    // log-variance heads of the model / of every member (bbmpc_set_mlp_logvar_head; bbmpc_mlp.hip, kernels_mlp_particles.hpp):
     // the particle rollouts add (sigma + sd(s, a)) * eps.  lv_heads = max(1, ens_E) while installed, else 0; removed by
     // bbmpc_set_mlp and bbmpc_set_mlp_ensemble.  No deterministic path reads them.
     int lv_heads = 0;

@@ -17,14 +17,22 @@ F = np.float32
 SIGMA = 0.02                                    # process noise of the GPU cases (tests/test_gpu_particles.py's)
 MARGIN_TOL = 2e-4                               # parity_util.assert_cheetah_rewards' default margin_tol
 SWISH_NET = ([26, 200, 200, 20], ["swish", "swish", None], 20, 6, "cheetah")      # an activation after sigmoid: EXT kernels
+# A narrow net with wide state and action: 16 hidden units run ONE wave of 64 threads, and the tiles [S][16] = 320 noise
+# and [16][U] = 160 action elements exceed the 2 * 64 a workgroup holds in registers -- the only cases in which the particle
+# kernels fetch noise and actions on their fall-back paths.  N 5, P 4: 20 rows per agent (a full and a partial tile), with
+# E = 2 10 rows per member.  Checked on the CPU for every case built on it here, in tests/test_gaussian_cpu.py and in
+# tests/test_gpu_particles.py (model seed 42, the input seeds those cases use): the float32 helper meets rtol / atol of the
+# GPU tests against a float64 evaluation of the same recurrence on every row, and no visited state comes within margin_tol
+# per step of an indicator threshold (smallest margin 5.6e-4), so assert_cheetah_rewards has no flip to let through.
+NARROW_NET = ([30, 16, 16, 20], ["tanh", "tanh", None], 20, 10, "cheetah")
 # (network, N, A, P, E, H, seed) of tests/test_gpu_ensemble.py::test_returns_match_the_helper
 CASES = [("CHEETAH", 5, 1, 6, 3, 2, 42), ("CHEETAH", 37, 3, 4, 2, 12, 42), ("PEND_MLP", 33, 2, 16, 8, 9, 42),
-         ("PEND_MLP", 33, 2, 3, 1, 9, 42), ("SWISH", 5, 1, 6, 3, 2, 42)]
+         ("PEND_MLP", 33, 2, 3, 1, 9, 42), ("SWISH", 5, 1, 6, 3, 2, 42), ("NARROW", 5, 2, 4, 2, 3, 42)]
 
 
 def network(name):
     from tests import test_gpu_mlp as TM
-    return SWISH_NET if name == "SWISH" else getattr(TM, name)
+    return {"SWISH": SWISH_NET, "NARROW": NARROW_NET}.get(name) or getattr(TM, name)
 
 
 def member_params(dims, seed, e):

@@ -19,9 +19,10 @@ SIGMA = TE.SIGMA
 MARGIN_TOL = TE.MARGIN_TOL
 # (network, N, A, P, E, H, seed, normalized) of tests/test_gpu_gaussian.py::test_returns_match_the_helper; E = 1: no ensemble
 CASES = [("PEND_MLP", 33, 2, 3, 1, 9, 42, True), ("PEND_MLP", 33, 2, 16, 8, 9, 42, True), ("CHEETAH", 5, 1, 6, 3, 2, 42, True),
-         ("CHEETAH", 37, 3, 4, 2, 12, 42, True), ("SWISH", 5, 1, 6, 3, 2, 42, True), ("PEND_MLP", 33, 2, 4, 2, 9, 42, False)]
+         ("CHEETAH", 37, 3, 4, 2, 12, 42, True), ("SWISH", 5, 1, 6, 3, 2, 42, True), ("PEND_MLP", 33, 2, 4, 2, 9, 42, False),
+         ("NARROW", 5, 2, 4, 1, 3, 42, True), ("NARROW", 5, 2, 4, 2, 3, 42, True)]     # (test_ensemble_cpu.NARROW_NET: the fall-back fetches)
 # the seeds of the cases' inputs, chosen on the helper alone so that the cheetah cases meet the margin condition below
-INPUT_SEEDS = [3000, 3001, 3002, 3003, 3005, 3006]
+INPUT_SEEDS = [3000, 3001, 3002, 3003, 3005, 3006, 3007, 3009]
 # gaussian case -> test_ensemble_cpu.CASES' case of the same (network family, N, A, H)
 _ENSEMBLE_CASE = {2: 0, 3: 1, 4: 4}
 

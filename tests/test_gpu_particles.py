@@ -91,12 +91,14 @@ def _mlp_problem(L, spec, A, H, **kw):
 
 
 def _mlp_specs():
+    from tests.test_ensemble_cpu import NARROW_NET
     from tests.test_gpu_mlp import CHEETAH, PEND_MLP
-    # cheetah: 15 and 148 rows per agent in 16-row tiles that mix candidates, the second with a partial last tile
-    return [(CHEETAH, 5, 1, 3, 2), (CHEETAH, 37, 3, 4, 12), (PEND_MLP, 33, 2, 16, 9)]
+    # cheetah: 15 and 148 rows per agent in 16-row tiles that mix candidates, the second with a partial last tile; the narrow
+    # net: one wave, noise and actions on the fall-back fetches (tests/test_ensemble_cpu.py, also for how its inputs were checked)
+    return [(CHEETAH, 5, 1, 3, 2), (CHEETAH, 37, 3, 4, 12), (PEND_MLP, 33, 2, 16, 9), (NARROW_NET, 5, 2, 4, 3)]
 
 
-@pytest.mark.parametrize("case", range(3))
+@pytest.mark.parametrize("case", range(4))
 def test_mlp_particle_returns_match_the_helper(L, case):
     spec, N, A, P, H = _mlp_specs()[case]
     eng, ev, S, U, reward = _mlp_problem(L, spec, A, H)
