@@ -9,9 +9,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbbmpc.so")
 # engine + ABI | persistent pendulum kernels | CMA-ES | learned-model rollouts | user functions (hiprtc) + their ABI |
-# trajectory prediction + its ABI | particle trajectory evaluator + its ABI
+# trajectory prediction + its ABI | particle trajectory evaluator + its ABI | trajectory distributions + their ABI
 SOURCES = ["bbmpc.hip", "bbmpc_fused.hip", "bbmpc_cma.hip", "bbmpc_mlp.hip", "bbmpc_user.hip", "bbmpc_traj.hip",
-           "bbmpc_particles.hip"]
+           "bbmpc_particles.hip", "bbmpc_traj_particles.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          # one rounding per reference op: never contract a*b+c behind the source's back
          "-ffp-contract=off",

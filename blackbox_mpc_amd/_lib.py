@@ -85,6 +85,7 @@ SYMBOLS = [
     "bbmpc_set_keep_plan", "bbmpc_get_plan",
     "bbmpc_set_particles", "bbmpc_evaluate_particles", "bbmpc_evaluate_particles_dev",
     "bbmpc_set_mlp_ensemble", "bbmpc_set_mlp_logvar_head",
+    "bbmpc_predict_trajectory_particles", "bbmpc_predict_trajectory_particles_dev",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -174,6 +175,8 @@ def _load():
     lib.bbmpc_evaluate_particles_dev.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.bbmpc_set_mlp_ensemble.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     lib.bbmpc_set_mlp_logvar_head.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
+    lib.bbmpc_predict_trajectory_particles.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.bbmpc_predict_trajectory_particles_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

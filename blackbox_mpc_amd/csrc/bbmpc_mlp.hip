@@ -8,6 +8,7 @@
 #include "engine_util.hpp"
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
+#include "kernels_mlp_traj_particles.hpp"
 
 namespace bbmpc {
 
@@ -576,6 +577,59 @@ void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     if (kind == MLP_PART_GAUSS) launch(MlpGaussParticleArgs());
     else if (kind == MLP_PART_ENS) launch(MlpEnsParticleArgs());
     else launch(MlpParticleArgs());
+}
+
+// bbmpc_predict_trajectory_particles on a learned model with a built-in reward: one launch of the frame of
+// kernels_mlp_traj_particles.hpp, 16 (b, p) rows per workgroup, grid.z = member; the kinds, operands and LDS limits of
+// launch_rollout_mlp_particles above
+void Engine::launch_traj_mlp_particles(const TrajParticleArgs& pa) {
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    size_t lds = (size_t)mlp_traj_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the activation / partial-sum buffers of this network do not fit one CU's LDS");
+    const int kind = lv_heads > 0 ? MLP_PART_GAUSS : ens_E > 0 ? MLP_PART_ENS : MLP_PART_PLAIN;
+    const int E = std::max(1, ens_E);
+    if (kind == MLP_PART_GAUSS) REQUIRE(lv_heads == E && pa.P % E == 0, BBMPC_E_INVALID, "internal: log-variance heads per model");
+    if (kind == MLP_PART_ENS) REQUIRE(pa.P % E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");
+    const long rows = (long)pa.B * (pa.P / E);                // per member
+    dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), 1, E), block(mlp_nw * 64);
+    bool ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    auto launch = [&](auto q) {
+        using ARGS = decltype(q);
+        memset(&q, 0, sizeof(q));
+        q.m = mlp;
+        q.nw = mlp_nw;
+        q.p = pa;
+        for (int l = 0; l < mlp.n_layers; ++l) {
+            q.wp4[l] = ens_E > 0 ? d_ens_wp4[l].p : d_wpack4[l].p;
+            q.m.bpack[l] = ens_E > 0 ? d_ens_bp[l].p : d_bpack[l].p;
+            if constexpr (ARGS::KIND != MLP_PART_PLAIN) {
+                q.wstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * mlp.tiles[l] * 256 : 0;
+                q.bstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * 256 : 0;
+            }
+        }
+        if constexpr (ARGS::KIND != MLP_PART_PLAIN) q.E = E;
+        if constexpr (ARGS::KIND == MLP_PART_GAUSS) {
+            const int Ll = mlp.n_layers - 1;
+            q.hp4 = d_lv_wp4.p;
+            q.hbp = d_lv_bp.p;
+            q.hwstride = mlp.tiles[Ll + 1] * mlp.tiles[Ll] * 256;
+            q.hbstride = mlp.tiles[Ll + 1] * 256;
+            q.min_logvar = d_lv_bounds.p;
+            q.max_logvar = d_lv_bounds.p + S;
+            lds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
+            REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
+        }
+        const size_t lds_all = lds + MLP_TRAJ_PART_ROWMAP * sizeof(int);       // (the row map of the tile lies behind the layout)
+        const void* fn = ext ? (const void*)k_traj_mlp_particles_kind<ARGS, true> : (const void*)k_traj_mlp_particles_kind<ARGS, false>;
+        if (lds_all > 64 * 1024) ensure_max_lds(fn, 159 * 1024 + MLP_TRAJ_PART_ROWMAP * (int)sizeof(int));
+        if (ext) hipLaunchKernelGGL((k_traj_mlp_particles_kind<ARGS, true>), grid, block, lds_all, stream, q);
+        else hipLaunchKernelGGL((k_traj_mlp_particles_kind<ARGS, false>), grid, block, lds_all, stream, q);
+        HIP_CHECK(hipGetLastError());
+    };
+    if (kind == MLP_PART_GAUSS) launch(MlpGaussTrajParticleArgs());
+    else if (kind == MLP_PART_ENS) launch(MlpEnsTrajParticleArgs());
+    else launch(MlpTrajParticleArgs());
 }
 
 }  // namespace bbmpc

@@ -1,0 +1,130 @@
+// Trajectory distributions (bbmpc_predict_trajectory_particles[_dev]; kernels_traj_particles.hpp):
+// the particle recurrence of bbmpc_set_particles from every row's own start state with every state and reward kept, and
+// the per-step mean / std over the particles.  The launch sequence  draws (unless supplied) -> noisy trajectories of every
+// (b, p) row -> moments, and the ABI.  The learned model's trajectory kernel is launched from bbmpc_mlp.hip.
+#include "abi_util.hpp"
+#include "kernels_traj_particles.hpp"
+
+namespace bbmpc {
+
+// what both entry points refuse, before anything is allocated, copied or launched
+static void check_traj_particles(const Engine& e, int batch, int horizon, bool any_out) {
+    REQUIRE(e.particles_on(), BBMPC_E_STATE, "trajectory distribution: particles are off: call bbmpc_set_particles first");
+    REQUIRE(batch >= 1, BBMPC_E_INVALID, "batch must be >= 1");
+    REQUIRE(horizon >= 1 && horizon <= 4096, BBMPC_E_INVALID, "horizon must be in [1, 4096]");
+    REQUIRE(any_out, BBMPC_E_INVALID, "all six outputs are null");
+    REQUIRE(!e.user_path(), BBMPC_E_UNSUPPORTED, "particles with user-supplied functions or an inverse target transform");
+    if (e.cfg.dynamics == BBMPC_DYN_MLP) REQUIRE(e.mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    const long qp = ((long)horizon * e.S + 3) / 4;
+    REQUIRE((long)batch * e.part_P * horizon * e.S < (1L << 31) && (long)batch * horizon * e.U < (1L << 31), BBMPC_E_UNSUPPORTED,
+            "trajectory distribution: more than 2^31 particle-state or action elements per call");
+    REQUIRE((long)batch * qp < (1L << 32), BBMPC_E_UNSUPPORTED, "trajectory distribution: more than 2^32 noise blocks per call");
+}
+
+void Engine::predict_trajectory_particles_dev(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps,
+                                              float* d_smean, float* d_sstd, float* d_rmean, float* d_rstd, float* d_pstates, float* d_prewards) {
+    check_traj_particles(*this, batch, horizon, d_smean || d_sstd || d_rmean || d_rstd || d_pstates || d_prewards);
+    const int P = part_P;
+    const size_t nps = (size_t)batch * P * horizon * S, npr = (size_t)batch * P * horizon;
+    if (!d_eps) {
+        // the handle's own draws: the process-noise stream with the row in the agent word, the handle's current control step,
+        // iteration 0 -- at batch = A, horizon = H the tensor bbmpc_evaluate_particles rolls
+        if (tjp_noise.n < nps) tjp_noise.alloc(nps);
+        RngKey kk = key(step_counter);
+        kk.q_per_agent = (uint32_t)((horizon * S + 3) / 4);
+        kk.step_src = nullptr;
+        // (k_gen_process_noise indexes its batch * P * Qp blocks in int: below 2^29 + batch * P behind check_traj_particles'
+        // batch * P * horizon * S < 2^31)
+        const long blocks = (long)batch * P * kk.q_per_agent;
+        hipLaunchKernelGGL(k_gen_process_noise, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, stream, kk, 0u, batch, P, horizon * S,
+                           cfg.agent_offset, tjp_noise.p);
+        HIP_CHECK(hipGetLastError());
+        d_eps = tjp_noise.p;
+    }
+    if (!d_pstates) {
+        if (tjp_ps.n < nps) tjp_ps.alloc(nps);
+        d_pstates = tjp_ps.p;
+    }
+    if (!d_prewards) {
+        if (tjp_pr.n < npr) tjp_pr.alloc(npr);
+        d_prewards = tjp_pr.p;
+    }
+    TrajParticleArgs q;
+    memset(&q, 0, sizeof(q));
+    q.B = batch; q.P = P; q.Hq = horizon; q.U = U; q.S = S;
+    q.reward_kind = builtin_reward_kind();
+    q.fix_q1 = fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER) ? 1 : 0;
+    q.states = d_states; q.seq = d_seq;
+    q.sigma = d_psigma.p;
+    q.eps = d_eps;
+    q.pstates = d_pstates; q.prewards = d_prewards;
+    if (cfg.dynamics == BBMPC_DYN_MLP) {
+        launch_traj_mlp_particles(q);
+    } else {
+        const long rows = (long)batch * P;
+        const int bs = rows <= 16384 ? 64 : 256;           // few rows: one wave per workgroup, as k_rollout_pendulum_particles
+        hipLaunchKernelGGL(k_traj_pendulum_particles, dim3((unsigned)((rows + bs - 1) / bs)), dim3(bs), 0, stream, q);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (d_smean || d_sstd || d_rmean || d_rstd) {
+        const long n = ((d_smean || d_sstd) ? (long)batch * horizon * S : 0) + ((d_rmean || d_rstd) ? (long)batch * horizon : 0);
+        hipLaunchKernelGGL(k_traj_particle_moments, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)d_pstates,
+                           (const float*)d_prewards, batch, P, horizon, S, d_smean, d_sstd, d_rmean, d_rstd);
+        HIP_CHECK(hipGetLastError());
+    }
+}
+
+}  // namespace bbmpc
+
+extern "C" {
+
+int bbmpc_predict_trajectory_particles_dev(bbmpc_handle h, const float* d_states, const float* d_seq, int32_t batch, int32_t horizon,
+                                           const float* d_eps, float* d_state_mean, float* d_state_std, float* d_reward_mean,
+                                           float* d_reward_std, float* d_particle_states, float* d_particle_rewards) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_states);
+    CHECK_PTR(d_seq);
+    h->e->predict_trajectory_particles_dev(d_states, d_seq, batch, horizon, d_eps, d_state_mean, d_state_std, d_reward_mean, d_reward_std,
+                                           d_particle_states, d_particle_rewards);
+    API_END
+}
+
+int bbmpc_predict_trajectory_particles(bbmpc_handle h, const float* states, const float* seq, int32_t batch, int32_t horizon,
+                                       const float* eps, float* state_mean, float* state_std, float* reward_mean, float* reward_std,
+                                       float* particle_states, float* particle_rewards) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(states);
+    CHECK_PTR(seq);
+    Engine& e = *h->e;
+    bbmpc::check_traj_particles(e, batch, horizon, state_mean || state_std || reward_mean || reward_std || particle_states || particle_rewards);
+    const size_t P = (size_t)e.part_P;
+    const size_t ns = (size_t)batch * e.S, nq = (size_t)batch * horizon * e.U, nm = (size_t)batch * horizon * e.S, nr = (size_t)batch * horizon;
+    const size_t nps = nm * P, npr = nr * P;
+    // staging: states | sequences | eps | the outputs that are wanted, in the order of the arguments
+    float* const outs[6] = {state_mean, state_std, reward_mean, reward_std, particle_states, particle_rewards};
+    const size_t sizes[6] = {nm, nm, nr, nr, nps, npr};
+    size_t need = ns + nq + (eps ? nps : 0);
+    for (int i = 0; i < 6; ++i) need += outs[i] ? sizes[i] : 0;
+    if (e.tjp_io.n < need) e.tjp_io.alloc(need);
+    float* ds = e.tjp_io.p;
+    float* dq = ds + ns;
+    float* deps = eps ? dq + nq : nullptr;
+    float* next = dq + nq + (eps ? nps : 0);
+    float* douts[6];
+    for (int i = 0; i < 6; ++i) {
+        douts[i] = outs[i] ? next : nullptr;
+        next += outs[i] ? sizes[i] : 0;
+    }
+    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(dq, seq, nq * 4, hipMemcpyHostToDevice, e.stream));
+    if (eps) HIP_CHECK(hipMemcpyAsync(deps, eps, nps * 4, hipMemcpyHostToDevice, e.stream));
+    e.predict_trajectory_particles_dev(ds, dq, batch, horizon, deps, douts[0], douts[1], douts[2], douts[3], douts[4], douts[5]);
+    for (int i = 0; i < 6; ++i)
+        if (outs[i]) HIP_CHECK(hipMemcpyAsync(outs[i], douts[i], sizes[i] * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
+
+}  // extern "C"

@@ -36,6 +36,7 @@
 namespace bbmpc {
 
 struct ParticleArgs;       // kernels_particles.hpp
+struct TrajParticleArgs;   // kernels_traj_particles.hpp
 
 struct HipError : std::runtime_error {
     int code;
@@ -432,6 +433,14 @@ struct Engine {
     DevBuf<float> d_lv_wp4, d_lv_bp, d_lv_bounds;                        // [heads][OT][IT][64][4] | [heads][OT][64][4] | min [S], max [S]
     void set_mlp_logvar_head(int num_heads, const float* const* w, const float* const* b, const float* min_logvar, const float* max_logvar);
     void evaluate_particles_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_scores, float* d_returns);
+    // trajectory distributions (bbmpc_predict_trajectory_particles; bbmpc_traj_particles.hip, kernels_traj_particles.hpp): the
+    // particle recurrence from every row's own start state, every state and reward kept, and their moments over the particles.
+    // Buffers of its own: the draws [B][P][Hq][S] (never d_pnoise, whose validity flags belong to the control step), the
+    // particle tensors when the caller does not want them, the host call's staging.
+    DevBuf<float> tjp_noise, tjp_ps, tjp_pr, tjp_io;
+    void predict_trajectory_particles_dev(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps,
+                                          float* d_smean, float* d_sstd, float* d_rmean, float* d_rstd, float* d_pstates, float* d_prewards);
+    void launch_traj_mlp_particles(const TrajParticleArgs& pa);               // bbmpc_mlp.hip
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
     DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging

@@ -44,6 +44,21 @@ def multistep_windows(observations_trajectories, actions_trajectories, horizon, 
             np.ascontiguousarray(np.concatenate(obs_w, axis=0)))
 
 
+def calibration_z_rms(mean, std, observed):
+    """RMS over the windows of the standardised error of a predicted distribution: mean / std / observed [W, horizon, S]
+    -> z_rms [horizon, S] = sqrt(mean_w(((observed - mean) / max(std, 1e-12))^2)), in float64.  About 1 where the
+    predicted spread is honest, above 1 where it is too narrow (std = 0 against a wrong mean gives a huge value, not a
+    division by zero), below 1 where it is too wide."""
+    mean, std, observed = (np.asarray(v, np.float64) for v in (mean, std, observed))
+    if mean.ndim != 3 or mean.shape != std.shape or mean.shape != observed.shape:
+        raise ValueError("mean, std and observed must be equal [W, horizon, S] arrays, got %s, %s, %s"
+                         % (mean.shape, std.shape, observed.shape))
+    if mean.shape[0] == 0:
+        raise ValueError("calibration_z_rms: no window")
+    z = (observed - mean) / np.maximum(std, 1e-12)
+    return np.sqrt(np.mean(z * z, axis=0))
+
+
 def _logvar_head(fn):
     """DenseTrainer's `logvar_head` of a (member) model: (W_v, b_v, min_logvar, max_logvar), None for a plain model."""
     if not hasattr(fn, "logvar_weights"):
@@ -389,3 +404,23 @@ class SystemDynamicsHandler:
         rmse = np.sqrt(total / n).reshape(horizon, self._dim_S)
         self.multistep_rmse = (rmse, n)
         return rmse, n
+
+    def multistep_calibration(self, observations_trajectories, actions_trajectories, horizon, stride, evaluator):
+        """Is the spread a ParticleTrajectoryEvaluator predicts honest?  Every window of `horizon` steps
+        (multistep_windows) is rolled out from its first observation under the recorded actions as a particle distribution
+        (evaluator.predict_trajectory_distribution) and the recorded states are standardised against it.  Returns
+        (z_rms [horizon, dim_S] -- calibration_z_rms, about 1 for an honest spread -- and the number of windows) and keeps
+        it in `multistep_z_rms`."""
+        if not hasattr(evaluator, "predict_trajectory_distribution"):
+            raise TypeError("multistep_calibration() needs a ParticleTrajectoryEvaluator, got %s" % type(evaluator).__name__)
+        starts, acts, observed = multistep_windows(observations_trajectories, actions_trajectories, horizon, stride)
+        n = starts.shape[0]
+        if n == 0:
+            raise ValueError("multistep_calibration: no episode is %d steps long" % int(horizon))
+        if starts.shape[1] != self._dim_S or acts.shape[2] != self._dim_U:
+            raise ValueError("multistep_calibration: episodes of dim_S %d / dim_U %d for a handler of %d / %d"
+                             % (starts.shape[1], acts.shape[2], self._dim_S, self._dim_U))
+        mean, std = evaluator.predict_trajectory_distribution(starts, acts)[:2]
+        z_rms = calibration_z_rms(mean, std, observed)
+        self.multistep_z_rms = (z_rms, n)
+        return z_rms, n

@@ -454,6 +454,44 @@ class Engine:
                                                      int(batch), int(horizon), ctypes.c_void_p(d_states_out or 0),
                                                      ctypes.c_void_p(d_rewards_out or 0)))
 
+    def predict_trajectory_particles(self, states, action_sequences, eps=None, want_particles=False):
+        """Trajectory distributions (bbmpc_predict_trajectory_particles): states [B,S], action_sequences [B,Hq,U] ->
+        (state_mean [B,Hq,S], state_std [B,Hq,S], reward_mean [B,Hq], reward_std [B,Hq]) over the P particles of
+        set_particles, each rolled with process noise (and the ensemble member / log-variance head it follows) from the
+        row's own start state; with want_particles also (particle_states [B,P,Hq,S], particle_rewards [B,P,Hq]).
+        eps: standard normals [B,P,Hq,S], or None for the handle's own draws."""
+        states, seq = L.f32c(states), L.f32c(action_sequences)
+        b = states.shape[0] if states.ndim == 2 else -1
+        # the C side copies b*S, b*Hq*U and b*P*Hq*S floats from these buffers: a wrong shape must not become an out-of-bounds read
+        if states.shape != (b, self.S) or seq.ndim != 3 or seq.shape[0] != b or seq.shape[2] != self.U:
+            raise ValueError("states [B,%d] and action_sequences [B,Hq,%d] expected, got %s, %s"
+                             % (self.S, self.U, states.shape, seq.shape))
+        p = getattr(self, "P", 0)
+        if p <= 0:
+            raise ValueError("particles are off: call set_particles first")
+        hq = seq.shape[1]
+        if eps is not None:
+            eps = L.f32c(eps)
+            if eps.shape != (b, p, hq, self.S):
+                raise ValueError("eps must be [B, P, Hq, dim_S] = [%d, %d, %d, %d], got %s" % (b, p, hq, self.S, eps.shape))
+        outs = [np.empty((b, hq, self.S), np.float32), np.empty((b, hq, self.S), np.float32),
+                np.empty((b, hq), np.float32), np.empty((b, hq), np.float32)]
+        if want_particles:
+            outs += [np.empty((b, p, hq, self.S), np.float32), np.empty((b, p, hq), np.float32)]
+        ptrs = [L.ptr(o) for o in outs] + [None] * (6 - len(outs))
+        L.check(L.lib.bbmpc_predict_trajectory_particles(self._h, L.ptr(states), L.ptr(seq), b, hq, L.ptr(eps), *ptrs))
+        return tuple(outs)
+
+    def predict_trajectory_particles_dev(self, d_states, d_action_sequences, batch, horizon, d_eps=0, d_state_mean=0,
+                                         d_state_std=0, d_reward_mean=0, d_reward_std=0, d_particle_states=0,
+                                         d_particle_rewards=0):
+        """The same on device addresses, enqueued on the handle's stream (any output may be 0, not all six; d_eps = 0: the
+        handle's own draws)."""
+        L.check(L.lib.bbmpc_predict_trajectory_particles_dev(
+            self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_action_sequences), int(batch), int(horizon),
+            *[ctypes.c_void_p(v or 0) for v in (d_eps, d_state_mean, d_state_std, d_reward_mean, d_reward_std,
+                                                d_particle_states, d_particle_rewards)]))
+
     def set_keep_plan(self, enabled=True):
         """Opt-in switch of plan readback (bbmpc_set_keep_plan): the control steps that follow keep their solution in HBM
         (the routing of set_trace: same results, slower paths).  Off by default."""

@@ -86,6 +86,24 @@ class OptimizerBase:
         states, rewards = eng.predict_trajectories(np.asarray(current_state, np.float32), actions)
         return actions, states, rewards
 
+    def plan_distribution(self, current_state):
+        """(actions [A,H,U], state_mean [A,H,S], state_std [A,H,S], reward_mean [A,H], reward_std [A,H]): the plan of
+        `plan`, rolled out from `current_state` once per particle of the ParticleTrajectoryEvaluator -- process noise, the
+        ensemble member a particle follows, the noise a log-variance head predicts -- and reduced to its per-step mean and
+        spread.  Needs keep_plan(True) before the call whose plan is wanted, and a ParticleTrajectoryEvaluator."""
+        if getattr(self._trajectory_evaluator, "particle_settings", None) is None:
+            raise TypeError("plan_distribution() needs a ParticleTrajectoryEvaluator (the optimizer's evaluator is %s, which is "
+                            "deterministic: use plan())" % type(self._trajectory_evaluator).__name__)
+        eng = self._require_engine()
+        try:
+            actions = eng.get_plan()
+        except L.BBMPCError as ex:
+            if ex.code == L.E_STATE:
+                raise RuntimeError("plan_distribution(): plan readback was not on during the last call -- switch it on with "
+                                   "optimizer.keep_plan(True) (MPCPolicy.keep_plan(True)) before calling the optimizer") from ex
+            raise
+        return (actions,) + eng.predict_trajectory_particles(np.asarray(current_state, np.float32), actions)
+
     def reset(self):
         if type(self)._engine_optimizer == L.OPT_NONE:
             raise Exception("reset function is not implemented yet")

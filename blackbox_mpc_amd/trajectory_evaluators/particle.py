@@ -44,11 +44,24 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
     def _particle_engine(self, seq):
         if seq.ndim != 4:
             raise ValueError("action_sequences must be [population, num_agents, planning_horizon, dim_U]")
-        eng = self._engine(seq.shape[1], seq.shape[2])
+        return self._apply_particles(self._engine(seq.shape[1], seq.shape[2]))
+
+    def _apply_particles(self, eng):
+        """The particle settings on `eng` unless they are this evaluator's already."""
         if getattr(eng, "P", 0) != self._num_particles or getattr(eng, "_particle_settings", None) is not self:
             eng.set_particles(*self.particle_settings)
             eng._particle_settings = self
         return eng
+
+    def predict_trajectory_distribution(self, current_states, action_sequences, eps=None, return_particles=False):
+        """current_states [B,S], action_sequences [B,Hq,U] -> (state_mean [B,Hq,S], state_std [B,Hq,S], reward_mean [B,Hq],
+        reward_std [B,Hq]) over the particles, each rolled open loop from the row's own start state with this evaluator's
+        process noise -- and, with an EnsembleMLP / ProbabilisticMLP handler, the member it follows and the noise its head
+        predicts; with return_particles also (particle_states [B,P,Hq,S], particle_rewards [B,P,Hq]).  eps: standard
+        normals [B,P,Hq,S], or None for the engine's own draws.  Served by the one-step calls' engine, as
+        predict_trajectories (Hq is free of any planning horizon)."""
+        eng = self._apply_particles(self._engine(self._one_step_agents(), 1))
+        return eng.predict_trajectory_particles(current_states, action_sequences, eps=eps, want_particles=return_particles)
 
     def __call__(self, current_states, action_sequences, time_step=0):
         """current_states [A,S], action_sequences [N,A,H,U] -> scores [N,A]."""

@@ -427,6 +427,33 @@ int bbmpc_get_plan(bbmpc_handle h, float* actions);
  * equal bits.  On the handle's stream.  No counterpart in the reference (its train() reports a one-step loss only). */
 int bbmpc_trajectory_sq_error_dev(bbmpc_handle h, const float* d_predicted, const float* d_observed, int32_t batch,
                                   int32_t horizon, double* d_sum_sq);
+/* Trajectory distributions: the particle recurrence of bbmpc_set_particles (with the ensemble of bbmpc_set_mlp_ensemble
+ * and the heads of bbmpc_set_mlp_logvar_head when they are installed) from every row's OWN start state, every state and
+ * reward kept, and their per-step moments over the particles.  Needs bbmpc_set_particles on the handle: P and sigma are
+ * the handle's, risk_kappa plays no part.  states [B,S], action_sequences [B,Hq,U], eps [B,P,Hq,S] standard normals or
+ * NULL; for every row b and particle p, with s_0 = states[b], for t = 0 .. Hq-1:
+ *     nxt = predict_next_state_member(p % E)(s_t, a[b,t]) + (sigma + sd(s_t, a[b,t])) (.) eps[b,p,t,:]
+ *     particle_states[b,p,t] = nxt;  particle_rewards[b,p,t] = reward(s_t, a[b,t], nxt);  s_{t+1} = nxt
+ *     mean[b,t,f] = (sum_p x[b,p,t,f]) / P;  std[b,t,f] = sqrt(sum_p (x[b,p,t,f] - mean[b,t,f])^2 / P)
+ * (fp32, p in index order, as the scores of bbmpc_evaluate_particles; the same for the rewards).  Outputs: state_mean /
+ * state_std [B,Hq,S], reward_mean / reward_std [B,Hq], particle_states [B,P,Hq,S], particle_rewards [B,P,Hq]; any of them
+ * may be NULL, not all six.  As in bbmpc_predict_trajectories the actions are used as given, per-step values are returned as
+ * computed (no clip, no penalty, no NaN -> -1e6), Hq is independent of the planning horizon (1 <= Hq <= 4096) and any
+ * handle that bbmpc_set_particles accepts serves.  eps == NULL: the handle's own draws -- the BBMPC_NOISE_PROCESS stream
+ * with row b in the agent word (agent_offset + b), Qp = ceil(Hq * S / 4), the handle's current control step, iteration 0:
+ * at B = num_agents, Hq = planning_horizon exactly the tensor bbmpc_evaluate_particles rolls.  Equal calls give equal bits.
+ * An injected BBMPC_NOISE_PROCESS tensor is not read here (its layout is the planning horizon's): pass it as eps.
+ * BBMPC_E_STATE: particles off, learned model without weights; BBMPC_E_INVALID: batch < 1, horizon outside [1, 4096], all
+ * outputs NULL; BBMPC_E_UNSUPPORTED: B * P * Hq * S >= 2^31, B * Hq * U >= 2^31, B * Qp >= 2^32, a network whose buffers do
+ * not fit the LDS (as the particle rollouts).  The host variant is synchronous (eps a host pointer); _dev enqueues on the
+ * handle's stream (eps a device pointer). */
+int bbmpc_predict_trajectory_particles(bbmpc_handle h, const float* states, const float* action_sequences, int32_t batch,
+                                       int32_t horizon, const float* eps, float* state_mean, float* state_std,
+                                       float* reward_mean, float* reward_std, float* particle_states, float* particle_rewards);
+int bbmpc_predict_trajectory_particles_dev(bbmpc_handle h, const float* d_states, const float* d_action_sequences, int32_t batch,
+                                           int32_t horizon, const float* d_eps, float* d_state_mean, float* d_state_std,
+                                           float* d_reward_mean, float* d_reward_std, float* d_particle_states,
+                                           float* d_particle_rewards);
 
 /* Closed-loop episode on the device -- counterpart of utils/rollouts.py:60-139 (_sample) with the engine's own
  * model as the environment: T control steps, each feeding its predicted next state back as the next observation;
