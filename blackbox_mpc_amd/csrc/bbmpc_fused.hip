@@ -187,7 +187,21 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
 #ifdef BBMPC_KERNEL_DBG
     static long long* dbg_buf = nullptr;
     if (sw.dbg) {
-        if (!dbg_buf) HIP_CHECK(hipHostMalloc((void**)&dbg_buf, 64 * 8, hipHostMallocDefault));
+        if (!dbg_buf) {
+            HIP_CHECK(hipHostMalloc((void**)&dbg_buf, 64 * 8, hipHostMallocDefault));
+            memset(dbg_buf, 0, 64 * 8);
+        }
+        // a resident kernel's passes never come by the print below: the launch that follows a resident kernel prints the
+        // clocks of that kernel's last pass (slot 42 is written by resident passes only; the kernel has left by now)
+        if (dbg_buf[42]) {
+            const long long* d = dbg_buf;
+            fprintf(stderr, "[dbg] last resident pass, 10ns units rel. to its start:");
+            for (int i = 0; i <= 1 + iters * 4; ++i) fprintf(stderr, " %lld", d[i] - d[0]);
+            fprintf(stderr, "\n[dbg] iter0 per-wave rollout end:");
+            for (int i = 24; i < 32; ++i) fprintf(stderr, " %lld", d[i] - d[0]);
+            fprintf(stderr, "\n[dbg] request accepted %lld  first model step %lld  completion stored %lld\n", d[42] - d[0], d[44] - d[0], d[43] - d[0]);
+            dbg_buf[42] = 0;
+        }
         fa.dbg = dbg_buf;
     }
 #endif
@@ -228,6 +242,9 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
             pf_waited[pb] = true; pf_inflight[pb] = false;
         }
         fa.inj = d_noise_pf[pb].p + (size_t)((int64_t)step - c * pf_steps) * pf_step_floats;
+        // what a resident workgroup needs to guess the next request's pointer (and to stay inside the buffers doing so)
+        fa.pf_buf[0] = d_noise_pf[0].p; fa.pf_buf[1] = d_noise_pf[1].p;
+        fa.pf_step_floats = pf_step_floats; fa.pf_chunk_floats = pf_step_floats * (size_t)pf_steps;
         if (pf_chunk[nb] != c + 1) {
             // the other buffer was last read by kernels already enqueued on `stream`: the side stream fills it for
             // the next chunk while this chunk's control steps run
@@ -268,7 +285,7 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
         default: launch_fused<FOPT_PI2>(*this, fa, ilp, threads, lds_base, lds_samples, use_pf ? 2 : 1); break;
     }
     prof_end();
-    if (fa.dbg) {
+    if (fa.dbg && !resident_alive) {      // (a resident launch is not waited for: its clocks are printed by the launch after it)
         HIP_CHECK(hipStreamSynchronize(stream));
         if (step == 5) {
             fprintf(stderr, "[dbg] phase clocks (10ns units) rel. to start:");

@@ -68,7 +68,17 @@ struct FusedArgs {
     int test_quit_agent;     // test hook (BBMPC_LINGER_TEST_QUIT = a + 1): agent a's workgroup leaves after every control step, -1 = none;
                              // 1000 + a: every agent from a on leaves (more than one 16-entry line of the agent map)
     const int* amap;         // optional: blockIdx.x -> agent (a launch for a subset of the agents), null = identity
+    // (LINGER, INJ = 2) the two noise chunk buffers and their strides: a resident workgroup fetches the first draws of the
+    // NEXT control step while it waits for the request, from inj + pf_step_floats when that still lies inside the chunk
+    // buffer inj lies in.  Timing only: the request names the pointer, and a fetch from anywhere else is thrown away.
+    const float* pf_buf[2];
+    unsigned long long pf_step_floats, pf_chunk_floats;      // floats per control step / per chunk buffer (0 = no prediction)
 };
+
+// float4 index of particle n's first Philox block in the layout k_noise_fill writes, [it][A][Nst][Q]
+__device__ __forceinline__ size_t noise_block_index(int it, int A, int a, int Nst, int n, int Q) {
+    return (((size_t)it * A + a) * Nst + n) * Q;
+}
 
 // phase clocks for kernel development: build with -DBBMPC_KERNEL_DBG and run with BBMPC_DBG=1
 #ifdef BBMPC_KERNEL_DBG
@@ -136,11 +146,9 @@ __global__ void k_fused_pendulum(FusedArgs p) {
     // variance every time, quirk Q2; PI2 / SPSA / warm-started CEM: the mean it has just written to prev_mean)
     const bool keep_init = LINGER && OPT != FOPT_RS && p.HU <= nthr;
     [[maybe_unused]] float m_keep = 0.0f, v_keep = 0.0f, s_keep = 0.0f;
-    [[maybe_unused]] bool have_init = false;
-    for (;;) {      // one pass per control step; a single pass unless LINGER
-
-        // ---- distribution init (cem.py:129-132 starts every control step from the ctor mean/var, quirk Q2)
-        if (keep_init && have_init) {        // resident pass: no global round trip
+    // ---- distribution init (cem.py:129-132 starts every control step from the ctor mean/var, quirk Q2)
+    auto dist_init = [&](bool from_keep) {
+        if (from_keep) {                     // resident pass: no global round trip
             if (tid < p.HU) {
                 mean[tid] = m_keep;
                 var[tid] = v_keep;
@@ -156,10 +164,31 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 sigma[j] = sg;
                 if (keep_init) { m_keep = m; v_keep = v; s_keep = sg; }
             }
-            have_init = true;
         }
-        __syncthreads();
-        const float s0 = red[60], s1 = red[61], s2 = red[62];
+    };
+    // (INJ == 2) the first two blocks of a thread's first trajectory are fetched while the PREVIOUS iteration selects and
+    // refits (a resident pass: while the workgroup waits for its request): at the top of the rollout their loads would be
+    // one exposed memory round trip per iteration
+    typedef float pfvec4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) pfvec4* pfvec4p;
+    [[maybe_unused]] pfvec4 pf0 = {0.0f, 0.0f, 0.0f, 0.0f}, pf1 = {0.0f, 0.0f, 0.0f, 0.0f};
+    [[maybe_unused]] auto prefetch_first = [&](const float* base, int it_n) {
+        if constexpr (INJ == 2) {
+            const int Q = (p.HU + 3) >> 2;
+            if (tid < p.N) {                 // the lanes past the population roll nothing out
+                const pfvec4p q = (pfvec4p)(reinterpret_cast<const float4*>(base) + noise_block_index(it_n, p.A, a, p.Nst, tid, Q));
+                pf0 = q[0];
+                if (OPT != FOPT_SPSA) pf1 = q[min(1, Q - 1)];
+            }
+        }
+    };
+    dist_init(false);
+    __syncthreads();
+    float s0 = red[60], s1 = red[61], s2 = red[62];
+    if (p.iters > 0) prefetch_first(inj_s, 0);
+    for (;;) {      // one pass per control step; a single pass unless LINGER
+        // (a resident pass arrives here with the distribution in LDS, the state in s0..s2 and its first draws on their way:
+        // see the hand-off at the end of the loop)
 
         float action0 = (OPT == FOPT_RS) ? 0.0f : mean[0];          // iters == 0 -> untouched mean[:,0]
 
@@ -167,20 +196,6 @@ __global__ void k_fused_pendulum(FusedArgs p) {
 #ifdef BBMPC_KERNEL_DBG
         if (p.dbg && tid == 0 && a == 0) dbg_lds[40] = (long long)clock64();
 #endif
-        // (INJ == 2) the first two blocks of a thread's first trajectory are fetched while the PREVIOUS iteration selects and
-        // refits: at the top of the rollout their loads would be one exposed memory round trip per iteration
-        typedef float pfvec4 __attribute__((ext_vector_type(4)));
-        typedef const __attribute__((address_space(1))) pfvec4* pfvec4p;
-        [[maybe_unused]] pfvec4 pf0 = {0.0f, 0.0f, 0.0f, 0.0f}, pf1 = {0.0f, 0.0f, 0.0f, 0.0f};
-        [[maybe_unused]] auto prefetch_first = [&](int it_n) {
-            if constexpr (INJ == 2) {
-                const int Q = (p.HU + 3) >> 2;
-                const pfvec4p q = (pfvec4p)(reinterpret_cast<const float4*>(inj_s) + (((size_t)it_n * p.A + a) * p.Nst + min(tid, p.N - 1)) * Q);
-                pf0 = q[0];
-                if (OPT != FOPT_SPSA) pf1 = q[min(1, Q - 1)];
-            }
-        };
-        if (p.iters > 0) prefetch_first(0);
         for (int it = 0; it < p.iters; ++it) {
             BB_DBG(1 + it * 4);
             // ---- sample + rollout: one lane per trajectory, state in VGPRs
@@ -210,7 +225,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     [[maybe_unused]] gvec4sp mine4 = nullptr;
                     [[maybe_unused]] gvec4s cur4 = {1.0f, 1.0f, 1.0f, 1.0f};
                     if constexpr (INJ == 2) {            // draws prefetched by k_noise_fill, one float4 per 4 steps
-                        mine4 = (gvec4sp)(reinterpret_cast<const float4*>(inj_s) + (((size_t)it * p.A + a) * p.Nst + n) * nb4);
+                        mine4 = (gvec4sp)(reinterpret_cast<const float4*>(inj_s) + noise_block_index(it, p.A, a, p.Nst, n, nb4));   // (U == 1: nb4 == Q)
                         if (n == tid) cur4 = pf0;                    // fetched while the previous iteration refitted
                         else cur4 = mine4[0];
                     }
@@ -260,7 +275,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 // Loads run TWO blocks (8 steps, ~2 us) ahead of their use so that L2/HBM latency never reaches the
                 // recurrence; the Philox rounds (a quarter of this kernel's VALU work) are gone from the critical path.
                 const int Q = (p.HU + 3) >> 2;
-                const float4* inj4 = reinterpret_cast<const float4*>(inj_s) + ((size_t)it * p.A + a) * p.Nst * Q;
+                const float4* inj4 = reinterpret_cast<const float4*>(inj_s);
                 int* prog = (int*)red;                             // per-wave progress (red[] is idle during the rollout)
                 const int wave = tid >> 6, lane = tid & 63;
                 const bool balance = p.balance != 0 && nw > 4 && nw <= 64 && p.N <= nthr;
@@ -273,7 +288,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     // block it had just prefetched: one memory round trip per eight model steps)
                     typedef float gvec4 __attribute__((ext_vector_type(4)));
                     typedef const __attribute__((address_space(1))) gvec4* gvec4p;
-                    const gvec4p mine = (gvec4p)(inj4 + (size_t)n * Q);
+                    const gvec4p mine = (gvec4p)(inj4 + noise_block_index(it, p.A, a, p.Nst, n, Q));
                     auto ld = [&](int b) { const gvec4 v = mine[min(b, Q - 1)]; return make_float4(v.x, v.y, v.z, v.w); };
                     auto step1 = [&](int t, float xi) {
                         float x = (OPT == FOPT_RS) ? xi * (hi - lo) + lo : xi * sigma[t] + mean[t];
@@ -324,6 +339,9 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     if (n == tid) { c0 = make_float4(pf0.x, pf0.y, pf0.z, pf0.w); c1 = make_float4(pf1.x, pf1.y, pf1.z, pf1.w); }   // fetched an iteration ago
                     else { c0 = ld(0); c1 = ld(1); }
                     int b = 0;
+#ifdef BBMPC_KERNEL_DBG
+                    if (it == 0 && n == tid) { asm volatile("" :: "v"(c0.x)); BB_DBG(44); }     // the first draws are there
+#endif
                     // Waves that share a SIMD (wave ids equal mod 4) run the same instruction stream, and the arbiter
                     // favours the older one: it finishes early and the younger one then runs alone at a lone wave's
                     // issue rate (measured: 4.5 us vs 6.0 us for the two halves of a 500-particle population).  Each
@@ -436,7 +454,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
 #endif
             // the selection's first part reads only the rewards this thread has just written: in front of the barrier the
             // rollout needs anyway instead of behind it with a barrier of its own (topk.hpp)
-            if (it + 1 < p.iters) prefetch_first(it + 1);
+            if (it + 1 < p.iters) prefetch_first(inj_s, it + 1);
             if (OPT == FOPT_CEM) block_topk_prepass(rew, p.N, p.k, hist, tid, nthr);
             BB_DBG(2 + it * 4);
             __syncthreads();
@@ -597,10 +615,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
 
         BB_DBG(1 + p.iters * 4);
 #ifdef BBMPC_KERNEL_DBG
-        if (p.dbg && tid == 0 && a == 0) {
-            dbg_lds[41] = (long long)clock64();
-            for (int i = 0; i < 48; ++i) p.dbg[i] = dbg_lds[i];
-        }
+        if (p.dbg && tid == 0 && a == 0) dbg_lds[41] = (long long)clock64();
 #endif
         // ---- state carried to the next control step
         if (OPT != FOPT_RS) {
@@ -651,6 +666,10 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             // launch stream.
             if constexpr (LINGER) publish_records_done(p.done_flag + a * 16, nullptr, done_value_s, 1u);    // this agent's own completion word
             else publish_records_done(p.done_flag, p.done_count, done_value_s, gridDim.x);
+            BB_DBG(43);      // completion word stored; slot 42: this pass's request accepted, 44: its first model step
+#ifdef BBMPC_KERNEL_DBG
+            if (p.dbg && a == 0) for (int i = 0; i < 48; ++i) p.dbg[i] = dbg_lds[i];
+#endif
         }
         if constexpr (!LINGER) {
             break;
@@ -663,8 +682,22 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             // host-to-host for a resident kernel's mailbox round trip against 6.8 us for launch + completion,
             // tools/microbench/launch_latency.hip); the stop word in word 15, or linger_ticks without a request, ends the
             // kernel, which says so in `gone` first and never looks at the line again, so the host knows whether to launch.
+            // Everything the next pass needs that does not depend on the request is staged BEFORE the poll: its starting
+            // distribution goes to LDS (from the kept registers, or -- RandomSearch, H*U > threads -- from the global copies
+            // this thread has just written itself), and every thread fetches its first draws from where the next request
+            // will most likely point.  Behind the request there is one barrier.  (Wave 0 fetches its draws in front of the
+            // poll like everybody else: its first read of the request line waits for them, a device-memory round trip at a
+            // moment when the host has not even seen this pass's completion word.)
             unsigned* mb = (unsigned*)ekeys;                       // 16 words of LDS that are idle outside the top-k
-            __syncthreads();
+            __syncthreads();                                       // mean[] / ekeys / red have been read for the last time
+            dist_init(keep_init);
+            [[maybe_unused]] const float* inj_pred = nullptr;
+            if constexpr (INJ == 2) {
+                if (p.pf_step_floats)
+                    for (int b = 0; b < 2; ++b)
+                        if (inj_s >= p.pf_buf[b] && inj_s + 2 * p.pf_step_floats <= p.pf_buf[b] + p.pf_chunk_floats) inj_pred = inj_s + p.pf_step_floats;
+                if (inj_pred && p.iters > 0) prefetch_first(inj_pred, 0);
+            }
             if (tid < 64) {
                 const long long t0 = (long long)wall_clock64();
                 const unsigned want = done_value_s + 1u;
@@ -678,6 +711,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     if (w15 == 0xffffffffu || (long long)wall_clock64() - t0 > (long long)p.linger_ticks || a == p.test_quit_agent || (p.test_quit_agent >= 999 && a >= p.test_quit_agent - 999)) { quit = true; break; }
                 }
                 if (tid < 16) mb[tid] = (quit && tid == 15) ? 0xffffffffu : w;
+                BB_DBG(42);
             }
             __syncthreads();
             if (mb[15] == 0xffffffffu) {
@@ -689,10 +723,13 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             add_noise_s = (int)(mb[2] >> 16);
             inj_s = reinterpret_cast<const float*>(((unsigned long long)(mb[3] >> 16)) | ((unsigned long long)(mb[4] >> 16) << 16) |
                                                    ((unsigned long long)(mb[5] >> 16) << 32) | ((unsigned long long)(mb[6] >> 16) << 48));
-            const int sw_ = 7 + 2 * min(tid, 2);
-            const float st_next = __uint_as_float((mb[sw_] >> 16) | (mb[sw_ + 1] & 0xffff0000u));
-            __syncthreads();                                        // every thread has read the request before `red` / `ekeys` are reused
-            if (tid < 3) red[60 + tid] = st_next;
+            // (every thread decodes the state itself; `ekeys` is next written behind the rollout's barrier at the earliest --
+            // with iters == 0 behind the barrier in front of the next pass's staging)
+            s0 = __uint_as_float((mb[7] >> 16) | (mb[8] & 0xffff0000u));
+            s1 = __uint_as_float((mb[9] >> 16) | (mb[10] & 0xffff0000u));
+            s2 = __uint_as_float((mb[11] >> 16) | (mb[12] & 0xffff0000u));
+            if (p.iters > 0 && inj_s != inj_pred) prefetch_first(inj_s, 0);      // nothing was predicted (the chunk's last step), or -- not
+                                                                                 // reachable through the host's entry points today -- another pointer
         }
     }
 }
