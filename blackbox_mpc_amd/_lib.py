@@ -30,6 +30,8 @@ NOISE_PSO_RESEED_TRUNC, NOISE_PSO_RESEED_UNIFORM, NOISE_PSO_RESET_POS, NOISE_PSO
 NOISE_EXPLORATION = 10
 NOISE_PROCESS = 11                                      # [iters][A,P,H,S] N(0,1): the particle evaluator's process noise
 MAX_PARTICLES = 64
+RISK_MEAN_STD, RISK_CVAR = 0, 1                         # bbmpc_set_particle_risk
+MAX_QUANTILE_LEVELS = 8                                 # bbmpc_predict_trajectory_quantiles
 MAX_ENSEMBLE_MEMBERS = 8                                # bbmpc_set_mlp_ensemble
 LOGVAR_ABS_MAX = 40.0                                   # bbmpc_set_mlp_logvar_head: |min_logvar|, |max_logvar| <= 40
 TRACE_REWARDS, TRACE_MEAN, TRACE_VAR, TRACE_ELITES, TRACE_SAMPLES = 1, 2, 3, 4, 5
@@ -86,6 +88,7 @@ SYMBOLS = [
     "bbmpc_set_particles", "bbmpc_evaluate_particles", "bbmpc_evaluate_particles_dev",
     "bbmpc_set_mlp_ensemble", "bbmpc_set_mlp_logvar_head",
     "bbmpc_predict_trajectory_particles", "bbmpc_predict_trajectory_particles_dev",
+    "bbmpc_set_particle_risk", "bbmpc_predict_trajectory_quantiles", "bbmpc_predict_trajectory_quantiles_dev",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -177,6 +180,9 @@ def _load():
     lib.bbmpc_set_mlp_logvar_head.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
     lib.bbmpc_predict_trajectory_particles.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.bbmpc_predict_trajectory_particles_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.bbmpc_set_particle_risk.argtypes = [vp, i32, i32]
+    lib.bbmpc_predict_trajectory_quantiles.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.bbmpc_predict_trajectory_quantiles_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

@@ -1,5 +1,5 @@
-// Particle trajectory evaluator (bbmpc_set_particles, bbmpc_evaluate_particles; kernels_particles.hpp): the switch, the
-// process-noise buffer, the launch sequence  candidates -> noisy rollouts -> aggregate  that Engine::launch_rollout takes
+// Particle trajectory evaluator (bbmpc_set_particles, bbmpc_set_particle_risk, bbmpc_evaluate_particles;
+// kernels_particles.hpp): the switch, the scoring rule, the process-noise buffer, the launch sequence  candidates -> noisy rollouts -> aggregate  that Engine::launch_rollout takes
 // while the switch is on, and the ABI.  The learned model's rollout kernel is launched from bbmpc_mlp.hip.
 #include <cmath>
 
@@ -29,6 +29,9 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     REQUIRE(ens_E == 0 || num_particles % ens_E == 0, BBMPC_E_INVALID,
             "particles: num_particles = " + std::to_string(num_particles) + " is no multiple of the model ensemble's num_members = " +
                 std::to_string(ens_E) + " (the members must carry equal weight in the mean)");
+    REQUIRE(part_risk != BBMPC_RISK_CVAR || part_tail <= num_particles, BBMPC_E_INVALID,
+            "particles: num_particles = " + std::to_string(num_particles) + " is below the CVaR tail_count = " + std::to_string(part_tail) +
+                " of bbmpc_set_particle_risk");
     HIP_CHECK(hipStreamSynchronize(stream));
     if (num_particles != part_P) inj.erase(BBMPC_NOISE_PROCESS);       // (its layout depends on P)
     if (d_psigma.n < (size_t)S) d_psigma.alloc((size_t)S);
@@ -38,6 +41,21 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     part_P = num_particles;
     part_kappa = kappa;
     pnoise_valid = false;
+}
+
+void Engine::set_particle_risk(int kind, int tail_count) {
+    REQUIRE(kind == BBMPC_RISK_MEAN_STD || kind == BBMPC_RISK_CVAR, BBMPC_E_INVALID, "particle risk: unknown kind " + std::to_string(kind));
+    if (kind == BBMPC_RISK_MEAN_STD) {
+        REQUIRE(tail_count == 0, BBMPC_E_INVALID, "particle risk: tail_count must be 0 with BBMPC_RISK_MEAN_STD");
+    } else {
+        // (particles off: the rule against P is bbmpc_set_particles' to enforce)
+        const int pmax = part_P > 0 ? part_P : PARTICLES_MAX;
+        REQUIRE(tail_count >= 1 && tail_count <= pmax, BBMPC_E_INVALID,
+                "particle risk: CVaR tail_count = " + std::to_string(tail_count) + " must be in [1, num_particles = " + std::to_string(pmax) + "]");
+    }
+    invalidate_step_graph();
+    part_risk = kind;
+    part_tail = tail_count;
 }
 
 // eps [A][P][H][S] of (control step, iteration): the injected tensor, or the handle's own draws, generated once per
@@ -117,7 +135,11 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
         HIP_CHECK(hipGetLastError());
     }
     prof_end();
-    hipLaunchKernelGGL(k_particle_aggregate, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, q, part_kappa);
+    if (part_risk == BBMPC_RISK_CVAR)
+        hipLaunchKernelGGL(k_particle_aggregate_cvar, dim3((ra.n_pop + CVAR_WAVES - 1) / CVAR_WAVES, A), dim3(CVAR_WAVES * 64), 0, stream, q,
+                           part_tail);
+    else
+        hipLaunchKernelGGL(k_particle_aggregate, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, q, part_kappa);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -159,6 +181,13 @@ int bbmpc_set_particles(bbmpc_handle h, int32_t num_particles, const float* sigm
     API_BEGIN
     CHECK_HANDLE(h);
     h->e->set_particles(num_particles, sigma, risk_kappa);
+    API_END
+}
+
+int bbmpc_set_particle_risk(bbmpc_handle h, int32_t kind, int32_t tail_count) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_particle_risk(kind, tail_count);
     API_END
 }
 

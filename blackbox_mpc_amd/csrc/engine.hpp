@@ -412,6 +412,10 @@ struct Engine {
     // (one launch sequence per iteration: no resident, fused or graph-replayed form) and launch_rollout scores through it.
     int part_P = 0;
     float part_kappa = 0.0f;
+    // how the P returns become the score (bbmpc_set_particle_risk): mean - kappa * std, or the mean of
+    // the part_tail worst returns (CVaR; kappa is then ignored).  Kept while particles are off.
+    int part_risk = BBMPC_RISK_MEAN_STD, part_tail = 0;
+    void set_particle_risk(int kind, int tail_count);
     DevBuf<float> d_psigma, d_pnoise, d_preturns, d_pe_io;   // sigma [S] | eps [A][P][H][S] | returns [A][Nst * P] | host-call staging
     bool pnoise_valid = false;         // d_pnoise holds the draws of (pnoise_step, pnoise_iter)
     uint32_t pnoise_step = 0, pnoise_iter = 0;
@@ -441,6 +445,13 @@ struct Engine {
     void predict_trajectory_particles_dev(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps,
                                           float* d_smean, float* d_sstd, float* d_rmean, float* d_rstd, float* d_pstates, float* d_prewards);
     void launch_traj_mlp_particles(const TrajParticleArgs& pa);               // bbmpc_mlp.hip
+    // draws (unless supplied) -> noisy trajectories into d_pstates / d_prewards (null: the handle's scratch, returned)
+    void roll_trajectory_particles(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps, float*& d_pstates,
+                                   float*& d_prewards);
+    // the same with nearest-rank quantiles over the particles (bbmpc_predict_trajectory_quantiles)
+    void predict_trajectory_quantiles_dev(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps, float* d_smean,
+                                          float* d_sstd, float* d_rmean, float* d_rstd, float* d_pstates, float* d_prewards, int num_levels,
+                                          const int32_t* ranks, float* d_squant, float* d_rquant);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
     DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging

@@ -12,6 +12,7 @@
 // and forms the bound penalty of PI2 / PSO / SPSA / CMA-ES, which is subtracted from the score.
 #pragma once
 #include "models.hpp"
+#include "particle_rank.hpp"
 #include "rng.hpp"
 
 namespace bbmpc {
@@ -149,6 +150,51 @@ static __global__ void k_particle_aggregate(ParticleArgs q, float kappa) {
         if (q.penalty_out) q.penalty_out[(size_t)a * q.Nst + n] = pen;
     }
     q.rewards[(size_t)a * q.Nst + n] = score;
+}
+
+// CVaR score (bbmpc_set_particle_risk): the mean of the k worst returns of a candidate,
+//     sel[p] = rank[p] < k        score = (sum over the selected p, in index order) / (float)k
+// rank the stable rank of particle_rank.hpp, so the selection is exact and k = P gives the bits of the kappa = 0 mean.
+// One wave per (candidate, agent): lane p holds r[p] (one coalesced load), ranks it, the ballot of sel is walked in index
+// order with every lane carrying the sum through lane broadcasts.  The penalty / write-back tail is k_particle_aggregate's:
+// lane l clips and writes back elements l, l + 64, .. (independent writes; an element is read and written by one lane, so
+// samples may alias cand), and the squared distances are added over j in index order, again carried by every lane.
+// grid (ceil(n_pop / CVAR_WAVES), A), CVAR_WAVES * 64 threads: four waves fill the four SIMDs of a CU, and 1000 candidates
+// still spread over 250 CUs
+constexpr int CVAR_WAVES = 4;
+static __global__ __launch_bounds__(CVAR_WAVES * 64) void k_particle_aggregate_cvar(ParticleArgs q, int k) {
+    const int a = blockIdx.y, lane = threadIdx.x & 63;
+    const int n = blockIdx.x * CVAR_WAVES + (threadIdx.x >> 6);
+    if (n >= q.n_pop) return;                                   // (the whole wave)
+    const float x = lane < q.P ? q.returns[(size_t)a * q.RS + (size_t)n * q.P + lane] : 0.0f;
+    const int rank = particle_stable_rank(x, lane, q.P);
+    float sum = 0.0f;
+    for (unsigned long long m = __ballot(lane < q.P && rank < k); m; m &= m - 1) sum = sum + wave_bcast(x, __builtin_ctzll(m));
+    float score = sum / (float)k;
+    if (q.pen) {
+        float pen = 0.0f;
+        for (int j0 = 0; j0 < q.HU; j0 += 64) {
+            const int j = j0 + lane;
+            float d = 0.0f;
+            if (j < q.HU) {
+                const int u = j % q.U;
+                const float c = q.from_ref ? q.seq[((size_t)n * q.A + a) * q.HU + j] : q.cand[((size_t)a * q.HU + j) * q.Nst + n];
+                const float cf = clipf(c, q.lo[u], q.hi[u]);
+                d = c - cf;
+                if (q.samples) q.samples[((size_t)a * q.HU + j) * q.Nst + n] = cf;
+            }
+            const int cnt = min(64, q.HU - j0);
+            for (int i = 0; i < cnt; ++i) {
+                const float di = wave_bcast(d, i);
+                pen = pen + di * di;
+            }
+        }
+        const float nr = sqrtf(pen);                            // tf.norm(...)**2  pi2.py:72-75
+        pen = nr * nr;
+        score = score - pen;
+        if (lane == 0 && q.penalty_out) q.penalty_out[(size_t)a * q.Nst + n] = pen;
+    }
+    if (lane == 0) q.rewards[(size_t)a * q.Nst + n] = score;
 }
 
 }  // namespace bbmpc

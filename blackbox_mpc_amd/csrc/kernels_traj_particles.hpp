@@ -7,7 +7,7 @@
 // as k_particle_aggregate forms them of the returns.  Actions are used as given, per-step values are stored as computed
 // (no clip, no penalty, no NaN rule), as bbmpc_predict_trajectories does.  The analytic pendulum rolls one (b, p) row per
 // lane (below); the learned model's rows go through the matrix cores (kernels_mlp_traj_particles.hpp, compiled in the
-// bbmpc_mlp unit).  Offsets into the noise and the particle tensors are 32 bit: the host refuses B * P * Hq * S >= 2^31.
+// bbmpc_mlp unit).  Nearest-rank quantiles over the particles (bbmpc_predict_trajectory_quantiles) are at the end.  Offsets into the noise and the particle tensors are 32 bit: the host refuses B * P * Hq * S >= 2^31.
 #pragma once
 #include "kernels_particles.hpp"
 #include "traj_particle_args.hpp"
@@ -75,6 +75,49 @@ static __global__ void k_traj_particle_moments(const float* __restrict__ pstates
         const long i = idx - ns;
         const int b = (int)(i / Hq), t = (int)(i - (long)b * Hq);
         particle_moments(prewards + (size_t)b * P * Hq + t, P, (size_t)Hq, rmean ? rmean + i : nullptr, rstd ? rstd + i : nullptr);
+    }
+}
+
+// Nearest-rank quantiles over the particles (bbmpc_predict_trajectory_quantiles): for level l the
+// particle value whose stable rank (particle_rank.hpp) among the P values of (b, t, f) is r[l] -- an element of the particle
+// tensor, bit for bit.  A NaN among the P values makes their ranks meaningless (particle_rank.hpp): nothing special is
+// propagated, and an output whose rank no lane holds is not written.
+constexpr int QUANTILE_LEVELS_MAX = 8;
+struct QuantileRanks {
+    int n;                            // levels, 1 .. 8
+    int r[QUANTILE_LEVELS_MAX];       // each in [0, P)
+};
+
+// lane p of the wave holds x[p * stride]; for each level the lane whose rank matches stores to out[l * level_stride]
+__device__ __forceinline__ void particle_quantiles(const float* x, int lane, int P, size_t stride, const QuantileRanks& lv, float* out,
+                                                   size_t level_stride) {
+    const float v = lane < P ? x[(size_t)lane * stride] : 0.0f;
+    const int rank = particle_stable_rank(v, lane, P);
+#pragma unroll
+    for (int l = 0; l < QUANTILE_LEVELS_MAX; ++l)
+        if (l < lv.n && lane < P && rank == lv.r[l]) out[(size_t)l * level_stride] = v;
+}
+
+// One wave per output element: (b, t, f) of the state quantiles [B, L, Hq, S], behind them (b, t) of the reward quantiles
+// [B, L, Hq]; the particle stride of a lane's load is Hq * S (Hq).  No atomics.  Only the outputs that are not null are
+// written.  grid (ceil(elements / QUANTILE_WAVES)), QUANTILE_WAVES * 64 threads
+constexpr int QUANTILE_WAVES = 4;
+static __global__ __launch_bounds__(QUANTILE_WAVES * 64) void k_traj_particle_quantiles(const float* __restrict__ pstates,
+                                                                                        const float* __restrict__ prewards, int B, int P, int Hq,
+                                                                                        int S, QuantileRanks lv, float* __restrict__ squant,
+                                                                                        float* __restrict__ rquant) {
+    const long ns = squant ? (long)B * Hq * S : 0;
+    const long nr = rquant ? (long)B * Hq : 0;
+    const int lane = threadIdx.x & 63;
+    const long idx = (long)blockIdx.x * QUANTILE_WAVES + (threadIdx.x >> 6);
+    if (idx < ns) {
+        const int b = (int)(idx / (Hq * S)), j = (int)(idx - (long)b * (Hq * S));             // j = t * S + f
+        particle_quantiles(pstates + (size_t)b * P * Hq * S + j, lane, P, (size_t)Hq * S, lv, squant + (size_t)b * lv.n * Hq * S + j,
+                           (size_t)Hq * S);
+    } else if (idx - ns < nr) {
+        const long i = idx - ns;
+        const int b = (int)(i / Hq), t = (int)(i - (long)b * Hq);
+        particle_quantiles(prewards + (size_t)b * P * Hq + t, lane, P, (size_t)Hq, lv, rquant + (size_t)b * lv.n * Hq + t, (size_t)Hq);
     }
 }
 

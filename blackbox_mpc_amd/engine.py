@@ -8,6 +8,8 @@ from . import _lib as L
 
 
 class Engine:
+    risk = (L.RISK_MEAN_STD, 0)        # (kind, tail_count) of set_particle_risk: a new handle scores mean - kappa * std
+
     def __init__(self, optimizer, dynamics, reward, action_low, action_high, dim_s, num_agents,
                  planning_horizon, population_size=0, max_iterations=0, num_elite=0, seed=0, quirks=0,
                  agent_offset=0, num_agents_global=None, device=-1, alpha=0.25, lamda=1.0,
@@ -382,6 +384,13 @@ class Engine:
         L.check(L.lib.bbmpc_set_particles(self._h, p, L.ptr(sg), ctypes.c_float(float(risk_kappa))))
         self.P = p
 
+    def set_particle_risk(self, kind=L.RISK_MEAN_STD, tail_count=0):
+        """How the particle returns become the score (bbmpc_set_particle_risk): RISK_MEAN_STD (tail_count 0) is
+        mean - risk_kappa * std; RISK_CVAR is the mean of the `tail_count` worst returns, 1 <= tail_count <= num_particles
+        (1: the worst case over the particles).  Handle state, before or after set_particles."""
+        L.check(L.lib.bbmpc_set_particle_risk(self._h, int(kind), int(tail_count)))
+        self.risk = (int(kind), int(tail_count))
+
     def evaluate_particles(self, state, action_sequences, want_returns=True):
         """(scores [n, A], per-particle returns [n, P, A] or None) -- bbmpc_evaluate_particles."""
         state = L.f32c(state)
@@ -454,12 +463,15 @@ class Engine:
                                                      int(batch), int(horizon), ctypes.c_void_p(d_states_out or 0),
                                                      ctypes.c_void_p(d_rewards_out or 0)))
 
-    def predict_trajectory_particles(self, states, action_sequences, eps=None, want_particles=False):
+    def predict_trajectory_particles(self, states, action_sequences, eps=None, want_particles=False, quantile_ranks=None):
         """Trajectory distributions (bbmpc_predict_trajectory_particles): states [B,S], action_sequences [B,Hq,U] ->
         (state_mean [B,Hq,S], state_std [B,Hq,S], reward_mean [B,Hq], reward_std [B,Hq]) over the P particles of
         set_particles, each rolled with process noise (and the ensemble member / log-variance head it follows) from the
         row's own start state; with want_particles also (particle_states [B,P,Hq,S], particle_rewards [B,P,Hq]).
-        eps: standard normals [B,P,Hq,S], or None for the handle's own draws."""
+        eps: standard normals [B,P,Hq,S], or None for the handle's own draws.  quantile_ranks: up to 8 ranks in [0, P) --
+        then (bbmpc_predict_trajectory_quantiles) state_quantiles [B,L,Hq,S] and reward_quantiles [B,L,Hq] follow the
+        moments (and precede the particle tensors): for rank r the particle value whose stable rank among the P particles
+        of that element is r (0: the minimum, P - 1: the maximum)."""
         states, seq = L.f32c(states), L.f32c(action_sequences)
         b = states.shape[0] if states.ndim == 2 else -1
         # the C side copies b*S, b*Hq*U and b*P*Hq*S floats from these buffers: a wrong shape must not become an out-of-bounds read
@@ -476,11 +488,21 @@ class Engine:
                 raise ValueError("eps must be [B, P, Hq, dim_S] = [%d, %d, %d, %d], got %s" % (b, p, hq, self.S, eps.shape))
         outs = [np.empty((b, hq, self.S), np.float32), np.empty((b, hq, self.S), np.float32),
                 np.empty((b, hq), np.float32), np.empty((b, hq), np.float32)]
-        if want_particles:
-            outs += [np.empty((b, p, hq, self.S), np.float32), np.empty((b, p, hq), np.float32)]
-        ptrs = [L.ptr(o) for o in outs] + [None] * (6 - len(outs))
-        L.check(L.lib.bbmpc_predict_trajectory_particles(self._h, L.ptr(states), L.ptr(seq), b, hq, L.ptr(eps), *ptrs))
-        return tuple(outs)
+        parts = [np.empty((b, p, hq, self.S), np.float32), np.empty((b, p, hq), np.float32)] if want_particles else []
+        pptrs = [L.ptr(o) for o in parts] or [None, None]
+        if quantile_ranks is None:
+            L.check(L.lib.bbmpc_predict_trajectory_particles(self._h, L.ptr(states), L.ptr(seq), b, hq, L.ptr(eps),
+                                                             *([L.ptr(o) for o in outs] + pptrs)))
+            return tuple(outs + parts)
+        ranks = np.ascontiguousarray(np.asarray(quantile_ranks).reshape(-1), np.int32)
+        nl = ranks.size
+        if not 1 <= nl <= L.MAX_QUANTILE_LEVELS:           # (the C side sizes its copies by num_levels: refuse before it)
+            raise ValueError("quantile_ranks must hold 1 to %d ranks, got %d" % (L.MAX_QUANTILE_LEVELS, nl))
+        quants = [np.empty((b, nl, hq, self.S), np.float32), np.empty((b, nl, hq), np.float32)]
+        L.check(L.lib.bbmpc_predict_trajectory_quantiles(self._h, L.ptr(states), L.ptr(seq), b, hq, L.ptr(eps),
+                                                         *([L.ptr(o) for o in outs] + pptrs + [nl, ranks.ctypes.data_as(ctypes.c_void_p)]
+                                                           + [L.ptr(o) for o in quants])))
+        return tuple(outs + quants + parts)
 
     def predict_trajectory_particles_dev(self, d_states, d_action_sequences, batch, horizon, d_eps=0, d_state_mean=0,
                                          d_state_std=0, d_reward_mean=0, d_reward_std=0, d_particle_states=0,
@@ -491,6 +513,19 @@ class Engine:
             self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_action_sequences), int(batch), int(horizon),
             *[ctypes.c_void_p(v or 0) for v in (d_eps, d_state_mean, d_state_std, d_reward_mean, d_reward_std,
                                                 d_particle_states, d_particle_rewards)]))
+
+    def predict_trajectory_quantiles_dev(self, d_states, d_action_sequences, batch, horizon, quantile_ranks, d_eps=0,
+                                         d_state_mean=0, d_state_std=0, d_reward_mean=0, d_reward_std=0, d_particle_states=0,
+                                         d_particle_rewards=0, d_state_quantiles=0, d_reward_quantiles=0):
+        """bbmpc_predict_trajectory_quantiles_dev on device addresses (any output may be 0, not all eight); quantile_ranks
+        is a host sequence."""
+        ranks = np.ascontiguousarray(np.asarray(quantile_ranks).reshape(-1), np.int32)
+        L.check(L.lib.bbmpc_predict_trajectory_quantiles_dev(
+            self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_action_sequences), int(batch), int(horizon),
+            *([ctypes.c_void_p(v or 0) for v in (d_eps, d_state_mean, d_state_std, d_reward_mean, d_reward_std,
+                                                 d_particle_states, d_particle_rewards)]
+              + [int(ranks.size), ranks.ctypes.data_as(ctypes.c_void_p)]
+              + [ctypes.c_void_p(d_state_quantiles or 0), ctypes.c_void_p(d_reward_quantiles or 0)])))
 
     def set_keep_plan(self, enabled=True):
         """Opt-in switch of plan readback (bbmpc_set_keep_plan): the control steps that follow keep their solution in HBM

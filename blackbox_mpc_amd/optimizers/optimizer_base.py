@@ -86,14 +86,17 @@ class OptimizerBase:
         states, rewards = eng.predict_trajectories(np.asarray(current_state, np.float32), actions)
         return actions, states, rewards
 
-    def plan_distribution(self, current_state):
+    def plan_distribution(self, current_state, quantiles=None):
         """(actions [A,H,U], state_mean [A,H,S], state_std [A,H,S], reward_mean [A,H], reward_std [A,H]): the plan of
         `plan`, rolled out from `current_state` once per particle of the ParticleTrajectoryEvaluator -- process noise, the
         ensemble member a particle follows, the noise a log-variance head predicts -- and reduced to its per-step mean and
-        spread.  Needs keep_plan(True) before the call whose plan is wanted, and a ParticleTrajectoryEvaluator."""
+        spread.  quantiles: levels in (0, 1], e.g. [0.05, 0.95] -- then state_quantiles [A,L,H,S] and reward_quantiles
+        [A,L,H] follow (ParticleTrajectoryEvaluator.predict_trajectory_distribution).  Needs keep_plan(True) before the call
+        whose plan is wanted, and a ParticleTrajectoryEvaluator."""
         if getattr(self._trajectory_evaluator, "particle_settings", None) is None:
             raise TypeError("plan_distribution() needs a ParticleTrajectoryEvaluator (the optimizer's evaluator is %s, which is "
                             "deterministic: use plan())" % type(self._trajectory_evaluator).__name__)
+        ranks = None if quantiles is None else self._trajectory_evaluator.quantile_ranks(quantiles)
         eng = self._require_engine()
         try:
             actions = eng.get_plan()
@@ -102,7 +105,7 @@ class OptimizerBase:
                 raise RuntimeError("plan_distribution(): plan readback was not on during the last call -- switch it on with "
                                    "optimizer.keep_plan(True) (MPCPolicy.keep_plan(True)) before calling the optimizer") from ex
             raise
-        return (actions,) + eng.predict_trajectory_particles(np.asarray(current_state, np.float32), actions)
+        return (actions,) + eng.predict_trajectory_particles(np.asarray(current_state, np.float32), actions, quantile_ranks=ranks)
 
     def reset(self):
         if type(self)._engine_optimizer == L.OPT_NONE:
@@ -131,6 +134,9 @@ class OptimizerBase:
         particles = getattr(trajectory_evaluator, "particle_settings", None)
         if particles is not None:                     # a ParticleTrajectoryEvaluator: (num_particles, process_noise_std, risk_kappa)
             self._engine.set_particles(*particles)
+            risk = getattr(trajectory_evaluator, "risk_settings", (L.RISK_MEAN_STD, 0))
+            if risk[0] != L.RISK_MEAN_STD:            # (the engine is new: mean - kappa * std is what it starts with)
+                self._engine.set_particle_risk(*risk)
         if self._engine._param_fns:
             self._require_engine = self._require_engine_and_params
         else:

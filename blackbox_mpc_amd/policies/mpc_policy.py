@@ -71,15 +71,16 @@ class MPCPolicy(ModelBasedBasePolicy):
             return actions[0], states[0], rewards[0]
         return actions, states, rewards
 
-    def plan_distribution(self, observations):
+    def plan_distribution(self, observations, quantiles=None):
         """The plan the last `act` took its action from, rolled out from `observations` once per particle of the
         ParticleTrajectoryEvaluator: (actions [A,H,U], state_mean [A,H,S], state_std [A,H,S], reward_mean [A,H],
-        reward_std [A,H]); a 1-D observation is un-batched as in `plan`."""
+        reward_std [A,H]) and, with quantile levels such as [0.05, 0.95], (state_quantiles [A,L,H,S], reward_quantiles
+        [A,L,H]); a 1-D observation is un-batched as in `plan`."""
         observations = np.asarray(observations)
         batched = observations
         if observations.ndim == 1:
             batched = np.tile(observations[None], (self._optimizer._num_agents, 1))
-        out = self._optimizer.plan_distribution(batched)
+        out = self._optimizer.plan_distribution(batched, quantiles=quantiles)
         if observations.ndim == 1:
             return tuple(o[0] for o in out)
         return out

@@ -344,6 +344,23 @@ int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* ac
 int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const float* d_action_sequences, int32_t n_pop,
                                  float* d_scores, float* d_returns);
 
+/* How the particle evaluator reduces the P returns of a candidate to its score.  BBMPC_RISK_MEAN_STD (the default):
+ * mean - risk_kappa * std as above; tail_count must be 0.  BBMPC_RISK_CVAR: the conditional value at risk of the lower
+ * tail, the mean of the tail_count worst returns (1 <= tail_count <= num_particles; tail_count = 1 is the worst case over
+ * the particles) -- with the stable rank  rank[p] = #{q : r[q] < r[p]} + #{q < p : r[q] == r[p]}  (equal returns are
+ * ordered by particle index, every comparison exact),
+ *     score[n,a] = (sum of r[n,p,a] over the p with rank[p] < tail_count, in particle index order) / (float)tail_count
+ * in fp32, so the selection is exact given the returns and tail_count = num_particles gives the bits of the risk_kappa = 0
+ * mean.  risk_kappa is ignored under CVaR.  Everything else of bbmpc_set_particles is unchanged: the returns (NaN -> -1e6 per
+ * particle, so no NaN is ranked), the noise, the bound penalties subtracted from the score, the feasible samples written
+ * back; all six optimizers then plan on the CVaR score, and bbmpc_evaluate[_particles] returns it.  The setting is handle
+ * state: it may be made before or after bbmpc_set_particles and survives bbmpc_set_particles(0).
+ * BBMPC_E_INVALID: an unknown kind, tail_count != 0 with MEAN_STD, tail_count outside [1, 64], tail_count > num_particles --
+ * from whichever of bbmpc_set_particles / bbmpc_set_particle_risk comes second.  A refused call leaves the handle as it was. */
+#define BBMPC_RISK_MEAN_STD 0
+#define BBMPC_RISK_CVAR     1
+int bbmpc_set_particle_risk(bbmpc_handle h, int32_t kind, int32_t tail_count);
+
 /* Model ensemble with trajectory sampling for the particle evaluator (PETS, TS-infinity): num_members networks of the shape,
  * activations and six normalisation statistics of the model that bbmpc_set_mlp installed, e.g. fitted on bootstrap
  * resamples of the training rows.  weights / biases: num_members x n_layers pointers, member-major (entry e * n_layers + l),
@@ -454,6 +471,28 @@ int bbmpc_predict_trajectory_particles_dev(bbmpc_handle h, const float* d_states
                                            int32_t horizon, const float* d_eps, float* d_state_mean, float* d_state_std,
                                            float* d_reward_mean, float* d_reward_std, float* d_particle_states,
                                            float* d_particle_rewards);
+/* The same with nearest-rank quantiles over the particles: bbmpc_predict_trajectory_particles' arguments, then num_levels in
+ * [1, 8], ranks [num_levels] (a HOST array in both variants, each rank in [0, num_particles)) and the outputs
+ * state_quantiles [B,L,Hq,S], reward_quantiles [B,L,Hq] (L = num_levels).  With the stable rank of bbmpc_set_particle_risk
+ * among the P particle values x[b,:,t,f],
+ *     state_quantiles[b,l,t,f] = x[b,p,t,f] of the particle p whose rank is ranks[l]
+ * -- an element of the particle tensor, bit for bit: rank 0 is the minimum over the particles, P - 1 the maximum, P = 1
+ * returns the particle; the level tau in (0, 1] of the nearest-rank definition is rank ceil(tau P) - 1.  The same for the
+ * rewards.  The draws, the trajectories and the moments are those of bbmpc_predict_trajectory_particles (same eps, same
+ * bits); all eight outputs are optional, not all may be NULL.  Per-step values are not NaN-filtered here: where a NaN is
+ * among the P values their ranks mean nothing and so do the quantiles of that element (nothing special is propagated).
+ * Refusals, before anything is allocated, copied or launched: everything bbmpc_predict_trajectory_particles refuses;
+ * BBMPC_E_INVALID: num_levels outside [1, 8], ranks NULL, a rank outside [0, num_particles); BBMPC_E_UNSUPPORTED:
+ * B * L * Hq * S >= 2^31. */
+int bbmpc_predict_trajectory_quantiles(bbmpc_handle h, const float* states, const float* action_sequences, int32_t batch,
+                                       int32_t horizon, const float* eps, float* state_mean, float* state_std,
+                                       float* reward_mean, float* reward_std, float* particle_states, float* particle_rewards,
+                                       int32_t num_levels, const int32_t* ranks, float* state_quantiles, float* reward_quantiles);
+int bbmpc_predict_trajectory_quantiles_dev(bbmpc_handle h, const float* d_states, const float* d_action_sequences, int32_t batch,
+                                           int32_t horizon, const float* d_eps, float* d_state_mean, float* d_state_std,
+                                           float* d_reward_mean, float* d_reward_std, float* d_particle_states,
+                                           float* d_particle_rewards, int32_t num_levels, const int32_t* ranks,
+                                           float* d_state_quantiles, float* d_reward_quantiles);
 
 /* Closed-loop episode on the device -- counterpart of utils/rollouts.py:60-139 (_sample) with the engine's own
  * model as the environment: T control steps, each feeding its predicted next state back as the next observation;
