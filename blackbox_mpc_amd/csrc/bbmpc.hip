@@ -2,6 +2,7 @@
 #include "engine.hpp"
 #include "abi_util.hpp"
 #include "engine_util.hpp"
+#include "kernels_corr.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -539,6 +540,57 @@ void Engine::draw_candidates(int mode, RolloutArgs& ra) {
     HIP_CHECK(hipGetLastError());
 }
 
+// bbmpc_set_sampling_correlation.  Everything that can be refused is refused before the handle
+// changes; the copy runs on the handle's stream and is waited for.
+void Engine::set_sampling_correlation(const float* mix, int64_t count) {
+    if (!mix) {
+        REQUIRE(count == 0, BBMPC_E_INVALID, "sampling correlation: a null matrix goes with count 0 (it removes the matrix)");
+        if (corr_installed) invalidate_step_graph();
+        corr_installed = false;
+        return;
+    }
+    REQUIRE(cfg.optimizer == BBMPC_OPT_CEM || cfg.optimizer == BBMPC_OPT_PI2, BBMPC_E_UNSUPPORTED,
+            "sampling correlation with an optimizer other than CEM or PI2: only their candidates are truncated-normal draws around a mean");
+    REQUIRE(!pop_sharded() && cfg.population_global <= N && auto_split <= 1, BBMPC_E_UNSUPPORTED,
+            "sampling correlation with a sharded population: the sharded control steps draw inside their rollout kernels");
+    REQUIRE(HU <= CORR_MAX_HU, BBMPC_E_UNSUPPORTED,
+            "sampling correlation: planning_horizon * dim_u = " + std::to_string(HU) + " exceeds " + std::to_string(CORR_MAX_HU) +
+                ", the most one wave's draws take of a CU's LDS (k_gen_candidates_corr's tile is H*U x 64 floats)");
+    REQUIRE(count == (int64_t)H * H, BBMPC_E_INVALID,
+            "sampling correlation: the matrix must be [planning_horizon, planning_horizon] = " + std::to_string((int64_t)H * H) + " floats");
+    for (int64_t i = 0; i < count; ++i) REQUIRE(std::isfinite(mix[i]), BBMPC_E_INVALID, "sampling correlation: the matrix has a non-finite element");
+    std::vector<int> row_end((size_t)H, 1);
+    for (int t = 0; t < H; ++t)
+        for (int s = H - 1; s >= 1; --s)
+            if (mix[(size_t)t * H + s] != 0.0f) { row_end[t] = s + 1; break; }
+    invalidate_step_graph();
+    if (!d_corr_mix.p) { d_corr_mix.alloc((size_t)H * H); d_corr_end.alloc((size_t)H); }
+    corr_installed = false;                        // (a failed copy must not leave half a matrix in use)
+    HIP_CHECK(hipMemcpyAsync(d_corr_mix.p, mix, (size_t)H * H * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_corr_end.p, row_end.data(), (size_t)H * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    corr_installed = true;
+}
+
+// The mixed candidates of this CEM / PI2 iteration into the sample buffer (kernels_corr.hpp): clipped for CEM, as drawn for
+// PI2, whose rollout clips and charges the penalty itself.
+void Engine::draw_candidates_corr(RolloutArgs& ra) {
+    REQUIRE(ra.samples, BBMPC_E_STATE, "sampling correlation: no sample buffer");
+    REQUIRE(ra.H == H && ra.HU == HU, BBMPC_E_INVALID, "internal: correlated draw horizon");
+    const size_t lds = (size_t)HU * CORR_LANES * sizeof(float);
+    dim3 grid((ra.n_pop + CORR_LANES - 1) / CORR_LANES, A), block(CORR_LANES);
+    if (cfg.optimizer == BBMPC_OPT_CEM) {
+        want_lds((const void*)k_gen_candidates_corr<true>, lds);
+        hipLaunchKernelGGL(k_gen_candidates_corr<true>, grid, block, lds, stream, ra, (const float*)d_corr_mix.p, (const int*)d_corr_end.p, ra.mean, ra.sigma,
+                           ra.lo, ra.hi, ra.samples);
+    } else {
+        want_lds((const void*)k_gen_candidates_corr<false>, lds);
+        hipLaunchKernelGGL(k_gen_candidates_corr<false>, grid, block, lds, stream, ra, (const float*)d_corr_mix.p, (const int*)d_corr_end.p, ra.mean, ra.sigma,
+                           ra.lo, ra.hi, ra.samples);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
 // [batch, U] actions in a dense block: the caller's own when they are, else gathered from rows astride apart
 const float* Engine::dense_actions(const float* d_actions, int astride, int batch) {
     if (astride == U) return d_actions;
@@ -548,6 +600,11 @@ const float* Engine::dense_actions(const float* d_actions, int astride, int batc
 }
 
 void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
+    if (corr_on() && mode == SRC_TRUNC) {                 // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
+        draw_candidates_corr(ra);
+        mode = SRC_BUF;
+        ra.cand = ra.samples;
+    }
     if (particles_on()) {                                 // bbmpc_set_particles: noisy rollouts + aggregate (bbmpc_particles.hip)
         rollout_particles(mode, pen, ra, nullptr, 0);
         return;
@@ -792,7 +849,7 @@ void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_recor
             // (no BBMPC_FIX_Q2_CEM_WARM_START): prev_mean, var0 and the sigma they give are constants, so from the second
             // control step on k_dist_init is skipped as for PI2 below -- the first rollout samples from (prev_mean, sigma0)
             // and reads the state from the pinned buffer, the first refit smooths against (prev_mean, var0)
-            const bool cem_skip = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() &&
+            const bool cem_skip = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() &&
                                   iters >= 1 && k <= 64 && !sw.refit_v1 && !fix(BBMPC_FIX_Q2_CEM_WARM_START) && cem_sigma0_ready &&
                                   pi2_copy_seen && stage_state_src != nullptr;
             const float* cem_pinned = nullptr;
@@ -905,7 +962,7 @@ void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_recor
             // launch of its own in front of a 360 us control step) has nothing left to do -- PI2 never changes sigma, the
             // first rollout samples around prev_mean directly, the refit writes every element of the mean, and the first
             // rollout reads the state from the pinned buffer itself (its workgroup 0 stores it for the later launches).
-            const bool skip_init = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() &&
+            const bool skip_init = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() &&
                                    iters >= 1 && pi2_dist_ready && pi2_copy_seen && stage_state_src != nullptr;
             const float* pinned_state = nullptr;
             last_step_steady = skip_init;
@@ -1712,7 +1769,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                 // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
                 // replayed as a graph (engine.hpp: step_graph)
                 const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&
-                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && e.stream == e.own_stream && !e.any_injected();
+                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && e.stream == e.own_stream && !e.any_injected();
                 const uint64_t sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
                 bool replayed = false;
                 if (graph_ok && e.step_graph && e.step_graph_sig == sig) {
@@ -1975,6 +2032,21 @@ int bbmpc_set_trace(bbmpc_handle h, int32_t enabled) {
     if (enabled && h->e->auto_split > 1)
         throw HipError(BBMPC_E_UNSUPPORTED, "the parity trace is per shard: not available for a population > 32768 (played as shards)");
     h->e->trace_on = enabled != 0;
+    API_END
+}
+
+int bbmpc_set_sampling_correlation(bbmpc_handle h, const float* mix, int64_t count) {
+    API_BEGIN
+    CHECK_HANDLE(h);                     // (settles the handle: a resident control-step kernel is stopped first)
+    h->e->set_sampling_correlation(mix, count);
+    API_END
+}
+
+int bbmpc_get_sampling_correlation(bbmpc_handle h, int32_t* installed) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(installed);
+    *installed = h->e->corr_on() ? 1 : 0;
     API_END
 }
 

@@ -452,6 +452,16 @@ struct Engine {
     void predict_trajectory_quantiles_dev(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps, float* d_smean,
                                           float* d_sstd, float* d_rmean, float* d_rstd, float* d_pstates, float* d_prewards, int num_levels,
                                           const int32_t* ranks, float* d_squant, float* d_rquant);
+    // temporally correlated sampling for CEM / PI2 (bbmpc_set_sampling_correlation; kernels_corr.hpp):
+    // one H x H mixing matrix applied along the time axis of the standard draws.  While it is installed, control steps are
+    // routed as bbmpc_set_trace routes them (one launch sequence per iteration: no resident, fused or graph-replayed form)
+    // and launch_rollout draws the candidates into the sample buffer, then rolls them out in the SRC_BUF form.
+    DevBuf<float> d_corr_mix;          // [H][H] row-major
+    DevBuf<int> d_corr_end;            // [H] per row: index after the last non-zero column (at least 1)
+    bool corr_installed = false;
+    bool corr_on() const { return corr_installed; }
+    void set_sampling_correlation(const float* mix, int64_t count);
+    void draw_candidates_corr(RolloutArgs& ra);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
     DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging

@@ -527,6 +527,22 @@ class Engine:
               + [int(ranks.size), ranks.ctypes.data_as(ctypes.c_void_p)]
               + [ctypes.c_void_p(d_state_quantiles or 0), ctypes.c_void_p(d_reward_quantiles or 0)])))
 
+    def set_sampling_correlation(self, matrix):
+        """Temporally correlated sampling for CEM / PI2 (bbmpc_set_sampling_correlation): `matrix` is the [H, H] mixing
+        matrix applied along the time axis of the standard draws (utils/colored_noise.py builds the usual ones); None
+        removes it.  While one is installed control steps take the per-iteration launch paths, as with set_trace."""
+        if matrix is None:
+            L.check(L.lib.bbmpc_set_sampling_correlation(self._h, None, 0))
+            return
+        m = L.f32c(matrix)
+        L.check(L.lib.bbmpc_set_sampling_correlation(self._h, L.ptr(m), int(m.size)))
+
+    def sampling_correlation_installed(self):
+        """True while a mixing matrix is installed (bbmpc_get_sampling_correlation)."""
+        v = ctypes.c_int32(0)
+        L.check(L.lib.bbmpc_get_sampling_correlation(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
     def set_keep_plan(self, enabled=True):
         """Opt-in switch of plan readback (bbmpc_set_keep_plan): the control steps that follow keep their solution in HBM
         (the routing of set_trace: same results, slower paths).  Off by default."""

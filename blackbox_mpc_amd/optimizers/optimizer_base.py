@@ -137,6 +137,9 @@ class OptimizerBase:
             risk = getattr(trajectory_evaluator, "risk_settings", (L.RISK_MEAN_STD, 0))
             if risk[0] != L.RISK_MEAN_STD:            # (the engine is new: mean - kappa * std is what it starts with)
                 self._engine.set_particle_risk(*risk)
+        mix = getattr(self, "_sampling_mix", None)    # CEM / PI2 with noise_beta / sampling_correlation
+        if mix is not None:
+            self._engine.set_sampling_correlation(mix)
         if self._engine._param_fns:
             self._require_engine = self._require_engine_and_params
         else:

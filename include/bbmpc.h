@@ -494,6 +494,29 @@ int bbmpc_predict_trajectory_quantiles_dev(bbmpc_handle h, const float* d_states
                                            float* d_particle_rewards, int32_t num_levels, const int32_t* ranks,
                                            float* d_state_quantiles, float* d_reward_quantiles);
 
+/* Temporally correlated ("colored") sampling for CEM and PI2.  mix is a row-major [H, H] matrix M
+ * (H = planning_horizon) shared by all agents and action dimensions; with z[n,a,s,u] the unit truncated-normal draws of
+ * an iteration (stream BBMPC_NOISE_TRUNC_NORMAL, keyed as always; an injected tensor of that kind is the z that is mixed,
+ * bbmpc_dump_noise still returns the unmixed z) the candidates become
+ *     y[n,a,t,u] = sum over s = 0 .. H-1, ascending, in fp32, of M[t,s] * z[n,a,s,u]
+ *     x[n,a,t,u] = y * sigma[a,t,u] + mean[a,t,u]
+ * with the sigma and mean the iteration would use anyway; M = identity gives the bits of the uncorrelated draw.  CEM: x is
+ * clipped to [action_low, action_high] (a mixed draw is not bounded by two sigma); the clipped x is rolled out, stored and
+ * seen by the refit, no penalty.  PI2: unchanged from there on (clip, squared-norm penalty, feasible samples stored).
+ * iCEM's power-law noise, smooth-MPPI and Ornstein-Uhlenbeck exploration are all a lower-triangular M (the Cholesky factor
+ * of the wanted autocovariance; blackbox_mpc_amd/utils/colored_noise.py builds two).
+ * mix != NULL, count == H * H installs M: copied to the device on the handle's stream, the call waits for the copy.
+ * mix == NULL, count == 0 removes it and restores every path bit for bit.  While a matrix is installed, control steps are
+ * routed as bbmpc_set_trace routes them (one launch sequence per iteration: no resident, fused or graph-replayed form): same
+ * rule on every model, slower paths.  Like the other setters the call stops a resident control-step kernel first and
+ * invalidates the captured step graph.  Survives bbmpc_reset.
+ * Refusals, before anything is allocated, copied or launched (the handle stays as it was): BBMPC_E_UNSUPPORTED: an
+ * optimizer other than CEM or PI2, a sharded population, H * dim_u > 636 (the kernel's LDS tile); BBMPC_E_INVALID: count
+ * != H * H (or != 0 with mix == NULL), a non-finite element.  No counterpart in the reference. */
+int bbmpc_set_sampling_correlation(bbmpc_handle h, const float* mix, int64_t count);
+/* *installed = 1 while a matrix is installed, else 0. */
+int bbmpc_get_sampling_correlation(bbmpc_handle h, int32_t* installed);
+
 /* Closed-loop episode on the device -- counterpart of utils/rollouts.py:60-139 (_sample) with the engine's own
  * model as the environment: T control steps, each feeding its predicted next state back as the next observation;
  * nothing leaves HBM until the end.  records_out is [T][A][U+S+1] (action | next_state | reward) on the host.
