@@ -791,7 +791,32 @@ void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_recor
     ra.penalty_out = d_penalty.p;
     ra.key = key(step);
     ra.pop_offset = cfg.population_offset;
+    switch (cfg.optimizer) {
+        case BBMPC_OPT_RANDOM_SEARCH: optimize_random_search(ra); break;
+        case BBMPC_OPT_CEM: optimize_cem(ra); break;
+        case BBMPC_OPT_PI2: optimize_pi2(ra); break;
+        case BBMPC_OPT_SPSA: optimize_spsa(ra, step); break;
+        case BBMPC_OPT_PSO: optimize_pso(ra, step); break;
+        case BBMPC_OPT_CMAES: optimize_cma(ra, step); break;
+        default: throw HipError(BBMPC_E_UNSUPPORTED, "optimizer not built yet");
+    }
+    finalize(d_state_in, add_noise, d_record_out, d_next_out, step);
+}
 
+// ps_part of every rank -> ps_all.  The exchange sits ON the launch stream: the merge needs it, nothing can overlap it.
+// A sharded code path without a communicator (BBMPC_POPSHARD_FORCE on one handle) has only its own payload to hand over.
+void Engine::gather_shards(size_t pw, const char* what) {
+    if (ps_loopback > 1) return;                   // play_shards wrote every shard's slot itself
+    if (rc.comm) {
+        const Rccl& r = *rc.api;
+        r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), what);
+    } else {
+        REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
+        HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
+    }
+}
+
+RefitArgs Engine::refit_args() const {
     RefitArgs rf;
     memset(&rf, 0, sizeof(rf));
     rf.N = N; rf.A = A; rf.H = H; rf.U = U; rf.HU = HU; rf.Nst = Nst; rf.k = k;
@@ -801,263 +826,213 @@ void Engine::optimize_dev(const float* d_state_in, int add_noise, float* d_recor
     rf.lo = d_lo.p; rf.hi = d_hi.p;
     rf.mean = d_mean.p; rf.var = d_var.p; rf.sigma = d_sigma.p;
     rf.elites = d_elites.p; rf.action = d_action.p;
+    return rf;
+}
 
-    const int nelem = A * HU;
-    const size_t inj_stride = (size_t)A * HU * Nst;
-    switch (cfg.optimizer) {
-        case BBMPC_OPT_RANDOM_SEARCH: {
-            ra.stream = BBMPC_NOISE_UNIFORM; ra.iter = 0;
-            ra.inj = injected(BBMPC_NOISE_UNIFORM);
-            if (pop_sharded()) {
-                // population sharded over ranks: local first maximum, one exchange, first maximum by global index
-                const int G = ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1);
-                const size_t pw = (size_t)A * (U + 2);
-                if (!ps_part.p || ps_part.n < pw) ps_part.alloc(pw);
-                if (ps_all.n < pw * G) ps_all.alloc(pw * G);
-                if (ps_loopback > 1) {
-                    for (int r = 0; r < G; ++r) {
-                        ra.pop_offset = r * N;
-                        launch_rollout(SRC_UNIFORM, false, ra);
-                        hipLaunchKernelGGL(k_refit_argmax, dim3(A), dim3(REFIT_THREADS), 0, stream, rf, ps_all.p + pw * r, r * N);
-                    }
-                    ra.pop_offset = cfg.population_offset;
-                } else {
-                    launch_rollout(SRC_UNIFORM, false, ra);
-                    hipLaunchKernelGGL(k_refit_argmax, dim3(A), dim3(REFIT_THREADS), 0, stream, rf, ps_part.p, (int)cfg.population_offset);
-                    if (rc.comm) {
-                        const Rccl& r = *rc.api;
-                        r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), "ncclAllGather (RandomSearch local bests)");
-                    } else {
-                        REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
-                        HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
-                    }
-                }
-                HIP_CHECK(hipGetLastError());
-                hipLaunchKernelGGL(k_argmax_merge, dim3(A), dim3(64), 0, stream, rf, ps_all.p, G);
-                HIP_CHECK(hipGetLastError());
-                capture_trace(0);
-                break;
-            }
-            launch_rollout(SRC_UNIFORM, false, ra);
-            hipLaunchKernelGGL(k_refit_argmax, dim3(A), dim3(REFIT_THREADS), 0, stream, rf, (float*)nullptr, 0);
-            HIP_CHECK(hipGetLastError());
-            capture_trace(0);
-            break;
-        }
-        case BBMPC_OPT_CEM: {
-            // Learned model on the quad kernel, the reference's restart from the constructor distribution every control step
-            // (no BBMPC_FIX_Q2_CEM_WARM_START): prev_mean, var0 and the sigma they give are constants, so from the second
-            // control step on k_dist_init is skipped as for PI2 below -- the first rollout samples from (prev_mean, sigma0)
-            // and reads the state from the pinned buffer, the first refit smooths against (prev_mean, var0)
-            const bool cem_skip = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() &&
-                                  iters >= 1 && k <= 64 && !sw.refit_v1 && !fix(BBMPC_FIX_Q2_CEM_WARM_START) && cem_sigma0_ready &&
-                                  pi2_copy_seen && stage_state_src != nullptr;
-            const float* cem_pinned = nullptr;
-            last_step_steady = cem_skip;
-            if (cem_skip) {
-                cem_pinned = stage_state_src;
-            } else {
-                hipLaunchKernelGGL(k_dist_init, dim3((nelem + 255) / 256), dim3(256), 0, stream, A, HU, U, d_lo.p, d_hi.p,
-                                   d_prev_mean.p, d_var0.p, d_mean.p, d_var.p, d_sigma.p, 1, stage_state_src, d_state.p, A * S);
-                if (!cem_sigma0_ready && !fix(BBMPC_FIX_Q2_CEM_WARM_START)) {
-                    if (!step_capturing) invalidate_step_graph();   // (a replayed control step samples from d_sigma0: never capture across its allocation)
-                    d_sigma0.alloc(nelem);
-                    HIP_CHECK(hipMemcpyAsync(d_sigma0.p, d_sigma.p, (size_t)nelem * 4, hipMemcpyDeviceToDevice, stream));
-                    cem_sigma0_ready = true;
-                }
-            }
-            stage_state_src = nullptr;
-            // iters == 0: action = mean[:,0] of the untouched distribution (otherwise the last refit writes it)
-            if (iters == 0)
-                HIP_CHECK(hipMemcpy2DAsync(d_action.p, U * 4, d_prev_mean.p, HU * 4, U * 4, A, hipMemcpyDeviceToDevice, stream));
-            const float* inj_t = injected(BBMPC_NOISE_TRUNC_NORMAL);
-            // LDS budget for the refit: rewards + elite idx + elite tile
-            const int kpad = (k + 3) & ~3;
-            const int fixed = Nst + kpad + TOPK_HIST_WORDS + 2 * kpad;
-            const int budget = fixed * 4 > 48 * 1024 ? 158 * 1024 / 4 : 62 * 1024 / 4;     // floats; big populations take the whole LDS
-            int JC = (int)((size_t)std::max(budget - fixed, k) / (size_t)k);
-            JC = std::max(1, std::min(JC, HU));
-            const size_t lds = (size_t)(fixed + (size_t)k * JC) * 4;
-            want_lds((const void*)k_refit_cem_v2, (size_t)fixed * 4);
-            want_lds((const void*)k_refit_cem, lds);
-            for (int it = 0; it < iters; ++it) {
-                ra.stream = BBMPC_NOISE_TRUNC_NORMAL; ra.iter = (uint32_t)it;
-                ra.inj = inj_t ? inj_t + inj_stride * it : nullptr;
-                if (pop_sharded()) {
-                    // population sharded over ranks: local top-k + rows, one exchange, global top-k + refit
-                    const int G = ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1);
-                    const size_t pw = (size_t)A * k * (HU + 2);
-                    if (!ps_part.p) ps_part.alloc(pw);
-                    if (ps_all.n < pw * G) ps_all.alloc(pw * G);
-                    const size_t tl = (size_t)fixed * 4;
-                    want_lds((const void*)k_cem_local_topk, tl);
-                    const int psg = sw.refit_wgs > 0 ? sw.refit_wgs : std::max(1, std::min(8, HU / 16));   // workgroups per agent (kernels_tail.hpp)
-                    RefitArgs rfs = rf;
-                    if (!trace_on) rfs.elites = nullptr;
-                    if (ps_loopback > 1) {
-                        for (int r = 0; r < G; ++r) {
-                            ra.pop_offset = r * N;
-                            launch_rollout(SRC_TRUNC, false, ra);
-                            hipLaunchKernelGGL(k_cem_local_topk, dim3(psg, A), dim3(1024), tl, stream, rf, r * N, ps_all.p + pw * r);
-                        }
-                        ra.pop_offset = cfg.population_offset;
-                    } else {
-                        launch_rollout(SRC_TRUNC, false, ra);
-                        hipLaunchKernelGGL(k_cem_local_topk, dim3(psg, A), dim3(1024), tl, stream, rf, (int)cfg.population_offset, ps_part.p);
-                        if (rc.comm) {
-                            const Rccl& r = *rc.api;
-                            r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), "ncclAllGather (CEM local elites)");
-                        } else {
-                            REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
-                            HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
-                        }
-                    }
-                    HIP_CHECK(hipGetLastError());
-                    const size_t ml = ((size_t)2 * G * k + k) * 4;
-                    want_lds((const void*)k_cem_merge, ml);
-                    hipLaunchKernelGGL(k_cem_merge, dim3(psg, A), dim3(256), ml, stream, rfs, ps_all.p, G);
-                    HIP_CHECK(hipGetLastError());
-                    capture_trace(it);
-                    continue;
-                }
-                bool first_from_constants = false;
-                if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path()) {
-                    if (cem_skip) { ra.mean = d_prev_mean.p; ra.sigma = d_sigma0.p; ra.state = cem_pinned; }
-                    mlp_state_copy = d_state.p;                        // (without the skip: only asks whether the kernel would take it)
-                    launch_rollout(SRC_TRUNC, false, ra);
-                    const bool took = mlp_state_copy == nullptr;
-                    mlp_state_copy = nullptr;
-                    pi2_copy_seen = took;
-                    if (cem_skip) {
-                        if (!took)                                       // a shape the quad kernel refused after all: nobody stored the state
-                            HIP_CHECK(hipMemcpyAsync(d_state.p, cem_pinned, (size_t)A * S * 4, hipMemcpyDefault, stream));
-                        ra.mean = d_mean.p; ra.sigma = d_sigma.p; ra.state = d_state_in;
-                        first_from_constants = true;
-                    }
-                } else {
-                    launch_rollout(SRC_TRUNC, false, ra);
-                }
-                if (k <= 64 && !sw.refit_v1) {
-                    const int rthreads = N > 512 ? 1024 : (N > 256 ? 512 : 256);
-                    RefitArgs rf2 = rf;
-                    if (!trace_on) rf2.elites = nullptr;          // the sorted elite list is only needed by the parity trace
-                    if (first_from_constants) { rf2.mean_in = d_prev_mean.p; rf2.var_in = d_var0.p; }
-                    // G workgroups per agent share the elite gather (kernels_refit.hpp); at least 16 rows each
-                    const int rg = sw.refit_wgs > 0 ? sw.refit_wgs : std::max(1, std::min(8, HU / 16));
-                    hipLaunchKernelGGL(k_refit_cem_v2, dim3(rg, A), dim3(rthreads), (size_t)fixed * 4, stream, rf2);
-                } else {
-                    hipLaunchKernelGGL(k_refit_cem, dim3(A), dim3(REFIT_THREADS), lds, stream, rf, JC);
-                }
-                HIP_CHECK(hipGetLastError());
-                capture_trace(it);
-            }
-            if (fix(BBMPC_FIX_Q2_CEM_WARM_START)) {
-                if (cfg.dynamics == BBMPC_DYN_MLP || user_path()) pending_warm = 2;      // prev = mean, in k_tail_mlp
-                else HIP_CHECK(hipMemcpyAsync(d_prev_mean.p, d_mean.p, (size_t)nelem * 4, hipMemcpyDeviceToDevice, stream));
-            }
-            break;
-        }
-        case BBMPC_OPT_PI2: {
-            // Learned model on the quad kernel (k_rollout_mlp_q4s): from the second control step on k_dist_init (4.3 us, a
-            // launch of its own in front of a 360 us control step) has nothing left to do -- PI2 never changes sigma, the
-            // first rollout samples around prev_mean directly, the refit writes every element of the mean, and the first
-            // rollout reads the state from the pinned buffer itself (its workgroup 0 stores it for the later launches).
-            const bool skip_init = sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() &&
-                                   iters >= 1 && pi2_dist_ready && pi2_copy_seen && stage_state_src != nullptr;
-            const float* pinned_state = nullptr;
-            last_step_steady = skip_init;
-            if (skip_init) {
-                pinned_state = stage_state_src;
-            } else {
-                hipLaunchKernelGGL(k_dist_init, dim3((nelem + 255) / 256), dim3(256), 0, stream, A, HU, U, d_lo.p, d_hi.p,
-                                   d_prev_mean.p, d_var0.p, d_mean.p, d_var.p, d_sigma.p, 0, stage_state_src, d_state.p, A * S);
-                pi2_dist_ready = true;
-            }
-            stage_state_src = nullptr;
-            if (iters == 0)              // otherwise the last refit writes the action
-                HIP_CHECK(hipMemcpy2DAsync(d_action.p, U * 4, d_prev_mean.p, HU * 4, U * 4, A, hipMemcpyDeviceToDevice, stream));
-            const float* inj_t = injected(BBMPC_NOISE_TRUNC_NORMAL);
-            const size_t lds = (size_t)(Nst + 64) * 4;
-            want_lds((const void*)k_refit_pi2_mw, lds);
-            want_lds((const void*)k_refit_pi2, lds);
-            want_lds((const void*)k_refit_pi2_partial, lds);
-            for (int it = 0; it < iters; ++it) {
-                ra.stream = BBMPC_NOISE_TRUNC_NORMAL; ra.iter = (uint32_t)it;
-                ra.inj = inj_t ? inj_t + inj_stride * it : nullptr;
-                if (pop_sharded()) {
-                    // population sharded over ranks: partial sums here, one exchange, merge in rank order
-                    const int G = ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1);
-                    const size_t pw = (size_t)A * (HU + 2);
-                    if (!ps_part.p) { ps_part.alloc(pw); }
-                    if (ps_all.n < pw * G) ps_all.alloc(pw * G);
-                    dim3 pgrid((HU + PI2_ROWS - 1) / PI2_ROWS, A), pblock(64 * PI2_ROWS);
-                    if (ps_loopback > 1) {
-                        // one handle plays every shard in turn (test / measurement hook): shard r = particles [r*N, (r+1)*N)
-                        for (int r = 0; r < G; ++r) {
-                            ra.pop_offset = r * N;
-                            launch_rollout(SRC_TRUNC, true, ra);
-                            hipLaunchKernelGGL(k_refit_pi2_partial, pgrid, pblock, lds, stream, rf, ps_all.p + pw * r);
-                        }
-                        ra.pop_offset = cfg.population_offset;
-                    } else {
-                        launch_rollout(SRC_TRUNC, true, ra);
-                        hipLaunchKernelGGL(k_refit_pi2_partial, pgrid, pblock, lds, stream, rf, ps_part.p);
-                        if (rc.comm) {
-                            // the exchange sits ON the launch stream: the merge needs it, nothing can overlap it
-                            const Rccl& r = *rc.api;
-                            r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), "ncclAllGather (PI2 partials)");
-                        } else {
-                            REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
-                            HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
-                        }
-                    }
-                    HIP_CHECK(hipGetLastError());
-                    hipLaunchKernelGGL(k_refit_pi2_merge, dim3((HU + 255) / 256, A), dim3(256), 0, stream, rf, ps_all.p, G);
-                    HIP_CHECK(hipGetLastError());
-                    capture_trace(it);
-                    continue;
-                }
-                if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path()) {
-                    if (skip_init) { ra.mean = d_prev_mean.p; ra.state = pinned_state; mlp_state_copy = d_state.p; }
-                    else mlp_state_copy = d_state.p;                   // (only asks: would this launch take the request?)
-                    launch_rollout(SRC_TRUNC, true, ra);
-                    const bool took = mlp_state_copy == nullptr;
-                    mlp_state_copy = nullptr;
-                    pi2_copy_seen = took;
-                    if (skip_init) {
-                        if (!took)                                       // a shape the quad kernel refused after all: nobody stored the state
-                            HIP_CHECK(hipMemcpyAsync(d_state.p, pinned_state, (size_t)A * S * 4, hipMemcpyDefault, stream));
-                        ra.mean = d_mean.p; ra.state = d_state_in;
-                    }
-                } else {
-                    launch_rollout(SRC_TRUNC, true, ra);
-                }
-                if (sw.refit_v1) hipLaunchKernelGGL(k_refit_pi2, dim3(A), dim3(REFIT_THREADS), lds, stream, rf);
-                else hipLaunchKernelGGL(k_refit_pi2_mw, dim3((HU + PI2_ROWS - 1) / PI2_ROWS, A), dim3(64 * PI2_ROWS), lds, stream, rf);
-                HIP_CHECK(hipGetLastError());
-                capture_trace(it);
-            }
-            if (cfg.dynamics == BBMPC_DYN_MLP || user_path()) {
-                pending_warm = 1;                      // prev = shift_left(mean) (pi2.py:92-93) happens in k_tail_mlp
-            } else {
-                hipLaunchKernelGGL(k_shift_left, dim3((nelem + 255) / 256), dim3(256), 0, stream, A, H, U, d_mean.p, d_prev_mean.p);
-                HIP_CHECK(hipGetLastError());
-            }
-            break;
-        }
-        case BBMPC_OPT_SPSA:
-            optimize_spsa(ra, step);
-            break;
-        case BBMPC_OPT_PSO:
-            optimize_pso(ra, step);
-            break;
-        case BBMPC_OPT_CMAES:
-            optimize_cma(ra, step);
-            break;
-        default:
-            throw HipError(BBMPC_E_UNSUPPORTED, "optimizer not built yet");
+// Learned model on the quad kernel (k_rollout_mlp_q4s), CEM and PI2: from the second control step on k_dist_init (4.3 us, a
+// launch of its own in front of a 360 us control step) has nothing left to do when the distribution the first rollout
+// samples from is a constant of the handle -- the rollout samples from the constants directly and reads the state from the
+// pinned buffer itself (its workgroup 0 stores it for the later launches).  What else must hold is the optimizer's own.
+bool Engine::dist_init_skippable() const {
+    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() &&
+           iters >= 1 && pi2_copy_seen && stage_state_src != nullptr;
+}
+
+// The first rollout of a learned-model CEM / PI2 control step; returns whether the kernel took the request to store the
+// state.  pinned_state != null: k_dist_init was skipped, so this one launch samples from (mean, sigma; sigma == null: the
+// handle's) and reads the state from the pinned buffer.  Otherwise the request only asks whether the kernel would take it.
+bool Engine::first_rollout_mlp(bool pen, RolloutArgs& ra, const float* mean, const float* sigma, const float* pinned_state) {
+    const float *mean_it = ra.mean, *sigma_it = ra.sigma, *state_it = ra.state;
+    if (pinned_state) {
+        ra.mean = mean; ra.state = pinned_state;
+        if (sigma) ra.sigma = sigma;
     }
-    finalize(d_state_in, add_noise, d_record_out, d_next_out, step);
+    mlp_state_copy = d_state.p;
+    launch_rollout(SRC_TRUNC, pen, ra);
+    const bool took = mlp_state_copy == nullptr;
+    mlp_state_copy = nullptr;
+    pi2_copy_seen = took;
+    if (pinned_state) {
+        if (!took)                                       // a shape the quad kernel refused after all: nobody stored the state
+            HIP_CHECK(hipMemcpyAsync(d_state.p, pinned_state, (size_t)A * S * 4, hipMemcpyDefault, stream));
+        ra.mean = mean_it; ra.sigma = sigma_it; ra.state = state_it;
+    }
+    return took;
+}
+
+// RandomSearchOptimizer._optimize  random_search.py:38-48
+void Engine::optimize_random_search(RolloutArgs& ra) {
+    const RefitArgs rf = refit_args();
+    ra.stream = BBMPC_NOISE_UNIFORM; ra.iter = 0;
+    ra.inj = injected(BBMPC_NOISE_UNIFORM);
+    if (pop_sharded()) {
+        // population sharded over ranks: local first maximum, one exchange, first maximum by global index
+        const size_t pw = (size_t)A * (U + 2);
+        shard_buffers(pw);
+        play_shards(pw, ra.pop_offset, [&](int pop_offset, float* part) {
+            launch_rollout(SRC_UNIFORM, false, ra);
+            hipLaunchKernelGGL(k_refit_argmax, dim3(A), dim3(REFIT_THREADS), 0, stream, rf, part, pop_offset);
+        });
+        gather_shards(pw, "ncclAllGather (RandomSearch local bests)");
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_argmax_merge, dim3(A), dim3(64), 0, stream, rf, ps_all.p, shard_count());
+        HIP_CHECK(hipGetLastError());
+        capture_trace(0);
+        return;
+    }
+    launch_rollout(SRC_UNIFORM, false, ra);
+    hipLaunchKernelGGL(k_refit_argmax, dim3(A), dim3(REFIT_THREADS), 0, stream, rf, (float*)nullptr, 0);
+    HIP_CHECK(hipGetLastError());
+    capture_trace(0);
+}
+
+// CEMOptimizer._optimize  cem.py:74-136
+void Engine::optimize_cem(RolloutArgs& ra) {
+    const RefitArgs rf = refit_args();
+    const int nelem = A * HU;
+    // The reference's restart from the constructor distribution every control step (no BBMPC_FIX_Q2_CEM_WARM_START):
+    // prev_mean, var0 and the sigma they give are constants, so k_dist_init can be skipped (dist_init_skippable) -- the
+    // first rollout samples from (prev_mean, sigma0), the first refit smooths against (prev_mean, var0)
+    const bool cem_skip = dist_init_skippable() && k <= 64 && !sw.refit_v1 && !fix(BBMPC_FIX_Q2_CEM_WARM_START) && cem_sigma0_ready;
+    const float* cem_pinned = nullptr;
+    last_step_steady = cem_skip;
+    if (cem_skip) {
+        cem_pinned = stage_state_src;
+    } else {
+        hipLaunchKernelGGL(k_dist_init, dim3((nelem + 255) / 256), dim3(256), 0, stream, A, HU, U, d_lo.p, d_hi.p,
+                           d_prev_mean.p, d_var0.p, d_mean.p, d_var.p, d_sigma.p, 1, stage_state_src, d_state.p, A * S);
+        if (!cem_sigma0_ready && !fix(BBMPC_FIX_Q2_CEM_WARM_START)) {
+            if (!step_capturing) invalidate_step_graph();   // (a replayed control step samples from d_sigma0: never capture across its allocation)
+            d_sigma0.alloc(nelem);
+            HIP_CHECK(hipMemcpyAsync(d_sigma0.p, d_sigma.p, (size_t)nelem * 4, hipMemcpyDeviceToDevice, stream));
+            cem_sigma0_ready = true;
+        }
+    }
+    stage_state_src = nullptr;
+    // iters == 0: action = mean[:,0] of the untouched distribution (otherwise the last refit writes it)
+    if (iters == 0)
+        HIP_CHECK(hipMemcpy2DAsync(d_action.p, U * 4, d_prev_mean.p, HU * 4, U * 4, A, hipMemcpyDeviceToDevice, stream));
+    const float* inj_t = injected(BBMPC_NOISE_TRUNC_NORMAL);
+    const size_t inj_stride = (size_t)A * HU * Nst;
+    // LDS budget for the refit: rewards + elite idx + elite tile
+    const int kpad = (k + 3) & ~3;
+    const int fixed = Nst + kpad + TOPK_HIST_WORDS + 2 * kpad;
+    const int budget = fixed * 4 > 48 * 1024 ? 158 * 1024 / 4 : 62 * 1024 / 4;     // floats; big populations take the whole LDS
+    int JC = (int)((size_t)std::max(budget - fixed, k) / (size_t)k);
+    JC = std::max(1, std::min(JC, HU));
+    const size_t lds = (size_t)(fixed + (size_t)k * JC) * 4;
+    want_lds((const void*)k_refit_cem_v2, (size_t)fixed * 4);
+    want_lds((const void*)k_refit_cem, lds);
+    for (int it = 0; it < iters; ++it) {
+        ra.stream = BBMPC_NOISE_TRUNC_NORMAL; ra.iter = (uint32_t)it;
+        ra.inj = inj_t ? inj_t + inj_stride * it : nullptr;
+        if (pop_sharded()) {
+            // population sharded over ranks: local top-k + rows, one exchange, global top-k + refit
+            const int G = shard_count();
+            const size_t pw = (size_t)A * k * (HU + 2);
+            shard_buffers(pw);
+            const size_t tl = (size_t)fixed * 4;
+            want_lds((const void*)k_cem_local_topk, tl);
+            const int psg = sw.refit_wgs > 0 ? sw.refit_wgs : std::max(1, std::min(8, HU / 16));   // workgroups per agent (kernels_tail.hpp)
+            RefitArgs rfs = rf;
+            if (!trace_on) rfs.elites = nullptr;
+            play_shards(pw, ra.pop_offset, [&](int pop_offset, float* part) {
+                launch_rollout(SRC_TRUNC, false, ra);
+                hipLaunchKernelGGL(k_cem_local_topk, dim3(psg, A), dim3(1024), tl, stream, rf, pop_offset, part);
+            });
+            gather_shards(pw, "ncclAllGather (CEM local elites)");
+            HIP_CHECK(hipGetLastError());
+            const size_t ml = ((size_t)2 * G * k + k) * 4;
+            want_lds((const void*)k_cem_merge, ml);
+            hipLaunchKernelGGL(k_cem_merge, dim3(psg, A), dim3(256), ml, stream, rfs, ps_all.p, G);
+            HIP_CHECK(hipGetLastError());
+            capture_trace(it);
+            continue;
+        }
+        bool first_from_constants = false;
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path()) {
+            first_rollout_mlp(false, ra, d_prev_mean.p, d_sigma0.p, cem_pinned);
+            first_from_constants = cem_skip;
+        } else {
+            launch_rollout(SRC_TRUNC, false, ra);
+        }
+        if (k <= 64 && !sw.refit_v1) {
+            const int rthreads = N > 512 ? 1024 : (N > 256 ? 512 : 256);
+            RefitArgs rf2 = rf;
+            if (!trace_on) rf2.elites = nullptr;          // the sorted elite list is only needed by the parity trace
+            if (first_from_constants) { rf2.mean_in = d_prev_mean.p; rf2.var_in = d_var0.p; }
+            // G workgroups per agent share the elite gather (kernels_refit.hpp); at least 16 rows each
+            const int rg = sw.refit_wgs > 0 ? sw.refit_wgs : std::max(1, std::min(8, HU / 16));
+            hipLaunchKernelGGL(k_refit_cem_v2, dim3(rg, A), dim3(rthreads), (size_t)fixed * 4, stream, rf2);
+        } else {
+            hipLaunchKernelGGL(k_refit_cem, dim3(A), dim3(REFIT_THREADS), lds, stream, rf, JC);
+        }
+        HIP_CHECK(hipGetLastError());
+        capture_trace(it);
+    }
+    if (fix(BBMPC_FIX_Q2_CEM_WARM_START)) {
+        if (cfg.dynamics == BBMPC_DYN_MLP || user_path()) pending_warm = 2;      // prev = mean, in k_tail_mlp
+        else HIP_CHECK(hipMemcpyAsync(d_prev_mean.p, d_mean.p, (size_t)nelem * 4, hipMemcpyDeviceToDevice, stream));
+    }
+}
+
+// PI2Optimizer._optimize  pi2.py:58-96
+void Engine::optimize_pi2(RolloutArgs& ra) {
+    const RefitArgs rf = refit_args();
+    const int nelem = A * HU;
+    // PI2 never changes sigma, the first rollout samples around prev_mean directly and the refit writes every element of
+    // the mean: k_dist_init can be skipped (dist_init_skippable) once it has run
+    const bool skip_init = dist_init_skippable() && pi2_dist_ready;
+    const float* pinned_state = nullptr;
+    last_step_steady = skip_init;
+    if (skip_init) {
+        pinned_state = stage_state_src;
+    } else {
+        hipLaunchKernelGGL(k_dist_init, dim3((nelem + 255) / 256), dim3(256), 0, stream, A, HU, U, d_lo.p, d_hi.p,
+                           d_prev_mean.p, d_var0.p, d_mean.p, d_var.p, d_sigma.p, 0, stage_state_src, d_state.p, A * S);
+        pi2_dist_ready = true;
+    }
+    stage_state_src = nullptr;
+    if (iters == 0)              // otherwise the last refit writes the action
+        HIP_CHECK(hipMemcpy2DAsync(d_action.p, U * 4, d_prev_mean.p, HU * 4, U * 4, A, hipMemcpyDeviceToDevice, stream));
+    const float* inj_t = injected(BBMPC_NOISE_TRUNC_NORMAL);
+    const size_t inj_stride = (size_t)A * HU * Nst;
+    const size_t lds = (size_t)(Nst + 64) * 4;
+    want_lds((const void*)k_refit_pi2_mw, lds);
+    want_lds((const void*)k_refit_pi2, lds);
+    want_lds((const void*)k_refit_pi2_partial, lds);
+    for (int it = 0; it < iters; ++it) {
+        ra.stream = BBMPC_NOISE_TRUNC_NORMAL; ra.iter = (uint32_t)it;
+        ra.inj = inj_t ? inj_t + inj_stride * it : nullptr;
+        if (pop_sharded()) {
+            // population sharded over ranks: partial sums here, one exchange, merge in rank order
+            const size_t pw = (size_t)A * (HU + 2);
+            shard_buffers(pw);
+            dim3 pgrid((HU + PI2_ROWS - 1) / PI2_ROWS, A), pblock(64 * PI2_ROWS);
+            play_shards(pw, ra.pop_offset, [&](int, float* part) {
+                launch_rollout(SRC_TRUNC, true, ra);
+                hipLaunchKernelGGL(k_refit_pi2_partial, pgrid, pblock, lds, stream, rf, part);
+            });
+            gather_shards(pw, "ncclAllGather (PI2 partials)");
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_refit_pi2_merge, dim3((HU + 255) / 256, A), dim3(256), 0, stream, rf, ps_all.p, shard_count());
+            HIP_CHECK(hipGetLastError());
+            capture_trace(it);
+            continue;
+        }
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path()) first_rollout_mlp(true, ra, d_prev_mean.p, nullptr, pinned_state);
+        else launch_rollout(SRC_TRUNC, true, ra);
+        if (sw.refit_v1) hipLaunchKernelGGL(k_refit_pi2, dim3(A), dim3(REFIT_THREADS), lds, stream, rf);
+        else hipLaunchKernelGGL(k_refit_pi2_mw, dim3((HU + PI2_ROWS - 1) / PI2_ROWS, A), dim3(64 * PI2_ROWS), lds, stream, rf);
+        HIP_CHECK(hipGetLastError());
+        capture_trace(it);
+    }
+    if (cfg.dynamics == BBMPC_DYN_MLP || user_path()) {
+        pending_warm = 1;                      // prev = shift_left(mean) (pi2.py:92-93) happens in k_tail_mlp
+    } else {
+        hipLaunchKernelGGL(k_shift_left, dim3((nelem + 255) / 256), dim3(256), 0, stream, A, H, U, d_mean.p, d_prev_mean.p);
+        HIP_CHECK(hipGetLastError());
+    }
 }
 
 
@@ -1077,8 +1052,9 @@ void Engine::optimize_spsa(RolloutArgs& ra, uint32_t step) {
         OptArgs oa = opt_args(step, (uint32_t)it);
         if (particles_on()) ra.iter = (uint32_t)it;       // the process noise is drawn per iteration
         want_lds((const void*)k_refit_spsa, (size_t)Nst * 4);
-        // candidates -> the two rollouts -> row sums of this handle's perturbation pairs (part != null: sharded population)
-        auto shard_pass = [&](float* part) {
+        // candidates -> the two rollouts -> row sums of this handle's perturbation pairs (part != null: sharded population;
+        // the population offset is oa's)
+        auto shard_pass = [&](int, float* part) {
             hipLaunchKernelGGL(k_spsa_candidates, dim3((N + 255) / 256, HU, A), dim3(256), 0, stream, oa, d_mean.p, ck,
                                inj_r ? inj_r + inj_stride * it : nullptr, d_samples.p, d_cand_a.p, d_cand_b.p);
             HIP_CHECK(hipGetLastError());
@@ -1095,32 +1071,16 @@ void Engine::optimize_spsa(RolloutArgs& ra, uint32_t step) {
         };
         if (pop_sharded()) {
             // population sharded over ranks: row sums here, one exchange, the step in rank order (kernels_opt.hpp)
-            const int G = ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1);
+            const int G = shard_count();
             const size_t pw = (size_t)A * HU;
-            if (!ps_part.p || ps_part.n < pw) ps_part.alloc(pw);
-            if (ps_all.n < pw * G) ps_all.alloc(pw * G);
-            if (ps_loopback > 1) {
-                // one handle plays every shard in turn (test / measurement hook): shard r = particles [r*N, (r+1)*N)
-                for (int r = 0; r < G; ++r) {
-                    oa.pop_offset = r * N;
-                    shard_pass(ps_all.p + pw * r);
-                }
-                oa.pop_offset = cfg.population_offset;
-            } else {
-                shard_pass(ps_part.p);
-                if (rc.comm) {
-                    const Rccl& r = *rc.api;
-                    r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), "ncclAllGather (SPSA row sums)");
-                } else {
-                    REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
-                    HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
-                }
-            }
+            shard_buffers(pw);
+            play_shards(pw, oa.pop_offset, shard_pass);
+            gather_shards(pw, "ncclAllGather (SPSA row sums)");
             const int n_global = ps_loopback > 1 ? G * N : std::max(N, (int)cfg.population_global);
             hipLaunchKernelGGL(k_spsa_merge, dim3((HU + 255) / 256, A), dim3(256), 0, stream, oa, ps_all.p, G, n_global, ak, d_mean.p, d_action.p);
             HIP_CHECK(hipGetLastError());
         } else {
-            shard_pass(nullptr);
+            shard_pass(oa.pop_offset, nullptr);
         }
         if (trace_on) {
             capture_trace(it);
@@ -1145,13 +1105,10 @@ void Engine::optimize_pso(RolloutArgs& ra, uint32_t step) {
     // population sharded over ranks: every rank moves ITS particles; the one cross-particle operation, the
     // argmax of the personal bests (pso.py:94), becomes local best -> all-gather -> first maximum by global index
     const bool sharded = pop_sharded();
-    const int G = !sharded ? 1 : (ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1));
+    const int G = sharded ? shard_count() : 1;
     const int shards_here = ps_loopback > 1 ? ps_loopback : 1;         // the loopback hook plays every shard in turn
     const size_t pw = (size_t)A * (HU + 2);
-    if (sharded) {
-        if (!ps_part.p || ps_part.n < pw) ps_part.alloc(pw);
-        if (ps_all.n < pw * G) ps_all.alloc(pw * G);
-    }
+    if (sharded) shard_buffers(pw);
     for (int it = 0; it < iters; ++it) {
         OptArgs oa = opt_args(step, (uint32_t)it);
         if (particles_on()) ra.iter = (uint32_t)it;       // the process noise is drawn per iteration
@@ -1165,15 +1122,7 @@ void Engine::optimize_pso(RolloutArgs& ra, uint32_t step) {
             HIP_CHECK(hipGetLastError());
         }
         if (sharded) {
-            if (ps_loopback <= 1) {
-                if (rc.comm) {
-                    const Rccl& r = *rc.api;
-                    r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), "ncclAllGather (PSO local bests)");
-                } else {
-                    REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
-                    HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
-                }
-            }
+            gather_shards(pw, "ncclAllGather (PSO local bests)");
             hipLaunchKernelGGL(k_pso_merge, dim3(A), dim3(256), 0, stream, oa, ps, ps_all.p, G);
             HIP_CHECK(hipGetLastError());
         }

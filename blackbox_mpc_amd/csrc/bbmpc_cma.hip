@@ -185,8 +185,9 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
         // selection + path update of an unsharded population share a launch (both one workgroup per instance)
         const bool merge_sp = !pop_sharded() && n > 128;
         if (merge_sp) want_lds((const void*)k_cma_select_paths, lds, 4096 + 512 + 4 * 512 * 4 + 2 * 4096 + 256);
-        // sample -> roll out -> sorted top-k of this handle's particles (part != null: sharded population)
-        auto shard_pass = [&](float* part) {
+        // sample -> roll out -> sorted top-k of this handle's particles (part != null: sharded population; the population
+        // offset is q's)
+        auto shard_pass = [&](int, float* part) {
             hipLaunchKernelGGL(k_cma_noise, dim3((N + 255) / 256, HU, A), dim3(256), 0, stream, q);
             if (mfma_y) hipLaunchKernelGGL(k_cma_gemm_y_mfma, dim3((N + 63) / 64, (n + 63) / 64, G), dim3(256), 0, stream, q);
             else hipLaunchKernelGGL(k_cma_gemm_y, dim3((N + 63) / 64, (n + 63) / 64, G), dim3(256), 0, stream, q);
@@ -204,31 +205,15 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
             // population sharded over ranks: every rank samples and rolls out ITS particles, the sorted local
             // elites (reward, global index, candidate) are exchanged and merged (kernels_cma.hpp); the path / covariance
             // update and the eigen-decomposition run replicated on every rank
-            const int R = ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1);
             const size_t pw = (size_t)G * k * (n + 2);
-            if (!ps_part.p || ps_part.n < pw) ps_part.alloc(pw);
-            if (ps_all.n < pw * R) ps_all.alloc(pw * R);
-            if (ps_loopback > 1) {
-                for (int r = 0; r < R; ++r) {
-                    q.pop_offset = r * N;
-                    shard_pass(ps_all.p + pw * r);
-                }
-                q.pop_offset = cfg.population_offset;
-            } else {
-                shard_pass(ps_part.p);
-                if (rc.comm) {
-                    const Rccl& r = *rc.api;
-                    r.check(r.AllGather(ps_part.p, ps_all.p, pw, Rccl::kFloat32, rc.comm, stream), "ncclAllGather (CMA-ES local elites)");
-                } else {
-                    REQUIRE(cfg.population_global <= N, BBMPC_E_STATE, "population sharding needs a communicator: call bbmpc_comm_init first");
-                    HIP_CHECK(hipMemcpyAsync(ps_all.p, ps_part.p, pw * 4, hipMemcpyDeviceToDevice, stream));
-                }
-            }
+            shard_buffers(pw);
+            play_shards(pw, q.pop_offset, shard_pass);
+            gather_shards(pw, "ncclAllGather (CMA-ES local elites)");
             if (trace_on && !c_eidx_glob.p) c_eidx_glob.alloc((size_t)G * k);
-            hipLaunchKernelGGL(k_cma_merge, dim3(G), dim3(1024), 0, stream, q, ps_all.p, R, trace_on ? c_eidx_glob.p : (int*)nullptr);
+            hipLaunchKernelGGL(k_cma_merge, dim3(G), dim3(1024), 0, stream, q, ps_all.p, shard_count(), trace_on ? c_eidx_glob.p : (int*)nullptr);
             HIP_CHECK(hipGetLastError());
         } else {
-            shard_pass(nullptr);
+            shard_pass(q.pop_offset, nullptr);
         }
         if (merge_sp) hipLaunchKernelGGL(k_cma_select_paths, dim3(G), dim3(1024), lds, stream, q);
         else hipLaunchKernelGGL(k_cma_paths, dim3(G), dim3(n > 128 ? 1024 : REFIT_THREADS), 0, stream, q);

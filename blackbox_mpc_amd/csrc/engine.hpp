@@ -359,6 +359,30 @@ struct Engine {
     bool pop_sharded() const { return cfg.population_global > N || ps_loopback > 1 || ps_force; }
     // ... and over RANKS (the per-iteration exchange goes through the communicator): not the one-GPU splits
     bool pop_sharded_across_ranks() const { return ps_force || (ps_loopback <= 1 && cfg.population_global > N); }
+    // The per-iteration exchange of a sharded population, the same for every optimizer: each shard's pass leaves a payload
+    // of pw floats, all payloads meet in ps_all in shard order, the optimizer's own merge kernel reads them there.
+    int shard_count() const { return ps_loopback > 1 ? ps_loopback : std::max(1, rc.comm ? rc.nranks : 1); }
+    void shard_buffers(size_t pw) {
+        if (!ps_part.p || ps_part.n < pw) ps_part.alloc(pw);
+        if (ps_all.n < pw * shard_count()) ps_all.alloc(pw * shard_count());
+    }
+    // pass(population offset, destination) runs this handle's share: once into ps_part, or -- the loopback hook, a test /
+    // measurement aid and the way one GPU plays a population too large for one shard -- every shard in turn, shard r =
+    // particles [r*N, (r+1)*N), straight into its slot of ps_all.  pop_offset is the field of the caller's launch arguments
+    // that the draws are keyed by: it follows the shard being played and is cfg.population_offset again afterwards.
+    template <class Offset, class Pass>
+    void play_shards(size_t pw, Offset& pop_offset, Pass&& pass) {
+        if (ps_loopback > 1) {
+            for (int r = 0; r < ps_loopback; ++r) {
+                pop_offset = r * N;
+                pass(r * N, ps_all.p + pw * r);
+            }
+            pop_offset = cfg.population_offset;
+        } else {
+            pass((int)cfg.population_offset, ps_part.p);
+        }
+    }
+    void gather_shards(size_t pw, const char* what);     // ps_part of every rank -> ps_all (nothing to do under the loopback hook)
     // CMA-ES at n <= 32 on the analytic pendulum: the last iteration's update launch is held back until finalize() knows the
     // record's arguments and then carries the tail of the control step as well (kernels_eigh_small.hpp)
     struct PendingCmaUpdate { bool set = false; CmaArgs q; size_t lds = 0; int yef = 0; } pending_cma_update;
@@ -384,6 +408,14 @@ struct Engine {
     bool use_fused() const;
     void optimize_fused(const float* d_state_in, int add_noise, float* d_record_out, float* d_next_out, uint32_t step);
     void ensure_trace();
+    RefitArgs refit_args() const;
+    // CEM / PI2 on the learned model: what both ask before a control step opens without k_dist_init, and the first rollout
+    // of a control step (bbmpc.hip)
+    bool dist_init_skippable() const;
+    bool first_rollout_mlp(bool pen, RolloutArgs& ra, const float* mean, const float* sigma, const float* pinned_state);
+    void optimize_random_search(RolloutArgs& ra);
+    void optimize_cem(RolloutArgs& ra);
+    void optimize_pi2(RolloutArgs& ra);
     void optimize_spsa(RolloutArgs& ra, uint32_t step);
     void optimize_pso(RolloutArgs& ra, uint32_t step);
     void optimize_cma(RolloutArgs& ra, uint32_t step);

@@ -384,6 +384,73 @@ def test_spsa_exchange_through_a_one_rank_rccl_communicator(L, monkeypatch):
     one.comm_destroy()
 
 
+@pytest.mark.parametrize("opt_name", ["CEM", "PI2", "SPSA", "PSO"])
+def test_forced_exchange_without_a_communicator_is_a_local_copy(L, monkeypatch, opt_name):
+    # BBMPC_POPSHARD_FORCE and no communicator: the partials / local elites / local bests of the one shard are copied into
+    # the gathered buffer and merged -- the unsharded engine's control steps (PSO bit for bit, the others up to the order
+    # of the fp32 sums).  BBMPC_FUSED=0: the fused PI2 refit sums in another order again.
+    from blackbox_mpc_amd.engine import Engine
+    monkeypatch.setenv("BBMPC_FUSED", "0")
+    N, A, H, iters = 128, 2, 8, 3
+    opt, kw = {"CEM": (L.OPT_CEM, dict(num_elite=8)), "PI2": (L.OPT_PI2, dict(lamda=1.0)), "SPSA": (L.OPT_SPSA, {}),
+               "PSO": (L.OPT_PSO, {})}[opt_name]
+    mk = lambda **more: Engine(opt, L.DYN_PENDULUM, L.REW_PENDULUM, [-2.0], [2.0], dim_s=3, num_agents=A, planning_horizon=H,
+                               population_size=N, max_iterations=iters, seed=19, **kw, **more)
+    full = mk()
+    monkeypatch.setenv("BBMPC_POPSHARD_FORCE", "1")
+    one = mk(population_global=N)
+    monkeypatch.delenv("BBMPC_POPSHARD_FORCE")
+    s = O.pendulum_start_states(A)
+    for t in range(3):
+        a_f, n_f, r_f = full.optimize(s, t)
+        a_o, n_o, r_o = one.optimize(s, t)
+        if opt_name == "PSO":
+            np.testing.assert_array_equal(a_o, a_f)
+            np.testing.assert_array_equal(n_o, n_f)
+            np.testing.assert_array_equal(r_o, r_f)
+        elif opt_name == "CEM":
+            np.testing.assert_allclose(one.get_state("mean"), full.get_state("mean"), rtol=0, atol=2e-5)
+            np.testing.assert_allclose(one.get_state("var"), full.get_state("var"), rtol=1e-4, atol=2e-6)
+            np.testing.assert_allclose(a_o, a_f, rtol=0, atol=2e-5)
+        else:
+            np.testing.assert_allclose(a_o, a_f, rtol=0, atol=2e-5)
+            np.testing.assert_allclose(n_o, n_f, rtol=0, atol=2e-5)
+            np.testing.assert_allclose(one.get_state("prev_mean"), full.get_state("prev_mean"), rtol=0, atol=2e-5)
+        s = n_f
+
+
+def test_cem_exchange_through_a_one_rank_rccl_communicator(L, monkeypatch):
+    # CEM's sharded code path as a rank runs it -- local top-k + rows, ncclAllGather on the launch stream, global top-k +
+    # refit -- with one rank, on the learned model
+    from blackbox_mpc_amd.engine import Engine
+    S, U, N, H, iters, k = 20, 6, 512, 10, 3, 16
+    ws, bs = O.make_mlp_params([26, 200, 200, 20], seed=42)
+    stats = [np.zeros(S, F), np.ones(S, F), np.zeros(U, F), np.ones(U, F), np.zeros(S, F), np.full(S, 0.1, F)]
+
+    def mk(**kw):
+        e = Engine(L.OPT_CEM, L.DYN_MLP, L.REW_CHEETAH, [-1.0] * U, [1.0] * U, dim_s=S, num_agents=1, planning_horizon=H,
+                   population_size=N, max_iterations=iters, num_elite=k, seed=3, **kw)
+        e.set_mlp(ws, bs, [1, 1, 0], stats)
+        return e
+    full = mk()
+    monkeypatch.setenv("BBMPC_POPSHARD_FORCE", "1")
+    one = mk(population_global=N)
+    monkeypatch.delenv("BBMPC_POPSHARD_FORCE")
+    one.comm_init(Engine.comm_unique_id(), 1, 0)
+    assert one.comm_info()[0] == 1
+    s = O.cheetah_start_states(1, S)
+    for t in range(2):
+        a_f, n_f, _ = full.optimize(s, t)
+        a_o, n_o, _ = one.optimize(s, t)
+        np.testing.assert_allclose(one.get_state("mean"), full.get_state("mean"), rtol=0, atol=2e-5)
+        np.testing.assert_allclose(one.get_state("var"), full.get_state("var"), rtol=1e-4, atol=2e-6)
+        np.testing.assert_allclose(a_o, a_f, rtol=0, atol=2e-5)
+        np.testing.assert_allclose(n_o, n_f, rtol=0, atol=2e-4)
+        s = n_f
+    one.synchronize()
+    one.comm_destroy()
+
+
 def test_population_above_32768_is_played_as_shards_on_one_gpu(L):
     # The refit kernels keep an agent's rewards in one CU's LDS (32768 floats); a larger population runs as equal shards of
     # the same machinery on the one GPU (draws keyed by the global particle).  PI2 at N = 40000 and CEM at N = 65536 (two
