@@ -90,6 +90,7 @@ SYMBOLS = [
     "bbmpc_predict_trajectory_particles", "bbmpc_predict_trajectory_particles_dev",
     "bbmpc_set_particle_risk", "bbmpc_predict_trajectory_quantiles", "bbmpc_predict_trajectory_quantiles_dev",
     "bbmpc_set_sampling_correlation", "bbmpc_get_sampling_correlation",
+    "bbmpc_set_elite_carry", "bbmpc_get_elite_carry",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -186,6 +187,8 @@ def _load():
     lib.bbmpc_predict_trajectory_quantiles_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.bbmpc_set_sampling_correlation.argtypes = [vp, vp, i64]
     lib.bbmpc_get_sampling_correlation.argtypes = [vp, ctypes.POINTER(i32)]
+    lib.bbmpc_set_elite_carry.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    lib.bbmpc_get_elite_carry.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     return lib

@@ -3,6 +3,7 @@
 #include "abi_util.hpp"
 #include "engine_util.hpp"
 #include "kernels_corr.hpp"
+#include "kernels_elite_carry.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -435,6 +436,7 @@ PsoState Engine::pso_state(int shard) {
 
 
 void Engine::reset() {
+    carry_stored = 0;                              // bbmpc_set_elite_carry: the stored elites go, the setting stays
     // CEM/PI2/SPSA reset(): previous solution <- bounds midpoint (cem.py:138-149, pi2.py:98-105)
     if (cfg.optimizer == BBMPC_OPT_NONE || cfg.optimizer == BBMPC_OPT_RANDOM_SEARCH) return;
     cem_sigma0_ready = false;                      // (prev_mean is rewritten below)
@@ -591,6 +593,47 @@ void Engine::draw_candidates_corr(RolloutArgs& ra) {
     HIP_CHECK(hipGetLastError());
 }
 
+// bbmpc_set_elite_carry.  Everything that can be refused is refused before the handle changes; an
+// accepted call drops the stored elites, so the next control step injects nothing into its first iteration.
+void Engine::set_elite_carry(int keep, int shift) {
+    if (keep == 0 && shift == 0) {
+        if (carry_on()) invalidate_step_graph();
+        carry_keep = carry_shift = carry_stored = 0;
+        return;
+    }
+    REQUIRE(cfg.optimizer == BBMPC_OPT_CEM, BBMPC_E_UNSUPPORTED,
+            "elite carry with an optimizer other than CEM: only CEM selects elites that the next iteration could take up again");
+    REQUIRE(!pop_sharded() && cfg.population_global <= N && auto_split <= 1, BBMPC_E_UNSUPPORTED,
+            "elite carry with a sharded population: the sharded control steps draw inside their rollout kernels");
+    REQUIRE(keep >= 0 && shift >= 0, BBMPC_E_INVALID, "elite carry: keep and shift must not be negative");
+    REQUIRE(keep <= k && shift <= k, BBMPC_E_INVALID,
+            "elite carry: keep and shift must not exceed num_elite = " + std::to_string(k));
+    REQUIRE(keep < N && shift < N, BBMPC_E_INVALID,
+            "elite carry: keep and shift must be below population_size = " + std::to_string(N));
+    invalidate_step_graph();
+    const size_t need = (size_t)A * HU * std::max(keep, shift);
+    if (d_carry.n != need) {
+        HIP_CHECK(hipStreamSynchronize(stream));   // (nothing may still read the buffer that is replaced)
+        carry_keep = carry_shift = carry_stored = 0;   // (a failed allocation must not leave a setting without its buffer)
+        d_carry.alloc(need);
+    }
+    carry_keep = keep; carry_shift = shift; carry_stored = 0;
+}
+
+// The first `count` sorted elites of the refit that has just run, out of the sample buffer into the carry buffer
+// (kernels_elite_carry.hpp); shift: moved one planning step forward, the last step repeated.
+void Engine::save_elites(int count, bool shift) {
+    if (count <= 0) return;
+    dim3 grid((HU * count + CARRY_THREADS - 1) / CARRY_THREADS, A), block(CARRY_THREADS);
+    if (shift)
+        hipLaunchKernelGGL(k_elite_save<true>, grid, block, 0, stream, HU, U, Nst, N, k, carry_stride(), count, (const int*)d_elites.p,
+                           (const float*)d_samples.p, d_carry.p);
+    else
+        hipLaunchKernelGGL(k_elite_save<false>, grid, block, 0, stream, HU, U, Nst, N, k, carry_stride(), count, (const int*)d_elites.p,
+                           (const float*)d_samples.p, d_carry.p);
+    HIP_CHECK(hipGetLastError());
+}
+
 // [batch, U] actions in a dense block: the caller's own when they are, else gathered from rows astride apart
 const float* Engine::dense_actions(const float* d_actions, int astride, int batch) {
     if (astride == U) return d_actions;
@@ -600,8 +643,17 @@ const float* Engine::dense_actions(const float* d_actions, int astride, int batc
 }
 
 void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
-    if (corr_on() && mode == SRC_TRUNC) {                 // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
-        draw_candidates_corr(ra);
+    // bbmpc_set_elite_carry (CEM): the candidates go to the sample buffer, the stored elites over its last columns
+    const bool carry = carry_on() && cfg.optimizer == BBMPC_OPT_CEM && mode == SRC_TRUNC;
+    if ((corr_on() || carry) && mode == SRC_TRUNC) {      // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
+        if (corr_on()) draw_candidates_corr(ra);
+        else draw_candidates(SRC_TRUNC, ra);
+        if (carry && carry_inject > 0) {
+            REQUIRE(ra.n_pop == N && ra.HU == HU && ra.Nst == Nst && carry_inject < N && d_carry.p, BBMPC_E_INVALID, "internal: elite carry shape");
+            hipLaunchKernelGGL(k_elite_inject, dim3((HU * carry_inject + CARRY_THREADS - 1) / CARRY_THREADS, A), dim3(CARRY_THREADS), 0, stream, HU, Nst,
+                               N, carry_stride(), carry_inject, (const float*)d_carry.p, ra.samples);
+            HIP_CHECK(hipGetLastError());
+        }
         mode = SRC_BUF;
         ra.cand = ra.samples;
     }
@@ -834,7 +886,7 @@ RefitArgs Engine::refit_args() const {
 // samples from is a constant of the handle -- the rollout samples from the constants directly and reads the state from the
 // pinned buffer itself (its workgroup 0 stores it for the later launches).  What else must hold is the optimizer's own.
 bool Engine::dist_init_skippable() const {
-    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() &&
+    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() &&
            iters >= 1 && pi2_copy_seen && stage_state_src != nullptr;
 }
 
@@ -923,8 +975,13 @@ void Engine::optimize_cem(RolloutArgs& ra) {
     const size_t lds = (size_t)(fixed + (size_t)k * JC) * 4;
     want_lds((const void*)k_refit_cem_v2, (size_t)fixed * 4);
     want_lds((const void*)k_refit_cem, lds);
+    // bbmpc_set_elite_carry: what the previous control step left goes into iteration 0 and is then used up
+    const bool carry = carry_on() && !pop_sharded();
+    const int carry_first = carry ? carry_stored : 0;
+    if (carry) carry_stored = 0;
     for (int it = 0; it < iters; ++it) {
         ra.stream = BBMPC_NOISE_TRUNC_NORMAL; ra.iter = (uint32_t)it;
+        carry_inject = !carry ? 0 : (it == 0 ? carry_first : carry_keep);
         ra.inj = inj_t ? inj_t + inj_stride * it : nullptr;
         if (pop_sharded()) {
             // population sharded over ranks: local top-k + rows, one exchange, global top-k + refit
@@ -959,7 +1016,7 @@ void Engine::optimize_cem(RolloutArgs& ra) {
         if (k <= 64 && !sw.refit_v1) {
             const int rthreads = N > 512 ? 1024 : (N > 256 ? 512 : 256);
             RefitArgs rf2 = rf;
-            if (!trace_on) rf2.elites = nullptr;          // the sorted elite list is only needed by the parity trace
+            if (!trace_on && !carry) rf2.elites = nullptr;   // the sorted elite list is only needed by the parity trace and the elite carry
             if (first_from_constants) { rf2.mean_in = d_prev_mean.p; rf2.var_in = d_var0.p; }
             // G workgroups per agent share the elite gather (kernels_refit.hpp); at least 16 rows each
             const int rg = sw.refit_wgs > 0 ? sw.refit_wgs : std::max(1, std::min(8, HU / 16));
@@ -968,8 +1025,13 @@ void Engine::optimize_cem(RolloutArgs& ra) {
             hipLaunchKernelGGL(k_refit_cem, dim3(A), dim3(REFIT_THREADS), lds, stream, rf, JC);
         }
         HIP_CHECK(hipGetLastError());
+        if (carry) {                                      // the elite rows leave the sample buffer before the next draw rewrites it
+            if (it + 1 < iters) save_elites(carry_keep, false);
+            else { save_elites(carry_shift, true); carry_stored = carry_shift; }
+        }
         capture_trace(it);
     }
+    carry_inject = 0;
     if (fix(BBMPC_FIX_Q2_CEM_WARM_START)) {
         if (cfg.dynamics == BBMPC_DYN_MLP || user_path()) pending_warm = 2;      // prev = mean, in k_tail_mlp
         else HIP_CHECK(hipMemcpyAsync(d_prev_mean.p, d_mean.p, (size_t)nelem * 4, hipMemcpyDeviceToDevice, stream));
@@ -1718,7 +1780,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                 // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
                 // replayed as a graph (engine.hpp: step_graph)
                 const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&
-                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && e.stream == e.own_stream && !e.any_injected();
+                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && e.stream == e.own_stream && !e.any_injected();
                 const uint64_t sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
                 bool replayed = false;
                 if (graph_ok && e.step_graph && e.step_graph_sig == sig) {
@@ -1996,6 +2058,25 @@ int bbmpc_get_sampling_correlation(bbmpc_handle h, int32_t* installed) {
     CHECK_HANDLE(h);
     CHECK_PTR(installed);
     *installed = h->e->corr_on() ? 1 : 0;
+    API_END
+}
+
+int bbmpc_set_elite_carry(bbmpc_handle h, int keep, int shift) {
+    API_BEGIN
+    CHECK_HANDLE(h);                     // (settles the handle: a resident control-step kernel is stopped first)
+    h->e->set_elite_carry(keep, shift);
+    API_END
+}
+
+int bbmpc_get_elite_carry(bbmpc_handle h, int* keep, int* shift, int* stored) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(keep);
+    CHECK_PTR(shift);
+    CHECK_PTR(stored);
+    *keep = h->e->carry_keep;
+    *shift = h->e->carry_shift;
+    *stored = h->e->carry_stored;
     API_END
 }
 

@@ -494,6 +494,19 @@ struct Engine {
     bool corr_on() const { return corr_installed; }
     void set_sampling_correlation(const float* mix, int64_t count);
     void draw_candidates_corr(RolloutArgs& ra);
+    // elite carry-over for CEM (bbmpc_set_elite_carry; kernels_elite_carry.hpp): the best carry_keep
+    // elites of an iteration replace the last candidates of the next one, the best carry_shift of a control step's last
+    // iteration, moved one planning step forward, those of the next control step's first iteration.  While it is on,
+    // control steps are routed as with a mixing matrix (one launch sequence per iteration) and launch_rollout draws the
+    // candidates into the sample buffer, overwrites its last columns, then rolls them out in the SRC_BUF form.
+    int carry_keep = 0, carry_shift = 0;
+    int carry_stored = 0;              // shifted elites held for the next control step (0 after reset and after the setter)
+    int carry_inject = 0;              // columns the next CEM draw is followed by (set by optimize_cem around launch_rollout)
+    DevBuf<float> d_carry;             // [A][HU][max(carry_keep, carry_shift)]
+    bool carry_on() const { return carry_keep > 0 || carry_shift > 0; }
+    int carry_stride() const { return std::max(carry_keep, carry_shift); }
+    void set_elite_carry(int keep, int shift);
+    void save_elites(int count, bool shift);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
     DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging

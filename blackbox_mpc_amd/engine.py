@@ -543,6 +543,20 @@ class Engine:
         L.check(L.lib.bbmpc_get_sampling_correlation(self._h, ctypes.byref(v)))
         return bool(v.value)
 
+    def set_elite_carry(self, keep, shift):
+        """Elite carry-over for CEM (bbmpc_set_elite_carry): the best `keep` elites of an iteration replace the last
+        candidates of the next one, the best `shift` elites of a control step's last iteration, moved one planning step
+        forward, those of the next control step's first iteration.  (0, 0) switches it off.  While it is on control steps
+        take the per-iteration launch paths, as with set_trace."""
+        L.check(L.lib.bbmpc_set_elite_carry(self._h, int(keep), int(shift)))
+
+    def elite_carry(self):
+        """(keep, shift, stored): the setting and the number of elites held for the next control step
+        (bbmpc_get_elite_carry)."""
+        v = [ctypes.c_int(0) for _ in range(3)]
+        L.check(L.lib.bbmpc_get_elite_carry(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     def set_keep_plan(self, enabled=True):
         """Opt-in switch of plan readback (bbmpc_set_keep_plan): the control steps that follow keep their solution in HBM
         (the routing of set_trace: same results, slower paths).  Off by default."""

@@ -1,7 +1,17 @@
 """Cross-Entropy Method -- kwargs/defaults of the reference's CEMOptimizer (optimizers/cem.py:7-10)."""
+import numbers
+
 from .. import _lib as L
 from ..utils.colored_noise import resolve_sampling_correlation
 from .optimizer_base import OptimizerBase
+
+
+def _elite_count(name, value, num_elite):
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
+        raise ValueError("%s must be an int, got %r" % (name, value))
+    if value < 0 or value > int(num_elite):
+        raise ValueError("%s must lie in [0, num_elite] = [0, %d], got %d" % (name, int(num_elite), value))
+    return int(value)
 
 
 class CEMOptimizer(OptimizerBase):
@@ -9,10 +19,14 @@ class CEMOptimizer(OptimizerBase):
 
     def __init__(self, env_action_space, env_observation_space, planning_horizon=50, max_iterations=5,
                  population_size=500, num_elite=50, num_agents=5, epsilon=0.001, alpha=0.25, noise_beta=None,
-                 sampling_correlation=None, **engine_args):
+                 sampling_correlation=None, keep_elites=0, shift_elites=0, **engine_args):
         # temporally correlated sampling (no counterpart in the reference): noise_beta = the exponent of iCEM's colored
         # noise, or sampling_correlation = an [H, H] mixing matrix of the caller's (utils/colored_noise.py)
         self._sampling_mix = resolve_sampling_correlation(planning_horizon, noise_beta, sampling_correlation)
+        # elite carry-over, the other half of iCEM (Engine.set_elite_carry): the best keep_elites of an iteration are put
+        # back among the candidates of the next one, the best shift_elites of a control step, moved one planning step
+        # forward, among those of the next control step
+        self._elite_carry = (_elite_count("keep_elites", keep_elites, num_elite), _elite_count("shift_elites", shift_elites, num_elite))
         super().__init__(name=None, planning_horizon=planning_horizon, max_iterations=max_iterations,
                          num_agents=num_agents, env_action_space=env_action_space,
                          env_observation_space=env_observation_space, **engine_args)

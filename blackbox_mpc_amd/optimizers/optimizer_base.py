@@ -140,6 +140,9 @@ class OptimizerBase:
         mix = getattr(self, "_sampling_mix", None)    # CEM / PI2 with noise_beta / sampling_correlation
         if mix is not None:
             self._engine.set_sampling_correlation(mix)
+        carry = getattr(self, "_elite_carry", (0, 0))  # CEM with keep_elites / shift_elites
+        if carry != (0, 0):
+            self._engine.set_elite_carry(*carry)
         if self._engine._param_fns:
             self._require_engine = self._require_engine_and_params
         else:

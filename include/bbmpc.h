@@ -517,6 +517,30 @@ int bbmpc_set_sampling_correlation(bbmpc_handle h, const float* mix, int64_t cou
 /* *installed = 1 while a matrix is installed, else 0. */
 int bbmpc_get_sampling_correlation(bbmpc_handle h, int32_t* installed);
 
+/* Elite carry-over for CEM, the second half of iCEM.  With k = num_elite, N = population_size,
+ * E_i[a] the sorted elite list of iteration i of agent a (best first, ties by lower index) and X_i[n,a,t,u] the candidates
+ * of iteration i as rolled out:
+ *   keep:  for i >= 1 within a control step, after the draw of iteration i,
+ *              X_i[N - keep + e, a] = X_{i-1}[E_{i-1}[a][e], a]                      e = 0 .. keep-1, bit for bit
+ *   shift: with L the last iteration of control step c, after the draw of iteration 0 of control step c + 1,
+ *              X_0[N - shift + e, a, t, :] = X_L[E_L[a][e], a, min(t + 1, H - 1), :]   e = 0 .. shift-1, bit for bit
+ *          (the elite moved one planning step forward, its last action repeated).
+ * The replaced columns are always the last ones; their draws are still made, keyed as always, and then overwritten
+ * (bbmpc_dump_noise returns what it returned before).  Everything behind the candidates is untouched: rollout, top-k over
+ * all N columns (a carried column can be selected again), refit, smoothing, the action; mean and variance across control
+ * steps stay governed by the quirk bits.  The stored elites live in a buffer of the handle's own: bbmpc_evaluate, the
+ * predict calls and bbmpc_set_trace between two control steps do not disturb them; bbmpc_reset and an accepted call of
+ * this setter drop them (the next control step injects nothing into its first iteration); the setting itself survives
+ * bbmpc_reset.  keep = shift = 0 switches it off and restores every path bit for bit.  While it is on, control steps are
+ * routed as bbmpc_set_trace routes them (one launch sequence per iteration: no resident, fused or graph-replayed form).
+ * Like the other setters the call stops a resident control-step kernel first and invalidates the captured step graph.
+ * Refusals, before anything is allocated or launched (the handle, an earlier setting and its stored elites included,
+ * stays as it was): BBMPC_E_UNSUPPORTED: an optimizer other than CEM, a sharded population; BBMPC_E_INVALID: keep or shift
+ * negative, above num_elite, or not below population_size.  No counterpart in the reference. */
+int bbmpc_set_elite_carry(bbmpc_handle h, int keep, int shift);
+/* The setting, and *stored = the number of elites currently held for the next control step. */
+int bbmpc_get_elite_carry(bbmpc_handle h, int* keep, int* shift, int* stored);
+
 /* Closed-loop episode on the device -- counterpart of utils/rollouts.py:60-139 (_sample) with the engine's own
  * model as the environment: T control steps, each feeding its predicted next state back as the next observation;
  * nothing leaves HBM until the end.  records_out is [T][A][U+S+1] (action | next_state | reward) on the host.
