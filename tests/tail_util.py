@@ -5,6 +5,7 @@ The reference takes the device's PRE-noise action as given; the model step is no
 pendulum / MLP step evaluates the device's own noisy action)."""
 import numpy as np
 
+from oracle import oracle_np as O
 from tests import philox_np as P
 
 F = np.float32
@@ -121,3 +122,89 @@ def designed_xi(A, U, seed):
         if i < n:
             xi[(i * 5 + seed) % n if n > 5 and np.gcd(5, n) == 1 else i] = v
     return xi.reshape(A, U).astype(F)
+
+
+# ---- the problems the tail tests and the bounds tests share: states, user functions, learned models --------------
+def pendulum_states(steps, A, seed):
+    rng = np.random.default_rng(seed)
+    th = rng.uniform(-np.pi, np.pi, (steps, A))
+    return np.stack([np.cos(th), np.sin(th), rng.uniform(-6, 6, (steps, A))], -1).astype(F)
+
+
+INTENDED_PENDULUM_REWARD = """
+__device__ float bbmpc_user_reward(const float* cur, const float* act, const float* nxt, int S, int U) {
+    const float PI = 3.14159274101257324f, TWO_PI = 6.28318548202514648f;
+    const float th = atan2f(cur[1], cur[0]);
+    float m = fmodf(th + PI, TWO_PI);
+    if (m < 0.0f) m = m + TWO_PI;
+    const float ang = m - PI;
+    const float first = ang * ang + 0.1f * (cur[2] * cur[2]);
+    float ss = 0.0f;
+    for (int u = 0; u < U; ++u) ss = ss + act[u] * act[u];
+    return (-first) - 0.001f * ss;
+}
+"""
+# a linear model with two inputs: delta[i] = 0.05 * act[i % U] - 0.01 * x[i]
+LINEAR_DYNAMICS = """
+__device__ void bbmpc_user_dynamics(const float* x, float* delta, int S, int U) {
+    for (int i = 0; i < S; ++i) delta[i] = 0.05f * x[S + (i % U)] - 0.01f * x[i];
+}
+"""
+
+
+def linear_dynamics_np(x):
+    x = np.asarray(x, F)
+    S, U = 3, x.shape[1] - 3
+    return np.stack([(F(0.05) * x[:, S + (i % U)]).astype(F) - (F(0.01) * x[:, i]).astype(F) for i in range(S)], 1).astype(F)
+
+
+def intended_reward(cur, act, nxt):
+    return O.pendulum_reward(cur, act, nxt, as_executed=False)
+
+
+ACT = {"tanh": 1, "relu": 2, "sigmoid": 3, None: 0}
+MLP_SHAPES = {
+    "S20-U6-h200": ([26, 200, 200, 20], ["tanh", "tanh", None], 20, 6, "cheetah"),
+    "S3-U2-h16": ([5, 16, 3], ["tanh", None], 3, 2, "pendulum"),
+    # the two corners of what bbmpc_set_mlp accepts (dim_S + dim_U <= 128 and dim_S <= 64).  Widest state: k_tail_mlp's state
+    # threads 64..64+S are all in use.  Widest action: its action threads 64..64+U and tid < U run far past the state range, act[128]
+    # is all but full, and a production draw takes 32 Philox blocks per agent
+    "S64-U64-h96": ([128, 96, 64], ["tanh", None], 64, 64, "cheetah"),
+    "S3-U125-h96": ([128, 96, 3], ["tanh", None], 3, 125, "pendulum"),
+}
+
+
+def mlp_stats(S, U, seed):
+    rng = np.random.default_rng(seed)
+    return [rng.normal(0, 0.2, S).astype(F), rng.uniform(0.5, 1.5, S).astype(F),
+            rng.normal(0, 0.1, U).astype(F), rng.uniform(0.5, 1.5, U).astype(F),
+            rng.normal(0, 0.01, S).astype(F), rng.uniform(0.05, 0.15, S).astype(F)]
+
+
+_NETS = {}
+
+
+def net(shape, normalized):
+    """weights / statistics / oracle evaluator of a shape: made once, shared by the cases, never changed"""
+    key = (shape, normalized)
+    if key not in _NETS:
+        dims, acts, S, U, reward = MLP_SHAPES[shape]
+        ws, bs = O.make_mlp_params(dims, seed=42)
+        rng = np.random.default_rng(43)
+        bs = [rng.normal(0, 0.05, b.shape).astype(F) for b in bs]
+        stats = mlp_stats(S, U, 44) if normalized else None
+        ev = O.Evaluator(reward, O.Handler(O.MLP(ws, bs, acts), False, normalized, stats))
+        _NETS[key] = (ws, bs, stats, ev)
+    return _NETS[key]
+
+
+def mlp_bounds(U):
+    lo, hi = MLP_BOUNDS[U] if U in MLP_BOUNDS else wide_bounds(U)
+    return np.asarray(lo, F), np.asarray(hi, F)
+
+
+def mlp_states(shape, steps, A, seed):
+    S = MLP_SHAPES[shape][2]
+    if S == 3:
+        return pendulum_states(steps, A, seed)
+    return np.random.default_rng(seed).normal(0, 0.3, (steps, A, S)).astype(F)

@@ -17,6 +17,13 @@ import pytest
 
 from oracle import oracle_np as O
 from tests import tail_util as T
+from tests.tail_util import ACT, INTENDED_PENDULUM_REWARD, LINEAR_DYNAMICS, MLP_SHAPES
+from tests.tail_util import intended_reward as _intended
+from tests.tail_util import linear_dynamics_np as _linear_dynamics_np
+from tests.tail_util import mlp_bounds as _mlp_bounds
+from tests.tail_util import mlp_states as _mlp_states
+from tests.tail_util import net as _net
+from tests.tail_util import pendulum_states as _pendulum_states
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -42,12 +49,6 @@ def _opt(L, name):
     return {"RS": (L.OPT_RANDOM_SEARCH, 0, 0), "CEM": (L.OPT_CEM, 0, 0), "CEM-warm": (L.OPT_CEM, L.FIX_Q2_CEM_WARM_START, 2),
             "PI2": (L.OPT_PI2, 0, 1), "SPSA": (L.OPT_SPSA, 0, 1), "PSO": (L.OPT_PSO, 0, 0), "CMA": (L.OPT_CMAES, 0, 0),
             "CMA-pa": (L.OPT_CMAES, L.CMAES_PER_AGENT, 0)}[name]
-
-
-def _pendulum_states(steps, A, seed):
-    rng = np.random.default_rng(seed)
-    th = rng.uniform(-np.pi, np.pi, (steps, A))
-    return np.stack([np.cos(th), np.sin(th), rng.uniform(-6, 6, (steps, A))], -1).astype(F)
 
 
 def _prev(eng):
@@ -253,35 +254,6 @@ def test_rollout_episode_matches_the_host_loop_and_the_reference(L, monkeypatch)
 
 
 # ---- the user-function route: k_explore + step_dev + k_pack_record + k_shift_left -------------------------------------
-INTENDED_PENDULUM_REWARD = """
-__device__ float bbmpc_user_reward(const float* cur, const float* act, const float* nxt, int S, int U) {
-    const float PI = 3.14159274101257324f, TWO_PI = 6.28318548202514648f;
-    const float th = atan2f(cur[1], cur[0]);
-    float m = fmodf(th + PI, TWO_PI);
-    if (m < 0.0f) m = m + TWO_PI;
-    const float ang = m - PI;
-    const float first = ang * ang + 0.1f * (cur[2] * cur[2]);
-    float ss = 0.0f;
-    for (int u = 0; u < U; ++u) ss = ss + act[u] * act[u];
-    return (-first) - 0.001f * ss;
-}
-"""
-# a linear model with two inputs: delta[i] = 0.05 * act[i % U] - 0.01 * x[i]
-LINEAR_DYNAMICS = """
-__device__ void bbmpc_user_dynamics(const float* x, float* delta, int S, int U) {
-    for (int i = 0; i < S; ++i) delta[i] = 0.05f * x[S + (i % U)] - 0.01f * x[i];
-}
-"""
-
-
-def _linear_dynamics_np(x):
-    x = np.asarray(x, F)
-    S, U = 3, x.shape[1] - 3
-    return np.stack([(F(0.05) * x[:, S + (i % U)]).astype(F) - (F(0.01) * x[:, i]).astype(F) for i in range(S)], 1).astype(F)
-
-
-def _intended(cur, act, nxt):
-    return O.pendulum_reward(cur, act, nxt, as_executed=False)
 
 
 def _user_route(L, route):
@@ -335,45 +307,6 @@ def test_user_function_route_tail_by_value(L, route, opt_name, fix):
 
 
 # ---- learned dynamics: k_tail_mlp (noisy action + model step + record + warm start in one launch) ------------------------
-ACT = {"tanh": 1, "relu": 2, "sigmoid": 3, None: 0}
-MLP_SHAPES = {
-    "S20-U6-h200": ([26, 200, 200, 20], ["tanh", "tanh", None], 20, 6, "cheetah"),
-    "S3-U2-h16": ([5, 16, 3], ["tanh", None], 3, 2, "pendulum"),
-    # the two corners of what bbmpc_set_mlp accepts (dim_S + dim_U <= 128 and dim_S <= 64).  Widest state: k_tail_mlp's state
-    # threads 64..64+S are all in use.  Widest action: its action threads 64..64+U and tid < U run far past the state range, act[128]
-    # is all but full, and a production draw takes 32 Philox blocks per agent
-    "S64-U64-h96": ([128, 96, 64], ["tanh", None], 64, 64, "cheetah"),
-    "S3-U125-h96": ([128, 96, 3], ["tanh", None], 3, 125, "pendulum"),
-}
-
-
-def _stats(S, U, seed):
-    rng = np.random.default_rng(seed)
-    return [rng.normal(0, 0.2, S).astype(F), rng.uniform(0.5, 1.5, S).astype(F),
-            rng.normal(0, 0.1, U).astype(F), rng.uniform(0.5, 1.5, U).astype(F),
-            rng.normal(0, 0.01, S).astype(F), rng.uniform(0.05, 0.15, S).astype(F)]
-
-
-_NETS = {}
-
-
-def _net(shape, normalized):
-    """weights / statistics / oracle evaluator of a shape: made once, shared by the cases, never changed"""
-    key = (shape, normalized)
-    if key not in _NETS:
-        dims, acts, S, U, reward = MLP_SHAPES[shape]
-        ws, bs = O.make_mlp_params(dims, seed=42)
-        rng = np.random.default_rng(43)
-        bs = [rng.normal(0, 0.05, b.shape).astype(F) for b in bs]
-        stats = _stats(S, U, 44) if normalized else None
-        ev = O.Evaluator(reward, O.Handler(O.MLP(ws, bs, acts), False, normalized, stats))
-        _NETS[key] = (ws, bs, stats, ev)
-    return _NETS[key]
-
-
-def _mlp_bounds(U):
-    lo, hi = T.MLP_BOUNDS[U] if U in T.MLP_BOUNDS else T.wide_bounds(U)
-    return np.asarray(lo, F), np.asarray(hi, F)
 
 
 def _mlp_engine(L, shape, normalized, opt_name, A, fix, **kw):
@@ -387,13 +320,6 @@ def _mlp_engine(L, shape, normalized, opt_name, A, fix, **kw):
                  quirks=quirks | (L.FIX_Q7_EXPL_NOISE_ZERO_MEAN if fix else 0), **kw)
     eng.set_mlp(ws, bs, [ACT[a] for a in acts], stats)
     return eng
-
-
-def _mlp_states(shape, steps, A, seed):
-    S = MLP_SHAPES[shape][2]
-    if S == 3:
-        return _pendulum_states(steps, A, seed)
-    return np.random.default_rng(seed).normal(0, 0.3, (steps, A, S)).astype(F)
 
 
 def _mlp_case(L, shape, normalized, opt_name, fix, A, mode):
