@@ -3,6 +3,7 @@
 // kernels (kernels_mlp*.hpp).  A translation unit of its own: the template kernels are instantiated here only.
 #define BBMPC_TU_MLP
 #include <cmath>
+#include <type_traits>
 
 #include "engine.hpp"
 #include "engine_util.hpp"
@@ -520,7 +521,7 @@ void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int 
     HIP_CHECK(hipGetLastError());
 }
 
-// Particle rollouts of a learned model with a built-in reward (bbmpc_set_particles): one launch of the frame of
+// Particle rollouts of a learned model (bbmpc_set_particles; built-in reward, or with pa.traj the TRAJ form for a HIP-source one): one launch of the frame of
 // kernels_mlp_particles.hpp, 16 (candidate, particle) rows per workgroup, grid.y = agent -- the coverage of k_traj_mlp,
 // always fp32.  Kind MLP_PART_PLAIN; with an ensemble installed (bbmpc_set_mlp_ensemble) MLP_PART_ENS, rows grouped by
 // member and grid.z = member; with log-variance heads (bbmpc_set_mlp_logvar_head), with or without an ensemble,
@@ -533,6 +534,8 @@ void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     const long act_elems = pa.from_ref ? (long)pa.n_pop * A * pa.HU : (long)A * pa.HU * pa.Nst;
     REQUIRE(act_elems < (1L << 31) && (long)A * pa.P * pa.H * S < (1L << 31), BBMPC_E_UNSUPPORTED,
             "particle rollout: more than 2^31 action or noise elements per launch");
+    if (pa.traj)
+        REQUIRE((long)pa.H * A * S * pa.RS < (1L << 31), BBMPC_E_UNSUPPORTED, "particle rollout: more than 2^31 trajectory elements per launch");
     const int kind = lv_heads > 0 ? MLP_PART_GAUSS : ens_E > 0 ? MLP_PART_ENS : MLP_PART_PLAIN;
     const int E = std::max(1, ens_E);
     if (kind == MLP_PART_GAUSS) REQUIRE(lv_heads == E && pa.P % E == 0, BBMPC_E_INVALID, "internal: log-variance heads per model");
@@ -568,10 +571,17 @@ void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
             lds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
             REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
         }
-        const void* fn = ext ? (const void*)k_rollout_mlp_particles_kind<ARGS, true> : (const void*)k_rollout_mlp_particles_kind<ARGS, false>;
-        if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-        if (ext) hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, true>), grid, block, lds, stream, q);
-        else hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, false>), grid, block, lds, stream, q);
+        // pa.traj set (a HIP-source reward): the TRAJ form, which stores every noisy next state and leaves the returns to the scorer
+        auto launch_form = [&](auto traj) {
+            constexpr bool TRAJ = decltype(traj)::value;
+            const void* fn = ext ? (const void*)k_rollout_mlp_particles_kind<ARGS, true, TRAJ> : (const void*)k_rollout_mlp_particles_kind<ARGS, false, TRAJ>;
+            const size_t lds_all = lds + (TRAJ ? MLP_PART_ROWSLOT * sizeof(int) : 0);       // (TRAJ: the row slots lie behind the layout)
+            if (lds_all > 64 * 1024) ensure_max_lds(fn, 159 * 1024 + (TRAJ ? MLP_PART_ROWSLOT * (int)sizeof(int) : 0));
+            if (ext) hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, true, TRAJ>), grid, block, lds_all, stream, q);
+            else hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, false, TRAJ>), grid, block, lds_all, stream, q);
+        };
+        if (pa.traj) launch_form(std::true_type());
+        else launch_form(std::false_type());
         HIP_CHECK(hipGetLastError());
     };
     if (kind == MLP_PART_GAUSS) launch(MlpGaussParticleArgs());

@@ -20,8 +20,10 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     for (int s = 0; s < S; ++s)
         REQUIRE(std::isfinite(sigma[s]) && sigma[s] >= 0.0f, BBMPC_E_INVALID, "process noise sigma must be finite and >= 0");
     REQUIRE(std::isfinite(kappa), BBMPC_E_INVALID, "risk_kappa must be finite");
-    REQUIRE(cfg.reward != BBMPC_REW_USER && cfg.dynamics != BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
-            "particles with a HIP-source or callback reward / dynamics: the noisy rollouts are built for the built-in models and rewards");
+    // a HIP-source reward scores the learned model's particles; the analytic pendulum keeps its built-in rewards
+    REQUIRE((cfg.reward != BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_MLP) && cfg.dynamics != BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
+            "particles with HIP-source or callback dynamics, or with a user reward beside the built-in pendulum model: a user reward "
+            "scores the noisy rollouts of a learned model (BBMPC_DYN_MLP) only");
     REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED, "particles with an inverse target transform: the noise is added to next = dev + state");
     REQUIRE(!pop_sharded() && cfg.population_global <= N, BBMPC_E_UNSUPPORTED,
             "particles with a sharded population: the shards would have to exchange per-particle returns");
@@ -96,8 +98,14 @@ void Engine::dump_process_noise(int control_step, int iteration, float* out, int
 // noisy rollouts of every (candidate, particle) row, the aggregate into ra.rewards.  d_returns: where the per-particle
 // returns [A][returns_stride] go (null: the handle's own buffer).
 void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_returns, int returns_stride) {
-    REQUIRE(!user_path(), BBMPC_E_UNSUPPORTED, "particles with user-supplied functions or an inverse target transform");
+    const bool user_rew = particle_user_reward();          // a HIP-source reward over the learned model: TRAJ rollout + scorer
+    REQUIRE(!user_path() || user_rew, BBMPC_E_UNSUPPORTED, "particles with user-supplied dynamics or an inverse target transform");
     const int P = part_P;
+    if (user_rew) {                                        // refused before anything is allocated, drawn or launched
+        require_particle_user_reward();
+        (void)user_reward_params_dev();                    // (declared but not set: BBMPC_E_STATE)
+        require_particle_traj_fits(d_returns ? returns_stride : (long)ra.Nst * P);
+    }
     if (!d_returns) {
         returns_stride = ra.Nst * P;
         if (d_preturns.n < (size_t)A * returns_stride) d_preturns.alloc((size_t)A * returns_stride);
@@ -121,12 +129,18 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
     q.rewards = ra.rewards;
     q.penalty_out = ra.penalty_out;
     REQUIRE(ra.H == H, BBMPC_E_INVALID, "internal: particle rollout horizon");
+    if (user_rew) {
+        const size_t need = (size_t)ra.H * A * S * returns_stride;
+        if (d_ptraj.n < need) d_ptraj.alloc(need);
+        q.traj = d_ptraj.p;
+    }
     const long rows = (long)ra.n_pop * P;
     dominant_inst[0] = 0;
     prof_begin();
     if (cfg.dynamics == BBMPC_DYN_MLP) {
         dominant_kernel = lv_heads > 0 ? "k_rollout_mlp_particles_gauss" : ens_E > 0 ? "k_rollout_mlp_particles_ens" : "k_rollout_mlp_particles";
         launch_rollout_mlp_particles(q);
+        if (user_rew) score_particles_user(q);             // inside the profiled span, under the kind's name
     } else {
         dominant_kernel = "k_rollout_pendulum_particles";
         // few rows -> one wave per workgroup so every wave gets its own SIMD; many -> 256-thread workgroups
@@ -143,6 +157,31 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
     HIP_CHECK(hipGetLastError());
 }
 
+// returns [A][RS] from the states the TRAJ rollout left in pa.traj: one lane per (candidate, particle) row, grid.y = agent
+void Engine::score_particles_user(const ParticleArgs& pa) {
+    int n_pop = pa.n_pop, P = pa.P, Aa = A, Hh = pa.H, Nst_ = pa.Nst, RS = pa.RS, from_ref = pa.from_ref, ipen = pa.pen;
+    const float* state = pa.state;
+    const float* traj = pa.traj;
+    const float* seq = pa.seq;
+    const float* cand = pa.cand;
+    const float* lo_ = pa.lo;
+    const float* hi_ = pa.hi;
+    float* returns = pa.returns;
+    if (!from_ref) REQUIRE(cand, BBMPC_E_STATE, "user reward over the learned model's particles: no candidate buffer");
+    const float* params = user_reward_params_dev();                  // a parameterised reward only
+    void* args[] = {&n_pop, &P, &Aa, &Hh, &Nst_, &RS, &from_ref, &ipen, &state, &traj, &seq, &cand, &lo_, &hi_, &returns, &params};
+    const long rows = (long)n_pop * P;
+    const unsigned bs = (rows * A <= 16384) ? 64 : 256;                       // as k_rollout_pendulum_particles sizes its workgroups
+    HIP_CHECK(hipModuleLaunchKernel(user_reward.fn_particles, (unsigned)((rows + bs - 1) / bs), (unsigned)A, 1, bs, 1, 1, 0, stream, args, nullptr));
+}
+
+
+// the TRAJ rollout's buffer [H][A][S][RS] is addressed with 32-bit offsets
+void Engine::require_particle_traj_fits(long returns_stride) const {
+    REQUIRE((long)H * A * S * returns_stride < (1L << 31), BBMPC_E_UNSUPPORTED,
+            "particles with a HIP-source reward: horizon * num_agents * dim_s * (candidates * num_particles) reaches 2^31 trajectory elements");
+}
+
 // scores [n_pop, A] and (optional) returns [n_pop, P, A] in the reference's layouts, from the caller's sequences
 void Engine::evaluate_particles_dev(const float* d_state_in, const float* d_seq, int n_pop, float* d_scores, float* d_ret_out) {
     REQUIRE(particles_on(), BBMPC_E_STATE, "particles are off: call bbmpc_set_particles first");
@@ -150,6 +189,7 @@ void Engine::evaluate_particles_dev(const float* d_state_in, const float* d_seq,
     REQUIRE((long)n_pop * part_P <= (1L << 24), BBMPC_E_UNSUPPORTED, "particles: n_pop * num_particles must not exceed 2^24 per call");
     const int P = part_P;
     const int st = ((n_pop + 63) / 64) * 64;
+    if (particle_user_reward()) require_particle_traj_fits((long)st * P);
     if (d_eval_rew.n < (size_t)A * st) d_eval_rew.alloc((size_t)A * st);
     RolloutArgs ra;
     memset(&ra, 0, sizeof(ra));
@@ -211,6 +251,7 @@ int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* se
     Engine& e = *h->e;
     if (!e.particles_on()) throw HipError(BBMPC_E_STATE, "particles are off: call bbmpc_set_particles first");
     if (n_pop < 1) throw HipError(BBMPC_E_INVALID, "n_pop must be >= 1");
+    if (e.particle_user_reward()) e.require_particle_traj_fits((((long)n_pop + 63) / 64) * 64 * e.part_P);     // before the staging buffer
     const size_t nseq = (size_t)n_pop * e.A * e.HU, nsc = (size_t)n_pop * e.A, nret = returns ? nsc * e.part_P : 0;
     if (e.d_pe_io.n < nseq + nsc + nret) e.d_pe_io.alloc(nseq + nsc + nret);
     float* dseq = e.d_pe_io.p;

@@ -23,7 +23,8 @@ static void check_traj_particles(const Engine& e, int batch, int horizon, bool a
             REQUIRE(ranks[l] >= 0 && ranks[l] < e.part_P, BBMPC_E_INVALID,
                     "trajectory quantiles: rank " + std::to_string(ranks[l]) + " is outside [0, num_particles = " + std::to_string(e.part_P) + ")");
     }
-    REQUIRE(!e.user_path(), BBMPC_E_UNSUPPORTED, "particles with user-supplied functions or an inverse target transform");
+    REQUIRE(!e.user_path() || e.particle_user_reward(), BBMPC_E_UNSUPPORTED, "particles with user-supplied dynamics or an inverse target transform");
+    if (e.particle_user_reward()) e.require_particle_user_reward();       // a callback, or no source yet
     if (e.cfg.dynamics == BBMPC_DYN_MLP) REQUIRE(e.mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
     const long qp = ((long)horizon * e.S + 3) / 4;
     REQUIRE((long)batch * e.part_P * horizon * e.S < (1L << 31) && (long)batch * horizon * e.U < (1L << 31), BBMPC_E_UNSUPPORTED,
@@ -37,6 +38,11 @@ static void check_traj_particles(const Engine& e, int batch, int horizon, bool a
 void Engine::roll_trajectory_particles(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps, float*& d_pstates,
                                        float*& d_prewards) {
     const int P = part_P;
+    if (particle_user_reward()) {                          // refused before anything is allocated or launched
+        if (user_reward_params_dev() && rew_params.per_agent)
+            REQUIRE(batch % A == 0, BBMPC_E_INVALID,
+                    "per-agent runtime parameters: a call on B rows needs B to be a multiple of num_agents (B / A consecutive rows per agent)");
+    }
     const size_t nps = (size_t)batch * P * horizon * S, npr = (size_t)batch * P * horizon;
     if (!d_eps) {
         // the handle's own draws: the process-noise stream with the row in the agent word, the handle's current control step,
@@ -72,6 +78,9 @@ void Engine::roll_trajectory_particles(const float* d_states, const float* d_seq
     q.pstates = d_pstates; q.prewards = d_prewards;
     if (cfg.dynamics == BBMPC_DYN_MLP) {
         launch_traj_mlp_particles(q);
+        // a HIP-source reward: the kernel above left zeros (REW_NONE); the scorer fills prewards from
+        // pstates before the moments and the quantiles read them
+        if (particle_user_reward()) score_traj_particles_user(q);
     } else {
         const long rows = (long)batch * P;
         const int bs = rows <= 16384 ? 64 : 256;           // few rows: one wave per workgroup, as k_rollout_pendulum_particles

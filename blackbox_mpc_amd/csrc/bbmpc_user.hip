@@ -3,6 +3,7 @@
 // draws random numbers (candidates come from the core's Engine::draw_candidates): no quantile-table upload for this unit.
 #include "abi_util.hpp"
 #include "rtc.hpp"
+#include "traj_particle_args.hpp"
 
 namespace bbmpc {
 
@@ -22,7 +23,11 @@ static void load_program(UserFunction& f, int form, const std::vector<char>& cod
     f.release();
     HIP_CHECK(hipModuleLoadData(&f.module, code.data()));
     HIP_CHECK(hipModuleGetFunction(&f.fn, f.module, program_kernel(form)));
-    if (form == USER_KIND_REWARD) HIP_CHECK(hipModuleGetFunction(&f.fn_traj, f.module, "bbmpc_user_reward_traj"));
+    if (form == USER_KIND_REWARD) {
+        HIP_CHECK(hipModuleGetFunction(&f.fn_traj, f.module, "bbmpc_user_reward_traj"));
+        HIP_CHECK(hipModuleGetFunction(&f.fn_particles, f.module, "bbmpc_user_reward_particles"));
+        HIP_CHECK(hipModuleGetFunction(&f.fn_traj_particles, f.module, "bbmpc_user_reward_traj_particles"));
+    }
 }
 
 // one lane per row; the launch reads as many entries of args[] as the kernel has, so a classic one ignores the parameters at the end
@@ -114,6 +119,8 @@ const float* Engine::user_params_dev(int kind) {
                                                                        : "user dynamics: runtime parameters not set (bbmpc_set_user_params)");
     return user_pp(kind).d.p;
 }
+
+const float* Engine::user_reward_params_dev() { return user_params_dev(USER_KIND_REWARD); }
 
 // rows of one agent in a batch of rows (the evaluator's layout b = a * rows + n): per-agent parameters need a multiple of A
 // rows; shared ones any batch (every row then reads agent 0's copy)
@@ -378,6 +385,28 @@ void Engine::rollout_mlp_user_reward(int mode, bool pen, RolloutArgs& ra) {
     const float* params = user_params_dev(USER_KIND_REWARD);                  // a parameterised reward only
     void* args[] = {&n_pop, &Aa, &Hh, &Nst_, &from_ref, &state, &traj, &seq, &cand, &rewards, &params};
     HIP_CHECK(hipModuleLaunchKernel(user_reward.fn_traj, (unsigned)((n_pop + 255) / 256), (unsigned)A, 1, 256, 1, 1, 0, stream, args, nullptr));
+}
+
+// A HIP-source reward over the learned model's particles.  What the path refuses when it computes;
+// bbmpc_set_particles has let the handle through on BBMPC_DYN_MLP + BBMPC_REW_USER alone.
+void Engine::require_particle_user_reward() const {
+    REQUIRE(!user_reward.cb, BBMPC_E_UNSUPPORTED,
+            "particles with a callback reward: the particle evaluator needs a HIP-source reward (bbmpc_set_reward_source)");
+    REQUIRE(user_reward.fn_particles && user_reward.fn_traj_particles, BBMPC_E_STATE, "user reward: call bbmpc_set_reward_source before computing");
+}
+
+// prewards [B][P][Hq] from the particle states k_traj_mlp_particles_kind left in pa.pstates: one lane per (b, p, t)
+void Engine::score_traj_particles_user(const TrajParticleArgs& pa) {
+    int B = pa.B, P = pa.P, Hq = pa.Hq;
+    const float* states = pa.states;
+    const float* seq = pa.seq;
+    const float* pstates = pa.pstates;
+    float* prewards = pa.prewards;
+    const float* params = user_params_dev(USER_KIND_REWARD);
+    int rpa = params ? rows_per_agent(USER_KIND_REWARD, B) : B;
+    void* args[] = {&B, &P, &Hq, &states, &seq, &pstates, &prewards, &params, &rpa};
+    const long n = (long)B * P * Hq;
+    HIP_CHECK(hipModuleLaunchKernel(user_reward.fn_traj_particles, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, stream, args, nullptr));
 }
 
 // The learned-model rollout with the inverse target transform (and a user reward, if any) inlined: kernels_mlp_xform.hpp,

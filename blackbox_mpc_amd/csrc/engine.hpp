@@ -90,6 +90,8 @@ struct UserFunction {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
     hipFunction_t fn_traj = nullptr;       // reward module only: bbmpc_user_reward_traj
+    hipFunction_t fn_particles = nullptr;       // ... bbmpc_user_reward_particles (the particle rollout's scorer)
+    hipFunction_t fn_traj_particles = nullptr;  // ... bbmpc_user_reward_traj_particles (the trajectory distribution's)
     bbmpc_rows_callback cb = nullptr;      // or: a host callback working on device memory (bbmpc_set_*_callback)
     void* cb_user = nullptr;
     void release() {
@@ -97,6 +99,8 @@ struct UserFunction {
         module = nullptr;
         fn = nullptr;
         fn_traj = nullptr;
+        fn_particles = nullptr;
+        fn_traj_particles = nullptr;
     }
 };
 
@@ -334,6 +338,7 @@ struct Engine {
     int64_t rtc_compiles = 0;          // hiprtc compilations of this handle (bbmpc_compile_stats)
     void set_user_params(int kind, const float* data, int64_t count);
     const float* user_params_dev(int kind);
+    const float* user_reward_params_dev();      // user_params_dev(USER_KIND_REWARD), for the units that do not see rtc.hpp
     int rows_per_agent(int kind, int batch);
     UserFunction& user_fn(int kind);            // the reward / dynamics side: its function, its parameters, ...
     UserParams& user_pp(int kind);
@@ -457,6 +462,14 @@ struct Engine {
     void dump_process_noise(int control_step, int iteration, float* out, int64_t count);
     void rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_returns, int returns_stride);
     void launch_rollout_mlp_particles(const ParticleArgs& pa);                 // bbmpc_mlp.hip
+    // a HIP-source reward over the learned model's particles: the rollout stores every noisy next state
+    // to d_ptraj [H][A][S][RS] (ParticleArgs::traj), rtc.hpp's scorers turn states into returns / per-step rewards
+    DevBuf<float> d_ptraj;
+    bool particle_user_reward() const { return cfg.dynamics == BBMPC_DYN_MLP && cfg.reward == BBMPC_REW_USER && !has_xform(); }
+    void require_particle_user_reward() const;                                // bbmpc_user.hip: what this path refuses at compute time
+    void score_particles_user(const ParticleArgs& pa);                        // bbmpc_particles.hip
+    void require_particle_traj_fits(long returns_stride) const;               // H * A * S * RS < 2^31, before anything is allocated
+    void score_traj_particles_user(const TrajParticleArgs& pa);               // bbmpc_user.hip
     // model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble; bbmpc_mlp.hip, kernels_mlp_particles.hpp): particle p
     // follows member p % ens_E.  Every deterministic path keeps the model of bbmpc_set_mlp.
     int ens_E = 0;

@@ -21,6 +21,10 @@
 //       stride 0.
 // Every instantiation compiles to the instruction stream the three separate kernels had; the order of the statements below
 // is theirs, and reordering them moves instructions.
+// A third template argument, TRAJ, gives the form a HIP-source reward needs: no reward and no returns
+// store, instead every step's noisy next states go to ParticleArgs::traj, feature-major [H][A][S][RS], for rtc.hpp's
+// bbmpc_user_reward_particles to score.  Everything TRAJ adds is behind `if constexpr`: the TRAJ = false instantiations are
+// the kernels they were (same resource remarks).
 // Dims, activations and the normalisation statistics are the primary model's (MlpDesc).  Offsets into the action source and
 // the noise are 32 bit (the host refuses larger buffers).
 // The prologue and the epilogue restate k_traj_mlp / rollout_mlp_body<0>: a fix in one of them belongs here as well.
@@ -72,13 +76,18 @@ struct MlpGaussParticleArgs {
     ParticleArgs p;
 };
 
+constexpr int MLP_PART_ROWSLOT = MLP_TP;      // TRAJ: ints behind the layout's total
 constexpr int MLP_PART_PF = 2;      // noise elements a thread holds in registers across a step's Dense stack
 
-template <class ARGS, bool EXT>
+template <class ARGS, bool EXT, bool TRAJ = false>
 __global__ void k_rollout_mlp_particles_kind(ARGS q) {
     constexpr int KIND = ARGS::KIND;
     constexpr bool MEMBER = KIND != MLP_PART_PLAIN;       // rows grouped by member, grid.z = member
     constexpr bool GAUSS = KIND == MLP_PART_GAUSS;        // a log-variance head behind the last layer
+    // noise elements held in registers across the Dense stack.  The head's TRAJ form is the one instantiation at the register
+    // limit with nothing to give: it holds one (the others are fetched in the epilogue, which only networks of fewer than
+    // 16 * S / 64 waves notice) and so stays free of scratch.
+    constexpr int NPF = (TRAJ && GAUSS) ? 1 : MLP_PART_PF;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpDesc& m = q.m;
     const ParticleArgs& pa = q.p;
@@ -150,10 +159,10 @@ __global__ void k_rollout_mlp_particles_kind(ARGS q) {
             abase[j] = pa.from_ref ? (n * pa.A + a) * pa.HU + u : (a * pa.HU + u) * pa.Nst + n;
         }
     }
-    int nbase[MLP_PART_PF];
-    float nsig[MLP_PART_PF];
+    int nbase[NPF];
+    float nsig[NPF];
 #pragma unroll
-    for (int j = 0; j < MLP_PART_PF; ++j) {
+    for (int j = 0; j < NPF; ++j) {
         const int i = tid + j * nthr;
         const int f = i / MLP_TP, pp = i - f * MLP_TP;
         nbase[j] = -1;
@@ -208,6 +217,13 @@ __global__ void k_rollout_mlp_particles_kind(ARGS q) {
 
     const int OTl = m.tiles[L];
     float racc = 0.0f;                                 // lanes 0..15 of wave 0: the row's reward sum
+    // TRAJ: the slot of each of the tile's rows in a feature's run of pa.traj -- its returns index, -1 = a row past the last --
+    // in the MLP_PART_ROWSLOT ints the launch adds behind the layout (as k_traj_mlp_particles_kind keeps its row map: a
+    // register held across the Dense stack spills in the widest instantiation).  Published by the barriers of step 0.
+    [[maybe_unused]] int* rowslot = reinterpret_cast<int*>(smem + lay.total);
+    if constexpr (TRAJ) {
+        if (tid < MLP_TP) rowslot[tid] = (n0 + tid < R) ? (MEMBER ? row_n(n0 + tid) * P + row_p(n0 + tid) : n0 + tid) : -1;
+    }
     for (int t = 0; t < H; ++t) {
         float* cur = st + (t & 1) * MLP_TP * Sp;
         float* nxt = st + ((t + 1) & 1) * MLP_TP * Sp;
@@ -228,9 +244,9 @@ __global__ void k_rollout_mlp_particles_kind(ARGS q) {
             }
             pf[j] = v;
         }
-        float en[MLP_PART_PF];
+        float en[NPF];
 #pragma unroll
-        for (int j = 0; j < MLP_PART_PF; ++j) en[j] = nbase[j] >= 0 ? noise_elem(nsig[j], pa.pnoise[nbase[j] + t * S]) : 0.0f;
+        for (int j = 0; j < NPF; ++j) en[j] = nbase[j] >= 0 ? noise_elem(nsig[j], pa.pnoise[nbase[j] + t * S]) : 0.0f;
         // ---- dense layers (kernels_mlp.hpp, SPEC 0)
         int in_off = lay.xs;
         for (int l = 0; l < L - 1; ++l) {
@@ -271,11 +287,11 @@ __global__ void k_rollout_mlp_particles_kind(ARGS q) {
             xs[tile_addr(f, pp)] = (ns - nmean[f]) * ninv[f];
         };
 #pragma unroll
-        for (int j = 0; j < MLP_PART_PF; ++j) {
+        for (int j = 0; j < NPF; ++j) {
             const int i = tid + j * nthr;
             if (i < MLP_TP * S) epilogue(i, nsig[j], en[j]);
         }
-        for (int i = tid + MLP_PART_PF * nthr; i < MLP_TP * S; i += nthr) epilogue(i, pa.sigma[i / MLP_TP], fetch_noise(i, t));
+        for (int i = tid + NPF * nthr; i < MLP_TP * S; i += nthr) epilogue(i, pa.sigma[i / MLP_TP], fetch_noise(i, t));
         if (more) {
 #pragma unroll
             for (int j = 0; j < MLP_TRAJ_PF; ++j) {
@@ -296,9 +312,24 @@ __global__ void k_rollout_mlp_particles_kind(ARGS q) {
         __syncthreads();
         // ---- the step's reward overlaps the next step's first layer: wave 0, one lane per row.  `cur` / `act_t` are next
         // written behind step t + 1's Dense stack, whose barriers wave 0 passes after this.
-        if (tid < MLP_TP)
+        if constexpr (TRAJ) {
+            // no reward here (the kind is REW_NONE): the step's noisy next states go to pa.traj [H][A][S][RS] instead, from
+            // the LDS tile and BEHIND the barrier, so the stores drain under step t + 1's Dense stack and no barrier the
+            // MFMA loop waits on has them in front of it.  16 consecutive lanes write 16 consecutive rows of one feature
+            // (64 bytes; with members the slots of one candidate are E apart).  `nxt` is next written by step t + 2's epilogue.
+            const int pp = tid & (MLP_TP - 1);       // every element i = tid + j * nthr of this thread is of row tid % 16
+            const int slot = rowslot[pp];
+            if (slot >= 0) {
+#pragma unroll 1
+                for (int i = tid; i < MLP_TP * S; i += nthr) {
+                    const int f = i / MLP_TP;
+                    pa.traj[((t * pa.A + a) * S + f) * pa.RS + slot] = nxt[pp * Sp + f];
+                }
+            }
+        } else if (tid < MLP_TP)
             racc = racc + reward_generic(pa.reward_kind, pa.fix_q1 != 0, cur + tid * Sp, act_t + tid * U, nxt + tid * Sp, S, U);
     }
+    if constexpr (TRAJ) return;                                 // (the scorer writes the returns: rtc.hpp bbmpc_user_reward_particles)
     if (tid < MLP_TP && n0 + tid < R) {
         if (racc != racc) racc = -1.0e6f;                       // deterministic.py:75-77, per particle
         // the row's element of the agent's returns, n * P + p (without members the row itself; two index expressions here, not

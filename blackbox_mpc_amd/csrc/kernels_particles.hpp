@@ -39,6 +39,9 @@ struct ParticleArgs {
     float* samples;           // aggregate: where the feasible candidates go (internal layout) or null
     float* rewards;           // aggregate: scores [A][Nst]
     float* penalty_out;       // aggregate: optional [A][Nst]
+    // the learned model's TRAJ rollout only (a HIP-source reward): the noisy next state of every row
+    // and step, feature-major [H][A][S][RS] with the row's slot its returns index n * P + p.  The last field: no other moves.
+    float* traj;
 };
 
 // Element j = t * S + s of particle p, global agent ga: counter (p, ga * Qp + (j >> 2), control step, (11 << 16) | iter),

@@ -155,6 +155,68 @@ extern "C" __global__ void bbmpc_user_reward_traj(int n_pop, int A, int H, int N
     if (total != total) total = -1.0e6f;
     rewards[(size_t)a * Nst + n] = total + rewards[(size_t)a * Nst + n];
 }
+
+// The particle evaluator over the learned model (bbmpc_set_particles, DESIGN.md section 8i): the TRAJ form of the MFMA
+// particle rollout (kernels_mlp_particles.hpp) leaves the NOISY next state of every (candidate, particle) row and step in
+// traj [H][A][S][RS], feature-major, the row's slot its returns index r = n * P + p.  One lane per row of agent blockIdx.y
+// walks the horizon from the agent's state: consecutive lanes read consecutive floats of every feature.  The action is
+// candidate n's, clipped HERE when `pen` (the particle path writes the feasible samples back only in the aggregate, behind
+// this; kernels_particles.hpp particle_action).  Sum in index order, NaN -> -1e6 per particle, returns [A][RS].
+extern "C" __global__ void bbmpc_user_reward_particles(int n_pop, int P, int A, int H, int Nst, int RS, int from_ref, int pen,
+                                                       const float* __restrict__ state, const float* __restrict__ traj,
+                                                       const float* __restrict__ seq, const float* __restrict__ cand,
+                                                       const float* __restrict__ lo, const float* __restrict__ hi,
+                                                       float* __restrict__ returns
+#ifdef BBMPC_REW_NPARAMS
+                                                       , const float* __restrict__ params
+#endif
+                                                       ) {
+    const int a = blockIdx.y, r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_pop * P) return;
+    const int n = r / P;
+    const int HU = H * BBMPC_U;
+    float c[BBMPC_S], nx[BBMPC_S], ac[BBMPC_U];
+    for (int i = 0; i < BBMPC_S; ++i) c[i] = state[a * BBMPC_S + i];
+    float total = 0.0f;
+    for (int t = 0; t < H; ++t) {
+        const float* tile = traj + (((size_t)t * A + a) * BBMPC_S) * RS + r;
+        for (int i = 0; i < BBMPC_S; ++i) nx[i] = tile[(size_t)i * RS];
+        for (int u = 0; u < BBMPC_U; ++u) {
+            const int j = t * BBMPC_U + u;
+            float v = from_ref ? seq[((size_t)n * A + a) * HU + j] : cand[((size_t)a * HU + j) * Nst + n];
+            if (pen) v = (v < lo[u]) ? lo[u] : ((v > hi[u]) ? hi[u] : v);
+            ac[u] = v;
+        }
+        total = total + BBMPC_CALL_REWARD(c, ac, nx, params, a, t);
+        for (int i = 0; i < BBMPC_S; ++i) c[i] = nx[i];
+    }
+    if (total != total) total = -1.0e6f;
+    returns[(size_t)a * RS + r] = total;
+}
+
+// Trajectory distributions (bbmpc_predict_trajectory_particles / _quantiles): k_traj_mlp_particles_kind leaves every
+// particle state in pstates [B][P][Hq][S]; one lane per (b, p, t) fills prewards [B][P][Hq] from it -- the current state is
+// row b's start state at t = 0 and pstates[b, p, t - 1] afterwards, no recurrence.  No clip and no NaN rule, as with a
+// built-in reward.  Row b belongs to agent b / rows_per_agent, t is the step inside the sequence.
+extern "C" __global__ void bbmpc_user_reward_traj_particles(int B, int P, int Hq, const float* __restrict__ states,
+                                                            const float* __restrict__ seq, const float* __restrict__ pstates,
+                                                            float* __restrict__ prewards
+#ifdef BBMPC_REW_NPARAMS
+                                                            , const float* __restrict__ params, int rows_per_agent
+#endif
+                                                            ) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * P * Hq) return;
+    const int t = (int)(idx % Hq);
+    const int b = (int)(idx / ((size_t)P * Hq));
+    float c[BBMPC_S], nx[BBMPC_S], ac[BBMPC_U];
+    for (int i = 0; i < BBMPC_S; ++i) {
+        c[i] = t == 0 ? states[(size_t)b * BBMPC_S + i] : pstates[(idx - 1) * BBMPC_S + i];
+        nx[i] = pstates[idx * BBMPC_S + i];
+    }
+    for (int u = 0; u < BBMPC_U; ++u) ac[u] = seq[((size_t)b * Hq + t) * BBMPC_U + u];
+    prewards[idx] = BBMPC_CALL_REWARD(c, ac, nx, params, b / rows_per_agent, t);
+}
 )RTC";
 
 static const char* const k_inverse_transform_rows_text = R"RTC(
@@ -391,7 +453,8 @@ struct UserProgram {
     std::string& own_source(int kind) { return kind == USER_KIND_REWARD ? reward_src : kind == USER_KIND_DYNAMICS ? dynamics_src : xform_src; }
 };
 
-// the kernel a loaded program is entered by (the reward rows program also has bbmpc_user_reward_traj)
+// the kernel a loaded program is entered by (the reward rows program also has bbmpc_user_reward_traj and the two particle
+// scorers, bbmpc_user_reward_particles and bbmpc_user_reward_traj_particles)
 inline const char* program_kernel(int form) {
     static const char* const names[] = {"", "bbmpc_user_reward_rows", "bbmpc_user_dynamics_rows", "bbmpc_user_inverse_transform_rows",
                                         "bbmpc_user_transform_rows", "bbmpc_user_rollout", "bbmpc_mlp_xform_rollout", "bbmpc_user_traj"};
