@@ -34,7 +34,8 @@ OBJ_DIR = os.path.join(CSRC, "_obj")
 GUARDED = {"kernels_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_eigh.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_eigh_small.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
-           "kernels_fused_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA")}
+           "kernels_fused_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
+           "kernels_reward_mlp.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP")}
 
 
 def _after_matching_endif(rest):

@@ -14,7 +14,8 @@ ABI_VERSION = 4
 # enums (bbmpc.h)
 OPT_NONE, OPT_RANDOM_SEARCH, OPT_CEM, OPT_PI2, OPT_PSO, OPT_CMAES, OPT_SPSA = range(7)
 DYN_PENDULUM, DYN_MLP, DYN_USER = 1, 2, 3
-REW_PENDULUM, REW_CHEETAH, REW_USER = 1, 2, 3
+REW_PENDULUM, REW_CHEETAH, REW_USER, REW_MLP = 1, 2, 3, 4
+REW_MLP_IN_STATE, REW_MLP_IN_ACTION, REW_MLP_IN_NEXT_STATE = 1, 2, 4      # bbmpc_set_reward_mlp: input_mask bits
 USER_KIND_REWARD, USER_KIND_DYNAMICS, USER_KIND_INVERSE_TRANSFORM, USER_KIND_TRANSFORM = 1, 2, 3, 4
 MAX_USER_PARAMS = 4096                                  # BBMPC_MAX_USER_PARAMS: runtime parameters per agent
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID = range(4)
@@ -91,6 +92,7 @@ SYMBOLS = [
     "bbmpc_set_particle_risk", "bbmpc_predict_trajectory_quantiles", "bbmpc_predict_trajectory_quantiles_dev",
     "bbmpc_set_sampling_correlation", "bbmpc_get_sampling_correlation",
     "bbmpc_set_elite_carry", "bbmpc_get_elite_carry",
+    "bbmpc_set_reward_mlp",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -122,6 +124,8 @@ def _load():
     lib.bbmpc_set_stream_default.argtypes = [vp]
     lib.bbmpc_set_mlp.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
                                   ctypes.POINTER(vp), i32, ctypes.POINTER(vp)]
+    lib.bbmpc_set_reward_mlp.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
+                                         ctypes.POINTER(vp), i32, i32, ctypes.POINTER(vp)]
     lib.bbmpc_reset.argtypes = [vp]
     lib.bbmpc_optimize.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.bbmpc_optimize_dev.argtypes = [vp, vp, i32, i32, vp, vp]

@@ -110,7 +110,11 @@ Engine::Engine(const bbmpc_config& c) : cfg(c) {
     REQUIRE(c.action_low && c.action_high, BBMPC_E_INVALID, "action_low/action_high are required");
     REQUIRE(c.optimizer >= BBMPC_OPT_NONE && c.optimizer <= BBMPC_OPT_SPSA, BBMPC_E_INVALID, "unknown optimizer");
     REQUIRE(c.dynamics == BBMPC_DYN_PENDULUM || c.dynamics == BBMPC_DYN_MLP || c.dynamics == BBMPC_DYN_USER, BBMPC_E_INVALID, "unknown dynamics kind");
-    REQUIRE(c.reward == BBMPC_REW_PENDULUM || c.reward == BBMPC_REW_CHEETAH || c.reward == BBMPC_REW_USER, BBMPC_E_INVALID, "unknown reward kind");
+    REQUIRE(c.reward == BBMPC_REW_PENDULUM || c.reward == BBMPC_REW_CHEETAH || c.reward == BBMPC_REW_USER || c.reward == BBMPC_REW_MLP,
+            BBMPC_E_INVALID, "unknown reward kind");
+    if (c.reward == BBMPC_REW_MLP)
+        REQUIRE(c.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
+                "a learned reward model (BBMPC_REW_MLP) scores the rollouts of a learned model: the handle needs BBMPC_DYN_MLP, not analytic or user dynamics");
     if (c.dynamics == BBMPC_DYN_USER || c.reward == BBMPC_REW_USER)
         REQUIRE(S <= 256 && U <= 256, BBMPC_E_UNSUPPORTED, "user device functions: dim_s, dim_u <= 256 (per-row arrays live in registers)");
     if (c.dynamics == BBMPC_DYN_PENDULUM)
@@ -206,6 +210,7 @@ Engine::Engine(const bbmpc_config& c) : cfg(c) {
         sw.host_poll = !flag("BBMPC_NO_HOST_POLL");
         sw.mlp_no_half_tail = flag("BBMPC_MLP_NO_HALF_TAIL");
         sw.dbg = flag("BBMPC_DBG");
+        sw.prof_reward_mlp = flag("BBMPC_PROF_REWARD_MLP");
         user_stepwise_only = flag("BBMPC_USER_STEPWISE");
         if (c.optimizer != BBMPC_OPT_NONE) {
             ps_loopback = auto_split > 1 ? auto_split : ival("BBMPC_POPSHARD_LOOPBACK", 0);
@@ -659,6 +664,11 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
     }
     if (particles_on()) {                                 // bbmpc_set_particles: noisy rollouts + aggregate (bbmpc_particles.hip)
         rollout_particles(mode, pen, ra, nullptr, 0);
+        return;
+    }
+    if (cfg.reward == BBMPC_REW_MLP) {                    // a learned reward: MFMA rollout + MFMA scorer, whatever BBMPC_USER_STEPWISE says
+        dominant_kernel = "k_rollout_mlp";
+        rollout_mlp_reward_mlp(mode, pen, ra);
         return;
     }
     if (user_path()) {
@@ -1293,7 +1303,7 @@ void Engine::step_dev(const float* d_states, const float* d_actions, int astride
 }
 
 void Engine::reward_dev(const float* d_cur, const float* d_next, const float* d_act, int batch, float* d_rew) {
-    if (cfg.reward == BBMPC_REW_USER) {
+    if (cfg.reward == BBMPC_REW_USER || cfg.reward == BBMPC_REW_MLP) {
         reward_rows(d_cur, d_next, d_act, U, batch, d_rew, 0);
         return;
     }

@@ -5,8 +5,10 @@
 #include <cmath>
 #include <type_traits>
 
+#include "abi_util.hpp"
 #include "engine.hpp"
 #include "engine_util.hpp"
+#include "kernels_reward_mlp.hpp"
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
 #include "kernels_mlp_traj_particles.hpp"
@@ -642,4 +644,179 @@ void Engine::launch_traj_mlp_particles(const TrajParticleArgs& pa) {
     else launch(MlpTrajParticleArgs());
 }
 
+// ------------------------------------------------------------------------------------------------
+// learned reward model (bbmpc_set_reward_mlp; kernels_reward_mlp.hpp)
+// ------------------------------------------------------------------------------------------------
+// Everything is checked and packed on the host before the handle is touched, so a refusal leaves it as it was.
+void Engine::set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
+                            int input_mask, int is_normalized, const float* const* stats) {
+    REQUIRE(cfg.reward == BBMPC_REW_MLP, BBMPC_E_STATE, "handle was not created with BBMPC_REW_MLP");
+    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
+    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "reward model: at least one Dense layer");
+    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "reward model: 1..8 Dense layers are supported");
+    REQUIRE(input_mask >= 1 && input_mask <= 7, BBMPC_E_INVALID, "reward model: input_mask must select at least one of s_t (1), a_t (2), s_t+1 (4)");
+    const int D = ((input_mask & 1) ? S : 0) + ((input_mask & 2) ? U : 0) + ((input_mask & 4) ? S : 0);
+    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
+    REQUIRE(dims[0] == D, BBMPC_E_INVALID,
+            "reward model: dims[0] = " + std::to_string(dims[0]) + " but input_mask selects " + std::to_string(D) + " input columns");
+    REQUIRE(dims[n_layers] == 1, BBMPC_E_INVALID, "reward model: the last layer must have one output (dims[n_layers] == 1)");
+    for (int l = 0; l < n_layers; ++l) {
+        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
+        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
+    }
+    if (is_normalized) {
+        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
+        for (int i = 0; i < 4; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
+    }
+    REQUIRE(D <= REW_MLP_MAX_IN, BBMPC_E_UNSUPPORTED, "reward model: more than 192 input columns");
+    for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= REW_MLP_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
+    RewMlpDesc d;
+    memset(&d, 0, sizeof(d));
+    MlpDesc shape;                              // what mlp_pack_layer reads: widths and tiles, features in index order
+    memset(&shape, 0, sizeof(shape));
+    d.n_layers = shape.n_layers = n_layers;
+    int hidden_tiles = 1;
+    for (int l = 0; l <= n_layers; ++l) {
+        d.dims[l] = shape.dims[l] = dims[l];
+        d.tiles[l] = shape.tiles[l] = (dims[l] + 15) / 16;
+        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, d.tiles[l]);
+    }
+    d.nw = std::min(16, hidden_tiles);
+    d.mask = input_mask; d.S = S; d.U = U; d.D = D;
+    d.off_a = (input_mask & 1) ? S : 0;
+    d.off_n = d.off_a + ((input_mask & 2) ? U : 0);
+    REQUIRE((size_t)rew_mlp_lds_layout(d).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "reward model: the activation buffers of this network do not fit one CU's LDS");
+    std::vector<float> w4[MLP_MAX_LAYERS], bp[MLP_MAX_LAYERS];
+    for (int l = 0; l < n_layers; ++l) {
+        d.act[l] = acts[l];
+        if (l < n_layers - 1) {
+            std::vector<float> wp;
+            mlp_pack_layer(shape, l, w[l], b[l], wp, w4[l], bp[l]);
+        }
+    }
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));
+    rew_mlp_ready = false;
+    for (int l = 0; l < n_layers - 1; ++l) {
+        upload(d_rw_wp4[l], w4[l]);
+        upload(d_rw_bp[l], bp[l]);
+        d.wp4[l] = d_rw_wp4[l].p;
+        d.bpack[l] = d_rw_bp[l].p;
+    }
+    upload(d_rw_last, std::vector<float>(w[n_layers - 1], w[n_layers - 1] + dims[n_layers - 1]));      // [K][1]
+    d.wlast = d_rw_last.p;
+    d.blast = b[n_layers - 1][0];
+    d.normalized = is_normalized ? 1 : 0;
+    if (is_normalized) {
+        std::vector<float> st(stats[0], stats[0] + D);
+        st.insert(st.end(), stats[1], stats[1] + D);
+        upload(d_rw_stats, st);
+        d.mean_in = d_rw_stats.p;
+        d.std_in = d_rw_stats.p + D;
+        d.mean_r = stats[2][0];
+        d.std_r = stats[3][0];
+    }
+    rew_mlp = d;
+    rew_mlp_ready = true;
+}
+
+static void launch_reward_mlp_lds(const void* fn, size_t lds) {
+    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+}
+
+// The learned model's rollout with a learned reward: Engine::rollout_mlp_user_reward's sequence with the network in place
+// of the user's function -- the MFMA rollout (reward kind REW_NONE) records u_traj and leaves -(penalty) in ra.rewards,
+// k_reward_mlp_traj scores every (candidate, step) row, k_reward_mlp_finish sums the steps.
+void Engine::rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra) {
+    REQUIRE(rew_mlp_ready, BBMPC_E_STATE, "learned reward: call bbmpc_set_reward_mlp before computing");
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    const size_t need = (size_t)ra.H * A * ra.Nst * S, need_r = (size_t)ra.H * A * ra.Nst;
+    if (u_traj.n < need) u_traj.alloc(need);
+    if (d_rw_step.n < need_r) d_rw_step.alloc(need_r);
+    mlp_traj_out = u_traj.p;
+    // BBMPC_PROF_REWARD_MLP: the profiling events go around the scorer below, not around the rollout kernel
+    const bool prof = profiling;
+    if (sw.prof_reward_mlp) profiling = false;
+    try {
+        launch_rollout_mlp(mode, pen, ra, false, nullptr);
+    } catch (...) {
+        mlp_traj_out = nullptr;
+        profiling = prof;
+        throw;
+    }
+    mlp_traj_out = nullptr;
+    profiling = prof;
+    RewMlpTrajArgs q;
+    memset(&q, 0, sizeof(q));
+    q.m = rew_mlp;
+    q.n_pop = ra.n_pop; q.A = A; q.H = ra.H; q.Nst = ra.Nst; q.HU = ra.HU;
+    q.from_ref = mode == SRC_REF ? 1 : 0;
+    q.state = ra.state;
+    q.traj = u_traj.p;
+    q.seq = ra.seq;
+    q.cand = mode == SRC_BUF ? ra.cand : ra.samples;
+    q.step_out = d_rw_step.p;
+    if (mode != SRC_REF) REQUIRE(q.cand, BBMPC_E_STATE, "learned reward over the learned model: no candidate buffer");
+    // steps are independent rows: enough t-chunks that two rounds of workgroups cover the CUs even when the population is a
+    // few tiles (the number of agents plays no part, and the chunking none in the result: the steps are summed afterwards)
+    const int tiles = (ra.n_pop + MLP_TP - 1) / MLP_TP;
+    const int chunks = std::max(1, std::min(ra.H, (512 + tiles - 1) / tiles));
+    q.tchunk = (ra.H + chunks - 1) / chunks;
+    const size_t lds = (size_t)rew_mlp_lds_layout(rew_mlp).total * sizeof(float);
+    launch_reward_mlp_lds((const void*)k_reward_mlp_traj, lds);
+    dim3 grid(tiles, A, (ra.H + q.tchunk - 1) / q.tchunk), block(rew_mlp.nw * 64);
+    if (sw.prof_reward_mlp) {
+        dominant_kernel = "k_reward_mlp_traj";
+        prof_begin();
+    }
+    hipLaunchKernelGGL(k_reward_mlp_traj, grid, block, lds, stream, q);
+    if (sw.prof_reward_mlp) prof_end();
+    hipLaunchKernelGGL(k_reward_mlp_finish, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, ra.n_pop, A, ra.H, ra.Nst,
+                       (const float*)d_rw_step.p, ra.rewards);
+    HIP_CHECK(hipGetLastError());
+}
+
+void Engine::reward_mlp_rows(const RewMlpRowsArgs& rows) {
+    REQUIRE(rew_mlp_ready, BBMPC_E_STATE, "learned reward: call bbmpc_set_reward_mlp before computing");
+    RewMlpRowsArgs q = rows;
+    q.m = rew_mlp;
+    const size_t lds = (size_t)rew_mlp_lds_layout(rew_mlp).total * sizeof(float);
+    launch_reward_mlp_lds((const void*)k_reward_mlp_rows, lds);
+    hipLaunchKernelGGL(k_reward_mlp_rows, dim3((q.B + MLP_TP - 1) / MLP_TP), dim3(rew_mlp.nw * 64), lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
+// bbmpc_predict_trajectories with a learned reward: the states from k_traj_mlp (they do not depend on the reward), then ONE
+// launch of the rows frame over the B * Hq (row, step) pairs of states_out [B, Hq, S]
+void Engine::traj_mlp_reward_mlp(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out) {
+    REQUIRE(rew_mlp_ready, BBMPC_E_STATE, "learned reward: call bbmpc_set_reward_mlp before computing");
+    REQUIRE((long)batch * horizon < (1L << 31), BBMPC_E_UNSUPPORTED, "trajectory prediction with a learned reward: more than 2^31 (row, step) pairs");
+    float* so = d_states_out;
+    if (!so) {
+        const size_t ns = (size_t)batch * horizon * S;
+        if (d_rw_states.n < ns) d_rw_states.alloc(ns);
+        so = d_rw_states.p;
+    }
+    traj_mlp(d_states, d_seq, batch, horizon, so, nullptr);
+    RewMlpRowsArgs q;
+    memset(&q, 0, sizeof(q));
+    q.B = batch * horizon;
+    q.period = horizon; q.cur_shift = 1;
+    q.first = d_states;
+    q.cur = so; q.cur_stride = S;
+    q.act = d_seq; q.act_stride = U;
+    q.nxt = so; q.nxt_stride = S;
+    q.out = d_rewards_out;
+    reward_mlp_rows(q);
+}
+
 }  // namespace bbmpc
+
+extern "C" int bbmpc_set_reward_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
+                                    const float* const* b, int32_t input_mask, int32_t is_normalized, const float* const* stats) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_reward_mlp(n_layers, dims, acts, w, b, input_mask, is_normalized, stats);
+    API_END
+}

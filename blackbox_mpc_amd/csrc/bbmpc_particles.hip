@@ -20,6 +20,8 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     for (int s = 0; s < S; ++s)
         REQUIRE(std::isfinite(sigma[s]) && sigma[s] >= 0.0f, BBMPC_E_INVALID, "process noise sigma must be finite and >= 0");
     REQUIRE(std::isfinite(kappa), BBMPC_E_INVALID, "risk_kappa must be finite");
+    REQUIRE(cfg.reward != BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
+            "particles with a learned reward model (BBMPC_REW_MLP): the particle evaluator scores built-in and HIP-source rewards only");
     // a HIP-source reward scores the learned model's particles; the analytic pendulum keeps its built-in rewards
     REQUIRE((cfg.reward != BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_MLP) && cfg.dynamics != BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
             "particles with HIP-source or callback dynamics, or with a user reward beside the built-in pendulum model: a user reward "

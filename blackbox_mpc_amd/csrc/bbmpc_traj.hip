@@ -6,6 +6,7 @@
 //   learned MLP, built-in reward           k_traj_mlp (kernels_mlp_traj.hpp, launched from bbmpc_mlp.hip), one launch
 //   HIP-source dynamics and / or reward    bbmpc_user_traj (rtc.hpp), compiled on the handle's first prediction, one launch
 //   on an analytic model (no callbacks)    (Engine::traj_user_fused, bbmpc_user.hip)
+//   learned MLP, learned reward            k_traj_mlp for the states + k_reward_mlp_rows (kernels_reward_mlp.hpp), two launches
 //   torch callbacks; learned model with    step by step: the handle's row kernels / callbacks Hq times
 //   a transform or a HIP-source reward
 // ... and plan readback (bbmpc_set_keep_plan / bbmpc_get_plan).
@@ -43,6 +44,10 @@ void Engine::predict_trajectories_dev(const float* d_states, const float* d_seq,
     if (cfg.dynamics == BBMPC_DYN_MLP && !has_xform() && !d_rewards_out) {
         // states only: a learned model's states do not depend on the reward, whatever kind the handle was created with
         traj_mlp(d_states, d_seq, batch, horizon, d_states_out, nullptr);
+        return;
+    }
+    if (cfg.reward == BBMPC_REW_MLP) {                    // learned reward: the states, then one launch of the scorer's rows frame
+        traj_mlp_reward_mlp(d_states, d_seq, batch, horizon, d_states_out, d_rewards_out);
         return;
     }
     if (user_path() && cfg.dynamics != BBMPC_DYN_MLP && !user_callbacks()) {

@@ -138,6 +138,8 @@ void Engine::set_transform_source(int kind, const char* src) {
     const bool clear = !src || !*src;
     const bool inverse = kind == USER_KIND_INVERSE_TRANSFORM;
     if (inverse && !clear) {
+        REQUIRE(cfg.reward != BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
+                "an inverse target transform beside a learned reward model (BBMPC_REW_MLP): the transform rollout has no learned-reward form");
         REQUIRE(cfg.dynamics == BBMPC_DYN_MLP || cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
                 "an inverse target transform needs a learned-model (BBMPC_DYN_MLP) or BBMPC_DYN_USER handle; the built-in pendulum "
                 "model keeps next = dev + state");
@@ -215,6 +217,18 @@ void Engine::dynamics_rows(const float* d_states, const float* d_actions, int as
 // total (+)= reward_function(cur, actions, next) on [batch] rows   deterministic.py:65-66, 105-127
 void Engine::reward_rows(const float* d_cur, const float* d_next, const float* d_actions, int astride, int batch, float* d_total,
                          int accumulate, int t) {
+    if (cfg.reward == BBMPC_REW_MLP) {                                    // the rows frame of kernels_reward_mlp.hpp: one reward per row
+        REQUIRE(!accumulate, BBMPC_E_INVALID, "internal: a learned reward is never scored step by step");
+        RewMlpRowsArgs q;
+        memset(&q, 0, sizeof(q));
+        q.B = batch;
+        q.cur = d_cur; q.cur_stride = S;
+        q.act = d_actions; q.act_stride = astride;
+        q.nxt = d_next; q.nxt_stride = S;
+        q.out = d_total;
+        reward_mlp_rows(q);
+        return;
+    }
     if (cfg.reward == BBMPC_REW_USER && user_reward.cb) {
         const float* acts_c = dense_actions(d_actions, astride, batch);
         if (u_cb_rew.n < (size_t)batch) u_cb_rew.alloc((size_t)batch);

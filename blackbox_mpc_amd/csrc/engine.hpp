@@ -29,6 +29,7 @@
 #include "kernels_mlp_wave.hpp"
 #include "kernels_opt.hpp"
 #include "kernels_refit.hpp"
+#include "kernels_reward_mlp.hpp"
 #include "kernels_rollout.hpp"
 #include "kernels_tail.hpp"
 #include "kernels_user.hpp"
@@ -164,6 +165,7 @@ struct Engine {
         bool zero_copy = true;         // !BBMPC_NO_ZERO_COPY
         bool mlp_no_half_tail = false; // BBMPC_MLP_NO_HALF_TAIL: keep hidden features in index order (no skipped MFMAs)
         bool host_poll = true;         // !BBMPC_NO_HOST_POLL: host calls return on the kernel's own completion word
+        bool prof_reward_mlp = false;  // BBMPC_PROF_REWARD_MLP: bbmpc_set_profiling brackets k_reward_mlp_traj instead of the rollout kernel in front of it
         bool dbg = false;              // BBMPC_DBG
     } sw;
 
@@ -324,8 +326,20 @@ struct Engine {
     void rollout_mlp_xform(int mode, bool pen, RolloutArgs& ra);
     void mlp_xform_rows(const float* d_states, const float* d_actions, int astride, int batch, float* d_next);
     DevBuf<float> u_xin, u_xraw;       // learned model + transform, step-wise: processed inputs / de-normalised outputs
-    bool user_path() const { return cfg.reward == BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_USER || has_xform(); }
-    int builtin_reward_kind() const { return cfg.reward == BBMPC_REW_USER ? REW_NONE : cfg.reward; }
+    // (a learned reward model, BBMPC_REW_MLP, is routed exactly as a HIP-source reward over the learned model is)
+    bool user_path() const { return cfg.reward == BBMPC_REW_USER || cfg.reward == BBMPC_REW_MLP || cfg.dynamics == BBMPC_DYN_USER || has_xform(); }
+    int builtin_reward_kind() const { return (cfg.reward == BBMPC_REW_USER || cfg.reward == BBMPC_REW_MLP) ? REW_NONE : cfg.reward; }
+    // learned reward model (bbmpc_set_reward_mlp; bbmpc_mlp.hip, kernels_reward_mlp.hpp): the MFMA
+    // rollout records the trajectory as for a HIP-source reward, k_reward_mlp_traj + k_reward_mlp_finish score it; the
+    // one-step calls and bbmpc_predict_trajectories go through k_reward_mlp_rows
+    bool rew_mlp_ready = false;
+    RewMlpDesc rew_mlp;
+    DevBuf<float> d_rw_wp4[MLP_MAX_LAYERS], d_rw_bp[MLP_MAX_LAYERS], d_rw_last, d_rw_stats, d_rw_step, d_rw_states;
+    void set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b, int input_mask,
+                        int is_normalized, const float* const* stats);
+    void rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra);
+    void reward_mlp_rows(const RewMlpRowsArgs& rows);
+    void traj_mlp_reward_mlp(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void set_user_source(int kind, const char* src, int nparams = 0);
     void set_user_callback(int kind, bbmpc_rows_callback fn, void* user);
     // runtime parameters of a parameterised user reward / dynamics (bbmpc_set_user_params): [A][P] on the device -- a

@@ -103,6 +103,28 @@ class Engine:
             L.check(L.lib.bbmpc_set_mlp(self._h, n, dims_a, acts_a, wp, bp, 0, None))
         self._mlp_last_hidden = dims[-2]                 # rows of a log-variance head's kernel (set_mlp_logvar_head)
 
+    def set_reward_mlp(self, weights, biases, activations, input_mask=7, stats=None):
+        """Learned reward model of a DYN_MLP + REW_MLP handle (bbmpc_set_reward_mlp): Dense kernels [in, out] / biases [out]
+        ending in one output, any ACT_* code per layer; input_mask bit 0 = s_t, 1 = a_t, 2 = s_{t+1} (concatenated in that
+        order); stats = (mean_in [D], std_in [D], mean_r, std_r) or None."""
+        n = len(weights)
+        ws = [L.f32c(w) for w in weights]
+        bs = [L.f32c(np.asarray(b).reshape(-1)) for b in biases]
+        dims = [ws[0].shape[0]] + [w.shape[1] for w in ws]
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            if w.ndim != 2 or w.shape[0] != dims[i] or b.shape != (w.shape[1],):
+                raise ValueError("layer %d: kernel must be [in,out] and bias [out]" % i)
+        dims_a = (ctypes.c_int32 * (n + 1))(*dims)
+        acts_a = (ctypes.c_int32 * n)(*[int(a) for a in activations])
+        wp = (ctypes.c_void_p * n)(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bs])
+        if stats is not None:
+            st = [L.f32c(np.asarray(s).reshape(-1)) for s in stats]
+            sp = (ctypes.c_void_p * 4)(*[s.ctypes.data for s in st])
+            L.check(L.lib.bbmpc_set_reward_mlp(self._h, n, dims_a, acts_a, wp, bp, int(input_mask), 1, sp))
+        else:
+            L.check(L.lib.bbmpc_set_reward_mlp(self._h, n, dims_a, acts_a, wp, bp, int(input_mask), 0, None))
+
     def set_mlp_ensemble(self, members):
         """Model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble): `members` is a list of (weights, biases)
         pairs or of objects with `.weights` / `.biases`, each of the shape of the model set_mlp installed; particle p

@@ -51,6 +51,11 @@ class OptimizerBase:
         if eng.__dict__.get("_dyn_version") != (getattr(h._dynamics_function, "_version", 0), h._version):
             from ..trajectory_evaluators.deterministic import configure_dynamics
             configure_dynamics(eng, h)
+        if eng.cfg.reward == L.REW_MLP:               # a learned reward model that was refitted / reloaded, likewise
+            rf = self._trajectory_evaluator._reward_function
+            if eng.__dict__.get("_rew_version") != getattr(rf, "_version", 0):
+                from ..trajectory_evaluators.deterministic import configure_reward
+                configure_reward(eng, rf)
         return eng
 
     def _require_engine_and_params(self):

@@ -80,6 +80,10 @@ def plugin_kinds(reward_function, handler):
     dk = getattr(dp, "_bbmpc_dynamics_kind", None)
     if dk is None:
         dk = L.DYN_USER
+    if rk == L.REW_MLP and (dk != L.DYN_MLP or getattr(handler, "_inverse_transform_targets_func", None) is not None):
+        raise NotImplementedError("a LearnedRewardMLP scores the rollouts of a learned model: it needs a DeterministicMLP (or "
+                                  "EnsembleMLP / ProbabilisticMLP) dynamics function without an inverse target transform, not %s"
+                                  % type(dp).__name__)
     hip_true_model = dk == L.DYN_PENDULUM or (dk == L.DYN_USER and isinstance(getattr(dp, "hip_source", None), str))
     if hip_true_model and not handler._is_true_model:
         raise Exception("%s must be used with true_model=True" % type(dp).__name__)
@@ -122,6 +126,11 @@ def configure_dynamics(engine, handler):
 
 def configure_reward(engine, reward_function, handler=None):
     """Compile + attach the user's reward device function (or its torch callback), once per engine."""
+    if engine.cfg.reward == L.REW_MLP:                # a LearnedRewardMLP: uploaded now and again whenever it was refitted / reloaded
+        engine.set_reward_mlp(reward_function.weights, reward_function.biases, reward_function.activation_codes,
+                              reward_function.input_mask, reward_function.normalization_stats())
+        engine._rew_version = getattr(reward_function, "_version", 0)
+        return
     if engine.cfg.reward != L.REW_USER:
         return
     from ..utils import device_functions as DF
@@ -143,6 +152,11 @@ def dynamics_stale(engine, handler):
     return getattr(engine, "_dyn_version", None) != (getattr(dyn, "_version", 0), handler._version)
 
 
+def reward_stale(engine, reward_function):
+    """A learned reward model (REW_MLP) whose weights changed since they were uploaded; never true for the other kinds."""
+    return engine.cfg.reward == L.REW_MLP and engine.__dict__.get("_rew_version") != getattr(reward_function, "_version", 0)
+
+
 class DeterministicTrajectoryEvaluator(EvaluatorBase):
     def __init__(self, reward_function, system_dynamics_handler, quirks=0):
         super().__init__(reward_function=reward_function, system_dynamics_handler=system_dynamics_handler, name=None)
@@ -162,6 +176,8 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
             self._engines[key] = eng
         if dynamics_stale(eng, h):
             configure_dynamics(eng, h)
+        if reward_stale(eng, self._reward_function):
+            configure_reward(eng, self._reward_function)
         if eng._param_fns:
             from ..utils.device_functions import sync_user_params
             sync_user_params(eng)

@@ -48,6 +48,9 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
         the natural choice.  risk_kappa > 0 prefers candidates whose return varies little over the particles.
         risk_alpha in (0, 1] scores the mean of the ceil(risk_alpha * num_particles) worst returns instead (CVaR; not
         together with risk_kappa != 0)."""
+        if getattr(reward_function, "_bbmpc_reward_kind", None) == L.REW_MLP:
+            raise NotImplementedError("ParticleTrajectoryEvaluator does not score a LearnedRewardMLP yet: the particle rollouts take "
+                                      "built-in and HIP-source rewards (use DeterministicTrajectoryEvaluator with a learned reward)")
         super().__init__(reward_function, system_dynamics_handler, quirks=quirks)
         p = int(num_particles)
         if not 1 <= p <= 64:

@@ -18,10 +18,11 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
                                      tf_writer=None, save_model_frequency=1, saved_model_dir=None,
                                      exploration_noise=False, epochs=30, learning_rate=1e-3, validation_split=0.2,
                                      batch_size=128, start_episode=0, train_args=None, multistep_horizon=None,
-                                     **optimizer_args):
+                                     reward_model=None, reward_train_args=None, **optimizer_args):
     """Same arguments as the reference (+ `train_args`, a dict forwarded to SystemDynamicsHandler.train, and
     `multistep_horizon`: every fit is followed by the open-loop error over that many steps, kept as
-    `handler.multistep_rmse`; None = not computed).
+    `handler.multistep_rmse`; None = not computed; and `reward_model`, a LearnedRewardMLP refitted in every iteration from
+    the rewards the rollouts collect -- pass the same object as `reward_function` to plan with it).
     Returns (system_dynamics_handler, refinement_policy)."""
     train_args = dict(train_args or {})
     if number_of_initial_rollouts > 0:
@@ -32,7 +33,8 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
             validation_split=validation_split, batch_size=batch_size, is_normalized=is_normalized,
             nn_optimizer=nn_optimizer, tf_writer=tf_writer, exploration_noise=exploration_noise, log_dir=log_dir,
             save_model_frequency=save_model_frequency, saved_model_dir=saved_model_dir,
-            multistep_horizon=multistep_horizon, **train_args)
+            multistep_horizon=multistep_horizon, reward_model=reward_model,
+            reward_train_args=reward_train_args, **train_args)
         logging.info("Trained initial system model")
     elif system_dynamics_handler is None:
         system_dynamics_handler = SystemDynamicsHandler(
@@ -53,5 +55,5 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
             is_normalized=is_normalized, nn_optimizer=nn_optimizer, tf_writer=tf_writer,
             exploration_noise=exploration_noise,
             start_episode=start_episode + (number_of_rollouts_for_refinement * i), multistep_horizon=multistep_horizon,
-            **train_args)
+            reward_model=reward_model, reward_train_args=reward_train_args, **train_args)
     return system_dynamics_handler, refinement_policy

@@ -60,6 +60,7 @@ extern "C" {
 #define BBMPC_REW_PENDULUM 1
 #define BBMPC_REW_CHEETAH  2
 #define BBMPC_REW_USER     3   /* caller-supplied: HIP source (bbmpc_set_reward_source) or a device-memory callback */
+#define BBMPC_REW_MLP      4   /* learned: a reward network (bbmpc_set_reward_mlp); with BBMPC_DYN_MLP only */
 
 /* Dense activations (tutorials use tf.math.tanh and None); the TF 2.0 definitions, fixed slopes and constants */
 #define BBMPC_ACT_NONE         0
@@ -179,6 +180,30 @@ int bbmpc_set_stream_default(bbmpc_handle h);   /* the legacy default (NULL) str
 int bbmpc_set_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* activations,
                   const float* const* weights, const float* const* biases,
                   int32_t is_normalized, const float* const* stats);
+
+/* Learned reward model for a handle created with BBMPC_DYN_MLP + BBMPC_REW_MLP: a Dense stack r(s_t, a_t, s_{t+1}) fitted
+ * next to the dynamics (the reference takes any callable as reward_function, trajectory_evaluators/deterministic.py:13-18;
+ * a network is one).  Layouts as bbmpc_set_mlp: Dense kernels [in, out] row-major, biases [out], dims has n_layers + 1
+ * entries, dims[n_layers] == 1, any BBMPC_ACT_* code per layer.  input_mask picks the network's inputs: bit 0 = s_t,
+ * bit 1 = a_t, bit 2 = s_{t+1}, at least one; the selected blocks are concatenated in that order and dims[0] is their total
+ * width D.  stats = {mean_in[D], std_in[D], mean_r[1], std_r[1]} or NULL when is_normalized == 0: the input is normalised
+ * as bbmpc_process_input normalises, x = (x - mean_in) / (std_in + 1e-7), and the reward is y * std_r + mean_r.
+ * The handle is routed exactly as a BBMPC_DYN_MLP handle with a HIP-source BBMPC_REW_USER reward: the MFMA rollout records
+ * the state after every step and a second MFMA kernel scores the trajectory -- sum over t in ascending order, NaN -> -1e6
+ * per trajectory, added to -(bound penalty); a_t is the feasible (clipped) action where the optimizer clips.  Control steps
+ * of all six optimizers, bbmpc_evaluate[_dev], bbmpc_evaluate_next_reward, the record's reward, bbmpc_predict_trajectories,
+ * bbmpc_rollout_episode, trace / keep_plan / elite carry / sampling correlation and agent and population shards work; there
+ * are no resident, fused or graph-replayed forms, BBMPC_USER_STEPWISE is ignored and BBMPC_FIX_Q1_REWARD_ARG_ORDER does not
+ * apply (the network always sees (s_t, a_t, s_{t+1})).  Equal calls give equal bits, whatever the number of agents.
+ * Calling it again replaces the network.  Refused before anything is allocated -- BBMPC_E_UNSUPPORTED: n_layers > 8, a
+ * hidden width > 512, D > 192; BBMPC_E_INVALID: NULL pointers, n_layers < 1, a width < 1, an unknown activation,
+ * input_mask outside [1, 7], dims[0] != D, dims[n_layers] != 1, is_normalized without stats; BBMPC_E_STATE: not a
+ * BBMPC_REW_MLP handle.  Computing before the network is set fails with BBMPC_E_STATE.  BBMPC_E_UNSUPPORTED as well:
+ * bbmpc_create with BBMPC_REW_MLP beside analytic or user dynamics, bbmpc_set_inverse_transform_source and
+ * bbmpc_set_particles (num_particles > 0) on such a handle. */
+int bbmpc_set_reward_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* activations,
+                         const float* const* weights, const float* const* biases, int32_t input_mask,
+                         int32_t is_normalized, const float* const* stats);
 
 /* User-supplied plug-ins.  The reference takes ANY callable as reward_function / dynamics_function
  * (trajectory_evaluators/deterministic.py:13-18; called at :65-66 as reward(current_state, actions, next_state) and at
