@@ -12,6 +12,8 @@
 //   (cem.py:74-136, pi2.py:58-96, random_search.py:38-48) -> DeterministicTrajectoryEvaluator.__call__
 //   (deterministic.py:26-77) -> PendulumTrueModel / pendulum_reward_function (utils/pendulum.py).
 #pragma once
+#include <type_traits>
+
 #include "kernels_opt.hpp"
 #include "kernels_refit.hpp"
 #include "kernels_rollout.hpp"
@@ -30,7 +32,7 @@ struct FusedArgs {
     int agent_offset;
     int fix_q1, fix_q7, add_noise;
     int warm_start;          // CEM: BBMPC_FIX_Q2 (keep the mean across control steps)
-    int balance;             // progress-balanced wave priorities in the rollout (BBMPC_BALANCE, default on)
+    int balance;             // progress-balanced wave priorities in the rollout (BBMPC_BALANCE, default off)
     unsigned* done_flag;     // optional completion counter in signal memory (see the kernel's tail), else null
     unsigned* done_count;
     unsigned done_value;
@@ -207,12 +209,23 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             const uint32_t rstream = (OPT == FOPT_RS) ? 2u : 1u;
             // ILP independent trajectories per lane: with half as many waves each SIMD runs a single wave whose two
             // recurrences interleave in program order, instead of two waves fighting over issue slots.
+            // quirk Q1's choice of the action-cost term is uniform for the launch: ONE branch here and a rollout body instantiated
+            // for either value, instead of a second fma and a select in every model step (the op-for-op model resolves the
+            // quirk inside its reward function: a single body)
+            auto with_q1 = [&](auto&& body) {
+                if constexpr (FASTM) {
+                    if (p.fix_q1 != 0) { body(std::true_type{}); return; }
+                }
+                body(std::false_type{});
+            };
             if constexpr (OPT == FOPT_SPSA) {
                 // SPSA (spsa.py:61-107): theta +- c_k * delta with delta in {-1,+1}; both candidates of a particle are
                 // rolled out by the same lane (two independent recurrences: four chains per SIMD at N = 500).  The
                 // Rademacher draws stay in LDS (samp) for the gradient estimate.
                 const float ck = p.spsa_ck[it];
                 const int nb4 = (p.H + 3) >> 2;
+                with_q1([&](auto Q1c) {
+                constexpr bool Q1 = decltype(Q1c)::value;
                 for (int n = tid; n < p.N; n += nthr) {
                     Roller<FASTM> rp, rm;
                     rp.init(p.fix_q1 != 0, s0, s1, s2);
@@ -254,8 +267,8 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                                 pp = pp + dp * dp;
                                 pm = pm + dm * dm;
                                 samp[(size_t)t * p.Nst + n] = d[i];
-                                rp.step_acc(xpf);
-                                rm.step_acc(xmf);
+                                rp.template step_acc_q1<Q1>(xpf);
+                                rm.template step_acc_q1<Q1>(xmf);
                             }
                         }
                     }
@@ -270,6 +283,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     }
                     rew[n] = r_p - r_m;
                 }
+                });
             } else if constexpr (INJ == 2) {
                 // Draws prefetched by idle CUs (k_noise_fill): one float4 = one Philox block = 4 steps of this trajectory.
                 // Loads run TWO blocks (8 steps, ~2 us) ahead of their use so that L2/HBM latency never reaches the
@@ -279,10 +293,21 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 int* prog = (int*)red;                             // per-wave progress (red[] is idle during the rollout)
                 const int wave = tid >> 6, lane = tid & 63;
                 const bool balance = p.balance != 0 && nw > 4 && nw <= 64 && p.N <= nthr;
+                // The rollout is bound by instruction issue, so what is uniform for the launch is decided ONCE
+                // here and not once per model step: quirk Q1's choice of the action-cost term (Q1c) and the row stride of
+                // samp[t][n] (NSTc: a compile-time stride turns the sample stores' addresses into immediate offsets of one
+                // per-trajectory base; 0 = the run-time stride p.Nst).
+                auto rollout = [&](auto Q1c, auto NSTc) {
+                constexpr bool Q1 = decltype(Q1c)::value;
+                constexpr int NSTC = decltype(NSTc)::value;
+                const size_t nst = NSTC ? (size_t)NSTC : (size_t)p.Nst;
+                const int nbp = HUp >> 2;                          // float4 blocks of the padded mean[] / sigma[]
                 for (int n = tid; n < p.N; n += nthr) {
                     Roller<FASTM> roll;
                     roll.init(p.fix_q1 != 0, s0, s1, s2);
                     float pen = 0.0f;
+                    float* sp = samp + n;                          // compile-time stride: samp[4b + row][n] = sp[row * nst] for the block b it
+                                                                   // stands at; run-time stride: the row of the next model step
                     // (a GLOBAL pointer, said so: inj_s may have come out of the mailbox, and as a generic pointer its loads are
                     // flat loads -- which count on the LDS counter too, so that every LDS wait of the loop below waited for the
                     // block it had just prefetched: one memory round trip per eight model steps)
@@ -290,51 +315,55 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     typedef const __attribute__((address_space(1))) gvec4* gvec4p;
                     const gvec4p mine = (gvec4p)(inj4 + noise_block_index(it, p.A, a, p.Nst, n, Q));
                     auto ld = [&](int b) { const gvec4 v = mine[min(b, Q - 1)]; return make_float4(v.x, v.y, v.z, v.w); };
-                    auto step1 = [&](int t, float xi) {
-                        float x = (OPT == FOPT_RS) ? xi * (hi - lo) + lo : xi * sigma[t] + mean[t];
+                    // sigma[4b .. 4b + 3] / mean[4b .. 4b + 3] (16-byte aligned, padded to a multiple of four) are read ONE block ahead
+                    // of the model steps that use them: behind the previous block's recurrence, not in front of their own, where
+                    // the LDS round trip stopped the chain at the top of every block.  (past the last block: the last one again)
+                    struct SigMean { float4 sg, mn; };
+                    auto rd = [&](int b) {
+                        SigMean r;
+                        if (OPT == FOPT_RS) {
+                            r.sg = r.mn = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        } else {
+                            const int bb = min(b, nbp - 1);
+                            r.sg = *reinterpret_cast<const float4*>(sigma + 4 * bb);
+                            r.mn = *reinterpret_cast<const float4*>(mean + 4 * bb);
+                        }
+                        return r;
+                    };
+                    auto action = [&](float xi, float sg, float mn) { return (OPT == FOPT_RS) ? xi * (hi - lo) + lo : xi * sg + mn; };
+                    // one model step on action x, row `row` (a constant at every call) of the block sp stands at
+                    auto step1 = [&](int row, float x) {
                         if (OPT == FOPT_PI2) {
                             const float xf = clipf(x, lo, hi);
                             const float d = x - xf;
                             pen = pen + d * d;
                             x = xf;
                         }
-                        samp[(size_t)t * p.Nst + n] = x;
-                        roll.step_acc(x);
-                    };
-#if BBMPC_FUSED_ACTIONS_AHEAD
-                    // a block's four actions are formed (sigma[t], mean[t] read from LDS) BEFORE its model steps: inside the
-                    // steps the reads would sit between the sine and the angle update of the pendulum's recurrence
-                    auto block4 = [&](const float4& z, int b) {
-                        const float zz[4] = {z.x, z.y, z.z, z.w};
-                        float x[4];
-                        if (OPT == FOPT_RS) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) x[i] = zz[i] * (hi - lo) + lo;
+                        if constexpr (NSTC != 0) {
+                            sp[(size_t)row * nst] = x;           // an immediate offset from the block's base
                         } else {
-                            // (a full block: t = 4b .. 4b + 3 < H; mean / sigma are 16-byte aligned and padded to a multiple of four)
-                            const float4 sg = *reinterpret_cast<const float4*>(sigma + 4 * b), mn = *reinterpret_cast<const float4*>(mean + 4 * b);
-                            x[0] = zz[0] * sg.x + mn.x; x[1] = zz[1] * sg.y + mn.y; x[2] = zz[2] * sg.z + mn.z; x[3] = zz[3] * sg.w + mn.w;
+                            *sp = x;                             // run-time stride: the pointer walks the rows
+                            sp += nst;
                         }
+                        roll.template step_acc_q1<Q1>(x);
+                    };
+                    // Block b: its four actions are formed from its draws z and from m = sigma / mean of block b BEFORE its model
+                    // steps (inside the steps they would sit between the sine and the angle update of the recurrence).  That is
+                    // the last use of both, so the loads of block b + 2's draws and of block b + 1's sigma / mean are issued
+                    // right there INTO THE SAME REGISTERS and run beside this block's recurrence: no copy at a loop's foot, and
+                    // neither the memory nor the LDS round trip ever stands in front of a model step.
+                    SigMean m = rd(0);
+                    auto block4 = [&](float4& z, int b, int row0, bool more) {
+                        float x[4] = {action(z.x, m.sg.x, m.mn.x), action(z.y, m.sg.y, m.mn.y), action(z.z, m.sg.z, m.mn.z), action(z.w, m.sg.w, m.mn.w)};
+#if BBMPC_FUSED_ACTIONS_AHEAD
 #pragma unroll
                         for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(x[i]));
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float v = x[i];
-                            if (OPT == FOPT_PI2) {
-                                const float xf = clipf(v, lo, hi);
-                                const float d = v - xf;
-                                pen = pen + d * d;
-                                v = xf;
-                            }
-                            samp[(size_t)(4 * b + i) * p.Nst + n] = v;
-                            roll.step_acc(v);
-                        }
-                    };
-#else
-                    auto block4 = [&](const float4& z, int b) {
-                        step1(4 * b + 0, z.x); step1(4 * b + 1, z.y); step1(4 * b + 2, z.z); step1(4 * b + 3, z.w);
-                    };
 #endif
+                        if (more) z = ld(b + 2);                 // draws: two blocks (8 steps, ~2 us) ahead of their use
+                        m = rd(b + 1);                           // (also what the remainder steps behind the last block use)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) step1(row0 + i, x[i]);
+                    };
                     float4 c0, c1;
                     if (n == tid) { c0 = make_float4(pf0.x, pf0.y, pf0.z, pf0.w); c1 = make_float4(pf1.x, pf1.y, pf1.z, pf1.w); }   // fetched an iteration ago
                     else { c0 = ld(0); c1 = ld(1); }
@@ -348,7 +377,6 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     // wave publishes its block counter in LDS and lowers its priority while it is ahead of a SIMD mate.
                     if (balance && lane == 0) prog[wave] = 0;
                     for (; b + 1 < nblk; b += 2) {
-                        const float4 n0 = ld(b + 2), n1 = ld(b + 3);
                         if (balance) {
                             if (lane == 0) prog[wave] = b;
                             int behind = b;
@@ -356,18 +384,18 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                             if (behind < b) __builtin_amdgcn_s_setprio(0);
                             else __builtin_amdgcn_s_setprio(2);
                         }
-                        block4(c0, b);
-                        block4(c1, b + 1);
-                        c0 = n0; c1 = n1;
+                        block4(c0, b, 0, true);
+                        block4(c1, b + 1, 4, true);
+                        if constexpr (NSTC != 0) sp += 8 * nst;
                     }
                     if (balance) {
                         if (lane == 0) prog[wave] = 1 << 30;
                         __builtin_amdgcn_s_setprio(0);
                     }
-                    if (b < nblk) { block4(c0, b); c0 = c1; ++b; }
-                    if (rem > 0) step1(4 * b + 0, c0.x);
-                    if (rem > 1) step1(4 * b + 1, c0.y);
-                    if (rem > 2) step1(4 * b + 2, c0.z);
+                    if (b < nblk) { block4(c0, b, 0, false); c0 = c1; ++b; if constexpr (NSTC != 0) sp += 4 * nst; }
+                    if (rem > 0) step1(0, action(c0.x, m.sg.x, m.mn.x));
+                    if (rem > 1) step1(1, action(c0.y, m.sg.y, m.mn.y));
+                    if (rem > 2) step1(2, action(c0.z, m.sg.z, m.mn.z));
                     float tot = roll.total();
                     if (tot != tot) tot = -1.0e6f;                                   // deterministic.py:75-77
                     if (OPT == FOPT_PI2) {
@@ -376,7 +404,18 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     }
                     rew[n] = tot;
                 }
+                };
+                // (SAMPLES_LDS, Nst = 512 -- populations of 449 .. 512: the whole array lies within a ds_write's 64 KB of
+                // immediate offset up to H = 31, and the compiler falls back to address arithmetic by itself beyond)
+                auto rollout_q1 = [&](auto NSTc) { with_q1([&](auto Q1c) { rollout(Q1c, NSTc); }); };
+                bool rolled = false;
+                if constexpr (SAMPLES_LDS) {
+                    if (p.Nst == 512) { rollout_q1(std::integral_constant<int, 512>{}); rolled = true; }
+                }
+                if (!rolled) rollout_q1(std::integral_constant<int, 0>{});
             } else
+            with_q1([&](auto Q1c) {
+            constexpr bool Q1 = decltype(Q1c)::value;
             for (int n0 = tid; n0 < p.N; n0 += ILP * nthr) {
                 int nn[ILP];
                 bool live[ILP];
@@ -418,7 +457,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                         x = xf;
                     }
                     if (live[q]) samp[(size_t)t * p.Nst + nn[q]] = x;
-                    roll[q].step_acc(x);     // (the H-step sum is the roller's: the same form as the prefetched-draws path above, bit for bit)
+                    roll[q].template step_acc_q1<Q1>(x);     // (the H-step sum is the roller's: the same form as the prefetched-draws path above, bit for bit)
                 };
 #pragma unroll
                 for (int q = 0; q < ILP; ++q) gen(q, 0);
@@ -449,6 +488,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     if (live[q]) rew[nn[q]] = tot;
                 }
             }
+            });
 #ifdef BBMPC_KERNEL_DBG
             if (p.dbg && a == 0 && it == 0 && (tid & 63) == 0) dbg_lds[24 + (tid >> 6) % 8] = (long long)wall_clock64();
 #endif

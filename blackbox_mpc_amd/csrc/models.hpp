@@ -180,7 +180,10 @@ struct PendulumTurnModel {
     // sums of squares (one fma each per step) and put together once in total() -- nine instructions per step less in the
     // persistent kernels' rollout, which is instruction-issue bound (two waves per SIMD running this recurrence).  Float32
     // rounding differs from the step-by-step sum at the 1e-7 relative level, the class of the reference's own.
-    __device__ __forceinline__ void step_acc(float u) {
+    // step_acc_q1<Q1>: the quirk-Q1 flag as a compile-time value, for a rollout whose caller has branched on it once per
+    // launch (the run-time form below spends a second fma and a select per step on a choice made before the launch)
+    template <bool Q1>
+    __device__ __forceinline__ void step_acc_q1(float u) {
         constexpr float C = 0.05f * BBMPC_INV_TWO_PI_F;
         const float b = fmaf(0.15f, u, thd);
         const float a = fmaf(b, C, phi);
@@ -194,9 +197,13 @@ struct PendulumTurnModel {
         const float n2 = (nthd - thd) + thd;
         q_ang = fmaf(phi0, phi0, q_ang);
         q_thd = fmaf(thd, thd, q_thd);
-        q_act = fix_q1 ? fmaf(u, u, q_act) : fmaf(n2, n2, q_act);
+        q_act = Q1 ? fmaf(u, u, q_act) : fmaf(n2, n2, q_act);
         q_n += 1;
         thd = n2;
+    }
+    __device__ __forceinline__ void step_acc(float u) {
+        if (fix_q1) step_acc_q1<true>(u);
+        else step_acc_q1<false>(u);
     }
     __device__ __forceinline__ float total() const {
         const float ss = fix_q1 ? q_act : (float)q_n + q_act;               // sum(next_state^2) = 1 + newthdot^2 per step (quirk Q1)
@@ -268,6 +275,9 @@ struct Roller<false> {
     // the H-step sum kept by the roller (Roller<true> has a cheaper form of it)
     float acc_ = 0.0f;
     __device__ __forceinline__ void step_acc(float u) { acc_ = acc_ + step(u); }
+    // (the strict form resolves the flag inside the reward; Q1 is accepted for the uniform interface)
+    template <bool Q1>
+    __device__ __forceinline__ void step_acc_q1(float u) { step_acc(u); }
     __device__ __forceinline__ float total() const { return acc_; }
 };
 template <>
@@ -289,10 +299,15 @@ struct Roller<true> {
     __device__ __forceinline__ float step(float u) { return m.step(u); }
 #if BBMPC_PENDULUM_HW_SIN == 2 && BBMPC_PENDULUM_SUMS
     __device__ __forceinline__ void step_acc(float u) { m.step_acc(u); }
+    // the caller's fix_q1 (the value given to init) as a template argument: decided once per launch, not once per step
+    template <bool Q1>
+    __device__ __forceinline__ void step_acc_q1(float u) { m.template step_acc_q1<Q1>(u); }
     __device__ __forceinline__ float total() const { return m.total(); }
 #else
     float acc_ = 0.0f;
     __device__ __forceinline__ void step_acc(float u) { acc_ = acc_ + m.step(u); }
+    template <bool Q1>
+    __device__ __forceinline__ void step_acc_q1(float u) { step_acc(u); }
     __device__ __forceinline__ float total() const { return acc_; }
 #endif
 };
