@@ -93,6 +93,7 @@ SYMBOLS = [
     "bbmpc_set_sampling_correlation", "bbmpc_get_sampling_correlation",
     "bbmpc_set_elite_carry", "bbmpc_get_elite_carry",
     "bbmpc_set_reward_mlp",
+    "bbmpc_set_terminal_value_mlp", "bbmpc_evaluate_terminal_value", "bbmpc_evaluate_terminal_value_dev",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -126,6 +127,10 @@ def _load():
                                   ctypes.POINTER(vp), i32, ctypes.POINTER(vp)]
     lib.bbmpc_set_reward_mlp.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
                                          ctypes.POINTER(vp), i32, i32, ctypes.POINTER(vp)]
+    lib.bbmpc_set_terminal_value_mlp.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
+                                                 ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.c_float]
+    lib.bbmpc_evaluate_terminal_value.argtypes = [vp, vp, i32, vp]
+    lib.bbmpc_evaluate_terminal_value_dev.argtypes = [vp, vp, i32, vp]
     lib.bbmpc_reset.argtypes = [vp]
     lib.bbmpc_optimize.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.bbmpc_optimize_dev.argtypes = [vp, vp, i32, i32, vp, vp]

@@ -666,6 +666,11 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
         rollout_particles(mode, pen, ra, nullptr, 0);
         return;
     }
+    if (value_on()) {                                     // a learned terminal value: today's rollout with recording on + one launch
+        dominant_kernel = "k_rollout_mlp";
+        rollout_terminal_value(mode, pen, ra);
+        return;
+    }
     if (cfg.reward == BBMPC_REW_MLP) {                    // a learned reward: MFMA rollout + MFMA scorer, whatever BBMPC_USER_STEPWISE says
         dominant_kernel = "k_rollout_mlp";
         rollout_mlp_reward_mlp(mode, pen, ra);
@@ -896,7 +901,7 @@ RefitArgs Engine::refit_args() const {
 // samples from is a constant of the handle -- the rollout samples from the constants directly and reads the state from the
 // pinned buffer itself (its workgroup 0 stores it for the later launches).  What else must hold is the optimizer's own.
 bool Engine::dist_init_skippable() const {
-    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() &&
+    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() &&
            iters >= 1 && pi2_copy_seen && stage_state_src != nullptr;
 }
 
@@ -1017,7 +1022,7 @@ void Engine::optimize_cem(RolloutArgs& ra) {
             continue;
         }
         bool first_from_constants = false;
-        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path()) {
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on()) {
             first_rollout_mlp(false, ra, d_prev_mean.p, d_sigma0.p, cem_pinned);
             first_from_constants = cem_skip;
         } else {
@@ -1092,7 +1097,7 @@ void Engine::optimize_pi2(RolloutArgs& ra) {
             capture_trace(it);
             continue;
         }
-        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path()) first_rollout_mlp(true, ra, d_prev_mean.p, nullptr, pinned_state);
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on()) first_rollout_mlp(true, ra, d_prev_mean.p, nullptr, pinned_state);
         else launch_rollout(SRC_TRUNC, true, ra);
         if (sw.refit_v1) hipLaunchKernelGGL(k_refit_pi2, dim3(A), dim3(REFIT_THREADS), lds, stream, rf);
         else hipLaunchKernelGGL(k_refit_pi2_mw, dim3((HU + PI2_ROWS - 1) / PI2_ROWS, A), dim3(64 * PI2_ROWS), lds, stream, rf);
@@ -1786,7 +1791,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                 // hundreds of rollout workgroups read the state: it goes to HBM once, the record comes back on its own.
                 // CEM / PI2 begin with k_dist_init, which fetches it from the pinned buffer itself; the others get a copy
                 const bool stage = (e.cfg.optimizer == BBMPC_OPT_CEM || e.cfg.optimizer == BBMPC_OPT_PI2) && !e.pop_sharded() &&
-                                   !e.user_path();
+                                   !e.user_path() && !e.value_on();
                 // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
                 // replayed as a graph (engine.hpp: step_graph)
                 const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&

@@ -647,6 +647,68 @@ void Engine::launch_traj_mlp_particles(const TrajParticleArgs& pa) {
 // ------------------------------------------------------------------------------------------------
 // learned reward model (bbmpc_set_reward_mlp; kernels_reward_mlp.hpp)
 // ------------------------------------------------------------------------------------------------
+// What the two setters of a one-output Dense stack share (the reward model here, the terminal value below): the
+// descriptor's shape and the packed operands on the host, then the uploads.
+struct DenseStackHost {
+    RewMlpDesc d;
+    std::vector<float> w4[MLP_MAX_LAYERS], bp[MLP_MAX_LAYERS];
+};
+
+static void dense_stack_pack(DenseStackHost& hs, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
+                             const float* const* b, int input_mask, int S, int U) {
+    RewMlpDesc& d = hs.d;
+    memset(&d, 0, sizeof(d));
+    MlpDesc shape;                              // what mlp_pack_layer reads: widths and tiles, features in index order
+    memset(&shape, 0, sizeof(shape));
+    d.n_layers = shape.n_layers = n_layers;
+    int hidden_tiles = 1;
+    for (int l = 0; l <= n_layers; ++l) {
+        d.dims[l] = shape.dims[l] = dims[l];
+        d.tiles[l] = shape.tiles[l] = (dims[l] + 15) / 16;
+        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, d.tiles[l]);
+    }
+    d.nw = std::min(16, hidden_tiles);
+    d.mask = input_mask; d.S = S; d.U = U; d.D = dims[0];
+    d.off_a = (input_mask & 1) ? S : 0;
+    d.off_n = d.off_a + ((input_mask & 2) ? U : 0);
+    for (int l = 0; l < n_layers; ++l) {
+        d.act[l] = acts[l];
+        if (l < n_layers - 1) {
+            std::vector<float> wp;
+            mlp_pack_layer(shape, l, w[l], b[l], wp, hs.w4[l], hs.bp[l]);
+        }
+    }
+}
+
+static void dense_stack_upload(DenseStackHost& hs, const float* const* w, const float* const* b, int is_normalized, const float* const* stats,
+                               DevBuf<float>* d_wp4, DevBuf<float>* d_bp, DevBuf<float>& d_last, DevBuf<float>& d_stats) {
+    RewMlpDesc& d = hs.d;
+    const int n_layers = d.n_layers, D = d.D;
+    for (int l = 0; l < n_layers - 1; ++l) {
+        upload(d_wp4[l], hs.w4[l]);
+        upload(d_bp[l], hs.bp[l]);
+        d.wp4[l] = d_wp4[l].p;
+        d.bpack[l] = d_bp[l].p;
+    }
+    upload(d_last, std::vector<float>(w[n_layers - 1], w[n_layers - 1] + d.dims[n_layers - 1]));      // [K][1]
+    d.wlast = d_last.p;
+    d.blast = b[n_layers - 1][0];
+    d.normalized = is_normalized ? 1 : 0;
+    if (is_normalized) {
+        std::vector<float> st(stats[0], stats[0] + D);
+        st.insert(st.end(), stats[1], stats[1] + D);
+        upload(d_stats, st);
+        d.mean_in = d_stats.p;
+        d.std_in = d_stats.p + D;
+        d.mean_r = stats[2][0];
+        d.std_r = stats[3][0];
+    }
+}
+
+static void launch_reward_mlp_lds(const void* fn, size_t lds) {
+    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+}
+
 // Everything is checked and packed on the host before the handle is touched, so a refusal leaves it as it was.
 void Engine::set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
                             int input_mask, int is_normalized, const float* const* stats) {
@@ -670,59 +732,117 @@ void Engine::set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* ac
     }
     REQUIRE(D <= REW_MLP_MAX_IN, BBMPC_E_UNSUPPORTED, "reward model: more than 192 input columns");
     for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= REW_MLP_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
-    RewMlpDesc d;
-    memset(&d, 0, sizeof(d));
-    MlpDesc shape;                              // what mlp_pack_layer reads: widths and tiles, features in index order
-    memset(&shape, 0, sizeof(shape));
-    d.n_layers = shape.n_layers = n_layers;
-    int hidden_tiles = 1;
-    for (int l = 0; l <= n_layers; ++l) {
-        d.dims[l] = shape.dims[l] = dims[l];
-        d.tiles[l] = shape.tiles[l] = (dims[l] + 15) / 16;
-        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, d.tiles[l]);
-    }
-    d.nw = std::min(16, hidden_tiles);
-    d.mask = input_mask; d.S = S; d.U = U; d.D = D;
-    d.off_a = (input_mask & 1) ? S : 0;
-    d.off_n = d.off_a + ((input_mask & 2) ? U : 0);
-    REQUIRE((size_t)rew_mlp_lds_layout(d).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+    DenseStackHost hs;
+    dense_stack_pack(hs, n_layers, dims, acts, w, b, input_mask, S, U);
+    REQUIRE((size_t)rew_mlp_lds_layout(hs.d).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
             "reward model: the activation buffers of this network do not fit one CU's LDS");
-    std::vector<float> w4[MLP_MAX_LAYERS], bp[MLP_MAX_LAYERS];
-    for (int l = 0; l < n_layers; ++l) {
-        d.act[l] = acts[l];
-        if (l < n_layers - 1) {
-            std::vector<float> wp;
-            mlp_pack_layer(shape, l, w[l], b[l], wp, w4[l], bp[l]);
-        }
-    }
     invalidate_step_graph();
     HIP_CHECK(hipStreamSynchronize(stream));
     rew_mlp_ready = false;
-    for (int l = 0; l < n_layers - 1; ++l) {
-        upload(d_rw_wp4[l], w4[l]);
-        upload(d_rw_bp[l], bp[l]);
-        d.wp4[l] = d_rw_wp4[l].p;
-        d.bpack[l] = d_rw_bp[l].p;
-    }
-    upload(d_rw_last, std::vector<float>(w[n_layers - 1], w[n_layers - 1] + dims[n_layers - 1]));      // [K][1]
-    d.wlast = d_rw_last.p;
-    d.blast = b[n_layers - 1][0];
-    d.normalized = is_normalized ? 1 : 0;
-    if (is_normalized) {
-        std::vector<float> st(stats[0], stats[0] + D);
-        st.insert(st.end(), stats[1], stats[1] + D);
-        upload(d_rw_stats, st);
-        d.mean_in = d_rw_stats.p;
-        d.std_in = d_rw_stats.p + D;
-        d.mean_r = stats[2][0];
-        d.std_r = stats[3][0];
-    }
-    rew_mlp = d;
+    dense_stack_upload(hs, w, b, is_normalized, stats, d_rw_wp4, d_rw_bp, d_rw_last, d_rw_stats);
+    rew_mlp = hs.d;
     rew_mlp_ready = true;
 }
 
-static void launch_reward_mlp_lds(const void* fn, size_t lds) {
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+// ------------------------------------------------------------------------------------------------
+// learned terminal value (bbmpc_set_terminal_value_mlp; kernels_reward_mlp.hpp)
+// ------------------------------------------------------------------------------------------------
+// As set_reward_mlp: checked and packed on the host before the handle is touched.  n_layers = 0 removes the network.
+void Engine::set_terminal_value_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
+                                    int is_normalized, const float* const* stats, float terminal_weight) {
+    if (n_layers == 0) {                        // back to the routing the handle had: nothing else of it was ever changed
+        if (!val_mlp_ready) return;
+        invalidate_step_graph();
+        HIP_CHECK(hipStreamSynchronize(stream));
+        val_mlp_ready = false;
+        return;
+    }
+    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
+    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "terminal value: n_layers must be >= 0");
+    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "terminal value: 1..8 Dense layers are supported");
+    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
+    REQUIRE(dims[0] == S, BBMPC_E_INVALID,
+            "terminal value: dims[0] = " + std::to_string(dims[0]) + " but the network reads the state, dim_s = " + std::to_string(S));
+    REQUIRE(dims[n_layers] == 1, BBMPC_E_INVALID, "terminal value: the last layer must have one output (dims[n_layers] == 1)");
+    for (int l = 0; l < n_layers; ++l) {
+        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
+        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
+    }
+    if (is_normalized) {
+        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
+        for (int i = 0; i < 4; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
+    }
+    REQUIRE(std::isfinite(terminal_weight), BBMPC_E_INVALID, "terminal value: terminal_weight must be finite");
+    for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= REW_MLP_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
+            "a learned terminal value closes the rollouts of a learned model: the handle needs BBMPC_DYN_MLP, not analytic or user dynamics");
+    REQUIRE(!user_callbacks(), BBMPC_E_UNSUPPORTED,
+            "a learned terminal value beside a callback plug-in: the step-wise rollout has no terminal-value form (use a HIP-source reward)");
+    REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED,
+            "a learned terminal value beside an inverse target transform: the transform rollout has no terminal-value form");
+    REQUIRE(!particles_on(), BBMPC_E_UNSUPPORTED,
+            "a learned terminal value with particles on: the particle evaluator has no terminal term (bbmpc_set_particles(0) first)");
+    DenseStackHost hs;
+    dense_stack_pack(hs, n_layers, dims, acts, w, b, 1, S, U);
+    REQUIRE((size_t)rew_mlp_lds_layout(hs.d).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "terminal value: the activation buffers of this network do not fit one CU's LDS");
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));
+    val_mlp_ready = false;
+    dense_stack_upload(hs, w, b, is_normalized, stats, d_vl_wp4, d_vl_bp, d_vl_last, d_vl_stats);
+    val_mlp = hs.d;
+    val_weight = terminal_weight;
+    val_mlp_ready = true;
+}
+
+// Whatever the handle runs today for its reward kind, with u_traj recording on, then the terminal term in one launch.
+// Built-in rewards: every learned-model kernel family records beside a run-time reward (launch_rollout_mlp keeps the
+// compile-time-reward pair kernel and the opt-in bf16 kernel, which do not, for calls without a trajectory pointer).
+void Engine::rollout_terminal_value(int mode, bool pen, RolloutArgs& ra) {
+    if (cfg.reward == BBMPC_REW_MLP) {
+        rollout_mlp_reward_mlp(mode, pen, ra);
+    } else if (cfg.reward == BBMPC_REW_USER) {            // HIP source (callbacks were refused); BBMPC_USER_STEPWISE has no recording form
+        rollout_mlp_user_reward(mode, pen, ra);
+    } else {
+        const size_t need = (size_t)ra.H * A * ra.Nst * S;
+        if (u_traj.n < need) u_traj.alloc(need);
+        mlp_traj_out = u_traj.p;
+        try {
+            launch_rollout_mlp(mode, pen, ra, false, nullptr);
+        } catch (...) {
+            mlp_traj_out = nullptr;
+            throw;
+        }
+        mlp_traj_out = nullptr;
+    }
+    ValMlpTermArgs q;
+    memset(&q, 0, sizeof(q));
+    q.m = val_mlp;
+    q.n_pop = ra.n_pop; q.A = A; q.Nst = ra.Nst;
+    q.weight = val_weight;
+    q.last = u_traj.p + (size_t)(ra.H - 1) * A * ra.Nst * S;
+    q.rewards = ra.rewards;
+    const size_t lds = (size_t)rew_mlp_lds_layout(val_mlp).total * sizeof(float);
+    launch_reward_mlp_lds((const void*)k_value_mlp_terminal, lds);
+    hipLaunchKernelGGL(k_value_mlp_terminal, dim3((ra.n_pop + MLP_TP - 1) / MLP_TP, A), dim3(val_mlp.nw * 64), lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
+// V on B rows of states [B][S]: the rows frame with the value network's descriptor, no weight and no NaN rule
+void Engine::terminal_value_rows(const float* d_states, int batch, float* d_out) {
+    REQUIRE(val_mlp_ready, BBMPC_E_STATE, "terminal value: call bbmpc_set_terminal_value_mlp before computing");
+    REQUIRE(batch >= 1, BBMPC_E_INVALID, "batch must be >= 1");
+    RewMlpRowsArgs q;
+    memset(&q, 0, sizeof(q));
+    q.m = val_mlp;
+    q.B = batch;
+    q.cur = d_states; q.cur_stride = S;
+    q.act = d_states; q.nxt = d_states;                   // never read: the mask selects s_t alone
+    q.out = d_out;
+    const size_t lds = (size_t)rew_mlp_lds_layout(val_mlp).total * sizeof(float);
+    launch_reward_mlp_lds((const void*)k_reward_mlp_rows, lds);
+    hipLaunchKernelGGL(k_reward_mlp_rows, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(val_mlp.nw * 64), lds, stream, q);
+    HIP_CHECK(hipGetLastError());
 }
 
 // The learned model's rollout with a learned reward: Engine::rollout_mlp_user_reward's sequence with the network in place
@@ -818,5 +938,40 @@ extern "C" int bbmpc_set_reward_mlp(bbmpc_handle h, int32_t n_layers, const int3
     API_BEGIN
     CHECK_HANDLE(h);
     h->e->set_reward_mlp(n_layers, dims, acts, w, b, input_mask, is_normalized, stats);
+    API_END
+}
+
+extern "C" int bbmpc_set_terminal_value_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
+                                            const float* const* b, int32_t is_normalized, const float* const* stats, float terminal_weight) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_terminal_value_mlp(n_layers, dims, acts, w, b, is_normalized, stats, terminal_weight);
+    API_END
+}
+
+extern "C" int bbmpc_evaluate_terminal_value_dev(bbmpc_handle h, const float* d_states, int32_t batch, float* d_values) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_states);
+    CHECK_PTR(d_values);
+    h->e->terminal_value_rows(d_states, batch, d_values);
+    API_END
+}
+
+extern "C" int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states, int32_t batch, float* values) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(states);
+    CHECK_PTR(values);
+    bbmpc::Engine& e = *h->e;
+    if (batch < 1) throw bbmpc::HipError(BBMPC_E_INVALID, "batch must be >= 1");
+    if (!e.val_mlp_ready) throw bbmpc::HipError(BBMPC_E_STATE, "terminal value: call bbmpc_set_terminal_value_mlp before computing");
+    const size_t ns = (size_t)batch * e.S;
+    if (e.d_vl_io.n < ns + batch) e.d_vl_io.alloc(ns + batch);
+    float* ds = e.d_vl_io.p; float* dv = ds + ns;
+    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
+    e.terminal_value_rows(ds, batch, dv);
+    HIP_CHECK(hipMemcpyAsync(values, dv, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
     API_END
 }

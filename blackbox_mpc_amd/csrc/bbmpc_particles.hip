@@ -22,6 +22,9 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     REQUIRE(std::isfinite(kappa), BBMPC_E_INVALID, "risk_kappa must be finite");
     REQUIRE(cfg.reward != BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
             "particles with a learned reward model (BBMPC_REW_MLP): the particle evaluator scores built-in and HIP-source rewards only");
+    REQUIRE(!value_on(), BBMPC_E_UNSUPPORTED,
+            "particles with a learned terminal value (bbmpc_set_terminal_value_mlp): the particle evaluator has no terminal term; remove "
+            "the value network first (n_layers = 0)");
     // a HIP-source reward scores the learned model's particles; the analytic pendulum keeps its built-in rewards
     REQUIRE((cfg.reward != BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_MLP) && cfg.dynamics != BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
             "particles with HIP-source or callback dynamics, or with a user reward beside the built-in pendulum model: a user reward "

@@ -74,6 +74,8 @@ void Engine::set_user_source(int kind, const char* src, int nparams) {
 
 void Engine::set_user_callback(int kind, bbmpc_rows_callback fn, void* user) {
     require_user_side(kind);
+    REQUIRE(!(fn && value_on()), BBMPC_E_UNSUPPORTED,
+            "a callback plug-in beside a learned terminal value (bbmpc_set_terminal_value_mlp): the step-wise rollout has no terminal-value form");
     REQUIRE(!(fn && kind == USER_KIND_DYNAMICS && has_xform()), BBMPC_E_UNSUPPORTED,
             "a dynamics callback returns absolute next states: apply the inverse target transform inside it (clear the transform first)");
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -138,6 +140,9 @@ void Engine::set_transform_source(int kind, const char* src) {
     const bool clear = !src || !*src;
     const bool inverse = kind == USER_KIND_INVERSE_TRANSFORM;
     if (inverse && !clear) {
+        REQUIRE(!value_on(), BBMPC_E_UNSUPPORTED,
+                "an inverse target transform beside a learned terminal value (bbmpc_set_terminal_value_mlp): the transform rollout has no "
+                "terminal-value form");
         REQUIRE(cfg.reward != BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
                 "an inverse target transform beside a learned reward model (BBMPC_REW_MLP): the transform rollout has no learned-reward form");
         REQUIRE(cfg.dynamics == BBMPC_DYN_MLP || cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,

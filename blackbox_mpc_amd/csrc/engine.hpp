@@ -340,6 +340,20 @@ struct Engine {
     void rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra);
     void reward_mlp_rows(const RewMlpRowsArgs& rows);
     void traj_mlp_reward_mlp(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
+    // learned terminal value (bbmpc_set_terminal_value_mlp; bbmpc_mlp.hip, kernels_reward_mlp.hpp): a
+    // network V over the state alone.  While one is installed every rollout of the handle records the trajectory and
+    // k_value_mlp_terminal adds terminal_weight * V(s_H) to the scores; control steps take one launch sequence per
+    // iteration (no skipped k_dist_init, no graph replay), as user_path() handles do.  One-step calls, the record and
+    // bbmpc_predict_trajectories never read it.
+    bool val_mlp_ready = false;
+    RewMlpDesc val_mlp;
+    float val_weight = 1.0f;
+    DevBuf<float> d_vl_wp4[MLP_MAX_LAYERS], d_vl_bp[MLP_MAX_LAYERS], d_vl_last, d_vl_stats, d_vl_io;
+    bool value_on() const { return val_mlp_ready; }
+    void set_terminal_value_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
+                                int is_normalized, const float* const* stats, float terminal_weight);
+    void rollout_terminal_value(int mode, bool pen, RolloutArgs& ra);
+    void terminal_value_rows(const float* d_states, int batch, float* d_out);
     void set_user_source(int kind, const char* src, int nparams = 0);
     void set_user_callback(int kind, bbmpc_rows_callback fn, void* user);
     // runtime parameters of a parameterised user reward / dynamics (bbmpc_set_user_params): [A][P] on the device -- a

@@ -19,6 +19,12 @@
 //                       depend on the chunking, on the number of agents or on the run.
 //   k_reward_mlp_rows   B independent rows with their own cur / act / nxt pointers and strides, one reward per row, no sum,
 //                       no NaN rule (evaluate_next_reward, the control step's record, predict_trajectories).
+// ... and a third for a learned terminal value (bbmpc_set_terminal_value_mlp), a network over the
+// state alone (mask = s_t, D = S):
+//   k_value_mlp_terminal  the 16 candidates' LAST recorded states (plane H - 1 of u_traj) through the stack, then lanes
+//                       0..15 finish in place: rewards[a][n] += w * V(s_H), NaN -> -1e6.  One launch behind whatever scored
+//                       the steps, no atomics.  k_reward_mlp_rows with the value network's descriptor serves
+//                       bbmpc_evaluate_terminal_value.
 #pragma once
 #include "kernels_mlp.hpp"
 
@@ -87,6 +93,14 @@ struct RewMlpRowsArgs {
     const float* nxt;
     long cur_stride, act_stride, nxt_stride;
     float* out;                              // [B]
+};
+
+struct ValMlpTermArgs {
+    RewMlpDesc m;                            // mask = 1 (s_t), D = S
+    int n_pop, A, Nst;
+    float weight;                            // terminal_weight
+    const float* last;                       // [A][Nst][S]: the trajectory buffer's last plane, u_traj + (H - 1) * A * Nst * S
+    float* rewards;                          // [A][Nst]: the step sum (NaN -> -1e6) - penalty, finished in place
 };
 
 #ifdef BBMPC_TU_MLP
@@ -290,6 +304,36 @@ __global__ void k_reward_mlp_rows(RewMlpRowsArgs q) {
     __syncthreads();
     const float r = rew_mlp_stack(m, lay, tid);
     if (tid < MLP_TP && r0 + tid < q.B) q.out[r0 + tid] = r;
+}
+
+// rewards[a][n] = rewards[a][n] + w * V(s_H[n, a]); a NaN w * V makes the score -1e6.  Rows past
+// n_pop are neither read nor written: their input columns stay zero.
+__global__ void k_value_mlp_terminal(ValMlpTermArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const RewMlpDesc& m = q.m;
+    const int tid = threadIdx.x, nthr = m.nw * 64;
+    const int a = blockIdx.y, n0 = blockIdx.x * MLP_TP, D = m.D;
+    const RewMlpLds lay = rew_mlp_lds_layout(m);
+    float* xs = smem + lay.xs;
+    const float* nmean = smem + lay.norm;
+    const float* nden = nmean + D;
+    rew_mlp_prologue(m, lay, tid, nthr);
+    rew_glb_cf* last = (rew_glb_cf*)q.last + ((size_t)a * q.Nst + n0) * D;      // the tile's 16 rows are 16 * S contiguous floats
+    for (int i = tid; i < MLP_TP * D; i += nthr) {
+        const int pp = i / D, k = i - pp * D;
+        float v = 0.0f;
+        if (n0 + pp < q.n_pop) v = (last[i] - nmean[k]) / nden[k];
+        xs[tile_addr(k, pp)] = v;
+    }
+    __syncthreads();
+    const float v = rew_mlp_stack(m, lay, tid);
+    if (tid < MLP_TP && n0 + tid < q.n_pop) {
+        const size_t o = (size_t)a * q.Nst + n0 + tid;
+        const float term = q.weight * v;
+        float total = q.rewards[o] + term;
+        if (term != term) total = -1.0e6f;
+        q.rewards[o] = total;
+    }
 }
 
 #endif  // BBMPC_TU_MLP

@@ -125,6 +125,47 @@ class Engine:
         else:
             L.check(L.lib.bbmpc_set_reward_mlp(self._h, n, dims_a, acts_a, wp, bp, int(input_mask), 0, None))
 
+    def set_terminal_value_mlp(self, weights, biases, activations, stats=None, terminal_weight=1.0):
+        """Learned terminal value of a DYN_MLP handle (bbmpc_set_terminal_value_mlp): Dense kernels [in, out] / biases [out]
+        from dim_S inputs to one output, any ACT_* code per layer; stats = (mean_in [S], std_in [S], mean_v, std_v) or
+        None.  Rollout scores become R + terminal_weight * V(s_H).  weights = None (or an empty list) removes the network."""
+        if not weights:
+            L.check(L.lib.bbmpc_set_terminal_value_mlp(self._h, 0, None, None, None, None, 0, None, 0.0))
+            return
+        n = len(weights)
+        ws = [L.f32c(w) for w in weights]
+        bs = [L.f32c(np.asarray(b).reshape(-1)) for b in biases]
+        dims = [ws[0].shape[0]] + [w.shape[1] for w in ws]
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            if w.ndim != 2 or w.shape[0] != dims[i] or b.shape != (w.shape[1],):
+                raise ValueError("layer %d: kernel must be [in,out] and bias [out]" % i)
+        dims_a = (ctypes.c_int32 * (n + 1))(*dims)
+        acts_a = (ctypes.c_int32 * n)(*[int(a) for a in activations])
+        wp = (ctypes.c_void_p * n)(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bs])
+        sp = None
+        if stats is not None:
+            st = [L.f32c(np.asarray(s).reshape(-1)) for s in stats]
+            if st[0].shape != (dims[0],) or st[1].shape != (dims[0],) or st[2].shape != (1,) or st[3].shape != (1,):
+                raise ValueError("stats must be (mean_in [%d], std_in [%d], mean_v [1], std_v [1])" % (dims[0], dims[0]))
+            sp = (ctypes.c_void_p * 4)(*[s.ctypes.data for s in st])
+        L.check(L.lib.bbmpc_set_terminal_value_mlp(self._h, n, dims_a, acts_a, wp, bp, 1 if stats is not None else 0, sp,
+                                                   float(terminal_weight)))
+
+    def evaluate_terminal_value(self, states):
+        """V on rows (bbmpc_evaluate_terminal_value): states [B, S] -> [B], without the weight and without a NaN rule."""
+        states = L.f32c(states)
+        b = states.shape[0] if states.ndim == 2 else -1
+        if states.shape != (b, self.S):                  # the C side copies b * S floats from this buffer
+            raise ValueError("states [B,%d] expected, got %s" % (self.S, states.shape))
+        out = np.empty((b,), np.float32)
+        if b:
+            L.check(L.lib.bbmpc_evaluate_terminal_value(self._h, L.ptr(states), b, L.ptr(out)))
+        return out
+
+    def evaluate_terminal_value_dev(self, d_states, batch, d_values):
+        L.check(L.lib.bbmpc_evaluate_terminal_value_dev(self._h, ctypes.c_void_p(d_states), int(batch), ctypes.c_void_p(d_values)))
+
     def set_mlp_ensemble(self, members):
         """Model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble): `members` is a list of (weights, biases)
         pairs or of objects with `.weights` / `.biases`, each of the shape of the model set_mlp installed; particle p

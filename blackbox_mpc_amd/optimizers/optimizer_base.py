@@ -56,6 +56,10 @@ class OptimizerBase:
             if eng.__dict__.get("_rew_version") != getattr(rf, "_version", 0):
                 from ..trajectory_evaluators.deterministic import configure_reward
                 configure_reward(eng, rf)
+        value = getattr(self._trajectory_evaluator, "_terminal_value", None)      # a refitted value network, likewise
+        if value is not None and eng.__dict__.get("_val_version") != getattr(value, "_version", 0):
+            from ..trajectory_evaluators.deterministic import configure_terminal_value
+            configure_terminal_value(eng, self._trajectory_evaluator)
         return eng
 
     def _require_engine_and_params(self):
@@ -119,7 +123,8 @@ class OptimizerBase:
             self._engine.reset()
 
     def set_trajectory_evaluator(self, trajectory_evaluator):
-        from ..trajectory_evaluators.deterministic import configure_dynamics, configure_reward, plugin_kinds
+        from ..trajectory_evaluators.deterministic import (configure_dynamics, configure_reward, configure_terminal_value,
+                                                           plugin_kinds)
         self._trajectory_evaluator = trajectory_evaluator
         if type(self)._engine_optimizer == L.OPT_NONE:
             return
@@ -136,6 +141,7 @@ class OptimizerBase:
                               population_global=self._population_global, **self._engine_kwargs())
         configure_dynamics(self._engine, h)
         configure_reward(self._engine, trajectory_evaluator._reward_function)
+        configure_terminal_value(self._engine, trajectory_evaluator)
         particles = getattr(trajectory_evaluator, "particle_settings", None)
         if particles is not None:                     # a ParticleTrajectoryEvaluator: (num_particles, process_noise_std, risk_kappa)
             self._engine.set_particles(*particles)

@@ -19,7 +19,13 @@ class MPCPolicy(ModelBasedBasePolicy):
     def __init__(self, trajectory_evaluator=None, optimizer=None, tf_writer=None, log_dir=None,
                  reward_function=None, env_action_space=None, env_observation_space=None,
                  dynamics_function=None, dynamics_handler=None, true_model=False, optimizer_name=None,
-                 num_agents=None, save_model_frequency=1, saved_model_dir=None, **optimizer_args):
+                 num_agents=None, save_model_frequency=1, saved_model_dir=None, terminal_value=None, terminal_weight=1.0,
+                 **optimizer_args):
+        """terminal_value / terminal_weight: a LearnedValueMLP that closes the planning horizon (handed to the
+        DeterministicTrajectoryEvaluator this constructor builds; an evaluator passed in takes them itself)."""
+        if trajectory_evaluator is not None and terminal_value is not None:
+            raise ValueError("terminal_value goes to the trajectory evaluator: construct it with terminal_value=, "
+                             "or leave trajectory_evaluator to MPCPolicy")
         if trajectory_evaluator is None:
             if dynamics_handler is None:
                 dynamics_handler = SystemDynamicsHandler(
@@ -28,7 +34,9 @@ class MPCPolicy(ModelBasedBasePolicy):
                     tf_writer=tf_writer, save_model_frequency=save_model_frequency,
                     saved_model_dir=saved_model_dir)
             trajectory_evaluator = DeterministicTrajectoryEvaluator(reward_function=reward_function,
-                                                                    system_dynamics_handler=dynamics_handler)
+                                                                    system_dynamics_handler=dynamics_handler,
+                                                                    terminal_value=terminal_value,
+                                                                    terminal_weight=terminal_weight)
         super(MPCPolicy, self).__init__(trajectory_evaluator=trajectory_evaluator)
         if optimizer is None:
             if num_agents is None:

@@ -157,10 +157,32 @@ def reward_stale(engine, reward_function):
     return engine.cfg.reward == L.REW_MLP and engine.__dict__.get("_rew_version") != getattr(reward_function, "_version", 0)
 
 
+def configure_terminal_value(engine, evaluator):
+    """Upload the evaluator's LearnedValueMLP (terminal_value=) and its weight; nothing to do without one."""
+    value = getattr(evaluator, "_terminal_value", None)
+    if value is None:
+        return
+    engine.set_terminal_value_mlp(value.weights, value.biases, value.activation_codes, value.normalization_stats(),
+                                  evaluator._terminal_weight)
+    engine._val_version = getattr(value, "_version", 0)
+
+
+def terminal_value_stale(engine, evaluator):
+    """A value network whose weights changed since they were uploaded (or that was never uploaded to this engine)."""
+    value = getattr(evaluator, "_terminal_value", None)
+    return value is not None and engine.__dict__.get("_val_version") != getattr(value, "_version", 0)
+
+
 class DeterministicTrajectoryEvaluator(EvaluatorBase):
-    def __init__(self, reward_function, system_dynamics_handler, quirks=0):
+    def __init__(self, reward_function, system_dynamics_handler, quirks=0, terminal_value=None, terminal_weight=1.0):
+        """terminal_value: a LearnedValueMLP V -- candidates then score sum_t r_t + terminal_weight * V(s_H) (learned
+        dynamics only; bbmpc_set_terminal_value_mlp).  The one-step calls and predict_trajectories do not read it."""
         super().__init__(reward_function=reward_function, system_dynamics_handler=system_dynamics_handler, name=None)
         self._quirks = int(quirks)
+        self._terminal_value = terminal_value
+        self._terminal_weight = float(terminal_weight)
+        if terminal_value is not None and not np.isfinite(self._terminal_weight):
+            raise ValueError("terminal_weight must be finite")
         self._engines = {}
 
     def _engine(self, num_agents, horizon):
@@ -178,6 +200,8 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
             configure_dynamics(eng, h)
         if reward_stale(eng, self._reward_function):
             configure_reward(eng, self._reward_function)
+        if terminal_value_stale(eng, self):
+            configure_terminal_value(eng, self)
         if eng._param_fns:
             from ..utils.device_functions import sync_user_params
             sync_user_params(eng)

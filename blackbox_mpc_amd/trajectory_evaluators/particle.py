@@ -43,7 +43,7 @@ def quantile_rank(tau, num_particles):
 
 class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
     def __init__(self, reward_function, system_dynamics_handler, num_particles, process_noise_std, risk_kappa=0.0,
-                 quirks=0, risk_alpha=None):
+                 quirks=0, risk_alpha=None, terminal_value=None, terminal_weight=1.0):
         """process_noise_std: a scalar or [dim_S], >= 0 -- for a learned model SystemDynamicsHandler.residual_std() is
         the natural choice.  risk_kappa > 0 prefers candidates whose return varies little over the particles.
         risk_alpha in (0, 1] scores the mean of the ceil(risk_alpha * num_particles) worst returns instead (CVaR; not
@@ -51,6 +51,9 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
         if getattr(reward_function, "_bbmpc_reward_kind", None) == L.REW_MLP:
             raise NotImplementedError("ParticleTrajectoryEvaluator does not score a LearnedRewardMLP yet: the particle rollouts take "
                                       "built-in and HIP-source rewards (use DeterministicTrajectoryEvaluator with a learned reward)")
+        if terminal_value is not None:
+            raise NotImplementedError("ParticleTrajectoryEvaluator has no terminal term yet: a LearnedValueMLP closes the rollouts of "
+                                      "DeterministicTrajectoryEvaluator only")
         super().__init__(reward_function, system_dynamics_handler, quirks=quirks)
         p = int(num_particles)
         if not 1 <= p <= 64:

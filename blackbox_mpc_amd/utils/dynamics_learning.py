@@ -9,7 +9,7 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
                                batch_size=128, is_normalized=True, nn_optimizer=None, tf_writer=None,
                                exploration_noise=False, log_dir=None, save_model_frequency=1, saved_model_dir=None,
                                start_episode=0, multistep_horizon=None, reward_model=None, reward_train_args=None,
-                               **train_args):
+                               value_model=None, value_n_step=10, value_train_args=None, **train_args):
     """Same arguments as the reference; `train_args` (device=, seed=, ...) are forwarded to `train`.
     `multistep_horizon`: when set, the fit is followed by one SystemDynamicsHandler.multistep_error call over that many
     steps on the episodes just collected (the train / validation split is per transition, so there is no held-out
@@ -17,7 +17,9 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
     as a training loss is: call `handler.multistep_error` on fresh episodes for a validation figure.  None: nothing extra is computed.
     `reward_model`: a LearnedRewardMLP that is refitted, on every episode it has been given so far, from the rewards these
     rollouts collect anyway (`reward_train_args`: a dict forwarded to its `train`; default: epochs / batch_size /
-    learning_rate / validation_split of this call)."""
+    learning_rate / validation_split of this call).
+    `value_model`: a LearnedValueMLP that is refitted beside them on the `value_n_step`-step returns of every episode it
+    has been given so far (`value_train_args`: a dict forwarded to its `train_on_rollouts`: gamma=, bootstrap=, epochs=, ...)."""
     if system_dynamics_handler is None:
         system_dynamics_handler = SystemDynamicsHandler(env_action_space=env.action_space,
                                                         env_observation_space=env.observation_space,
@@ -35,6 +37,10 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
         args = dict(epochs=epochs, batch_size=batch_size, learning_rate=learning_rate, validation_split=validation_split)
         args.update(reward_train_args or {})
         reward_model.train_on_rollouts(traj_obs, traj_acs, traj_rews, **args)
+    if value_model is not None:
+        args = dict(epochs=epochs, batch_size=batch_size, learning_rate=learning_rate, validation_split=validation_split)
+        args.update(value_train_args or {})
+        value_model.train_on_rollouts(traj_obs, traj_rews, value_n_step, **args)
     if multistep_horizon is not None:
         system_dynamics_handler.multistep_error(traj_obs, traj_acs, multistep_horizon)
     return system_dynamics_handler

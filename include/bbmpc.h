@@ -205,6 +205,34 @@ int bbmpc_set_reward_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, 
                          const float* const* weights, const float* const* biases, int32_t input_mask,
                          int32_t is_normalized, const float* const* stats);
 
+/* Learned terminal value for a BBMPC_DYN_MLP handle with any reward kind (built-in, HIP-source BBMPC_REW_USER, BBMPC_REW_MLP):
+ * a Dense stack V(s) over the state alone that closes every rollout of a plan,
+ *     R'[n, a] = R[n, a] + terminal_weight * V(s_H[n, a]),
+ * where R is what the handle computes without it (the step sum, NaN -> -1e6, minus the bound penalty) and s_H the state
+ * the rollout reached after its last step (after the clipped actions where the optimizer clips).  If terminal_weight * V
+ * is NaN the candidate scores -1e6.  Layouts as bbmpc_set_reward_mlp with a state-only input: dims[0] == dim_s,
+ * dims[n_layers] == 1, stats = {mean_in[dim_s], std_in[dim_s], mean_v[1], std_v[1]} or NULL when is_normalized == 0;
+ * V = y * std_v + mean_v on x = (s - mean_in) / (std_in + 1e-7).  While a network is installed, bbmpc_evaluate[_dev] and
+ * the control steps of all six optimizers (agent and population shards included) run what they ran before with the
+ * trajectory recorded, then one more kernel adds the terminal term: one launch sequence per iteration, no graph-replayed
+ * form.  The control step's record, bbmpc_predict_next_state, bbmpc_evaluate_next_reward and bbmpc_predict_trajectories
+ * are unchanged: the term belongs to a plan, not to a step.  Calling it again replaces the network and the weight;
+ * n_layers == 0 (every other argument is then ignored) removes it and restores the handle's previous routing and outputs
+ * bit for bit.  Refused before anything is allocated, the handle stays as it was -- BBMPC_E_UNSUPPORTED: n_layers > 8, a
+ * hidden width > 512, analytic or BBMPC_DYN_USER dynamics, a callback plug-in, an inverse target transform, particles on
+ * (and, the other way round, bbmpc_set_inverse_transform_source, a callback and bbmpc_set_particles (num_particles > 0)
+ * on a handle that has a value network); BBMPC_E_INVALID: NULL pointers, n_layers < 0, a width < 1, dims[0] != dim_s,
+ * dims[n_layers] != 1, an unknown activation, is_normalized without stats, a non-finite terminal_weight. */
+int bbmpc_set_terminal_value_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* activations,
+                                 const float* const* weights, const float* const* biases, int32_t is_normalized,
+                                 const float* const* stats, float terminal_weight);
+
+/* V on `batch` rows of states [batch][dim_s] -> values [batch]: the installed network alone, without terminal_weight and
+ * without a NaN rule.  BBMPC_E_STATE without a network.  The _dev form takes device pointers and is ordered on the
+ * handle's stream. */
+int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states, int32_t batch, float* values);
+int bbmpc_evaluate_terminal_value_dev(bbmpc_handle h, const float* d_states, int32_t batch, float* d_values);
+
 /* User-supplied plug-ins.  The reference takes ANY callable as reward_function / dynamics_function
  * (trajectory_evaluators/deterministic.py:13-18; called at :65-66 as reward(current_state, actions, next_state) and at
  * :99-100 as dynamics(x[B,S+U], train=False) -> delta[B,S]).  A Python callable cannot run inside a kernel; the
