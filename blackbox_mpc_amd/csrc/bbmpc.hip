@@ -203,6 +203,7 @@ Engine::Engine(const bbmpc_config& c) : cfg(c) {
         sw.mlp_wave = ival("BBMPC_MLP_WAVE", 1);
         sw.linger_us = std::max(0, ival("BBMPC_LINGER_US", 200));
         linger_test_quit = ival("BBMPC_LINGER_TEST_QUIT", 0) - 1;
+        host_seq = (uint32_t)ival("BBMPC_TEST_HOST_SEQ", 0);      // test hook: where the completion sequence numbers start (the 16-bit tag's wrap)
         sw.balance = ival("BBMPC_BALANCE", 0);      // (1: SIMD mates pace each other in the fused pendulum rollout -- paid while a model step took 160 ns, costs 1-2 % at 60)
         sw.ilp = ival("BBMPC_ILP", 1) == 2 ? 2 : 1;
         sw.refit_v1 = flag("BBMPC_REFIT_V1");
@@ -321,7 +322,7 @@ static void resident_unpublish(Engine* e);
 // a launch after all: the workgroups left (the stream is idle then), this step's noise chunk is not there yet, or -- a
 // request that crossed some workgroups' exit -- only part of the agents were served: subset_n / amap_host() then name the
 // rest and the launch that follows covers exactly those.
-bool Engine::resident_step(const float* state, int add_noise, uint32_t seq) {
+bool Engine::resident_step(const float* state, int add_noise, uint32_t seq, float* records) {
     {   // all workgroups gone already (linger time over, or another handle asked them to leave): nothing to stop or wait for
         bool all_gone = true;
         for (int a = 0; a < A && all_gone; ++a) all_gone = *(volatile const uint32_t*)gone_host(a) != 0u;
@@ -369,11 +370,11 @@ bool Engine::resident_step(const float* state, int add_noise, uint32_t seq) {
     const auto t0 = std::chrono::steady_clock::now();
     bool all = true;
     for (int a = 0; a < A; ++a) {
-        volatile const uint32_t* ack = ack_host(a);
+        volatile const uint32_t* ack = ack_host(a);              // the agent's completion line (completion_line.hpp)
         volatile const uint32_t* gone = gone_host(a);
         uint32_t spins = 0;
         for (;;) {
-            if (*ack == seq) break;
+            if (completion_line_decode(ack, seq, records + (size_t)a * kCompletionRecordFloats)) break;
             if (*gone != 0u) { all = false; break; }               // it left (before or after this request?)
             if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { all = false; break; }
         }
@@ -384,7 +385,7 @@ bool Engine::resident_step(const float* state, int add_noise, uint32_t seq) {
     int missing = 0;
     int32_t* amap = amap_host();
     for (int a = 0; a < A; ++a)
-        if (*(volatile const uint32_t*)ack_host(a) != seq) amap[missing++] = a;
+        if (!completion_line_decode(ack_host(a), seq, records + (size_t)a * kCompletionRecordFloats)) amap[missing++] = a;
     if (missing == 0) return true;                                // everybody took the request on the way out
     --step_counter;                                               // the launch that follows does this step ...
     subset_n = missing < A ? missing : 0;                         // ... for the agents that were not served (all of them: an ordinary launch)
@@ -1774,7 +1775,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                                e.stream == e.own_stream;      // on a caller's stream it would hold back the caller's next work
         bool handled = false;
         if (e.resident_alive) {
-            if (linger_ok) handled = e.resident_step(pin, noise, e.host_seq);
+            if (linger_ok) handled = e.resident_step(pin, noise, e.host_seq, pin + ns);
             else e.resident_stop();
         }
         if (handled) ++e.calls_resident; else ++e.calls_launched;
@@ -1882,16 +1883,17 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
         std::atomic_thread_fence(std::memory_order_acquire);
         e.lazy_sync = true;
     } else if (published && e.resident_alive) {
-        // a LINGER launch: every agent's workgroup publishes its own completion word
+        // a LINGER launch: every agent's workgroup publishes its own completion line, which carries the record
         const uint32_t want = e.host_seq;
         const auto t0 = std::chrono::steady_clock::now();
         for (int a = 0; a < e.A; ++a) {
             volatile const uint32_t* f = e.ack_host(a);
+            float* rec_a = pin + ns + (size_t)a * kCompletionRecordFloats;
             uint32_t spins = 0;
-            while (*f != want) {
+            while (!completion_line_decode(f, want, rec_a)) {
                 if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
                     e.resident_stop();                               // a fault surfaces in its synchronize
-                    if (*f != want) throw HipError(BBMPC_E_HIP, "bbmpc_optimize: the control step finished without publishing its records");
+                    if (!completion_line_decode(f, want, rec_a)) throw HipError(BBMPC_E_HIP, "bbmpc_optimize: the control step finished without publishing its records");
                 }
             }
         }

@@ -51,9 +51,14 @@ static void launch_fused4(Engine& e, FusedArgs& fa, int threads, size_t lds_base
                 auto fl = k_fused_pendulum<OPT, true, FASTM, INJ, ILP, true>;
                 note_inst(e, OPT, true, FASTM, INJ, ILP, true);
                 ensure_max_lds((const void*)fl, (int)limit);
+                // the completion lines carry the packed record itself: five floats in ten tagged half-words
+                if (e.rec != kCompletionRecordFloats) throw HipError(BBMPC_E_HIP, "internal: the resident pendulum kernel's record is not 5 floats");
                 for (int a = 0; a < e.A; ++a) {
                     volatile uint32_t* m = e.mbox_host(a);
-                    for (int i = 0; i < 13; ++i) m[i] = fa.done_value & 0xffffu;   // no payload word may carry the next request's tag by accident
+                    // no word of the completion line may carry this call's tag before the kernel stores it (a line left by
+                    // the call 65536 numbers ago would): the kernels that wrote these lines have ended
+                    volatile uint32_t* cl = e.ack_host(a);
+                    for (int i = 0; i < 16; ++i) cl[i] = (fa.done_value - 1u) & 0xffffu;                    for (int i = 0; i < 13; ++i) m[i] = fa.done_value & 0xffffu;   // no payload word may carry the next request's tag by accident
                     m[15] = fa.done_value;                            // nothing pending (a stale stop word must not end it)
                     *(volatile uint32_t*)e.gone_host(a) = 0u;
                 }
@@ -202,6 +207,9 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
             fprintf(stderr, "\n[dbg] iter0 per-wave rollout end:");
             for (int i = 24; i < 32; ++i) fprintf(stderr, " %lld", d[i] - d[0]);
             fprintf(stderr, "\n[dbg] request accepted %lld  first model step %lld  completion stored %lld\n", d[42] - d[0], d[44] - d[0], d[43] - d[0]);
+            const long long sel = d[iters > 0 ? 4 * iters : 0];      // the last iteration's selection done (CEM), else the pass's start
+            fprintf(stderr, "[dbg] tail rel. to the last selection: tail start %lld  noise applied %lld  model step %lld  record stored %lld  published %lld  last barrier %lld  carry stored %lld\n",
+                    d[38] - sel, d[35] - sel, d[36] - sel, d[37] - sel, d[43] - sel, d[1 + iters * 4] - sel, d[34] - sel);
             dbg_buf[42] = 0;
         }
         fa.dbg = dbg_buf;

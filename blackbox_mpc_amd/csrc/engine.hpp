@@ -16,6 +16,7 @@
 
 #include "../../include/bbmpc.h"
 #include "comm.hpp"
+#include "completion_line.hpp"
 #include "kernels_cma.hpp"
 #include "kernels_eigh.hpp"
 #include "kernels_eigh_small.hpp"
@@ -247,8 +248,10 @@ struct Engine {
     bool linger_launch = false;        // bbmpc_optimize asks optimize_fused for the LINGER variant
     bool resident_alive = false;       // a LINGER kernel may still be polling the mailbox
     // pinned block host_done, 16-word lines: 0 completion word of the launch-per-call paths | 1..A per-agent completion
-    // words | A+1..2A request lines | 2A+1..3A exit words | 3A+1.. agent map of a subset launch (one int32 per agent:
-    // ceil(A/16) lines -- every agent but one may be listed)
+    // lines of the resident kernel (completion_line.hpp: the record's ten half-words, each tagged with the low 16 bits of
+    // the call's sequence number, and the whole number in word 15 -- the line IS the record, the kernel writes no other) |
+    // A+1..2A request lines | 2A+1..3A exit words | 3A+1.. agent map of a subset launch (one int32 per agent: ceil(A/16)
+    // lines -- every agent but one may be listed)
     static constexpr int kLingerMaxAgents = 64;
     int sync_lines() const {
         const int al = std::max(1, std::min(A, kLingerMaxAgents));
@@ -267,7 +270,7 @@ struct Engine {
     int subset_n = 0;                  // > 0: the next persistent-kernel launch covers only the agents listed in amap_host()
     int linger_test_quit = -1;         // BBMPC_LINGER_TEST_QUIT (test hook, kernels_fused.hpp)
     int64_t calls_resident = 0, calls_launched = 0;   // bbmpc_call_stats
-    bool resident_step(const float* state, int add_noise, uint32_t seq);
+    bool resident_step(const float* state, int add_noise, uint32_t seq, float* records);   // records: [A][5], decoded from the completion lines
     void resident_stop();
     hipStream_t pf_stream = nullptr;
     hipEvent_t pf_done[2] = {nullptr, nullptr}, pf_free = nullptr;

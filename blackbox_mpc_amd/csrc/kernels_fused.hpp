@@ -33,7 +33,8 @@ struct FusedArgs {
     int fix_q1, fix_q7, add_noise;
     int warm_start;          // CEM: BBMPC_FIX_Q2 (keep the mean across control steps)
     int balance;             // progress-balanced wave priorities in the rollout (BBMPC_BALANCE, default off)
-    unsigned* done_flag;     // optional completion counter in signal memory (see the kernel's tail), else null
+    unsigned* done_flag;     // optional completion counter in signal memory (see the kernel's tail), else null;
+                             // LINGER: [A][16] pinned completion lines, which carry the records (p.record is not written)
     unsigned* done_count;
     unsigned done_value;
     float alpha, inv_lamda;
@@ -188,6 +189,68 @@ __global__ void k_fused_pendulum(FusedArgs p) {
     __syncthreads();
     float s0 = red[60], s1 = red[61], s2 = red[62];
     if (p.iters > 0) prefetch_first(inj_s, 0);
+    // ---- OptimizerBase.__call__ tail (optimizer_base.py:82-94), in two parts.
+    // noise_term: the additive exploration term, from the bounds this thread holds in registers (no global reload behind
+    // the carry stores).  It depends on the control step's key alone, not on the optimizer's result; evaluating it ahead of
+    // the tail (in the iteration loop, while wave 0 waits for its SIMD mates) was built and put spill reloads into the
+    // loop at this kernel's 128 registers: it stays in the tail (profiles/control_step_tail.md).
+    auto noise_term = [&]() {
+        FinalArgs fa;
+        fa.A = p.A; fa.U = 1; fa.S = 3;
+        fa.agent_offset = p.agent_offset;
+        fa.fix_q1 = p.fix_q1; fa.fix_q7 = p.fix_q7;
+        fa.add_noise = add_noise_s;
+        fa.lo = p.lo; fa.hi = p.hi;
+        fa.inj = p.inj_expl;
+        fa.key = key_s;
+        fa.key.q_per_agent = 1;
+        return exploration_noise(fa, a, 0, lo, hi);                 // (resident form: every lane of wave 0 the same value)
+    };
+    // tail: apply the term, one model step, the record.  Launch-per-call form: thread 0 stores the packed record and
+    // publishes with a release (publish_records_done).  Resident form: every lane of wave 0 computes the same five values
+    // and lanes 0..15 store the agent's COMPLETION LINE, one word each, relaxed, with no fence in front -- the request
+    // line's format mirrored: word 2f = (low half of float f) << 16 | tag, word 2f+1 = high half | tag, tag = the low 16 bits
+    // of the sequence number; words 10..14 the tag alone, word 15 the whole sequence number.  The host accepts the line
+    // when words 0..9 and 15 all name the call it waits for (completion_line.hpp), so neither the order in which the
+    // words arrive nor how the fabric splits the store matters, and nothing has to be waited for in front of it.
+    const bool tail_lanes = LINGER ? tid < 64 : tid == 0;
+    auto tail = [&](float act_in) {
+        BB_DBG(38);
+        float s[3] = {s0, s1, s2};
+        float act[1];
+        act[0] = add_noise_s ? exploration_apply(act_in, noise_term(), lo, hi) : act_in;
+        BB_DBG(35);
+        const float r = model.step(s, act);
+        BB_DBG(36);
+        if constexpr (LINGER) {
+            const unsigned tag = done_value_s & 0xffffu;
+            const float f = tid < 2 ? act[0] : (tid < 4 ? s[0] : (tid < 6 ? s[1] : (tid < 8 ? s[2] : r)));
+            const unsigned bits = __float_as_uint(f);
+            unsigned w = ((tid & 1) ? (bits & 0xffff0000u) : (bits << 16)) | tag;
+            if (tid >= 10) w = tag;
+            if (tid == 15) w = done_value_s;
+            if (tid < 16) __hip_atomic_store(p.done_flag + a * 16 + tid, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            BB_DBG(37);
+        } else {
+            float* rec = p.record + (size_t)a * 5;
+            rec[0] = act[0];
+            rec[1] = s[0];
+            rec[2] = s[1];
+            rec[3] = s[2];
+            rec[4] = r;
+            if (p.next_state) {
+                p.next_state[a * 3 + 0] = s[0];
+                p.next_state[a * 3 + 1] = s[1];
+                p.next_state[a * 3 + 2] = s[2];
+            }
+            BB_DBG(37);
+            // "records ready" for the all-gather that waits on another stream (comm.hpp): the last agent's workgroup
+            // publishes the sequence number once every agent's record is in HBM.  No event, no extra packet on the
+            // launch stream.
+            publish_records_done(p.done_flag, p.done_count, done_value_s, gridDim.x);
+        }
+        BB_DBG(43);      // completion stored; slot 42: this pass's request accepted, 44: its first model step
+    };
     for (;;) {      // one pass per control step; a single pass unless LINGER
         // (a resident pass arrives here with the distribution in LDS, the state in s0..s2 and its first draws on their way:
         // see the hand-off at the end of the loop)
@@ -657,7 +720,16 @@ __global__ void k_fused_pendulum(FusedArgs p) {
 #ifdef BBMPC_KERNEL_DBG
         if (p.dbg && tid == 0 && a == 0) dbg_lds[41] = (long long)clock64();
 #endif
-        // ---- state carried to the next control step
+        // ---- OptimizerBase.__call__ tail (optimizer_base.py:82-94).  (Running it from thread 0's own row-0 mean in front of
+        // CEM's last statistics barrier was built too: inlined into the iteration loop it put spill reloads into the
+        // selection, profiles/control_step_tail.md.)
+        if (tail_lanes) tail(action0);
+        // ---- state carried to the next control step, BEHIND the publish: the caller waits for the record, not for these.
+        // Invariant this rests on: nothing reads mean_out / var_out / prev_mean between the completion and the end of
+        // the kernel.  The host's readers (bbmpc_get_state, the traces, every entry point but bbmpc_optimize,
+        // bbmpc_optimize_gather and bbmpc_gather_wait) settle the handle first -- Engine::settle ends a resident kernel and
+        // joins the stream -- and the next control step is either a launch on the same stream or a resident pass, which
+        // starts from the registers kept here (m_keep), or from the copies this very thread stores below.
         if (OPT != FOPT_RS) {
             for (int j = tid; j < p.HU; j += nthr) {
                 p.mean_out[a * p.HU + j] = mean[j];
@@ -674,43 +746,10 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 }
             }
         }
-
-        // ---- OptimizerBase.__call__ tail (optimizer_base.py:82-94)
-        if (tid == 0) {
-            FinalArgs fa;
-            fa.A = p.A; fa.U = 1; fa.S = 3;
-            fa.agent_offset = p.agent_offset;
-            fa.fix_q1 = p.fix_q1; fa.fix_q7 = p.fix_q7;
-            fa.add_noise = add_noise_s;
-            fa.lo = p.lo; fa.hi = p.hi;
-            fa.inj = p.inj_expl;
-            fa.key = key_s;
-            fa.key.q_per_agent = 1;
-            float s[3] = {s0, s1, s2};
-            float act[1];
-            act[0] = exploration_action(fa, a, 0, action0);
-            const float r = model.step(s, act);
-            float* rec = p.record + (size_t)a * 5;
-            rec[0] = act[0];
-            rec[1] = s[0];
-            rec[2] = s[1];
-            rec[3] = s[2];
-            rec[4] = r;
-            if (p.next_state) {
-                p.next_state[a * 3 + 0] = s[0];
-                p.next_state[a * 3 + 1] = s[1];
-                p.next_state[a * 3 + 2] = s[2];
-            }
-            // "records ready" for the all-gather that waits on another stream (comm.hpp): the last agent's workgroup
-            // publishes the sequence number once every agent's record is in HBM.  No event, no extra packet on the
-            // launch stream.
-            if constexpr (LINGER) publish_records_done(p.done_flag + a * 16, nullptr, done_value_s, 1u);    // this agent's own completion word
-            else publish_records_done(p.done_flag, p.done_count, done_value_s, gridDim.x);
-            BB_DBG(43);      // completion word stored; slot 42: this pass's request accepted, 44: its first model step
+        BB_DBG(34);
 #ifdef BBMPC_KERNEL_DBG
-            if (p.dbg && a == 0) for (int i = 0; i < 48; ++i) p.dbg[i] = dbg_lds[i];
+        if (p.dbg && a == 0 && tid == 0) for (int i = 0; i < 48; ++i) p.dbg[i] = dbg_lds[i];
 #endif
-        }
         if constexpr (!LINGER) {
             break;
         } else {
@@ -727,7 +766,11 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             // this thread has just written itself), and every thread fetches its first draws from where the next request
             // will most likely point.  Behind the request there is one barrier.  (Wave 0 fetches its draws in front of the
             // poll like everybody else: its first read of the request line waits for them, a device-memory round trip at a
-            // moment when the host has not even seen this pass's completion word.)
+            // moment when the host has not even seen this pass's completion line.)
+            // The answer goes back the same way (the kernel's tail above): a self-validating 64-byte completion line per
+            // agent that carries the record itself, stored by relaxed stores with nothing waited for in front; the state
+            // carried to the next step (mean_out / var_out / prev_mean) is stored behind it, off the caller's critical path.
+            // A workgroup that leaves has stored the line of every step it served before it says so in `gone` (a release).
             unsigned* mb = (unsigned*)ekeys;                       // 16 words of LDS that are idle outside the top-k
             __syncthreads();                                       // mean[] / ekeys / red have been read for the last time
             dist_init(keep_init);

@@ -367,20 +367,29 @@ struct FinalArgs {
     RngKey key;
 };
 
-__device__ __forceinline__ float exploration_action(const FinalArgs& p, int a, int u, float act) {
-    if (!p.add_noise) return act;
+// The exploration step in two parts: the additive term depends on the control step's key (or the injected draw) and the
+// bounds only, not on the optimizer's result, so a caller may evaluate it long before the action exists (the persistent
+// pendulum kernel does, kernels_fused.hpp); applying it is one add and a clip.  Together they are exploration_action,
+// operation for operation.
+__device__ __forceinline__ float exploration_noise(const FinalArgs& p, int a, int u, float lo, float hi) {
     float xi;
     if (p.inj) xi = p.inj[a * p.U + u];
     else {
         U4 b = rng_block(rng_key_now(p.key), 10u /*BBMPC_NOISE_EXPLORATION*/, 0u, 0u, (uint32_t)(p.agent_offset + a), (uint32_t)u);
         xi = word_to_trunc_normal(pick_word(b, (uint32_t)u));
     }
-    const float lo = p.lo[u], hi = p.hi[u];
     const float d = lo - hi;
     const float var = (d * d) / 16.0f * 0.05f;                    // optimizer_base.py:46-48
     const float mean = p.fix_q7 ? 0.0f : (hi + lo) / 2.0f;        // :49-50 (quirk Q7: bounds midpoint)
-    const float noise = xi * sqrtf(var) + mean;                   // :83-86
+    return xi * sqrtf(var) + mean;                                // :83-86
+}
+__device__ __forceinline__ float exploration_apply(float act, float noise, float lo, float hi) {
     return clipf(act + noise, lo, hi);                            // :87-90
+}
+__device__ __forceinline__ float exploration_action(const FinalArgs& p, int a, int u, float act) {
+    if (!p.add_noise) return act;
+    const float lo = p.lo[u], hi = p.hi[u];
+    return exploration_apply(act, exploration_noise(p, a, u, lo, hi), lo, hi);
 }
 
 __device__ __forceinline__ void finalize_pendulum_agent(const FinalArgs& p, int a, float action_in) {
