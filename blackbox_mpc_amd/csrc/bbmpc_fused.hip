@@ -158,7 +158,6 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     fa.fix_q7 = fix(BBMPC_FIX_Q7_EXPL_NOISE_ZERO_MEAN);
     fa.add_noise = add_noise;
     fa.warm_start = fix(BBMPC_FIX_Q2_CEM_WARM_START);
-    fa.balance = sw.balance;
     if (tail_flag) {
         fa.done_flag = tail_flag; fa.done_count = tail_count; fa.done_value = tail_value;
         tail_attached = true;
@@ -221,7 +220,7 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     const int pf_nit = cfg.optimizer == BBMPC_OPT_RANDOM_SEARCH ? 1 : iters;
     if (pf_mode < 0) {
         const char* ev = getenv("BBMPC_NOISE_PREFETCH");
-        pf_step_floats = (size_t)pf_nit * A * Nst * ((HU + 3) / 4) * 4;
+        pf_step_floats = U == 1 ? noise_step_floats(pf_nit, A, Nst, H) : (size_t)pf_nit * A * Nst * ((HU + 3) / 4) * 4;
         const size_t budget = (size_t)128 << 20;     // bytes per chunk buffer
         pf_steps = pf_step_floats ? (int)std::min<size_t>(8, budget / (pf_step_floats * 4)) : 0;
         pf_mode = ((ev ? atoi(ev) != 0 : true) && pf_steps >= 1 && U == 1) ? 1 : 0;
@@ -234,7 +233,13 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
             }
             HIP_CHECK(hipEventCreateWithFlags(&pf_free, hipEventDisableTiming));
             for (int b = 0; b < 2; ++b) {
-                d_noise_pf[b].alloc(pf_step_floats * pf_steps);
+                // The rollout loads its draws through a walking pointer with no clamp at a row's end: up to two float4 past
+                // the last row of the buffer (noise_extent.hpp).  The pad behind the chunk holds them; it is no part of
+                // pf_chunk_floats, no fill ever writes it, and it holds NaNs (all bits set) from here on -- a draw from
+                // there that reached a result would show as the -1e6 reward rule.
+                const size_t pad = noise_pad_floats(H);
+                d_noise_pf[b].alloc(noise_alloc_floats(pf_steps, pf_nit, A, Nst, H));
+                HIP_CHECK(hipMemset(d_noise_pf[b].p + pf_step_floats * pf_steps, 0xff, pad * sizeof(float)));
                 HIP_CHECK(hipEventCreateWithFlags(&pf_done[b], hipEventDisableTiming));
             }
         }
@@ -272,6 +277,10 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     const int per = (N + ilp - 1) / ilp;
     const int threads = std::min(1024, std::max(((per + 63) / 64) * 64, ((std::max(k, 1) + 63) / 64) * 64));   // top-k needs k <= threads
     const int HUp = (HU + 3) & ~3, kp = (std::max(k, 1) + 3) & ~3;
+    // (the kernel's carve, in its order: rewards | mean | var | sigma | eidx | red | hist | ekeys.  The prefetched-draws
+    // rollout reads one float4 past mean[HUp] and past sigma[HUp] when H is a multiple of four: var and eidx (kp >= 4) lie
+    // behind them.  A reorder keeps 16 bytes of the carve behind both, or pads them here and there.)
+    static_assert(TOPK_HIST_WORDS % 4 == 0, "every piece of the carve is a multiple of 16 bytes");
     const size_t lds_base = (size_t)(Nst + 3 * HUp + kp + 64 + TOPK_HIST_WORDS + 2 * kp) * 4;
     const size_t lds_samples = (size_t)HU * Nst * 4;
     prof_begin();

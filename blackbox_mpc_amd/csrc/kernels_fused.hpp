@@ -17,6 +17,7 @@
 #include "kernels_opt.hpp"
 #include "kernels_refit.hpp"
 #include "kernels_rollout.hpp"
+#include "noise_extent.hpp"
 #include "topk.hpp"
 
 namespace bbmpc {
@@ -32,7 +33,6 @@ struct FusedArgs {
     int agent_offset;
     int fix_q1, fix_q7, add_noise;
     int warm_start;          // CEM: BBMPC_FIX_Q2 (keep the mean across control steps)
-    int balance;             // progress-balanced wave priorities in the rollout (BBMPC_BALANCE, default off)
     unsigned* done_flag;     // optional completion counter in signal memory (see the kernel's tail), else null;
                              // LINGER: [A][16] pinned completion lines, which carry the records (p.record is not written)
     unsigned* done_count;
@@ -78,10 +78,8 @@ struct FusedArgs {
     unsigned long long pf_step_floats, pf_chunk_floats;      // floats per control step / per chunk buffer (0 = no prediction)
 };
 
-// float4 index of particle n's first Philox block in the layout k_noise_fill writes, [it][A][Nst][Q]
-__device__ __forceinline__ size_t noise_block_index(int it, int A, int a, int Nst, int n, int Q) {
-    return (((size_t)it * A + a) * Nst + n) * Q;
-}
+// (noise_block_index: the float4 index of particle n's first Philox block in the layout k_noise_fill writes,
+// [it][A][Nst][Q], and how far behind it the rollout reads: noise_extent.hpp)
 
 // phase clocks for kernel development: build with -DBBMPC_KERNEL_DBG and run with BBMPC_DBG=1
 #ifdef BBMPC_KERNEL_DBG
@@ -111,6 +109,10 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid, int nw)
 
 // LDS carve (4-byte words): rewards[Nst] | mean[HUp] | var[HUp] | sigma[HUp] | eidx[kp] | red[64] | hist[272] |
 //                            ekeys[2*kp] | samples[HU][Nst]      (every piece a multiple of 16 B)
+// INVARIANT (the INJ == 2 rollout rests on it): mean[] and sigma[] are each FOLLOWED by at least 16 bytes of this carve.
+// With H a multiple of four the rollout reads one float4 past mean[HUp] and past sigma[HUp] -- here: var[0..3] and
+// eidx[0..3] (kp >= 4) -- and never uses it.  Whoever reorders the carve keeps a piece behind both, or pads them by a block
+// (and Engine::optimize_fused's lds_base with them).
 #ifndef BBMPC_FUSED_ACTIONS_AHEAD
 #define BBMPC_FUSED_ACTIONS_AHEAD 1
 #endif
@@ -181,7 +183,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             if (tid < p.N) {                 // the lanes past the population roll nothing out
                 const pfvec4p q = (pfvec4p)(reinterpret_cast<const float4*>(base) + noise_block_index(it_n, p.A, a, p.Nst, tid, Q));
                 pf0 = q[0];
-                if (OPT != FOPT_SPSA) pf1 = q[min(1, Q - 1)];
+                if (OPT != FOPT_SPSA) pf1 = q[1];          // (Q == 1: past the row, never used -- noise_extent.hpp)
             }
         }
     };
@@ -308,7 +310,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     for (int b = 0; b < nb4; ++b) {
                         float d[4];
                         if constexpr (INJ == 2) {
-                            const gvec4s nxt4 = mine4[min(b + 1, nb4 - 1)];
+                            const gvec4s nxt4 = mine4[b + 1];        // (the last one: past the row, never used -- noise_extent.hpp)
                             d[0] = cur4.x; d[1] = cur4.y; d[2] = cur4.z; d[3] = cur4.w;
                             cur4 = nxt4;
                         } else if (INJ == 1) {
@@ -353,9 +355,6 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 // recurrence; the Philox rounds (a quarter of this kernel's VALU work) are gone from the critical path.
                 const int Q = (p.HU + 3) >> 2;
                 const float4* inj4 = reinterpret_cast<const float4*>(inj_s);
-                int* prog = (int*)red;                             // per-wave progress (red[] is idle during the rollout)
-                const int wave = tid >> 6, lane = tid & 63;
-                const bool balance = p.balance != 0 && nw > 4 && nw <= 64 && p.N <= nthr;
                 // The rollout is bound by instruction issue, so what is uniform for the launch is decided ONCE
                 // here and not once per model step: quirk Q1's choice of the action-cost term (Q1c) and the row stride of
                 // samp[t][n] (NSTc: a compile-time stride turns the sample stores' addresses into immediate offsets of one
@@ -364,7 +363,6 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 constexpr bool Q1 = decltype(Q1c)::value;
                 constexpr int NSTC = decltype(NSTc)::value;
                 const size_t nst = NSTC ? (size_t)NSTC : (size_t)p.Nst;
-                const int nbp = HUp >> 2;                          // float4 blocks of the padded mean[] / sigma[]
                 for (int n = tid; n < p.N; n += nthr) {
                     Roller<FASTM> roll;
                     roll.init(p.fix_q1 != 0, s0, s1, s2);
@@ -376,20 +374,36 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     // block it had just prefetched: one memory round trip per eight model steps)
                     typedef float gvec4 __attribute__((ext_vector_type(4)));
                     typedef const __attribute__((address_space(1))) gvec4* gvec4p;
-                    const gvec4p mine = (gvec4p)(inj4 + noise_block_index(it, p.A, a, p.Nst, n, Q));
-                    auto ld = [&](int b) { const gvec4 v = mine[min(b, Q - 1)]; return make_float4(v.x, v.y, v.z, v.w); };
+                    // The pointer WALKS the row, and a load names its block by a constant distance from it (an immediate offset).
+                    // It steps two blocks at the TOP of a trip (there the add's result can take the register of its operand;
+                    // stepped at the foot, the add is scheduled in front of the trip's last load and costs a copy), so it
+                    // stands at the trip's first block inside a trip and TWO BLOCKS BEHIND the block the code is at outside one:
+                    // `ahead` below counts from the pointer.  No clamp at the row's end: the last trip's loads of blocks b + 2 /
+                    // b + 3 may lie up to two float4 past the row -- in the next row or in the pad behind the chunk buffer
+                    // (noise_extent.hpp) -- and are never used.
+                    gvec4p mine = (gvec4p)((uintptr_t)(inj4 + noise_block_index(it, p.A, a, p.Nst, n, Q)) - 2 * sizeof(float4));
+                    auto ld = [&](int ahead) { const gvec4 v = mine[ahead]; return make_float4(v.x, v.y, v.z, v.w); };
                     // sigma[4b .. 4b + 3] / mean[4b .. 4b + 3] (16-byte aligned, padded to a multiple of four) are read ONE block ahead
                     // of the model steps that use them: behind the previous block's recurrence, not in front of their own, where
-                    // the LDS round trip stopped the chain at the top of every block.  (past the last block: the last one again)
+                    // the LDS round trip stopped the chain at the top of every block.  Two bases that walk with the loop as the
+                    // draws' pointer does (two blocks behind outside a trip), the block named by its constant distance from them.  No clamp: with H a multiple of four the last block
+                    // reads one float4 past sigma[HUp] and mean[HUp], which the carve keeps inside this workgroup's LDS (see
+                    // the invariant at the carve), and nobody uses it.
+                    // (The bases are LDS addresses held in VGPRs, and the compiler is not told that they are uniform: knowing it,
+                    // it walks them in SGPRs and pays a scalar add and a v_mov per block to hand each to the LDS instruction.)
                     struct SigMean { float4 sg, mn; };
-                    auto rd = [&](int b) {
+                    typedef const __attribute__((address_space(3))) gvec4* lvec4p;
+                    uint32_t sga = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)sigma - 2 * (uint32_t)sizeof(float4);
+                    uint32_t mna = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)mean - 2 * (uint32_t)sizeof(float4);
+                    asm volatile("" : "+v"(sga), "+v"(mna));
+                    auto rd = [&](int ahead) {
                         SigMean r;
                         if (OPT == FOPT_RS) {
                             r.sg = r.mn = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                         } else {
-                            const int bb = min(b, nbp - 1);
-                            r.sg = *reinterpret_cast<const float4*>(sigma + 4 * bb);
-                            r.mn = *reinterpret_cast<const float4*>(mean + 4 * bb);
+                            const gvec4 sg = ((lvec4p)(uintptr_t)sga)[ahead], mn = ((lvec4p)(uintptr_t)mna)[ahead];
+                            r.sg = make_float4(sg.x, sg.y, sg.z, sg.w);
+                            r.mn = make_float4(mn.x, mn.y, mn.z, mn.w);
                         }
                         return r;
                     };
@@ -415,47 +429,37 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     // the last use of both, so the loads of block b + 2's draws and of block b + 1's sigma / mean are issued
                     // right there INTO THE SAME REGISTERS and run beside this block's recurrence: no copy at a loop's foot, and
                     // neither the memory nor the LDS round trip ever stands in front of a model step.
-                    SigMean m = rd(0);
-                    auto block4 = [&](float4& z, int b, int row0, bool more) {
+                    SigMean m = rd(2);
+                    auto block4 = [&](float4& z, int ahead, int row0, bool more) {      // ahead: blocks from where the bases stand to this one
                         float x[4] = {action(z.x, m.sg.x, m.mn.x), action(z.y, m.sg.y, m.mn.y), action(z.z, m.sg.z, m.mn.z), action(z.w, m.sg.w, m.mn.w)};
 #if BBMPC_FUSED_ACTIONS_AHEAD
 #pragma unroll
                         for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(x[i]));
 #endif
-                        if (more) z = ld(b + 2);                 // draws: two blocks (8 steps, ~2 us) ahead of their use
-                        m = rd(b + 1);                           // (also what the remainder steps behind the last block use)
+                        if (more) z = ld(ahead + 2);             // draws: two blocks (8 steps, ~2 us) ahead of their use
+                        m = rd(ahead + 1);                       // (also what the remainder steps behind the last block use)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) step1(row0 + i, x[i]);
                     };
                     float4 c0, c1;
                     if (n == tid) { c0 = make_float4(pf0.x, pf0.y, pf0.z, pf0.w); c1 = make_float4(pf1.x, pf1.y, pf1.z, pf1.w); }   // fetched an iteration ago
-                    else { c0 = ld(0); c1 = ld(1); }
-                    int b = 0;
+                    else { c0 = ld(2); c1 = ld(3); }
 #ifdef BBMPC_KERNEL_DBG
                     if (it == 0 && n == tid) { asm volatile("" :: "v"(c0.x)); BB_DBG(44); }     // the first draws are there
 #endif
-                    // Waves that share a SIMD (wave ids equal mod 4) run the same instruction stream, and the arbiter
-                    // favours the older one: it finishes early and the younger one then runs alone at a lone wave's
-                    // issue rate (measured: 4.5 us vs 6.0 us for the two halves of a 500-particle population).  Each
-                    // wave publishes its block counter in LDS and lowers its priority while it is ahead of a SIMD mate.
-                    if (balance && lane == 0) prog[wave] = 0;
-                    for (; b + 1 < nblk; b += 2) {
-                        if (balance) {
-                            if (lane == 0) prog[wave] = b;
-                            int behind = b;
-                            for (int w2 = wave & 3; w2 < nw; w2 += 4) behind = min(behind, prog[w2]);
-                            if (behind < b) __builtin_amdgcn_s_setprio(0);
-                            else __builtin_amdgcn_s_setprio(2);
-                        }
-                        block4(c0, b, 0, true);
-                        block4(c1, b + 1, 4, true);
+                    // (Waves that share a SIMD run the same instruction stream and the arbiter favours the older one; pacing
+                    // them against each other through LDS progress words or s_setprio was measured slower both times and is
+                    // gone: profiles/rollout_loop_issue_slots.md 5.  BBMPC_BALANCE is still accepted and does nothing.)
+                    for (int trips = nblk >> 1; trips > 0; --trips) {      // two blocks a trip; every base steps once
+                        mine += 2;
+                        sga += 2 * (uint32_t)sizeof(float4);
+                        mna += 2 * (uint32_t)sizeof(float4);
+                        asm volatile("" : "+v"(mine), "+v"(sga), "+v"(mna));      // three adds, not one shared scalar offset and an add per base per trip to apply it
+                        block4(c0, 0, 0, true);
+                        block4(c1, 1, 4, true);
                         if constexpr (NSTC != 0) sp += 8 * nst;
                     }
-                    if (balance) {
-                        if (lane == 0) prog[wave] = 1 << 30;
-                        __builtin_amdgcn_s_setprio(0);
-                    }
-                    if (b < nblk) { block4(c0, b, 0, false); c0 = c1; ++b; if constexpr (NSTC != 0) sp += 4 * nst; }
+                    if (nblk & 1) { block4(c0, 2, 0, false); c0 = c1; if constexpr (NSTC != 0) sp += 4 * nst; }
                     if (rem > 0) step1(0, action(c0.x, m.sg.x, m.mn.x));
                     if (rem > 1) step1(1, action(c0.y, m.sg.y, m.mn.y));
                     if (rem > 2) step1(2, action(c0.z, m.sg.z, m.mn.z));
