@@ -30,6 +30,7 @@ NOISE_TRUNC_NORMAL, NOISE_UNIFORM, NOISE_RADEMACHER, NOISE_NORMAL, NOISE_PSO_SCA
 NOISE_PSO_RESEED_TRUNC, NOISE_PSO_RESEED_UNIFORM, NOISE_PSO_RESET_POS, NOISE_PSO_RESET_VEL = 6, 7, 8, 9
 NOISE_EXPLORATION = 10
 NOISE_PROCESS = 11                                      # [iters][A,P,H,S] N(0,1): the particle evaluator's process noise
+NOISE_POLICY = 12                                       # [iters][A,K,H,U] N(0,1): the policy prior's action noise
 MAX_PARTICLES = 64
 RISK_MEAN_STD, RISK_CVAR = 0, 1                         # bbmpc_set_particle_risk
 MAX_QUANTILE_LEVELS = 8                                 # bbmpc_predict_trajectory_quantiles
@@ -94,6 +95,8 @@ SYMBOLS = [
     "bbmpc_set_elite_carry", "bbmpc_get_elite_carry",
     "bbmpc_set_reward_mlp",
     "bbmpc_set_terminal_value_mlp", "bbmpc_evaluate_terminal_value", "bbmpc_evaluate_terminal_value_dev",
+    "bbmpc_set_policy_prior_mlp", "bbmpc_get_policy_prior", "bbmpc_evaluate_policy_prior", "bbmpc_evaluate_policy_prior_dev",
+    "bbmpc_predict_policy_rollouts", "bbmpc_predict_policy_rollouts_dev",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -131,6 +134,13 @@ def _load():
                                                  ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.c_float]
     lib.bbmpc_evaluate_terminal_value.argtypes = [vp, vp, i32, vp]
     lib.bbmpc_evaluate_terminal_value_dev.argtypes = [vp, vp, i32, vp]
+    lib.bbmpc_set_policy_prior_mlp.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
+                                               ctypes.POINTER(vp), i32, ctypes.POINTER(vp), i32, ctypes.c_float]
+    lib.bbmpc_get_policy_prior.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float)]
+    lib.bbmpc_evaluate_policy_prior.argtypes = [vp, vp, i32, vp]
+    lib.bbmpc_evaluate_policy_prior_dev.argtypes = [vp, vp, i32, vp]
+    lib.bbmpc_predict_policy_rollouts.argtypes = [vp, vp, vp, vp, vp]
+    lib.bbmpc_predict_policy_rollouts_dev.argtypes = [vp, vp, vp, vp, vp]
     lib.bbmpc_reset.argtypes = [vp]
     lib.bbmpc_optimize.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.bbmpc_optimize_dev.argtypes = [vp, vp, i32, i32, vp, vp]

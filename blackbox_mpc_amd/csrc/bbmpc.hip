@@ -616,6 +616,9 @@ void Engine::set_elite_carry(int keep, int shift) {
             "elite carry: keep and shift must not exceed num_elite = " + std::to_string(k));
     REQUIRE(keep < N && shift < N, BBMPC_E_INVALID,
             "elite carry: keep and shift must be below population_size = " + std::to_string(N));
+    REQUIRE(!prior_on() || (long)prior_K + std::max(keep, shift) < (long)N, BBMPC_E_INVALID,
+            "elite carry: policy prior count + max(keep, shift) = " + std::to_string((long)prior_K + std::max(keep, shift)) +
+                " must be below population_size = " + std::to_string(N));
     invalidate_step_graph();
     const size_t need = (size_t)A * HU * std::max(keep, shift);
     if (d_carry.n != need) {
@@ -651,9 +654,17 @@ const float* Engine::dense_actions(const float* d_actions, int astride, int batc
 void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
     // bbmpc_set_elite_carry (CEM): the candidates go to the sample buffer, the stored elites over its last columns
     const bool carry = carry_on() && cfg.optimizer == BBMPC_OPT_CEM && mode == SRC_TRUNC;
-    if ((corr_on() || carry) && mode == SRC_TRUNC) {      // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
+    // bbmpc_set_policy_prior_mlp (CEM): the policy's rollouts over the columns in front of the carried ones
+    const bool prior = prior_on() && cfg.optimizer == BBMPC_OPT_CEM && mode == SRC_TRUNC;
+    if ((corr_on() || carry || prior) && mode == SRC_TRUNC) {      // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
         if (corr_on()) draw_candidates_corr(ra);
         else draw_candidates(SRC_TRUNC, ra);
+        if (prior) {
+            const int c_i = carry ? carry_inject : 0;
+            REQUIRE(ra.n_pop == N && ra.HU == HU && ra.H == H && ra.Nst == Nst && N - c_i - prior_K >= 0, BBMPC_E_INVALID, "internal: policy prior shape");
+            policy_prior_rollouts(ra.state, prior_sigma != 0.0f ? policy_noise(ra.key.step, ra.iter) : nullptr, ra.samples, Nst,
+                                  N - c_i - prior_K, nullptr, nullptr);
+        }
         if (carry && carry_inject > 0) {
             REQUIRE(ra.n_pop == N && ra.HU == HU && ra.Nst == Nst && carry_inject < N && d_carry.p, BBMPC_E_INVALID, "internal: elite carry shape");
             hipLaunchKernelGGL(k_elite_inject, dim3((HU * carry_inject + CARRY_THREADS - 1) / CARRY_THREADS, A), dim3(CARRY_THREADS), 0, stream, HU, Nst,
@@ -902,7 +913,7 @@ RefitArgs Engine::refit_args() const {
 // samples from is a constant of the handle -- the rollout samples from the constants directly and reads the state from the
 // pinned buffer itself (its workgroup 0 stores it for the later launches).  What else must hold is the optimizer's own.
 bool Engine::dist_init_skippable() const {
-    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() &&
+    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() && !prior_on() &&
            iters >= 1 && pi2_copy_seen && stage_state_src != nullptr;
 }
 
@@ -1362,6 +1373,14 @@ void Engine::inject(int kind, const float* data, int64_t count) {
             HIP_CHECK(hipMemcpy(b.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
             break;
         }
+        case BBMPC_NOISE_POLICY: {
+            REQUIRE(prior_on(), BBMPC_E_STATE, "policy noise: call bbmpc_set_policy_prior_mlp first (the layout depends on count)");
+            REQUIRE(count == (int64_t)A * prior_K * HU * std::max(iters, 1), BBMPC_E_INVALID, "policy noise must be [iters][A,K,H,U]");
+            auto& b = inj[kind];
+            b.alloc((size_t)count);
+            HIP_CHECK(hipMemcpy(b.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
+            break;
+        }
         case BBMPC_NOISE_EXPLORATION: {
             REQUIRE(count == (int64_t)A * U, BBMPC_E_INVALID, "exploration noise must be [A,U]");
             auto& b = inj[kind];
@@ -1406,6 +1425,10 @@ void Engine::dump_noise(int kind, int control_step, int iteration, float* out, i
     int n = auto_split > 1 ? N * auto_split : N, a = A, hu = HU;       // (draws are keyed by the global particle)
     if (kind == BBMPC_NOISE_PROCESS) {
         dump_process_noise(control_step, iteration, out, count);
+        return;
+    }
+    if (kind == BBMPC_NOISE_POLICY) {
+        dump_policy_noise(control_step, iteration, out, count);
         return;
     }
     RngKey kk = key((uint32_t)control_step);
@@ -1796,7 +1819,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                 // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
                 // replayed as a graph (engine.hpp: step_graph)
                 const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&
-                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && e.stream == e.own_stream && !e.any_injected();
+                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && !e.prior_on() && e.stream == e.own_stream && !e.any_injected();
                 const uint64_t sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
                 bool replayed = false;
                 if (graph_ok && e.step_graph && e.step_graph_sig == sig) {

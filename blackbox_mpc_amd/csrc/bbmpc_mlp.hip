@@ -12,6 +12,7 @@
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
 #include "kernels_mlp_traj_particles.hpp"
+#include "kernels_policy_prior.hpp"
 
 namespace bbmpc {
 
@@ -198,6 +199,9 @@ void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* 
         lv_heads = 0;                           // (one head per member: bbmpc_set_mlp_logvar_head comes after this call)
         return;
     }
+    REQUIRE(!prior_on(), BBMPC_E_UNSUPPORTED,
+            "a model ensemble beside a policy prior (bbmpc_set_policy_prior_mlp): the policy rollout is the noise-free step of one model; "
+            "remove the policy network first (n_layers = 0)");
     REQUIRE(w && b, BBMPC_E_INVALID, "null argument");
     const int L = mlp.n_layers;
     for (int i = 0; i < E * L; ++i) REQUIRE(w[i] && b[i], BBMPC_E_INVALID, "null weight/bias pointer");
@@ -236,6 +240,9 @@ void Engine::set_mlp_logvar_head(int num_heads, const float* const* w, const flo
         lv_heads = 0;
         return;
     }
+    REQUIRE(!prior_on(), BBMPC_E_UNSUPPORTED,
+            "log-variance heads beside a policy prior (bbmpc_set_policy_prior_mlp): the policy rollout is the noise-free step of one model; "
+            "remove the policy network first (n_layers = 0)");
     REQUIRE(w && b && min_logvar && max_logvar, BBMPC_E_INVALID, "null argument");
     const int want = std::max(1, ens_E);
     REQUIRE(num_heads == want, BBMPC_E_INVALID,
@@ -931,7 +938,290 @@ void Engine::traj_mlp_reward_mlp(const float* d_states, const float* d_seq, int 
     reward_mlp_rows(q);
 }
 
+// ------------------------------------------------------------------------------------------------
+// learned policy prior (bbmpc_set_policy_prior_mlp; kernels_policy_prior.hpp)
+// ------------------------------------------------------------------------------------------------
+// Everything is checked and packed on the host before the handle is touched, so a refusal leaves it as it was.
+// n_layers = 0 removes the network.
+void Engine::set_policy_prior_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
+                                  int is_normalized, const float* const* stats, int count, float noise_std) {
+    if (n_layers == 0) {                        // back to the routing the handle had: nothing else of it was ever changed
+        if (!prior_ready) return;
+        invalidate_step_graph();
+        HIP_CHECK(hipStreamSynchronize(stream));
+        prior_ready = false;
+        prior_K = 0;
+        prior_noise_valid = false;
+        inj.erase(BBMPC_NOISE_POLICY);
+        return;
+    }
+    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
+    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "policy prior: n_layers must be >= 0");
+    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "policy prior: 1..8 Dense layers are supported");
+    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
+    REQUIRE(dims[0] == S, BBMPC_E_INVALID,
+            "policy prior: dims[0] = " + std::to_string(dims[0]) + " but the network reads the state, dim_s = " + std::to_string(S));
+    REQUIRE(dims[n_layers] == U, BBMPC_E_INVALID,
+            "policy prior: dims[n_layers] = " + std::to_string(dims[n_layers]) + " but the network returns an action, dim_u = " + std::to_string(U));
+    for (int l = 0; l < n_layers; ++l) {
+        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
+        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
+    }
+    if (is_normalized) {
+        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
+        for (int i = 0; i < 4; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
+    }
+    REQUIRE(std::isfinite(noise_std) && noise_std >= 0.0f, BBMPC_E_INVALID, "policy prior: noise_std must be finite and >= 0");
+    REQUIRE(count >= 1, BBMPC_E_INVALID, "policy prior: count must be >= 1");
+    for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= POLICY_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
+    REQUIRE(cfg.optimizer == BBMPC_OPT_CEM, BBMPC_E_UNSUPPORTED,
+            "a policy prior with an optimizer other than CEM: only CEM's candidates are replaced between the draw and the rollout");
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
+            "a policy prior rolls the policy through a learned model: the handle needs BBMPC_DYN_MLP, not analytic or user dynamics");
+    REQUIRE(!user_callbacks(), BBMPC_E_UNSUPPORTED, "a policy prior beside a callback plug-in: the step-wise rollout draws for itself");
+    REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED,
+            "a policy prior beside an inverse target transform: the policy rollout's model step is next = dev + state");
+    REQUIRE(!pop_sharded() && cfg.population_global <= N && auto_split <= 1, BBMPC_E_UNSUPPORTED,
+            "a policy prior with a sharded population: the sharded control steps draw inside their rollout kernels");
+    REQUIRE(ens_E == 0 && lv_heads == 0, BBMPC_E_UNSUPPORTED,
+            "a policy prior beside a model ensemble or log-variance heads: the policy rollout is the noise-free step of one model");
+    REQUIRE((long)count + carry_stride() < (long)N, BBMPC_E_INVALID,
+            "policy prior: count + max(keep_elites, shift_elites) = " + std::to_string((long)count + carry_stride()) +
+                " must be below population_size = " + std::to_string(N));
+    REQUIRE((long)A * count * HU < (1L << 31), BBMPC_E_UNSUPPORTED, "policy prior: more than 2^31 noise elements per iteration");
+    MlpDesc d;
+    memset(&d, 0, sizeof(d));
+    d.n_layers = n_layers;
+    int hidden_tiles = 1;
+    for (int l = 0; l <= n_layers; ++l) {
+        d.dims[l] = dims[l];
+        d.tiles[l] = (dims[l] + 15) / 16;
+        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, d.tiles[l]);
+    }
+    const int pnw = std::min(16, hidden_tiles);
+    if (mlp_ready)
+        REQUIRE((size_t)policy_prior_lds_layout(mlp, d, U, S, std::max(pnw, mlp_nw)).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+                "policy prior: the activation / partial-sum buffers of the two networks do not fit one CU's LDS");
+    REQUIRE((size_t)policy_rows_lds_layout(d, U, S, pnw).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "policy prior: the activation / partial-sum buffers of this network do not fit one CU's LDS");
+    std::vector<float> w4[MLP_MAX_LAYERS], bp[MLP_MAX_LAYERS], st;
+    for (int l = 0; l < n_layers; ++l) {
+        d.act[l] = acts[l];
+        std::vector<float> wp;
+        mlp_pack_layer(d, l, w[l], b[l], wp, w4[l], bp[l]);
+    }
+    if (is_normalized) {
+        const int lens[4] = {S, S, U, U};
+        for (int i = 0; i < 4; ++i) st.insert(st.end(), stats[i], stats[i] + lens[i]);
+    }
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));
+    prior_ready = false;
+    if (count != prior_K) inj.erase(BBMPC_NOISE_POLICY);             // (its layout depends on K)
+    for (int l = 0; l < n_layers; ++l) {
+        upload(d_pr_wp4[l], w4[l]);
+        upload(d_pr_bp[l], bp[l]);
+        d.bpack[l] = d_pr_bp[l].p;
+    }
+    d.normalized = is_normalized ? 1 : 0;
+    if (is_normalized) {
+        upload(d_pr_stats, st);
+        d.mean_s = d_pr_stats.p;
+        d.std_s = d_pr_stats.p + S;
+        d.mean_t = d_pr_stats.p + 2 * S;
+        d.std_t = d_pr_stats.p + 2 * S + U;
+    }
+    const size_t ne = (size_t)A * count * HU;
+    if (d_pr_noise.n < ne) d_pr_noise.alloc(ne);
+    prior_mlp = d;
+    prior_nw = pnw;
+    prior_K = count;
+    prior_sigma = noise_std;
+    prior_noise_valid = false;
+    prior_ready = true;
+}
+
+// xi [A][K][H][U] of (control step, iteration): the injected tensor, or the handle's own draws, generated once per
+// (step, iteration)
+const float* Engine::policy_noise(uint32_t step, uint32_t iter) {
+    const size_t ne = (size_t)A * prior_K * HU;
+    if (const float* in = injected(BBMPC_NOISE_POLICY)) return in + ne * std::min<size_t>(iter, (size_t)std::max(iters, 1) - 1);
+    if (prior_noise_valid && prior_noise_step == step && prior_noise_iter == iter) return d_pr_noise.p;
+    RngKey kk = key(step);
+    kk.step_src = nullptr;
+    const int blocks = A * prior_K * (int)kk.q_per_agent;
+    hipLaunchKernelGGL(k_gen_policy_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, iter, A, prior_K, HU, cfg.agent_offset,
+                       d_pr_noise.p);
+    HIP_CHECK(hipGetLastError());
+    prior_noise_valid = true; prior_noise_step = step; prior_noise_iter = iter;
+    return d_pr_noise.p;
+}
+
+void Engine::dump_policy_noise(int control_step, int iteration, float* out, int64_t count) {
+    REQUIRE(prior_on(), BBMPC_E_STATE, "dump_noise: policy noise needs bbmpc_set_policy_prior_mlp first");
+    const int64_t total = (int64_t)A * prior_K * HU;
+    REQUIRE(count == total, BBMPC_E_INVALID, "dump_noise: policy noise is [A, K, H, U]");
+    RngKey kk = key((uint32_t)control_step);
+    kk.step_src = nullptr;
+    DevBuf<float> tmp;
+    tmp.alloc((size_t)total);
+    const int blocks = A * prior_K * (int)kk.q_per_agent;
+    hipLaunchKernelGGL(k_gen_policy_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, (uint32_t)iteration, A, prior_K, HU,
+                       cfg.agent_offset, tmp.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, tmp.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// The K policy rollouts of every agent from d_state [A][S]: into columns col0 .. col0 + K - 1 of `samples` [A][HU][nst]
+// (the control step), into d_actions_out [K,A,H,U] / d_states_out [K,A,H,S] (bbmpc_predict_policy_rollouts), or both.
+// One kernel, one instantiation per activation set, whoever calls.
+void Engine::policy_prior_rollouts(const float* d_state, const float* d_noise, float* samples, int nst, int col0, float* d_actions_out,
+                                   float* d_states_out) {
+    REQUIRE(prior_ready, BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    const int K = prior_K;
+    if (samples) REQUIRE(col0 >= 0 && col0 + K <= nst, BBMPC_E_INVALID, "internal: policy prior columns");
+    PolicyPriorArgs q;
+    memset(&q, 0, sizeof(q));
+    q.m = mlp;
+    q.pm = prior_mlp;
+    for (int l = 0; l < mlp.n_layers; ++l) q.wp4[l] = d_wpack4[l].p;
+    for (int l = 0; l < prior_mlp.n_layers; ++l) q.pwp4[l] = d_pr_wp4[l].p;
+    q.nw = std::max(mlp_nw, prior_nw);
+    q.K = K; q.A = A; q.H = H; q.S = S; q.U = U;
+    q.Nst = nst; q.col0 = col0;
+    q.sigma = prior_sigma;
+    q.state = d_state;
+    q.noise = d_noise;
+    q.lo = d_lo.p; q.hi = d_hi.p;
+    q.samples = samples;
+    q.actions_out = d_actions_out;
+    q.states_out = d_states_out;
+    if (prior_sigma != 0.0f) REQUIRE(d_noise, BBMPC_E_INVALID, "internal: policy prior noise");
+    const size_t lds = (size_t)policy_prior_lds_layout(mlp, prior_mlp, U, S, q.nw).total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "policy prior: the activation / partial-sum buffers of the two networks do not fit one CU's LDS");
+    bool ext = false;
+    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    for (int l = 0; l < prior_mlp.n_layers; ++l) ext = ext || prior_mlp.act[l] > BBMPC_ACT_SIGMOID;
+    const void* fn = ext ? (const void*)k_policy_prior_rollout<true> : (const void*)k_policy_prior_rollout<false>;
+    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+    dim3 grid((K + MLP_TP - 1) / MLP_TP, A), block(q.nw * 64);
+    if (ext) hipLaunchKernelGGL(k_policy_prior_rollout<true>, grid, block, lds, stream, q);
+    else hipLaunchKernelGGL(k_policy_prior_rollout<false>, grid, block, lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
+// pi on B rows of states [B][S] -> actions [B][U]: no noise, no clip
+void Engine::policy_prior_rows(const float* d_states, int batch, float* d_actions) {
+    REQUIRE(prior_ready, BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
+    REQUIRE(batch >= 1, BBMPC_E_INVALID, "batch must be >= 1");
+    PolicyRowsArgs q;
+    memset(&q, 0, sizeof(q));
+    q.pm = prior_mlp;
+    for (int l = 0; l < prior_mlp.n_layers; ++l) q.pwp4[l] = d_pr_wp4[l].p;
+    q.nw = prior_nw;
+    q.B = batch; q.S = S; q.U = U;
+    q.states = d_states;
+    q.actions = d_actions;
+    const size_t lds = (size_t)policy_rows_lds_layout(prior_mlp, U, S, prior_nw).total * sizeof(float);
+    bool ext = false;
+    for (int l = 0; l < prior_mlp.n_layers; ++l) ext = ext || prior_mlp.act[l] > BBMPC_ACT_SIGMOID;
+    const void* fn = ext ? (const void*)k_policy_prior_rows<true> : (const void*)k_policy_prior_rows<false>;
+    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
+    dim3 grid((batch + MLP_TP - 1) / MLP_TP), block(prior_nw * 64);
+    if (ext) hipLaunchKernelGGL(k_policy_prior_rows<true>, grid, block, lds, stream, q);
+    else hipLaunchKernelGGL(k_policy_prior_rows<false>, grid, block, lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace bbmpc
+
+extern "C" int bbmpc_set_policy_prior_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
+                                          const float* const* b, int32_t is_normalized, const float* const* stats, int32_t count,
+                                          float noise_std) {
+    API_BEGIN
+    CHECK_HANDLE(h);                     // (settles the handle: a resident control-step kernel is stopped first)
+    h->e->set_policy_prior_mlp(n_layers, dims, acts, w, b, is_normalized, stats, count, noise_std);
+    API_END
+}
+
+extern "C" int bbmpc_get_policy_prior(bbmpc_handle h, int32_t* count, float* noise_std) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(count);
+    CHECK_PTR(noise_std);
+    *count = h->e->prior_on() ? h->e->prior_K : 0;
+    *noise_std = h->e->prior_on() ? h->e->prior_sigma : 0.0f;
+    if (!h->e->prior_on()) throw bbmpc::HipError(BBMPC_E_STATE, "policy prior: no network installed");
+    API_END
+}
+
+extern "C" int bbmpc_evaluate_policy_prior_dev(bbmpc_handle h, const float* d_states, int32_t batch, float* d_actions) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_states);
+    CHECK_PTR(d_actions);
+    h->e->policy_prior_rows(d_states, batch, d_actions);
+    API_END
+}
+
+extern "C" int bbmpc_evaluate_policy_prior(bbmpc_handle h, const float* states, int32_t batch, float* actions) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(states);
+    CHECK_PTR(actions);
+    bbmpc::Engine& e = *h->e;
+    if (batch < 1) throw bbmpc::HipError(BBMPC_E_INVALID, "batch must be >= 1");
+    if (!e.prior_on()) throw bbmpc::HipError(BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
+    const size_t ns = (size_t)batch * e.S, na = (size_t)batch * e.U;
+    if (e.d_pr_io.n < ns + na) e.d_pr_io.alloc(ns + na);
+    float* ds = e.d_pr_io.p; float* da = ds + ns;
+    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
+    e.policy_prior_rows(ds, batch, da);
+    HIP_CHECK(hipMemcpyAsync(actions, da, na * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
+
+extern "C" int bbmpc_predict_policy_rollouts_dev(bbmpc_handle h, const float* d_states, const float* d_noise, float* d_actions_out,
+                                                 float* d_states_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_states);
+    bbmpc::Engine& e = *h->e;
+    if (!d_actions_out && !d_states_out) throw bbmpc::HipError(BBMPC_E_INVALID, "policy rollouts: actions_out and states_out are both NULL");
+    if (!e.prior_on()) throw bbmpc::HipError(BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
+    if (!d_noise && e.prior_sigma != 0.0f) d_noise = e.policy_noise(e.step_counter, 0);
+    e.policy_prior_rollouts(d_states, d_noise, nullptr, 0, 0, d_actions_out, d_states_out);
+    API_END
+}
+
+extern "C" int bbmpc_predict_policy_rollouts(bbmpc_handle h, const float* states, const float* noise, float* actions_out, float* states_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(states);
+    bbmpc::Engine& e = *h->e;
+    if (!actions_out && !states_out) throw bbmpc::HipError(BBMPC_E_INVALID, "policy rollouts: actions_out and states_out are both NULL");
+    if (!e.prior_on()) throw bbmpc::HipError(BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
+    if (!e.mlp_ready) throw bbmpc::HipError(BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    const size_t ns = (size_t)e.A * e.S, nn = noise ? (size_t)e.A * e.prior_K * e.HU : 0;
+    const size_t na = actions_out ? (size_t)e.prior_K * e.A * e.HU : 0, nso = states_out ? (size_t)e.prior_K * e.A * e.H * e.S : 0;
+    if (e.d_pr_io.n < ns + nn + na + nso) e.d_pr_io.alloc(ns + nn + na + nso);
+    float* ds = e.d_pr_io.p;
+    float* dn = ds + ns;
+    float* da = dn + nn;
+    float* dso = da + na;
+    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
+    if (noise) HIP_CHECK(hipMemcpyAsync(dn, noise, nn * 4, hipMemcpyHostToDevice, e.stream));
+    const float* use = noise ? dn : (e.prior_sigma != 0.0f ? e.policy_noise(e.step_counter, 0) : nullptr);
+    e.policy_prior_rollouts(ds, use, nullptr, 0, 0, actions_out ? da : nullptr, states_out ? dso : nullptr);
+    if (actions_out) HIP_CHECK(hipMemcpyAsync(actions_out, da, na * 4, hipMemcpyDeviceToHost, e.stream));
+    if (states_out) HIP_CHECK(hipMemcpyAsync(states_out, dso, nso * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
 
 extern "C" int bbmpc_set_reward_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
                                     const float* const* b, int32_t input_mask, int32_t is_normalized, const float* const* stats) {

@@ -76,6 +76,8 @@ void Engine::set_user_callback(int kind, bbmpc_rows_callback fn, void* user) {
     require_user_side(kind);
     REQUIRE(!(fn && value_on()), BBMPC_E_UNSUPPORTED,
             "a callback plug-in beside a learned terminal value (bbmpc_set_terminal_value_mlp): the step-wise rollout has no terminal-value form");
+    REQUIRE(!(fn && prior_on()), BBMPC_E_UNSUPPORTED,
+            "a callback plug-in beside a policy prior (bbmpc_set_policy_prior_mlp): the step-wise rollout draws for itself");
     REQUIRE(!(fn && kind == USER_KIND_DYNAMICS && has_xform()), BBMPC_E_UNSUPPORTED,
             "a dynamics callback returns absolute next states: apply the inverse target transform inside it (clear the transform first)");
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -143,6 +145,9 @@ void Engine::set_transform_source(int kind, const char* src) {
         REQUIRE(!value_on(), BBMPC_E_UNSUPPORTED,
                 "an inverse target transform beside a learned terminal value (bbmpc_set_terminal_value_mlp): the transform rollout has no "
                 "terminal-value form");
+        REQUIRE(!prior_on(), BBMPC_E_UNSUPPORTED,
+                "an inverse target transform beside a policy prior (bbmpc_set_policy_prior_mlp): the policy rollout's model step is "
+                "next = dev + state");
         REQUIRE(cfg.reward != BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
                 "an inverse target transform beside a learned reward model (BBMPC_REW_MLP): the transform rollout has no learned-reward form");
         REQUIRE(cfg.dynamics == BBMPC_DYN_MLP || cfg.dynamics == BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,

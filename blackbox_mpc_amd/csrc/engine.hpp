@@ -551,6 +551,26 @@ struct Engine {
     int carry_stride() const { return std::max(carry_keep, carry_shift); }
     void set_elite_carry(int keep, int shift);
     void save_elites(int count, bool shift);
+    // learned policy prior for CEM (bbmpc_set_policy_prior_mlp; bbmpc_mlp.hip, kernels_policy_prior.hpp, DESIGN.md section
+    // 8l): prior_K closed-loop rollouts of a policy network through the learned model overwrite the candidate columns in
+    // front of the carried elites, between the draw and the SRC_BUF rollout.  While it is on, control steps are routed as
+    // with elite carry (one launch sequence per iteration).
+    bool prior_ready = false;
+    MlpDesc prior_mlp;                 // dims[0] = S, dims[L] = U; mean_s / std_s = mean_in / std_in, mean_t / std_t = mean_out / std_out
+    int prior_nw = 1;                  // waves its widest hidden layer asks for
+    int prior_K = 0;
+    float prior_sigma = 0.0f;
+    DevBuf<float> d_pr_wp4[MLP_MAX_LAYERS], d_pr_bp[MLP_MAX_LAYERS], d_pr_stats, d_pr_noise, d_pr_io;
+    bool prior_noise_valid = false;    // d_pr_noise holds the draws of (prior_noise_step, prior_noise_iter)
+    uint32_t prior_noise_step = 0, prior_noise_iter = 0;
+    bool prior_on() const { return prior_ready; }
+    void set_policy_prior_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
+                              int is_normalized, const float* const* stats, int count, float noise_std);
+    const float* policy_noise(uint32_t step, uint32_t iter);
+    void dump_policy_noise(int control_step, int iteration, float* out, int64_t count);
+    void policy_prior_rollouts(const float* d_state, const float* d_noise, float* samples, int nst, int col0, float* d_actions_out,
+                               float* d_states_out);
+    void policy_prior_rows(const float* d_states, int batch, float* d_actions);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
     DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging

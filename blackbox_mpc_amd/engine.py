@@ -620,6 +620,83 @@ class Engine:
         L.check(L.lib.bbmpc_get_elite_carry(self._h, *[ctypes.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    def set_policy_prior_mlp(self, weights, biases, activations, stats=None, count=1, noise_std=0.0):
+        """Learned policy prior of a CEM + DYN_MLP handle (bbmpc_set_policy_prior_mlp): Dense kernels [in, out] / biases
+        [out] from dim_S inputs to dim_U outputs, any ACT_* code per layer; stats = (mean_in [S], std_in [S], mean_out [U],
+        std_out [U]) or None.  `count` closed-loop rollouts of the policy through the learned model, with N(0, noise_std^2)
+        added to every action, replace that many sampled candidates of every iteration.  weights = None (or an empty list)
+        removes the network."""
+        if not weights:
+            L.check(L.lib.bbmpc_set_policy_prior_mlp(self._h, 0, None, None, None, None, 0, None, 0, 0.0))
+            return
+        n = len(weights)
+        ws = [L.f32c(w) for w in weights]
+        bs = [L.f32c(np.asarray(b).reshape(-1)) for b in biases]
+        dims = [ws[0].shape[0]] + [w.shape[1] for w in ws]
+        for i, (w, b) in enumerate(zip(ws, bs)):
+            if w.ndim != 2 or w.shape[0] != dims[i] or b.shape != (w.shape[1],):
+                raise ValueError("layer %d: kernel must be [in,out] and bias [out]" % i)
+        dims_a = (ctypes.c_int32 * (n + 1))(*dims)
+        acts_a = (ctypes.c_int32 * n)(*[int(a) for a in activations])
+        wp = (ctypes.c_void_p * n)(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bs])
+        sp = None
+        if stats is not None:
+            st = [L.f32c(np.asarray(s).reshape(-1)) for s in stats]
+            if [s.shape for s in st] != [(dims[0],), (dims[0],), (dims[-1],), (dims[-1],)]:
+                raise ValueError("stats must be (mean_in [%d], std_in [%d], mean_out [%d], std_out [%d])"
+                                 % (dims[0], dims[0], dims[-1], dims[-1]))
+            sp = (ctypes.c_void_p * 4)(*[s.ctypes.data for s in st])
+        L.check(L.lib.bbmpc_set_policy_prior_mlp(self._h, n, dims_a, acts_a, wp, bp, 1 if stats is not None else 0, sp,
+                                                 int(count), float(noise_std)))
+
+    def policy_prior(self):
+        """(count, noise_std) of the installed policy prior (bbmpc_get_policy_prior); BBMPCError (state) without one."""
+        c, s = ctypes.c_int32(0), ctypes.c_float(0.0)
+        L.check(L.lib.bbmpc_get_policy_prior(self._h, ctypes.byref(c), ctypes.byref(s)))
+        return int(c.value), float(s.value)
+
+    def evaluate_policy_prior(self, states):
+        """pi on rows (bbmpc_evaluate_policy_prior): states [B, S] -> actions [B, U], no noise and no clip."""
+        states = L.f32c(states)
+        b = states.shape[0] if states.ndim == 2 else -1
+        if states.shape != (b, self.S):                  # the C side copies b * S floats from this buffer
+            raise ValueError("states [B,%d] expected, got %s" % (self.S, states.shape))
+        out = np.empty((b, self.U), np.float32)
+        if b:
+            L.check(L.lib.bbmpc_evaluate_policy_prior(self._h, L.ptr(states), b, L.ptr(out)))
+        return out
+
+    def evaluate_policy_prior_dev(self, d_states, batch, d_actions):
+        L.check(L.lib.bbmpc_evaluate_policy_prior_dev(self._h, ctypes.c_void_p(d_states), int(batch), ctypes.c_void_p(d_actions)))
+
+    def predict_policy_rollouts(self, states, noise=None, want_actions=True, want_states=True):
+        """The K policy rollouts of every agent (bbmpc_predict_policy_rollouts), by the kernel the control step runs:
+        states [A, S], noise [A, K, H, U] standard normals or None (the handle's own stream at the current control step,
+        iteration 0) -> (actions [K, A, H, U], states [K, A, H, S]); an output not wanted is None."""
+        states = L.f32c(states)
+        if states.shape != (self.A, self.S):
+            raise ValueError("states [%d,%d] expected, got %s" % (self.A, self.S, states.shape))
+        k = self.policy_prior()[0]
+        if not (want_actions or want_states):
+            raise ValueError("at least one of want_actions / want_states")
+        nz = None
+        if noise is not None:
+            nz = L.f32c(noise)
+            if nz.shape != (self.A, k, self.H, self.U):
+                raise ValueError("noise [%d,%d,%d,%d] expected, got %s" % (self.A, k, self.H, self.U, nz.shape))
+        acts = np.empty((k, self.A, self.H, self.U), np.float32) if want_actions else None
+        sts = np.empty((k, self.A, self.H, self.S), np.float32) if want_states else None
+        L.check(L.lib.bbmpc_predict_policy_rollouts(self._h, L.ptr(states), L.ptr(nz) if nz is not None else None,
+                                                    L.ptr(acts) if acts is not None else None,
+                                                    L.ptr(sts) if sts is not None else None))
+        return acts, sts
+
+    def predict_policy_rollouts_dev(self, d_states, d_noise=0, d_actions_out=0, d_states_out=0):
+        """Device pointers (0 = NULL), enqueued on the handle's stream (bbmpc_predict_policy_rollouts_dev)."""
+        L.check(L.lib.bbmpc_predict_policy_rollouts_dev(self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_noise or None),
+                                                        ctypes.c_void_p(d_actions_out or None), ctypes.c_void_p(d_states_out or None)))
+
     def set_keep_plan(self, enabled=True):
         """Opt-in switch of plan readback (bbmpc_set_keep_plan): the control steps that follow keep their solution in HBM
         (the routing of set_trace: same results, slower paths).  Off by default."""

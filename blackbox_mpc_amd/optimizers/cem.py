@@ -14,12 +14,35 @@ def _elite_count(name, value, num_elite):
     return int(value)
 
 
+def _policy_prior_setting(policy_prior, prior_candidates, prior_std, carry, population_size):
+    """(network, count, std), or None without a network."""
+    if isinstance(prior_candidates, bool) or not isinstance(prior_candidates, numbers.Integral):
+        raise ValueError("prior_candidates must be an int, got %r" % (prior_candidates,))
+    if isinstance(prior_std, bool) or not isinstance(prior_std, numbers.Real) or not (0.0 <= float(prior_std) < float("inf")):
+        raise ValueError("prior_std must be a finite number >= 0, got %r" % (prior_std,))
+    if policy_prior is None:
+        if prior_candidates != 0:
+            raise ValueError("prior_candidates = %d without a policy_prior network" % prior_candidates)
+        return None
+    for attr in ("weights", "biases", "activation_codes", "normalization_stats"):
+        if not hasattr(policy_prior, attr):
+            raise TypeError("policy_prior must be a LearnedPolicyMLP (an object with weights, biases, activation_codes and "
+                            "normalization_stats()), got %s" % type(policy_prior).__name__)
+    if prior_candidates < 1:
+        raise ValueError("prior_candidates must be >= 1 with a policy_prior network, got %d" % prior_candidates)
+    if prior_candidates + max(carry) >= int(population_size):
+        raise ValueError("prior_candidates + max(keep_elites, shift_elites) = %d must be below population_size = %d"
+                         % (prior_candidates + max(carry), int(population_size)))
+    return policy_prior, int(prior_candidates), float(prior_std)
+
+
 class CEMOptimizer(OptimizerBase):
     _engine_optimizer = L.OPT_CEM
 
     def __init__(self, env_action_space, env_observation_space, planning_horizon=50, max_iterations=5,
                  population_size=500, num_elite=50, num_agents=5, epsilon=0.001, alpha=0.25, noise_beta=None,
-                 sampling_correlation=None, keep_elites=0, shift_elites=0, **engine_args):
+                 sampling_correlation=None, keep_elites=0, shift_elites=0, policy_prior=None, prior_candidates=0,
+                 prior_std=0.0, **engine_args):
         # temporally correlated sampling (no counterpart in the reference): noise_beta = the exponent of iCEM's colored
         # noise, or sampling_correlation = an [H, H] mixing matrix of the caller's (utils/colored_noise.py)
         self._sampling_mix = resolve_sampling_correlation(planning_horizon, noise_beta, sampling_correlation)
@@ -27,6 +50,10 @@ class CEMOptimizer(OptimizerBase):
         # back among the candidates of the next one, the best shift_elites of a control step, moved one planning step
         # forward, among those of the next control step
         self._elite_carry = (_elite_count("keep_elites", keep_elites, num_elite), _elite_count("shift_elites", shift_elites, num_elite))
+        # learned policy prior (Engine.set_policy_prior_mlp): prior_candidates closed-loop rollouts of policy_prior (a
+        # LearnedPolicyMLP) through the learned model, with N(0, prior_std^2) on every action, replace that many sampled
+        # candidates of every iteration
+        self._policy_prior = _policy_prior_setting(policy_prior, prior_candidates, prior_std, self._elite_carry, population_size)
         super().__init__(name=None, planning_horizon=planning_horizon, max_iterations=max_iterations,
                          num_agents=num_agents, env_action_space=env_action_space,
                          env_observation_space=env_observation_space, **engine_args)

@@ -60,7 +60,19 @@ class OptimizerBase:
         if value is not None and eng.__dict__.get("_val_version") != getattr(value, "_version", 0):
             from ..trajectory_evaluators.deterministic import configure_terminal_value
             configure_terminal_value(eng, self._trajectory_evaluator)
+        prior = getattr(self, "_policy_prior", None)                              # a refitted policy prior, likewise
+        if prior is not None and eng.__dict__.get("_prior_version") != getattr(prior[0], "_version", 0):
+            self._configure_policy_prior(eng)
         return eng
+
+    def _configure_policy_prior(self, eng):
+        net, count, std = self._policy_prior
+        if (net.dim_S, net.dim_U) != (self._dim_S, self._dim_U):
+            raise ValueError("policy_prior maps %d -> %d but the optimizer's spaces are %d -> %d"
+                             % (net.dim_S, net.dim_U, self._dim_S, self._dim_U))
+        eng.set_policy_prior_mlp(net.weights, net.biases, net.activation_codes, stats=net.normalization_stats(), count=count,
+                                 noise_std=std)
+        eng._prior_version = getattr(net, "_version", 0)
 
     def _require_engine_and_params(self):
         # what _require_engine is on an optimizer whose reward / dynamics has runtime parameters: they are uploaded when
@@ -154,6 +166,8 @@ class OptimizerBase:
         carry = getattr(self, "_elite_carry", (0, 0))  # CEM with keep_elites / shift_elites
         if carry != (0, 0):
             self._engine.set_elite_carry(*carry)
+        if getattr(self, "_policy_prior", None) is not None:   # CEM with policy_prior / prior_candidates / prior_std
+            self._configure_policy_prior(self._engine)
         if self._engine._param_fns:
             self._require_engine = self._require_engine_and_params
         else:

@@ -9,7 +9,8 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
                                batch_size=128, is_normalized=True, nn_optimizer=None, tf_writer=None,
                                exploration_noise=False, log_dir=None, save_model_frequency=1, saved_model_dir=None,
                                start_episode=0, multistep_horizon=None, reward_model=None, reward_train_args=None,
-                               value_model=None, value_n_step=10, value_train_args=None, **train_args):
+                               value_model=None, value_n_step=10, value_train_args=None, policy_model=None, policy_train_args=None,
+                               **train_args):
     """Same arguments as the reference; `train_args` (device=, seed=, ...) are forwarded to `train`.
     `multistep_horizon`: when set, the fit is followed by one SystemDynamicsHandler.multistep_error call over that many
     steps on the episodes just collected (the train / validation split is per transition, so there is no held-out
@@ -19,7 +20,9 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
     rollouts collect anyway (`reward_train_args`: a dict forwarded to its `train`; default: epochs / batch_size /
     learning_rate / validation_split of this call).
     `value_model`: a LearnedValueMLP that is refitted beside them on the `value_n_step`-step returns of every episode it
-    has been given so far (`value_train_args`: a dict forwarded to its `train_on_rollouts`: gamma=, bootstrap=, epochs=, ...)."""
+    has been given so far (`value_train_args`: a dict forwarded to its `train_on_rollouts`: gamma=, bootstrap=, epochs=, ...).
+    `policy_model`: a LearnedPolicyMLP that is refitted beside them on the (observation, executed action) pairs of every
+    episode it has been given so far (`policy_train_args`: a dict forwarded to its `train_on_rollouts`)."""
     if system_dynamics_handler is None:
         system_dynamics_handler = SystemDynamicsHandler(env_action_space=env.action_space,
                                                         env_observation_space=env.observation_space,
@@ -41,6 +44,10 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
         args = dict(epochs=epochs, batch_size=batch_size, learning_rate=learning_rate, validation_split=validation_split)
         args.update(value_train_args or {})
         value_model.train_on_rollouts(traj_obs, traj_rews, value_n_step, **args)
+    if policy_model is not None:
+        args = dict(epochs=epochs, batch_size=batch_size, learning_rate=learning_rate, validation_split=validation_split)
+        args.update(policy_train_args or {})
+        policy_model.train_on_rollouts(traj_obs, traj_acs, **args)
     if multistep_horizon is not None:
         system_dynamics_handler.multistep_error(traj_obs, traj_acs, multistep_horizon)
     return system_dynamics_handler

@@ -19,13 +19,14 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
                                      exploration_noise=False, epochs=30, learning_rate=1e-3, validation_split=0.2,
                                      batch_size=128, start_episode=0, train_args=None, multistep_horizon=None,
                                      reward_model=None, reward_train_args=None, value_model=None, value_n_step=10,
-                                     value_train_args=None, **optimizer_args):
+                                     value_train_args=None, policy_model=None, policy_train_args=None, **optimizer_args):
     """Same arguments as the reference (+ `train_args`, a dict forwarded to SystemDynamicsHandler.train, and
     `multistep_horizon`: every fit is followed by the open-loop error over that many steps, kept as
     `handler.multistep_rmse`; None = not computed; and `reward_model`, a LearnedRewardMLP refitted in every iteration from
     the rewards the rollouts collect -- pass the same object as `reward_function` to plan with it; and `value_model`, a
     LearnedValueMLP refitted likewise on `value_n_step`-step returns -- it is handed to the refinement policy this call
-    builds as its terminal_value).
+    builds as its terminal_value; and `policy_model`, a LearnedPolicyMLP refitted likewise on the (observation, executed
+    action) pairs -- pass the same object as `policy_prior=` among the optimizer arguments to plan with it).
     Returns (system_dynamics_handler, refinement_policy)."""
     train_args = dict(train_args or {})
     if number_of_initial_rollouts > 0:
@@ -38,7 +39,7 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
             save_model_frequency=save_model_frequency, saved_model_dir=saved_model_dir,
             multistep_horizon=multistep_horizon, reward_model=reward_model,
             reward_train_args=reward_train_args, value_model=value_model, value_n_step=value_n_step,
-            value_train_args=value_train_args, **train_args)
+            value_train_args=value_train_args, policy_model=policy_model, policy_train_args=policy_train_args, **train_args)
         logging.info("Trained initial system model")
     elif system_dynamics_handler is None:
         system_dynamics_handler = SystemDynamicsHandler(
@@ -61,5 +62,6 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
             exploration_noise=exploration_noise,
             start_episode=start_episode + (number_of_rollouts_for_refinement * i), multistep_horizon=multistep_horizon,
             reward_model=reward_model, reward_train_args=reward_train_args, value_model=value_model,
-            value_n_step=value_n_step, value_train_args=value_train_args, **train_args)
+            value_n_step=value_n_step, value_train_args=value_train_args, policy_model=policy_model,
+            policy_train_args=policy_train_args, **train_args)
     return system_dynamics_handler, refinement_policy

@@ -98,6 +98,7 @@ extern "C" {
 #define BBMPC_NOISE_PSO_RESET_VEL      9  /* [N,A,H,U]: pso.py:151-152 */
 #define BBMPC_NOISE_EXPLORATION       10  /* [A,U] unit trunc normal: optimizer_base.py:83-86 */
 #define BBMPC_NOISE_PROCESS           11  /* [iters][A,P,H,S] N(0,1) ([A,P,H,S] on evaluator-only handles): bbmpc_set_particles */
+#define BBMPC_NOISE_POLICY            12  /* [iters][A,K,H,U] N(0,1): bbmpc_set_policy_prior_mlp */
 
 /* trace items for bbmpc_get_trace (per-iteration parity data) */
 #define BBMPC_TRACE_REWARDS 1   /* [N,A]  (SPSA: [2N,A], plus then minus)   */
@@ -593,6 +594,45 @@ int bbmpc_get_sampling_correlation(bbmpc_handle h, int32_t* installed);
 int bbmpc_set_elite_carry(bbmpc_handle h, int keep, int shift);
 /* The setting, and *stored = the number of elites currently held for the next control step. */
 int bbmpc_get_elite_carry(bbmpc_handle h, int* keep, int* shift, int* stored);
+
+/* Learned policy prior for CEM on a learned model (BBMPC_DYN_MLP): `count` = K closed-loop rollouts of a policy network
+ * pi through the learned model replace K sampled candidates of every iteration.  pi is a Dense stack dims[0] = dim_s ->
+ * dims[n_layers] = dim_u in bbmpc_set_mlp's layouts (any BBMPC_ACT_* per layer), stats = mean_in [dim_s], std_in [dim_s],
+ * mean_out [dim_u], std_out [dim_u] when is_normalized:
+ *   pi(s) = y * std_out + mean_out,  y = stack((s - mean_in) / (std_in + 1e-7f))          (y itself when not normalised)
+ * For iteration i of control step c, agent a, policy rollout e = 0 .. K-1:
+ *   s_0 = state[a];   a_t = clip(pi(s_t) + noise_std * xi[i, a, e, t, :], lo, hi);
+ *   s_{t+1} = what bbmpc_predict_next_state computes for (s_t, a_t);   X_i[N - c_i - K + e, a, t, :] = a_t
+ * with c_i the carried elites injected in that iteration (bbmpc_set_elite_carry; 0 without): the policy columns sit
+ * directly in front of the carried ones.  The draws of the replaced columns are still made, with unchanged keying, and then
+ * overwritten; everything behind the candidates (rollout, top-k, refit, smoothing, the action) is untouched.  xi is stream
+ * BBMPC_NOISE_POLICY, [iters][A,K,H,U] N(0,1): Philox counter (e, ga * Qk + (j >> 2), control_step, (12 << 16) | iter), ga
+ * the global agent id, j = t * dim_u + u, Qk = ceil(H * dim_u / 4), Box-Muller on word pairs -- or injected
+ * (bbmpc_inject_noise).  While a network is installed control steps take one launch sequence per iteration, as with
+ * bbmpc_set_elite_carry.  n_layers = 0 removes the network and restores routing and outputs bit for bit.  An accepted call
+ * settles the handle (a resident control-step kernel is stopped, a captured step graph dropped); a refused one leaves it as
+ * it was.  BBMPC_E_UNSUPPORTED: more than 8 layers, a hidden width > 512, an optimizer other than CEM, dynamics other than
+ * BBMPC_DYN_MLP, callback plug-ins, an inverse target transform, a sharded population, a model ensemble or log-variance
+ * heads (each of the last four also refused by its own setter while a prior is installed), buffers that do not fit the LDS.
+ * BBMPC_E_INVALID: NULL pointers, dims[0] != dim_s, dims[n_layers] != dim_u, a width < 1, an unknown activation,
+ * is_normalized without stats, noise_std negative or not finite, count < 1, count + max(keep, shift) >= population_size
+ * (bbmpc_set_elite_carry checks the same while a prior is installed).  bbmpc_reset keeps the setting. */
+int bbmpc_set_policy_prior_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* activations,
+                               const float* const* weights, const float* const* biases, int32_t is_normalized,
+                               const float* const* stats, int32_t count, float noise_std);
+/* The setting; BBMPC_E_STATE (and *count = 0) without a network. */
+int bbmpc_get_policy_prior(bbmpc_handle h, int32_t* count, float* noise_std);
+/* pi on `batch` rows of states [batch][dim_s] -> actions [batch][dim_u]: no noise, no clip.  BBMPC_E_STATE without a
+ * network.  The _dev form takes device pointers and is ordered on the handle's stream. */
+int bbmpc_evaluate_policy_prior(bbmpc_handle h, const float* states, int32_t batch, float* actions);
+int bbmpc_evaluate_policy_prior_dev(bbmpc_handle h, const float* d_states, int32_t batch, float* d_actions);
+/* The K policy rollouts of every agent from states [A][dim_s], by exactly the kernel a control step runs:
+ * actions_out [K,A,H,dim_u] (the candidate columns) and states_out [K,A,H,dim_s] (s_1 .. s_H); either may be NULL, not
+ * both.  noise: [A,K,H,dim_u] standard normals, or NULL for the handle's BBMPC_NOISE_POLICY stream at the current control
+ * step, iteration 0 (equal calls give equal bits).  BBMPC_E_STATE without a network or without bbmpc_set_mlp. */
+int bbmpc_predict_policy_rollouts(bbmpc_handle h, const float* states, const float* noise, float* actions_out, float* states_out);
+int bbmpc_predict_policy_rollouts_dev(bbmpc_handle h, const float* d_states, const float* d_noise, float* d_actions_out,
+                                      float* d_states_out);
 
 /* Closed-loop episode on the device -- counterpart of utils/rollouts.py:60-139 (_sample) with the engine's own
  * model as the environment: T control steps, each feeding its predicted next state back as the next observation;
