@@ -97,6 +97,7 @@ SYMBOLS = [
     "bbmpc_set_terminal_value_mlp", "bbmpc_evaluate_terminal_value", "bbmpc_evaluate_terminal_value_dev",
     "bbmpc_set_policy_prior_mlp", "bbmpc_get_policy_prior", "bbmpc_evaluate_policy_prior", "bbmpc_evaluate_policy_prior_dev",
     "bbmpc_predict_policy_rollouts", "bbmpc_predict_policy_rollouts_dev",
+    "bbmpc_plan_gradient", "bbmpc_plan_gradient_dev",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -141,6 +142,8 @@ def _load():
     lib.bbmpc_evaluate_policy_prior_dev.argtypes = [vp, vp, i32, vp]
     lib.bbmpc_predict_policy_rollouts.argtypes = [vp, vp, vp, vp, vp]
     lib.bbmpc_predict_policy_rollouts_dev.argtypes = [vp, vp, vp, vp, vp]
+    lib.bbmpc_plan_gradient.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.bbmpc_plan_gradient_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.bbmpc_reset.argtypes = [vp]
     lib.bbmpc_optimize.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.bbmpc_optimize_dev.argtypes = [vp, vp, i32, i32, vp, vp]

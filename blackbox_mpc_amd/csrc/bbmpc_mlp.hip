@@ -13,6 +13,7 @@
 #include "kernels_mlp_particles.hpp"
 #include "kernels_mlp_traj_particles.hpp"
 #include "kernels_policy_prior.hpp"
+#include "kernels_plan_grad.hpp"
 
 namespace bbmpc {
 
@@ -184,6 +185,8 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
         mlp.std_t = q;
     }
     mlp_ready = true;
+    pg_host[0].keep(n_layers, dims, acts, w, b);        // (plan gradients pack W^T from these at their next call)
+    pg_stale[0] = true;
 }
 
 // bbmpc_set_mlp_ensemble: E networks of the installed model's shape for the particle rollouts (kernels_mlp_particles.hpp).
@@ -749,6 +752,8 @@ void Engine::set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* ac
     dense_stack_upload(hs, w, b, is_normalized, stats, d_rw_wp4, d_rw_bp, d_rw_last, d_rw_stats);
     rew_mlp = hs.d;
     rew_mlp_ready = true;
+    pg_host[1].keep(n_layers, dims, acts, w, b);        // (plan gradients pack W^T from these at their next call)
+    pg_stale[1] = true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -800,6 +805,8 @@ void Engine::set_terminal_value_mlp(int n_layers, const int32_t* dims, const int
     val_mlp = hs.d;
     val_weight = terminal_weight;
     val_mlp_ready = true;
+    pg_host[2].keep(n_layers, dims, acts, w, b);
+    pg_stale[2] = true;
 }
 
 // Whatever the handle runs today for its reward kind, with u_traj recording on, then the terminal term in one launch.
@@ -1136,6 +1143,136 @@ void Engine::policy_prior_rows(const float* d_states, int batch, float* d_action
     HIP_CHECK(hipGetLastError());
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// plan gradients (bbmpc_plan_gradient; kernels_plan_grad.hpp)
+// ------------------------------------------------------------------------------------------------
+// W and W^T of every layer of network `which` (0 dynamics, 1 reward, 2 value), both through mlp_pack_layer, features in
+// index order, into the feature's own buffers; the reversed network's biases are one shared block of zeros.
+void Engine::plan_gradient_pack(int which) {
+    const PgHostNet& hn = pg_host[which];
+    PgNet n;
+    memset(&n, 0, sizeof(n));
+    const int L = hn.L;
+    n.f.n_layers = n.r.n_layers = L;
+    for (int l = 0; l <= L; ++l) {
+        n.f.dims[l] = hn.dims[l];
+        n.f.tiles[l] = (hn.dims[l] + 15) / 16;
+        n.r.dims[L - l] = n.f.dims[l];
+        n.r.tiles[L - l] = n.f.tiles[l];
+        if (l >= 1 && l < L) n.hid += n.f.tiles[l];
+    }
+    if (d_pg_zero.n == 0) {
+        d_pg_zero.alloc(2 * 16 * MLP_TMAX * 256);
+        HIP_CHECK(hipMemset(d_pg_zero.p, 0, d_pg_zero.n * sizeof(float)));
+    }
+    for (int l = 0; l < L; ++l) {
+        n.act[l] = hn.acts[l];
+        std::vector<float> wp, w4, bp;
+        mlp_pack_layer(n.f, l, hn.w[l].data(), hn.b[l].data(), wp, w4, bp);
+        upload(d_pg_wf[which][l], w4);
+        upload(d_pg_bf[which][l], bp);
+        n.wf[l] = d_pg_wf[which][l].p;
+        n.f.bpack[l] = d_pg_bf[which][l].p;
+        const int j = L - 1 - l, K = hn.dims[l], M = hn.dims[l + 1];       // reversed layer j: [M][K]
+        std::vector<float> wt((size_t)M * K), zb((size_t)K, 0.0f);
+        for (int k = 0; k < K; ++k)
+            for (int o = 0; o < M; ++o) wt[(size_t)o * K + k] = hn.w[l][(size_t)k * M + o];
+        mlp_pack_layer(n.r, j, wt.data(), zb.data(), wp, w4, bp);
+        upload(d_pg_wr[which][j], w4);
+        n.wr[j] = d_pg_wr[which][j].p;
+        n.r.bpack[j] = d_pg_zero.p;
+    }
+    pg_net[which] = n;
+    pg_stale[which] = false;
+}
+
+// Every refusal of a gradient call, the launch shape and the sizes -- before anything is allocated or packed.
+void Engine::plan_gradient_check(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats) {
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
+            "plan gradient: the return is differentiated through a learned model: the handle needs BBMPC_DYN_MLP, not analytic or user dynamics");
+    REQUIRE(cfg.reward == BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
+            "plan gradient: the reward must be a learned reward network (BBMPC_REW_MLP), not a built-in or HIP-source reward");
+    REQUIRE(ens_E == 0 && lv_heads == 0, BBMPC_E_UNSUPPORTED,
+            "plan gradient beside a model ensemble or log-variance heads: the gradient is that of one noise-free model");
+    REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED, "plan gradient beside an inverse target transform: the differentiated step is next = dev + state");
+    REQUIRE(!user_callbacks(), BBMPC_E_UNSUPPORTED, "plan gradient beside a callback plug-in: a callback has no derivative");
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "plan gradient: learned dynamics not set: call bbmpc_set_mlp before computing");
+    REQUIRE(rew_mlp_ready, BBMPC_E_STATE, "plan gradient: learned reward not set: call bbmpc_set_reward_mlp before computing");
+    REQUIRE(batch >= 1, BBMPC_E_INVALID, "batch must be >= 1");
+    REQUIRE(horizon >= 1 && horizon <= 4096, BBMPC_E_INVALID, "horizon must be in [1, 4096]");
+    memset(&q, 0, sizeof(q));
+    // the shapes alone decide the sizes: taken from the host copies, so that nothing has to be packed to refuse
+    PgNet shape[3];
+    memset(shape, 0, sizeof(shape));
+    int hidden_tiles = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (i == 2 && !val_mlp_ready) continue;
+        const PgHostNet& hn = pg_host[i];
+        shape[i].f.n_layers = hn.L;
+        for (int l = 0; l <= hn.L; ++l) {
+            shape[i].f.dims[l] = hn.dims[l];
+            shape[i].f.tiles[l] = (hn.dims[l] + 15) / 16;
+            if (l >= 1 && l < hn.L) {
+                shape[i].hid += shape[i].f.tiles[l];
+                hidden_tiles = std::max(hidden_tiles, shape[i].f.tiles[l]);
+            }
+        }
+    }
+    q.has_val = val_mlp_ready ? 1 : 0;
+    q.nw = std::min(16, hidden_tiles);
+    q.B = batch; q.Hq = horizon; q.S = S; q.U = U;
+    q.r_D = rew_mlp.D;
+    lds = (size_t)plan_grad_lds_layout(shape[0], shape[1], shape[2], q.has_val, S, U, rew_mlp.D).total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "plan gradient: the activation buffers of the three networks do not fit one CU's LDS");
+    q.step_stride = plan_grad_step_stride(shape[0].hid, shape[1].hid, S);
+    const long tiles = (batch + MLP_TP - 1) / MLP_TP;
+    const long tile_stride = (long)horizon * q.step_stride + (q.has_val ? shape[2].hid * 256 : 0);
+    REQUIRE(tiles * tile_stride < (1L << 31), BBMPC_E_UNSUPPORTED,
+            "plan gradient: the workspace of this batch and horizon has 2^31 elements or more (split the batch)");
+    q.tile_stride = (int)tile_stride;
+    ws_floats = (size_t)(tiles * tile_stride);
+}
+
+void Engine::plan_gradient_dev(const float* d_states, const float* d_seq, int batch, int horizon, float* d_returns, float* d_grad) {
+    PlanGradArgs q;
+    size_t lds = 0, wsn = 0;
+    plan_gradient_check(batch, horizon, q, lds, wsn);
+    for (int i = 0; i < 3; ++i)
+        if (pg_stale[i] && (i < 2 || val_mlp_ready)) {
+            HIP_CHECK(hipStreamSynchronize(stream));               // (a call in flight may still read the old operands)
+            plan_gradient_pack(i);
+        }
+    if (d_pg_ws.n < wsn) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        d_pg_ws.alloc(wsn);
+    }
+    q.dyn = pg_net[0];
+    q.dyn.f.normalized = mlp.normalized;
+    q.dyn.f.mean_s = mlp.mean_s; q.dyn.f.std_s = mlp.std_s;
+    q.dyn.f.mean_a = mlp.mean_a; q.dyn.f.std_a = mlp.std_a;
+    q.dyn.f.mean_t = mlp.mean_t; q.dyn.f.std_t = mlp.std_t;
+    q.rew = pg_net[1];
+    q.r_norm = rew_mlp.normalized; q.r_mask = rew_mlp.mask; q.r_off_a = rew_mlp.off_a; q.r_off_n = rew_mlp.off_n;
+    q.r_mean = rew_mlp.mean_in; q.r_std = rew_mlp.std_in;
+    q.r_mean_out = rew_mlp.mean_r; q.r_std_out = rew_mlp.std_r;
+    if (q.has_val) {
+        q.val = pg_net[2];
+        q.w = val_weight;
+        q.v_norm = val_mlp.normalized;
+        q.v_mean = val_mlp.mean_in; q.v_std = val_mlp.std_in;
+        q.v_mean_out = val_mlp.mean_r; q.v_std_out = val_mlp.std_r;
+    }
+    q.states = d_states;
+    q.seq = d_seq;
+    q.returns_out = d_returns;
+    q.grad_out = d_grad;
+    q.ws = d_pg_ws.p;
+    if (lds > 64 * 1024) ensure_max_lds((const void*)k_plan_grad, 159 * 1024);
+    hipLaunchKernelGGL(k_plan_grad, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(q.nw * 64), lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace bbmpc
 
 extern "C" int bbmpc_set_policy_prior_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
@@ -1262,6 +1399,48 @@ extern "C" int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states
     HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
     e.terminal_value_rows(ds, batch, dv);
     HIP_CHECK(hipMemcpyAsync(values, dv, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
+
+extern "C" int bbmpc_plan_gradient_dev(bbmpc_handle h, const float* d_states, const float* d_seq, int32_t batch, int32_t horizon,
+                                       float* d_returns_out, float* d_grad_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_states);
+    CHECK_PTR(d_seq);
+    CHECK_PTR(d_grad_out);
+    h->e->plan_gradient_dev(d_states, d_seq, batch, horizon, d_returns_out, d_grad_out);
+    API_END
+}
+
+extern "C" int bbmpc_plan_gradient(bbmpc_handle h, const float* states, const float* seq, int32_t batch, int32_t horizon, float* returns_out,
+                                   float* grad_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(states);
+    CHECK_PTR(seq);
+    CHECK_PTR(grad_out);
+    bbmpc::Engine& e = *h->e;
+    {   // every refusal before the staging buffer is touched
+        bbmpc::PlanGradArgs q;
+        size_t lds = 0, wsn = 0;
+        e.plan_gradient_check(batch, horizon, q, lds, wsn);
+    }
+    const size_t ns = (size_t)batch * e.S, nq = (size_t)batch * horizon * e.U;
+    if (e.d_pg_io.n < ns + 2 * nq + batch) {
+        HIP_CHECK(hipStreamSynchronize(e.stream));
+        e.d_pg_io.alloc(ns + 2 * nq + batch);
+    }
+    float* ds = e.d_pg_io.p;
+    float* dq = ds + ns;
+    float* dg = dq + nq;
+    float* dr = dg + nq;
+    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(dq, seq, nq * 4, hipMemcpyHostToDevice, e.stream));
+    e.plan_gradient_dev(ds, dq, batch, horizon, dr, dg);
+    HIP_CHECK(hipMemcpyAsync(grad_out, dg, nq * 4, hipMemcpyDeviceToHost, e.stream));
+    if (returns_out) HIP_CHECK(hipMemcpyAsync(returns_out, dr, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
     HIP_CHECK(hipStreamSynchronize(e.stream));
     API_END
 }

@@ -29,6 +29,7 @@
 #include "kernels_mlp_w4.hpp"
 #include "kernels_mlp_wave.hpp"
 #include "kernels_opt.hpp"
+#include "kernels_plan_grad.hpp"
 #include "kernels_refit.hpp"
 #include "kernels_reward_mlp.hpp"
 #include "kernels_rollout.hpp"
@@ -357,6 +358,31 @@ struct Engine {
                                 int is_normalized, const float* const* stats, float terminal_weight);
     void rollout_terminal_value(int mode, bool pen, RolloutArgs& ra);
     void terminal_value_rows(const float* d_states, int batch, float* d_out);
+    // plan gradients (bbmpc_plan_gradient; bbmpc_mlp.hip, kernels_plan_grad.hpp): dR/da through the
+    // three networks.  The setters keep the raw weights on the host (nothing else of them changes); the first gradient call
+    // after a (re)install packs W and W^T of every layer with mlp_pack_layer into buffers of the feature's own.
+    struct PgHostNet {
+        int L = 0;
+        std::vector<int> dims, acts;
+        std::vector<std::vector<float>> w, b;
+        void keep(int n_layers, const int32_t* d, const int32_t* a, const float* const* ws, const float* const* bs) {
+            L = n_layers;
+            dims.assign(d, d + n_layers + 1);
+            acts.assign(a, a + n_layers);
+            w.clear(); b.clear();
+            for (int l = 0; l < n_layers; ++l) {
+                w.emplace_back(ws[l], ws[l] + (size_t)d[l] * d[l + 1]);
+                b.emplace_back(bs[l], bs[l] + d[l + 1]);
+            }
+        }
+    };
+    PgHostNet pg_host[3];              // 0 dynamics, 1 reward, 2 terminal value
+    bool pg_stale[3] = {true, true, true};
+    PgNet pg_net[3];
+    DevBuf<float> d_pg_wf[3][MLP_MAX_LAYERS], d_pg_bf[3][MLP_MAX_LAYERS], d_pg_wr[3][MLP_MAX_LAYERS], d_pg_zero, d_pg_ws, d_pg_io;
+    void plan_gradient_check(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats);
+    void plan_gradient_pack(int which);
+    void plan_gradient_dev(const float* d_states, const float* d_seq, int batch, int horizon, float* d_returns, float* d_grad);
     void set_user_source(int kind, const char* src, int nparams = 0);
     void set_user_callback(int kind, bbmpc_rows_callback fn, void* user);
     // runtime parameters of a parameterised user reward / dynamics (bbmpc_set_user_params): [A][P] on the device -- a

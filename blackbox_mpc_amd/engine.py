@@ -526,6 +526,28 @@ class Engine:
                                                      int(batch), int(horizon), ctypes.c_void_p(d_states_out or 0),
                                                      ctypes.c_void_p(d_rewards_out or 0)))
 
+    def plan_gradient(self, states, action_sequences, want_returns=True):
+        """Plan gradients (bbmpc_plan_gradient): states [B,S], action_sequences [B,Hq,U] -> (returns [B], grad [B,Hq,U]) with
+        R[b] = sum_t r(s_t, a_t, s_{t+1}) + terminal_weight * V(s_Hq) through the learned dynamics, the learned reward and
+        (when installed) the learned terminal value, and grad[b,t,u] = dR[b] / da_t[u].  Actions are used as given.  A rows
+        call: Hq is free of the handle's planning horizon.  returns comes back None when it is not wanted."""
+        states, seq = L.f32c(states), L.f32c(action_sequences)
+        b = states.shape[0] if states.ndim == 2 else -1
+        # the C side copies b*S and b*Hq*U floats from these buffers: a wrong shape must not become an out-of-bounds read
+        if states.shape != (b, self.S) or seq.ndim != 3 or seq.shape[0] != b or seq.shape[2] != self.U:
+            raise ValueError("states [B,%d] and action_sequences [B,Hq,%d] expected, got %s, %s"
+                             % (self.S, self.U, states.shape, seq.shape))
+        hq = seq.shape[1]
+        out_r = np.empty((b,), np.float32) if want_returns else None
+        out_g = np.empty((b, hq, self.U), np.float32)
+        L.check(L.lib.bbmpc_plan_gradient(self._h, L.ptr(states), L.ptr(seq), b, hq, L.ptr(out_r), L.ptr(out_g)))
+        return out_r, out_g
+
+    def plan_gradient_dev(self, d_states, d_action_sequences, batch, horizon, d_returns_out, d_grad_out):
+        """The same on device addresses, enqueued on the handle's stream (d_returns_out may be 0)."""
+        L.check(L.lib.bbmpc_plan_gradient_dev(self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_action_sequences), int(batch),
+                                              int(horizon), ctypes.c_void_p(d_returns_out or 0), ctypes.c_void_p(d_grad_out)))
+
     def predict_trajectory_particles(self, states, action_sequences, eps=None, want_particles=False, quantile_ranks=None):
         """Trajectory distributions (bbmpc_predict_trajectory_particles): states [B,S], action_sequences [B,Hq,U] ->
         (state_mean [B,Hq,S], state_std [B,Hq,S], reward_mean [B,Hq], reward_std [B,Hq]) over the P particles of

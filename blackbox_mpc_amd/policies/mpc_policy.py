@@ -20,9 +20,29 @@ class MPCPolicy(ModelBasedBasePolicy):
                  reward_function=None, env_action_space=None, env_observation_space=None,
                  dynamics_function=None, dynamics_handler=None, true_model=False, optimizer_name=None,
                  num_agents=None, save_model_frequency=1, saved_model_dir=None, terminal_value=None, terminal_weight=1.0,
-                 **optimizer_args):
+                 refine_steps=0, refine_lr=0.05, **optimizer_args):
         """terminal_value / terminal_weight: a LearnedValueMLP that closes the planning horizon (handed to the
-        DeterministicTrajectoryEvaluator this constructor builds; an evaluator passed in takes them itself)."""
+        DeterministicTrajectoryEvaluator this constructor builds; an evaluator passed in takes them itself).
+        refine_steps / refine_lr: with refine_steps > 0 every `act` refines the optimizer's plan by that many projected
+        gradient steps on the model return (utils.plan_refinement.refine_plan, Engine.plan_gradient) and acts on the refined
+        plan's first action; needs learned dynamics and a LearnedRewardMLP.  The optimizer's own warm start is left alone.
+        refine_steps = 0 changes nothing."""
+        self._refine_steps, self._refine_lr = int(refine_steps), float(refine_lr)
+        if self._refine_steps < 0:
+            raise ValueError("refine_steps must be >= 0, got %r" % (refine_steps,))
+        if self._refine_steps > 0:
+            if not (self._refine_lr > 0.0 and np.isfinite(self._refine_lr)):
+                raise ValueError("refine_lr must be positive and finite, got %r" % (refine_lr,))
+            from .. import _lib as L
+            rf = reward_function if trajectory_evaluator is None else trajectory_evaluator._reward_function
+            handler = dynamics_handler if trajectory_evaluator is None else trajectory_evaluator._system_dynamics_handler
+            df = dynamics_function if handler is None else handler._dynamics_function
+            if (getattr(rf, "_bbmpc_reward_kind", None) != L.REW_MLP or getattr(df, "_bbmpc_dynamics_kind", None) != L.DYN_MLP
+                    or hasattr(df, "members") or getattr(df, "logvar_heads", None)):
+                raise ValueError("refine_steps > 0 differentiates the plan through learned networks: it needs learned dynamics "
+                                 "(DeterministicMLP) and a learned reward (LearnedRewardMLP), got %s and %s"
+                                 % (type(df).__name__, type(rf).__name__))
+        self._refined_plan = self._unrefined_plan = None
         if trajectory_evaluator is not None and terminal_value is not None:
             raise ValueError("terminal_value goes to the trajectory evaluator: construct it with terminal_value=, "
                              "or leave trajectory_evaluator to MPCPolicy")
@@ -57,11 +77,34 @@ class MPCPolicy(ModelBasedBasePolicy):
         batched = observations
         if observations.ndim == 1:
             batched = np.tile(observations[None], (self._optimizer._num_agents, 1))
-        action, next_observations, rewards = self._optimizer(batched, t, exploration_noise)
+        if self._refine_steps > 0:
+            if exploration_noise:
+                raise ValueError("exploration noise and plan refinement in one call: the refined action is the plan's first "
+                                 "action (construct the policy with refine_steps=0 to explore)")
+            action, next_observations, rewards = self._act_refined(batched, t)
+        else:
+            action, next_observations, rewards = self._optimizer(batched, t, exploration_noise)
         self._act_call_counter += 1
         if observations.ndim == 1:
             return action[0], next_observations[0], rewards[0]
         return action, next_observations, rewards
+
+    def _act_refined(self, batched, t):
+        """The optimizer's control step, then refine_steps projected gradient steps on its plan: (first action of the
+        refined plan [A,U], the model's next state [A,S] and reward [A] for that action)."""
+        from ..utils.plan_refinement import refine_plan
+        opt = self._optimizer
+        if not getattr(self, "_refine_readback_on", False) or opt._engine is not getattr(self, "_refine_engine", None):
+            opt.keep_plan(True)
+            self._refine_readback_on, self._refine_engine = True, opt._engine
+        opt(batched, t, False)
+        eng = opt._require_engine()
+        plan = eng.get_plan()
+        refined, ret = refine_plan(eng, np.asarray(batched, np.float32), plan, self._refine_steps, self._refine_lr,
+                                   opt._action_lower_bound, opt._action_upper_bound)
+        self._unrefined_plan, self._refined_plan, self._refined_return = plan, refined, ret
+        states, rewards = eng.predict_trajectories(np.asarray(batched, np.float32), refined[:, :1])
+        return refined[:, 0].copy(), states[:, 0], rewards[:, 0]
 
     def keep_plan(self, enabled=True):
         """Switch plan readback on (off) for the `act` calls that follow (OptimizerBase.keep_plan)."""
@@ -74,7 +117,13 @@ class MPCPolicy(ModelBasedBasePolicy):
         batched = observations
         if observations.ndim == 1:
             batched = np.tile(observations[None], (self._optimizer._num_agents, 1))
-        actions, states, rewards = self._optimizer.plan(batched)
+        if self._refine_steps > 0:                      # the refined plan the last `act` acted on
+            if self._refined_plan is None:
+                raise RuntimeError("plan(): call act() first")
+            actions = self._refined_plan
+            states, rewards = self._optimizer._require_engine().predict_trajectories(np.asarray(batched, np.float32), actions)
+        else:
+            actions, states, rewards = self._optimizer.plan(batched)
         if observations.ndim == 1:
             return actions[0], states[0], rewards[0]
         return actions, states, rewards

@@ -234,5 +234,21 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
         parameter-sync logic as __call__."""
         return self._engine(self._one_step_agents(), 1).predict_trajectories(current_states, action_sequences)
 
+    def value_and_gradient(self, current_states, action_sequences):
+        """current_states [A,S], action_sequences [n,A,H,U] -> (rewards [n,A], grad [n,A,H,U]): the model return of every
+        sequence -- sum_t r_t + terminal_weight * V(s_H), actions as given, no NaN rule -- and its derivative in every
+        action (Engine.plan_gradient).  Needs learned dynamics and a LearnedRewardMLP.  Refitted networks are uploaded
+        first, as in __call__."""
+        seq = np.asarray(action_sequences, np.float32)
+        if seq.ndim != 4:
+            raise ValueError("action_sequences must be [n, num_agents, planning_horizon, dim_U]")
+        n, a, hq, u = seq.shape
+        s = np.asarray(current_states, np.float32)
+        if s.shape != (a, self._system_dynamics_handler._dim_S):
+            raise ValueError("current_states must be [num_agents, dim_S]")
+        rows = np.broadcast_to(s[None], (n, a, s.shape[1])).reshape(n * a, -1)
+        ret, grad = self._engine(a, hq).plan_gradient(rows, seq.reshape(n * a, hq, u))
+        return ret.reshape(n, a), grad.reshape(n, a, hq, u)
+
     def evaluate_next_reward(self, current_states, next_states, current_actions):
         return self._engine(self._one_step_agents(), 1).evaluate_next_reward(current_states, next_states, current_actions)

@@ -234,6 +234,28 @@ int bbmpc_set_terminal_value_mlp(bbmpc_handle h, int32_t n_layers, const int32_t
 int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states, int32_t batch, float* values);
 int bbmpc_evaluate_terminal_value_dev(bbmpc_handle h, const float* d_states, int32_t batch, float* d_values);
 
+/* Plan gradients: the derivative of the model return with respect to every action of a plan, through the learned dynamics
+ * (BBMPC_DYN_MLP, bbmpc_set_mlp), the learned reward (BBMPC_REW_MLP, bbmpc_set_reward_mlp, any input_mask) and, when one is
+ * installed, the learned terminal value.  For row b, s_0 = states[b] and a_0 .. a_{horizon-1} = seq[b]:
+ *     s_{t+1} = the learned model's noise-free step (bbmpc_predict_trajectories' rule), r_t = RewardMLP(s_t, a_t, s_{t+1}),
+ *     R[b] = sum over t ascending of r_t + terminal_weight * V(s_horizon)        (the last term only with a value network)
+ *     grad_out[b, t, u] = dR[b] / da_t[u],      returns_out[b] = R[b]   (returns_out may be NULL)
+ * by reverse accumulation in one kernel launch.  Actions are used as given: no clip, no bound penalty, no NaN rule (NaN
+ * propagates).  At a kink of relu, relu6, leaky_relu or hard_sigmoid the derivative is that of the branch the forward's
+ * comparison takes.  A rows call like bbmpc_predict_trajectories: the handle's optimizer, particles, colored noise, elite
+ * carry and policy prior play no part, and nothing of the handle changes but a workspace of its own that grows on demand.
+ * Deterministic: two calls give equal bits, and a batch split at a multiple of 16 rows equals the whole bit for bit.
+ * Refused before anything is allocated, the handle stays as it was -- BBMPC_E_UNSUPPORTED: dynamics other than
+ * BBMPC_DYN_MLP, a reward kind other than BBMPC_REW_MLP, a model ensemble or log-variance heads, an inverse target
+ * transform, a callback plug-in, networks whose activation tiles do not fit one CU's LDS, a workspace of 2^31 elements or
+ * more (split the batch); BBMPC_E_STATE: bbmpc_set_mlp or bbmpc_set_reward_mlp not called yet; BBMPC_E_INVALID: NULL
+ * states / seq / grad_out, batch < 1, horizon outside [1, 4096].  The _dev form takes device pointers and is ordered on
+ * the handle's stream. */
+int bbmpc_plan_gradient(bbmpc_handle h, const float* states, const float* seq, int32_t batch, int32_t horizon,
+                        float* returns_out, float* grad_out);
+int bbmpc_plan_gradient_dev(bbmpc_handle h, const float* d_states, const float* d_seq, int32_t batch, int32_t horizon,
+                            float* d_returns_out, float* d_grad_out);
+
 /* User-supplied plug-ins.  The reference takes ANY callable as reward_function / dynamics_function
  * (trajectory_evaluators/deterministic.py:13-18; called at :65-66 as reward(current_state, actions, next_state) and at
  * :99-100 as dynamics(x[B,S+U], train=False) -> delta[B,S]).  A Python callable cannot run inside a kernel; the
