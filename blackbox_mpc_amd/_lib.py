@@ -98,6 +98,7 @@ SYMBOLS = [
     "bbmpc_set_policy_prior_mlp", "bbmpc_get_policy_prior", "bbmpc_evaluate_policy_prior", "bbmpc_evaluate_policy_prior_dev",
     "bbmpc_predict_policy_rollouts", "bbmpc_predict_policy_rollouts_dev",
     "bbmpc_plan_gradient", "bbmpc_plan_gradient_dev",
+    "bbmpc_refine_plans", "bbmpc_refine_plans_dev", "bbmpc_set_grad_refine", "bbmpc_get_grad_refine",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -144,6 +145,10 @@ def _load():
     lib.bbmpc_predict_policy_rollouts_dev.argtypes = [vp, vp, vp, vp, vp]
     lib.bbmpc_plan_gradient.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.bbmpc_plan_gradient_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.bbmpc_refine_plans.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_float, i32, i32, vp]
+    lib.bbmpc_refine_plans_dev.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.c_float, i32, i32, vp]
+    lib.bbmpc_set_grad_refine.argtypes = [vp, i32, ctypes.c_float, i32, i32]
+    lib.bbmpc_get_grad_refine.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.bbmpc_reset.argtypes = [vp]
     lib.bbmpc_optimize.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.bbmpc_optimize_dev.argtypes = [vp, vp, i32, i32, vp, vp]

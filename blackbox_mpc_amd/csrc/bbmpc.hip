@@ -656,7 +656,9 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
     const bool carry = carry_on() && cfg.optimizer == BBMPC_OPT_CEM && mode == SRC_TRUNC;
     // bbmpc_set_policy_prior_mlp (CEM): the policy's rollouts over the columns in front of the carried ones
     const bool prior = prior_on() && cfg.optimizer == BBMPC_OPT_CEM && mode == SRC_TRUNC;
-    if ((corr_on() || carry || prior) && mode == SRC_TRUNC) {      // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
+    // bbmpc_set_grad_refine (CEM): gradient steps on the last columns, after everything else has formed them
+    const bool grad = grad_on() && cfg.optimizer == BBMPC_OPT_CEM && mode == SRC_TRUNC;
+    if ((corr_on() || carry || prior || grad) && mode == SRC_TRUNC) {      // bbmpc_set_sampling_correlation: mixed draws, then the SRC_BUF form
         if (corr_on()) draw_candidates_corr(ra);
         else draw_candidates(SRC_TRUNC, ra);
         if (prior) {
@@ -671,6 +673,7 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
                                N, carry_stride(), carry_inject, (const float*)d_carry.p, ra.samples);
             HIP_CHECK(hipGetLastError());
         }
+        if (grad) grad_refine_candidates(ra);
         mode = SRC_BUF;
         ra.cand = ra.samples;
     }
@@ -913,7 +916,7 @@ RefitArgs Engine::refit_args() const {
 // samples from is a constant of the handle -- the rollout samples from the constants directly and reads the state from the
 // pinned buffer itself (its workgroup 0 stores it for the later launches).  What else must hold is the optimizer's own.
 bool Engine::dist_init_skippable() const {
-    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() && !prior_on() &&
+    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() && !prior_on() && !grad_on() &&
            iters >= 1 && pi2_copy_seen && stage_state_src != nullptr;
 }
 
@@ -1034,7 +1037,7 @@ void Engine::optimize_cem(RolloutArgs& ra) {
             continue;
         }
         bool first_from_constants = false;
-        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on()) {
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !grad_on()) {
             first_rollout_mlp(false, ra, d_prev_mean.p, d_sigma0.p, cem_pinned);
             first_from_constants = cem_skip;
         } else {
@@ -1521,6 +1524,12 @@ void Engine::get_state(const std::string& name, float* out, int64_t count) {
     HIP_CHECK(hipStreamSynchronize(stream));
     const size_t nm = (size_t)A * HU;
     const float* src = nullptr;
+    if (name == "sample_buffer") {                            // the candidates as they lie in HBM, padding columns included: [A][HU][Nst]
+        REQUIRE(d_samples.p, BBMPC_E_STATE, "this handle has no sample buffer");
+        REQUIRE(count == (int64_t)A * HU * Nst, BBMPC_E_INVALID, "sample_buffer has A * H*U * Nst elements (Nst = population_size rounded up to 64)");
+        HIP_CHECK(hipMemcpy(out, d_samples.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+        return;
+    }
     if (cfg.optimizer == BBMPC_OPT_CMAES) goto cma_names;     // "sigma"/"m" etc. mean the CMA-ES state there
     if (name == "prev_mean") src = d_prev_mean.p;
     else if (name == "mean") src = d_mean.p;
@@ -1582,6 +1591,12 @@ void Engine::set_state(const std::string& name, const float* data, int64_t count
     HIP_CHECK(hipStreamSynchronize(stream));
     size_t nm = (size_t)A * HU;
     float* dst = nullptr;
+    if (name == "sample_buffer") {                            // (tests: a sentinel in the padding columns)
+        REQUIRE(d_samples.p, BBMPC_E_STATE, "this handle has no sample buffer");
+        REQUIRE(count == (int64_t)A * HU * Nst, BBMPC_E_INVALID, "sample_buffer has A * H*U * Nst elements (Nst = population_size rounded up to 64)");
+        HIP_CHECK(hipMemcpy(d_samples.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
+        return;
+    }
     if (name == "prev_mean") dst = d_prev_mean.p;
     else if (name == "C" && cfg.optimizer == BBMPC_OPT_CMAES) { dst = c_C.p; nm = (size_t)cma_G * cma_n * cma_n; }   // (tests: a covariance at another scale)
     else if (name == "var0") { dst = d_var0.p; pi2_dist_ready = false; }
@@ -1819,7 +1834,7 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
                 // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
                 // replayed as a graph (engine.hpp: step_graph)
                 const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&
-                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && !e.prior_on() && e.stream == e.own_stream && !e.any_injected();
+                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && !e.prior_on() && !e.grad_on() && e.stream == e.own_stream && !e.any_injected();
                 const uint64_t sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
                 bool replayed = false;
                 if (graph_ok && e.step_graph && e.step_graph_sig == sig) {

@@ -19,6 +19,7 @@ bool Engine::use_fused() const {
     if (corr_on()) return false;                // bbmpc_set_sampling_correlation: the mixed draws are a kernel of their own
     if (carry_on()) return false;               // bbmpc_set_elite_carry: the candidates are drawn, overwritten and rolled out by launches of their own
     if (prior_on()) return false;               // bbmpc_set_policy_prior_mlp: the same, with the policy rollouts' columns
+    if (grad_on()) return false;                // bbmpc_set_grad_refine: the same, with gradient steps on the columns
     if (cfg.optimizer == BBMPC_OPT_SPSA) {
         if (iters > FUSED_MAX_SPSA_ITERS) return false;
     } else if (cfg.optimizer != BBMPC_OPT_RANDOM_SEARCH && cfg.optimizer != BBMPC_OPT_CEM && cfg.optimizer != BBMPC_OPT_PI2) {

@@ -14,6 +14,7 @@
 #include "kernels_mlp_traj_particles.hpp"
 #include "kernels_policy_prior.hpp"
 #include "kernels_plan_grad.hpp"
+#include "kernels_plan_refine.hpp"
 
 namespace bbmpc {
 
@@ -205,6 +206,9 @@ void Engine::set_mlp_ensemble(int E, const float* const* w, const float* const* 
     REQUIRE(!prior_on(), BBMPC_E_UNSUPPORTED,
             "a model ensemble beside a policy prior (bbmpc_set_policy_prior_mlp): the policy rollout is the noise-free step of one model; "
             "remove the policy network first (n_layers = 0)");
+    REQUIRE(!grad_on(), BBMPC_E_UNSUPPORTED,
+            "a model ensemble beside gradient refinement (bbmpc_set_grad_refine): the gradient is that of one noise-free model; switch it "
+            "off first (steps = 0)");
     REQUIRE(w && b, BBMPC_E_INVALID, "null argument");
     const int L = mlp.n_layers;
     for (int i = 0; i < E * L; ++i) REQUIRE(w[i] && b[i], BBMPC_E_INVALID, "null weight/bias pointer");
@@ -246,6 +250,9 @@ void Engine::set_mlp_logvar_head(int num_heads, const float* const* w, const flo
     REQUIRE(!prior_on(), BBMPC_E_UNSUPPORTED,
             "log-variance heads beside a policy prior (bbmpc_set_policy_prior_mlp): the policy rollout is the noise-free step of one model; "
             "remove the policy network first (n_layers = 0)");
+    REQUIRE(!grad_on(), BBMPC_E_UNSUPPORTED,
+            "log-variance heads beside gradient refinement (bbmpc_set_grad_refine): the gradient is that of one noise-free model; switch "
+            "it off first (steps = 0)");
     REQUIRE(w && b && min_logvar && max_logvar, BBMPC_E_INVALID, "null argument");
     const int want = std::max(1, ens_E);
     REQUIRE(num_heads == want, BBMPC_E_INVALID,
@@ -1189,6 +1196,11 @@ void Engine::plan_gradient_pack(int which) {
 
 // Every refusal of a gradient call, the launch shape and the sizes -- before anything is allocated or packed.
 void Engine::plan_gradient_check(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats) {
+    plan_gradient_eligible();
+    plan_gradient_sizes(batch, horizon, q, lds, ws_floats);
+}
+
+void Engine::plan_gradient_eligible() const {
     REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
             "plan gradient: the return is differentiated through a learned model: the handle needs BBMPC_DYN_MLP, not analytic or user dynamics");
     REQUIRE(cfg.reward == BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
@@ -1197,6 +1209,9 @@ void Engine::plan_gradient_check(int batch, int horizon, PlanGradArgs& q, size_t
             "plan gradient beside a model ensemble or log-variance heads: the gradient is that of one noise-free model");
     REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED, "plan gradient beside an inverse target transform: the differentiated step is next = dev + state");
     REQUIRE(!user_callbacks(), BBMPC_E_UNSUPPORTED, "plan gradient beside a callback plug-in: a callback has no derivative");
+}
+
+void Engine::plan_gradient_sizes(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats) {
     REQUIRE(mlp_ready, BBMPC_E_STATE, "plan gradient: learned dynamics not set: call bbmpc_set_mlp before computing");
     REQUIRE(rew_mlp_ready, BBMPC_E_STATE, "plan gradient: learned reward not set: call bbmpc_set_reward_mlp before computing");
     REQUIRE(batch >= 1, BBMPC_E_INVALID, "batch must be >= 1");
@@ -1238,6 +1253,13 @@ void Engine::plan_gradient_dev(const float* d_states, const float* d_seq, int ba
     PlanGradArgs q;
     size_t lds = 0, wsn = 0;
     plan_gradient_check(batch, horizon, q, lds, wsn);
+    plan_gradient_prepare(wsn);
+    plan_gradient_launch(q, lds, d_states, d_seq, d_returns, d_grad);
+}
+
+// W / W^T of a network installed since the last call, and the workspace: everything of a gradient call that may wait for
+// the stream or allocate
+void Engine::plan_gradient_prepare(size_t wsn) {
     for (int i = 0; i < 3; ++i)
         if (pg_stale[i] && (i < 2 || val_mlp_ready)) {
             HIP_CHECK(hipStreamSynchronize(stream));               // (a call in flight may still read the old operands)
@@ -1247,6 +1269,11 @@ void Engine::plan_gradient_dev(const float* d_states, const float* d_seq, int ba
         HIP_CHECK(hipStreamSynchronize(stream));
         d_pg_ws.alloc(wsn);
     }
+}
+
+// One launch of k_plan_grad on checked arguments (q from plan_gradient_check, after plan_gradient_prepare)
+void Engine::plan_gradient_launch(PlanGradArgs q, size_t lds, const float* d_states, const float* d_seq, float* d_returns, float* d_grad) {
+    const int batch = q.B;
     q.dyn = pg_net[0];
     q.dyn.f.normalized = mlp.normalized;
     q.dyn.f.mean_s = mlp.mean_s; q.dyn.f.std_s = mlp.std_s;
@@ -1273,7 +1300,179 @@ void Engine::plan_gradient_dev(const float* d_states, const float* d_seq, int ba
     HIP_CHECK(hipGetLastError());
 }
 
+// ------------------------------------------------------------------------------------------------
+// plan refinement on the device (bbmpc_refine_plans, bbmpc_set_grad_refine; kernels_plan_refine.hpp)
+// ------------------------------------------------------------------------------------------------
+void Engine::refine_plans_check(int batch, int horizon, int steps, float lr, int method, int keep_best, PlanGradArgs& q, size_t& lds,
+                                size_t& wsn) {
+    plan_gradient_check(batch, horizon, q, lds, wsn);
+    REQUIRE(steps >= 0 && steps <= REFINE_MAX_STEPS, BBMPC_E_INVALID, "refine plans: steps must be in [0, 64]");
+    REQUIRE(std::isfinite(lr) && lr > 0.0f, BBMPC_E_INVALID, "refine plans: lr must be finite and positive");
+    REQUIRE(method == REFINE_ADAM || method == REFINE_SGD, BBMPC_E_INVALID, "refine plans: method must be 0 (adam) or 1 (sgd)");
+    REQUIRE(keep_best == 0 || keep_best == 1, BBMPC_E_INVALID, "refine plans: keep_best must be 0 or 1");
+}
+
+void Engine::refine_plans_dev(const float* d_states, float* d_seq, int batch, int horizon, int steps, float lr, int method, int keep_best,
+                              float* d_returns_out) {
+    PlanGradArgs q;
+    size_t lds = 0, wsn = 0;
+    refine_plans_check(batch, horizon, steps, lr, method, keep_best, q, lds, wsn);
+    refine_plans_run(q, lds, wsn, d_states, d_seq, steps, lr, method, keep_best, d_returns_out);
+}
+
+// The loop on checked arguments (q, lds, wsn from refine_plans_check: no check is repeated per step).  d_seq [B, Hq, U] is
+// refined in place.  keep_best: steps + 1 gradient calls, the best plan per row by model return (the input included) into
+// d_seq, its return into d_returns_out.  Otherwise steps gradient calls, the last iterate stays in d_seq, and d_returns_out
+// (when not null) costs one more call that scores it.
+void Engine::refine_plans_run(const PlanGradArgs& q, size_t lds, size_t wsn, const float* d_states, float* d_seq, int steps, float lr, int method,
+                              int keep_best, float* d_returns_out) {
+    const int batch = q.B, horizon = q.Hq;
+    // everything that allocates or packs, before the first launch: from here on no synchronisation and no host visit
+    plan_gradient_prepare(wsn);
+    const size_t n = (size_t)batch * horizon * U, np4 = (n + 3) & ~(size_t)3, nb = ((size_t)batch + 3) & ~(size_t)3;
+    if (d_rf.n < 4 * np4 + 2 * nb) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        d_rf.alloc(4 * np4 + 2 * nb);
+    }
+    float* g = d_rf.p;
+    float* m = g + np4;
+    float* v = m + np4;
+    float* best = v + np4;
+    float* ret = best + np4;
+    float* best_ret = ret + nb;
+    if (method == REFINE_ADAM && steps > 0) HIP_CHECK(hipMemsetAsync(m, 0, 2 * np4 * sizeof(float), stream));
+    RefineStepArgs a;
+    a.x = d_seq; a.g = g; a.m = m; a.v = v;
+    a.lo = d_lo.p; a.hi = d_hi.p;
+    a.n = (long)n; a.U = U; a.method = method; a.lr = lr;
+    const bool v4 = n % 4 == 0 && ((uintptr_t)d_seq & 15) == 0;      // (the handle's own buffers are 16-byte aligned)
+    const int row = horizon * U;
+    for (int k = 0; k <= steps; ++k) {
+        if (k == steps && !keep_best && !d_returns_out) break;
+        plan_gradient_launch(q, lds, d_states, d_seq, (k == steps && !keep_best) ? d_returns_out : ret, g);
+        if (keep_best) {
+            hipLaunchKernelGGL(k_refine_keep_best, dim3(batch), dim3(64), 0, stream, (const float*)d_seq, (const float*)ret, best, best_ret, row,
+                               k == 0 ? 1 : 0);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (k == steps) break;
+        refine_bias_correction(k + 1, a.c1, a.c2);
+        if (v4) hipLaunchKernelGGL(k_refine_step<true>, dim3((unsigned)((n / 4 + REFINE_THREADS - 1) / REFINE_THREADS)), dim3(REFINE_THREADS), 0, stream, a);
+        else hipLaunchKernelGGL(k_refine_step<false>, dim3((unsigned)((n + REFINE_THREADS - 1) / REFINE_THREADS)), dim3(REFINE_THREADS), 0, stream, a);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (keep_best) {
+        HIP_CHECK(hipMemcpyAsync(d_seq, best, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (d_returns_out) HIP_CHECK(hipMemcpyAsync(d_returns_out, best_ret, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+}
+
+// bbmpc_set_grad_refine.  Everything that can be refused is refused before the handle changes.
+void Engine::set_grad_refine(int steps, float lr, int method, int candidates) {
+    REQUIRE(cfg.optimizer == BBMPC_OPT_CEM, BBMPC_E_UNSUPPORTED,
+            "gradient refinement with an optimizer other than CEM: only CEM's candidates are refined between the draw and the rollout");
+    if (steps == 0) {
+        if (grad_on()) invalidate_step_graph();
+        gr_steps = 0;
+        return;
+    }
+    REQUIRE(steps >= 1 && steps <= REFINE_MAX_STEPS, BBMPC_E_INVALID, "gradient refinement: steps must be in [0, 64]");
+    REQUIRE(std::isfinite(lr) && lr > 0.0f, BBMPC_E_INVALID, "gradient refinement: lr must be finite and positive");
+    REQUIRE(method == REFINE_ADAM || method == REFINE_SGD, BBMPC_E_INVALID, "gradient refinement: method must be 0 (adam) or 1 (sgd)");
+    REQUIRE(candidates >= 0 && candidates <= N, BBMPC_E_INVALID,
+            "gradient refinement: candidates must be in [0, population_size = " + std::to_string(N) + "] (0: all)");
+    REQUIRE(!particles_on(), BBMPC_E_UNSUPPORTED,
+            "gradient refinement with particles (bbmpc_set_particles): the gradient is that of one noise-free rollout");
+    REQUIRE(!pop_sharded() && cfg.population_global <= N && auto_split <= 1, BBMPC_E_UNSUPPORTED,
+            "gradient refinement with a sharded population: the sharded control steps draw inside their rollout kernels");
+    plan_gradient_eligible();
+    invalidate_step_graph();
+    gr_steps = steps; gr_lr = lr; gr_method = method; gr_M = candidates;
+}
+
+// Columns [N - M, N) of every agent's candidates: out of the sample buffer into rows, gr_steps gradient steps from the
+// agent's state (refine_plans_dev, keep_best = 0, no returns), back over the same columns.
+void Engine::grad_refine_candidates(RolloutArgs& ra) {
+    REQUIRE(ra.n_pop == N && ra.HU == HU && ra.H == H && ra.Nst == Nst && ra.samples, BBMPC_E_INVALID, "internal: gradient refinement shape");
+    const int M = gr_M > 0 ? gr_M : N;
+    const int B = A * M;
+    PlanGradArgs q;
+    size_t lds = 0, wsn = 0;
+    refine_plans_check(B, H, gr_steps, gr_lr, gr_method, 0, q, lds, wsn);    // (networks not installed: BBMPC_E_STATE, before anything is allocated)
+    if (d_gr_rows.n < (size_t)B * HU || d_gr_states.n < (size_t)B * S) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        d_gr_rows.alloc((size_t)B * HU);
+        d_gr_states.alloc((size_t)B * S);
+    }
+    hipLaunchKernelGGL(k_refine_gather, dim3((HU * M + S * M + REFINE_THREADS - 1) / REFINE_THREADS, A), dim3(REFINE_THREADS), 0, stream,
+                       (const float*)ra.samples, ra.state, d_gr_rows.p, d_gr_states.p, HU, S, Nst, N, M);
+    HIP_CHECK(hipGetLastError());
+    refine_plans_run(q, lds, wsn, d_gr_states.p, d_gr_rows.p, gr_steps, gr_lr, gr_method, 0, nullptr);
+    hipLaunchKernelGGL(k_refine_scatter, dim3((HU * M + REFINE_THREADS - 1) / REFINE_THREADS, A), dim3(REFINE_THREADS), 0, stream,
+                       (const float*)d_gr_rows.p, ra.samples, HU, Nst, N, M);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace bbmpc
+
+extern "C" int bbmpc_refine_plans_dev(bbmpc_handle h, const float* d_states, float* d_seq, int32_t batch, int32_t horizon, int32_t steps,
+                                      float lr, int32_t method, int32_t keep_best, float* d_returns_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(d_states);
+    CHECK_PTR(d_seq);
+    h->e->refine_plans_dev(d_states, d_seq, batch, horizon, steps, lr, method, keep_best, d_returns_out);
+    API_END
+}
+
+extern "C" int bbmpc_refine_plans(bbmpc_handle h, const float* states, float* seq, int32_t batch, int32_t horizon, int32_t steps, float lr,
+                                  int32_t method, int32_t keep_best, float* returns_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(states);
+    CHECK_PTR(seq);
+    bbmpc::Engine& e = *h->e;
+    bbmpc::PlanGradArgs q;
+    size_t lds = 0, wsn = 0;
+    e.refine_plans_check(batch, horizon, steps, lr, method, keep_best, q, lds, wsn);     // every refusal before the staging buffer is touched
+    const size_t ns = ((size_t)batch * e.S + 3) & ~(size_t)3, nq = ((size_t)batch * horizon * e.U + 3) & ~(size_t)3;
+    if (e.d_rf_io.n < ns + nq + batch) {
+        HIP_CHECK(hipStreamSynchronize(e.stream));
+        e.d_rf_io.alloc(ns + nq + batch);
+    }
+    float* dq = e.d_rf_io.p;                                                 // (first: float4 traffic wants the plans aligned)
+    float* ds = dq + nq;
+    float* dr = ds + ns;
+    HIP_CHECK(hipMemcpyAsync(ds, states, (size_t)batch * e.S * 4, hipMemcpyHostToDevice, e.stream));
+    HIP_CHECK(hipMemcpyAsync(dq, seq, (size_t)batch * horizon * e.U * 4, hipMemcpyHostToDevice, e.stream));
+    e.refine_plans_run(q, lds, wsn, ds, dq, steps, lr, method, keep_best, returns_out ? dr : nullptr);
+    HIP_CHECK(hipMemcpyAsync(seq, dq, (size_t)batch * horizon * e.U * 4, hipMemcpyDeviceToHost, e.stream));
+    if (returns_out) HIP_CHECK(hipMemcpyAsync(returns_out, dr, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
+    HIP_CHECK(hipStreamSynchronize(e.stream));
+    API_END
+}
+
+extern "C" int bbmpc_set_grad_refine(bbmpc_handle h, int32_t steps, float lr, int32_t method, int32_t candidates) {
+    API_BEGIN
+    CHECK_HANDLE(h);                     // (settles the handle: a resident control-step kernel is stopped first)
+    h->e->set_grad_refine(steps, lr, method, candidates);
+    API_END
+}
+
+extern "C" int bbmpc_get_grad_refine(bbmpc_handle h, int32_t* steps, float* lr, int32_t* method, int32_t* candidates) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(steps);
+    CHECK_PTR(lr);
+    CHECK_PTR(method);
+    CHECK_PTR(candidates);
+    const bbmpc::Engine& e = *h->e;
+    *steps = e.gr_steps;
+    *lr = e.grad_on() ? e.gr_lr : 0.0f;
+    *method = e.grad_on() ? e.gr_method : 0;
+    *candidates = e.grad_on() ? e.gr_M : 0;
+    API_END
+}
 
 extern "C" int bbmpc_set_policy_prior_mlp(bbmpc_handle h, int32_t n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
                                           const float* const* b, int32_t is_normalized, const float* const* stats, int32_t count,

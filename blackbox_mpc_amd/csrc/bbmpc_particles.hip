@@ -20,6 +20,9 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     for (int s = 0; s < S; ++s)
         REQUIRE(std::isfinite(sigma[s]) && sigma[s] >= 0.0f, BBMPC_E_INVALID, "process noise sigma must be finite and >= 0");
     REQUIRE(std::isfinite(kappa), BBMPC_E_INVALID, "risk_kappa must be finite");
+    REQUIRE(!grad_on(), BBMPC_E_UNSUPPORTED,
+            "particles beside gradient refinement (bbmpc_set_grad_refine): the gradient is that of one noise-free rollout; switch it off "
+            "first (steps = 0)");
     REQUIRE(cfg.reward != BBMPC_REW_MLP, BBMPC_E_UNSUPPORTED,
             "particles with a learned reward model (BBMPC_REW_MLP): the particle evaluator scores built-in and HIP-source rewards only");
     REQUIRE(!value_on(), BBMPC_E_UNSUPPORTED,

@@ -30,6 +30,7 @@
 #include "kernels_mlp_wave.hpp"
 #include "kernels_opt.hpp"
 #include "kernels_plan_grad.hpp"
+#include "kernels_plan_refine.hpp"
 #include "kernels_refit.hpp"
 #include "kernels_reward_mlp.hpp"
 #include "kernels_rollout.hpp"
@@ -383,6 +384,28 @@ struct Engine {
     void plan_gradient_check(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats);
     void plan_gradient_pack(int which);
     void plan_gradient_dev(const float* d_states, const float* d_seq, int batch, int horizon, float* d_returns, float* d_grad);
+    void plan_gradient_eligible() const;                // the handle-level refusals of a gradient call (BBMPC_E_UNSUPPORTED)
+    void plan_gradient_sizes(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats);   // state, arguments, sizes
+    // plan refinement on the device (bbmpc_refine_plans; bbmpc_mlp.hip, kernels_plan_refine.hpp): the
+    // loop gradient -> Adam / SGD step -> clip (-> keep-best) on the handle's stream, nothing in between visits the host.
+    // d_rf: gradient | m | v | best [4][n rounded up to 4] | returns [B] | best returns [B]
+    DevBuf<float> d_rf, d_rf_io;
+    void plan_gradient_prepare(size_t ws_floats);
+    void plan_gradient_launch(PlanGradArgs q, size_t lds, const float* d_states, const float* d_seq, float* d_returns, float* d_grad);
+    void refine_plans_check(int batch, int horizon, int steps, float lr, int method, int keep_best, PlanGradArgs& q, size_t& lds, size_t& wsn);
+    void refine_plans_run(const PlanGradArgs& q, size_t lds, size_t wsn, const float* d_states, float* d_seq, int steps, float lr, int method,
+                          int keep_best, float* d_returns_out);
+    void refine_plans_dev(const float* d_states, float* d_seq, int batch, int horizon, int steps, float lr, int method, int keep_best,
+                          float* d_returns_out);
+    // gradient steps on CEM's candidates (bbmpc_set_grad_refine): between the elite injection and the
+    // SRC_BUF rollout, columns [N - M, N) of every agent go through refine_plans_dev (keep_best = 0) from that agent's
+    // state.  While it is on, control steps are routed as with elite carry (one launch sequence per iteration).
+    int gr_steps = 0, gr_method = 0, gr_M = 0;          // gr_M = 0: all N columns
+    float gr_lr = 0.0f;
+    DevBuf<float> d_gr_rows, d_gr_states;               // [A * M][HU] | [A * M][S]
+    bool grad_on() const { return gr_steps > 0; }
+    void set_grad_refine(int steps, float lr, int method, int candidates);
+    void grad_refine_candidates(RolloutArgs& ra);
     void set_user_source(int kind, const char* src, int nparams = 0);
     void set_user_callback(int kind, bbmpc_rows_callback fn, void* user);
     // runtime parameters of a parameterised user reward / dynamics (bbmpc_set_user_params): [A][P] on the device -- a

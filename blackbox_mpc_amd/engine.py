@@ -548,6 +548,47 @@ class Engine:
         L.check(L.lib.bbmpc_plan_gradient_dev(self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_action_sequences), int(batch),
                                               int(horizon), ctypes.c_void_p(d_returns_out or 0), ctypes.c_void_p(d_grad_out)))
 
+    REFINE_METHODS = {"adam": 0, "sgd": 1}
+
+    def refine_plans(self, states, plans, steps, lr, method="adam", keep_best=True):
+        """Plan refinement on the device (bbmpc_refine_plans): `steps` projected ascent steps ("adam" or "sgd", step size
+        lr, clipped to the handle's action bounds) on the model return of plan_gradient, the whole loop on the handle's
+        stream.  states [B,S], plans [B,Hq,U] -> (plans [B,Hq,U] float32, returns [B]).  keep_best: per row the best plan
+        by model return, the input included, and its return; otherwise the last iterate and its return."""
+        if method not in self.REFINE_METHODS:
+            raise ValueError("method must be 'adam' or 'sgd', got %r" % (method,))
+        states = L.f32c(states)
+        seq = np.array(plans, np.float32, order="C")            # a copy: the C side refines it in place
+        b = states.shape[0] if states.ndim == 2 else -1
+        if states.shape != (b, self.S) or seq.ndim != 3 or seq.shape[0] != b or seq.shape[2] != self.U:
+            raise ValueError("states [B,%d] and plans [B,Hq,%d] expected, got %s, %s" % (self.S, self.U, states.shape, seq.shape))
+        out_r = np.empty((b,), np.float32)
+        L.check(L.lib.bbmpc_refine_plans(self._h, L.ptr(states), L.ptr(seq), b, seq.shape[1], int(steps), float(lr),
+                                         self.REFINE_METHODS[method], 1 if keep_best else 0, L.ptr(out_r)))
+        return seq, out_r
+
+    def refine_plans_dev(self, d_states, d_plans, batch, horizon, steps, lr, method="adam", keep_best=True, d_returns_out=0):
+        """The same on device addresses, enqueued on the handle's stream: d_plans is refined in place (d_returns_out may be 0)."""
+        if method not in self.REFINE_METHODS:
+            raise ValueError("method must be 'adam' or 'sgd', got %r" % (method,))
+        L.check(L.lib.bbmpc_refine_plans_dev(self._h, ctypes.c_void_p(d_states), ctypes.c_void_p(d_plans), int(batch), int(horizon),
+                                             int(steps), float(lr), self.REFINE_METHODS[method], 1 if keep_best else 0,
+                                             ctypes.c_void_p(d_returns_out or 0)))
+
+    def set_grad_refine(self, steps, lr=0.05, method="adam", candidates=0):
+        """Gradient steps on CEM's candidates (bbmpc_set_grad_refine): in every iteration the last `candidates` columns of
+        every agent (0: all) take `steps` steps of refine_plans_dev(keep_best=False) before the rollout scores them.
+        steps = 0 switches it off."""
+        if method not in self.REFINE_METHODS:
+            raise ValueError("method must be 'adam' or 'sgd', got %r" % (method,))
+        L.check(L.lib.bbmpc_set_grad_refine(self._h, int(steps), float(lr), self.REFINE_METHODS[method], int(candidates)))
+
+    def get_grad_refine(self):
+        """(steps, lr, method, candidates) of set_grad_refine; steps = 0 while it is off."""
+        s, m, c, lr = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_float()
+        L.check(L.lib.bbmpc_get_grad_refine(self._h, ctypes.byref(s), ctypes.byref(lr), ctypes.byref(m), ctypes.byref(c)))
+        return s.value, lr.value, "sgd" if m.value == 1 else "adam", c.value
+
     def predict_trajectory_particles(self, states, action_sequences, eps=None, want_particles=False, quantile_ranks=None):
         """Trajectory distributions (bbmpc_predict_trajectory_particles): states [B,S], action_sequences [B,Hq,U] ->
         (state_mean [B,Hq,S], state_std [B,Hq,S], reward_mean [B,Hq], reward_std [B,Hq]) over the P particles of

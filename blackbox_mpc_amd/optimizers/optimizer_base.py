@@ -142,6 +142,15 @@ class OptimizerBase:
             return
         h = trajectory_evaluator._system_dynamics_handler
         dk, rk = plugin_kinds(trajectory_evaluator._reward_function, h)
+        grad = getattr(self, "_grad_refine", None)    # CEM with grad_steps / grad_lr / grad_method / grad_candidates
+        if grad is not None:
+            df = h._dynamics_function
+            if (dk != L.DYN_MLP or rk != L.REW_MLP or hasattr(df, "members") or getattr(df, "logvar_heads", None)
+                    or getattr(trajectory_evaluator, "particle_settings", None) is not None):
+                raise ValueError("grad_steps > 0 differentiates the candidates through learned networks: it needs learned dynamics "
+                                 "(DeterministicMLP), a learned reward (LearnedRewardMLP) and the deterministic evaluator, got %s, %s "
+                                 "and %s" % (type(df).__name__, type(trajectory_evaluator._reward_function).__name__,
+                                             type(trajectory_evaluator).__name__))
         if self._engine is not None:
             self._engine.close()
         quirks = self._quirks | int(getattr(trajectory_evaluator, "_quirks", 0))
@@ -168,6 +177,8 @@ class OptimizerBase:
             self._engine.set_elite_carry(*carry)
         if getattr(self, "_policy_prior", None) is not None:   # CEM with policy_prior / prior_candidates / prior_std
             self._configure_policy_prior(self._engine)
+        if grad is not None:
+            self._engine.set_grad_refine(*grad)
         if self._engine._param_fns:
             self._require_engine = self._require_engine_and_params
         else:

@@ -20,14 +20,19 @@ class MPCPolicy(ModelBasedBasePolicy):
                  reward_function=None, env_action_space=None, env_observation_space=None,
                  dynamics_function=None, dynamics_handler=None, true_model=False, optimizer_name=None,
                  num_agents=None, save_model_frequency=1, saved_model_dir=None, terminal_value=None, terminal_weight=1.0,
-                 refine_steps=0, refine_lr=0.05, **optimizer_args):
+                 refine_steps=0, refine_lr=0.05, refine_device=False, **optimizer_args):
         """terminal_value / terminal_weight: a LearnedValueMLP that closes the planning horizon (handed to the
         DeterministicTrajectoryEvaluator this constructor builds; an evaluator passed in takes them itself).
         refine_steps / refine_lr: with refine_steps > 0 every `act` refines the optimizer's plan by that many projected
         gradient steps on the model return (utils.plan_refinement.refine_plan, Engine.plan_gradient) and acts on the refined
         plan's first action; needs learned dynamics and a LearnedRewardMLP.  The optimizer's own warm start is left alone.
-        refine_steps = 0 changes nothing."""
+        refine_steps = 0 changes nothing.  refine_device=True runs those steps on the device (Engine.refine_plans: the same
+        rule in float32, no host visit between steps); the default keeps the host loop.  grad_steps / grad_lr / grad_method /
+        grad_candidates (optimizer_name="CEM") go to CEMOptimizer: gradient steps on the candidates of every iteration."""
         self._refine_steps, self._refine_lr = int(refine_steps), float(refine_lr)
+        if not isinstance(refine_device, (bool, np.bool_)):
+            raise ValueError("refine_device must be a bool, got %r" % (refine_device,))
+        self._refine_device = bool(refine_device)
         if self._refine_steps < 0:
             raise ValueError("refine_steps must be >= 0, got %r" % (refine_steps,))
         if self._refine_steps > 0:
@@ -100,8 +105,11 @@ class MPCPolicy(ModelBasedBasePolicy):
         opt(batched, t, False)
         eng = opt._require_engine()
         plan = eng.get_plan()
-        refined, ret = refine_plan(eng, np.asarray(batched, np.float32), plan, self._refine_steps, self._refine_lr,
-                                   opt._action_lower_bound, opt._action_upper_bound)
+        if self._refine_device:
+            refined, ret = eng.refine_plans(np.asarray(batched, np.float32), plan, self._refine_steps, self._refine_lr)
+        else:
+            refined, ret = refine_plan(eng, np.asarray(batched, np.float32), plan, self._refine_steps, self._refine_lr,
+                                       opt._action_lower_bound, opt._action_upper_bound)
         self._unrefined_plan, self._refined_plan, self._refined_return = plan, refined, ret
         states, rewards = eng.predict_trajectories(np.asarray(batched, np.float32), refined[:, :1])
         return refined[:, 0].copy(), states[:, 0], rewards[:, 0]

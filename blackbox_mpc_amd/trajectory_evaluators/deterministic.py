@@ -250,5 +250,13 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
         ret, grad = self._engine(a, hq).plan_gradient(rows, seq.reshape(n * a, hq, u))
         return ret.reshape(n, a), grad.reshape(n, a, hq, u)
 
+    def refine_plans_rows(self, states, plans, steps, lr, method="adam"):
+        """states [B,S], plans [B,Hq,U] -> (plans [B,Hq,U], returns [B]): Engine.refine_plans (keep-best, the engine's own
+        action bounds) on the engine value_and_gradient uses, so that refitted networks are uploaded first."""
+        plans = np.asarray(plans, np.float32)
+        if plans.ndim != 3:
+            raise ValueError("plans must be [B, planning_horizon, dim_U]")
+        return self._engine(self._one_step_agents(), 1).refine_plans(states, plans, steps, lr, method=method, keep_best=True)
+
     def evaluate_next_reward(self, current_states, next_states, current_actions):
         return self._engine(self._one_step_agents(), 1).evaluate_next_reward(current_states, next_states, current_actions)

@@ -21,6 +21,31 @@ def _backend(obj):
                     % type(obj).__name__)
 
 
+def refine_plan_device(evaluator_or_engine, states, plans, steps, lr, method="adam"):
+    """refine_plan with the whole loop on the device (Engine.refine_plans, bbmpc_refine_plans): the
+    same rule in float32, the bounds the handle's own.  Takes an Engine, or a DeterministicTrajectoryEvaluator (its rows
+    engine, as value_and_gradient).  Returns (plans [B,H,U] in the input's dtype, returns [B] float64); steps = 0 returns
+    the input and its return."""
+    if method not in ("adam", "sgd"):
+        raise ValueError("method must be 'adam' or 'sgd', got %r" % (method,))
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps must be >= 0")
+    if not (float(lr) > 0.0 and np.isfinite(lr)):
+        raise ValueError("lr must be positive and finite")
+    plans = np.asarray(plans)
+    if plans.ndim != 3:
+        raise ValueError("plans must be [B, planning_horizon, dim_U]")
+    if hasattr(evaluator_or_engine, "refine_plans"):
+        out, ret = evaluator_or_engine.refine_plans(states, plans, steps, lr, method=method, keep_best=True)
+    elif hasattr(evaluator_or_engine, "refine_plans_rows"):
+        out, ret = evaluator_or_engine.refine_plans_rows(states, plans, steps, lr, method=method)
+    else:
+        raise TypeError("refine_plan_device needs an Engine (refine_plans) or a DeterministicTrajectoryEvaluator "
+                        "(refine_plans_rows), got %s" % type(evaluator_or_engine).__name__)
+    return out.astype(plans.dtype), np.asarray(ret, np.float64)
+
+
 def refine_plan(evaluator_or_engine, states, plans, steps, lr, lo, hi, method="adam"):
     """Projected gradient ascent on the model return of `plans` [B,H,U] from `states` [B,S]: `steps` updates with step size
     `lr` ("adam": Adam with beta 0.9 / 0.999 on the ascent direction; "sgd": plain ascent), each followed by a clip to the

@@ -256,6 +256,34 @@ int bbmpc_plan_gradient(bbmpc_handle h, const float* states, const float* seq, i
 int bbmpc_plan_gradient_dev(bbmpc_handle h, const float* d_states, const float* d_seq, int32_t batch, int32_t horizon,
                             float* d_returns_out, float* d_grad_out);
 
+/* Plan refinement on the device: projected gradient ascent on the model return of bbmpc_plan_gradient,
+ * the whole loop on the handle's stream.  states [batch][dim_s]; seq [batch][horizon][dim_u] is refined IN PLACE.  Every step:
+ * gradient, then method 0 (Adam, beta 0.9 / 0.999, epsilon 1e-8, on the ascent direction) or 1 (plain ascent), a non-finite
+ * step element counting as 0, x <- clip(x + lr * step, action_low[u], action_high[u]) with the handle's bounds; moments start
+ * at zero in every call.  keep_best = 1: steps + 1 gradient calls, seq receives per row the best plan by model return, the
+ * input included (a NaN return never replaces anything), returns_out [batch] (may be NULL) its return; steps = 0 returns the
+ * input and its return.  keep_best = 0: steps gradient calls, seq receives the last iterate, and returns_out, when not NULL,
+ * costs one more call that scores it.  Refusals: those of bbmpc_plan_gradient, checked before anything is allocated, and
+ * BBMPC_E_INVALID for steps outside [0, 64], lr not finite or not positive, method outside {0, 1}, keep_best outside
+ * {0, 1}.  The _dev form takes device pointers, is ordered on the handle's stream and does not wait for it. */
+int bbmpc_refine_plans(bbmpc_handle h, const float* states, float* seq, int32_t batch, int32_t horizon, int32_t steps, float lr,
+                       int32_t method, int32_t keep_best, float* returns_out);
+int bbmpc_refine_plans_dev(bbmpc_handle h, const float* d_states, float* d_seq, int32_t batch, int32_t horizon, int32_t steps,
+                           float lr, int32_t method, int32_t keep_best, float* d_returns_out);
+/* Gradient steps on CEM's candidates (GradCEM).  In every CEM iteration, after the draw, the policy-prior
+ * rollouts and the elite injection, the last `candidates` columns of every agent (0: all population_size) take `steps`
+ * steps of bbmpc_refine_plans_dev(keep_best = 0, returns_out = NULL) from that agent's current state; the rollout then scores
+ * the buffer as it does otherwise, and the trace's samples are the refined candidates.  While it is on, control steps run one
+ * launch sequence per iteration (no resident, fused or graph-replayed form).  steps = 0 switches it off.
+ * BBMPC_E_UNSUPPORTED: an optimizer other than CEM, a handle bbmpc_plan_gradient would refuse, particles, a sharded
+ * population (particles, a model ensemble and log-variance heads are refused by their own setters while it is on).
+ * BBMPC_E_INVALID: steps outside [0, 64], lr not finite or not positive, method outside {0, 1}, candidates outside
+ * [0, population_size].  Networks not yet installed: BBMPC_E_STATE at the control step.  A refused call leaves the handle as
+ * it was.  bbmpc_reset keeps the setting. */
+int bbmpc_set_grad_refine(bbmpc_handle h, int32_t steps, float lr, int32_t method, int32_t candidates);
+/* The setting; steps = 0 (and zeros) while it is off. */
+int bbmpc_get_grad_refine(bbmpc_handle h, int32_t* steps, float* lr, int32_t* method, int32_t* candidates);
+
 /* User-supplied plug-ins.  The reference takes ANY callable as reward_function / dynamics_function
  * (trajectory_evaluators/deterministic.py:13-18; called at :65-66 as reward(current_state, actions, next_state) and at
  * :99-100 as dynamics(x[B,S+U], train=False) -> delta[B,S]).  A Python callable cannot run inside a kernel; the
