@@ -38,6 +38,7 @@ MAX_ENSEMBLE_MEMBERS = 8                                # bbmpc_set_mlp_ensemble
 LOGVAR_ABS_MAX = 40.0                                   # bbmpc_set_mlp_logvar_head: |min_logvar|, |max_logvar| <= 40
 TRACE_REWARDS, TRACE_MEAN, TRACE_VAR, TRACE_ELITES, TRACE_SAMPLES = 1, 2, 3, 4, 5
 TRACE_CMA_B, TRACE_CMA_C, TRACE_CMA_D, TRACE_CMA_SVD_STATS = 6, 7, 8, 9
+TRACE_TOPK_PASSES = 10
 
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_UNSUPPORTED = -1, -2, -3, -4, -5
 

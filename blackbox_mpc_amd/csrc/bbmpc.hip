@@ -747,6 +747,8 @@ void Engine::ensure_trace() {
         t_var.alloc(nm * nit);
         t_samples.alloc(ns * nit);
         t_elites.alloc(ne * nit);
+        t_passes.alloc((size_t)A * nit);
+        HIP_CHECK(hipMemsetAsync(t_passes.p, 0, (size_t)A * nit * 4, stream));
     }
 }
 
@@ -996,6 +998,7 @@ void Engine::optimize_cem(RolloutArgs& ra) {
         HIP_CHECK(hipMemcpy2DAsync(d_action.p, U * 4, d_prev_mean.p, HU * 4, U * 4, A, hipMemcpyDeviceToDevice, stream));
     const float* inj_t = injected(BBMPC_NOISE_TRUNC_NORMAL);
     const size_t inj_stride = (size_t)A * HU * Nst;
+    if (trace_on) ensure_trace();                         // (the refit kernels store their pass counts into the trace itself)
     // LDS budget for the refit: rewards + elite idx + elite tile
     const int kpad = (k + 3) & ~3;
     const int fixed = Nst + kpad + TOPK_HIST_WORDS + 2 * kpad;
@@ -1046,13 +1049,16 @@ void Engine::optimize_cem(RolloutArgs& ra) {
         if (k <= 64 && !sw.refit_v1) {
             const int rthreads = N > 512 ? 1024 : (N > 256 ? 512 : 256);
             RefitArgs rf2 = rf;
+            rf2.passes = trace_on ? t_passes.p + (size_t)A * it : nullptr;
             if (!trace_on && !carry) rf2.elites = nullptr;   // the sorted elite list is only needed by the parity trace and the elite carry
             if (first_from_constants) { rf2.mean_in = d_prev_mean.p; rf2.var_in = d_var0.p; }
             // G workgroups per agent share the elite gather (kernels_refit.hpp); at least 16 rows each
             const int rg = sw.refit_wgs > 0 ? sw.refit_wgs : std::max(1, std::min(8, HU / 16));
             hipLaunchKernelGGL(k_refit_cem_v2, dim3(rg, A), dim3(rthreads), (size_t)fixed * 4, stream, rf2);
         } else {
-            hipLaunchKernelGGL(k_refit_cem, dim3(A), dim3(REFIT_THREADS), lds, stream, rf, JC);
+            RefitArgs rf1 = rf;
+            rf1.passes = trace_on ? t_passes.p + (size_t)A * it : nullptr;
+            hipLaunchKernelGGL(k_refit_cem, dim3(A), dim3(REFIT_THREADS), lds, stream, rf1, JC);
         }
         HIP_CHECK(hipGetLastError());
         if (carry) {                                      // the elite rows leave the sample buffer before the next draw rewrites it
@@ -1489,6 +1495,12 @@ void Engine::get_trace(int it, int item, void* out, int64_t bytes) {
                                : (cfg.optimizer == BBMPC_OPT_CMAES ? (size_t)cma_G * k : (size_t)A);
             REQUIRE(bytes == (int64_t)cnt * 4, BBMPC_E_INVALID, "trace elites: wrong size");
             HIP_CHECK(hipMemcpy(out, t_elites.p + ne * it, cnt * 4, hipMemcpyDeviceToHost));
+            break;
+        }
+        case BBMPC_TRACE_TOPK_PASSES: {
+            REQUIRE(cfg.optimizer == BBMPC_OPT_CEM, BBMPC_E_INVALID, "trace top-k passes: CEM only");
+            REQUIRE(bytes == (int64_t)A * 4, BBMPC_E_INVALID, "trace top-k passes: wrong size");
+            HIP_CHECK(hipMemcpy(out, t_passes.p + (size_t)A * it, (size_t)A * 4, hipMemcpyDeviceToHost));
             break;
         }
         case BBMPC_TRACE_SAMPLES: {

@@ -149,7 +149,7 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
         if (particles_on()) ra.iter = (uint32_t)it;       // the process noise is drawn per iteration
         q.inj = inj_n ? inj_n + inj_stride * it : nullptr;
         const int kp = (k + 3) & ~3;
-        const size_t lds = (size_t)(Nst + TOPK_HIST_WORDS + 2 * kp) * 4;
+        const size_t lds = (size_t)(Nst + TOPK_HIST_WORDS_NARROW + 2 * kp) * 4;
         const bool small3 = sw.cma_small3 && cma_use_eigh_small() && !pop_sharded();
         if (small3) {
             // n <= 32: sample | roll out | update, three launches per iteration (kernels_eigh_small.hpp)
@@ -183,8 +183,15 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
         if (!mfma_y) hipLaunchKernelGGL(k_cma_bd, dim3((unsigned)((gnn + 255) / 256)), dim3(256), 0, stream, q);
         want_lds((const void*)k_cma_select, lds, 4096 + 512);       // eidx_s[1024] + the selection's small static words
         // selection + path update of an unsharded population share a launch (both one workgroup per instance)
-        const bool merge_sp = !pop_sharded() && n > 128;
-        if (merge_sp) want_lds((const void*)k_cma_select_paths, lds, 4096 + 512 + 4 * 512 * 4 + 2 * 4096 + 256);
+        // -- while the selection's LDS fits beside the path update's static words: at the largest population with the most
+        // elites (N = 32 768, k > 664) it does not, and the two run as the separate launches they are elsewhere (the same
+        // two bodies at the same block size: the same bits)
+        const size_t sp_static = 4096 + 512 + 4 * 512 * 4 + 2 * 4096 + 256;
+        // the documented limits (population 32 768, num_elite 1 024) fit the merged launch with the narrow selection only
+        static_assert((size_t)(32768 + TOPK_HIST_WORDS_NARROW + 2 * 1024) * 4 + 4096 + 512 + 4 * 512 * 4 + 2 * 4096 + 256 <= (size_t)159 * 1024,
+                      "k_cma_select_paths: the selection's LDS words moved the CMA-ES population limit");
+        const bool merge_sp = !pop_sharded() && n > 128 && lds + sp_static <= (size_t)159 * 1024;
+        if (merge_sp) want_lds((const void*)k_cma_select_paths, lds, sp_static);
         // sample -> roll out -> sorted top-k of this handle's particles (part != null: sharded population; the population
         // offset is q's)
         auto shard_pass = [&](int, float* part) {
@@ -395,7 +402,7 @@ void Engine::optimize_fused_cma(const float* d_state_in, int add_noise, float* d
         tail_attached = true;
     }
     const int kp = (k + 3) & ~3;
-    const size_t lds = std::max((size_t)(Nst + TOPK_HIST_WORDS + 2 * kp) * 4, (size_t)cma_n * cma_n * 4);
+    const size_t lds = std::max((size_t)(Nst + TOPK_HIST_WORDS_NARROW + 2 * kp) * 4, (size_t)cma_n * cma_n * 4);
     // (the factorisation's workspace is static LDS: with the dynamic part the kernel is past the 64 KB default)
     ensure_max_lds((const void*)k_fused_cma_pendulum<true>, 32 * 1024);
     ensure_max_lds((const void*)k_fused_cma_pendulum<false>, 32 * 1024);

@@ -186,7 +186,7 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     fa.next_state = d_next_out;
     if (trace_on) {
         ensure_trace();
-        fa.t_rewards = t_rewards.p; fa.t_mean = t_mean.p; fa.t_var = t_var.p; fa.t_elites = t_elites.p; fa.t_samples = t_samples.p;
+        fa.t_rewards = t_rewards.p; fa.t_mean = t_mean.p; fa.t_var = t_var.p; fa.t_elites = t_elites.p; fa.t_passes = t_passes.p; fa.t_samples = t_samples.p;
         if (cfg.optimizer == BBMPC_OPT_SPSA) {
             if (!t_rewards2.p) t_rewards2.alloc((size_t)A * Nst * std::max(iters, 1));
             fa.t_rewards2 = t_rewards2.p;
@@ -283,7 +283,9 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     // rollout reads one float4 past mean[HUp] and past sigma[HUp] when H is a multiple of four: var and eidx (kp >= 4) lie
     // behind them.  A reorder keeps 16 bytes of the carve behind both, or pads them here and there.)
     static_assert(TOPK_HIST_WORDS % 4 == 0, "every piece of the carve is a multiple of 16 bytes");
-    const size_t lds_base = (size_t)(Nst + 3 * HUp + kp + 64 + TOPK_HIST_WORDS + 2 * kp) * 4;
+    static_assert(TOPK_HIST_WORDS_NARROW % 4 == 0, "every piece of the carve is a multiple of 16 bytes");
+    const int hist_words = cfg.optimizer == BBMPC_OPT_CEM ? TOPK_HIST_WORDS : TOPK_HIST_WORDS_NARROW;     // (the kernel's carve: only CEM selects)
+    const size_t lds_base = (size_t)(Nst + 3 * HUp + kp + 64 + hist_words + 2 * kp) * 4;
     const size_t lds_samples = (size_t)HU * Nst * 4;
     prof_begin();
     switch (cfg.optimizer) {

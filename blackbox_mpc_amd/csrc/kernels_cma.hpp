@@ -175,7 +175,7 @@ __device__ __forceinline__ void cma_select_body(const CmaArgs& p, int g, float* 
     const int tid = threadIdx.x;
     float* rs = smem;
     uint32_t* hist = (uint32_t*)(rs + p.Nst);
-    unsigned long long* ekeys = (unsigned long long*)(hist + TOPK_HIST_WORDS);
+    unsigned long long* ekeys = (unsigned long long*)(hist + TOPK_HIST_WORDS_NARROW);   // (the narrow selection: topk.hpp)
     __shared__ int eidx_s[1024];
     for (int q = tid; q < p.N; q += REFIT_THREADS) {
         float s = 0.0f;
@@ -184,7 +184,7 @@ __device__ __forceinline__ void cma_select_body(const CmaArgs& p, int g, float* 
         rs[q] = s;
     }
     __syncthreads();
-    block_topk_sorted(rs, p.N, p.k, eidx_s, hist, ekeys, tid, REFIT_THREADS);   // argsort DESCENDING, first k
+    block_topk_sorted<false>(rs, p.N, p.k, eidx_s, hist, ekeys, tid, REFIT_THREADS);   // argsort DESCENDING, first k
     if (part) {
         const int n = p.n, rowlen = n + 2;
         float* out = part + (size_t)g * p.k * rowlen;

@@ -76,6 +76,7 @@ struct FusedArgs {
     // buffer inj lies in.  Timing only: the request names the pointer, and a fetch from anywhere else is thrown away.
     const float* pf_buf[2];
     unsigned long long pf_step_floats, pf_chunk_floats;      // floats per control step / per chunk buffer (0 = no prediction)
+    int* t_passes;           // trace, with t_elites: [iters][A] radix passes of the elite selection (last: no other field moves)
 };
 
 // (noise_block_index: the float4 index of particle n's first Philox block in the layout k_noise_fill writes,
@@ -107,8 +108,8 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid, int nw)
     return r;
 }
 
-// LDS carve (4-byte words): rewards[Nst] | mean[HUp] | var[HUp] | sigma[HUp] | eidx[kp] | red[64] | hist[272] |
-//                            ekeys[2*kp] | samples[HU][Nst]      (every piece a multiple of 16 B)
+// LDS carve (4-byte words): rewards[Nst] | mean[HUp] | var[HUp] | sigma[HUp] | eidx[kp] | red[64] | hist[..]  |
+//                            ekeys[2*kp] | samples[HU][Nst]      (every piece a multiple of 16 B; hist = TOPK_HIST_WORDS)
 // INVARIANT (the INJ == 2 rollout rests on it): mean[] and sigma[] are each FOLLOWED by at least 16 bytes of this carve.
 // With H a multiple of four the rollout reads one float4 past mean[HUp] and past sigma[HUp] -- here: var[0..3] and
 // eidx[0..3] (kp >= 4) -- and never uses it.  Whoever reorders the carve keeps a piece behind both, or pads them by a block
@@ -132,7 +133,8 @@ __global__ void k_fused_pendulum(FusedArgs p) {
     int* eidx = (int*)(sigma + HUp);
     float* red = (float*)(eidx + kp);
     uint32_t* hist = (uint32_t*)(red + 64);
-    unsigned long long* ekeys = (unsigned long long*)(hist + TOPK_HIST_WORDS);
+    // (only CEM selects: the other optimizers keep the narrow words, i.e. the carve they always had)
+    unsigned long long* ekeys = (unsigned long long*)(hist + (OPT == FOPT_CEM ? TOPK_HIST_WORDS : TOPK_HIST_WORDS_NARROW));
     float* samp = SAMPLES_LDS ? (float*)(ekeys + kp) : (p.samples_g + (size_t)a * p.HU * p.Nst);
 #ifdef BBMPC_KERNEL_DBG
     __shared__ long long dbg_lds[48];
@@ -582,6 +584,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 // the sorted list tf.nn.top_k returns is produced only for the parity trace.  The statistics below always
                 // run over the index-ordered list, so results do not depend on tracing.
                 const TopkSel sel = block_topk_select(rew, p.N, p.k, hist, tid, nthr, true);
+                if (p.t_passes && tid == 0) p.t_passes[(size_t)it * p.A + a] = sel.passes;      // (null unless traced)
                 if (p.t_elites) {
                     block_topk_finish_sorted(rew, p.N, p.k, eidx, hist, ekeys, sel, tid, nthr);
                     for (int e = tid; e < p.k; e += nthr) p.t_elites[((size_t)it * p.A + a) * p.k + e] = eidx[e];
@@ -775,7 +778,13 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             // agent that carries the record itself, stored by relaxed stores with nothing waited for in front; the state
             // carried to the next step (mean_out / var_out / prev_mean) is stored behind it, off the caller's critical path.
             // A workgroup that leaves has stored the line of every step it served before it says so in `gone` (a release).
-            unsigned* mb = (unsigned*)ekeys;                       // 16 words of LDS that are idle outside the top-k
+            // The request's 16 words are handed to the other waves in red[16..31], which nothing else ever writes.  They
+            // used to go through ekeys[]: with num_elite = 0 (PI2, SPSA, RandomSearch) or < 8 that piece of the carve is
+            // shorter than 16 words and the words lay on samples[0][0..15], which wave 0 stores in its first model step of
+            // the next pass -- with no barrier between that store and the other waves' reads below.  A late wave then
+            // decoded part of its state from sample values: config 3 (PI2, 8 agents x 16 waves) gave other results in
+            // a few of every ten 200-step runs, depending on nothing but timing.
+            unsigned* mb = (unsigned*)(red + 16);
             __syncthreads();                                       // mean[] / ekeys / red have been read for the last time
             dist_init(keep_init);
             [[maybe_unused]] const float* inj_pred = nullptr;
@@ -810,8 +819,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             add_noise_s = (int)(mb[2] >> 16);
             inj_s = reinterpret_cast<const float*>(((unsigned long long)(mb[3] >> 16)) | ((unsigned long long)(mb[4] >> 16) << 16) |
                                                    ((unsigned long long)(mb[5] >> 16) << 32) | ((unsigned long long)(mb[6] >> 16) << 48));
-            // (every thread decodes the state itself; `ekeys` is next written behind the rollout's barrier at the earliest --
-            // with iters == 0 behind the barrier in front of the next pass's staging)
+            // (every thread decodes the state itself; red[16..31] is not written again before the next pass's poll)
             s0 = __uint_as_float((mb[7] >> 16) | (mb[8] & 0xffff0000u));
             s1 = __uint_as_float((mb[9] >> 16) | (mb[10] & 0xffff0000u));
             s2 = __uint_as_float((mb[11] >> 16) | (mb[12] & 0xffff0000u));

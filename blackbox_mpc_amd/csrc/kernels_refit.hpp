@@ -77,6 +77,7 @@ struct RefitArgs {
     float* var;            // [A][HU]  in/out (CEM)
     float* sigma;          // [A][HU]  out: sqrt of the constrained variance the NEXT iteration samples with
     int* elites;           // [A][k] out (sorted, best first)   | RandomSearch/PSO: [A] best index
+    int* passes;           // CEM: [A] out, radix passes of the elite selection; null unless traced
     float* action;         // [A][U] out
     const float* mean_in;  // CEM (k_refit_cem_v2): the distribution the smoothing starts from when it is not mean / var themselves
     const float* var_in;   // (first iteration of a control step that skipped k_dist_init: prev_mean / var0), or null
@@ -110,7 +111,7 @@ static __global__ void k_dist_init(int A, int HU, int U, const float* lo, const 
 
 // CEM refit  cem.py:97-125: top-k (sorted, ties -> lower index), elite mean / biased variance
 // (accumulated sequentially in elite order), alpha smoothing.
-// LDS: rewards[Nst] | elite idx[kpad] | hist[272] | ekeys[2*kpad] | elite tile [k][JC]
+// LDS: rewards[Nst] | elite idx[kpad] | hist[TOPK_HIST_WORDS] | ekeys[2*kpad] | elite tile [k][JC]
 static __global__ __launch_bounds__(REFIT_THREADS) void k_refit_cem(RefitArgs p, int JC) {
     extern __shared__ float smem[];
     const int a = blockIdx.x;
@@ -124,7 +125,8 @@ static __global__ __launch_bounds__(REFIT_THREADS) void k_refit_cem(RefitArgs p,
 
     for (int n = tid; n < p.N; n += REFIT_THREADS) r[n] = p.rewards[(size_t)a * p.Nst + n];
     __syncthreads();
-    block_topk_sorted(r, p.N, p.k, eidx, hist, ekeys, tid, REFIT_THREADS);
+    const int passes = block_topk_sorted(r, p.N, p.k, eidx, hist, ekeys, tid, REFIT_THREADS);
+    if (p.passes && tid == 0) p.passes[a] = passes;
     if (p.elites)
         for (int e = tid; e < p.k; e += REFIT_THREADS) p.elites[a * p.k + e] = eidx[e];
 
@@ -183,6 +185,7 @@ static __global__ __launch_bounds__(1024) void k_refit_cem_v2(RefitArgs p) {
     for (int n = tid; n < p.N; n += nthr) r[n] = p.rewards[(size_t)a * p.Nst + n];
     __syncthreads();
     const TopkSel sel = block_topk_select(r, p.N, p.k, hist, tid, nthr);
+    if (p.passes && blockIdx.x == 0 && tid == 0) p.passes[a] = sel.passes;
     if (p.elites && blockIdx.x == 0) {                // parity trace wants tf.nn.top_k's sorted order
         block_topk_finish_sorted(r, p.N, p.k, eidx, hist, ekeys, sel, tid, nthr);
         for (int e = tid; e < p.k; e += nthr) p.elites[a * p.k + e] = eidx[e];

@@ -1,25 +1,30 @@
 // Exact sorted top-k of a workgroup's LDS-resident rewards: tf.nn.top_k(sorted=True) semantics
 // (cem.py:97-99) -- larger first, ties -> lower index first.
 //
-// MSD radix select on order-preserving 32-bit keys: <= 4 passes of 8-bit digits taken below the bits
-// all keys share, each pass one LDS histogram (ds_add_u32) + one 256-bin scan by a single wave, i.e.
-// O(N) work per pass instead of the O(N^2) comparison count of ranking by counting.  That pins the
-// k-th key exactly; the <= k winners are then compacted and ranked among themselves (k^2 comparisons
-// on 64-bit (key,index) words).
+// MSD radix select on order-preserving 32-bit keys, taken as OFFSETS from the smallest key (topk_digits.hpp holds the
+// arithmetic, for the kernels and for a CPU program alike): with B an upper bound of the k-th smallest key, only keys
+// within span = B - kmin take part, the first pass takes the top TOPK_W1 = 10 bits of the span (1024 bins), later
+// passes 8 bits each -- <= 4 passes, each one LDS histogram (ds_add_u32, a few dozen per pass: keys above the bound
+// issue none) + one scan by a single wave, i.e. O(N) work per pass instead of the O(N^2) comparison count of ranking by
+// counting.  A pass is two barriers; most selections of a CEM population end after the first (a digit taken below the
+// highest bit in which kmin and B DIFFER left two or three bins to a population that straddles a binade, and a second
+// pass to five selections in six: profiles/cem_select_offset_digits.md).  That pins the k-th key exactly; the <= k
+// winners are then listed in index order, or compacted and ranked among themselves (k^2 comparisons on 64-bit
+// (key,index) words).
+//
+// LDS (TOPK_HIST_WORDS): second histogram [256] | control words [16] | first histogram [1024].  Pass 0 uses the first
+// histogram (bins at topk_first_slot(), so that wave 0's four 16-byte reads per lane are conflict free), pass 1 the
+// second, pass 2 the first 256 words of the first, ...; the array of pass p + 1 is zeroed while pass p is scanned.
+// The per-wave (kmin, bound) slots live in words [0, 32) of the second histogram.
+// WIDE = false (the CMA-ES kernels): 8 bits in the first pass as well, TOPK_HIST_WORDS_NARROW words, the LDS these
+// kernels had before the wide pass -- their population limit is set by the words beside the rewards.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "topk_digits.hpp"
+
 namespace bbmpc {
-
-constexpr int TOPK_HIST_WORDS = 528;   // histogram A (256 bins) + 16 control words + histogram B (256 bins)
-
-// smaller key == better (larger reward); equal rewards <=> equal keys (-0 is folded onto +0 first)
-__device__ __forceinline__ uint32_t reward_key(float r) {
-    const uint32_t u = __float_as_uint(r + 0.0f);
-    const uint32_t asc = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return ~asc;
-}
 
 // inclusive prefix sum over the 64 lanes: DPP row_shr scan inside each 16-lane row, row totals via readlane
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
@@ -37,7 +42,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
 
 // vals[N] in LDS (left untouched); eidx[k] out; hist[TOPK_HIST_WORDS] and ekeys[k] are LDS scratch.
 // All threads of the workgroup must call (k <= nthr); ends with a barrier (eidx visible to everyone).
-// Barrier budget: 1 (key range) + 2 per radix pass (usually 2 passes) + 1 (compaction) + 2 (ranking).
+// Barrier budget: 1 (key range) + 2 per radix pass (usually 1 pass) + 1 (compaction) + 2 (ranking).
 #ifdef BBMPC_KERNEL_DBG
 __shared__ long long g_topk_dbg[16];
 #define TOPK_DBG(i) do { if (tid == 0) g_topk_dbg[(i)] = (long long)wall_clock64(); } while (0)
@@ -45,26 +50,30 @@ __shared__ long long g_topk_dbg[16];
 #define TOPK_DBG(i) do {} while (0)
 #endif
 
+// Keys are OFFSET keys throughout (reward_key(r) - kmin): T, lim and the key halves of ekeys[] (the order is the same
+// as the real keys').
 struct TopkSel {
-    uint32_t T;          // decided high bits of the k-th key
+    uint32_t kmin;       // smallest key of the population
+    uint32_t T;          // decided high bits of the k-th offset key
+    uint32_t lim;        // eq_total == remaining: offset keys <= lim are the winners (topk_winner_limit)
     uint32_t remaining;  // how many keys of the boundary bucket are winners
-    uint32_t eq_total;   // how many keys the boundary bucket holds
-    int top;             // number of low bits left undecided (early exit)
+    uint32_t eq_total;   // how many keys the boundary bucket holds; != remaining only with no low bit left undecided
+    int passes;          // radix passes the selection took (0: min == bound)
 };
 
 // First part of the selection, up to (not including) its first barrier: every thread reads only the elements
 // n = tid, tid + nthr, ... -- a caller whose threads have just WRITTEN exactly those elements (the persistent kernel's
 // rollout) runs it in front of the barrier it needs anyway and then calls block_topk_select(..., prepass_done = true).
+template <bool WIDE = true>
 __device__ __forceinline__ void block_topk_prepass(const float* vals, int N, int k, uint32_t* hist, int tid, int nthr) {
     const int lane = tid & 63, wave = tid >> 6;
-    uint32_t* hist2 = hist + 272;                // second histogram: zeroed while the other one is scanned
-    // ---- key range: digits are taken from the highest bit where the smallest key and an UPPER BOUND B of the
-    // k-th smallest key differ.  Rewards of one population mostly share sign + exponent, so a fixed top-8-bit
-    // digit would send a whole wave's ds_add_u32 to one or two bins (serialised); and the worst rewards are far
-    // outliers, so [min, max] would still squeeze everything that matters into a few bins.  Bound: every 16-lane
-    // row contributes its two smallest keys (distinct elements); if that makes >= k elements, the largest of them
-    // is >= the k-th smallest overall.  Keys that do not share the common prefix of (min, B) are > B and never
-    // enter a histogram.
+    uint32_t* hist2 = hist + TOPK_HIST2_OFF;     // second histogram; its first 32 words carry the per-wave slots first
+    // ---- key range: digits are taken from the top of span = B - min, B an UPPER BOUND of the k-th smallest key.
+    // Rewards of one population mostly share sign + exponent, so a fixed top-8-bit digit would send a whole wave's
+    // ds_add_u32 to one or two bins (serialised); and the worst rewards are far outliers, so [min, max] would still
+    // squeeze everything that matters into a few bins.  Bound: every 16-lane row contributes its two smallest keys
+    // (distinct elements); if that makes >= k elements, the largest of them is >= the k-th smallest overall.  Keys
+    // above B never enter a histogram.
     uint32_t k1 = 0xFFFFFFFFu, kmaxl = 0u;           // this lane's smallest key (one element per lane) / largest
     for (int n = tid; n < N; n += nthr) {
         const uint32_t key = reward_key(vals[n]);
@@ -98,21 +107,58 @@ __device__ __forceinline__ void block_topk_prepass(const float* vals, int N, int
                                     : (uint32_t)__builtin_amdgcn_readlane((int)kmaxl, 16 * r);
         if (!bound_ok || row < rows_ok) kmax = max(kmax, b);
     }
-    // per-wave slots instead of atomics; the min of wave w goes to hist[w] (low bins), the bound to hist[16+w],
-    // both are consumed before the first histogram pass touches the bins
-    if (lane == 0) { hist[wave] = kmin; hist[16 + wave] = kmax; }
-    for (int i = tid; i < 256; i += nthr) hist2[i] = 0;          // first pass histograms into hist2
+    // per-wave slots instead of atomics; the min of wave w goes to hist2[w], the bound to hist2[16+w]: the first pass
+    // does not use that array, and it is zeroed for the second one behind the barrier all slots are read in front of
+    if (lane == 0) { hist2[wave] = kmin; hist2[16 + wave] = kmax; }
+    // the first pass histograms into the first histogram's 1024 words: two words per thread at 512 threads
+    uint2* hz = reinterpret_cast<uint2*>(hist + TOPK_HIST1_OFF);
+    for (int i = tid; i < (WIDE ? TOPK_BINS1 : TOPK_BINSN) / 2; i += nthr) hz[i] = make_uint2(0u, 0u);
+}
+
+// wave 0's part of a pass over the FIRST histogram (1024 bins at topk_first_slot()): lane l holds the 16 consecutive bins
+// 16 l .. 16 l + 15 in four vectors; after the wave scan has found the lane, the bin is found among its 16 with a
+// two-level compare and select (the quad, then the element) -- no serial search, no indexed register array.
+__device__ __forceinline__ void topk_scan_first(const uint32_t* h, uint32_t* ctrl, uint32_t remaining, int lane) {
+    const uint4* hv = reinterpret_cast<const uint4*>(h);
+    const uint4 c0 = hv[lane], c1 = hv[64 + lane], c2 = hv[128 + lane], c3 = hv[192 + lane];
+    const uint32_t s0 = c0.x + c0.y + c0.z + c0.w, s1 = c1.x + c1.y + c1.z + c1.w;
+    const uint32_t s2 = c2.x + c2.y + c2.z + c2.w, s3 = c3.x + c3.y + c3.z + c3.w;
+    const uint32_t s = (s0 + s1) + (s2 + s3);
+    const uint32_t incl = wave_incl_scan(s, lane);
+    const uint32_t excl = incl - s;
+    if (excl < remaining && remaining <= incl) {            // exactly one lane
+        const uint32_t p1 = excl + s0, p2 = p1 + s1, p3 = p2 + s2;       // keys in front of quads 1, 2, 3
+        const bool g1 = remaining > p1, g2 = remaining > p2, g3 = remaining > p3;       // (g3 => g2 => g1)
+        const uint32_t q = (uint32_t)g1 + (uint32_t)g2 + (uint32_t)g3;
+        const uint32_t pq = g3 ? p3 : (g2 ? p2 : (g1 ? p1 : excl));
+        const uint32_t x = g3 ? c3.x : (g2 ? c2.x : (g1 ? c1.x : c0.x));
+        const uint32_t y = g3 ? c3.y : (g2 ? c2.y : (g1 ? c1.y : c0.y));
+        const uint32_t z = g3 ? c3.z : (g2 ? c2.z : (g1 ? c1.z : c0.z));
+        const uint32_t w = g3 ? c3.w : (g2 ? c2.w : (g1 ? c1.w : c0.w));
+        const uint32_t e1 = pq + x, e2 = e1 + y, e3 = e2 + z;            // keys in front of elements 1, 2, 3
+        const bool h1 = remaining > e1, h2 = remaining > e2, h3 = remaining > e3;
+        const uint32_t e = (uint32_t)h1 + (uint32_t)h2 + (uint32_t)h3;
+        const uint32_t cum = h3 ? e3 : (h2 ? e2 : (h1 ? e1 : pq));
+        const uint32_t cnt = h3 ? w : (h2 ? z : (h1 ? y : x));
+        ctrl[0] = 16u * (uint32_t)lane + 4u * q + e;
+        ctrl[1] = remaining - cum;     // how many keys of this bucket are still wanted
+        ctrl[2] = cnt;                 // how many keys the bucket holds
+        ctrl[3] = 0;                   // compaction cursor
+    }
 }
 
 // Selection only: pins the boundary bucket of the k-th key.  Ends with a barrier; ctrl[3] (compaction cursor) is 0.
+template <bool WIDE = true>
 __device__ __forceinline__ TopkSel block_topk_select(const float* vals, int N, int k, uint32_t* hist, int tid, int nthr,
                                                      bool prepass_done = false) {
     const int lane = tid & 63, nw = nthr >> 6;
     TOPK_DBG(0);
-    uint32_t* ctrl = hist + 256;                 // [0] bucket [1] wanted [2] bucket size [3] compaction cursor
-    uint32_t* hist2 = hist + 272;                // second histogram: zeroed while the other one is scanned
+    uint32_t* ctrl = hist + TOPK_CTRL_OFF;       // [0] bucket [1] wanted [2] bucket size [3] compaction cursor
+    uint32_t* hist2 = hist + TOPK_HIST2_OFF;     // second histogram; its first 32 words carry the per-wave slots first
+    uint32_t* hist1 = hist + TOPK_HIST1_OFF;     // first histogram: 1024 words (WIDE) or 256
+    constexpr int W1 = WIDE ? TOPK_W1 : TOPK_WN;
     if (!prepass_done) {
-        block_topk_prepass(vals, N, k, hist, tid, nthr);
+        block_topk_prepass<WIDE>(vals, N, k, hist, tid, nthr);
         __syncthreads();
     }
     uint32_t kmin, kmax;
@@ -120,63 +166,71 @@ __device__ __forceinline__ TopkSel block_topk_select(const float* vals, int N, i
     // combine the (<= 16) per-wave slots with ONE LDS round trip: lane w fetches wave w's pair, then a 16-lane DPP
     // reduction (a serial loop over the slots costs one LDS latency per wave)
     kmin = 0xFFFFFFFFu; kmax = 0u;
-    if (lane < nw) { kmin = hist[lane]; kmax = hist[16 + lane]; }
+    if (lane < nw) { kmin = hist2[lane]; kmax = hist2[16 + lane]; }
 #define BB_ROW_U32(op, v, ctrl) v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, 0xf, 0xf, false))
     BB_ROW_U32(min, kmin, 0xB1); BB_ROW_U32(min, kmin, 0x4E); BB_ROW_U32(min, kmin, 0x141); BB_ROW_U32(min, kmin, 0x140);
     BB_ROW_U32(max, kmax, 0xB1); BB_ROW_U32(max, kmax, 0x4E); BB_ROW_U32(max, kmax, 0x141); BB_ROW_U32(max, kmax, 0x140);
 #undef BB_ROW_U32
     kmin = (uint32_t)__builtin_amdgcn_readlane((int)kmin, 0);
     kmax = (uint32_t)__builtin_amdgcn_readlane((int)kmax, 0);
-    const uint32_t diff = kmin ^ kmax;
-    int top = diff ? 32 - __clz(diff) : 0;        // number of low bits that are not common to all keys
-    uint32_t T = (top >= 32) ? 0u : (kmin >> top) << top;   // common high bits
+    const TopkRange rg = topk_range(kmin, kmax);
+    const uint32_t span = rg.span;
+    int top = rg.top;                             // number of low bits of the k-th OFFSET key still undecided
+    uint32_t T = 0u;                              // its decided high bits
     uint32_t remaining = (uint32_t)k;
-    uint32_t eq_total = (uint32_t)N;              // top == 0: every key equal
+    uint32_t eq_total = (uint32_t)N;              // span == 0: at least k keys equal the smallest
     int pass = 0;
-    // hist is still being read above by slower waves: the first pass uses hist2 (zeroed before the barrier),
-    // later passes alternate; the array for pass p+1 is zeroed by the idle waves while wave 0 scans pass p.
+    // The first pass uses the 1024-bin histogram (zeroed before the barrier; the slots read above are in hist2), the
+    // second hist2, later ones alternate between the first 256 words of hist1 and hist2; the array for pass p+1 is zeroed
+    // by the idle waves while wave 0 scans pass p.
     while (top > 0) {
-        uint32_t* h = (pass & 1) ? hist : hist2;
-        uint32_t* hn = (pass & 1) ? hist2 : hist;
-        const int width = top >= 8 ? 8 : top;
-        const int shift = top - width;
-        const uint32_t dmask = (1u << width) - 1u;
+        uint32_t* h = (pass & 1) ? hist2 : hist1;
+        uint32_t* hn = (pass & 1) ? hist1 : hist2;
+        const int shift = topk_pass_shift(pass, top, W1);
         for (int n = tid; n < N; n += nthr) {
-            const uint32_t key = reward_key(vals[n]);
-            const bool in = (top >= 32) || ((key >> top) == (T >> top));
+            const uint32_t kp = topk_offset_key(vals[n], kmin);
+            if (topk_takes_part(kp, span, T, top)) {
+                const uint32_t d = topk_digit(kp, pass, top, W1);
+                const uint32_t slot = (WIDE && pass == 0) ? topk_first_slot(d) : d;
 #ifdef BBMPC_EXP_NOATOMIC
-            if (in) h[(key >> shift) & dmask] = 1u;
+                h[slot] = 1u;
 #else
-            if (in) atomicAdd(&h[(key >> shift) & dmask], 1u);
+                atomicAdd(&h[slot], 1u);
 #endif
+            }
         }
         __syncthreads();
         TOPK_DBG(2 + 2 * pass);
         if (tid < 64) {
-            const uint4 c = *reinterpret_cast<const uint4*>(h + 4 * lane);
-            const uint32_t s = c.x + c.y + c.z + c.w;
-            const uint32_t incl = wave_incl_scan(s, lane);
-            const uint32_t excl = incl - s;
-            if (excl < remaining && remaining <= incl) {        // exactly one lane
-                uint32_t cum = excl, b = 4 * lane, cnt = c.x;
-                if (cum + c.x < remaining) { cum += c.x; b += 1; cnt = c.y;
-                    if (cum + c.y < remaining) { cum += c.y; b += 1; cnt = c.z;
-                        if (cum + c.z < remaining) { cum += c.z; b += 1; cnt = c.w; } } }
-                ctrl[0] = b;
-                ctrl[1] = remaining - cum;     // how many keys of this bucket are still wanted
-                ctrl[2] = cnt;                 // how many keys the bucket holds
-                ctrl[3] = 0;                   // compaction cursor
+            if (WIDE && pass == 0) {
+                topk_scan_first(h, ctrl, remaining, lane);
+            } else {
+                const uint4 c = *reinterpret_cast<const uint4*>(h + 4 * lane);
+                const uint32_t s = c.x + c.y + c.z + c.w;
+                const uint32_t incl = wave_incl_scan(s, lane);
+                const uint32_t excl = incl - s;
+                if (excl < remaining && remaining <= incl) {        // exactly one lane
+                    uint32_t cum = excl, b = 4 * lane, cnt = c.x;
+                    if (cum + c.x < remaining) { cum += c.x; b += 1; cnt = c.y;
+                        if (cum + c.y < remaining) { cum += c.y; b += 1; cnt = c.z;
+                            if (cum + c.z < remaining) { cum += c.z; b += 1; cnt = c.w; } } }
+                    ctrl[0] = b;
+                    ctrl[1] = remaining - cum;     // how many keys of this bucket are still wanted
+                    ctrl[2] = cnt;                 // how many keys the bucket holds
+                    ctrl[3] = 0;                   // compaction cursor
+                }
             }
         } else {
-            for (int i = tid - 64; i < 256; i += nthr - 64) hn[i] = 0;
+            for (int i = tid - 64; i < TOPK_BINSN; i += nthr - 64) hn[i] = 0;
         }
         if (nthr == 64)
-            for (int i = tid; i < 256; i += 64) hn[i] = 0;
+            for (int i = tid; i < TOPK_BINSN; i += 64) hn[i] = 0;
         __syncthreads();
         TOPK_DBG(3 + 2 * pass);
-        T |= ctrl[0] << shift;
-        remaining = ctrl[1];
-        eq_total = ctrl[2];
+        // (every lane reads the same words: scalar registers)
+        T |= (uint32_t)__builtin_amdgcn_readfirstlane((int)ctrl[0]) << shift;
+        remaining = (uint32_t)__builtin_amdgcn_readfirstlane((int)ctrl[1]);
+        eq_total = (uint32_t)__builtin_amdgcn_readfirstlane((int)ctrl[2]);
         top = shift;
         ++pass;
         if (eq_total == remaining) break;      // every key of the boundary bucket is a winner: the undecided
@@ -186,19 +240,17 @@ __device__ __forceinline__ TopkSel block_topk_select(const float* vals, int N, i
         __syncthreads();                       // exact tie path (lowest indices win)
         eq_total = remaining + 1u;
     }
-    return TopkSel{T, remaining, eq_total, top};
+    return TopkSel{kmin, T, topk_winner_limit(span, T, top), remaining, eq_total, pass};
 }
 
 // Winner test for element n given the selection (exact ties at the boundary: lowest indices win)
 __device__ __forceinline__ bool topk_is_winner(const float* vals, int n, const TopkSel& s) {
-    const uint32_t Tp = (s.top >= 32) ? 0u : (s.T >> s.top);
-    const uint32_t key = reward_key(vals[n]);
-    const uint32_t kp_ = (s.top >= 32) ? 0u : (key >> s.top);
-    if (kp_ < Tp) return true;
-    if (kp_ != Tp) return false;
-    if (s.eq_total == s.remaining) return true;                  // the whole boundary bucket is in
-    uint32_t before = 0;                                         // top == 0 here (rare): count equal keys ahead of n
-    for (int m = 0; m < n; ++m) before += (reward_key(vals[m]) == s.T) ? 1u : 0u;
+    const uint32_t kp = topk_offset_key(vals[n], s.kmin);
+    if (s.eq_total == s.remaining) return kp <= s.lim;           // the whole boundary bucket is in
+    if (kp < s.T) return true;                                   // no low bit is undecided here (rare): T is the k-th key
+    if (kp != s.T) return false;
+    uint32_t before = 0;                                         // count equal keys ahead of n
+    for (int m = 0; m < n; ++m) before += (topk_offset_key(vals[m], s.kmin) == s.T) ? 1u : 0u;
     return before < s.remaining;
 }
 
@@ -237,24 +289,21 @@ __device__ __forceinline__ void block_topk_finish_indexed(const float* vals, int
 // Finish B: the k winners sorted (tf.nn.top_k(sorted=True)): atomic compaction + k x k ranking.
 __device__ __forceinline__ void block_topk_finish_sorted(const float* vals, int N, int k, int* eidx, uint32_t* hist,
                                                          unsigned long long* ekeys, const TopkSel& sel, int tid, int nthr) {
-    uint32_t* ctrl = hist + 256;
-    const uint32_t T = sel.T, remaining = sel.remaining, eq_total = sel.eq_total;
-    const int top = sel.top;
-    // ---- compaction of the winners (any order); `top` low bits may be undecided after an early exit
-    const uint32_t Tp = (top >= 32) ? 0u : (T >> top);
+    uint32_t* ctrl = hist + TOPK_CTRL_OFF;
+    const uint32_t T = sel.T, remaining = sel.remaining, eq_total = sel.eq_total, kmin = sel.kmin;
+    // ---- compaction of the winners (any order); low bits may be undecided after an early exit: sel.lim covers them
     for (int e = tid; e < k; e += nthr) eidx[e] = 0;             // rank counters for the next phase
     if (eq_total == remaining) {                                 // the whole boundary bucket is in (the usual case)
         for (int n = tid; n < N; n += nthr) {
-            const uint32_t key = reward_key(vals[n]);
-            const uint32_t kp_ = (top >= 32) ? 0u : (key >> top);
-            if (kp_ <= Tp) {
+            const uint32_t key = topk_offset_key(vals[n], kmin);
+            if (key <= sel.lim) {
                 const uint32_t slot = atomicAdd(&ctrl[3], 1u);
                 ekeys[slot] = ((unsigned long long)key << 32) | (uint32_t)n;
             }
         }
         __syncthreads();
     } else {
-        // top == 0 here: more keys EQUAL the k-th one than are wanted, the lowest indices win.  The number of equal keys
+        // no low bit undecided here: more keys EQUAL the k-th one than are wanted, the lowest indices win.  The number of equal keys
         // ahead of element n comes from a ballot / prefix count per wave and the waves' totals (one barrier per round of
         // nthr elements) -- counting them one by one per element was 25-30 us when a hundred candidates tie, which is the
         // steady state of CMA-ES on the pendulum: its step size is never reset (cma_es.py:215-227 restores m and sigma at
@@ -266,7 +315,7 @@ __device__ __forceinline__ void block_topk_finish_sorted(const float* vals, int 
         int round = 0;
         for (int n0 = 0; n0 < N; n0 += nthr, ++round) {
             const int n = n0 + tid;
-            const uint32_t key = n < N ? reward_key(vals[n]) : 0xFFFFFFFFu;
+            const uint32_t key = n < N ? topk_offset_key(vals[n], kmin) : 0xFFFFFFFFu;
             const bool tie = n < N && key == T;
             const unsigned long long bal = __ballot(tie);
             const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
@@ -310,10 +359,13 @@ __device__ __forceinline__ void block_topk_finish_sorted(const float* vals, int 
 
 // vals[N] in LDS (left untouched); eidx[k] out; hist[TOPK_HIST_WORDS] and ekeys[k] are LDS scratch.
 // All threads of the workgroup must call (k <= nthr); ends with a barrier (eidx visible to everyone).
-__device__ __forceinline__ void block_topk_sorted(const float* vals, int N, int k, int* eidx, uint32_t* hist,
-                                                  unsigned long long* ekeys, int tid, int nthr) {
-    const TopkSel sel = block_topk_select(vals, N, k, hist, tid, nthr);
+// Returns the number of radix passes the selection took.
+template <bool WIDE = true>
+__device__ __forceinline__ int block_topk_sorted(const float* vals, int N, int k, int* eidx, uint32_t* hist,
+                                                 unsigned long long* ekeys, int tid, int nthr) {
+    const TopkSel sel = block_topk_select<WIDE>(vals, N, k, hist, tid, nthr);
     block_topk_finish_sorted(vals, N, k, eidx, hist, ekeys, sel, tid, nthr);
+    return sel.passes;
 }
 
 }  // namespace bbmpc

@@ -805,6 +805,8 @@ class Engine:
                 out = np.empty((groups, self.k), np.int32)
             else:
                 out = np.empty((self.A,), np.int32)
+        elif item == L.TRACE_TOPK_PASSES:
+            out = np.empty((self.A,), np.int32)
         elif item == L.TRACE_SAMPLES:
             out = np.empty((self.N, self.A, self.H, self.U), np.float32)
         elif item in (L.TRACE_CMA_B, L.TRACE_CMA_C, L.TRACE_CMA_D):

@@ -114,6 +114,8 @@ extern "C" {
                                      * Jacobi ran for it; on the Jacobi-only paths 1 = sweep 0 rotated something.  n <= 32 (one
                                      * workgroup factorises, falls back and finishes in one kernel) records nothing: all zero. */
 #define BBMPC_TRACE_CMA_D   8   /* CMA-ES [G,n]   diag(D) = sqrt(eigenvalues) after the iteration (:197,205)   */
+#define BBMPC_TRACE_TOPK_PASSES 10 /* CEM int32 [A]: radix passes the iteration's elite selection took (csrc/topk.hpp); the persistent pendulum
+                                     * kernel and the per-iteration refit kernels record it, every other path leaves 0 */
 
 typedef struct bbmpc_handle_s* bbmpc_handle;
 
