@@ -712,7 +712,7 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
     }
     if (cfg.dynamics == BBMPC_DYN_MLP) {
         dominant_kernel = "k_rollout_mlp";
-        launch_rollout_mlp(mode, pen, ra, false, nullptr);
+        launch_rollout_mlp(mode, pen, ra, false, nullptr, nullptr);
         return;
     }
     // few trajectories -> one wave per workgroup so every wave gets its own SIMD (latency);
@@ -1319,7 +1319,7 @@ void Engine::step_dev(const float* d_states, const float* d_actions, int astride
         ra.rewards = rew;
         const bool prof = profiling;
         profiling = false;
-        launch_rollout_mlp(SRC_REF, false, ra, true, d_next);
+        launch_rollout_mlp(SRC_REF, false, ra, true, d_next, nullptr);
         profiling = prof;
         return;
     }

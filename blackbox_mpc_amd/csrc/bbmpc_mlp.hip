@@ -285,8 +285,202 @@ void Engine::set_mlp_logvar_head(int num_heads, const float* const* w, const flo
     lv_heads = num_heads;
 }
 
-void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_particle_state, float* final_state) {
+// an activation after sigmoid (activations.hpp): the *_ext instantiations, which dispatch over every code; networks of
+// none / tanh / relu / sigmoid keep the kernels they always ran
+static bool mlp_has_ext_act(const MlpDesc& d) {
+    for (int l = 0; l < d.n_layers; ++l)
+        if (d.act[l] > BBMPC_ACT_SIGMOID) return true;
+    return false;
+}
+
+// `hidden` on every hidden layer and a linear output: the networks whose activations some instantiations take at compile time
+static bool mlp_is_hidden_act_net(const MlpDesc& d, int hidden) {
+    for (int l = 0; l + 1 < d.n_layers; ++l)
+        if (d.act[l] != hidden) return false;
+    return d.act[d.n_layers - 1] == BBMPC_ACT_NONE;
+}
+static bool mlp_is_tanh_net(const MlpDesc& d) { return mlp_is_hidden_act_net(d, BBMPC_ACT_TANH); }
+
+// Launch of a kernel that takes one argument struct by value; where it needs more dynamic LDS than the 64 KB default the
+// kernel's limit is raised to lds_cap first (ensure_max_lds: once per device and kernel)
+template <class Args>
+static void launch_args(void (*fn)(Args), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args& q, int lds_cap = 159 * 1024) {
+    if (lds > 64 * 1024) ensure_max_lds((const void*)fn, lds_cap);
+    hipLaunchKernelGGL(fn, grid, block, lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+}
+
+// What Engine::choose_rollout_mlp decides and Engine::launch_rollout_mlp carries out
+struct MlpLaunch {
+    using Fn = void (*)(MlpRolloutArgs);
+    Fn fn;
+    dim3 grid, block;
+    size_t lds;                     // dynamic LDS of the launch
+    int lds_cap;                    // what the kernel's limit is raised to when lds passes the 64 KB default
+    bool raise_lds_always;          // ... or whatever lds is
+    const char* name;               // dominant_kernel; nullptr: the caller's stays
+    char inst[128];                 // dominant_inst; empty: what is there stays
+    bool takes_state_copy;          // the kernel serves a mlp_state_copy request
+};
+
+// Which kernel rolls the learned model out, and in what launch shape: every instantiation of kernels_mlp*.hpp is named here
+// and nowhere else.  In order of precedence: the opt-in bf16 modes, the two small-network kernels, the quad kernels and
+// the pipelined tile kernel of the 26-200-200-20 family, the generic kernel (spec 0..2) and its one-step form (spec 3).
+MlpLaunch Engine::choose_rollout_mlp(const RolloutArgs& ra, bool per_particle_state, bool final_state, bool record) const {
+    using Fn = MlpLaunch::Fn;
+    const int L = mlp.n_layers;
+    const unsigned tiles16 = (ra.n_pop + MLP_TP - 1) / MLP_TP, quads = (ra.n_pop + 3) / 4, rows_y = per_particle_state ? 1 : A;
+    auto pick = [](Fn fn, dim3 grid, dim3 block, size_t lds, const char* name, int lds_cap = 159 * 1024) {
+        MlpLaunch k;
+        memset(&k, 0, sizeof(k));
+        k.fn = fn; k.grid = grid; k.block = block; k.lds = lds; k.lds_cap = lds_cap; k.name = name;
+        return k;
+    };
+    const size_t lds = (size_t)mlp_lds_layout(mlp, ra.H, U, S, mlp_nw).total * sizeof(float);
+    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED,
+            "learned-model rollout: a 16-particle tile's action block (planning_horizon x 16 x dim_u floats) plus the activation / "
+            "partial-sum buffers of this network do not fit one CU's LDS (shorten the horizon or narrow the network)");
+    // weights-stationary specialisations (kernels_mlp.hpp)
+    int spec = 0;
+    const bool small_io = mlp.tiles[0] <= 2 && mlp.tiles[L] <= 2;
+    if (small_io && L == 3 && mlp.tiles[1] == mlp.tiles[2] && mlp.tiles[1] <= 16 && mlp_nw == mlp.tiles[1]) spec = 1;
+    if (small_io && L == 4 && mlp.tiles[1] == mlp.tiles[2] && mlp.tiles[2] == mlp.tiles[3] && mlp.tiles[1] <= 4 && mlp_nw == mlp.tiles[1]) spec = 2;
+    if (sw.mlp_generic) spec = 0;
+    const bool single_step = per_particle_state && ra.H == 1;
+    if (single_step) spec = 3;
+    const bool ext = mlp_has_ext_act(mlp), tanh_net = mlp_is_tanh_net(mlp);
+
+    // opt-in reduced-precision mode (kernels_mlp.hpp): never selected automatically; trajectory recording lives in
+    // rollout_mlp_body's epilogue only
+    if (sw.mlp_bf16 && spec == 1 && !per_particle_state && !final_state && !record) {
+        const bool split = sw.mlp_bf16 == 3;
+        return pick(split ? k_rollout_mlp_bf16<3> : k_rollout_mlp_bf16<1>, dim3(tiles16, A), dim3(mlp_nw * 64), lds,
+                    split ? "k_rollout_mlp_bf16<3>" : "k_rollout_mlp_bf16<1>");
+    }
+
+    // small networks, one wave per four particles and nothing through LDS between layers (kernels_mlp_w4.hpp): 2..4 Dense
+    // layers of at most 32 units, dim_S <= 20, dim_U <= 8 -- the reference tutorials' 4-32-32-32-3 and 26-32-32-32-20
+    // (bbmpc_set_mlp packed the operands: the shape qualifies)
+    if (!sw.mlp_generic && sw.mlp_w4 != 0 && !single_step && d_w4pack.p != nullptr) {
+        const size_t wlds = (size_t)mlp_w4_lds_layout(ra.H, U, S).total * sizeof(float);
+        if (wlds <= 159 * 1024) {
+            static const Fn table[2][3] = {{k_rollout_mlp_w4<2, false>, k_rollout_mlp_w4<3, false>, k_rollout_mlp_w4<4, false>},
+                                           {k_rollout_mlp_w4<2, true>, k_rollout_mlp_w4<3, true>, k_rollout_mlp_w4<4, true>}};
+            static const Fn table_ext[3] = {k_rollout_mlp_w4_ext<2>, k_rollout_mlp_w4_ext<3>, k_rollout_mlp_w4_ext<4>};
+            MlpLaunch k = pick(ext ? table_ext[L - 2] : table[tanh_net ? 1 : 0][L - 2], dim3((ra.n_pop + W4_TP - 1) / W4_TP, rows_y), dim3(256),
+                               wlds, "k_rollout_mlp_w4");
+            if (ext) snprintf(k.inst, sizeof(k.inst), "k_rollout_mlp_w4_ext<%d>", L);
+            else snprintf(k.inst, sizeof(k.inst), "k_rollout_mlp_w4<%d, %s>", L, tanh_net ? "true" : "false");
+            return k;
+        }
+    }
+
+    // small networks: one wave per 16-particle tile, the whole Dense stack in its registers (kernels_mlp_wave.hpp)
+    if (!sw.mlp_generic && sw.mlp_wave != 0 && !single_step && small_io && L >= 2 && L <= 4 && mlp.tiles[1] <= 4) {
+        bool same = true;
+        for (int l = 2; l < L; ++l) same = same && mlp.tiles[l] == mlp.tiles[1];
+        const int wht = mlp.tiles[1];
+        const size_t wlds = (size_t)mlp_wave_lds_layout(ra.H, U, S, L - 1, wht).total * sizeof(float);
+        if (same && wlds <= 159 * 1024) {
+            static const Fn table[2][3][4] = {
+                {{k_rollout_mlp_wave<1, 1, false>, k_rollout_mlp_wave<1, 2, false>, k_rollout_mlp_wave<1, 3, false>, k_rollout_mlp_wave<1, 4, false>},
+                 {k_rollout_mlp_wave<2, 1, false>, k_rollout_mlp_wave<2, 2, false>, k_rollout_mlp_wave<2, 3, false>, k_rollout_mlp_wave<2, 4, false>},
+                 {k_rollout_mlp_wave<3, 1, false>, k_rollout_mlp_wave<3, 2, false>, k_rollout_mlp_wave<3, 3, false>, k_rollout_mlp_wave<3, 4, false>}},
+                {{k_rollout_mlp_wave<1, 1, true>, k_rollout_mlp_wave<1, 2, true>, k_rollout_mlp_wave<1, 3, true>, k_rollout_mlp_wave<1, 4, true>},
+                 {k_rollout_mlp_wave<2, 1, true>, k_rollout_mlp_wave<2, 2, true>, k_rollout_mlp_wave<2, 3, true>, k_rollout_mlp_wave<2, 4, true>},
+                 {k_rollout_mlp_wave<3, 1, true>, k_rollout_mlp_wave<3, 2, true>, k_rollout_mlp_wave<3, 3, true>, k_rollout_mlp_wave<3, 4, true>}}};
+            static const Fn table_ext[3][4] = {
+                {k_rollout_mlp_wave<1, 1, false, true>, k_rollout_mlp_wave<1, 2, false, true>, k_rollout_mlp_wave<1, 3, false, true>, k_rollout_mlp_wave<1, 4, false, true>},
+                {k_rollout_mlp_wave<2, 1, false, true>, k_rollout_mlp_wave<2, 2, false, true>, k_rollout_mlp_wave<2, 3, false, true>, k_rollout_mlp_wave<2, 4, false, true>},
+                {k_rollout_mlp_wave<3, 1, false, true>, k_rollout_mlp_wave<3, 2, false, true>, k_rollout_mlp_wave<3, 3, false, true>, k_rollout_mlp_wave<3, 4, false, true>}};
+            return pick(ext ? table_ext[L - 2][wht - 1] : table[tanh_net ? 1 : 0][L - 2][wht - 1], dim3(tiles16, rows_y),
+                        dim3(64 * mlp_wave_waves(wht)), wlds, "k_rollout_mlp_wave");
+        }
+    }
+
+    // the 26-200-200-20 tanh/tanh/linear family has its own kernels (all of them can record the trajectory)
+    const bool fam_dims = spec == 1 && mlp.tiles[1] == 13 && !per_particle_state;     // (spec == 1: two hidden layers of equal tile count, <= 32 inputs and outputs)
+    const bool fam_ok = fam_dims && tanh_net;
+    // quad mode (4 particles per workgroup, 4x4x1_16b MFMA, all weights in registers) when the population is too
+    // small to give every CU a 16-particle tile
+    const bool q4_dims = mlp.dims[0] <= 28 && mlp.dims[1] == 200 && mlp.dims[2] == 200 && mlp.dims[3] <= 64;
+    const bool q4_ok = fam_ok && q4_dims;
+    // k_rollout_mlp_q4s: two hidden layers of 200 or of 256 units, dim_S <= 20, dim_U <= 8, any activations
+    const bool wide = spec == 1 && mlp.tiles[1] == 16 && !per_particle_state && mlp.dims[0] <= 28 && mlp.dims[1] == 256 && mlp.dims[2] == 256;
+    const bool q4s_ok = ((fam_dims && q4_dims) || wide) && S <= 20 && U <= 8 && mlp.dims[3] == S && d_wq4s0.p != nullptr &&
+                        (ra.reward_kind == REW_CHEETAH || ra.reward_kind == REW_NONE);
+    // measured on MI355X (tools/q4_sweep.py, PI2, H = 30, us per control step): a "wave" of 256 quad workgroups (one
+    // per CU, 1024 particles) costs ~400 us, the 16-particle tiling ~850 us for anything up to 4096 particles:
+    // quads win up to two waves (N*A <= 2048: 810 vs 860), lose from the third on (2500: 1177 vs 868)
+    const long quads_total = (long)quads * A;
+    bool q4 = (q4_ok || q4s_ok) && quads_total <= 512;
+    if (sw.mlp_q4 >= 0) q4 = sw.mlp_q4 != 0 && (q4_ok || q4s_ok);
+    // four equal waves, the state in registers, the last layer from registers, two barriers per model step (kernels_mlp_q4s.hpp)
+    if (q4 && !sw.mlp_generic && sw.mlp_q4s && q4s_ok) {
+        const size_t qlds = (size_t)mlp_q4s_lds_floats(wide ? 64 : 50, 7, ra.H, U) * sizeof(float);
+        const int qpairs = 4 * ((ra.H * U + 3) / 4);
+        if (qlds <= 160 * 1024 && qpairs <= Q4S_MAX_ACTION_PAIRS) {
+            // the activations at compile time for tanh networks and, at 200 units, relu networks; at run time otherwise (RT: up
+            // to sigmoid, RTX: every code).  Indexed [256 units][activations][two action pairs per thread]
+            enum { F_TANH, F_RELU, F_RT, F_RTX };
+            static const int codes[4][3] = {{ACT_TANH, ACT_TANH, ACT_NONE}, {ACT_RELU, ACT_RELU, ACT_NONE}, {ACT_RT, ACT_RT, ACT_RT}, {ACT_RTX, ACT_RTX, ACT_RTX}};
+            static const Fn table[2][4][2] = {
+                {{k_rollout_mlp_q4s<50, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1>, k_rollout_mlp_q4s<50, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>},
+                 {k_rollout_mlp_q4s<50, 7, ACT_RELU, ACT_RELU, ACT_NONE, 1>, k_rollout_mlp_q4s<50, 7, ACT_RELU, ACT_RELU, ACT_NONE, 2>},
+                 {k_rollout_mlp_q4s<50, 7, ACT_RT, ACT_RT, ACT_RT, 1>, k_rollout_mlp_q4s<50, 7, ACT_RT, ACT_RT, ACT_RT, 2>},
+                 {k_rollout_mlp_q4s<50, 7, ACT_RTX, ACT_RTX, ACT_RTX, 1>, k_rollout_mlp_q4s<50, 7, ACT_RTX, ACT_RTX, ACT_RTX, 2>}},
+                {{k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1>, k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>},
+                 {nullptr, nullptr},                                                          // (no relu form at 256 units: F_RT)
+                 {k_rollout_mlp_q4s<64, 7, ACT_RT, ACT_RT, ACT_RT, 1>, k_rollout_mlp_q4s<64, 7, ACT_RT, ACT_RT, ACT_RT, 2>},
+                 {k_rollout_mlp_q4s<64, 7, ACT_RTX, ACT_RTX, ACT_RTX, 1>, k_rollout_mlp_q4s<64, 7, ACT_RTX, ACT_RTX, ACT_RTX, 2>}}};
+            const int form = ext ? F_RTX : tanh_net ? F_TANH : (!wide && mlp_is_hidden_act_net(mlp, BBMPC_ACT_RELU)) ? F_RELU : F_RT;
+            const int ne = qpairs <= 256 ? 1 : 2;
+            MlpLaunch k = pick(table[wide ? 1 : 0][form][ne - 1], dim3(quads, A), dim3(256), qlds, "k_rollout_mlp_q4s", 160 * 1024);
+            // the instantiation as rocprofv3 prints it (bbmpc_profile_instantiation): HG, K0G, three activations, NE
+            snprintf(k.inst, sizeof(k.inst), "k_rollout_mlp_q4s<%d, 7, %d, %d, %d, %d>", wide ? 64 : 50, codes[form][0], codes[form][1],
+                     codes[form][2], ne);
+            k.takes_state_copy = true;
+            return k;
+        }
+    }
+    if (q4 && q4_ok && !sw.mlp_generic) {
+        const size_t qlds = (size_t)mlp_q4_lds_floats(50, 7, 4, ra.H, U, S) * sizeof(float);
+        if (qlds <= 160 * 1024)
+            return pick(k_rollout_mlp_q4<50, 7, 4, ACT_TANH, ACT_TANH, ACT_NONE>, dim3(quads, A), dim3(256), qlds, "k_rollout_mlp_q4", 160 * 1024);
+    }
+
+    // pipelined kernel for the 26-200-200-20 family: two tiles per workgroup (software-pipelined) when tiles outnumber the
+    // CUs, one tile per workgroup otherwise (more workgroups beat better per-workgroup efficiency then)
+    if (fam_ok && !sw.mlp_generic) {
+        const long tiles_total = (long)tiles16 * A;
+        bool pair = tiles_total > 256;
+        if (sw.mlp_pair >= 0) pair = sw.mlp_pair != 0;
+        const int nt = pair ? 2 : 1;
+        const size_t plds = (size_t)mlp_pair_lds_floats(13, ra.H, U, S, nt) * sizeof(float);
+        if (plds <= 159 * 1024) {
+            const bool cheetah_io = S == 20 && U == 6;
+            Fn fn = k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 1>;
+            if (nt == 2 && cheetah_io && ra.H == 50 && ra.reward_kind == REW_CHEETAH && !record && mlp.half_tail[1] && mlp.half_tail[2])
+                // BASELINE config 5: dimensions and the reward at compile time (no register spills, kernels_mlp.hpp)
+                fn = k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6, 50, REW_CHEETAH, 1>;
+            else if (nt == 2 && cheetah_io && ra.H == 50) fn = k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6, 50>;
+            else if (nt == 2 && cheetah_io) fn = k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6>;
+            else if (nt == 2) fn = k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2>;
+            MlpLaunch k = pick(fn, dim3((ra.n_pop + nt * MLP_TP - 1) / (nt * MLP_TP), A), dim3(mlp_pair_waves(13, nt) * 64), plds, "k_rollout_mlp_pair");
+            k.raise_lds_always = true;             // (as this branch always did)
+            return k;
+        }
+    }
+
+    // the generic kernel, [*_ext][spec]; the name is the caller's
+    static const Fn generic[2][4] = {{k_rollout_mlp<0>, k_rollout_mlp<1>, k_rollout_mlp<2>, k_step_mlp},
+                                     {k_rollout_mlp_ext<0>, k_rollout_mlp_ext<1>, k_rollout_mlp_ext<2>, k_step_mlp_ext}};
+    return pick(generic[ext ? 1 : 0][spec], dim3(tiles16, rows_y), dim3(mlp_nw * 64), lds, nullptr);
+}
+
+void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_particle_state, float* final_state, float* traj_out) {
     REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    const MlpLaunch k = choose_rollout_mlp(ra, per_particle_state, final_state != nullptr, traj_out != nullptr);
     MlpRolloutArgs q;
     memset(&q, 0, sizeof(q));
     q.r = ra;
@@ -296,218 +490,19 @@ void Engine::launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_pa
     q.per_particle_state = per_particle_state ? 1 : 0;
     q.final_state = final_state;
     q.nw = mlp_nw;
-    q.traj = mlp_traj_out;
-    const bool record = mlp_traj_out != nullptr;       // trajectory recording lives in rollout_mlp_body's epilogue only
+    q.traj = traj_out;
     for (int l = 0; l < mlp.n_layers; ++l) { q.wraw[l] = d_wraw[l].p; q.braw[l] = d_braw[l].p; q.wq4[l] = d_wq4[l].p; q.wp4[l] = d_wpack4[l].p; q.wbf[l] = reinterpret_cast<const uint4*>(d_wbf[l].p); }
     q.wq4s0 = d_wq4s0.p;
     q.w4pack = d_w4pack.p;
-    const MlpLds lay = mlp_lds_layout(mlp, ra.H, U, S, mlp_nw);
-    const size_t lds = (size_t)lay.total * sizeof(float);
-    REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED,
-            "learned-model rollout: a 16-particle tile's action block (planning_horizon x 16 x dim_u floats) plus the activation / "
-            "partial-sum buffers of this network do not fit one CU's LDS (shorten the horizon or narrow the network)");
-    // weights-stationary specialisations (kernels_mlp.hpp)
-    int spec = 0;
-    const bool small_io = mlp.tiles[0] <= 2 && mlp.tiles[mlp.n_layers] <= 2;
-    if (small_io && mlp.n_layers == 3 && mlp.tiles[1] == mlp.tiles[2] && mlp.tiles[1] <= 16 && mlp_nw == mlp.tiles[1]) spec = 1;
-    if (small_io && mlp.n_layers == 4 && mlp.tiles[1] == mlp.tiles[2] && mlp.tiles[2] == mlp.tiles[3] && mlp.tiles[1] <= 4 &&
-        mlp_nw == mlp.tiles[1]) spec = 2;
-    if (sw.mlp_generic) spec = 0;
-    const bool single_step = per_particle_state && ra.H == 1;
-    if (single_step) spec = 3;
-    // an activation after sigmoid (activations.hpp): the *_ext instantiations, which dispatch over every code; networks of
-    // none / tanh / relu / sigmoid keep the kernels they always ran
-    bool ext = false;
-    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
-    if (sw.mlp_bf16 && spec == 1 && !per_particle_state && !final_state && !record) {
-        // opt-in reduced-precision mode (kernels_mlp.hpp): never selected automatically
-        dim3 bgrid((ra.n_pop + MLP_TP - 1) / MLP_TP, A), bblock(mlp_nw * 64);
-        dominant_kernel = sw.mlp_bf16 == 3 ? "k_rollout_mlp_bf16<3>" : "k_rollout_mlp_bf16<1>";
-        const void* bfn = sw.mlp_bf16 == 3 ? (const void*)k_rollout_mlp_bf16<3> : (const void*)k_rollout_mlp_bf16<1>;
-        if (lds > 64 * 1024) ensure_max_lds(bfn, 159 * 1024);
-        prof_begin();
-        if (sw.mlp_bf16 == 3) hipLaunchKernelGGL(k_rollout_mlp_bf16<3>, bgrid, bblock, lds, stream, q);
-        else hipLaunchKernelGGL(k_rollout_mlp_bf16<1>, bgrid, bblock, lds, stream, q);
-        HIP_CHECK(hipGetLastError());
-        prof_end();
-        return;
+    if (k.takes_state_copy) {
+        q.state_copy = mlp_state_copy;
+        mlp_state_copy = nullptr;
     }
-    // small networks, one wave per four particles and nothing through LDS between layers (kernels_mlp_w4.hpp): 2..4 Dense
-    // layers of at most 32 units, dim_S <= 20, dim_U <= 8 -- the reference tutorials' 4-32-32-32-3 and 26-32-32-32-20
-    if (!sw.mlp_generic && sw.mlp_w4 != 0 && !single_step && d_w4pack.p != nullptr) {
-        const bool small = true;                                   // (bbmpc_set_mlp packed the operands: the shape qualifies)
-        bool tanh_net = mlp.act[mlp.n_layers - 1] == BBMPC_ACT_NONE;
-        for (int l = 0; l + 1 < mlp.n_layers; ++l) tanh_net = tanh_net && mlp.act[l] == BBMPC_ACT_TANH;
-        const size_t wlds = (size_t)mlp_w4_lds_layout(ra.H, U, S).total * sizeof(float);
-        if (small && wlds <= 159 * 1024) {
-            using KFn = void (*)(MlpRolloutArgs);
-            static const KFn table[2][3] = {{k_rollout_mlp_w4<2, false>, k_rollout_mlp_w4<3, false>, k_rollout_mlp_w4<4, false>},
-                                            {k_rollout_mlp_w4<2, true>, k_rollout_mlp_w4<3, true>, k_rollout_mlp_w4<4, true>}};
-            static const KFn table_ext[3] = {k_rollout_mlp_w4_ext<2>, k_rollout_mlp_w4_ext<3>, k_rollout_mlp_w4_ext<4>};
-            const KFn wfn = ext ? table_ext[mlp.n_layers - 2] : table[tanh_net ? 1 : 0][mlp.n_layers - 2];
-            if (wlds > 64 * 1024) ensure_max_lds((const void*)wfn, 159 * 1024);
-            dim3 wgrid((ra.n_pop + W4_TP - 1) / W4_TP, per_particle_state ? 1 : A), wblock(256);
-            dominant_kernel = "k_rollout_mlp_w4";
-            if (ext) snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_w4_ext<%d>", mlp.n_layers);
-            else snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_w4<%d, %s>", mlp.n_layers, tanh_net ? "true" : "false");
-            prof_begin();
-            hipLaunchKernelGGL(wfn, wgrid, wblock, wlds, stream, q);
-            HIP_CHECK(hipGetLastError());
-            prof_end();
-            return;
-        }
-    }
-    // small networks: one wave per 16-particle tile, the whole Dense stack in its registers (kernels_mlp_wave.hpp)
-    if (!sw.mlp_generic && sw.mlp_wave != 0 && !single_step && small_io && mlp.n_layers >= 2 && mlp.n_layers <= 4 && mlp.tiles[1] <= 4) {
-        bool same = true;
-        for (int l = 2; l < mlp.n_layers; ++l) same = same && mlp.tiles[l] == mlp.tiles[1];
-        if (same) {
-            using KFn = void (*)(MlpRolloutArgs);
-            static const KFn table[2][3][4] = {
-                {{k_rollout_mlp_wave<1, 1, false>, k_rollout_mlp_wave<1, 2, false>, k_rollout_mlp_wave<1, 3, false>, k_rollout_mlp_wave<1, 4, false>},
-                 {k_rollout_mlp_wave<2, 1, false>, k_rollout_mlp_wave<2, 2, false>, k_rollout_mlp_wave<2, 3, false>, k_rollout_mlp_wave<2, 4, false>},
-                 {k_rollout_mlp_wave<3, 1, false>, k_rollout_mlp_wave<3, 2, false>, k_rollout_mlp_wave<3, 3, false>, k_rollout_mlp_wave<3, 4, false>}},
-                {{k_rollout_mlp_wave<1, 1, true>, k_rollout_mlp_wave<1, 2, true>, k_rollout_mlp_wave<1, 3, true>, k_rollout_mlp_wave<1, 4, true>},
-                 {k_rollout_mlp_wave<2, 1, true>, k_rollout_mlp_wave<2, 2, true>, k_rollout_mlp_wave<2, 3, true>, k_rollout_mlp_wave<2, 4, true>},
-                 {k_rollout_mlp_wave<3, 1, true>, k_rollout_mlp_wave<3, 2, true>, k_rollout_mlp_wave<3, 3, true>, k_rollout_mlp_wave<3, 4, true>}}};
-            bool tanh_net = mlp.act[mlp.n_layers - 1] == BBMPC_ACT_NONE;
-            for (int l = 0; l + 1 < mlp.n_layers; ++l) tanh_net = tanh_net && mlp.act[l] == BBMPC_ACT_TANH;
-            static const KFn table_ext[3][4] = {
-                {k_rollout_mlp_wave<1, 1, false, true>, k_rollout_mlp_wave<1, 2, false, true>, k_rollout_mlp_wave<1, 3, false, true>, k_rollout_mlp_wave<1, 4, false, true>},
-                {k_rollout_mlp_wave<2, 1, false, true>, k_rollout_mlp_wave<2, 2, false, true>, k_rollout_mlp_wave<2, 3, false, true>, k_rollout_mlp_wave<2, 4, false, true>},
-                {k_rollout_mlp_wave<3, 1, false, true>, k_rollout_mlp_wave<3, 2, false, true>, k_rollout_mlp_wave<3, 3, false, true>, k_rollout_mlp_wave<3, 4, false, true>}};
-            const KFn wfn = ext ? table_ext[mlp.n_layers - 2][mlp.tiles[1] - 1] : table[tanh_net ? 1 : 0][mlp.n_layers - 2][mlp.tiles[1] - 1];
-            const int wht = mlp.tiles[1];
-            const size_t wlds = (size_t)mlp_wave_lds_layout(ra.H, U, S, mlp.n_layers - 1, wht).total * sizeof(float);
-            if (wlds <= 159 * 1024) {
-                if (wlds > 64 * 1024) ensure_max_lds((const void*)wfn, 159 * 1024);
-                dim3 wgrid((ra.n_pop + MLP_TP - 1) / MLP_TP, per_particle_state ? 1 : A), wblock(64 * mlp_wave_waves(wht));
-                dominant_kernel = "k_rollout_mlp_wave";
-                prof_begin();
-                hipLaunchKernelGGL(wfn, wgrid, wblock, wlds, stream, q);
-                HIP_CHECK(hipGetLastError());
-                prof_end();
-                return;
-            }
-        }
-    }
-    const void* fn = ext ? (spec == 3 ? (const void*)k_step_mlp_ext : spec == 1 ? (const void*)k_rollout_mlp_ext<1> : (spec == 2 ? (const void*)k_rollout_mlp_ext<2> : (const void*)k_rollout_mlp_ext<0>))
-                         : (spec == 3 ? (const void*)k_step_mlp : spec == 1 ? (const void*)k_rollout_mlp<1> : (spec == 2 ? (const void*)k_rollout_mlp<2> : (const void*)k_rollout_mlp<0>));
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-    // pair mode (two tiles per workgroup, software-pipelined) when there are more tiles than CUs can hold one each
-    const long tiles_total = (long)((ra.n_pop + MLP_TP - 1) / MLP_TP) * A;
-    // the 26-200-200-20 tanh/tanh/linear family has its own kernels (all of them can record the trajectory)
-    const bool fam_dims = spec == 1 && mlp.tiles[1] == 13 && !per_particle_state;     // (spec == 1: two hidden layers of equal tile count, <= 32 inputs and outputs)
-    const bool fam_ok = fam_dims && mlp.act[0] == BBMPC_ACT_TANH && mlp.act[1] == BBMPC_ACT_TANH && mlp.act[2] == BBMPC_ACT_NONE;
-    const bool pair_ok = fam_ok;
-    int pair = (pair_ok && tiles_total > 256) ? 1 : 0;
-    if (sw.mlp_pair >= 0) pair = (sw.mlp_pair != 0 && pair_ok) ? 1 : 0;
-    // quad mode (4 particles per workgroup, 4x4x1_16b MFMA, all weights in registers) when the population is too
-    // small to give every CU a 16-particle tile
-    {
-        const bool q4_dims = mlp.dims[0] <= 28 && mlp.dims[1] == 200 && mlp.dims[2] == 200 && mlp.dims[3] <= 64;
-        const bool q4_ok = fam_ok && q4_dims;
-        // k_rollout_mlp_q4s: two hidden layers of 200 or of 256 units, dim_S <= 20, dim_U <= 8, any activations
-        const bool wide = spec == 1 && mlp.tiles[1] == 16 && !per_particle_state && mlp.dims[0] <= 28 && mlp.dims[1] == 256 && mlp.dims[2] == 256;
-        const bool q4s_ok = ((fam_dims && q4_dims) || wide) && S <= 20 && U <= 8 && mlp.dims[3] == S && d_wq4s0.p != nullptr &&
-                            (ra.reward_kind == REW_CHEETAH || ra.reward_kind == REW_NONE);
-        // measured on MI355X (tools/q4_sweep.py, PI2, H = 30, us per control step): a "wave" of 256 quad workgroups (one
-        // per CU, 1024 particles) costs ~400 us, the 16-particle tiling ~850 us for anything up to 4096 particles:
-        // quads win up to two waves (N*A <= 2048: 810 vs 860), lose from the third on (2500: 1177 vs 868)
-        const long quads_total = (long)((ra.n_pop + 3) / 4) * A;
-        int q4 = ((q4_ok || q4s_ok) && quads_total <= 512) ? 1 : 0;
-        if (sw.mlp_q4 >= 0) q4 = (sw.mlp_q4 != 0 && (q4_ok || q4s_ok)) ? 1 : 0;
-        // four equal waves, the state in registers, the last layer from registers, two barriers per model step (kernels_mlp_q4s.hpp)
-        if (q4 && !sw.mlp_generic && sw.mlp_q4s && q4s_ok) {
-            const size_t qlds = (size_t)mlp_q4s_lds_floats(wide ? 64 : 50, 7, ra.H, U) * sizeof(float);
-            const int qpairs = 4 * ((ra.H * U + 3) / 4);
-            if (qlds <= 160 * 1024 && qpairs <= Q4S_MAX_ACTION_PAIRS) {
-                using KFn = void (*)(MlpRolloutArgs);
-                const bool ne1 = qpairs <= 256;
-                const bool tanh_net = mlp.act[0] == BBMPC_ACT_TANH && mlp.act[1] == BBMPC_ACT_TANH && mlp.act[2] == BBMPC_ACT_NONE;
-                const bool relu_net = mlp.act[0] == BBMPC_ACT_RELU && mlp.act[1] == BBMPC_ACT_RELU && mlp.act[2] == BBMPC_ACT_NONE;
-                const KFn fn = ext      ? (wide ? (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_RTX, ACT_RTX, ACT_RTX, 1> : k_rollout_mlp_q4s<64, 7, ACT_RTX, ACT_RTX, ACT_RTX, 2>)
-                                                : (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_RTX, ACT_RTX, ACT_RTX, 1> : k_rollout_mlp_q4s<50, 7, ACT_RTX, ACT_RTX, ACT_RTX, 2>))
-                             : wide     ? (tanh_net ? (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1> : k_rollout_mlp_q4s<64, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>)
-                                                    : (ne1 ? k_rollout_mlp_q4s<64, 7, ACT_RT, ACT_RT, ACT_RT, 1> : k_rollout_mlp_q4s<64, 7, ACT_RT, ACT_RT, ACT_RT, 2>))
-                             : tanh_net ? (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_TANH, ACT_TANH, ACT_NONE, 1> : k_rollout_mlp_q4s<50, 7, ACT_TANH, ACT_TANH, ACT_NONE, 2>)
-                             : relu_net ? (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_RELU, ACT_RELU, ACT_NONE, 1> : k_rollout_mlp_q4s<50, 7, ACT_RELU, ACT_RELU, ACT_NONE, 2>)
-                                        : (ne1 ? k_rollout_mlp_q4s<50, 7, ACT_RT, ACT_RT, ACT_RT, 1> : k_rollout_mlp_q4s<50, 7, ACT_RT, ACT_RT, ACT_RT, 2>);
-                if (qlds > 64 * 1024) ensure_max_lds((const void*)fn, 160 * 1024);
-                dim3 qgrid((ra.n_pop + 3) / 4, A), qblock(256);
-                dominant_kernel = "k_rollout_mlp_q4s";
-                {   // the instantiation as rocprofv3 prints it (bbmpc_profile_instantiation): HG, K0G, three activations, NE
-                    const int rt = ext ? ACT_RTX : ACT_RT;
-                    const int a0 = (tanh_net || (!wide && relu_net)) ? mlp.act[0] : rt, a1 = (tanh_net || (!wide && relu_net)) ? mlp.act[1] : rt,
-                              a2 = (tanh_net || (!wide && relu_net)) ? mlp.act[2] : rt;
-                    snprintf(dominant_inst, sizeof(dominant_inst), "k_rollout_mlp_q4s<%d, 7, %d, %d, %d, %d>", wide ? 64 : 50, a0, a1, a2, ne1 ? 1 : 2);
-                }
-                q.state_copy = mlp_state_copy;
-                mlp_state_copy = nullptr;
-                prof_begin();
-                hipLaunchKernelGGL(fn, qgrid, qblock, qlds, stream, q);
-                HIP_CHECK(hipGetLastError());
-                prof_end();
-                return;
-            }
-        }
-        if (q4 && q4_ok && !sw.mlp_generic) {
-            const size_t qlds = (size_t)mlp_q4_lds_floats(50, 7, 4, ra.H, U, S) * sizeof(float);
-            if (qlds <= 160 * 1024) {
-                auto fn = k_rollout_mlp_q4<50, 7, 4, ACT_TANH, ACT_TANH, ACT_NONE>;
-                if (qlds > 64 * 1024) ensure_max_lds((const void*)fn, 160 * 1024);
-                dim3 qgrid((ra.n_pop + 3) / 4, A), qblock(256);
-                dominant_kernel = "k_rollout_mlp_q4";
-                prof_begin();
-                hipLaunchKernelGGL(fn, qgrid, qblock, qlds, stream, q);
-                HIP_CHECK(hipGetLastError());
-                prof_end();
-                return;
-            }
-        }
-    }
-    if (pair_ok && !sw.mlp_generic) {
-        // pipelined kernel for the 26-200-200-20 family: two tiles per workgroup when tiles outnumber the CUs,
-        // one tile per workgroup otherwise (more workgroups beat better per-workgroup efficiency then)
-        const int nt = pair ? 2 : 1;
-        const size_t plds = (size_t)mlp_pair_lds_floats(13, ra.H, U, S, nt) * sizeof(float);
-        if (plds <= 159 * 1024) {
-            dim3 pgrid((ra.n_pop + nt * MLP_TP - 1) / (nt * MLP_TP), A), pblock(mlp_pair_waves(13, nt) * 64);
-            dominant_kernel = "k_rollout_mlp_pair";
-            prof_begin();
-            if (nt == 2 && S == 20 && U == 6 && ra.H == 50 && ra.reward_kind == REW_CHEETAH && !q.traj && mlp.half_tail[1] && mlp.half_tail[2]) {
-                // BASELINE config 5: dimensions and the reward at compile time (no register spills, kernels_mlp.hpp)
-                ensure_max_lds((const void*)(k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6, 50, REW_CHEETAH, 1>), 159 * 1024);
-                hipLaunchKernelGGL((k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6, 50, REW_CHEETAH, 1>), pgrid, pblock, plds, stream, q);
-            } else if (nt == 2 && S == 20 && U == 6 && ra.H == 50) {
-                ensure_max_lds((const void*)(k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6, 50>), 159 * 1024);
-                hipLaunchKernelGGL((k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6, 50>), pgrid, pblock, plds, stream, q);
-            } else if (nt == 2 && S == 20 && U == 6) {
-                ensure_max_lds((const void*)(k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6>), 159 * 1024);
-                hipLaunchKernelGGL((k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2, 20, 6>), pgrid, pblock, plds, stream, q);
-            } else if (nt == 2) {
-                ensure_max_lds((const void*)(k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2>), 159 * 1024);
-                hipLaunchKernelGGL((k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 2>), pgrid, pblock, plds, stream, q);
-            } else {
-                ensure_max_lds((const void*)(k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 1>), 159 * 1024);
-                hipLaunchKernelGGL((k_rollout_mlp_pair<13, ACT_TANH, ACT_TANH, ACT_NONE, 1>), pgrid, pblock, plds, stream, q);
-            }
-            HIP_CHECK(hipGetLastError());
-            prof_end();
-            return;
-        }
-    }
-    dim3 grid((ra.n_pop + MLP_TP - 1) / MLP_TP, per_particle_state ? 1 : A), block(mlp_nw * 64);
+    if (k.raise_lds_always || k.lds > 64 * 1024) ensure_max_lds((const void*)k.fn, k.lds_cap);
+    if (k.name) dominant_kernel = k.name;
+    if (k.inst[0]) memcpy(dominant_inst, k.inst, sizeof(dominant_inst));
     prof_begin();
-    if (ext) {
-        if (spec == 3) hipLaunchKernelGGL(k_step_mlp_ext, grid, block, lds, stream, q);
-        else if (spec == 1) hipLaunchKernelGGL(k_rollout_mlp_ext<1>, grid, block, lds, stream, q);
-        else if (spec == 2) hipLaunchKernelGGL(k_rollout_mlp_ext<2>, grid, block, lds, stream, q);
-        else hipLaunchKernelGGL(k_rollout_mlp_ext<0>, grid, block, lds, stream, q);
-    } else if (spec == 3) hipLaunchKernelGGL(k_step_mlp, grid, block, lds, stream, q);
-    else if (spec == 1) hipLaunchKernelGGL(k_rollout_mlp<1>, grid, block, lds, stream, q);
-    else if (spec == 2) hipLaunchKernelGGL(k_rollout_mlp<2>, grid, block, lds, stream, q);
-    else hipLaunchKernelGGL(k_rollout_mlp<0>, grid, block, lds, stream, q);
+    hipLaunchKernelGGL(k.fn, k.grid, k.block, k.lds, stream, q);
     HIP_CHECK(hipGetLastError());
     prof_end();
 }
@@ -530,14 +525,40 @@ void Engine::traj_mlp(const float* d_states, const float* d_seq, int batch, int 
     q.rewards_out = d_rewards_out;
     const size_t lds = (size_t)mlp_traj_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
     REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "trajectory prediction: the activation / partial-sum buffers of this network do not fit one CU's LDS");
-    bool ext = false;
-    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
-    const void* fn = ext ? (const void*)k_traj_mlp<true> : (const void*)k_traj_mlp<false>;
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-    dim3 grid((batch + MLP_TP - 1) / MLP_TP), block(mlp_nw * 64);
-    if (ext) hipLaunchKernelGGL(k_traj_mlp<true>, grid, block, lds, stream, q);
-    else hipLaunchKernelGGL(k_traj_mlp<false>, grid, block, lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    launch_args(mlp_has_ext_act(mlp) ? k_traj_mlp<true> : k_traj_mlp<false>, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(mlp_nw * 64), lds, stream, q);
+}
+
+// What the six argument structs of the particle frames (kernels_mlp_particles.hpp, kernels_mlp_traj_particles.hpp) share:
+// the model's operands or the ensemble's with their member strides, the log-variance heads, and for kind MLP_PART_GAUSS the
+// LDS of the doubled last layer in `lds`
+template <class ARGS, class PA>
+static void mlp_particle_operands(const Engine& e, const PA& pa, ARGS& q, size_t& lds) {
+    const MlpDesc& m = e.mlp;
+    const bool ens = e.ens_E > 0;
+    memset(&q, 0, sizeof(q));
+    q.m = m;
+    q.nw = e.mlp_nw;
+    q.p = pa;
+    for (int l = 0; l < m.n_layers; ++l) {
+        q.wp4[l] = ens ? e.d_ens_wp4[l].p : e.d_wpack4[l].p;
+        q.m.bpack[l] = ens ? e.d_ens_bp[l].p : e.d_bpack[l].p;
+        if constexpr (ARGS::KIND != MLP_PART_PLAIN) {
+            q.wstride[l] = ens ? m.tiles[l + 1] * m.tiles[l] * 256 : 0;
+            q.bstride[l] = ens ? m.tiles[l + 1] * 256 : 0;
+        }
+    }
+    if constexpr (ARGS::KIND != MLP_PART_PLAIN) q.E = std::max(1, e.ens_E);
+    if constexpr (ARGS::KIND == MLP_PART_GAUSS) {
+        const int Ll = m.n_layers - 1;
+        q.hp4 = e.d_lv_wp4.p;
+        q.hbp = e.d_lv_bp.p;
+        q.hwstride = m.tiles[Ll + 1] * m.tiles[Ll] * 256;
+        q.hbstride = m.tiles[Ll + 1] * 256;
+        q.min_logvar = e.d_lv_bounds.p;
+        q.max_logvar = e.d_lv_bounds.p + e.S;
+        lds = (size_t)mlp_gauss_lds_layout(m, e.U, e.S, e.mlp_nw).total * sizeof(float);
+        REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
+    }
 }
 
 // Particle rollouts of a learned model (bbmpc_set_particles; built-in reward, or with pa.traj the TRAJ form for a HIP-source one): one launch of the frame of
@@ -561,47 +582,19 @@ void Engine::launch_rollout_mlp_particles(const ParticleArgs& pa) {
     if (kind == MLP_PART_ENS) REQUIRE(pa.P % E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");
     const long rows = (long)pa.n_pop * (pa.P / E);            // per (agent, member)
     dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), A, E), block(mlp_nw * 64);
-    bool ext = false;
-    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
-    // the arguments of kind ARGS::KIND and its launch (the kernel takes exactly this one struct by value)
+    const bool ext = mlp_has_ext_act(mlp);
+    // the arguments of kind ARGS::KIND and its launch; pa.traj set (a HIP-source reward): the TRAJ form, which stores every noisy
+    // next state and leaves the returns to the scorer (its row slots lie behind the layout)
     auto launch = [&](auto q) {
         using ARGS = decltype(q);
-        memset(&q, 0, sizeof(q));
-        q.m = mlp;
-        q.nw = mlp_nw;
-        q.p = pa;
-        for (int l = 0; l < mlp.n_layers; ++l) {
-            q.wp4[l] = ens_E > 0 ? d_ens_wp4[l].p : d_wpack4[l].p;
-            q.m.bpack[l] = ens_E > 0 ? d_ens_bp[l].p : d_bpack[l].p;
-            if constexpr (ARGS::KIND != MLP_PART_PLAIN) {
-                q.wstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * mlp.tiles[l] * 256 : 0;
-                q.bstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * 256 : 0;
-            }
-        }
-        if constexpr (ARGS::KIND != MLP_PART_PLAIN) q.E = E;
-        if constexpr (ARGS::KIND == MLP_PART_GAUSS) {
-            const int Ll = mlp.n_layers - 1;
-            q.hp4 = d_lv_wp4.p;
-            q.hbp = d_lv_bp.p;
-            q.hwstride = mlp.tiles[Ll + 1] * mlp.tiles[Ll] * 256;
-            q.hbstride = mlp.tiles[Ll + 1] * 256;
-            q.min_logvar = d_lv_bounds.p;
-            q.max_logvar = d_lv_bounds.p + S;
-            lds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
-            REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
-        }
-        // pa.traj set (a HIP-source reward): the TRAJ form, which stores every noisy next state and leaves the returns to the scorer
-        auto launch_form = [&](auto traj) {
-            constexpr bool TRAJ = decltype(traj)::value;
-            const void* fn = ext ? (const void*)k_rollout_mlp_particles_kind<ARGS, true, TRAJ> : (const void*)k_rollout_mlp_particles_kind<ARGS, false, TRAJ>;
-            const size_t lds_all = lds + (TRAJ ? MLP_PART_ROWSLOT * sizeof(int) : 0);       // (TRAJ: the row slots lie behind the layout)
-            if (lds_all > 64 * 1024) ensure_max_lds(fn, 159 * 1024 + (TRAJ ? MLP_PART_ROWSLOT * (int)sizeof(int) : 0));
-            if (ext) hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, true, TRAJ>), grid, block, lds_all, stream, q);
-            else hipLaunchKernelGGL((k_rollout_mlp_particles_kind<ARGS, false, TRAJ>), grid, block, lds_all, stream, q);
-        };
-        if (pa.traj) launch_form(std::true_type());
-        else launch_form(std::false_type());
-        HIP_CHECK(hipGetLastError());
+        mlp_particle_operands(*this, pa, q, lds);
+        const size_t slots = MLP_PART_ROWSLOT * sizeof(int);
+        if (pa.traj)
+            launch_args(ext ? k_rollout_mlp_particles_kind<ARGS, true, true> : k_rollout_mlp_particles_kind<ARGS, false, true>, grid, block,
+                        lds + slots, stream, q, 159 * 1024 + (int)slots);
+        else
+            launch_args(ext ? k_rollout_mlp_particles_kind<ARGS, true, false> : k_rollout_mlp_particles_kind<ARGS, false, false>, grid, block,
+                        lds, stream, q);
     };
     if (kind == MLP_PART_GAUSS) launch(MlpGaussParticleArgs());
     else if (kind == MLP_PART_ENS) launch(MlpEnsParticleArgs());
@@ -621,40 +614,13 @@ void Engine::launch_traj_mlp_particles(const TrajParticleArgs& pa) {
     if (kind == MLP_PART_ENS) REQUIRE(pa.P % E == 0, BBMPC_E_INVALID, "internal: particles per ensemble member");
     const long rows = (long)pa.B * (pa.P / E);                // per member
     dim3 grid((unsigned)((rows + MLP_TP - 1) / MLP_TP), 1, E), block(mlp_nw * 64);
-    bool ext = false;
-    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
+    const bool ext = mlp_has_ext_act(mlp);
     auto launch = [&](auto q) {
         using ARGS = decltype(q);
-        memset(&q, 0, sizeof(q));
-        q.m = mlp;
-        q.nw = mlp_nw;
-        q.p = pa;
-        for (int l = 0; l < mlp.n_layers; ++l) {
-            q.wp4[l] = ens_E > 0 ? d_ens_wp4[l].p : d_wpack4[l].p;
-            q.m.bpack[l] = ens_E > 0 ? d_ens_bp[l].p : d_bpack[l].p;
-            if constexpr (ARGS::KIND != MLP_PART_PLAIN) {
-                q.wstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * mlp.tiles[l] * 256 : 0;
-                q.bstride[l] = ens_E > 0 ? mlp.tiles[l + 1] * 256 : 0;
-            }
-        }
-        if constexpr (ARGS::KIND != MLP_PART_PLAIN) q.E = E;
-        if constexpr (ARGS::KIND == MLP_PART_GAUSS) {
-            const int Ll = mlp.n_layers - 1;
-            q.hp4 = d_lv_wp4.p;
-            q.hbp = d_lv_bp.p;
-            q.hwstride = mlp.tiles[Ll + 1] * mlp.tiles[Ll] * 256;
-            q.hbstride = mlp.tiles[Ll + 1] * 256;
-            q.min_logvar = d_lv_bounds.p;
-            q.max_logvar = d_lv_bounds.p + S;
-            lds = (size_t)mlp_gauss_lds_layout(mlp, U, S, mlp_nw).total * sizeof(float);
-            REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED, "particle rollout: the log-variance head's partial sums do not fit one CU's LDS");
-        }
-        const size_t lds_all = lds + MLP_TRAJ_PART_ROWMAP * sizeof(int);       // (the row map of the tile lies behind the layout)
-        const void* fn = ext ? (const void*)k_traj_mlp_particles_kind<ARGS, true> : (const void*)k_traj_mlp_particles_kind<ARGS, false>;
-        if (lds_all > 64 * 1024) ensure_max_lds(fn, 159 * 1024 + MLP_TRAJ_PART_ROWMAP * (int)sizeof(int));
-        if (ext) hipLaunchKernelGGL((k_traj_mlp_particles_kind<ARGS, true>), grid, block, lds_all, stream, q);
-        else hipLaunchKernelGGL((k_traj_mlp_particles_kind<ARGS, false>), grid, block, lds_all, stream, q);
-        HIP_CHECK(hipGetLastError());
+        mlp_particle_operands(*this, pa, q, lds);
+        const size_t rowmap = MLP_TRAJ_PART_ROWMAP * sizeof(int);                 // (the row map of the tile lies behind the layout)
+        launch_args(ext ? k_traj_mlp_particles_kind<ARGS, true> : k_traj_mlp_particles_kind<ARGS, false>, grid, block, lds + rowmap, stream, q,
+                    159 * 1024 + (int)rowmap);
     };
     if (kind == MLP_PART_GAUSS) launch(MlpGaussTrajParticleArgs());
     else if (kind == MLP_PART_ENS) launch(MlpEnsTrajParticleArgs());
@@ -671,20 +637,53 @@ struct DenseStackHost {
     std::vector<float> w4[MLP_MAX_LAYERS], bp[MLP_MAX_LAYERS];
 };
 
+// The argument checks of the Dense-stack setters (reward model, terminal value, policy prior), in the order each of them has
+// always made them: pointers and layer count, own_first(), widths, own_shape() -- what the setter asks of dims[0] and
+// dims[n_layers] --, then every layer's activation and pointers and the n_stats statistics vectors.
+template <class OwnFirst, class OwnShape>
+static void check_dense_stack(const std::string& prefix, const char* too_few_layers, int n_layers, const int32_t* dims, const int32_t* acts,
+                              const float* const* w, const float* const* b, int is_normalized, const float* const* stats, int n_stats,
+                              OwnFirst own_first, OwnShape own_shape) {
+    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
+    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, prefix + too_few_layers);
+    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, prefix + "1..8 Dense layers are supported");
+    own_first();
+    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
+    own_shape();
+    for (int l = 0; l < n_layers; ++l) {
+        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
+        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
+    }
+    if (is_normalized) {
+        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
+        for (int i = 0; i < n_stats; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
+    }
+}
+
+// Widths and tiles of a Dense stack, features in index order (what mlp_pack_layer reads) -> the waves of a workgroup
+static int dense_stack_shape(MlpDesc& shape, int n_layers, const int32_t* dims) {
+    memset(&shape, 0, sizeof(shape));
+    shape.n_layers = n_layers;
+    int hidden_tiles = 1;
+    for (int l = 0; l <= n_layers; ++l) {
+        shape.dims[l] = dims[l];
+        shape.tiles[l] = (dims[l] + 15) / 16;
+        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, shape.tiles[l]);
+    }
+    return std::min(16, hidden_tiles);
+}
+
 static void dense_stack_pack(DenseStackHost& hs, int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w,
                              const float* const* b, int input_mask, int S, int U) {
     RewMlpDesc& d = hs.d;
     memset(&d, 0, sizeof(d));
-    MlpDesc shape;                              // what mlp_pack_layer reads: widths and tiles, features in index order
-    memset(&shape, 0, sizeof(shape));
-    d.n_layers = shape.n_layers = n_layers;
-    int hidden_tiles = 1;
+    MlpDesc shape;
+    d.nw = dense_stack_shape(shape, n_layers, dims);
+    d.n_layers = n_layers;
     for (int l = 0; l <= n_layers; ++l) {
-        d.dims[l] = shape.dims[l] = dims[l];
-        d.tiles[l] = shape.tiles[l] = (dims[l] + 15) / 16;
-        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, d.tiles[l]);
+        d.dims[l] = shape.dims[l];
+        d.tiles[l] = shape.tiles[l];
     }
-    d.nw = std::min(16, hidden_tiles);
     d.mask = input_mask; d.S = S; d.U = U; d.D = dims[0];
     d.off_a = (input_mask & 1) ? S : 0;
     d.off_n = d.off_a + ((input_mask & 2) ? U : 0);
@@ -722,31 +721,19 @@ static void dense_stack_upload(DenseStackHost& hs, const float* const* w, const 
     }
 }
 
-static void launch_reward_mlp_lds(const void* fn, size_t lds) {
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-}
-
 // Everything is checked and packed on the host before the handle is touched, so a refusal leaves it as it was.
 void Engine::set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
                             int input_mask, int is_normalized, const float* const* stats) {
     REQUIRE(cfg.reward == BBMPC_REW_MLP, BBMPC_E_STATE, "handle was not created with BBMPC_REW_MLP");
-    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
-    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "reward model: at least one Dense layer");
-    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "reward model: 1..8 Dense layers are supported");
-    REQUIRE(input_mask >= 1 && input_mask <= 7, BBMPC_E_INVALID, "reward model: input_mask must select at least one of s_t (1), a_t (2), s_t+1 (4)");
     const int D = ((input_mask & 1) ? S : 0) + ((input_mask & 2) ? U : 0) + ((input_mask & 4) ? S : 0);
-    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
-    REQUIRE(dims[0] == D, BBMPC_E_INVALID,
-            "reward model: dims[0] = " + std::to_string(dims[0]) + " but input_mask selects " + std::to_string(D) + " input columns");
-    REQUIRE(dims[n_layers] == 1, BBMPC_E_INVALID, "reward model: the last layer must have one output (dims[n_layers] == 1)");
-    for (int l = 0; l < n_layers; ++l) {
-        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
-        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
-    }
-    if (is_normalized) {
-        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
-        for (int i = 0; i < 4; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
-    }
+    check_dense_stack(
+        "reward model: ", "at least one Dense layer", n_layers, dims, acts, w, b, is_normalized, stats, 4,
+        [&] { REQUIRE(input_mask >= 1 && input_mask <= 7, BBMPC_E_INVALID, "reward model: input_mask must select at least one of s_t (1), a_t (2), s_t+1 (4)"); },
+        [&] {
+            REQUIRE(dims[0] == D, BBMPC_E_INVALID,
+                    "reward model: dims[0] = " + std::to_string(dims[0]) + " but input_mask selects " + std::to_string(D) + " input columns");
+            REQUIRE(dims[n_layers] == 1, BBMPC_E_INVALID, "reward model: the last layer must have one output (dims[n_layers] == 1)");
+        });
     REQUIRE(D <= REW_MLP_MAX_IN, BBMPC_E_UNSUPPORTED, "reward model: more than 192 input columns");
     for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= REW_MLP_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
     DenseStackHost hs;
@@ -776,21 +763,11 @@ void Engine::set_terminal_value_mlp(int n_layers, const int32_t* dims, const int
         val_mlp_ready = false;
         return;
     }
-    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
-    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "terminal value: n_layers must be >= 0");
-    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "terminal value: 1..8 Dense layers are supported");
-    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
-    REQUIRE(dims[0] == S, BBMPC_E_INVALID,
-            "terminal value: dims[0] = " + std::to_string(dims[0]) + " but the network reads the state, dim_s = " + std::to_string(S));
-    REQUIRE(dims[n_layers] == 1, BBMPC_E_INVALID, "terminal value: the last layer must have one output (dims[n_layers] == 1)");
-    for (int l = 0; l < n_layers; ++l) {
-        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
-        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
-    }
-    if (is_normalized) {
-        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
-        for (int i = 0; i < 4; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
-    }
+    check_dense_stack("terminal value: ", "n_layers must be >= 0", n_layers, dims, acts, w, b, is_normalized, stats, 4, [] {}, [&] {
+        REQUIRE(dims[0] == S, BBMPC_E_INVALID,
+                "terminal value: dims[0] = " + std::to_string(dims[0]) + " but the network reads the state, dim_s = " + std::to_string(S));
+        REQUIRE(dims[n_layers] == 1, BBMPC_E_INVALID, "terminal value: the last layer must have one output (dims[n_layers] == 1)");
+    });
     REQUIRE(std::isfinite(terminal_weight), BBMPC_E_INVALID, "terminal value: terminal_weight must be finite");
     for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= REW_MLP_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
     REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
@@ -827,14 +804,7 @@ void Engine::rollout_terminal_value(int mode, bool pen, RolloutArgs& ra) {
     } else {
         const size_t need = (size_t)ra.H * A * ra.Nst * S;
         if (u_traj.n < need) u_traj.alloc(need);
-        mlp_traj_out = u_traj.p;
-        try {
-            launch_rollout_mlp(mode, pen, ra, false, nullptr);
-        } catch (...) {
-            mlp_traj_out = nullptr;
-            throw;
-        }
-        mlp_traj_out = nullptr;
+        launch_rollout_mlp(mode, pen, ra, false, nullptr, u_traj.p);
     }
     ValMlpTermArgs q;
     memset(&q, 0, sizeof(q));
@@ -844,9 +814,7 @@ void Engine::rollout_terminal_value(int mode, bool pen, RolloutArgs& ra) {
     q.last = u_traj.p + (size_t)(ra.H - 1) * A * ra.Nst * S;
     q.rewards = ra.rewards;
     const size_t lds = (size_t)rew_mlp_lds_layout(val_mlp).total * sizeof(float);
-    launch_reward_mlp_lds((const void*)k_value_mlp_terminal, lds);
-    hipLaunchKernelGGL(k_value_mlp_terminal, dim3((ra.n_pop + MLP_TP - 1) / MLP_TP, A), dim3(val_mlp.nw * 64), lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    launch_args(k_value_mlp_terminal, dim3((ra.n_pop + MLP_TP - 1) / MLP_TP, A), dim3(val_mlp.nw * 64), lds, stream, q);
 }
 
 // V on B rows of states [B][S]: the rows frame with the value network's descriptor, no weight and no NaN rule
@@ -861,9 +829,7 @@ void Engine::terminal_value_rows(const float* d_states, int batch, float* d_out)
     q.act = d_states; q.nxt = d_states;                   // never read: the mask selects s_t alone
     q.out = d_out;
     const size_t lds = (size_t)rew_mlp_lds_layout(val_mlp).total * sizeof(float);
-    launch_reward_mlp_lds((const void*)k_reward_mlp_rows, lds);
-    hipLaunchKernelGGL(k_reward_mlp_rows, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(val_mlp.nw * 64), lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    launch_args(k_reward_mlp_rows, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(val_mlp.nw * 64), lds, stream, q);
 }
 
 // The learned model's rollout with a learned reward: Engine::rollout_mlp_user_reward's sequence with the network in place
@@ -875,19 +841,11 @@ void Engine::rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra) {
     const size_t need = (size_t)ra.H * A * ra.Nst * S, need_r = (size_t)ra.H * A * ra.Nst;
     if (u_traj.n < need) u_traj.alloc(need);
     if (d_rw_step.n < need_r) d_rw_step.alloc(need_r);
-    mlp_traj_out = u_traj.p;
-    // BBMPC_PROF_REWARD_MLP: the profiling events go around the scorer below, not around the rollout kernel
-    const bool prof = profiling;
-    if (sw.prof_reward_mlp) profiling = false;
-    try {
-        launch_rollout_mlp(mode, pen, ra, false, nullptr);
-    } catch (...) {
-        mlp_traj_out = nullptr;
-        profiling = prof;
-        throw;
+    {   // BBMPC_PROF_REWARD_MLP: the profiling events go around the scorer below, not around the rollout kernel
+        struct Restore { bool& flag; bool was; ~Restore() { flag = was; } } restore{profiling, profiling};
+        if (sw.prof_reward_mlp) profiling = false;
+        launch_rollout_mlp(mode, pen, ra, false, nullptr, u_traj.p);
     }
-    mlp_traj_out = nullptr;
-    profiling = prof;
     RewMlpTrajArgs q;
     memset(&q, 0, sizeof(q));
     q.m = rew_mlp;
@@ -905,7 +863,7 @@ void Engine::rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra) {
     const int chunks = std::max(1, std::min(ra.H, (512 + tiles - 1) / tiles));
     q.tchunk = (ra.H + chunks - 1) / chunks;
     const size_t lds = (size_t)rew_mlp_lds_layout(rew_mlp).total * sizeof(float);
-    launch_reward_mlp_lds((const void*)k_reward_mlp_traj, lds);
+    if (lds > 64 * 1024) ensure_max_lds((const void*)k_reward_mlp_traj, 159 * 1024);       // (in front of the profiling event)
     dim3 grid(tiles, A, (ra.H + q.tchunk - 1) / q.tchunk), block(rew_mlp.nw * 64);
     if (sw.prof_reward_mlp) {
         dominant_kernel = "k_reward_mlp_traj";
@@ -923,9 +881,7 @@ void Engine::reward_mlp_rows(const RewMlpRowsArgs& rows) {
     RewMlpRowsArgs q = rows;
     q.m = rew_mlp;
     const size_t lds = (size_t)rew_mlp_lds_layout(rew_mlp).total * sizeof(float);
-    launch_reward_mlp_lds((const void*)k_reward_mlp_rows, lds);
-    hipLaunchKernelGGL(k_reward_mlp_rows, dim3((q.B + MLP_TP - 1) / MLP_TP), dim3(rew_mlp.nw * 64), lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    launch_args(k_reward_mlp_rows, dim3((q.B + MLP_TP - 1) / MLP_TP), dim3(rew_mlp.nw * 64), lds, stream, q);
 }
 
 // bbmpc_predict_trajectories with a learned reward: the states from k_traj_mlp (they do not depend on the reward), then ONE
@@ -969,22 +925,12 @@ void Engine::set_policy_prior_mlp(int n_layers, const int32_t* dims, const int32
         inj.erase(BBMPC_NOISE_POLICY);
         return;
     }
-    REQUIRE(dims && acts && w && b, BBMPC_E_INVALID, "null argument");
-    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "policy prior: n_layers must be >= 0");
-    REQUIRE(n_layers <= MLP_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "policy prior: 1..8 Dense layers are supported");
-    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "layer width must be >= 1");
-    REQUIRE(dims[0] == S, BBMPC_E_INVALID,
-            "policy prior: dims[0] = " + std::to_string(dims[0]) + " but the network reads the state, dim_s = " + std::to_string(S));
-    REQUIRE(dims[n_layers] == U, BBMPC_E_INVALID,
-            "policy prior: dims[n_layers] = " + std::to_string(dims[n_layers]) + " but the network returns an action, dim_u = " + std::to_string(U));
-    for (int l = 0; l < n_layers; ++l) {
-        REQUIRE(acts[l] >= BBMPC_ACT_NONE && acts[l] <= BBMPC_ACT_RELU6, BBMPC_E_INVALID, "unknown activation");
-        REQUIRE(w[l] && b[l], BBMPC_E_INVALID, "null weight/bias pointer");
-    }
-    if (is_normalized) {
-        REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
-        for (int i = 0; i < 4; ++i) REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
-    }
+    check_dense_stack("policy prior: ", "n_layers must be >= 0", n_layers, dims, acts, w, b, is_normalized, stats, 4, [] {}, [&] {
+        REQUIRE(dims[0] == S, BBMPC_E_INVALID,
+                "policy prior: dims[0] = " + std::to_string(dims[0]) + " but the network reads the state, dim_s = " + std::to_string(S));
+        REQUIRE(dims[n_layers] == U, BBMPC_E_INVALID,
+                "policy prior: dims[n_layers] = " + std::to_string(dims[n_layers]) + " but the network returns an action, dim_u = " + std::to_string(U));
+    });
     REQUIRE(std::isfinite(noise_std) && noise_std >= 0.0f, BBMPC_E_INVALID, "policy prior: noise_std must be finite and >= 0");
     REQUIRE(count >= 1, BBMPC_E_INVALID, "policy prior: count must be >= 1");
     for (int l = 1; l < n_layers; ++l) REQUIRE(dims[l] <= POLICY_MAX_HIDDEN, BBMPC_E_UNSUPPORTED, "hidden width > 512 not supported");
@@ -1004,15 +950,7 @@ void Engine::set_policy_prior_mlp(int n_layers, const int32_t* dims, const int32
                 " must be below population_size = " + std::to_string(N));
     REQUIRE((long)A * count * HU < (1L << 31), BBMPC_E_UNSUPPORTED, "policy prior: more than 2^31 noise elements per iteration");
     MlpDesc d;
-    memset(&d, 0, sizeof(d));
-    d.n_layers = n_layers;
-    int hidden_tiles = 1;
-    for (int l = 0; l <= n_layers; ++l) {
-        d.dims[l] = dims[l];
-        d.tiles[l] = (dims[l] + 15) / 16;
-        if (l >= 1 && l < n_layers) hidden_tiles = std::max(hidden_tiles, d.tiles[l]);
-    }
-    const int pnw = std::min(16, hidden_tiles);
+    const int pnw = dense_stack_shape(d, n_layers, dims);
     if (mlp_ready)
         REQUIRE((size_t)policy_prior_lds_layout(mlp, d, U, S, std::max(pnw, mlp_nw)).total * sizeof(float) <= 159 * 1024, BBMPC_E_UNSUPPORTED,
                 "policy prior: the activation / partial-sum buffers of the two networks do not fit one CU's LDS");
@@ -1116,15 +1054,8 @@ void Engine::policy_prior_rollouts(const float* d_state, const float* d_noise, f
     const size_t lds = (size_t)policy_prior_lds_layout(mlp, prior_mlp, U, S, q.nw).total * sizeof(float);
     REQUIRE(lds <= 159 * 1024, BBMPC_E_UNSUPPORTED,
             "policy prior: the activation / partial-sum buffers of the two networks do not fit one CU's LDS");
-    bool ext = false;
-    for (int l = 0; l < mlp.n_layers; ++l) ext = ext || mlp.act[l] > BBMPC_ACT_SIGMOID;
-    for (int l = 0; l < prior_mlp.n_layers; ++l) ext = ext || prior_mlp.act[l] > BBMPC_ACT_SIGMOID;
-    const void* fn = ext ? (const void*)k_policy_prior_rollout<true> : (const void*)k_policy_prior_rollout<false>;
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-    dim3 grid((K + MLP_TP - 1) / MLP_TP, A), block(q.nw * 64);
-    if (ext) hipLaunchKernelGGL(k_policy_prior_rollout<true>, grid, block, lds, stream, q);
-    else hipLaunchKernelGGL(k_policy_prior_rollout<false>, grid, block, lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    const bool ext = mlp_has_ext_act(mlp) || mlp_has_ext_act(prior_mlp);
+    launch_args(ext ? k_policy_prior_rollout<true> : k_policy_prior_rollout<false>, dim3((K + MLP_TP - 1) / MLP_TP, A), dim3(q.nw * 64), lds, stream, q);
 }
 
 // pi on B rows of states [B][S] -> actions [B][U]: no noise, no clip
@@ -1140,14 +1071,8 @@ void Engine::policy_prior_rows(const float* d_states, int batch, float* d_action
     q.states = d_states;
     q.actions = d_actions;
     const size_t lds = (size_t)policy_rows_lds_layout(prior_mlp, U, S, prior_nw).total * sizeof(float);
-    bool ext = false;
-    for (int l = 0; l < prior_mlp.n_layers; ++l) ext = ext || prior_mlp.act[l] > BBMPC_ACT_SIGMOID;
-    const void* fn = ext ? (const void*)k_policy_prior_rows<true> : (const void*)k_policy_prior_rows<false>;
-    if (lds > 64 * 1024) ensure_max_lds(fn, 159 * 1024);
-    dim3 grid((batch + MLP_TP - 1) / MLP_TP), block(prior_nw * 64);
-    if (ext) hipLaunchKernelGGL(k_policy_prior_rows<true>, grid, block, lds, stream, q);
-    else hipLaunchKernelGGL(k_policy_prior_rows<false>, grid, block, lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    launch_args(mlp_has_ext_act(prior_mlp) ? k_policy_prior_rows<true> : k_policy_prior_rows<false>, dim3((batch + MLP_TP - 1) / MLP_TP),
+                dim3(prior_nw * 64), lds, stream, q);
 }
 
 
@@ -1295,9 +1220,7 @@ void Engine::plan_gradient_launch(PlanGradArgs q, size_t lds, const float* d_sta
     q.returns_out = d_returns;
     q.grad_out = d_grad;
     q.ws = d_pg_ws.p;
-    if (lds > 64 * 1024) ensure_max_lds((const void*)k_plan_grad, 159 * 1024);
-    hipLaunchKernelGGL(k_plan_grad, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(q.nw * 64), lds, stream, q);
-    HIP_CHECK(hipGetLastError());
+    launch_args(k_plan_grad, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(q.nw * 64), lds, stream, q);
 }
 
 // ------------------------------------------------------------------------------------------------

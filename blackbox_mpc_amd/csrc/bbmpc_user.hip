@@ -391,14 +391,7 @@ void Engine::rollout_mlp_user_reward(int mode, bool pen, RolloutArgs& ra) {
     REQUIRE(user_reward.fn_traj, BBMPC_E_STATE, "user reward: call bbmpc_set_reward_source before computing");
     const size_t need = (size_t)ra.H * A * ra.Nst * S;
     if (u_traj.n < need) u_traj.alloc(need);
-    mlp_traj_out = u_traj.p;
-    try {
-        launch_rollout_mlp(mode, pen, ra, false, nullptr);          // reward kind REW_NONE: leaves -(penalty) in ra.rewards
-    } catch (...) {
-        mlp_traj_out = nullptr;
-        throw;
-    }
-    mlp_traj_out = nullptr;
+    launch_rollout_mlp(mode, pen, ra, false, nullptr, u_traj.p);          // reward kind REW_NONE: leaves -(penalty) in ra.rewards
     int n_pop = ra.n_pop, Aa = A, Hh = ra.H, Nst_ = ra.Nst, from_ref = mode == SRC_REF ? 1 : 0;
     const float* state = ra.state;
     const float* traj = u_traj.p;

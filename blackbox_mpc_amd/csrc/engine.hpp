@@ -41,6 +41,7 @@ namespace bbmpc {
 
 struct ParticleArgs;       // kernels_particles.hpp
 struct TrajParticleArgs;   // kernels_traj_particles.hpp
+struct MlpLaunch;          // bbmpc_mlp.hip
 
 struct HipError : std::runtime_error {
     int code;
@@ -312,9 +313,9 @@ struct Engine {
     void rollout_user_fused(int mode, bool pen, RolloutArgs& ra);
     void rollout_mlp_user_reward(int mode, bool pen, RolloutArgs& ra);
     DevBuf<float> u_traj;              // [H][A][Nst][S] states after every step of the MFMA rollout
-    float* mlp_traj_out = nullptr;     // set around a launch_rollout_mlp call that should record the trajectory
     // set around a launch_rollout_mlp call whose state argument is the pinned host buffer: a kernel that can store the
-    // state for the later launches itself (k_rollout_mlp_q4s) takes the request and clears it
+    // state for the later launches itself (k_rollout_mlp_q4s) takes the request and clears it.  A member and not an
+    // argument because the request crosses launch_rollout's routing between first_rollout_mlp and launch_rollout_mlp
     float* mlp_state_copy = nullptr;
     bool pi2_dist_ready = false;       // d_sigma holds the constructor variance's root (PI2 never changes it)
     bool pi2_copy_seen = false;        // the previous control step's first rollout took such a request
@@ -635,7 +636,9 @@ struct Engine {
 
     // helpers
     void launch_rollout(int mode, bool pen, RolloutArgs& ra);
-    void launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_particle_state, float* final_state);
+    // traj_out: [H][A][Nst][S], the state after every step (u_traj), or nullptr
+    void launch_rollout_mlp(int mode, bool pen, RolloutArgs& ra, bool per_particle_state, float* final_state, float* traj_out);
+    MlpLaunch choose_rollout_mlp(const RolloutArgs& ra, bool per_particle_state, bool final_state, bool record) const;   // bbmpc_mlp.hip
     void set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
                  int is_normalized, const float* const* stats);
     void prof_begin();
