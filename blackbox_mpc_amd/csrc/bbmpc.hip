@@ -366,18 +366,17 @@ bool Engine::resident_step(const float* state, int add_noise, uint32_t seq, floa
         HIP_CHECK(hipEventRecord(pf_done[nb], pf_stream));
         pf_chunk[nb] = c + 1; pf_waited[nb] = false; pf_inflight[nb] = true;
     }
-    if (in_flight_hook && !in_flight_called) { in_flight_called = true; in_flight_hook(this); }
+    note_in_flight();
     const auto t0 = std::chrono::steady_clock::now();
     bool all = true;
     for (int a = 0; a < A; ++a) {
         volatile const uint32_t* ack = ack_host(a);              // the agent's completion line (completion_line.hpp)
         volatile const uint32_t* gone = gone_host(a);
-        uint32_t spins = 0;
-        for (;;) {
-            if (completion_line_decode(ack, seq, records + (size_t)a * kCompletionRecordFloats)) break;
-            if (*gone != 0u) { all = false; break; }               // it left (before or after this request?)
-            if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { all = false; break; }
-        }
+        bool served = false;
+        // also over when the agent's workgroup left (before or after this request?); after 2 s nobody is asked again
+        spin_until(t0, [&] { return (served = completion_line_decode(ack, seq, records + (size_t)a * kCompletionRecordFloats)) || *gone != 0u; },
+                   [] { return false; });
+        if (!served) all = false;
     }
     if (all) return true;
     // some workgroups have left: end the others too (they finish the step they are in), then see who is missing
@@ -784,8 +783,8 @@ void Engine::finalize(const float* d_state_in, int add_noise, float* d_record_ou
         return;
     }
     if (cfg.dynamics == BBMPC_DYN_PENDULUM && !user_path()) {
-        if (tail_flag) tail_attached = true;         // the record is complete when this kernel ends: it publishes the sequence number
-        hipLaunchKernelGGL(k_finalize_pendulum, dim3((A + 63) / 64), dim3(64), 0, stream, fa, tail_flag, tail_count, tail_value);
+        const TailHandoff::Words w = tail.publish_words();   // the record is complete when this kernel ends: it publishes the sequence number
+        hipLaunchKernelGGL(k_finalize_pendulum, dim3((A + 63) / 64), dim3(64), 0, stream, fa, w.flag, w.count, w.value);
         HIP_CHECK(hipGetLastError());
         return;
     }
@@ -822,11 +821,8 @@ void Engine::finalize(const float* d_state_in, int add_noise, float* d_record_ou
     ta.mean = d_mean.p;
     ta.prev_mean = d_prev_mean.p;
     pending_warm = 0;
-    if (tail_flag) {             // the record is complete when this kernel ends: it publishes the sequence number itself
-        ta.done_flag = tail_flag; ta.done_count = tail_count; ta.done_value = tail_value;
-        ta.step_words = step_capturing ? step_words_dev : nullptr;
-        tail_attached = true;
-    }
+    tail.publish_into(ta);       // the record is complete when this kernel ends: it publishes the sequence number itself
+    if (tail.flag) ta.step_words = step_capturing ? step_words_dev : nullptr;
     launch_with_tail(*this, k_tail_mlp, dim3(A), dim3(TAIL_THREADS), 0, ta);
     HIP_CHECK(hipGetLastError());
 }
@@ -1781,6 +1777,223 @@ int bbmpc_optimize_dev(bbmpc_handle h, const float* d_state, int32_t, int32_t no
 
 }  // extern "C"
 
+// ---- one host-in / host-out control step (bbmpc_optimize, bbmpc_optimize_gather): optimize_host and its parts ----
+namespace bbmpc {
+
+void Engine::ensure_completion_block() {
+    if (host_done) return;
+    HIP_CHECK(hipHostMalloc((void**)&host_done, (size_t)sync_lines() * 64, hipHostMallocCoherent | hipHostMallocMapped));   // engine.hpp: completion words | request lines | exit words
+    memset(host_done, 0, (size_t)sync_lines() * 64);
+    HIP_CHECK(hipHostGetDevicePointer((void**)&host_done_dev, host_done, 0));
+    HIP_CHECK(hipMalloc((void**)&host_count, 8));
+    HIP_CHECK(hipMemset(host_count, 0, 8));
+}
+
+void Engine::ensure_step_words() {
+    if (step_words) return;
+    HIP_CHECK(hipHostMalloc((void**)&step_words, 64, 0));        // staging for the (rare) re-synchronisation of the device words
+    memset(step_words, 0, 64);
+    HIP_CHECK(hipMalloc((void**)&step_words_dev, 64));
+    HIP_CHECK(hipMemset(step_words_dev, 0, 64));
+    step_mirror[0] = step_mirror[1] = 0xFFFFFFFFu;
+}
+
+// How a host-in / host-out control step travels: decided once per call from the handle's configuration, before anything
+// is touched.
+struct HostStepPlan {
+    enum Transfer { kZeroCopyFused, kZeroCopyStaged, kCopies } transfer = kCopies;
+    bool host_poll = false;     // the step's last kernel publishes a completion word (or line) that the host polls
+    bool linger_ok = false;     // the resident form of the persistent pendulum kernel may serve / be launched
+    bool stage = false;         // kZeroCopyStaged: the step's first kernel fetches the state from the pinned buffer itself
+    bool graph_ok = false;      // kZeroCopyStaged: the step may be warmed up, captured and replayed as a graph
+    uint64_t sig = 0;           // ... and what a graph of this call would have been captured for
+};
+
+static HostStepPlan choose_host_step(const Engine& e, int32_t noise) {
+    HostStepPlan p;
+    // single-kernel control steps read the state straight from the pinned, device-mapped host buffer; those and the
+    // learned-dynamics path (whose last kernel, k_tail_mlp, owns the record) write the packed record straight into it
+    const bool fused_step = e.sw.zero_copy && (e.use_fused() || e.use_fused_pso());   // PSO: the swarm re-seed that follows touches neither
+    // every other optimizer path: the state goes to HBM once (many workgroups read it), the record comes back on its own --
+    // whichever kernel packs it writes straight into the pinned buffer; k_tail_mlp, k_finalize_pendulum and the fused
+    // CMA-ES kernel also publish the completion word, the rest is waited for on the stream
+    const bool mlp_tail = e.sw.zero_copy && !fused_step && e.cfg.optimizer != BBMPC_OPT_NONE;
+    if (!fused_step && !mlp_tail) return p;
+    p.transfer = fused_step ? HostStepPlan::kZeroCopyFused : HostStepPlan::kZeroCopyStaged;
+    // the last workgroup publishes a sequence number into a pinned host word right after the record stores
+    // (publish_records_done): the call returns when the host sees it, ~10 us earlier than hipStreamSynchronize notices
+    // the kernel's completion; the stream itself is joined lazily (settle)
+    p.host_poll = e.sw.host_poll && !e.trace_on;
+    // one agent on the persistent pendulum kernel: the previous call's kernel may still be there, waiting for this one
+    p.linger_ok = fused_step && p.host_poll && e.sw.linger_us > 0 && e.A <= Engine::kLingerMaxAgents && e.use_fused() &&
+                  !e.profiling && e.tail.event == nullptr &&
+                  e.stream == e.own_stream;      // on a caller's stream it would hold back the caller's next work
+    if (mlp_tail) {
+        // hundreds of rollout workgroups read the state: it goes to HBM once, the record comes back on its own.
+        // CEM / PI2 begin with k_dist_init, which fetches it from the pinned buffer itself; the others get a copy
+        p.stage = (e.cfg.optimizer == BBMPC_OPT_CEM || e.cfg.optimizer == BBMPC_OPT_PI2) && !e.pop_sharded() &&
+                  !e.user_path() && !e.value_on();
+        // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
+        // replayed as a graph (engine.hpp: step_graph)
+        p.graph_ok = e.sw.step_graph && p.stage && e.cfg.dynamics == BBMPC_DYN_MLP && p.host_poll &&
+                     e.tail.event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && !e.prior_on() && !e.grad_on() && e.stream == e.own_stream && !e.any_injected();
+        p.sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
+    }
+    return p;
+}
+
+// Capture this call's launches as the handle's step graph; nothing runs until the graph is launched.  Returns whether
+// there is a graph to replay now.
+static bool capture_step_graph(Engine& e, const HostStepPlan& plan, int32_t noise, float* dpin, size_t ns) {
+    if (e.step_graph) { (void)hipGraphExecDestroy(e.step_graph); e.step_graph = nullptr; }      // (captured for other arguments)
+    e.ensure_step_words();
+    const uint32_t saved_step = e.step_counter;
+    hipGraph_t g = nullptr;
+    bool ok = hipStreamBeginCapture(e.stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+        ScopedRequest<const float*> staged(e.stage_state_src, dpin);
+        e.step_capturing = true;
+        try {
+            e.optimize_dev(e.d_state.p, noise, dpin + ns, nullptr);
+        } catch (...) { ok = false; }
+        e.step_capturing = false;
+        ok = (hipStreamEndCapture(e.stream, &g) == hipSuccess) && ok && g != nullptr && e.last_step_steady && e.stage_state_src == nullptr;
+        if (ok) ok = hipGraphInstantiate(&e.step_graph, g, nullptr, nullptr, 0) == hipSuccess;
+        if (g) (void)hipGraphDestroy(g);
+    }
+    e.step_counter = saved_step;                 // the captured call has not run
+    (void)hipGetLastError();
+    if (ok) {
+        e.step_graph_sig = plan.sig;
+        return true;
+    }
+    // this handle keeps enqueueing its launches one by one; why is kept (bbmpc_graph_stats' callers see 0 replays,
+    // BBMPC_TRACE_GRAPH=1 prints it): a capture-illegal call added to the steady path must not go unnoticed
+    e.step_graph = nullptr; e.sw.step_graph = 0;
+    ++e.graph_capture_failures;
+    if (getenv("BBMPC_TRACE_GRAPH")) fprintf(stderr, "[bbmpc] control-step graph capture / instantiate failed (steady=%d): replay disabled for this handle\n", (int)e.last_step_steady);
+    return false;
+}
+
+static void replay_step_graph(Engine& e) {
+    // the device's (control step, completion value) advance by themselves at the end of every replay; calls that
+    // did not go through the graph in between put them out of step with the host's: one 8-byte copy then
+    if (e.step_mirror[0] != e.step_counter || e.step_mirror[1] != e.host_seq) {
+        HIP_CHECK(hipStreamSynchronize(e.stream));           // (the staging words may still be in use by an earlier copy)
+        e.step_words[0] = e.step_counter; e.step_words[1] = e.host_seq;
+        HIP_CHECK(hipMemcpyAsync(e.step_words_dev, e.step_words, 8, hipMemcpyHostToDevice, e.stream));
+    }
+    HIP_CHECK(hipGraphLaunch(e.step_graph, e.stream));
+    ++e.calls_graph;
+    ++e.step_counter;
+    e.step_mirror[0] = e.step_counter;
+    e.step_mirror[1] = e.host_seq + 1u == 0u ? 1u : e.host_seq + 1u;
+    e.tail.attached = true;                      // the captured k_tail_mlp publishes the completion word
+}
+
+// after a step that was enqueued launch by launch: the run of consecutive eligible steady-state calls a capture waits for
+static void count_warm_step(Engine& e, const HostStepPlan& plan) {
+    if (plan.graph_ok && e.last_step_steady && e.step_warm_sig == plan.sig) ++e.step_graph_warm;
+    else { e.step_graph_warm = (plan.graph_ok && e.last_step_steady) ? 1 : 0; e.step_warm_sig = plan.sig; }
+}
+
+// kZeroCopyStaged: replay, capture and replay, or enqueue the step's launches one by one
+static void run_staged_step(Engine& e, const HostStepPlan& plan, int32_t noise, const float* pin, float* dpin, size_t ns) {
+    const bool replay = plan.graph_ok && ((e.step_graph && e.step_graph_sig == plan.sig) ||
+                                          (e.step_graph_warm >= 3 && e.step_warm_sig == plan.sig && capture_step_graph(e, plan, noise, dpin, ns)));
+    if (replay) {
+        replay_step_graph(e);
+        return;
+    }
+    {
+        ScopedRequest<const float*> staged(e.stage_state_src, plan.stage ? dpin : nullptr);
+        if (!plan.stage) HIP_CHECK(hipMemcpyAsync(e.d_state.p, pin, ns * 4, hipMemcpyHostToDevice, e.stream));
+        e.optimize_dev(e.d_state.p, noise, dpin + ns, nullptr);
+        if (e.stage_state_src) throw HipError(BBMPC_E_HIP, "internal: the control step did not stage its state");
+    }
+    count_warm_step(e, plan);
+}
+
+enum class RecordWait { kServed, kPublished, kStream };   // the record is here | announced by the step's last kernel | behind the stream
+
+// The zero-copy forms: the step's kernels read the [A,S] state and write the packed record straight from / to the
+// pinned, device-mapped host buffer (a few PCIe transactions) -- no copy-engine round trips around a ~50 us kernel.
+static RecordWait run_zero_copy_step(Engine& e, const HostStepPlan& plan, int32_t noise, float* pin, size_t ns) {
+    float* dpin = e.h_pin_dev;
+    if (plan.host_poll) {
+        e.ensure_completion_block();
+        if (++e.host_seq == 0) e.host_seq = 1;
+    }
+    bool handled = false;                // served by the resident workgroups: the records are already in the pinned buffer
+    if (e.resident_alive) {
+        if (plan.linger_ok) handled = e.resident_step(pin, noise, e.host_seq, pin + ns);
+        else e.resident_stop();
+    }
+    if (handled) {
+        ++e.calls_resident;
+        return RecordWait::kServed;
+    }
+    ++e.calls_launched;
+    ClearOnThrow<int> subset(e.subset_n);                   // a subset named by resident_step must not outlive the call it was for
+    TailRequest want(e, plan.host_poll ? e.host_done_dev : nullptr, e.host_count, e.host_seq);
+    ScopedRequest<bool> linger(e.linger_launch, plan.linger_ok && e.subset_n == 0);      // a subset launch (after a crossed exit) is an ordinary one
+    if (plan.transfer == HostStepPlan::kZeroCopyFused) e.optimize_dev(dpin, noise, dpin + ns, nullptr);
+    else run_staged_step(e, plan, noise, pin, dpin, ns);
+    subset.done();
+    return want.taken() ? RecordWait::kPublished : RecordWait::kStream;
+}
+
+static void run_copied_step(Engine& e, int32_t noise, float* pin, size_t ns, size_t nr) {
+    ++e.calls_launched;
+    HIP_CHECK(hipMemcpyAsync(e.d_state.p, pin, ns * 4, hipMemcpyHostToDevice, e.stream));
+    e.optimize_dev(e.d_state.p, noise, e.d_record.p, nullptr);
+    HIP_CHECK(hipMemcpyAsync(pin + ns, e.d_record.p, nr * 4, hipMemcpyDeviceToHost, e.stream));
+}
+
+static void wait_for_records(Engine& e, RecordWait how, float* records) {
+    if (how == RecordWait::kStream) {
+        HIP_CHECK(hipStreamSynchronize(e.stream));
+        e.lazy_sync = false;
+        return;
+    }
+    if (how == RecordWait::kPublished) {
+        const uint32_t want = e.host_seq;
+        const auto t0 = std::chrono::steady_clock::now();
+        const auto unpublished = [] { return HipError(BBMPC_E_HIP, "bbmpc_optimize: the control step finished without publishing its records"); };
+        if (e.resident_alive) {
+            // a LINGER launch: every agent's workgroup publishes its own completion line, which carries the record
+            for (int a = 0; a < e.A; ++a) {
+                volatile const uint32_t* f = e.ack_host(a);
+                float* rec_a = records + (size_t)a * kCompletionRecordFloats;
+                spin_until(t0, [&] { return completion_line_decode(f, want, rec_a); }, [&] {
+                    e.resident_stop();                               // a fault surfaces in its synchronize
+                    if (!completion_line_decode(f, want, rec_a)) throw unpublished();
+                    return true;
+                });
+            }
+        } else {
+            volatile const uint32_t* f = e.host_done;
+            spin_until(t0, [&] { return *f == want; }, [&] {
+                HIP_CHECK(hipStreamSynchronize(e.stream));       // a fault surfaces here; otherwise the word must be there
+                if (*f != want) throw unpublished();
+                return true;
+            });
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    e.lazy_sync = true;
+}
+
+static void unpack_records(const Engine& e, const float* r, float* action, float* next_state, float* reward) {
+    for (int a = 0; a < e.A; ++a) {
+        if (action) memcpy(action + (size_t)a * e.U, r + (size_t)a * e.rec, e.U * 4);
+        if (next_state) memcpy(next_state + (size_t)a * e.S, r + (size_t)a * e.rec + e.U, e.S * 4);
+        if (reward) reward[a] = r[(size_t)a * e.rec + e.U + e.S];
+    }
+}
+
+}  // namespace bbmpc
+
 // One host-in / host-out control step (the body of bbmpc_optimize, shared with bbmpc_optimize_gather): returns the packed
 // records [A][U+S+1] in the handle's pinned buffer.  The caller has NOT settled the handle: consecutive calls are ordered
 // by the stream (or served by the resident kernel), everything else settles first.
@@ -1789,191 +2002,14 @@ static const float* optimize_host(bbmpc::Engine& e, const float* state, int32_t 
     const size_t ns = (size_t)e.A * e.S, nr = (size_t)e.A * e.rec;
     float* pin = e.pinned(ns + nr);
     memcpy(pin, state, ns * 4);
-    bool published = false;
-    bool handled_resident = false;       // served by the resident workgroups: the records are already in the pinned buffer
-    // single-kernel control steps read the state straight from the pinned, device-mapped host buffer; those and the
-    // learned-dynamics path (whose last kernel, k_tail_mlp, owns the record) write the packed record straight into it
-    const bool fused_step = e.sw.zero_copy && (e.use_fused() || e.use_fused_pso());   // PSO: the swarm re-seed that follows touches neither
-    // every other optimizer path: the state goes to HBM once (many workgroups read it), the record comes back on its own --
-    // whichever kernel packs it writes straight into the pinned buffer; k_tail_mlp, k_finalize_pendulum and the fused
-    // CMA-ES kernel also publish the completion word, the rest is waited for on the stream
-    const bool mlp_tail = e.sw.zero_copy && !fused_step && e.cfg.optimizer != BBMPC_OPT_NONE;
-    if (fused_step || mlp_tail) {
-        // the persistent kernel reads the [A,S] state and writes the packed record straight from / to the pinned,
-        // device-mapped host buffer (a few PCIe transactions) -- no copy-engine round trips around a ~50 us kernel
-        float* dpin = e.h_pin_dev;
-        if (e.sw.host_poll && !e.trace_on) {
-            // ... and its last workgroup publishes a sequence number into a pinned host word right after the record
-            // stores (publish_records_done): the call returns when the host sees it, ~10 us earlier than
-            // hipStreamSynchronize notices the kernel's completion; the stream itself is joined lazily (settle)
-            if (!e.host_done) {
-                HIP_CHECK(hipHostMalloc((void**)&e.host_done, (size_t)e.sync_lines() * 64, hipHostMallocCoherent | hipHostMallocMapped));   // engine.hpp: completion words | request lines | exit words
-                memset(e.host_done, 0, (size_t)e.sync_lines() * 64);
-                HIP_CHECK(hipHostGetDevicePointer((void**)&e.host_done_dev, e.host_done, 0));
-                HIP_CHECK(hipMalloc((void**)&e.host_count, 8));
-                HIP_CHECK(hipMemset(e.host_count, 0, 8));
-            }
-            if (++e.host_seq == 0) e.host_seq = 1;
-            e.tail_flag = e.host_done_dev;
-            e.tail_count = e.host_count;
-            e.tail_value = e.host_seq;
-            e.tail_attached = false;
-        }
-        // one agent on the persistent pendulum kernel: the previous call's kernel may still be there, waiting for this one
-        const bool linger_ok = fused_step && e.tail_flag != nullptr && e.sw.linger_us > 0 && e.A <= Engine::kLingerMaxAgents && e.use_fused() &&
-                               !e.profiling && e.tail_event == nullptr &&
-                               e.stream == e.own_stream;      // on a caller's stream it would hold back the caller's next work
-        bool handled = false;
-        if (e.resident_alive) {
-            if (linger_ok) handled = e.resident_step(pin, noise, e.host_seq, pin + ns);
-            else e.resident_stop();
-        }
-        if (handled) ++e.calls_resident; else ++e.calls_launched;
-        if (handled) {
-            published = true;
-            handled_resident = true;
-            e.tail_flag = nullptr;
-        } else
-        try {
-            e.linger_launch = linger_ok && e.subset_n == 0;      // a subset launch (after a crossed exit) is an ordinary one
-            if (fused_step) {
-                e.optimize_dev(dpin, noise, dpin + ns, nullptr);
-            } else {
-                // hundreds of rollout workgroups read the state: it goes to HBM once, the record comes back on its own.
-                // CEM / PI2 begin with k_dist_init, which fetches it from the pinned buffer itself; the others get a copy
-                const bool stage = (e.cfg.optimizer == BBMPC_OPT_CEM || e.cfg.optimizer == BBMPC_OPT_PI2) && !e.pop_sharded() &&
-                                   !e.user_path() && !e.value_on();
-                // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
-                // replayed as a graph (engine.hpp: step_graph)
-                const bool graph_ok = e.sw.step_graph && stage && e.cfg.dynamics == BBMPC_DYN_MLP && e.tail_flag != nullptr &&
-                                      e.tail_event == nullptr && !e.profiling && !e.trace_on && !e.particles_on() && !e.corr_on() && !e.carry_on() && !e.prior_on() && !e.grad_on() && e.stream == e.own_stream && !e.any_injected();
-                const uint64_t sig = ((uint64_t)e.mutations << 8) | (uint64_t)(noise ? 1 : 0) | 2u;
-                bool replayed = false;
-                if (graph_ok && e.step_graph && e.step_graph_sig == sig) {
-                    replayed = true;
-                } else if (graph_ok && e.step_graph_warm >= 3 && e.step_warm_sig == sig) {
-                    if (e.step_graph) { (void)hipGraphExecDestroy(e.step_graph); e.step_graph = nullptr; }      // (captured for other arguments)
-                    // capture this call's launches; nothing runs until the graph is launched below
-                    if (!e.step_words) {
-                        HIP_CHECK(hipHostMalloc((void**)&e.step_words, 64, 0));        // staging for the (rare) re-synchronisation of the device words
-                        memset(e.step_words, 0, 64);
-                        HIP_CHECK(hipMalloc((void**)&e.step_words_dev, 64));
-                        HIP_CHECK(hipMemset(e.step_words_dev, 0, 64));
-                        e.step_mirror[0] = e.step_mirror[1] = 0xFFFFFFFFu;
-                    }
-                    const uint32_t saved_step = e.step_counter;
-                    hipGraph_t g = nullptr;
-                    bool ok = hipStreamBeginCapture(e.stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                    if (ok) {
-                        e.step_capturing = true;
-                        try {
-                            e.stage_state_src = dpin;
-                            e.optimize_dev(e.d_state.p, noise, dpin + ns, nullptr);
-                        } catch (...) { ok = false; }
-                        e.step_capturing = false;
-                        ok = (hipStreamEndCapture(e.stream, &g) == hipSuccess) && ok && g != nullptr && e.last_step_steady && e.stage_state_src == nullptr;
-                        e.stage_state_src = nullptr;
-                        if (ok) ok = hipGraphInstantiate(&e.step_graph, g, nullptr, nullptr, 0) == hipSuccess;
-                        if (g) (void)hipGraphDestroy(g);
-                    }
-                    e.step_counter = saved_step;                 // the captured call has not run
-                    (void)hipGetLastError();
-                    if (ok) { replayed = true; e.step_graph_sig = sig; }
-                    else {
-                        // this handle keeps enqueueing its launches one by one; why is kept (bbmpc_graph_stats' callers see 0 replays,
-                        // BBMPC_TRACE_GRAPH=1 prints it): a capture-illegal call added to the steady path must not go unnoticed
-                        e.step_graph = nullptr; e.sw.step_graph = 0;
-                        ++e.graph_capture_failures;
-                        if (getenv("BBMPC_TRACE_GRAPH")) fprintf(stderr, "[bbmpc] control-step graph capture / instantiate failed (steady=%d): replay disabled for this handle\n", (int)e.last_step_steady);
-                    }
-                }
-                if (replayed) {
-                    // the device's (control step, completion value) advance by themselves at the end of every replay; calls that
-                    // did not go through the graph in between put them out of step with the host's: one 8-byte copy then
-                    if (e.step_mirror[0] != e.step_counter || e.step_mirror[1] != e.host_seq) {
-                        HIP_CHECK(hipStreamSynchronize(e.stream));           // (the staging words may still be in use by an earlier copy)
-                        e.step_words[0] = e.step_counter; e.step_words[1] = e.host_seq;
-                        HIP_CHECK(hipMemcpyAsync(e.step_words_dev, e.step_words, 8, hipMemcpyHostToDevice, e.stream));
-                    }
-                    HIP_CHECK(hipGraphLaunch(e.step_graph, e.stream));
-                    ++e.calls_graph;
-                    ++e.step_counter;
-                    e.step_mirror[0] = e.step_counter;
-                    e.step_mirror[1] = e.host_seq + 1u == 0u ? 1u : e.host_seq + 1u;
-                    e.tail_attached = true;
-                } else {
-                if (stage) e.stage_state_src = dpin;
-                else HIP_CHECK(hipMemcpyAsync(e.d_state.p, pin, ns * 4, hipMemcpyHostToDevice, e.stream));
-                e.optimize_dev(e.d_state.p, noise, dpin + ns, nullptr);
-                if (e.stage_state_src) {
-                    e.stage_state_src = nullptr;
-                    throw HipError(BBMPC_E_HIP, "internal: the control step did not stage its state");
-                }
-                if (graph_ok && e.last_step_steady && e.step_warm_sig == sig) ++e.step_graph_warm;
-                else { e.step_graph_warm = (graph_ok && e.last_step_steady) ? 1 : 0; e.step_warm_sig = sig; }
-                }
-            }
-            e.linger_launch = false;
-            published = e.tail_flag != nullptr && e.tail_attached;
-            e.tail_flag = nullptr;
-        } catch (...) {
-            e.linger_launch = false;
-            e.tail_flag = nullptr;
-            e.subset_n = 0;                                  // a subset named by resident_step must not outlive the call it was for
-            throw;
-        }
-    } else {
-        ++e.calls_launched;
-        HIP_CHECK(hipMemcpyAsync(e.d_state.p, pin, ns * 4, hipMemcpyHostToDevice, e.stream));
-        e.optimize_dev(e.d_state.p, noise, e.d_record.p, nullptr);
-        HIP_CHECK(hipMemcpyAsync(pin + ns, e.d_record.p, nr * 4, hipMemcpyDeviceToHost, e.stream));
-    }
-    if (e.in_flight_hook && !e.in_flight_called) { e.in_flight_called = true; e.in_flight_hook(&e); }   // launch path: the kernels are enqueued
-    if (handled_resident) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        e.lazy_sync = true;
-    } else if (published && e.resident_alive) {
-        // a LINGER launch: every agent's workgroup publishes its own completion line, which carries the record
-        const uint32_t want = e.host_seq;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int a = 0; a < e.A; ++a) {
-            volatile const uint32_t* f = e.ack_host(a);
-            float* rec_a = pin + ns + (size_t)a * kCompletionRecordFloats;
-            uint32_t spins = 0;
-            while (!completion_line_decode(f, want, rec_a)) {
-                if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-                    e.resident_stop();                               // a fault surfaces in its synchronize
-                    if (!completion_line_decode(f, want, rec_a)) throw HipError(BBMPC_E_HIP, "bbmpc_optimize: the control step finished without publishing its records");
-                }
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        e.lazy_sync = true;
-    } else if (published) {
-        volatile const uint32_t* f = e.host_done;
-        const uint32_t want = e.host_seq;
-        const auto t0 = std::chrono::steady_clock::now();
-        uint32_t spins = 0;
-        while (*f != want) {
-            if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-                HIP_CHECK(hipStreamSynchronize(e.stream));       // a fault surfaces here; otherwise the word must be there
-                if (*f != want) throw HipError(BBMPC_E_HIP, "bbmpc_optimize: the control step finished without publishing its records");
-                break;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        e.lazy_sync = true;
-    } else {
-        HIP_CHECK(hipStreamSynchronize(e.stream));
-        e.lazy_sync = false;
-    }
-    const float* r = pin + ns;
-    for (int a = 0; a < e.A; ++a) {
-        if (action) memcpy(action + (size_t)a * e.U, r + (size_t)a * e.rec, e.U * 4);
-        if (next_state) memcpy(next_state + (size_t)a * e.S, r + (size_t)a * e.rec + e.U, e.S * 4);
-        if (reward) reward[a] = r[(size_t)a * e.rec + e.U + e.S];
-    }
-    return r;
+    const HostStepPlan plan = choose_host_step(e, noise);
+    RecordWait how = RecordWait::kStream;
+    if (plan.transfer == HostStepPlan::kCopies) run_copied_step(e, noise, pin, ns, nr);
+    else how = run_zero_copy_step(e, plan, noise, pin, ns);
+    e.note_in_flight();                  // launch path: the kernels are enqueued
+    wait_for_records(e, how, pin + ns);
+    unpack_records(e, pin + ns, action, next_state, reward);
+    return pin + ns;
 }
 
 extern "C" {
@@ -2367,22 +2403,35 @@ static void gather_records(Engine* e, const float* d_records, float* d_gathered,
     gather_enqueue(e, d_records, d_gathered, count, slot, v);
 }
 
+// The first check of every gather entry point (in front of its pointer checks).
+// The communicator of a population-sharded handle carries the per-iteration partials on the LAUNCH stream; one RCCL
+// communicator must not be driven from two unsynchronised streams, so such a handle has no record gather (its ranks
+// all hold the same agents: there is nothing to gather).  A population that is only split into shards on THIS GPU
+// (population_size > 32768, or the loopback hook) never drives the communicator and gathers like any other handle
+static void refuse_gather_when_sharded_over_ranks(const Engine* e) {
+    if (e->pop_sharded_across_ranks()) throw HipError(BBMPC_E_UNSUPPORTED, "record gather on a handle whose population is sharded over ranks (every rank already holds every agent's record)");
+}
+
+// ... and the last ones (behind them): the handle's communicator, with `slot` free for entry point `who` to use.
+// count: bbmpc_gather_records_dev's own argument, checked where that entry point always checked it.
+static RecordComm& gather_comm(Engine* e, const char* who, int32_t slot, const int64_t* count = nullptr) {
+    RecordComm& c = e->rc;
+    const auto refusal = [who](int code, const char* why) { return HipError(code, std::string(who) + why); };
+    if (!c.comm) throw refusal(BBMPC_E_STATE, ": call bbmpc_comm_init first");
+    if (slot < 0 || slot >= RecordComm::kSlots) throw refusal(BBMPC_E_INVALID, ": slot must be 0 or 1");
+    if (count && *count <= 0) throw refusal(BBMPC_E_INVALID, ": count must be positive");
+    if (c.pending[slot]) throw refusal(BBMPC_E_STATE, ": slot still pending (call bbmpc_gather_wait)");
+    return c;
+}
+
 int bbmpc_gather_records_dev(bbmpc_handle h, const float* d_records, float* d_gathered, int64_t count, int32_t slot) {
     API_BEGIN
     CHECK_HANDLE(h);
-    // the communicator of a population-sharded handle carries the per-iteration partials on the LAUNCH stream; one RCCL
-    // communicator must not be driven from two unsynchronised streams, so such a handle has no record gather (its ranks
-    // all hold the same agents: there is nothing to gather).  A population that is only split into shards on THIS GPU
-    // (population_size > 32768, or the loopback hook) never drives the communicator and gathers like any other handle
-    if (h->e->pop_sharded_across_ranks()) throw HipError(BBMPC_E_UNSUPPORTED, "record gather on a handle whose population is sharded over ranks (every rank already holds every agent's record)");
+    Engine* e = h->e;
+    refuse_gather_when_sharded_over_ranks(e);
     CHECK_PTR(d_records);
     CHECK_PTR(d_gathered);
-    Engine* e = h->e;
-    RecordComm& c = e->rc;
-    if (!c.comm) throw HipError(BBMPC_E_STATE, "bbmpc_gather_records_dev: call bbmpc_comm_init first");
-    if (slot < 0 || slot >= RecordComm::kSlots) throw HipError(BBMPC_E_INVALID, "bbmpc_gather_records_dev: slot must be 0 or 1");
-    if (count <= 0) throw HipError(BBMPC_E_INVALID, "bbmpc_gather_records_dev: count must be positive");
-    if (c.pending[slot]) throw HipError(BBMPC_E_STATE, "bbmpc_gather_records_dev: slot still pending (call bbmpc_gather_wait)");
+    RecordComm& c = gather_comm(e, "bbmpc_gather_records_dev", slot, &count);
     gather_records(e, d_records, d_gathered, (size_t)count, slot, false, false, c.sync_mode ? next_comm_seq(e) : 0u);
     API_END
 }
@@ -2391,44 +2440,25 @@ int bbmpc_optimize_gather_dev(bbmpc_handle h, const float* d_state, int32_t, int
                               float* d_next_state, float* d_gathered, int32_t slot) {
     API_BEGIN
     CHECK_HANDLE(h);
-    h->e->invalidate_step_graph();
-    // the communicator of a population-sharded handle carries the per-iteration partials on the LAUNCH stream; one RCCL
-    // communicator must not be driven from two unsynchronised streams, so such a handle has no record gather (its ranks
-    // all hold the same agents: there is nothing to gather).  A population that is only split into shards on THIS GPU
-    // (population_size > 32768, or the loopback hook) never drives the communicator and gathers like any other handle
-    if (h->e->pop_sharded_across_ranks()) throw HipError(BBMPC_E_UNSUPPORTED, "record gather on a handle whose population is sharded over ranks (every rank already holds every agent's record)");
+    Engine* e = h->e;
+    e->invalidate_step_graph();
+    refuse_gather_when_sharded_over_ranks(e);
     CHECK_PTR(d_state);
     CHECK_PTR(d_records);
     CHECK_PTR(d_gathered);
     if (d_next_state == d_state) throw HipError(BBMPC_E_INVALID, "d_next_state must not alias d_state");
-    Engine* e = h->e;
-    RecordComm& c = e->rc;
-    if (!c.comm) throw HipError(BBMPC_E_STATE, "bbmpc_optimize_gather_dev: call bbmpc_comm_init first");
-    if (slot < 0 || slot >= RecordComm::kSlots) throw HipError(BBMPC_E_INVALID, "bbmpc_optimize_gather_dev: slot must be 0 or 1");
-    if (c.pending[slot]) throw HipError(BBMPC_E_STATE, "bbmpc_optimize_gather_dev: slot still pending (call bbmpc_gather_wait)");
+    RecordComm& c = gather_comm(e, "bbmpc_optimize_gather_dev", slot);
     // single-launch control steps carry the hand-off themselves: the sequence number published by the kernel's last
     // workgroup, or (BBMPC_COMM_SYNC=event) the ready event on the kernel's dispatch packet
-    uint32_t v = 0;
-    if (c.sync_mode == 1) {
-        v = next_comm_seq(e);
-        e->tail_flag = c.flag;
-        e->tail_count = c.count;
-        e->tail_value = v;
-    } else {
-        e->tail_event = c.ready[slot];
-    }
-    e->tail_attached = false;
-    try {
+    const uint32_t v = c.sync_mode == 1 ? next_comm_seq(e) : 0u;
+    bool taken = false;
+    {
+        using bbmpc::TailRequest;
+        const TailRequest want = c.sync_mode == 1 ? TailRequest(*e, c.flag, c.count, v) : TailRequest(*e, c.ready[slot]);
         e->optimize_dev(d_state, noise, d_records, d_next_state);
-    } catch (...) {
-        e->tail_event = nullptr;
-        e->tail_flag = nullptr;
-        throw;
+        taken = want.taken();
     }
-    e->tail_event = nullptr;
-    e->tail_flag = nullptr;
-    const bool published = c.sync_mode == 1 && e->tail_attached;
-    gather_records(e, d_records, d_gathered, (size_t)e->A * e->rec, slot, c.sync_mode == 0 && e->tail_attached, published, v);
+    gather_records(e, d_records, d_gathered, (size_t)e->A * e->rec, slot, c.sync_mode == 0 && taken, c.sync_mode == 1 && taken, v);
     API_END
 }
 
@@ -2439,19 +2469,12 @@ int bbmpc_optimize_gather(bbmpc_handle h, const float* state, int32_t, int32_t n
                           float* reward, float* d_gathered, int32_t slot) {
     API_BEGIN
     CHECK_HANDLE_NOSETTLE(h);            // as bbmpc_optimize: consecutive calls are ordered by the stream / the resident kernel
-    h->e->invalidate_step_graph();
-    // the communicator of a population-sharded handle carries the per-iteration partials on the LAUNCH stream; one RCCL
-    // communicator must not be driven from two unsynchronised streams, so such a handle has no record gather (its ranks
-    // all hold the same agents: there is nothing to gather).  A population that is only split into shards on THIS GPU
-    // (population_size > 32768, or the loopback hook) never drives the communicator and gathers like any other handle
-    if (h->e->pop_sharded_across_ranks()) throw HipError(BBMPC_E_UNSUPPORTED, "record gather on a handle whose population is sharded over ranks (every rank already holds every agent's record)");
+    Engine* e = h->e;
+    e->invalidate_step_graph();
+    refuse_gather_when_sharded_over_ranks(e);
     CHECK_PTR(state);
     CHECK_PTR(d_gathered);
-    Engine* e = h->e;
-    RecordComm& c = e->rc;
-    if (!c.comm) throw HipError(BBMPC_E_STATE, "bbmpc_optimize_gather: call bbmpc_comm_init first");
-    if (slot < 0 || slot >= RecordComm::kSlots) throw HipError(BBMPC_E_INVALID, "bbmpc_optimize_gather: slot must be 0 or 1");
-    if (c.pending[slot]) throw HipError(BBMPC_E_STATE, "bbmpc_optimize_gather: slot still pending (call bbmpc_gather_wait)");
+    RecordComm& c = gather_comm(e, "bbmpc_optimize_gather", slot);
     // this rank's agents: exactly bbmpc_optimize (zero-copy state, records polled from pinned memory, resident kernel).
     // While the control step runs on the GPU the host enqueues the collective of the PREVIOUS call's records: the
     // ~20 us of host API time (H2D copy, ncclAllGather, completion word) hide under the kernel instead of sitting
@@ -2461,16 +2484,12 @@ int bbmpc_optimize_gather(bbmpc_handle h, const float* state, int32_t, int32_t n
     if (!e->d_record_slot[slot].p) e->d_record_slot[slot].alloc(nr);
     if (!e->h_record_stage[slot])
         HIP_CHECK(hipHostMalloc((void**)&e->h_record_stage[slot], nr * sizeof(float), hipHostMallocDefault));
-    e->in_flight_hook = flush_deferred_gathers;
-    e->in_flight_called = false;
     const float* rec = nullptr;
-    try {
+    {
+        e->in_flight_called = false;
+        bbmpc::ScopedRequest<void (*)(Engine*)> hook(e->in_flight_hook, flush_deferred_gathers);
         rec = optimize_host(*e, state, noise, action, next_state, reward);
-    } catch (...) {
-        e->in_flight_hook = nullptr;
-        throw;
     }
-    e->in_flight_hook = nullptr;
     if (!e->in_flight_called) flush_deferred_gathers(e);
     memcpy(e->h_record_stage[slot], rec, nr * sizeof(float));      // the slot is free: its last gather was waited for (pending == false)
     e->gather_deferred[slot] = true;
@@ -2480,8 +2499,6 @@ int bbmpc_optimize_gather(bbmpc_handle h, const float* state, int32_t, int32_t n
     API_END
 }
 
-// What the communicator itself reports (ncclCommCount / ncclCommUserRank) + the hand-off mode in use:
-// sync_mode 1 = sequence numbers in signal memory, 0 = events.
 int bbmpc_call_stats(bbmpc_handle h, int64_t* served_resident, int64_t* launched) {
     API_BEGIN
     CHECK_HANDLE(h);
@@ -2505,6 +2522,8 @@ int bbmpc_handle_device(bbmpc_handle h, int32_t* device) {
     API_END
 }
 
+// What the communicator itself reports (ncclCommCount / ncclCommUserRank) + the hand-off mode in use:
+// sync_mode 1 = sequence numbers in signal memory, 0 = events.
 int bbmpc_comm_info(bbmpc_handle h, int32_t* nranks, int32_t* rank, int32_t* sync_mode) {
     API_BEGIN
     CHECK_HANDLE(h);

@@ -359,9 +359,9 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
 void Engine::launch_pending_cma_update(const FinalArgs& fa) {
     PendingCmaUpdate pu = pending_cma_update;
     pending_cma_update.set = false;
-    if (tail_flag) tail_attached = true;
+    const TailHandoff::Words w = tail.publish_words();
     launch_with_tail(*this, k_cma_update_final_small, dim3(cma_G), dim3(1024), pu.lds, pu.q, c_evec.p, c_eval.p, c_info.p, sw.cma_eigh_fail ? 1 : 0, pu.yef,
-                     fa, tail_flag, tail_count, tail_value);
+                     fa, w.flag, w.count, w.value);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -397,10 +397,7 @@ void Engine::optimize_fused_cma(const float* d_state_in, int add_noise, float* d
     fin.next_state = d_next_out;
     fin.key = key(step);
     fin.key.q_per_agent = (uint32_t)((U + 3) / 4);
-    if (tail_flag) {
-        fa.done_flag = tail_flag; fa.done_count = tail_count; fa.done_value = tail_value;
-        tail_attached = true;
-    }
+    tail.publish_into(fa);
     const int kp = (k + 3) & ~3;
     const size_t lds = std::max((size_t)(Nst + TOPK_HIST_WORDS_NARROW + 2 * kp) * 4, (size_t)cma_n * cma_n * 4);
     // (the factorisation's workspace is static LDS: with the dynamic part the kernel is past the 64 KB default)

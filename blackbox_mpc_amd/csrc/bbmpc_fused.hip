@@ -47,7 +47,7 @@ static void launch_fused4(Engine& e, FusedArgs& fa, int threads, size_t lds_base
     if (lds_base + lds_samples <= limit) {
         fa.test_quit_agent = -1;
         if constexpr (INJ == 2 && FASTM && ILP == 1) {
-            if (e.linger_launch && e.subset_n == 0 && fa.done_flag && e.tail_event == nullptr) {
+            if (e.linger_launch && e.subset_n == 0 && fa.done_flag && e.tail.event == nullptr) {
                 // the resident form: this launch serves the current call and then every workgroup waits for its agent's next
                 // request on its own (kernels_fused.hpp)
                 auto fl = k_fused_pendulum<OPT, true, FASTM, INJ, ILP, true>;
@@ -160,10 +160,7 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     fa.fix_q7 = fix(BBMPC_FIX_Q7_EXPL_NOISE_ZERO_MEAN);
     fa.add_noise = add_noise;
     fa.warm_start = fix(BBMPC_FIX_Q2_CEM_WARM_START);
-    if (tail_flag) {
-        fa.done_flag = tail_flag; fa.done_count = tail_count; fa.done_value = tail_value;
-        tail_attached = true;
-    }
+    tail.publish_into(fa);
     fa.alpha = cfg.alpha;
     fa.inv_lamda = 1.0f / cfg.lamda;
     fa.state = d_state_in;
@@ -343,10 +340,7 @@ void Engine::optimize_fused_pso(const float* d_state_in, int add_noise, float* d
     fa.fix_q7 = fix(BBMPC_FIX_Q7_EXPL_NOISE_ZERO_MEAN);
     fa.add_noise = add_noise;
     fa.w = cfg.pso_w; fa.c1 = cfg.pso_c1; fa.c2 = cfg.pso_c2; fa.v0frac = cfg.pso_v0_fraction;
-    if (tail_flag) {             // the records are complete when this kernel ends (k_pso_seed only re-seeds the swarm)
-        fa.done_flag = tail_flag; fa.done_count = tail_count; fa.done_value = tail_value;
-        tail_attached = true;
-    }
+    tail.publish_into(fa);       // the records are complete when this kernel ends (k_pso_seed only re-seeds the swarm)
     fa.state = d_state_in;
     fa.lo = d_lo.p; fa.hi = d_hi.p; fa.var0 = d_var0.p;
     fa.s = pso_state();

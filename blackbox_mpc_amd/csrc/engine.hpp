@@ -109,6 +109,29 @@ struct UserFunction {
     }
 };
 
+// The hand-off between the caller of a control step and the step's last kernel: the caller asks (engine_util.hpp:
+// TailRequest) either for a sequence number that the kernel publishes itself when the record is complete
+// (RecordComm::flag, or the host-polled completion word host_done) or for a completion event on the kernel's dispatch
+// packet; the launch site that can serve the request takes it and marks it attached.  Empty outside a request.
+struct TailHandoff {
+    uint32_t* flag = nullptr;      // where the last kernel publishes `value`
+    uint32_t* count = nullptr;     // arrival counter that goes with flag (device memory)
+    uint32_t value = 0;
+    hipEvent_t event = nullptr;    // or: completion event wanted on the last kernel (launch_with_tail)
+    bool attached = false;         // the step's last kernel took the request
+    // launch sites whose argument struct carries the three words
+    template <class KernelArgs>
+    void publish_into(KernelArgs& x) {
+        if (flag) { x.done_flag = flag; x.done_count = count; x.done_value = value; attached = true; }
+    }
+    // ... and those whose kernel takes them as trailing arguments
+    struct Words { uint32_t* flag; uint32_t* count; uint32_t value; };
+    Words publish_words() {
+        if (flag) attached = true;
+        return {flag, count, value};
+    }
+};
+
 struct Engine {
     bbmpc_config cfg;
     int N, A, H, U, S, HU, Nst, iters, k;
@@ -132,6 +155,7 @@ struct Engine {
     uint32_t* step_words_dev = nullptr;    // device memory: [0] control step, [1] completion value, [2] arrival counter of the tail's workgroups
     uint32_t* step_words = nullptr;        // pinned staging for re-synchronising them
     uint32_t step_mirror[2] = {0, 0};      // what the device words hold now
+    void ensure_step_words();              // allocates step_words / step_words_dev on first use
     bool step_capturing = false;
     int64_t calls_graph = 0;               // replays so far (bbmpc_graph_stats)
     int64_t graph_capture_failures = 0;    // captures / instantiations that failed (the handle then stops trying)
@@ -233,17 +257,15 @@ struct Engine {
     void (*settle_hook)(Engine*) = nullptr;      // flushes them when anything settles the handle
     void (*in_flight_hook)(Engine*) = nullptr;   // called once per host-in / host-out control step, right after it was handed to the GPU
     bool in_flight_called = false;
-    hipEvent_t tail_event = nullptr;   // completion event wanted on the control step's last kernel (launch_with_tail)
-    bool tail_attached = false;
-    uint32_t* tail_flag = nullptr;     // or: sequence number the last kernel should publish itself (RecordComm::flag / host_done)
-    uint32_t tail_value = 0;
-    uint32_t* tail_count = nullptr;    // arrival counter that goes with tail_flag (device memory)
+    void note_in_flight() { if (in_flight_hook && !in_flight_called) { in_flight_called = true; in_flight_hook(this); } }
+    TailHandoff tail;                  // what the caller of optimize_dev wants from the control step's last kernel (TailRequest installs it)
     // host-in/host-out calls of a single-kernel control step return as soon as the kernel has published its records
     // into host memory; the stream is joined lazily by the next call that needs it (settle)
     uint32_t* host_done = nullptr;     // pinned host word the kernel publishes to
     uint32_t* host_done_dev = nullptr; // its device address
     uint32_t* host_count = nullptr;    // device memory arrival counter
     uint32_t host_seq = 0;
+    void ensure_completion_block();    // allocates host_done / host_count on first use
     bool lazy_sync = false;
     void settle();
     // resident control-step kernel (one agent, persistent pendulum kernel, host-in / host-out calls): the kernel of one

@@ -1,5 +1,6 @@
 // Host-side helpers shared by the engine's translation units (bbmpc.hip, bbmpc_cma.hip, bbmpc_mlp.hip, bbmpc_fused.hip).
 #pragma once
+#include <chrono>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -44,12 +45,64 @@ inline void want_lds(const void* fn, size_t bytes, size_t static_bytes = 0) {
 // hipEventRecord costs the launch stream ~5 us per control step (tools/gather_overhead.py).
 template <class F, class... Args>
 inline void launch_with_tail(Engine& e, F fn, dim3 grid, dim3 block, size_t lds, const Args&... args) {
-    if (e.tail_event) {
-        hipExtLaunchKernelGGL(fn, grid, block, lds, e.stream, nullptr, e.tail_event, 0, args...);
-        e.tail_attached = true;
+    if (e.tail.event) {
+        hipExtLaunchKernelGGL(fn, grid, block, lds, e.stream, nullptr, e.tail.event, 0, args...);
+        e.tail.attached = true;
     } else {
         hipLaunchKernelGGL(fn, grid, block, lds, e.stream, args...);
     }
+}
+
+// The producer's side of Engine::tail, for the length of one optimize_dev: installs the request, and the handle is
+// back to the empty hand-off when the scope ends -- by return or by exception -- so no later control step can publish
+// into this call's memory.
+class TailRequest {
+    Engine& e_;
+public:
+    TailRequest(Engine& e, uint32_t* flag, uint32_t* count, uint32_t value) : e_(e) { e.tail = TailHandoff{flag, count, value, nullptr, false}; }
+    TailRequest(Engine& e, hipEvent_t event) : e_(e) { e.tail = TailHandoff{nullptr, nullptr, 0, event, false}; }
+    TailRequest(const TailRequest&) = delete;
+    TailRequest& operator=(const TailRequest&) = delete;
+    ~TailRequest() { e_.tail = TailHandoff{}; }
+    bool taken() const { return e_.tail.attached; }       // the step's last kernel carries the hand-off
+};
+
+// The other per-call requests that optimize_dev's callers leave in Engine members (linger_launch, stage_state_src,
+// in_flight_hook): set for the scope, back to "no request" on every way out of it.
+template <class T>
+class ScopedRequest {
+    T& slot_;
+public:
+    ScopedRequest(T& slot, T v) : slot_(slot) { slot_ = v; }
+    ScopedRequest(const ScopedRequest&) = delete;
+    ScopedRequest& operator=(const ScopedRequest&) = delete;
+    ~ScopedRequest() { slot_ = T{}; }
+};
+
+// ... and for a request that the launch itself uses up (subset_n): cleared only when the scope is left early, by an
+// exception -- the ordinary way out says done().
+template <class T>
+class ClearOnThrow {
+    T& slot_;
+    bool done_ = false;
+public:
+    explicit ClearOnThrow(T& slot) : slot_(slot) {}
+    ClearOnThrow(const ClearOnThrow&) = delete;
+    ClearOnThrow& operator=(const ClearOnThrow&) = delete;
+    void done() { done_ = true; }
+    ~ClearOnThrow() { if (!done_) slot_ = T{}; }
+};
+
+// Spin until done() holds.  The clock is looked at every 4096 spins; after 2 s last_look() -- the caller's "settle what
+// may still be running, then look once more" -- decides: it returns whether the wait is over (or throws).  Returns
+// false only when last_look() said so.
+template <class Done, class LastLook>
+inline bool spin_until(std::chrono::steady_clock::time_point t0, Done done, LastLook last_look) {
+    uint32_t spins = 0;
+    while (!done()) {
+        if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) return last_look();
+    }
+    return true;
 }
 
 // every translation unit has its own copy of the truncated-normal quantile table (rng.hpp, `static __device__`): the
