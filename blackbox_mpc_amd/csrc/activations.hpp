@@ -104,13 +104,18 @@ __device__ __forceinline__ float bb_swishf(float x) {
 // leaky_relu with tf.nn.leaky_relu's default slope 0.2: max(x, 0.2 x) (TF 2.0 spells it the same way); NaN in both operands.
 __device__ __forceinline__ float bb_leaky_reluf(float x) { return fmaxf(x, 0.2f * x); }
 
+// relu as a compare, so that NaN stays NaN: fmaxf(NaN, 0) is 0 (v_max_f32 returns the operand that is a number), which let a
+// NaN input leave a relu layer as an ordinary activation and its candidate keep a finite score.  Every other input gives
+// fmaxf's bits (-0 -> +0 included).
+__device__ __forceinline__ float bb_reluf(float x) { return x <= 0.0f ? 0.0f : x; }
+
 // relu6: min(max(x, 0), 6) as compares, so that NaN stays NaN.
 __device__ __forceinline__ float bb_relu6f(float x) { return x < 0.0f ? 0.0f : (x > 6.0f ? 6.0f : x); }
 
 template <int ACT>
 __device__ __forceinline__ float apply_act_ct(float x) {
     if constexpr (ACT == ACT_TANH) return bb_tanhf(x);
-    else if constexpr (ACT == ACT_RELU) return fmaxf(x, 0.0f);
+    else if constexpr (ACT == ACT_RELU) return bb_reluf(x);
     else if constexpr (ACT == ACT_SIGMOID) return 1.0f / (1.0f + expf(-x));
     else if constexpr (ACT == ACT_ELU) return bb_eluf(x);
     else if constexpr (ACT == ACT_SELU) return bb_seluf(x);
@@ -131,7 +136,7 @@ __device__ __forceinline__ float apply_act_ct(float x) {
 // over the later codes behind a guard.
 __device__ __forceinline__ float apply_act_base(float x, int act) {
     if (act == ACT_TANH) return bb_tanhf(x);
-    if (act == ACT_RELU) return fmaxf(x, 0.0f);
+    if (act == ACT_RELU) return bb_reluf(x);
     if (act == ACT_SIGMOID) return 1.0f / (1.0f + expf(-x));
     return x;
 }

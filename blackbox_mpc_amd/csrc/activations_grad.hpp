@@ -8,7 +8,7 @@
 //
 // Kinks.  relu, relu6, leaky_relu and hard_sigmoid are piecewise linear; at a kink the derivative is the slope of the
 // branch the forward's comparison takes there:
-//   relu          fmaxf(x, 0)                      x > 0 ? 1 : 0          (at 0 the forward returns the constant 0)
+//   relu          x <= 0 ? 0 : x                   x > 0 ? 1 : 0          (at 0 the forward returns the constant 0)
 //   relu6         x < 0 ? 0 : (x > 6 ? 6 : x)      0 at x < 0 and x > 6, else 1   (at 0 and at 6 the forward returns x)
 //   leaky_relu    fmaxf(x, 0.2 x)                  x > 0 ? 1 : 0.2
 //   hard_sigmoid  t = 0.2 x + 0.5 clipped          0 at t < 0 and t > 1, else 0.2  (at t = 0 and t = 1 the forward returns t)

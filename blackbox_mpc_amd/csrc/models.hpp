@@ -97,6 +97,15 @@ struct PendulumModel {
     }
 };
 
+// The H-step sum of a roller that carries the angle: the reference's last step reward holds sum(next_state^2) of the state
+// AFTER the last step (quirk Q1), which the carried forms replace by 1 + newthdot^2 with the speed clipped -- a NaN or
+// infinite last action would leave the sum finite where the reference's is NaN (deterministic.py:75-77 then scores -1e6).
+// The angle after the last step is NaN exactly then (nphi - rint(nphi), wrap of a non-finite angle), and is NaN as well
+// whenever an earlier step already made the sum NaN: one compare and select per rollout, nothing in the step.
+__device__ __forceinline__ float nonfinite_total(float total, float last_angle) {
+    return last_angle != last_angle ? last_angle : total;
+}
+
 // The same recurrence carried as (theta, thdot) instead of (cos, sin, thdot).
 //
 // The reference re-derives theta = atan2(sin, cos) from the state every step (utils/pendulum.py:82 and
@@ -122,7 +131,8 @@ struct PendulumAngleModel {
         float nthd = thd + acc * 0.05f;
         const float nth = theta + nthd * 0.05f;
         // one v_med3_f32 instead of two compare/select pairs.  (A NaN speed becomes -8 here, but theta is NaN in that
-        // case as well and keeps the step reward NaN, which is all the evaluator's NaN guard looks at.)
+        // case as well and makes the NEXT step's reward NaN; after the last step there is no next one, so the rollers'
+        // total() looks at the carried angle once more: nonfinite_total below.)
         nthd = __builtin_amdgcn_fmed3f(nthd, -8.0f, 8.0f);
         const float n2 = (nthd - thd) + thd;
         const float ss = fix_q1 ? u * u : 1.0f + n2 * n2;
@@ -208,7 +218,7 @@ struct PendulumTurnModel {
     __device__ __forceinline__ float total() const {
         const float ss = fix_q1 ? q_act : (float)q_n + q_act;               // sum(next_state^2) = 1 + newthdot^2 per step (quirk Q1)
         const float first = (BBMPC_TWO_PI_F * BBMPC_TWO_PI_F) * q_ang + 0.1f * q_thd;
-        return (-first) - 0.001f * ss;
+        return nonfinite_total((-first) - 0.001f * ss, phi);
     }
 #endif
     __device__ __forceinline__ float step(float u) {
@@ -308,7 +318,11 @@ struct Roller<true> {
     __device__ __forceinline__ void step_acc(float u) { acc_ = acc_ + m.step(u); }
     template <bool Q1>
     __device__ __forceinline__ void step_acc_q1(float u) { step_acc(u); }
-    __device__ __forceinline__ float total() const { return acc_; }
+#if BBMPC_PENDULUM_HW_SIN
+    __device__ __forceinline__ float total() const { return nonfinite_total(acc_, m.phi); }
+#else
+    __device__ __forceinline__ float total() const { return nonfinite_total(acc_, m.theta); }
+#endif
 #endif
 };
 

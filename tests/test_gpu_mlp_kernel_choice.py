@@ -92,35 +92,54 @@ def L():
     return _lib
 
 
-def run_case(L, c, setenv):
-    """-> (device result, oracle result, plain name, instantiation, evaluator, states, sequences); setenv(key, value) is
-    called for the case's switches before the engine is created (they are read there)."""
+def case_oracle(c, seed=42):
+    """-> (weights, biases, stats, oracle evaluator) of a case, without a device: the parameters _problem draws for `seed`"""
+    dims, acts, S, U = c["dims"], c["acts"], c["S"], c["U"]
+    ws, bs = O.make_mlp_params(dims, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    bs = [rng.normal(0, 0.05, b.shape).astype(F) for b in bs]
+    stats = _stats(S, U, seed + 2)
+    net = MLP64(ws, bs, acts) if any(a in EXT for a in acts) else O.MLP(ws, bs, acts)
+    ev = O.Evaluator(_q4s_user_reward_np if c["reward"] == "user" else c["reward"], O.Handler(net, False, True, stats))
+    return ws, bs, stats, ev
+
+
+def case_inputs(c):
+    """-> (start states [A, S], action sequences [N, A, H, U]) of a rollout case"""
+    rng = np.random.default_rng(sum(c["dims"]) + c["N"] + c["H"])
+    states = O.pendulum_start_states(c["A"]) if c["reward"] == "pendulum" else O.cheetah_start_states(c["A"], c["S"])
+    return states, rng.uniform(-1, 1, (c["N"], c["A"], c["H"], c["U"])).astype(F)
+
+
+def build_case(L, c, setenv):
+    """-> (engine, oracle evaluator) of a case; setenv(key, value) is called for the case's switches before the engine is
+    created (they are read there).  tests/test_gpu_nonfinite_candidates.py builds its engines here too."""
     from blackbox_mpc_amd.engine import Engine
     for k, v in c["env"].items():
         setenv(k, v)
-    dims, acts, S, U, A, H, N = c["dims"], c["acts"], c["S"], c["U"], c["A"], c["H"], c["N"]
-    seed = 42
+    dims, acts, S, U, A, H = c["dims"], c["acts"], c["S"], c["U"], c["A"], c["H"]
     if c["reward"] == "user" or any(a in EXT for a in acts):
-        ws, bs = O.make_mlp_params(dims, seed=seed)
-        rng = np.random.default_rng(seed + 1)
-        bs = [rng.normal(0, 0.05, b.shape).astype(F) for b in bs]
-        stats = _stats(S, U, seed + 2)
+        ws, bs, stats, ev = case_oracle(c)
         rk = {"cheetah": L.REW_CHEETAH, "pendulum": L.REW_PENDULUM, "user": L.REW_USER}[c["reward"]]
         eng = Engine(L.OPT_NONE, L.DYN_MLP, rk, [-1.0] * U, [1.0] * U, dim_s=S, num_agents=A, planning_horizon=H)
         if c["reward"] == "user":
             eng.set_reward_source(Q4S_USER_REWARD)
         eng.set_mlp(ws, bs, [CODE[a] for a in acts], stats)
-        net = MLP64(ws, bs, acts) if any(a in EXT for a in acts) else O.MLP(ws, bs, acts)
-        ev = O.Evaluator(_q4s_user_reward_np if c["reward"] == "user" else c["reward"], O.Handler(net, False, True, stats))
     else:
-        eng, ev, _, _ = _problem(L, dims, acts, S, U, c["reward"], True, seed=seed, A=A, H=H)
+        eng, ev, _, _ = _problem(L, dims, acts, S, U, c["reward"], True, seed=42, A=A, H=H)
+    return eng, ev
+
+
+def run_case(L, c, setenv):
+    """-> (device result, oracle result, plain name, instantiation, evaluator, states, sequences)"""
+    eng, ev = build_case(L, c, setenv)
+    dims, S, U, A, H, N = c["dims"], c["S"], c["U"], c["A"], c["H"], c["N"]
     rng = np.random.default_rng(sum(dims) + N + H)
     if c["step"]:
         s = rng.normal(0, 0.5, (N, S)).astype(F)
         a = rng.uniform(-1, 1, (N, U)).astype(F)
         return eng.predict_next_state(s, a), ev.predict_next_state(s, a), None, None, ev, s, a
-    states = O.pendulum_start_states(A) if c["reward"] == "pendulum" else O.cheetah_start_states(A, S)
-    seq = rng.uniform(-1, 1, (N, A, H, U)).astype(F)
+    states, seq = case_inputs(c)
     got = eng.evaluate(states, seq)
     return got, ev(states, seq), eng.get_profile()[2], eng.profile_instantiation(), ev, states, seq
 
