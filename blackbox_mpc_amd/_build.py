@@ -9,9 +9,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbbmpc.so")
 # engine + ABI | persistent pendulum kernels | CMA-ES | learned-model rollouts | user functions (hiprtc) + their ABI |
-# trajectory prediction + its ABI | particle trajectory evaluator + its ABI | trajectory distributions + their ABI
+# trajectory prediction + its ABI | particle trajectory evaluator + its ABI | trajectory distributions + their ABI |
+# Dense-stack training + its ABI
 SOURCES = ["bbmpc.hip", "bbmpc_fused.hip", "bbmpc_cma.hip", "bbmpc_mlp.hip", "bbmpc_user.hip", "bbmpc_traj.hip",
-           "bbmpc_particles.hip", "bbmpc_traj_particles.hip"]
+           "bbmpc_particles.hip", "bbmpc_traj_particles.hip", "bbmpc_train.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          # one rounding per reference op: never contract a*b+c behind the source's back
          "-ffp-contract=off",
@@ -37,7 +38,8 @@ GUARDED = {"kernels_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_fused_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_reward_mlp.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
            "kernels_plan_grad.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
-           "kernels_plan_refine.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP")}
+           "kernels_plan_refine.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
+           "kernels_train.hpp": ("bbmpc_train.hip", "#ifdef BBMPC_TU_TRAIN")}
 
 
 def _after_matching_endif(rest):

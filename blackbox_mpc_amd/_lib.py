@@ -40,6 +40,9 @@ TRACE_REWARDS, TRACE_MEAN, TRACE_VAR, TRACE_ELITES, TRACE_SAMPLES = 1, 2, 3, 4, 
 TRACE_CMA_B, TRACE_CMA_C, TRACE_CMA_D, TRACE_CMA_SVD_STATS = 6, 7, 8, 9
 TRACE_TOPK_PASSES = 10
 
+TRAIN_ADAM, TRAIN_SGD, TRAIN_RMSPROP = 1, 2, 3                # bbmpc_trainer_create: rule
+TRAIN_MAX_LAYERS, TRAIN_MAX_WIDTH, TRAIN_MAX_BATCH, TRAIN_LDS_LIMIT = 8, 512, 4096, 159 * 1024
+
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_UNSUPPORTED = -1, -2, -3, -4, -5
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -100,6 +103,8 @@ SYMBOLS = [
     "bbmpc_predict_policy_rollouts", "bbmpc_predict_policy_rollouts_dev",
     "bbmpc_plan_gradient", "bbmpc_plan_gradient_dev",
     "bbmpc_refine_plans", "bbmpc_refine_plans_dev", "bbmpc_set_grad_refine", "bbmpc_get_grad_refine",
+    "bbmpc_trainer_create", "bbmpc_trainer_destroy", "bbmpc_trainer_lds_bytes", "bbmpc_trainer_set_data", "bbmpc_trainer_fit",
+    "bbmpc_trainer_get_params", "bbmpc_trainer_residual_rms", "bbmpc_trainer_gradients",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -219,6 +224,15 @@ def _load():
     lib.bbmpc_get_elite_carry.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.bbmpc_process_input.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
     lib.bbmpc_process_output.argtypes = [vp, vp, vp, i32, ctypes.POINTER(vp), vp]
+    lib.bbmpc_trainer_create.argtypes = [ctypes.POINTER(vp), i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
+                                         ctypes.POINTER(vp), i32, ctypes.c_float]
+    lib.bbmpc_trainer_destroy.argtypes = [vp]
+    lib.bbmpc_trainer_lds_bytes.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
+    lib.bbmpc_trainer_set_data.argtypes = [vp, vp, vp, i32, vp, vp, i32]
+    lib.bbmpc_trainer_fit.argtypes = [vp, i32, i32, vp, ctypes.c_uint64, vp, vp]
+    lib.bbmpc_trainer_get_params.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.bbmpc_trainer_residual_rms.argtypes = [vp, vp, vp, i32, vp]
+    lib.bbmpc_trainer_gradients.argtypes = [vp, vp, i32, vp, vp]
     return lib
 
 

@@ -1,0 +1,407 @@
+// Training a Dense stack through the C ABI (bbmpc_trainer_*): the host side of kernels_train.hpp.
+// A trainer is independent of the planning handle: its own device, stream and buffers, no bbmpc_config.
+#define BBMPC_TU_TRAIN
+#include <cmath>
+#include <limits>
+
+#include "abi_util.hpp"
+#include "kernels_train.hpp"
+
+namespace bbmpc {
+
+// Everything bbmpc_trainer_create refuses, checked before a device is touched.  Fills the layout.
+static void train_describe(TrainNet& n, int32_t n_layers, const int32_t* dims, const int32_t* acts) {
+    REQUIRE(n_layers >= 1, BBMPC_E_INVALID, "trainer: n_layers must be >= 1");
+    REQUIRE(n_layers <= TR_MAX_LAYERS, BBMPC_E_UNSUPPORTED, "trainer: more than 8 layers");
+    REQUIRE(dims && acts, BBMPC_E_INVALID, "trainer: null dims / activations");
+    memset(&n, 0, sizeof(n));
+    n.L = n_layers;
+    for (int l = 0; l <= n_layers; ++l) {
+        REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "trainer: a layer width < 1");
+        n.dims[l] = dims[l];
+    }
+    for (int l = 0; l < n_layers; ++l) {
+        REQUIRE(acts[l] >= ACT_NONE && acts[l] <= ACT_RELU6, BBMPC_E_INVALID, "trainer: unknown activation code");
+        n.act[l] = acts[l];
+    }
+    for (int l = 0; l <= n_layers; ++l) REQUIRE(dims[l] <= TR_MAX_WIDTH, BBMPC_E_UNSUPPORTED, "trainer: a layer width > 512");
+    int o = 0;
+    for (int l = 0; l < n_layers; ++l) { n.woff[l] = o; o += n.dims[l] * n.dims[l + 1]; }
+    for (int l = 0; l < n_layers; ++l) { n.boff[l] = o; o += n.dims[l + 1]; }
+    n.n_params = o;
+    train_lds_layout(n);
+    REQUIRE((size_t)n.lds_floats * 4 <= (size_t)TR_LDS_LIMIT, BBMPC_E_UNSUPPORTED,
+            "trainer: the network's resident layer tiles need " + std::to_string((size_t)n.lds_floats * 4) +
+                " bytes of LDS, over the 159 KiB limit");
+}
+
+struct Trainer {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    TrainNet net;
+    int rule = TR_RULE_ADAM;
+    double lr = 1e-3;
+    DevBuf<float> theta, m, v, wf[TR_MAX_LAYERS], wr[TR_MAX_LAYERS], bp[TR_MAX_LAYERS];
+    DevBuf<double> pows;
+    long long steps = 0;
+    DevBuf<float> din, dout, vin, vout;
+    int n_train = 0, n_val = 0;
+    bool has_data = false;
+    DevBuf<float> part, lossp, loss_acc, val_loss, val_tiles, val_batch, grads, colsq, rms, rin, rout;
+    DevBuf<int> perms, idx;
+
+    Trainer(const TrainNet& n, int dev, const float* const* weights, const float* const* biases, int rule_, double lr_)
+        : device(dev), net(n), rule(rule_), lr(lr_) {
+        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        const int L = net.L;
+        std::vector<float> h((size_t)net.n_params);
+        for (int l = 0; l < L; ++l) {
+            memcpy(h.data() + net.woff[l], weights[l], sizeof(float) * net.dims[l] * net.dims[l + 1]);
+            memcpy(h.data() + net.boff[l], biases[l], sizeof(float) * net.dims[l + 1]);
+        }
+        theta.alloc(h.size());
+        m.alloc(h.size());
+        v.alloc(h.size());
+        pows.alloc(4);
+        HIP_CHECK(hipMemcpy(theta.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(m.p, 0, h.size() * sizeof(float)));
+        HIP_CHECK(hipMemset(v.p, 0, h.size() * sizeof(float)));
+        const double ones[4] = {1.0, 1.0, 1.0, 1.0};
+        HIP_CHECK(hipMemcpy(pows.p, ones, sizeof(ones), hipMemcpyHostToDevice));
+        for (int l = 0; l < L; ++l) {
+            const int in = net.dims[l], out = net.dims[l + 1], IT = net.tiles[l], OT = net.tiles[l + 1];
+            std::vector<float> f((size_t)IT * OT * 256, 0.0f), r((size_t)IT * OT * 256, 0.0f), b((size_t)OT * 16, 0.0f);
+            for (int i = 0; i < in; ++i)
+                for (int o = 0; o < out; ++o) {
+                    const float w = weights[l][(size_t)i * out + o];
+                    f[train_wf_index(IT, i, o)] = w;
+                    r[train_wr_index(OT, i, o)] = w;
+                }
+            for (int o = 0; o < out; ++o) b[o] = biases[l][o];
+            wf[l].alloc(f.size());
+            wr[l].alloc(r.size());
+            bp[l].alloc(b.size());
+            HIP_CHECK(hipMemcpy(wf[l].p, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(wr[l].p, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(bp[l].p, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
+            net.wf[l] = wf[l].p;
+            net.wr[l] = wr[l].p;
+            net.bp[l] = bp[l].p;
+        }
+        const int bytes = net.lds_floats * 4;
+        if (bytes > 64 * 1024) {
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_forward_mse), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        }
+    }
+    ~Trainer() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
+
+    static void upload(DevBuf<float>& d, const float* h, size_t count) {
+        d.alloc(count);
+        if (count) HIP_CHECK(hipMemcpy(d.p, h, count * sizeof(float), hipMemcpyHostToDevice));
+    }
+
+    void set_data(const float* tin, const float* tout, int nt, const float* vi, const float* vo, int nv) {
+        const int D = net.dims[0], O = net.dims[net.L];
+        upload(din, tin, (size_t)nt * D);
+        upload(dout, tout, (size_t)nt * O);
+        upload(vin, vi, (size_t)nv * D);
+        upload(vout, vo, (size_t)nv * O);
+        n_train = nt;
+        n_val = nv;
+        has_data = true;
+    }
+
+    static void check_batch(int B) {
+        REQUIRE(B >= 1 && B <= TR_MAX_BATCH, BBMPC_E_UNSUPPORTED, "trainer: batch_size must lie in [1, 4096]");
+    }
+
+    // forward + backward of the batch idx[0 .. B-1] (device pointer) into part / lossp
+    void launch_step(const int* d_idx, int B) {
+        TrainStepArgs q;
+        q.n = net;
+        q.din = din.p;
+        q.dout = dout.p;
+        q.idx = d_idx;
+        q.row0 = 0;
+        q.B = B;
+        q.gscale = (float)(2.0 / ((double)B * net.dims[net.L]));
+        q.part = part.p;
+        q.lossp = lossp.p;
+        const int tiles = (B + TR_ROWS - 1) / TR_ROWS;
+        hipLaunchKernelGGL(k_train_fwd_bwd, dim3(tiles), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        HIP_CHECK(hipGetLastError());
+    }
+
+    void launch_update(int rule_, int B, float* loss_slot, float* grads_out) {
+        TrainUpdateArgs u;
+        u.n = net;
+        u.theta = theta.p;
+        u.m = m.p;
+        u.v = v.p;
+        u.part = part.p;
+        u.lossp = lossp.p;
+        u.ntiles = (B + TR_ROWS - 1) / TR_ROWS;
+        u.rule = rule_;
+        const double b1 = 0.9, b2 = 0.999, rho = 0.9;          // Keras TF-2.0 defaults
+        u.lr = (float)lr;
+        u.b1 = (float)b1;
+        u.b2 = (float)b2;
+        u.omb1 = (float)(1.0 - b1);
+        u.omb2 = (float)(1.0 - b2);
+        u.rho = (float)rho;
+        u.omrho = (float)(1.0 - rho);
+        u.eps = 1e-7f;
+        u.lr_d = lr;
+        u.b1_d = b1;
+        u.b2_d = b2;
+        u.pows = pows.p;
+        u.parity = (int)(steps & 1);
+        u.inv_count = (float)(1.0 / ((double)B * net.dims[net.L]));
+        u.loss_acc = loss_slot;
+        u.grads_out = grads_out;
+        hipLaunchKernelGGL(k_train_update, dim3((net.n_params + 255) / 256), dim3(256), 0, stream, u);
+        HIP_CHECK(hipGetLastError());
+        if (rule_ != TR_RULE_NONE) ++steps;
+    }
+
+    void ensure_step_buffers(int B) {
+        const size_t tiles = (size_t)(B + TR_ROWS - 1) / TR_ROWS;
+        if (part.n < tiles * net.n_params) part.alloc(tiles * net.n_params);
+        if (lossp.n < tiles) lossp.alloc(tiles);
+    }
+
+    void launch_mse(const float* in, const float* out, int batches, int B, float* tile_loss, float* colsq_out) {
+        TrainMseArgs q;
+        q.n = net;
+        q.din = in;
+        q.dout = out;
+        q.B = B;
+        q.tiles_per_batch = (B + TR_ROWS - 1) / TR_ROWS;
+        q.tile_loss = tile_loss;
+        q.colsq = colsq_out;
+        hipLaunchKernelGGL(k_train_forward_mse, dim3((unsigned)((size_t)batches * q.tiles_per_batch)), dim3(net.nw * 64),
+                           (size_t)net.lds_floats * 4, stream, q);
+        HIP_CHECK(hipGetLastError());
+    }
+
+    void fit(int epochs, int B, const int32_t* perms_h, uint64_t seed, float* train_loss, float* val_loss_out) {
+        REQUIRE(has_data, BBMPC_E_STATE, "trainer: bbmpc_trainer_fit before bbmpc_trainer_set_data");
+        REQUIRE(epochs >= 1, BBMPC_E_INVALID, "trainer: epochs must be >= 1");
+        check_batch(B);
+        const int n = n_train, nb = n / B, nvb = n_val / B;
+        const int tpb = (B + TR_ROWS - 1) / TR_ROWS;
+        REQUIRE((long long)nvb * tpb < (1ll << 31) && (long long)epochs * n < (1ll << 40), BBMPC_E_UNSUPPORTED, "trainer: dataset too large");
+        std::vector<int32_t> drawn;
+        if (nb > 0) {
+            if (perms_h) {
+                for (size_t i = 0; i < (size_t)epochs * n; ++i)
+                    REQUIRE(perms_h[i] >= 0 && perms_h[i] < n, BBMPC_E_INVALID, "trainer: a permutation entry outside [0, n_train)");
+            } else {
+                drawn.resize((size_t)epochs * n);
+                for (int e = 0; e < epochs; ++e) train_draw_permutation(seed, e, n, drawn.data() + (size_t)e * n);
+                perms_h = drawn.data();
+            }
+            ensure_step_buffers(B);
+            if (perms.n < (size_t)epochs * n) perms.alloc((size_t)epochs * n);
+            HIP_CHECK(hipMemcpy(perms.p, perms_h, (size_t)epochs * n * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        if (loss_acc.n < (size_t)epochs) { loss_acc.alloc(epochs); val_loss.alloc(epochs); }
+        HIP_CHECK(hipMemsetAsync(loss_acc.p, 0, (size_t)epochs * sizeof(float), stream));
+        if (nvb > 0) {
+            if (val_tiles.n < (size_t)nvb * tpb) val_tiles.alloc((size_t)nvb * tpb);
+            if (val_batch.n < (size_t)nvb) val_batch.alloc(nvb);
+        }
+        // the epochs: nothing but launches on one stream
+        for (int e = 0; e < epochs; ++e) {
+            for (int bi = 0; bi < nb; ++bi) {
+                launch_step(perms.p + (size_t)e * n + (size_t)bi * B, B);
+                launch_update(rule, B, loss_acc.p + e, nullptr);
+            }
+            if (nvb > 0) {
+                launch_mse(vin.p, vout.p, nvb, B, val_tiles.p, nullptr);
+                hipLaunchKernelGGL(k_train_val_reduce, dim3(1), dim3(256), 0, stream, (const float*)val_tiles.p, nvb, tpb,
+                                   (float)(1.0 / ((double)B * net.dims[net.L])), val_batch.p, val_loss.p + e);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        std::vector<float> tl(epochs), vl(epochs);
+        HIP_CHECK(hipMemcpyAsync(tl.data(), loss_acc.p, (size_t)epochs * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (nvb > 0) HIP_CHECK(hipMemcpyAsync(vl.data(), val_loss.p, (size_t)epochs * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        for (int e = 0; e < epochs; ++e) {
+            train_loss[e] = nb > 0 ? (float)((double)tl[e] / nb) : nan;
+            val_loss_out[e] = nvb > 0 ? vl[e] : nan;
+        }
+    }
+
+    void gradients(const int32_t* idx_h, int B, float* grads_out, float* loss_out) {
+        REQUIRE(has_data, BBMPC_E_STATE, "trainer: bbmpc_trainer_gradients before bbmpc_trainer_set_data");
+        check_batch(B);
+        for (int i = 0; i < B; ++i) REQUIRE(idx_h[i] >= 0 && idx_h[i] < n_train, BBMPC_E_INVALID, "trainer: a row index outside [0, n_train)");
+        ensure_step_buffers(B);
+        if (idx.n < (size_t)B) idx.alloc(B);
+        if (grads.n < (size_t)net.n_params + 1) grads.alloc((size_t)net.n_params + 1);
+        HIP_CHECK(hipMemcpy(idx.p, idx_h, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+        launch_step(idx.p, B);
+        launch_update(TR_RULE_NONE, B, grads.p + net.n_params, grads.p);
+        std::vector<float> h((size_t)net.n_params + 1);
+        HIP_CHECK(hipMemcpyAsync(h.data(), grads.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        memcpy(grads_out, h.data(), (size_t)net.n_params * sizeof(float));
+        *loss_out = h[net.n_params];
+    }
+
+    void get_params(float* const* weights, float* const* biases) {
+        std::vector<float> h((size_t)net.n_params);
+        HIP_CHECK(hipMemcpyAsync(h.data(), theta.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (int l = 0; l < net.L; ++l) {
+            memcpy(weights[l], h.data() + net.woff[l], sizeof(float) * net.dims[l] * net.dims[l + 1]);
+            memcpy(biases[l], h.data() + net.boff[l], sizeof(float) * net.dims[l + 1]);
+        }
+    }
+
+    void residual_rms(const float* in, const float* out, int n, float* rms_out) {
+        REQUIRE(n >= 1, BBMPC_E_INVALID, "trainer: residual_rms needs at least one row");
+        const int D = net.dims[0], O = net.dims[net.L];
+        const int tiles = (n + TR_ROWS - 1) / TR_ROWS;
+        upload(rin, in, (size_t)n * D);
+        upload(rout, out, (size_t)n * O);
+        if (colsq.n < (size_t)tiles * O) colsq.alloc((size_t)tiles * O);
+        if (rms.n < (size_t)O) rms.alloc(O);
+        launch_mse(rin.p, rout.p, 1, n, nullptr, colsq.p);
+        hipLaunchKernelGGL(k_train_rms_reduce, dim3((O + 63) / 64), dim3(64), 0, stream, (const float*)colsq.p, tiles, O, (float)(1.0 / n), rms.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(rms_out, rms.p, (size_t)O * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+};
+
+}  // namespace bbmpc
+
+using bbmpc::Trainer;
+using bbmpc::TrainNet;
+
+struct bbmpc_trainer_s {
+    Trainer* t;
+};
+
+#define CHECK_TRAINER(h)                                                       \
+    if (!(h) || !(h)->t) throw HipError(BBMPC_E_INVALID, "null trainer");      \
+    DeviceGuard _device_guard((h)->t->device)
+
+extern "C" {
+
+int bbmpc_trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t* activations, int64_t* bytes) {
+    API_BEGIN
+    CHECK_PTR(bytes);
+    *bytes = 0;
+    REQUIRE(n_layers >= 1 && n_layers <= bbmpc::TR_MAX_LAYERS && dims && activations, BBMPC_E_INVALID, "trainer: n_layers outside [1, 8] or null arrays");
+    TrainNet n;
+    memset(&n, 0, sizeof(n));
+    n.L = n_layers;
+    for (int l = 0; l <= n_layers; ++l) {
+        REQUIRE(dims[l] >= 1, BBMPC_E_INVALID, "trainer: a layer width < 1");
+        n.dims[l] = dims[l];
+    }
+    for (int l = 0; l < n_layers; ++l) n.act[l] = activations[l];
+    bbmpc::train_lds_layout(n);
+    *bytes = (int64_t)n.lds_floats * 4;
+    API_END
+}
+
+int bbmpc_trainer_create(bbmpc_trainer* out, int32_t device, int32_t n_layers, const int32_t* dims, const int32_t* activations,
+                         const float* const* weights, const float* const* biases, int32_t rule, float learning_rate) {
+    API_BEGIN
+    CHECK_PTR(out);
+    *out = nullptr;
+    TrainNet n;
+    bbmpc::train_describe(n, n_layers, dims, activations);
+    CHECK_PTR(weights);
+    CHECK_PTR(biases);
+    for (int l = 0; l < n_layers; ++l) REQUIRE(weights[l] && biases[l], BBMPC_E_INVALID, "trainer: a null weight or bias array");
+    REQUIRE(rule == BBMPC_TRAIN_ADAM || rule == BBMPC_TRAIN_SGD || rule == BBMPC_TRAIN_RMSPROP, BBMPC_E_INVALID, "trainer: unknown update rule");
+    REQUIRE(std::isfinite(learning_rate) && learning_rate > 0.0f, BBMPC_E_INVALID, "trainer: learning_rate must be finite and positive");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        throw HipError(BBMPC_E_NO_DEVICE, "no HIP device available: this library has no CPU fallback");
+    REQUIRE(device < ndev, BBMPC_E_NO_DEVICE, "trainer: device out of range");
+    int dev = device;
+    if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
+    DeviceGuard guard(dev);
+    Trainer* t = new Trainer(n, dev, weights, biases, rule, (double)learning_rate);
+    *out = new bbmpc_trainer_s{t};
+    API_END
+}
+
+int bbmpc_trainer_destroy(bbmpc_trainer t) {
+    API_BEGIN
+    if (t) {
+        if (t->t) {
+            DeviceGuard g(t->t->device);
+            delete t->t;
+        }
+        delete t;
+    }
+    API_END
+}
+
+int bbmpc_trainer_set_data(bbmpc_trainer t, const float* train_in, const float* train_out, int32_t n_train, const float* val_in,
+                           const float* val_out, int32_t n_val) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    REQUIRE(n_train >= 0 && n_val >= 0, BBMPC_E_INVALID, "trainer: negative row count");
+    REQUIRE(n_train == 0 || (train_in && train_out), BBMPC_E_INVALID, "trainer: null training rows");
+    REQUIRE(n_val == 0 || (val_in && val_out), BBMPC_E_INVALID, "trainer: null validation rows");
+    t->t->set_data(train_in, train_out, n_train, val_in, val_out, n_val);
+    API_END
+}
+
+int bbmpc_trainer_fit(bbmpc_trainer t, int32_t epochs, int32_t batch_size, const int32_t* perms, uint64_t seed, float* train_loss_out,
+                      float* val_loss_out) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    CHECK_PTR(train_loss_out);
+    CHECK_PTR(val_loss_out);
+    t->t->fit(epochs, batch_size, perms, seed, train_loss_out, val_loss_out);
+    API_END
+}
+
+int bbmpc_trainer_get_params(bbmpc_trainer t, float* const* weights, float* const* biases) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    CHECK_PTR(weights);
+    CHECK_PTR(biases);
+    for (int l = 0; l < t->t->net.L; ++l) REQUIRE(weights[l] && biases[l], BBMPC_E_INVALID, "trainer: a null weight or bias array");
+    t->t->get_params(weights, biases);
+    API_END
+}
+
+int bbmpc_trainer_residual_rms(bbmpc_trainer t, const float* in, const float* out, int32_t n, float* rms_out) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    CHECK_PTR(in);
+    CHECK_PTR(out);
+    CHECK_PTR(rms_out);
+    t->t->residual_rms(in, out, n, rms_out);
+    API_END
+}
+
+int bbmpc_trainer_gradients(bbmpc_trainer t, const int32_t* idx, int32_t batch_size, float* grads_out, float* loss_out) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    CHECK_PTR(idx);
+    CHECK_PTR(grads_out);
+    CHECK_PTR(loss_out);
+    t->t->gradients(idx, batch_size, grads_out, loss_out);
+    API_END
+}
+
+}  // extern "C"

@@ -1,0 +1,459 @@
+// Training a Dense stack on the matrix cores (bbmpc_trainer_*): mini-batch MSE, backprop and the
+// Keras TF-2.0 update rules (adam / sgd / rmsprop) of dynamics_functions/_train_torch.DenseTrainer, as three kernels.
+//
+//   k_train_fwd_bwd      grid ceil(B / 16): a workgroup owns 16 rows of the batch.  It gathers them through the epoch's
+//                        permutation, runs the forward stack with EVERY layer's output tile resident in LDS, forms
+//                        delta_{L-1} = act'(y_L) * 2 (y_L - t) / (B O) and sweeps backwards: per layer its share of
+//                        dW_l = y_l^T delta_l (an MFMA product whose K extent is the tile's 16 rows), of
+//                        db_l = column sums of delta_l in row order, and g = delta_l W_l^T for the layer below.  Shares go
+//                        to part[tile][n_params], the tile's sum of squared errors to lossp[tile].  No atomics.
+//   k_train_update       one lane per parameter: adds the shares in ascending tile order, applies the rule (m, v and the
+//                        running powers b1^t, b2^t live on the device, the powers in double) and writes the parameter in
+//                        every layout the step kernel reads: the operand pack of W, the pack of W^T, the padded bias.
+//   k_train_forward_mse  forward only: per tile the squared error per output column and its sum (validation batches,
+//                        residual_rms).
+//
+// Every product is v_mfma_f32_16x16x4_f32 (fp32 in, fp32 accumulate).  Layer tiles use kernels_mlp.hpp's layout: a tile
+// array [T][64][4], lane l of tile t holding features 16 t + 4 (l >> 4) + {0..3} of row l & 15 -- the D fragment of one
+// product is the B operand of the next, in both sweeps.  Operand packs are mlp_pack_layer's [OT][IT][64][4]: lane l, slot s
+// of (ot, it) is M[16 it + 4 (l >> 4) + s][16 ot + (l & 15)], M = W for the forward sweep and W^T for the backward one,
+// zero where an index passes the matrix.
+//
+// delta_l overwrites y_{l+1} in place (y_{l+1} is dead once act' is taken and dW_{l+1} is out), so the backward sweep
+// needs ONE scratch tile array for g.  A layer's pre-activation is kept only for the codes whose derivative cannot be
+// rebuilt from the output (train_needs_pre: swish); the others use DenseTrainer's forms in y.
+//
+// Rows >= B of the last tile are never read from the dataset, and their delta is set to zero in every layer: their
+// shares are exact zeros.  Nothing depends on timing or on the grid: equal calls give equal bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "activations_grad.hpp"
+
+namespace bbmpc {
+
+typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int TR_MAX_LAYERS = 8;
+constexpr int TR_MAX_WIDTH = 512;
+constexpr int TR_MAX_BATCH = 4096;
+constexpr int TR_ROWS = 16;                      // batch rows per workgroup
+constexpr int TR_LDS_LIMIT = 159 * 1024;         // bytes, as the other kernels' carves
+constexpr int TR_SCRATCH = 64 + 1024;            // floats: 16 row indices (padded to 64) + one word per thread
+constexpr int TR_RULE_NONE = 0, TR_RULE_ADAM = 1, TR_RULE_SGD = 2, TR_RULE_RMSPROP = 3;      // BBMPC_TRAIN_*
+
+// activations whose derivative needs the pre-activation (act_grad's x): the forward sweep keeps that tile
+__host__ __device__ inline bool train_needs_pre(int act) { return act == ACT_SWISH; }
+
+// The network as the kernels see it.  theta is the parameter vector in natural order: W_0 .. W_{L-1} ([in][out] row
+// major), then b_0 .. b_{L-1}; woff / boff index it (and m, v, a gradient, a row of the share buffer).
+struct TrainNet {
+    int L;
+    int dims[TR_MAX_LAYERS + 1];
+    int tiles[TR_MAX_LAYERS + 1];                // ceil(dims / 16)
+    int act[TR_MAX_LAYERS];
+    int woff[TR_MAX_LAYERS], boff[TR_MAX_LAYERS];
+    int n_params;
+    int yoff[TR_MAX_LAYERS + 1];                 // LDS offsets (floats) of y_0 .. y_L
+    int zoff[TR_MAX_LAYERS];                     // ... of layer l's pre-activation, -1 when not kept
+    int goff, soff;                              // the adjoint scratch [Tmax][64][4]; TR_SCRATCH floats
+    int lds_floats;
+    int nw;                                      // waves per workgroup
+    float* wf[TR_MAX_LAYERS];                    // operand pack of W_l   [T_{l+1}][T_l][64][4]
+    float* wr[TR_MAX_LAYERS];                    // operand pack of W_l^T [T_l][T_{l+1}][64][4]
+    float* bp[TR_MAX_LAYERS];                    // b_l padded with zeros to 16 T_{l+1}
+};
+
+// LDS carve in floats:  256 * (sum_{l=0..L} T_l  +  sum over swish layers of T_{l+1}  +  max_l T_l) + TR_SCRATCH,
+// T_l = ceil(dims[l] / 16): the resident layer tiles, the kept pre-activations, the adjoint scratch, the row / loss words.
+__host__ __device__ inline void train_lds_layout(TrainNet& n) {
+    int o = 0, tmax = 1;
+    for (int l = 0; l <= n.L; ++l) {
+        n.tiles[l] = (n.dims[l] + 15) / 16;
+        n.yoff[l] = o;
+        o += n.tiles[l] * 256;
+        tmax = tmax > n.tiles[l] ? tmax : n.tiles[l];
+    }
+    for (int l = 0; l < n.L; ++l) {
+        n.zoff[l] = -1;
+        if (train_needs_pre(n.act[l])) {
+            n.zoff[l] = o;
+            o += n.tiles[l + 1] * 256;
+        }
+    }
+    n.goff = o; o += tmax * 256;
+    n.soff = o; o += TR_SCRATCH;
+    n.lds_floats = o;
+    n.nw = tmax < 4 ? 4 : (tmax > 16 ? 16 : tmax);
+}
+
+// offsets of parameter (i, o) of layer l in the two packs
+__host__ __device__ inline size_t train_wf_index(int IT, int i, int o) {
+    return (((size_t)(o >> 4) * IT + (i >> 4)) * 64 + (((i & 15) >> 2) * 16 + (o & 15))) * 4 + (i & 3);
+}
+__host__ __device__ inline size_t train_wr_index(int OT, int i, int o) {      // W^T: input o, output i
+    return (((size_t)(i >> 4) * OT + (o >> 4)) * 64 + (((o & 15) >> 2) * 16 + (i & 15))) * 4 + (o & 3);
+}
+
+// The epoch permutations bbmpc_trainer_fit draws when it is given none: Fisher-Yates from the top, j = floor(u (i + 1) /
+// 2^64) with u the next output of splitmix64, whose state starts at seed ^ (0xD1B54A32D192ED03 * (epoch + 1)).
+inline uint64_t train_splitmix64(uint64_t& s) {
+    s += 0x9E3779B97F4A7C15ull;
+    uint64_t z = s;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+inline void train_draw_permutation(uint64_t seed, int epoch, int n, int32_t* out) {
+    uint64_t s = seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(epoch + 1));
+    for (int i = 0; i < n; ++i) out[i] = i;
+    for (int i = n - 1; i >= 1; --i) {
+        const uint64_t u = train_splitmix64(s);
+        const int j = (int)(uint64_t)(((unsigned __int128)u * (uint64_t)(i + 1)) >> 64);
+        const int32_t t = out[i];
+        out[i] = out[j];
+        out[j] = t;
+    }
+}
+
+struct TrainStepArgs {
+    TrainNet n;
+    const float* din;                            // [rows][dims[0]]
+    const float* dout;                           // [rows][dims[L]]
+    const int* idx;                              // [B] dataset rows of this batch; null: rows row0 .. row0 + B - 1
+    int row0;
+    int B;
+    float gscale;                                // 2 / (B O)
+    float* part;                                 // [tiles][n_params]
+    float* lossp;                                // [tiles] sum of squared errors
+};
+
+struct TrainMseArgs {
+    TrainNet n;
+    const float* din;
+    const float* dout;
+    int B;                                       // rows per batch; tile blockIdx.x = (batch, tile of the batch)
+    int tiles_per_batch;
+    float* tile_loss;                            // [batches * tiles_per_batch] or null
+    float* colsq;                                // [batches * tiles_per_batch][O] or null
+};
+
+struct TrainUpdateArgs {
+    TrainNet n;
+    float* theta;
+    float* m;
+    float* v;
+    const float* part;
+    const float* lossp;
+    int ntiles;
+    int rule;
+    float lr, b1, b2, omb1, omb2, rho, omrho, eps;
+    double lr_d, b1_d, b2_d;
+    double* pows;                                // [2][2]: (b1^t, b2^t) read at [parity], written at [parity ^ 1]
+    int parity;
+    float inv_count;                             // 1 / (B O)
+    float* loss_acc;                             // += the batch loss (TR_RULE_NONE: = )
+    float* grads_out;                            // TR_RULE_NONE: the summed gradient [n_params]
+};
+
+#ifdef BBMPC_TU_TRAIN
+
+__device__ __forceinline__ int tr_addr(int f, int p) {                   // feature f of row p in a tile array
+    return (((f >> 4) * 64) + (((f & 15) >> 2) * 16 + p)) * 4 + (f & 3);
+}
+
+// d act / dx from the layer's output y (z: the pre-activation, read only where train_needs_pre): DenseTrainer._act_grad's
+// forms.  relu / elu / selu / leaky_relu test y > 0, which is x > 0; the three below cannot be asked through act_grad
+// without x.
+__device__ __forceinline__ float train_act_grad(float y, float z, int act) {
+    switch (act) {
+    case ACT_SOFTPLUS: return 1.0f - __builtin_amdgcn_exp2f(-BB_LOG2E * y);           // sigma(x) = 1 - e^-y
+    case ACT_HARD_SIGMOID: return (y > 0.0f && y < 1.0f) ? 0.2f : 0.0f;
+    case ACT_RELU6: return (y > 0.0f && y < 6.0f) ? 1.0f : 0.0f;
+    case ACT_SWISH: return act_grad(z, y, act);
+    default: return act_grad(y, y, act);
+    }
+}
+
+// acc += M[ot] . in over IT k tiles; W points at the pack's (ot, 0, lane)
+__device__ __forceinline__ tr_f32x4 tr_tile_product(const tr_f32x4* __restrict__ W, int in_off, int IT, int lane, tr_f32x4 acc) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+#pragma unroll 4
+    for (int it = 0; it < IT; ++it) {
+        const tr_f32x4 b = *reinterpret_cast<const tr_f32x4*>(smem + in_off + (it * 64 + lane) * 4);
+        const tr_f32x4 a = W[(size_t)it * 64];
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// The tile's dataset rows (scratch words 0 .. 15, -1 past the batch) and its input tile y_0.  Ends with a barrier.
+__device__ __forceinline__ void tr_load_input(const TrainNet& n, const float* din, const int* idx, int row0, int n0, int valid,
+                                              int tid, int nthr) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    int* rows = reinterpret_cast<int*>(smem + n.soff);
+    const int D = n.dims[0];
+    if (tid < TR_ROWS) rows[tid] = tid < valid ? (idx ? idx[n0 + tid] : row0 + n0 + tid) : -1;
+    for (int i = tid; i < n.tiles[0] * 256; i += nthr) smem[n.yoff[0] + i] = 0.0f;
+    __syncthreads();
+    for (int i = tid; i < TR_ROWS * D; i += nthr) {
+        const int pp = i / D, f = i - pp * D;
+        const int r = rows[pp];
+        if (r >= 0) smem[n.yoff[0] + tr_addr(f, pp)] = din[(size_t)r * D + f];
+    }
+    __syncthreads();
+}
+
+// The forward stack: y_{l+1} = act(y_l W_l + b_l) for every layer, all resident.  Ends with a barrier.
+__device__ __forceinline__ void tr_forward(const TrainNet& n, int wave, int lane) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    for (int l = 0; l < n.L; ++l) {
+        const int IT = n.tiles[l], OT = n.tiles[l + 1], a = n.act[l];
+        const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wf[l]);
+        for (int ot = wave; ot < OT; ot += n.nw) {
+            tr_f32x4 acc = *reinterpret_cast<const tr_f32x4*>(n.bp[l] + ot * 16 + (lane >> 4) * 4);     // the bias enters as C
+            acc = tr_tile_product(W + (size_t)ot * IT * 64 + lane, n.yoff[l], IT, lane, acc);
+            if (n.zoff[l] >= 0) *reinterpret_cast<tr_f32x4*>(smem + n.zoff[l] + (ot * 64 + lane) * 4) = acc;
+            acc.x = apply_act(acc.x, a); acc.y = apply_act(acc.y, a); acc.z = apply_act(acc.z, a); acc.w = apply_act(acc.w, a);
+            *reinterpret_cast<tr_f32x4*>(smem + n.yoff[l + 1] + (ot * 64 + lane) * 4) = acc;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const TrainNet& n = q.n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = n.nw, nthr = nw * 64;
+    const int n0 = blockIdx.x * TR_ROWS;
+    const int valid = q.B - n0 < TR_ROWS ? q.B - n0 : TR_ROWS;
+    const int L = n.L, O = n.dims[L];
+    const int p = lane & 15, g = lane >> 4;
+    const int* rows = reinterpret_cast<const int*>(smem + n.soff);
+    float* words = smem + n.soff + 64;                              // one word per thread
+    float* part = q.part + (size_t)blockIdx.x * n.n_params;
+
+    tr_load_input(n, q.din, q.idx, q.row0, n0, valid, tid, nthr);
+    tr_forward(n, wave, lane);
+
+    // ---- delta_{L-1} = act'(y_L) * 2 (y_L - t) / (B O), in place; each thread's squared errors go to its word
+    {
+        const int a = n.act[L - 1];
+        const int r = rows[p];
+        float sq = 0.0f;
+        for (int t = wave; t < n.tiles[L]; t += nw) {
+            float* yp = smem + n.yoff[L] + (t * 64 + lane) * 4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int f = 16 * t + 4 * g + c;
+                float d = 0.0f;
+                if (r >= 0 && f < O) {
+                    const float y = yp[c];
+                    const float z = n.zoff[L - 1] >= 0 ? smem[n.zoff[L - 1] + (t * 64 + lane) * 4 + c] : y;
+                    const float diff = y - q.dout[(size_t)r * O + f];
+                    sq = sq + diff * diff;
+                    d = train_act_grad(y, z, a) * (diff * q.gscale);
+                }
+                yp[c] = d;
+            }
+        }
+        words[tid] = sq;
+    }
+    __syncthreads();
+    // ---- the tile's sum of squared errors: wave 0, waves ascending per lane, then lane groups, then rows
+    if (wave == 0) {
+        float s = 0.0f;
+        for (int w = 0; w < nw; ++w) s = s + words[w * 64 + lane];
+        const float s0 = __shfl(s, p), s1 = __shfl(s, 16 + p), s2 = __shfl(s, 32 + p), s3 = __shfl(s, 48 + p);
+        const float rs = ((s0 + s1) + s2) + s3;
+        float tot = 0.0f;
+        for (int j = 0; j < TR_ROWS; ++j) tot = tot + __shfl(rs, j);
+        if (lane == 0) q.lossp[blockIdx.x] = tot;
+    }
+
+    // ---- backward sweep: delta_l sits in y_{l+1}'s tiles
+    for (int l = L - 1; l >= 0; --l) {
+        const int IT = n.tiles[l], OT = n.tiles[l + 1], in = n.dims[l], out = n.dims[l + 1];
+        // dW_l = y_l^T delta_l: K = the 16 rows, row r = 4 s + g in product s
+        for (int pr = wave; pr < IT * OT; pr += nw) {
+            const int it = pr / OT, ot = pr - it * OT;
+            const float* xa = smem + n.yoff[l] + (it * 64 + (p >> 2) * 16) * 4 + (p & 3);
+            const float* db = smem + n.yoff[l + 1] + (ot * 64 + (p >> 2) * 16) * 4 + (p & 3);
+            tr_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[(4 * s + g) * 4], db[(4 * s + g) * 4], acc, 0, 0, 0);
+            const int fo = 16 * ot + p;
+            if (fo < out) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int fi = 16 * it + 4 * g + c;
+                    if (fi < in) part[n.woff[l] + (size_t)fi * out + fo] = acc[c];
+                }
+            }
+        }
+        // db_l = column sums of delta_l in row order
+        for (int o = tid; o < out; o += nthr) {
+            const float* dp = smem + n.yoff[l + 1] + tr_addr(o, 0);
+            float s = 0.0f;
+#pragma unroll
+            for (int r = 0; r < TR_ROWS; ++r) s = s + dp[r * 4];
+            part[n.boff[l] + o] = s;
+        }
+        if (l == 0) break;
+        // g = delta_l W_l^T
+        {
+            const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wr[l]);
+            for (int ot = wave; ot < IT; ot += nw) {
+                tr_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+                acc = tr_tile_product(W + (size_t)ot * OT * 64 + lane, n.yoff[l + 1], OT, lane, acc);
+                *reinterpret_cast<tr_f32x4*>(smem + n.goff + (ot * 64 + lane) * 4) = acc;
+            }
+        }
+        __syncthreads();
+        // delta_{l-1} = act'(y_l) * g, in place of y_l; zero past the batch and past the layer's width
+        {
+            const int a = n.act[l - 1];
+            const bool live = rows[p] >= 0;
+            for (int t = wave; t < IT; t += nw) {
+                float* yp = smem + n.yoff[l] + (t * 64 + lane) * 4;
+                const float* gp = smem + n.goff + (t * 64 + lane) * 4;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int f = 16 * t + 4 * g + c;
+                    float d = 0.0f;
+                    if (live && f < in) {
+                        const float y = yp[c];
+                        const float z = n.zoff[l - 1] >= 0 ? smem[n.zoff[l - 1] + (t * 64 + lane) * 4 + c] : y;
+                        d = train_act_grad(y, z, a) * gp[c];
+                    }
+                    yp[c] = d;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Forward only on rows b * B + 16 t .. of batch b (tile t of the batch): squared errors per output column, and their sum.
+__global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const TrainNet& n = q.n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = n.nw * 64;
+    const int batch = blockIdx.x / q.tiles_per_batch, tile = blockIdx.x - batch * q.tiles_per_batch;
+    const int n0 = tile * TR_ROWS;
+    const int valid = q.B - n0 < TR_ROWS ? q.B - n0 : TR_ROWS;
+    const int L = n.L, O = n.dims[L];
+    const int* rows = reinterpret_cast<const int*>(smem + n.soff);
+    float* words = smem + n.soff + 64;
+    tr_load_input(n, q.din, nullptr, batch * q.B, n0, valid, tid, nthr);
+    tr_forward(n, wave, lane);
+    for (int o = tid; o < 1024; o += nthr) {
+        float s = 0.0f;
+        if (o < O)
+            for (int r = 0; r < valid; ++r) {
+                const float d = smem[n.yoff[L] + tr_addr(o, r)] - q.dout[(size_t)rows[r] * O + o];
+                s = s + d * d;
+            }
+        words[o] = s;
+        if (q.colsq && o < O) q.colsq[(size_t)blockIdx.x * O + o] = s;
+    }
+    __syncthreads();
+    if (wave == 0 && q.tile_loss) {
+        float s = 0.0f;
+        for (int o = lane; o < O; o += 64) s = s + words[o];
+        float tot = 0.0f;
+        for (int j = 0; j < 64; ++j) tot = tot + __shfl(s, j);
+        if (lane == 0) q.tile_loss[blockIdx.x] = tot;
+    }
+}
+
+// val_out[0] = mean over the batches of (sum of the batch's tile losses in tile order) / (B O); NaN without a batch
+__global__ void k_train_val_reduce(const float* tile_loss, int batches, int tiles_per_batch, float inv_count, float* batch_mse, float* val_out) {
+    for (int b = threadIdx.x; b < batches; b += blockDim.x) {
+        float s = 0.0f;
+        for (int t = 0; t < tiles_per_batch; ++t) s = s + tile_loss[(size_t)b * tiles_per_batch + t];
+        batch_mse[b] = s * inv_count;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.0f;
+        for (int b = 0; b < batches; ++b) s = s + batch_mse[b];
+        val_out[0] = s / (float)batches;
+    }
+}
+
+// rms_out[o] = sqrt(sum over tiles (ascending) of colsq[tile][o] / rows)
+__global__ void k_train_rms_reduce(const float* colsq, int tiles, int O, float inv_rows, float* rms_out) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= O) return;
+    float s = 0.0f;
+    for (int t = 0; t < tiles; ++t) s = s + colsq[(size_t)t * O + o];
+    rms_out[o] = sqrtf(s * inv_rows);
+}
+
+__global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
+    const TrainNet& n = q.n;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        float s = 0.0f;
+        for (int t = 0; t < q.ntiles; ++t) s = s + q.lossp[t];
+        const float loss = s * q.inv_count;
+        if (q.rule == TR_RULE_NONE) q.loss_acc[0] = loss;
+        else q.loss_acc[0] = q.loss_acc[0] + loss;
+    }
+    double b1t = 1.0, b2t = 1.0;
+    if (q.rule == TR_RULE_ADAM) {
+        b1t = q.pows[q.parity * 2 + 0] * q.b1_d;
+        b2t = q.pows[q.parity * 2 + 1] * q.b2_d;
+        if (i == 0) {
+            q.pows[(q.parity ^ 1) * 2 + 0] = b1t;
+            q.pows[(q.parity ^ 1) * 2 + 1] = b2t;
+        }
+    }
+    if (i >= n.n_params) return;
+    float gsum = 0.0f;
+    for (int t = 0; t < q.ntiles; ++t) gsum = gsum + q.part[(size_t)t * n.n_params + i];
+    if (q.rule == TR_RULE_NONE) {
+        q.grads_out[i] = gsum;
+        return;
+    }
+    float w = q.theta[i];
+    if (q.rule == TR_RULE_SGD) {
+        w = w + (-q.lr) * gsum;
+    } else if (q.rule == TR_RULE_RMSPROP) {
+        const float v = q.rho * q.v[i] + q.omrho * (gsum * gsum);
+        q.v[i] = v;
+        w = w + (-q.lr) * (gsum / (sqrtf(v) + q.eps));
+    } else {
+        const float lr_t = (float)(q.lr_d * sqrt(1.0 - b2t) / (1.0 - b1t));
+        const float m = q.b1 * q.m[i] + q.omb1 * gsum;
+        const float v = q.b2 * q.v[i] + q.omb2 * (gsum * gsum);
+        q.m[i] = m;
+        q.v[i] = v;
+        w = w + (-lr_t) * (m / (sqrtf(v) + q.eps));
+    }
+    q.theta[i] = w;
+    // every layout the step kernel reads
+    const int L = n.L;
+    if (i >= n.boff[0]) {
+        int l = L - 1;
+        while (i < n.boff[l]) --l;
+        n.bp[l][i - n.boff[l]] = w;
+    } else {
+        int l = L - 1;
+        while (i < n.woff[l]) --l;
+        const int out = n.dims[l + 1];
+        const int k = i - n.woff[l];
+        const int fi = k / out, fo = k - fi * out;
+        n.wf[l][train_wf_index(n.tiles[l], fi, fo)] = w;
+        n.wr[l][train_wr_index(n.tiles[l + 1], fi, fo)] = w;
+    }
+}
+
+#endif  // BBMPC_TU_TRAIN
+
+}  // namespace bbmpc

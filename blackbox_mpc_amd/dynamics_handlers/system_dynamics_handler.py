@@ -231,7 +231,7 @@ class SystemDynamicsHandler:
 
     def train(self, observations_trajectories, actions_trajectories, rewards_trajectories, validation_split=0.2,
               batch_size=128, learning_rate=1e-3, epochs=30, nn_optimizer=None, *, device=None, seed=None,
-              split_mask=None, permutations=None, bootstrap_indices=None):
+              split_mask=None, permutations=None, bootstrap_indices=None, backend="torch"):
         """Reference signature (:163-166); `nn_optimizer`: None / "Adam" / "SGD" / "RMSprop" or a class of that name
         (the reference's callers only ever pass tf.keras.optimizers.Adam).  Keyword-only extras: `device` (default: the GPU -- training on the
         host has to be asked for explicitly with device="cpu"), and the injected random draws `split_mask`,
@@ -239,7 +239,11 @@ class SystemDynamicsHandler:
         its own bootstrap resample of the training rows (`_train_ensemble`; `bootstrap_indices` injects the resamples).
         A ProbabilisticMLP (or an ensemble of them) is fitted, mean and log-variance head together, on the Gaussian
         negative log-likelihood: training_loss / validation_loss (and the member lists) then hold the NLL, while
-        residual_std() stays the mean network's residual."""
+        residual_std() stays the mean network's residual.  `backend`: "torch" (DenseTrainer, the default) or "hip"
+        (dynamics_functions/_train_hip.HipDenseTrainer: the hand-written training kernels, GPU only, plain MSE models --
+        a model with a log-variance head is refused by name)."""
+        from ..dynamics_functions._train_hip import check_backend, dense_trainer
+        check_backend(backend)
         if self._is_true_model:
             raise Exception("the true model has nothing to train")
         # the reference instantiates `nn_optimizer(learning_rate=learning_rate)` (:261): a Keras optimizer CLASS (or its
@@ -250,8 +254,11 @@ class SystemDynamicsHandler:
         fn = self._dynamics_function
         if fn is None or not hasattr(fn, "weights"):
             raise Exception("train() needs a DeterministicMLP dynamics function")
-        import torch
-        if device is None:
+        if backend == "hip" and getattr(fn, "logvar_heads", None):
+            raise ValueError("backend='hip' fits plain Dense stacks (MSE): %s has a log-variance head (Gaussian NLL) and "
+                             "trains with backend='torch'" % type(fn).__name__)
+        if device is None and backend == "torch":
+            import torch
             if not torch.cuda.is_available():
                 raise RuntimeError("SystemDynamicsHandler.train runs on the GPU and none is visible "
                                    "(pass device='cpu' explicitly to train on the host)")
@@ -264,15 +271,14 @@ class SystemDynamicsHandler:
             self._first_time = False
         tin, tout = self._normalize_data(self._model_training_in, self._model_training_out)
         vin, vout = self._normalize_data(self._model_validation_in, self._model_validation_out)
-        from ..dynamics_functions._train_torch import DenseTrainer
         if hasattr(fn, "members"):
             self._train_ensemble(fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
-                                 bootstrap_indices)
+                                 bootstrap_indices, backend)
             return self._after_training()
         if bootstrap_indices is not None:
             raise ValueError("bootstrap_indices are the resamples of an EnsembleMLP's members")
-        trainer = DenseTrainer(fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule,
-                               logvar_head=_logvar_head(fn))               # fresh optimizer per call (:258)
+        trainer = dense_trainer(backend, fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule,
+                                logvar_head=_logvar_head(fn))              # fresh optimizer per call (:258)
         self.training_loss, self.validation_loss = trainer.fit(tin, tout, vin, vout, epochs, batch_size,
                                                                permutations=permutations, generator_seed=seed)
         self._residual_rms = trainer.residual_rms(vin, vout)              # normalised target units; residual_std() scales it
@@ -291,7 +297,7 @@ class SystemDynamicsHandler:
         return
 
     def _train_ensemble(self, fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
-                        bootstrap_indices):
+                        bootstrap_indices, backend="torch"):
         """The members of an EnsembleMLP on the (normalised) rows train() prepared -- statistics, split and the
         freeze-after-first rule are shared.  Member e is fitted by a fresh DenseTrainer on a bootstrap resample of the
         training rows: n_train indices drawn with replacement, `bootstrap_indices[e]` when given, else from
@@ -299,7 +305,7 @@ class SystemDynamicsHandler:
         `permutations` are [E][epochs] (one list per member) or [epochs] (shared by the members).
         training_loss / validation_loss stay member 0's; the per-member lists go to member_training_loss /
         member_validation_loss, and residual_std() becomes the RMS over members of the members' validation residuals."""
-        from ..dynamics_functions._train_torch import DenseTrainer
+        from ..dynamics_functions._train_hip import dense_trainer
         n, members = tin.shape[0], fn.members
         if bootstrap_indices is not None:
             if len(bootstrap_indices) != len(members):
@@ -319,8 +325,8 @@ class SystemDynamicsHandler:
                 perms = [rng.permutation(n) for _ in range(epochs)]
             else:
                 perms = permutations[e] if per_member else permutations
-            trainer = DenseTrainer(member.weights, member.biases, member.activation_codes, device, learning_rate=learning_rate,
-                                   rule=rule, logvar_head=_logvar_head(member))
+            trainer = dense_trainer(backend, member.weights, member.biases, member.activation_codes, device,
+                                    learning_rate=learning_rate, rule=rule, logvar_head=_logvar_head(member))
             tl, vl = trainer.fit(tin[idx], tout[idx], vin, vout, epochs, batch_size, permutations=perms, generator_seed=seed)
             self.member_training_loss.append(tl)
             self.member_validation_loss.append(vl)

@@ -104,12 +104,15 @@ class LearnedValueMLP:
 
     # -- training -------------------------------------------------------------------------------------------------------
     def train(self, states, targets, epochs=30, batch_size=128, learning_rate=1e-3, validation_split=0.2, device=None,
-              seed=None, normalize=True):
+              seed=None, normalize=True, backend="torch"):
         """Fit MSE on normalised targets with Keras-Adam (dynamics_functions/_train_torch.DenseTrainer, on `device`: the
         GPU when PyTorch sees one, else the CPU).  states [B, S], targets [B].  The statistics are refreshed from exactly
         these rows and the version is bumped, so every engine that holds the network uploads it again before its next
-        computation.  Returns (train_loss [epochs], validation_loss [epochs])."""
-        from ..dynamics_functions._train_torch import DenseTrainer
+        computation.  Returns (train_loss [epochs], validation_loss [epochs]).
+        backend: "torch" (the default) or "hip" -- the hand-written training kernels
+        (dynamics_functions/_train_hip.HipDenseTrainer; GPU only, permutations drawn by the library from `seed`)."""
+        from ..dynamics_functions._train_hip import check_backend, dense_trainer
+        check_backend(backend)
         x = np.asarray(states, np.float32).reshape(-1, self.dim_S)
         y = np.asarray(targets, np.float32).reshape(-1, 1)
         if x.shape[0] != y.shape[0]:
@@ -126,10 +129,10 @@ class LearnedValueMLP:
         order = rng.permutation(x.shape[0])
         n_val = int(x.shape[0] * float(validation_split))
         val, trn = order[:n_val], order[n_val:]
-        if device is None:
+        if device is None and backend == "torch":
             import torch
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        tr = DenseTrainer(self.weights, self.biases, self.activation_codes, device, learning_rate=learning_rate)
+        tr = dense_trainer(backend, self.weights, self.biases, self.activation_codes, device, learning_rate=learning_rate)
         bs = max(1, min(int(batch_size), len(trn)))
         losses = tr.fit(xn[trn], yn[trn], xn[val], yn[val], int(epochs), bs,
                         generator_seed=None if seed is None else int(seed))

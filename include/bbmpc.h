@@ -776,6 +776,60 @@ int bbmpc_comm_info(bbmpc_handle h, int32_t* nranks, int32_t* rank, int32_t* syn
 int bbmpc_gather_wait(bbmpc_handle h, int32_t slot, int32_t host_block);
 int bbmpc_comm_destroy(bbmpc_handle h);
 
+/* ---- training a Dense stack ------------------------------------------------------------------------
+ * Counterpart of SystemDynamicsHandler._training_algorithm (dynamics_handlers/system_dynamics_handler.py:243-290) with
+ * DeterministicMLP.get_loss (Keras MeanSquaredError) and tf.keras.optimizers.{Adam, SGD, RMSprop}(learning_rate) at their
+ * TF-2.0 defaults, in hand-written kernels (csrc/kernels_train.hpp).  A trainer is its own opaque handle, independent of
+ * bbmpc_handle: training needs no planning configuration.  One trainer = one caller thread at a time.
+ *
+ * The rule.  Rows are already normalised: train_in [n_train][dims[0]], train_out [n_train][dims[n_layers]], val_in, val_out.
+ * One epoch takes the batches perm[s .. s + B), s = 0, B, 2B, ... and drops the remainder.  Loss = mean over the batch's
+ * B * dims[n_layers] elements of (f(x) - y)^2.  Per batch one update:
+ *   BBMPC_TRAIN_ADAM     m = 0.9 m + 0.1 g;  v = 0.999 v + 0.001 g^2;  lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t) (the powers
+ *                        carried in double);  w -= lr_t m / (sqrt(v) + 1e-7)
+ *   BBMPC_TRAIN_SGD      w -= lr g
+ *   BBMPC_TRAIN_RMSPROP  v = 0.9 v + 0.1 g^2;  w -= lr g / (sqrt(v) + 1e-7)
+ * m, v and t belong to the trainer and go on from one bbmpc_trainer_fit to the next.  train_loss_out[e] = mean of epoch e's
+ * batch losses (NaN without a full batch); val_loss_out[e] = mean of the per-batch MSEs over the floor(n_val / B) full batches
+ * val[0 .. B), val[B .. 2B), ... after the epoch (NaN without one).  Equal calls from equal starts give equal bits.
+ * Out of scope: log-variance heads / Gaussian NLL.
+ *
+ * Layouts as bbmpc_set_mlp: Dense kernels [in, out] row-major, biases [out], dims has n_layers + 1 entries (so the widths
+ * chain by construction), any BBMPC_ACT_* code per layer.  device: HIP ordinal, -1 = current.
+ * Refused before anything is allocated -- BBMPC_E_UNSUPPORTED: n_layers > 8, a width > 512, a network whose LDS carve
+ * (bbmpc_trainer_lds_bytes) passes 159 KiB; BBMPC_E_INVALID: NULL pointers, n_layers < 1, a width < 1, an unknown activation or
+ * rule, learning_rate not finite or not positive; BBMPC_E_NO_DEVICE. */
+#define BBMPC_TRAIN_ADAM    1
+#define BBMPC_TRAIN_SGD     2
+#define BBMPC_TRAIN_RMSPROP 3
+typedef struct bbmpc_trainer_s* bbmpc_trainer;
+int bbmpc_trainer_create(bbmpc_trainer* out, int32_t device, int32_t n_layers, const int32_t* dims, const int32_t* activations,
+                         const float* const* weights, const float* const* biases, int32_t rule, float learning_rate);
+int bbmpc_trainer_destroy(bbmpc_trainer t);     /* NULL is fine */
+/* The step kernel's LDS carve in bytes, 4 * (256 * (sum_{l=0..L} T_l + sum over swish layers of T_{l+1} + max_l T_l) + 1088),
+ * T_l = ceil(dims[l] / 16).  Host arithmetic only: no device needed. */
+int bbmpc_trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t* activations, int64_t* bytes);
+/* The dataset: host rows, copied to device memory once.  Replaces the previous one.  n_val may be 0. */
+int bbmpc_trainer_set_data(bbmpc_trainer t, const float* train_in, const float* train_out, int32_t n_train, const float* val_in,
+                           const float* val_out, int32_t n_val);
+/* `epochs` epochs at batch size B.  perms: [epochs][n_train] int32 row indices, one permutation per epoch, or NULL -- then the
+ * library draws them from `seed`: Fisher-Yates from the top, j = floor(u (i + 1) / 2^64) for i = n_train - 1 .. 1 with u the
+ * next splitmix64 output, the generator's state starting at seed ^ (0xD1B54A32D192ED03 * (epoch + 1)).  Every epoch's
+ * permutation is on the device before the first step; an epoch is nothing but kernel launches on the trainer's stream, and
+ * the losses [epochs] are read once at the end.  BBMPC_E_STATE before bbmpc_trainer_set_data; BBMPC_E_UNSUPPORTED: batch_size
+ * outside [1, 4096]; BBMPC_E_INVALID: epochs < 1, NULL outputs, a permutation entry outside [0, n_train).  A refused call
+ * leaves the trainer as it was. */
+int bbmpc_trainer_fit(bbmpc_trainer t, int32_t epochs, int32_t batch_size, const int32_t* perms, uint64_t seed, float* train_loss_out,
+                      float* val_loss_out);
+/* The current parameters (before any fit: the initial ones, bit for bit). */
+int bbmpc_trainer_get_params(bbmpc_trainer t, float* const* weights, float* const* biases);
+/* Per-output RMS of (out - prediction) over n >= 1 host rows: rms_out [dims[n_layers]]. */
+int bbmpc_trainer_residual_rms(bbmpc_trainer t, const float* in, const float* out, int32_t n, float* rms_out);
+/* Test window: loss and gradient of the batch made of training rows idx[0 .. batch_size), by exactly the step's kernels,
+ * without updating anything.  grads_out holds every parameter in the order W_0 .. W_{L-1} ([in][out] row-major), b_0 ..
+ * b_{L-1}.  Refusals as bbmpc_trainer_fit; an index outside [0, n_train) is BBMPC_E_INVALID. */
+int bbmpc_trainer_gradients(bbmpc_trainer t, const int32_t* idx, int32_t batch_size, float* grads_out, float* loss_out);
+
 #ifdef __cplusplus
 }
 #endif
