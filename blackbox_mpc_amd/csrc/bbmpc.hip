@@ -1428,23 +1428,14 @@ __global__ void k_dump_pso_scalars(OptArgs p, float* out) {
 
 void Engine::dump_noise(int kind, int control_step, int iteration, float* out, int64_t count) {
     int n = auto_split > 1 ? N * auto_split : N, a = A, hu = HU;       // (draws are keyed by the global particle)
-    if (kind == BBMPC_NOISE_PROCESS) {
-        dump_process_noise(control_step, iteration, out, count);
-        return;
-    }
-    if (kind == BBMPC_NOISE_POLICY) {
-        dump_policy_noise(control_step, iteration, out, count);
-        return;
-    }
+    if (kind == BBMPC_NOISE_PROCESS) return dump_process_noise(control_step, iteration, out, count);
+    if (kind == BBMPC_NOISE_POLICY) return dump_policy_noise(control_step, iteration, out, count);
     RngKey kk = key((uint32_t)control_step);
     if (kind == BBMPC_NOISE_PSO_SCALARS) {
         REQUIRE(count == 2, BBMPC_E_INVALID, "dump_noise: PSO scalars are [2] per (control step, iteration)");
-        DevBuf<float> tmp;
-        tmp.alloc(2);
-        hipLaunchKernelGGL(k_dump_pso_scalars, dim3(1), dim3(1), 0, stream, opt_args((uint32_t)control_step, (uint32_t)iteration), tmp.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out, tmp.p, 8, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+        stage_read_back(*this, out, 2, [&](float* d) {
+            hipLaunchKernelGGL(k_dump_pso_scalars, dim3(1), dim3(1), 0, stream, opt_args((uint32_t)control_step, (uint32_t)iteration), d);
+        });
         return;
     }
     if (kind == BBMPC_NOISE_EXPLORATION) {
@@ -1453,13 +1444,10 @@ void Engine::dump_noise(int kind, int control_step, int iteration, float* out, i
     }
     const int64_t total = (int64_t)n * a * hu;
     REQUIRE(count == total, BBMPC_E_INVALID, "dump_noise: wrong element count");
-    DevBuf<float> tmp;
-    tmp.alloc((size_t)total);
-    hipLaunchKernelGGL(k_dump_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, kk, (uint32_t)kind,
-                       (uint32_t)iteration, n, a, hu, cfg.agent_offset, tmp.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, tmp.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    stage_read_back(*this, out, (size_t)total, [&](float* d) {
+        hipLaunchKernelGGL(k_dump_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, kk, (uint32_t)kind,
+                           (uint32_t)iteration, n, a, hu, cfg.agent_offset, d);
+    });
 }
 
 void Engine::get_trace(int it, int item, void* out, int64_t bytes) {
@@ -1714,25 +1702,14 @@ static void process_io(Engine& e, int which, const float* a, const float* b, int
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
     const int S = e.S, U = e.U;
     const size_t na = (size_t)batch * S, nb = (size_t)batch * (which == 0 ? U : S), no = (size_t)batch * (which == 0 ? S + U : S);
-    const size_t nst = stats ? (size_t)4 * S + 2 * U : 0;
-    if (e.d_step_b.n < na + nb + no + nst) e.d_step_b.alloc(na + nb + no + nst);
-    float* da = e.d_step_b.p; float* db = da + na; float* dout = db + nb; float* dst = dout + no;
-    HIP_CHECK(hipMemcpyAsync(da, a, na * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(db, b, nb * 4, hipMemcpyHostToDevice, e.stream));
-    if (stats) {
-        std::vector<float> st;
-        const int lens[6] = {S, S, U, U, S, S};
-        for (int i = 0; i < 6; ++i) {
-            if (!stats[i]) throw HipError(BBMPC_E_INVALID, "null statistics vector");
-            st.insert(st.end(), stats[i], stats[i] + lens[i]);
-        }
-        HIP_CHECK(hipMemcpy(dst, st.data(), nst * 4, hipMemcpyHostToDevice));
-    }
-    if (which == 0) hipLaunchKernelGGL(bbmpc::k_process_input, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, e.stream, da, db, batch, S, U, stats ? dst : nullptr, dout);
-    else hipLaunchKernelGGL(bbmpc::k_process_output, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, e.stream, da, db, batch, S, U, stats ? dst : nullptr, dout);
+    const std::vector<float> flat = stats ? bbmpc::flatten_stats(stats, S, U) : std::vector<float>();     // (lives until finish())
+    HostStage st(e);
+    const int da = st.in(a, na), db = st.in(b, nb), dout = st.out(out, no), dst = st.in(flat.data(), flat.size());
+    st.upload();
+    if (which == 0) hipLaunchKernelGGL(bbmpc::k_process_input, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, e.stream, st[da], st[db], batch, S, U, st[dst], st[dout]);
+    else hipLaunchKernelGGL(bbmpc::k_process_output, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, e.stream, st[da], st[db], batch, S, U, st[dst], st[dout]);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, dout, no * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    st.finish();
 }
 
 int bbmpc_process_input(bbmpc_handle h, const float* states, const float* actions, int32_t batch, const float* const* stats, float* out) {
@@ -2033,13 +2010,12 @@ int bbmpc_rollout_episode(bbmpc_handle h, const float* start_state, int32_t num_
     Engine& e = *h->e;
     if (num_steps < 1) throw HipError(BBMPC_E_INVALID, "num_steps must be >= 1");
     const size_t ns = (size_t)e.A * e.S, nr = (size_t)e.A * e.rec;
-    if (e.d_step_d.n < 2 * ns + nr * (size_t)num_steps) e.d_step_d.alloc(2 * ns + nr * (size_t)num_steps);
-    float* st[2] = {e.d_step_d.p, e.d_step_d.p + ns};
-    float* recs = e.d_step_d.p + 2 * ns;
-    HIP_CHECK(hipMemcpyAsync(st[0], start_state, ns * 4, hipMemcpyHostToDevice, e.stream));
-    for (int t = 0; t < num_steps; ++t) e.optimize_dev(st[t & 1], noise, recs + nr * t, st[(t + 1) & 1]);
-    HIP_CHECK(hipMemcpyAsync(records_out, recs, nr * (size_t)num_steps * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s0 = st.in(start_state, ns), s1 = st.scratch(ns), r = st.out(records_out, nr * (size_t)num_steps);
+    st.upload();
+    float* const state[2] = {st[s0], st[s1]};                                // the state ping-pong
+    for (int t = 0; t < num_steps; ++t) e.optimize_dev(state[t & 1], noise, st[r] + nr * t, state[(t + 1) & 1]);
+    st.finish();
     API_END
 }
 
@@ -2061,13 +2037,12 @@ int bbmpc_evaluate(bbmpc_handle h, const float* state, const float* seq, int32_t
     CHECK_PTR(rewards);
     Engine& e = *h->e;
     if (n_pop < 1) throw HipError(BBMPC_E_INVALID, "n_pop must be >= 1");
-    const size_t nseq = (size_t)n_pop * e.A * e.HU, nrew = (size_t)n_pop * e.A;
-    if (e.d_eval_seq.n < nseq + nrew) e.d_eval_seq.alloc(nseq + nrew);
-    HIP_CHECK(hipMemcpyAsync(e.d_state.p, state, (size_t)e.A * e.S * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(e.d_eval_seq.p, seq, nseq * 4, hipMemcpyHostToDevice, e.stream));
-    e.evaluate_dev(e.d_state.p, e.d_eval_seq.p, n_pop, e.d_eval_seq.p + nseq);
-    HIP_CHECK(hipMemcpyAsync(rewards, e.d_eval_seq.p + nseq, nrew * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int q = st.in(seq, (size_t)n_pop * e.A * e.HU), r = st.out(rewards, (size_t)n_pop * e.A);
+    st.upload();
+    HIP_CHECK(hipMemcpyAsync(e.d_state.p, state, (size_t)e.A * e.S * 4, hipMemcpyHostToDevice, e.stream));   // (not a slot: DESIGN.md section 3a)
+    e.evaluate_dev(e.d_state.p, st[q], n_pop, st[r]);
+    st.finish();
     API_END
 }
 
@@ -2089,14 +2064,11 @@ int bbmpc_predict_next_state(bbmpc_handle h, const float* states, const float* a
     CHECK_PTR(next);
     Engine& e = *h->e;
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
-    const size_t ns = (size_t)batch * e.S, na = (size_t)batch * e.U;
-    if (e.d_step_a.n < 2 * ns + na) e.d_step_a.alloc(2 * ns + na);
-    float* ds = e.d_step_a.p; float* da = ds + ns; float* dn = da + na;
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(da, actions, na * 4, hipMemcpyHostToDevice, e.stream));
-    e.step_dev(ds, da, e.U, batch, dn, nullptr);
-    HIP_CHECK(hipMemcpyAsync(next, dn, ns * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s = st.in(states, (size_t)batch * e.S), a = st.in(actions, (size_t)batch * e.U), n = st.out(next, (size_t)batch * e.S);
+    st.upload();
+    e.step_dev(st[s], st[a], e.U, batch, st[n], nullptr);
+    st.finish();
     API_END
 }
 
@@ -2110,15 +2082,12 @@ int bbmpc_evaluate_next_reward(bbmpc_handle h, const float* states, const float*
     CHECK_PTR(rewards);
     Engine& e = *h->e;
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
-    const size_t ns = (size_t)batch * e.S, na = (size_t)batch * e.U;
-    if (e.d_step_b.n < 2 * ns + na + batch) e.d_step_b.alloc(2 * ns + na + batch);
-    float* dc = e.d_step_b.p; float* dn = dc + ns; float* da = dn + ns; float* dr = da + na;
-    HIP_CHECK(hipMemcpyAsync(dc, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(dn, next_states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(da, actions, na * 4, hipMemcpyHostToDevice, e.stream));
-    e.reward_dev(dc, dn, da, batch, dr);
-    HIP_CHECK(hipMemcpyAsync(rewards, dr, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int c = st.in(states, (size_t)batch * e.S), n = st.in(next_states, (size_t)batch * e.S);
+    const int a = st.in(actions, (size_t)batch * e.U), r = st.out(rewards, (size_t)batch);
+    st.upload();
+    e.reward_dev(st[c], st[n], st[a], batch, st[r]);
+    st.finish();
     API_END
 }
 

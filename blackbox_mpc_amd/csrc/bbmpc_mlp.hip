@@ -170,13 +170,7 @@ void Engine::set_mlp(int n_layers, const int32_t* dims, const int32_t* acts, con
     mlp.normalized = is_normalized ? 1 : 0;
     if (is_normalized) {
         REQUIRE(stats, BBMPC_E_INVALID, "normalisation statistics are required when is_normalized != 0");
-        std::vector<float> st;
-        const int lens[6] = {S, S, U, U, S, S};
-        for (int i = 0; i < 6; ++i) {
-            REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
-            st.insert(st.end(), stats[i], stats[i] + lens[i]);
-        }
-        upload(d_stats, st);
+        upload(d_stats, flatten_stats(stats, S, U));
         float* q = d_stats.p;
         mlp.mean_s = q; q += S;
         mlp.std_s = q; q += S;
@@ -1015,14 +1009,11 @@ void Engine::dump_policy_noise(int control_step, int iteration, float* out, int6
     REQUIRE(count == total, BBMPC_E_INVALID, "dump_noise: policy noise is [A, K, H, U]");
     RngKey kk = key((uint32_t)control_step);
     kk.step_src = nullptr;
-    DevBuf<float> tmp;
-    tmp.alloc((size_t)total);
     const int blocks = A * prior_K * (int)kk.q_per_agent;
-    hipLaunchKernelGGL(k_gen_policy_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, (uint32_t)iteration, A, prior_K, HU,
-                       cfg.agent_offset, tmp.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, tmp.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    stage_read_back(*this, out, (size_t)total, [&](float* d) {
+        hipLaunchKernelGGL(k_gen_policy_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, (uint32_t)iteration, A, prior_K, HU,
+                           cfg.agent_offset, d);
+    });
 }
 
 // The K policy rollouts of every agent from d_state [A][S]: into columns col0 .. col0 + K - 1 of `samples` [A][HU][nst]
@@ -1358,20 +1349,12 @@ extern "C" int bbmpc_refine_plans(bbmpc_handle h, const float* states, float* se
     bbmpc::PlanGradArgs q;
     size_t lds = 0, wsn = 0;
     e.refine_plans_check(batch, horizon, steps, lr, method, keep_best, q, lds, wsn);     // every refusal before the staging buffer is touched
-    const size_t ns = ((size_t)batch * e.S + 3) & ~(size_t)3, nq = ((size_t)batch * horizon * e.U + 3) & ~(size_t)3;
-    if (e.d_rf_io.n < ns + nq + batch) {
-        HIP_CHECK(hipStreamSynchronize(e.stream));
-        e.d_rf_io.alloc(ns + nq + batch);
-    }
-    float* dq = e.d_rf_io.p;                                                 // (first: float4 traffic wants the plans aligned)
-    float* ds = dq + nq;
-    float* dr = ds + ns;
-    HIP_CHECK(hipMemcpyAsync(ds, states, (size_t)batch * e.S * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(dq, seq, (size_t)batch * horizon * e.U * 4, hipMemcpyHostToDevice, e.stream));
-    e.refine_plans_run(q, lds, wsn, ds, dq, steps, lr, method, keep_best, returns_out ? dr : nullptr);
-    HIP_CHECK(hipMemcpyAsync(seq, dq, (size_t)batch * horizon * e.U * 4, hipMemcpyDeviceToHost, e.stream));
-    if (returns_out) HIP_CHECK(hipMemcpyAsync(returns_out, dr, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s = st.in(states, (size_t)batch * e.S), p = st.inout(seq, (size_t)batch * horizon * e.U, bbmpc::StageLayout::kVec4);
+    const int r = st.out(returns_out, (size_t)batch);                       // (the plans: k_refine_step's float4 form wants 16 bytes)
+    st.upload();
+    e.refine_plans_run(q, lds, wsn, st[s], st[p], steps, lr, method, keep_best, st[r]);
+    st.finish();
     API_END
 }
 
@@ -1434,13 +1417,11 @@ extern "C" int bbmpc_evaluate_policy_prior(bbmpc_handle h, const float* states, 
     bbmpc::Engine& e = *h->e;
     if (batch < 1) throw bbmpc::HipError(BBMPC_E_INVALID, "batch must be >= 1");
     if (!e.prior_on()) throw bbmpc::HipError(BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
-    const size_t ns = (size_t)batch * e.S, na = (size_t)batch * e.U;
-    if (e.d_pr_io.n < ns + na) e.d_pr_io.alloc(ns + na);
-    float* ds = e.d_pr_io.p; float* da = ds + ns;
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    e.policy_prior_rows(ds, batch, da);
-    HIP_CHECK(hipMemcpyAsync(actions, da, na * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s = st.in(states, (size_t)batch * e.S), a = st.out(actions, (size_t)batch * e.U);
+    st.upload();
+    e.policy_prior_rows(st[s], batch, st[a]);
+    st.finish();
     API_END
 }
 
@@ -1465,20 +1446,13 @@ extern "C" int bbmpc_predict_policy_rollouts(bbmpc_handle h, const float* states
     if (!actions_out && !states_out) throw bbmpc::HipError(BBMPC_E_INVALID, "policy rollouts: actions_out and states_out are both NULL");
     if (!e.prior_on()) throw bbmpc::HipError(BBMPC_E_STATE, "policy prior: call bbmpc_set_policy_prior_mlp before computing");
     if (!e.mlp_ready) throw bbmpc::HipError(BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
-    const size_t ns = (size_t)e.A * e.S, nn = noise ? (size_t)e.A * e.prior_K * e.HU : 0;
-    const size_t na = actions_out ? (size_t)e.prior_K * e.A * e.HU : 0, nso = states_out ? (size_t)e.prior_K * e.A * e.H * e.S : 0;
-    if (e.d_pr_io.n < ns + nn + na + nso) e.d_pr_io.alloc(ns + nn + na + nso);
-    float* ds = e.d_pr_io.p;
-    float* dn = ds + ns;
-    float* da = dn + nn;
-    float* dso = da + na;
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    if (noise) HIP_CHECK(hipMemcpyAsync(dn, noise, nn * 4, hipMemcpyHostToDevice, e.stream));
-    const float* use = noise ? dn : (e.prior_sigma != 0.0f ? e.policy_noise(e.step_counter, 0) : nullptr);
-    e.policy_prior_rollouts(ds, use, nullptr, 0, 0, actions_out ? da : nullptr, states_out ? dso : nullptr);
-    if (actions_out) HIP_CHECK(hipMemcpyAsync(actions_out, da, na * 4, hipMemcpyDeviceToHost, e.stream));
-    if (states_out) HIP_CHECK(hipMemcpyAsync(states_out, dso, nso * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s = st.in(states, (size_t)e.A * e.S), n = st.in(noise, (size_t)e.A * e.prior_K * e.HU);
+    const int a = st.out(actions_out, (size_t)e.prior_K * e.A * e.HU), so = st.out(states_out, (size_t)e.prior_K * e.A * e.H * e.S);
+    st.upload();
+    const float* use = noise ? st[n] : (e.prior_sigma != 0.0f ? e.policy_noise(e.step_counter, 0) : nullptr);
+    e.policy_prior_rollouts(st[s], use, nullptr, 0, 0, st[a], st[so]);
+    st.finish();
     API_END
 }
 
@@ -1515,13 +1489,11 @@ extern "C" int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states
     bbmpc::Engine& e = *h->e;
     if (batch < 1) throw bbmpc::HipError(BBMPC_E_INVALID, "batch must be >= 1");
     if (!e.val_mlp_ready) throw bbmpc::HipError(BBMPC_E_STATE, "terminal value: call bbmpc_set_terminal_value_mlp before computing");
-    const size_t ns = (size_t)batch * e.S;
-    if (e.d_vl_io.n < ns + batch) e.d_vl_io.alloc(ns + batch);
-    float* ds = e.d_vl_io.p; float* dv = ds + ns;
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    e.terminal_value_rows(ds, batch, dv);
-    HIP_CHECK(hipMemcpyAsync(values, dv, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s = st.in(states, (size_t)batch * e.S), v = st.out(values, (size_t)batch);
+    st.upload();
+    e.terminal_value_rows(st[s], batch, st[v]);
+    st.finish();
     API_END
 }
 
@@ -1549,20 +1521,12 @@ extern "C" int bbmpc_plan_gradient(bbmpc_handle h, const float* states, const fl
         size_t lds = 0, wsn = 0;
         e.plan_gradient_check(batch, horizon, q, lds, wsn);
     }
-    const size_t ns = (size_t)batch * e.S, nq = (size_t)batch * horizon * e.U;
-    if (e.d_pg_io.n < ns + 2 * nq + batch) {
-        HIP_CHECK(hipStreamSynchronize(e.stream));
-        e.d_pg_io.alloc(ns + 2 * nq + batch);
-    }
-    float* ds = e.d_pg_io.p;
-    float* dq = ds + ns;
-    float* dg = dq + nq;
-    float* dr = dg + nq;
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(dq, seq, nq * 4, hipMemcpyHostToDevice, e.stream));
-    e.plan_gradient_dev(ds, dq, batch, horizon, dr, dg);
-    HIP_CHECK(hipMemcpyAsync(grad_out, dg, nq * 4, hipMemcpyDeviceToHost, e.stream));
-    if (returns_out) HIP_CHECK(hipMemcpyAsync(returns_out, dr, (size_t)batch * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    const size_t nq = (size_t)batch * horizon * e.U;
+    HostStage st(e);
+    const int s = st.in(states, (size_t)batch * e.S), p = st.in(seq, nq);
+    const int g = st.out(grad_out, nq), r = st.out(returns_out, (size_t)batch);
+    st.upload();
+    e.plan_gradient_dev(st[s], st[p], batch, horizon, st[r], st[g]);
+    st.finish();
     API_END
 }

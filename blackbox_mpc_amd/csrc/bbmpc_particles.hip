@@ -92,14 +92,11 @@ void Engine::dump_process_noise(int control_step, int iteration, float* out, int
     RngKey kk = key((uint32_t)control_step);
     kk.q_per_agent = (uint32_t)((H * S + 3) / 4);
     kk.step_src = nullptr;
-    DevBuf<float> tmp;
-    tmp.alloc((size_t)total);
     const int blocks = A * part_P * (int)kk.q_per_agent;
-    hipLaunchKernelGGL(k_gen_process_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, (uint32_t)iteration, A, part_P, H * S,
-                       cfg.agent_offset, tmp.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out, tmp.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+    stage_read_back(*this, out, (size_t)total, [&](float* d) {
+        hipLaunchKernelGGL(k_gen_process_noise, dim3((blocks + 255) / 256), dim3(256), 0, stream, kk, (uint32_t)iteration, A, part_P, H * S,
+                           cfg.agent_offset, d);
+    });
 }
 
 // launch_rollout with particles on: the candidates into the sample buffer (as the user-function paths draw them), the
@@ -260,17 +257,13 @@ int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* se
     if (!e.particles_on()) throw HipError(BBMPC_E_STATE, "particles are off: call bbmpc_set_particles first");
     if (n_pop < 1) throw HipError(BBMPC_E_INVALID, "n_pop must be >= 1");
     if (e.particle_user_reward()) e.require_particle_traj_fits((((long)n_pop + 63) / 64) * 64 * e.part_P);     // before the staging buffer
-    const size_t nseq = (size_t)n_pop * e.A * e.HU, nsc = (size_t)n_pop * e.A, nret = returns ? nsc * e.part_P : 0;
-    if (e.d_pe_io.n < nseq + nsc + nret) e.d_pe_io.alloc(nseq + nsc + nret);
-    float* dseq = e.d_pe_io.p;
-    float* dsc = dseq + nseq;
-    float* dret = returns ? dsc + nsc : nullptr;
-    HIP_CHECK(hipMemcpyAsync(e.d_state.p, state, (size_t)e.A * e.S * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(dseq, seq, nseq * 4, hipMemcpyHostToDevice, e.stream));
-    e.evaluate_particles_dev(e.d_state.p, dseq, n_pop, dsc, dret);
-    HIP_CHECK(hipMemcpyAsync(scores, dsc, nsc * 4, hipMemcpyDeviceToHost, e.stream));
-    if (returns) HIP_CHECK(hipMemcpyAsync(returns, dret, nret * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    const size_t nsc = (size_t)n_pop * e.A;
+    HostStage st(e);
+    const int q = st.in(seq, nsc * e.HU), sc = st.out(scores, nsc), ret = st.out(returns, nsc * e.part_P);
+    st.upload();
+    HIP_CHECK(hipMemcpyAsync(e.d_state.p, state, (size_t)e.A * e.S * 4, hipMemcpyHostToDevice, e.stream));   // (not a slot: DESIGN.md section 3a)
+    e.evaluate_particles_dev(e.d_state.p, st[q], n_pop, st[sc], st[ret]);
+    st.finish();
     API_END
 }
 

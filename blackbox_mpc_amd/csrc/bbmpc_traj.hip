@@ -156,19 +156,12 @@ int bbmpc_predict_trajectories(bbmpc_handle h, const float* states, const float*
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
     if (horizon < 1 || horizon > 4096) throw HipError(BBMPC_E_INVALID, "horizon must be in [1, 4096]");
     if (!states_out && !rewards_out) throw HipError(BBMPC_E_INVALID, "states_out and rewards_out are both null");
-    const size_t ns = (size_t)batch * e.S, nq = (size_t)batch * horizon * e.U, no = (size_t)batch * horizon * e.S, nr = (size_t)batch * horizon;
-    const size_t need = ns + nq + (states_out ? no : 0) + (rewards_out ? nr : 0);
-    if (e.tj_io.n < need) e.tj_io.alloc(need);
-    float* ds = e.tj_io.p;
-    float* dq = ds + ns;
-    float* dout = states_out ? dq + nq : nullptr;
-    float* drew = rewards_out ? dq + nq + (states_out ? no : 0) : nullptr;
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(dq, seq, nq * 4, hipMemcpyHostToDevice, e.stream));
-    e.predict_trajectories_dev(ds, dq, batch, horizon, dout, drew);
-    if (states_out) HIP_CHECK(hipMemcpyAsync(states_out, dout, no * 4, hipMemcpyDeviceToHost, e.stream));
-    if (rewards_out) HIP_CHECK(hipMemcpyAsync(rewards_out, drew, nr * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int s = st.in(states, (size_t)batch * e.S), q = st.in(seq, (size_t)batch * horizon * e.U);
+    const int so = st.out(states_out, (size_t)batch * horizon * e.S), ro = st.out(rewards_out, (size_t)batch * horizon);
+    st.upload();
+    e.predict_trajectories_dev(st[s], st[q], batch, horizon, st[so], st[ro]);
+    st.finish();
     API_END
 }
 

@@ -138,32 +138,21 @@ static void traj_particles_host(Engine& e, const float* states, const float* seq
     const size_t P = (size_t)e.part_P;
     const size_t ns = (size_t)batch * e.S, nq = (size_t)batch * horizon * e.U, nm = (size_t)batch * horizon * e.S, nr = (size_t)batch * horizon;
     const size_t nps = nm * P, npr = nr * P;
-    // staging: states | sequences | eps | the outputs that are wanted, in the order of the arguments
+    // the slots are declared in the order of the arguments; an output that is not wanted gives a null slot
     const size_t nl = quantiles ? (size_t)num_levels : 0;
     const size_t sizes[8] = {nm, nm, nr, nr, nps, npr, nm * nl, nr * nl};
-    size_t need = ns + nq + (eps ? nps : 0);
-    for (int i = 0; i < 8; ++i) need += outs[i] ? sizes[i] : 0;
-    if (e.tjp_io.n < need) e.tjp_io.alloc(need);
-    float* ds = e.tjp_io.p;
-    float* dq = ds + ns;
-    float* deps = eps ? dq + nq : nullptr;
-    float* next = dq + nq + (eps ? nps : 0);
-    float* douts[8];
-    for (int i = 0; i < 8; ++i) {
-        douts[i] = outs[i] ? next : nullptr;
-        next += outs[i] ? sizes[i] : 0;
-    }
-    HIP_CHECK(hipMemcpyAsync(ds, states, ns * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(dq, seq, nq * 4, hipMemcpyHostToDevice, e.stream));
-    if (eps) HIP_CHECK(hipMemcpyAsync(deps, eps, nps * 4, hipMemcpyHostToDevice, e.stream));
+    HostStage st(e);
+    const int s = st.in(states, ns), q = st.in(seq, nq), ep = st.in(eps, nps);
+    int o[8];
+    float* d[8];                                                              // the outputs' slots and device pointers
+    for (int i = 0; i < 8; ++i) o[i] = st.out(outs[i], sizes[i]);
+    st.upload();
+    for (int i = 0; i < 8; ++i) d[i] = st[o[i]];
     if (quantiles)
-        e.predict_trajectory_quantiles_dev(ds, dq, batch, horizon, deps, douts[0], douts[1], douts[2], douts[3], douts[4], douts[5], num_levels,
-                                           ranks, douts[6], douts[7]);
+        e.predict_trajectory_quantiles_dev(st[s], st[q], batch, horizon, st[ep], d[0], d[1], d[2], d[3], d[4], d[5], num_levels, ranks, d[6], d[7]);
     else
-        e.predict_trajectory_particles_dev(ds, dq, batch, horizon, deps, douts[0], douts[1], douts[2], douts[3], douts[4], douts[5]);
-    for (int i = 0; i < 8; ++i)
-        if (outs[i]) HIP_CHECK(hipMemcpyAsync(outs[i], douts[i], sizes[i] * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+        e.predict_trajectory_particles_dev(st[s], st[q], batch, horizon, st[ep], d[0], d[1], d[2], d[3], d[4], d[5]);
+    st.finish();
 }
 
 }  // namespace bbmpc

@@ -655,13 +655,11 @@ int bbmpc_transform_rows(bbmpc_handle h, int32_t kind, const float* a, const flo
         throw HipError(BBMPC_E_INVALID, "kind must be 3 (inverse target transform) or 4 (target transform)");
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
     const size_t n = (size_t)batch * e.S;
-    if (e.d_step_b.n < 3 * n) e.d_step_b.alloc(3 * n);
-    float* da = e.d_step_b.p; float* db = da + n; float* dout = db + n;
-    HIP_CHECK(hipMemcpyAsync(da, a, n * 4, hipMemcpyHostToDevice, e.stream));
-    HIP_CHECK(hipMemcpyAsync(db, b, n * 4, hipMemcpyHostToDevice, e.stream));
-    e.transform_rows(kind, da, db, batch, dout);
-    HIP_CHECK(hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int da = st.in(a, n), db = st.in(b, n), dout = st.out(out, n);
+    st.upload();
+    e.transform_rows(kind, st[da], st[db], batch, st[dout]);
+    st.finish();
     API_END
 }
 
@@ -688,12 +686,11 @@ int bbmpc_mlp_forward(bbmpc_handle h, const float* x, int32_t batch, float* out)
     Engine& e = *h->e;
     if (batch < 1) throw HipError(BBMPC_E_INVALID, "batch must be >= 1");
     if (e.cfg.dynamics != BBMPC_DYN_MLP || !e.mlp_ready) throw HipError(BBMPC_E_STATE, "bbmpc_mlp_forward: needs a learned-dynamics handle with weights set");
-    const size_t nin = (size_t)batch * e.mlp.dims[0], nout = (size_t)batch * e.mlp.dims[e.mlp.n_layers];
-    if (e.d_step_a.n < nin + nout) e.d_step_a.alloc(nin + nout);
-    HIP_CHECK(hipMemcpyAsync(e.d_step_a.p, x, nin * 4, hipMemcpyHostToDevice, e.stream));
-    e.mlp_forward_rows(e.d_step_a.p, batch, e.d_step_a.p + nin);
-    HIP_CHECK(hipMemcpyAsync(out, e.d_step_a.p + nin, nout * 4, hipMemcpyDeviceToHost, e.stream));
-    HIP_CHECK(hipStreamSynchronize(e.stream));
+    HostStage st(e);
+    const int dx = st.in(x, (size_t)batch * e.mlp.dims[0]), dout = st.out(out, (size_t)batch * e.mlp.dims[e.mlp.n_layers]);
+    st.upload();
+    e.mlp_forward_rows(st[dx], batch, st[dout]);
+    st.finish();
     API_END
 }
 

@@ -230,8 +230,9 @@ struct Engine {
     hipStream_t eigh_side = nullptr;
     hipEvent_t eigh_ev[2] = {nullptr, nullptr};
     int eigh_side_state = -1;         // -1 undecided, 0 off, 1 on
-    // evaluate() scratch (grown on demand)
-    DevBuf<float> d_eval_seq, d_eval_rew, d_step_a, d_step_b, d_step_c, d_step_d;
+    DevBuf<float> d_eval_rew, d_step_c;    // evaluate_dev / step_dev scratch (grown on demand)
+    DevBuf<float> d_stage;                 // the one staging buffer of the host-in / host-out calls (abi_util.hpp HostStage): no _dev member touches it
+    int stage_depth = 0;                   // ... and how many stages are live (a nested one keeps a buffer of its own)
     // injected noise (internal layout), keyed by BBMPC_NOISE_*
     std::map<int, DevBuf<float>> inj;
     // traces
@@ -377,7 +378,7 @@ struct Engine {
     bool val_mlp_ready = false;
     RewMlpDesc val_mlp;
     float val_weight = 1.0f;
-    DevBuf<float> d_vl_wp4[MLP_MAX_LAYERS], d_vl_bp[MLP_MAX_LAYERS], d_vl_last, d_vl_stats, d_vl_io;
+    DevBuf<float> d_vl_wp4[MLP_MAX_LAYERS], d_vl_bp[MLP_MAX_LAYERS], d_vl_last, d_vl_stats;
     bool value_on() const { return val_mlp_ready; }
     void set_terminal_value_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b,
                                 int is_normalized, const float* const* stats, float terminal_weight);
@@ -404,7 +405,7 @@ struct Engine {
     PgHostNet pg_host[3];              // 0 dynamics, 1 reward, 2 terminal value
     bool pg_stale[3] = {true, true, true};
     PgNet pg_net[3];
-    DevBuf<float> d_pg_wf[3][MLP_MAX_LAYERS], d_pg_bf[3][MLP_MAX_LAYERS], d_pg_wr[3][MLP_MAX_LAYERS], d_pg_zero, d_pg_ws, d_pg_io;
+    DevBuf<float> d_pg_wf[3][MLP_MAX_LAYERS], d_pg_bf[3][MLP_MAX_LAYERS], d_pg_wr[3][MLP_MAX_LAYERS], d_pg_zero, d_pg_ws;
     void plan_gradient_check(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats);
     void plan_gradient_pack(int which);
     void plan_gradient_dev(const float* d_states, const float* d_seq, int batch, int horizon, float* d_returns, float* d_grad);
@@ -413,7 +414,7 @@ struct Engine {
     // plan refinement on the device (bbmpc_refine_plans; bbmpc_mlp.hip, kernels_plan_refine.hpp): the
     // loop gradient -> Adam / SGD step -> clip (-> keep-best) on the handle's stream, nothing in between visits the host.
     // d_rf: gradient | m | v | best [4][n rounded up to 4] | returns [B] | best returns [B]
-    DevBuf<float> d_rf, d_rf_io;
+    DevBuf<float> d_rf;
     void plan_gradient_prepare(size_t ws_floats);
     void plan_gradient_launch(PlanGradArgs q, size_t lds, const float* d_states, const float* d_seq, float* d_returns, float* d_grad);
     void refine_plans_check(int batch, int horizon, int steps, float lr, int method, int keep_best, PlanGradArgs& q, size_t& lds, size_t& wsn);
@@ -557,7 +558,7 @@ struct Engine {
     // the part_tail worst returns (CVaR; kappa is then ignored).  Kept while particles are off.
     int part_risk = BBMPC_RISK_MEAN_STD, part_tail = 0;
     void set_particle_risk(int kind, int tail_count);
-    DevBuf<float> d_psigma, d_pnoise, d_preturns, d_pe_io;   // sigma [S] | eps [A][P][H][S] | returns [A][Nst * P] | host-call staging
+    DevBuf<float> d_psigma, d_pnoise, d_preturns;   // sigma [S] | eps [A][P][H][S] | returns [A][Nst * P]
     bool pnoise_valid = false;         // d_pnoise holds the draws of (pnoise_step, pnoise_iter)
     uint32_t pnoise_step = 0, pnoise_iter = 0;
     bool particles_on() const { return part_P > 0; }
@@ -589,8 +590,8 @@ struct Engine {
     // trajectory distributions (bbmpc_predict_trajectory_particles; bbmpc_traj_particles.hip, kernels_traj_particles.hpp): the
     // particle recurrence from every row's own start state, every state and reward kept, and their moments over the particles.
     // Buffers of its own: the draws [B][P][Hq][S] (never d_pnoise, whose validity flags belong to the control step), the
-    // particle tensors when the caller does not want them, the host call's staging.
-    DevBuf<float> tjp_noise, tjp_ps, tjp_pr, tjp_io;
+    // particle tensors when the caller does not want them.
+    DevBuf<float> tjp_noise, tjp_ps, tjp_pr;
     void predict_trajectory_particles_dev(const float* d_states, const float* d_seq, int batch, int horizon, const float* d_eps,
                                           float* d_smean, float* d_sstd, float* d_rmean, float* d_rstd, float* d_pstates, float* d_prewards);
     void launch_traj_mlp_particles(const TrajParticleArgs& pa);               // bbmpc_mlp.hip
@@ -633,7 +634,7 @@ struct Engine {
     int prior_nw = 1;                  // waves its widest hidden layer asks for
     int prior_K = 0;
     float prior_sigma = 0.0f;
-    DevBuf<float> d_pr_wp4[MLP_MAX_LAYERS], d_pr_bp[MLP_MAX_LAYERS], d_pr_stats, d_pr_noise, d_pr_io;
+    DevBuf<float> d_pr_wp4[MLP_MAX_LAYERS], d_pr_bp[MLP_MAX_LAYERS], d_pr_stats, d_pr_noise;
     bool prior_noise_valid = false;    // d_pr_noise holds the draws of (prior_noise_step, prior_noise_iter)
     uint32_t prior_noise_step = 0, prior_noise_iter = 0;
     bool prior_on() const { return prior_ready; }
@@ -646,7 +647,7 @@ struct Engine {
     void policy_prior_rows(const float* d_states, int batch, float* d_actions);
     void traj_stepwise(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     void traj_sq_error_dev(const float* d_pred, const float* d_obs, int batch, int horizon, double* d_sumsq);
-    DevBuf<float> tj_x0, tj_x1, tj_rew, tj_io;      // step-wise form: dense state ping-pong and one step's rewards | host-call staging
+    DevBuf<float> tj_x0, tj_x1, tj_rew;             // step-wise form: dense state ping-pong and one step's rewards
     DevBuf<double> tj_part;                          // squared-error partials [row blocks][Hq*S]
 
     void inject(int kind, const float* data, int64_t count);

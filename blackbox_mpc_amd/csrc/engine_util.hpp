@@ -15,6 +15,17 @@ inline void upload(DevBuf<float>& b, const std::vector<float>& v) {
     HIP_CHECK(hipMemcpy(b.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
+// A dynamics model's six normalisation vectors as the kernels read them: mean_s | std_s | mean_a | std_a | mean_t | std_t
+inline std::vector<float> flatten_stats(const float* const* stats, int S, int U) {
+    std::vector<float> st;
+    const int lens[6] = {S, S, U, U, S, S};
+    for (int i = 0; i < 6; ++i) {
+        REQUIRE(stats[i], BBMPC_E_INVALID, "null statistics vector");
+        st.insert(st.end(), stats[i], stats[i] + lens[i]);
+    }
+    return st;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set it once per (device, kernel)
 // -- a process may hold handles on several devices (bbmpc_config.device).
 inline void ensure_max_lds(const void* fn, int bytes) {
