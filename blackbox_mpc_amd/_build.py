@@ -37,6 +37,7 @@ GUARDED = {"kernels_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_eigh_small.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_fused_cma.hpp": ("bbmpc_cma.hip", "#ifdef BBMPC_TU_CMA"),
            "kernels_reward_mlp.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
+           "kernels_return_shaping.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
            "kernels_plan_grad.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
            "kernels_plan_refine.hpp": ("bbmpc_mlp.hip", "#ifdef BBMPC_TU_MLP"),
            "kernels_train.hpp": ("bbmpc_train.hip", "#ifdef BBMPC_TU_TRAIN")}

@@ -99,6 +99,7 @@ SYMBOLS = [
     "bbmpc_set_elite_carry", "bbmpc_get_elite_carry",
     "bbmpc_set_reward_mlp",
     "bbmpc_set_terminal_value_mlp", "bbmpc_evaluate_terminal_value", "bbmpc_evaluate_terminal_value_dev",
+    "bbmpc_set_return_shaping", "bbmpc_get_termination_steps",
     "bbmpc_set_policy_prior_mlp", "bbmpc_get_policy_prior", "bbmpc_evaluate_policy_prior", "bbmpc_evaluate_policy_prior_dev",
     "bbmpc_predict_policy_rollouts", "bbmpc_predict_policy_rollouts_dev",
     "bbmpc_plan_gradient", "bbmpc_plan_gradient_dev",
@@ -142,6 +143,8 @@ def _load():
                                                  ctypes.POINTER(vp), i32, ctypes.POINTER(vp), ctypes.c_float]
     lib.bbmpc_evaluate_terminal_value.argtypes = [vp, vp, i32, vp]
     lib.bbmpc_evaluate_terminal_value_dev.argtypes = [vp, vp, i32, vp]
+    lib.bbmpc_set_return_shaping.argtypes = [vp, ctypes.c_float, vp, vp, ctypes.c_float]
+    lib.bbmpc_get_termination_steps.argtypes = [vp, vp, i32]
     lib.bbmpc_set_policy_prior_mlp.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(vp),
                                                ctypes.POINTER(vp), i32, ctypes.POINTER(vp), i32, ctypes.c_float]
     lib.bbmpc_get_policy_prior.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float)]

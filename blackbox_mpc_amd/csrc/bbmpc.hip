@@ -680,6 +680,11 @@ void Engine::launch_rollout(int mode, bool pen, RolloutArgs& ra) {
         rollout_particles(mode, pen, ra, nullptr, 0);
         return;
     }
+    if (shaping_on()) {                                   // bbmpc_set_return_shaping: recording on, every sequence ends in k_shaped_return
+        dominant_kernel = "k_rollout_mlp";
+        rollout_shaped(mode, pen, ra);
+        return;
+    }
     if (value_on()) {                                     // a learned terminal value: today's rollout with recording on + one launch
         dominant_kernel = "k_rollout_mlp";
         rollout_terminal_value(mode, pen, ra);
@@ -914,7 +919,7 @@ RefitArgs Engine::refit_args() const {
 // samples from is a constant of the handle -- the rollout samples from the constants directly and reads the state from the
 // pinned buffer itself (its workgroup 0 stores it for the later launches).  What else must hold is the optimizer's own.
 bool Engine::dist_init_skippable() const {
-    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() && !prior_on() && !grad_on() &&
+    return sw.pi2_skip_init && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !shaping_on() && !pop_sharded() && !trace_on && !particles_on() && !corr_on() && !carry_on() && !prior_on() && !grad_on() &&
            iters >= 1 && pi2_copy_seen && stage_state_src != nullptr;
 }
 
@@ -1036,7 +1041,7 @@ void Engine::optimize_cem(RolloutArgs& ra) {
             continue;
         }
         bool first_from_constants = false;
-        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !grad_on()) {
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !shaping_on() && !grad_on()) {
             first_rollout_mlp(false, ra, d_prev_mean.p, d_sigma0.p, cem_pinned);
             first_from_constants = cem_skip;
         } else {
@@ -1114,7 +1119,7 @@ void Engine::optimize_pi2(RolloutArgs& ra) {
             capture_trace(it);
             continue;
         }
-        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on()) first_rollout_mlp(true, ra, d_prev_mean.p, nullptr, pinned_state);
+        if (it == 0 && cfg.dynamics == BBMPC_DYN_MLP && !user_path() && !value_on() && !shaping_on()) first_rollout_mlp(true, ra, d_prev_mean.p, nullptr, pinned_state);
         else launch_rollout(SRC_TRUNC, true, ra);
         if (sw.refit_v1) hipLaunchKernelGGL(k_refit_pi2, dim3(A), dim3(REFIT_THREADS), lds, stream, rf);
         else hipLaunchKernelGGL(k_refit_pi2_mw, dim3((HU + PI2_ROWS - 1) / PI2_ROWS, A), dim3(64 * PI2_ROWS), lds, stream, rf);
@@ -1526,6 +1531,11 @@ void Engine::get_state(const std::string& name, float* out, int64_t count) {
         HIP_CHECK(hipMemcpy(out, d_samples.p, (size_t)count * 4, hipMemcpyDeviceToHost));
         return;
     }
+    if (name == "shaping_n_pop") {                            // candidates of the most recent shaped rollout (bbmpc_get_termination_steps' n / A); 0: none yet
+        REQUIRE(count == 1, BBMPC_E_INVALID, "shaping_n_pop has one element");
+        out[0] = (float)sh_last_npop;
+        return;
+    }
     if (cfg.optimizer == BBMPC_OPT_CMAES) goto cma_names;     // "sigma"/"m" etc. mean the CMA-ES state there
     if (name == "prev_mean") src = d_prev_mean.p;
     else if (name == "mean") src = d_mean.p;
@@ -1809,7 +1819,7 @@ static HostStepPlan choose_host_step(const Engine& e, int32_t noise) {
         // hundreds of rollout workgroups read the state: it goes to HBM once, the record comes back on its own.
         // CEM / PI2 begin with k_dist_init, which fetches it from the pinned buffer itself; the others get a copy
         p.stage = (e.cfg.optimizer == BBMPC_OPT_CEM || e.cfg.optimizer == BBMPC_OPT_PI2) && !e.pop_sharded() &&
-                  !e.user_path() && !e.value_on();
+                  !e.user_path() && !e.value_on() && !e.shaping_on();
         // steady state of the learned-model PI2 / CEM path: the same launches with the same arguments every call --
         // replayed as a graph (engine.hpp: step_graph)
         p.graph_ok = e.sw.step_graph && p.stage && e.cfg.dynamics == BBMPC_DYN_MLP && p.host_poll &&

@@ -153,7 +153,7 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
         const bool small3 = sw.cma_small3 && cma_use_eigh_small() && !pop_sharded();
         if (small3) {
             // n <= 32: sample | roll out | update, three launches per iteration (kernels_eigh_small.hpp)
-            const bool write_back = trace_on || user_path() || particles_on();
+            const bool write_back = trace_on || user_path() || particles_on() || shaping_on();   // (k_shaped_return reads the clipped candidates)
             // the analytic pendulum, one agent per instance: the rollouts ride on the sampling launch
             const bool roll_in = !write_back && cfg.dynamics == BBMPC_DYN_PENDULUM && cfg.reward == BBMPC_REW_PENDULUM && cma_G == A && U == 1 && S == 3;
             if (roll_in) {
@@ -202,7 +202,7 @@ void Engine::optimize_cma(RolloutArgs& ra, uint32_t step) {
             // the clipped candidates go back to the buffer only where somebody reads them whole (the parity trace, the sharded
             // selection, user functions): the path update clips the k elites it reads itself, and the write-back is 9.6 MB of
             // strided stores per launch at config 5's shape
-            const bool write_back = trace_on || pop_sharded() || user_path() || particles_on();
+            const bool write_back = trace_on || pop_sharded() || user_path() || particles_on() || shaping_on();
             ra.cand = d_cand_a.p; ra.samples = write_back ? d_cand_a.p : nullptr; ra.rewards = d_rewards.p; ra.penalty_out = nullptr;
             launch_rollout(SRC_BUF, true, ra);                          // clip + penalty (cma_es.py:147-157)
             if (part || !merge_sp) hipLaunchKernelGGL(k_cma_select, dim3(G), dim3(REFIT_THREADS), lds, stream, q, part);

@@ -9,6 +9,7 @@
 #include "engine.hpp"
 #include "engine_util.hpp"
 #include "kernels_reward_mlp.hpp"
+#include "kernels_return_shaping.hpp"
 #include "kernels_mlp_traj.hpp"
 #include "kernels_mlp_particles.hpp"
 #include "kernels_mlp_traj_particles.hpp"
@@ -826,10 +827,129 @@ void Engine::terminal_value_rows(const float* d_states, int batch, float* d_out)
     launch_args(k_reward_mlp_rows, dim3((batch + MLP_TP - 1) / MLP_TP), dim3(val_mlp.nw * 64), lds, stream, q);
 }
 
+// ------------------------------------------------------------------------------------------------
+// discounted, termination-aware returns (bbmpc_set_return_shaping; kernels_return_shaping.hpp)
+// ------------------------------------------------------------------------------------------------
+// Everything is checked before the handle is touched, so a refusal leaves it as it was.  discount == 1 with both bounds
+// NULL switches shaping off: the handle's routing and scores are then what they were before it was ever set.
+void Engine::set_return_shaping(float discount, const float* state_lo, const float* state_hi, float terminal_reward) {
+    REQUIRE(std::isfinite(discount) && discount > 0.0f && discount <= 1.0f, BBMPC_E_INVALID, "return shaping: discount must be in (0, 1]");
+    REQUIRE(std::isfinite(terminal_reward), BBMPC_E_INVALID, "return shaping: terminal_reward must be finite");
+    for (int i = 0; i < S; ++i) {
+        const float l = state_lo ? state_lo[i] : -INFINITY, h = state_hi ? state_hi[i] : INFINITY;
+        REQUIRE(l == l && h == h, BBMPC_E_INVALID, "return shaping: state bound " + std::to_string(i) + " is NaN (use -inf / +inf for unbounded)");
+        REQUIRE(l <= h, BBMPC_E_INVALID, "return shaping: state_lo[" + std::to_string(i) + "] exceeds state_hi[" + std::to_string(i) + "]");
+    }
+    if (discount == 1.0f && !state_lo && !state_hi) {
+        if (!sh_on) return;
+        invalidate_step_graph();
+        HIP_CHECK(hipStreamSynchronize(stream));
+        sh_on = false;
+        sh_last_npop = sh_last_Nst = 0;
+        return;
+    }
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
+            "return shaping walks the recorded rollouts of a learned model: the handle needs BBMPC_DYN_MLP, not analytic or user dynamics");
+    REQUIRE(cfg.reward != BBMPC_REW_USER, BBMPC_E_UNSUPPORTED,
+            "return shaping beside a BBMPC_REW_USER reward (HIP source or callback): its step rewards are summed inside run-time compiled "
+            "code; use a built-in reward or BBMPC_REW_MLP");
+    REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED,
+            "return shaping beside an inverse target transform (bbmpc_set_inverse_transform_source): the transform rollout has no shaped form");
+    REQUIRE(!particles_on(), BBMPC_E_UNSUPPORTED,
+            "return shaping with particles on (bbmpc_set_particles): the particle evaluator has no shaped form (bbmpc_set_particles(0) first)");
+    REQUIRE(!grad_on(), BBMPC_E_UNSUPPORTED,
+            "return shaping beside gradient refinement (bbmpc_set_grad_refine): the gradient steps climb the unshaped return; switch it "
+            "off first (steps = 0)");
+    std::vector<float> box((size_t)2 * S);
+    for (int i = 0; i < S; ++i) {
+        box[i] = state_lo ? state_lo[i] : -INFINITY;
+        box[S + i] = state_hi ? state_hi[i] : INFINITY;
+    }
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));               // (nothing in flight reads the box that is replaced)
+    sh_on = false;
+    upload(d_sh_box, box);
+    sh_gamma = discount;
+    sh_term_reward = terminal_reward;
+    sh_last_npop = sh_last_Nst = 0;
+    sh_on = true;
+}
+
+// The launch sequences of a shaping handle.  A built-in reward: the rollout with reward kind REW_NONE and recording on, the
+// way rollout_mlp_user_reward runs it -- k_shaped_return recomputes the step rewards with reward_generic.  BBMPC_REW_MLP:
+// the rollout and k_reward_mlp_traj, whose step buffer k_shaped_return reads in k_reward_mlp_finish's place.  A value
+// network: one k_reward_mlp_rows launch over the last plane (k_value_mlp_terminal's + w * V is unconditional).
+void Engine::rollout_shaped(int mode, bool pen, RolloutArgs& ra) {
+    REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
+    REQUIRE((long)ra.H * A * ra.Nst * S < (1L << 31), BBMPC_E_UNSUPPORTED, "return shaping: more than 2^31 trajectory elements per launch");
+    const size_t need = (size_t)ra.H * A * ra.Nst * S, need_n = (size_t)A * ra.Nst;
+    if (u_traj.n < need) u_traj.alloc(need);
+    if (d_sh_tsteps.n < need_n) d_sh_tsteps.alloc(need_n);
+    if (value_on() && d_sh_vterm.n < need_n) d_sh_vterm.alloc(need_n);
+    const bool learned = cfg.reward == BBMPC_REW_MLP;
+    if (learned) {
+        rollout_mlp_reward_mlp(mode, pen, ra, false);
+    } else {
+        struct Restore { int& kind; int was; ~Restore() { kind = was; } } restore{ra.reward_kind, ra.reward_kind};
+        ra.reward_kind = REW_NONE;                        // leaves -(penalty) in ra.rewards
+        launch_rollout_mlp(mode, pen, ra, false, nullptr, u_traj.p);
+    }
+    if (value_on()) {                                     // V of the last plane: per agent its n_pop rows, the padding rows stay untouched
+        const size_t vlds = (size_t)rew_mlp_lds_layout(val_mlp).total * sizeof(float);
+        for (int a = 0; a < A; ++a) {
+            RewMlpRowsArgs r;
+            memset(&r, 0, sizeof(r));
+            r.m = val_mlp;
+            r.B = ra.n_pop;
+            r.cur = u_traj.p + ((size_t)(ra.H - 1) * A + a) * ra.Nst * S; r.cur_stride = S;
+            r.act = r.cur; r.nxt = r.cur;                 // never read: the mask selects s_t alone
+            r.out = d_sh_vterm.p + (size_t)a * ra.Nst;
+            launch_args(k_reward_mlp_rows, dim3((r.B + MLP_TP - 1) / MLP_TP), dim3(val_mlp.nw * 64), vlds, stream, r);
+        }
+    }
+    ShapedReturnArgs q;
+    memset(&q, 0, sizeof(q));
+    q.n_pop = ra.n_pop; q.A = A; q.H = ra.H; q.Nst = ra.Nst; q.HU = ra.HU; q.S = S; q.U = U;
+    q.from_ref = mode == SRC_REF ? 1 : 0;
+    q.reward_kind = learned ? REW_NONE : (int)cfg.reward;
+    q.fix_q1 = fix(BBMPC_FIX_Q1_REWARD_ARG_ORDER) ? 1 : 0;
+    q.gamma = sh_gamma; q.term_reward = sh_term_reward; q.weight = val_weight;
+    q.state = ra.state;
+    q.traj = u_traj.p;
+    q.seq = ra.seq;
+    q.cand = mode == SRC_BUF ? ra.cand : ra.samples;
+    if (mode != SRC_REF) REQUIRE(q.cand, BBMPC_E_STATE, "return shaping over the learned model: no candidate buffer");
+    // a rollout that clips (pen) must have written the clipped candidates back: they are the a_t of the rule
+    if (mode == SRC_BUF && pen) REQUIRE(ra.samples == ra.cand, BBMPC_E_INVALID, "internal: return shaping needs the clipped candidates written back");
+    q.step = learned ? d_rw_step.p : nullptr;
+    q.vterm = value_on() ? d_sh_vterm.p : nullptr;
+    q.box = d_sh_box.p;
+    q.rewards = ra.rewards;
+    q.tsteps = d_sh_tsteps.p;
+    const size_t lds = (size_t)shaped_return_lds_floats(S, U) * sizeof(float);
+    const dim3 grid((ra.n_pop + SHAPED_LANES - 1) / SHAPED_LANES, A), block(SHAPED_LANES);
+    if (S % 4 == 0) hipLaunchKernelGGL(k_shaped_return<true>, grid, block, lds, stream, q);
+    else hipLaunchKernelGGL(k_shaped_return<false>, grid, block, lds, stream, q);
+    HIP_CHECK(hipGetLastError());
+    sh_last_npop = ra.n_pop;
+    sh_last_Nst = ra.Nst;
+}
+
+// T of the most recent rollout, [A][n_pop]
+void Engine::termination_steps(int32_t* out, int n) {
+    REQUIRE(shaping_on(), BBMPC_E_STATE, "termination steps: return shaping is off (bbmpc_set_return_shaping)");
+    REQUIRE(sh_last_npop > 0, BBMPC_E_STATE, "termination steps: nothing has been rolled out since return shaping was set");
+    REQUIRE(n == A * sh_last_npop, BBMPC_E_INVALID,
+            "termination steps: n must be num_agents * (candidates of the most recent rollout) = " + std::to_string(A * sh_last_npop));
+    HIP_CHECK(hipMemcpy2DAsync(out, (size_t)sh_last_npop * 4, d_sh_tsteps.p, (size_t)sh_last_Nst * 4, (size_t)sh_last_npop * 4, A,
+                               hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
 // The learned model's rollout with a learned reward: Engine::rollout_mlp_user_reward's sequence with the network in place
 // of the user's function -- the MFMA rollout (reward kind REW_NONE) records u_traj and leaves -(penalty) in ra.rewards,
 // k_reward_mlp_traj scores every (candidate, step) row, k_reward_mlp_finish sums the steps.
-void Engine::rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra) {
+void Engine::rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra, bool finish) {
     REQUIRE(rew_mlp_ready, BBMPC_E_STATE, "learned reward: call bbmpc_set_reward_mlp before computing");
     REQUIRE(mlp_ready, BBMPC_E_STATE, "learned dynamics: call bbmpc_set_mlp before computing");
     const size_t need = (size_t)ra.H * A * ra.Nst * S, need_r = (size_t)ra.H * A * ra.Nst;
@@ -865,8 +985,9 @@ void Engine::rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra) {
     }
     hipLaunchKernelGGL(k_reward_mlp_traj, grid, block, lds, stream, q);
     if (sw.prof_reward_mlp) prof_end();
-    hipLaunchKernelGGL(k_reward_mlp_finish, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, ra.n_pop, A, ra.H, ra.Nst,
-                       (const float*)d_rw_step.p, ra.rewards);
+    if (finish)                                           // (return shaping walks the steps itself: Engine::rollout_shaped)
+        hipLaunchKernelGGL(k_reward_mlp_finish, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, ra.n_pop, A, ra.H, ra.Nst,
+                           (const float*)d_rw_step.p, ra.rewards);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1125,6 +1246,9 @@ void Engine::plan_gradient_eligible() const {
             "plan gradient beside a model ensemble or log-variance heads: the gradient is that of one noise-free model");
     REQUIRE(!has_xform(), BBMPC_E_UNSUPPORTED, "plan gradient beside an inverse target transform: the differentiated step is next = dev + state");
     REQUIRE(!user_callbacks(), BBMPC_E_UNSUPPORTED, "plan gradient beside a callback plug-in: a callback has no derivative");
+    REQUIRE(!shaping_on(), BBMPC_E_UNSUPPORTED,
+            "plan gradient beside return shaping (bbmpc_set_return_shaping): the differentiated return is the undiscounted sum over the "
+            "full horizon, not the shaped one; switch shaping off first (discount = 1, no bounds)");
 }
 
 void Engine::plan_gradient_sizes(int batch, int horizon, PlanGradArgs& q, size_t& lds, size_t& ws_floats) {
@@ -1494,6 +1618,21 @@ extern "C" int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states
     st.upload();
     e.terminal_value_rows(st[s], batch, st[v]);
     st.finish();
+    API_END
+}
+
+extern "C" int bbmpc_set_return_shaping(bbmpc_handle h, float discount, const float* state_lo, const float* state_hi, float terminal_reward) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_return_shaping(discount, state_lo, state_hi, terminal_reward);
+    API_END
+}
+
+extern "C" int bbmpc_get_termination_steps(bbmpc_handle h, int32_t* out, int32_t n) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    CHECK_PTR(out);
+    h->e->termination_steps(out, n);
     API_END
 }
 

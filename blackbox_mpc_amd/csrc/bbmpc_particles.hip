@@ -28,6 +28,9 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     REQUIRE(!value_on(), BBMPC_E_UNSUPPORTED,
             "particles with a learned terminal value (bbmpc_set_terminal_value_mlp): the particle evaluator has no terminal term; remove "
             "the value network first (n_layers = 0)");
+    REQUIRE(!shaping_on(), BBMPC_E_UNSUPPORTED,
+            "particles with return shaping on (bbmpc_set_return_shaping): the particle evaluator has no shaped form; switch shaping "
+            "off first (discount = 1, no bounds)");
     // a HIP-source reward scores the learned model's particles; the analytic pendulum keeps its built-in rewards
     REQUIRE((cfg.reward != BBMPC_REW_USER || cfg.dynamics == BBMPC_DYN_MLP) && cfg.dynamics != BBMPC_DYN_USER, BBMPC_E_UNSUPPORTED,
             "particles with HIP-source or callback dynamics, or with a user reward beside the built-in pendulum model: a user reward "

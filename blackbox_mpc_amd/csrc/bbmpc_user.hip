@@ -145,6 +145,8 @@ void Engine::set_transform_source(int kind, const char* src) {
         REQUIRE(!value_on(), BBMPC_E_UNSUPPORTED,
                 "an inverse target transform beside a learned terminal value (bbmpc_set_terminal_value_mlp): the transform rollout has no "
                 "terminal-value form");
+        REQUIRE(!shaping_on(), BBMPC_E_UNSUPPORTED,
+                "an inverse target transform beside return shaping (bbmpc_set_return_shaping): the transform rollout has no shaped form");
         REQUIRE(!prior_on(), BBMPC_E_UNSUPPORTED,
                 "an inverse target transform beside a policy prior (bbmpc_set_policy_prior_mlp): the policy rollout's model step is "
                 "next = dev + state");

@@ -367,7 +367,7 @@ struct Engine {
     DevBuf<float> d_rw_wp4[MLP_MAX_LAYERS], d_rw_bp[MLP_MAX_LAYERS], d_rw_last, d_rw_stats, d_rw_step, d_rw_states;
     void set_reward_mlp(int n_layers, const int32_t* dims, const int32_t* acts, const float* const* w, const float* const* b, int input_mask,
                         int is_normalized, const float* const* stats);
-    void rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra);
+    void rollout_mlp_reward_mlp(int mode, bool pen, RolloutArgs& ra, bool finish = true);   // finish = false: the step rewards stay in d_rw_step
     void reward_mlp_rows(const RewMlpRowsArgs& rows);
     void traj_mlp_reward_mlp(const float* d_states, const float* d_seq, int batch, int horizon, float* d_states_out, float* d_rewards_out);
     // learned terminal value (bbmpc_set_terminal_value_mlp; bbmpc_mlp.hip, kernels_reward_mlp.hpp): a
@@ -384,6 +384,20 @@ struct Engine {
                                 int is_normalized, const float* const* stats, float terminal_weight);
     void rollout_terminal_value(int mode, bool pen, RolloutArgs& ra);
     void terminal_value_rows(const float* d_states, int batch, float* d_out);
+    // discounted, termination-aware returns (bbmpc_set_return_shaping; bbmpc_mlp.hip, kernels_return_shaping.hpp, DESIGN.md
+    // section 8q).  While it is on every rollout of the handle records the trajectory and ends in k_shaped_return, which
+    // walks each candidate's steps with the discount and the state box; a value network then enters through
+    // k_reward_mlp_rows on the last plane, not through k_value_mlp_terminal.  Routed as value_on() handles are: one launch
+    // sequence per iteration.  One-step calls, the record and bbmpc_predict_trajectories never read it.
+    bool sh_on = false;
+    float sh_gamma = 1.0f, sh_term_reward = 0.0f;
+    DevBuf<float> d_sh_box, d_sh_vterm;                 // [2][S] lo | hi; [A][Nst] V of the last plane
+    DevBuf<int> d_sh_tsteps;                            // [A][Nst] of the most recent rollout ...
+    int sh_last_npop = 0, sh_last_Nst = 0;              // ... and its shape (0: nothing rolled out since shaping was set)
+    bool shaping_on() const { return sh_on; }
+    void set_return_shaping(float discount, const float* state_lo, const float* state_hi, float terminal_reward);
+    void rollout_shaped(int mode, bool pen, RolloutArgs& ra);
+    void termination_steps(int32_t* out, int n);
     // plan gradients (bbmpc_plan_gradient; bbmpc_mlp.hip, kernels_plan_grad.hpp): dR/da through the
     // three networks.  The setters keep the raw weights on the host (nothing else of them changes); the first gradient call
     // after a (re)install packs W and W^T of every layer with mlp_pack_layer into buffers of the feature's own.

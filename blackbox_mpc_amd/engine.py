@@ -166,6 +166,29 @@ class Engine:
     def evaluate_terminal_value_dev(self, d_states, batch, d_values):
         L.check(L.lib.bbmpc_evaluate_terminal_value_dev(self._h, ctypes.c_void_p(d_states), int(batch), ctypes.c_void_p(d_values)))
 
+    def set_return_shaping(self, discount=1.0, state_low=None, state_high=None, terminal_reward=0.0):
+        """Discounted, termination-aware returns of a DYN_MLP handle (bbmpc_set_return_shaping): candidates score
+        sum_t discount^t r_t up to the first state outside [state_low, state_high] (each None or [dim_S], -inf / +inf =
+        unbounded), plus discount^T * terminal_reward there, or plus discount^H * w * V(s_H) when they never leave the box
+        and a value network is installed.  discount = 1 with both bounds None switches shaping off."""
+        bounds = []
+        for b in (state_low, state_high):
+            if b is not None:
+                b = L.f32c(np.asarray(b, np.float32).reshape(-1))
+                if b.shape != (self.S,):         # the C side reads dim_S floats from this buffer
+                    raise ValueError("a state bound must be [%d], got %s" % (self.S, b.shape))
+            bounds.append(b)
+        L.check(L.lib.bbmpc_set_return_shaping(self._h, float(discount), L.ptr(bounds[0]), L.ptr(bounds[1]), float(terminal_reward)))
+
+    def termination_steps(self, n_pop=None):
+        """T of the most recent rollout (bbmpc_get_termination_steps): int32 [n_pop, A] in evaluate's layout, the first
+        terminal step in 1 .. H, 0 = the candidate never left the box.  n_pop: the candidates of that rollout -- by
+        default what the handle says it rolled out (bbmpc_get_state "shaping_n_pop")."""
+        n = int(n_pop if n_pop is not None else self.get_state("shaping_n_pop", (1,))[0])
+        out = np.empty((self.A, max(1, n)), np.int32)
+        L.check(L.lib.bbmpc_get_termination_steps(self._h, L.ptr(out), int(out.size)))
+        return np.ascontiguousarray(out.T)
+
     def set_mlp_ensemble(self, members):
         """Model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble): `members` is a list of (weights, biases)
         pairs or of objects with `.weights` / `.biases`, each of the shape of the model set_mlp installed; particle p

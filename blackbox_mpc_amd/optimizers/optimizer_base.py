@@ -60,6 +60,10 @@ class OptimizerBase:
         if value is not None and eng.__dict__.get("_val_version") != getattr(value, "_version", 0):
             from ..trajectory_evaluators.deterministic import configure_terminal_value
             configure_terminal_value(eng, self._trajectory_evaluator)
+        term = getattr(self._trajectory_evaluator, "_termination", None)          # a box whose bounds were changed, likewise
+        if term is not None and eng.__dict__.get("_shaping_version", (0, 0, 0))[2] != term._version:
+            from ..trajectory_evaluators.deterministic import configure_return_shaping
+            configure_return_shaping(eng, self._trajectory_evaluator)
         prior = getattr(self, "_policy_prior", None)                              # a refitted policy prior, likewise
         if prior is not None and eng.__dict__.get("_prior_version") != getattr(prior[0], "_version", 0):
             self._configure_policy_prior(eng)
@@ -135,8 +139,8 @@ class OptimizerBase:
             self._engine.reset()
 
     def set_trajectory_evaluator(self, trajectory_evaluator):
-        from ..trajectory_evaluators.deterministic import (configure_dynamics, configure_reward, configure_terminal_value,
-                                                           plugin_kinds)
+        from ..trajectory_evaluators.deterministic import (configure_dynamics, configure_return_shaping, configure_reward,
+                                                           configure_terminal_value, plugin_kinds, shaping_on)
         self._trajectory_evaluator = trajectory_evaluator
         if type(self)._engine_optimizer == L.OPT_NONE:
             return
@@ -151,6 +155,9 @@ class OptimizerBase:
                                  "(DeterministicMLP), a learned reward (LearnedRewardMLP) and the deterministic evaluator, got %s, %s "
                                  "and %s" % (type(df).__name__, type(trajectory_evaluator._reward_function).__name__,
                                              type(trajectory_evaluator).__name__))
+        if grad is not None and shaping_on(trajectory_evaluator):
+            raise ValueError("grad_steps > 0 beside discount / termination: the gradient steps climb the undiscounted return over the "
+                             "full horizon, not the shaped one")
         if self._engine is not None:
             self._engine.close()
         quirks = self._quirks | int(getattr(trajectory_evaluator, "_quirks", 0))
@@ -163,6 +170,7 @@ class OptimizerBase:
         configure_dynamics(self._engine, h)
         configure_reward(self._engine, trajectory_evaluator._reward_function)
         configure_terminal_value(self._engine, trajectory_evaluator)
+        configure_return_shaping(self._engine, trajectory_evaluator)
         particles = getattr(trajectory_evaluator, "particle_settings", None)
         if particles is not None:                     # a ParticleTrajectoryEvaluator: (num_particles, process_noise_std, risk_kappa)
             self._engine.set_particles(*particles)

@@ -20,9 +20,12 @@ class MPCPolicy(ModelBasedBasePolicy):
                  reward_function=None, env_action_space=None, env_observation_space=None,
                  dynamics_function=None, dynamics_handler=None, true_model=False, optimizer_name=None,
                  num_agents=None, save_model_frequency=1, saved_model_dir=None, terminal_value=None, terminal_weight=1.0,
-                 refine_steps=0, refine_lr=0.05, refine_device=False, **optimizer_args):
+                 refine_steps=0, refine_lr=0.05, refine_device=False, discount=1.0, termination=None, **optimizer_args):
         """terminal_value / terminal_weight: a LearnedValueMLP that closes the planning horizon (handed to the
         DeterministicTrajectoryEvaluator this constructor builds; an evaluator passed in takes them itself).
+        discount / termination: a discount in (0, 1] and a utils.termination.StateBoxTermination, handed to that evaluator
+        likewise: plans score sum_t discount^t r_t up to the first state outside the box (bbmpc_set_return_shaping); not
+        together with refine_steps or grad_steps, whose gradient is that of the unshaped return.
         refine_steps / refine_lr: with refine_steps > 0 every `act` refines the optimizer's plan by that many projected
         gradient steps on the model return (utils.plan_refinement.refine_plan, Engine.plan_gradient) and acts on the refined
         plan's first action; needs learned dynamics and a LearnedRewardMLP.  The optimizer's own warm start is left alone.
@@ -51,6 +54,14 @@ class MPCPolicy(ModelBasedBasePolicy):
         if trajectory_evaluator is not None and terminal_value is not None:
             raise ValueError("terminal_value goes to the trajectory evaluator: construct it with terminal_value=, "
                              "or leave trajectory_evaluator to MPCPolicy")
+        if trajectory_evaluator is not None and (termination is not None or float(discount) != 1.0):
+            raise ValueError("discount / termination go to the trajectory evaluator: construct it with discount=, termination=, "
+                             "or leave trajectory_evaluator to MPCPolicy")
+        from ..trajectory_evaluators.deterministic import shaping_on
+        shaped = (termination is not None or float(discount) != 1.0) if trajectory_evaluator is None else shaping_on(trajectory_evaluator)
+        if shaped and (self._refine_steps > 0 or int(optimizer_args.get("grad_steps", 0) or 0) > 0):
+            raise ValueError("refine_steps / grad_steps beside discount / termination: the gradient is that of the undiscounted "
+                             "return over the full horizon, not of the shaped one")
         if trajectory_evaluator is None:
             if dynamics_handler is None:
                 dynamics_handler = SystemDynamicsHandler(
@@ -61,7 +72,8 @@ class MPCPolicy(ModelBasedBasePolicy):
             trajectory_evaluator = DeterministicTrajectoryEvaluator(reward_function=reward_function,
                                                                     system_dynamics_handler=dynamics_handler,
                                                                     terminal_value=terminal_value,
-                                                                    terminal_weight=terminal_weight)
+                                                                    terminal_weight=terminal_weight,
+                                                                    discount=discount, termination=termination)
         super(MPCPolicy, self).__init__(trajectory_evaluator=trajectory_evaluator)
         if optimizer is None:
             if num_agents is None:

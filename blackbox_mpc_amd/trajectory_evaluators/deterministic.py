@@ -173,16 +173,59 @@ def terminal_value_stale(engine, evaluator):
     return value is not None and engine.__dict__.get("_val_version") != getattr(value, "_version", 0)
 
 
+def shaping_on(evaluator):
+    """Whether the evaluator shapes its returns: a discount below 1 or a termination (discount=, termination=)."""
+    return getattr(evaluator, "_termination", None) is not None or getattr(evaluator, "_discount", 1.0) != 1.0
+
+
+def _shaping_version(evaluator):
+    term = getattr(evaluator, "_termination", None)
+    return (getattr(evaluator, "_discount", 1.0), id(term), getattr(term, "_version", 0))
+
+
+def configure_return_shaping(engine, evaluator):
+    """Upload the evaluator's discount and StateBoxTermination (discount=, termination=); nothing to do without either."""
+    if not shaping_on(evaluator):
+        return
+    term = evaluator._termination
+    if term is None:
+        engine.set_return_shaping(evaluator._discount)
+    else:
+        lo, hi = term.bounds(engine.S)
+        engine.set_return_shaping(evaluator._discount, lo, hi, term.terminal_reward)
+    engine._shaping_version = _shaping_version(evaluator)
+
+
+def return_shaping_stale(engine, evaluator):
+    """A box whose bounds or terminal reward changed since they were uploaded (or that was never uploaded to this engine)."""
+    return shaping_on(evaluator) and engine.__dict__.get("_shaping_version") != _shaping_version(evaluator)
+
+
+_SHAPED_GRADIENT = ("%s beside discount / termination: the differentiated return is the undiscounted sum over the full "
+                    "horizon, not the shaped one (construct the evaluator with discount=1.0, termination=None)")
+
+
 class DeterministicTrajectoryEvaluator(EvaluatorBase):
-    def __init__(self, reward_function, system_dynamics_handler, quirks=0, terminal_value=None, terminal_weight=1.0):
+    def __init__(self, reward_function, system_dynamics_handler, quirks=0, terminal_value=None, terminal_weight=1.0,
+                 discount=1.0, termination=None):
         """terminal_value: a LearnedValueMLP V -- candidates then score sum_t r_t + terminal_weight * V(s_H) (learned
-        dynamics only; bbmpc_set_terminal_value_mlp).  The one-step calls and predict_trajectories do not read it."""
+        dynamics only; bbmpc_set_terminal_value_mlp).  The one-step calls and predict_trajectories do not read it.
+        discount in (0, 1] / termination: a utils.termination.StateBoxTermination -- candidates then score
+        sum_t discount^t r_t up to the first state outside the box, where they collect discount^T * terminal_reward and no
+        terminal value; candidates that stay inside close with discount^H * terminal_weight * V(s_H) (learned dynamics with
+        a built-in reward or a LearnedRewardMLP; bbmpc_set_return_shaping)."""
         super().__init__(reward_function=reward_function, system_dynamics_handler=system_dynamics_handler, name=None)
         self._quirks = int(quirks)
         self._terminal_value = terminal_value
         self._terminal_weight = float(terminal_weight)
         if terminal_value is not None and not np.isfinite(self._terminal_weight):
             raise ValueError("terminal_weight must be finite")
+        self._discount = float(discount)
+        if not (np.isfinite(self._discount) and 0.0 < self._discount <= 1.0):
+            raise ValueError("discount must lie in (0, 1], got %r" % (discount,))
+        if termination is not None and not (callable(getattr(termination, "bounds", None)) and hasattr(termination, "terminal_reward")):
+            raise ValueError("termination must be a StateBoxTermination, got %r" % (termination,))
+        self._termination = termination
         self._engines = {}
 
     def _engine(self, num_agents, horizon):
@@ -202,6 +245,8 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
             configure_reward(eng, self._reward_function)
         if terminal_value_stale(eng, self):
             configure_terminal_value(eng, self)
+        if return_shaping_stale(eng, self):
+            configure_return_shaping(eng, self)
         if eng._param_fns:
             from ..utils.device_functions import sync_user_params
             sync_user_params(eng)
@@ -239,6 +284,8 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
         sequence -- sum_t r_t + terminal_weight * V(s_H), actions as given, no NaN rule -- and its derivative in every
         action (Engine.plan_gradient).  Needs learned dynamics and a LearnedRewardMLP.  Refitted networks are uploaded
         first, as in __call__."""
+        if shaping_on(self):
+            raise ValueError(_SHAPED_GRADIENT % "value_and_gradient")
         seq = np.asarray(action_sequences, np.float32)
         if seq.ndim != 4:
             raise ValueError("action_sequences must be [n, num_agents, planning_horizon, dim_U]")
@@ -253,6 +300,8 @@ class DeterministicTrajectoryEvaluator(EvaluatorBase):
     def refine_plans_rows(self, states, plans, steps, lr, method="adam"):
         """states [B,S], plans [B,Hq,U] -> (plans [B,Hq,U], returns [B]): Engine.refine_plans (keep-best, the engine's own
         action bounds) on the engine value_and_gradient uses, so that refitted networks are uploaded first."""
+        if shaping_on(self):
+            raise ValueError(_SHAPED_GRADIENT % "refine_plans_rows")
         plans = np.asarray(plans, np.float32)
         if plans.ndim != 3:
             raise ValueError("plans must be [B, planning_horizon, dim_U]")

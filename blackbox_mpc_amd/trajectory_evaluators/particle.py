@@ -43,7 +43,7 @@ def quantile_rank(tau, num_particles):
 
 class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
     def __init__(self, reward_function, system_dynamics_handler, num_particles, process_noise_std, risk_kappa=0.0,
-                 quirks=0, risk_alpha=None, terminal_value=None, terminal_weight=1.0):
+                 quirks=0, risk_alpha=None, terminal_value=None, terminal_weight=1.0, discount=1.0, termination=None):
         """process_noise_std: a scalar or [dim_S], >= 0 -- for a learned model SystemDynamicsHandler.residual_std() is
         the natural choice.  risk_kappa > 0 prefers candidates whose return varies little over the particles.
         risk_alpha in (0, 1] scores the mean of the ceil(risk_alpha * num_particles) worst returns instead (CVaR; not
@@ -54,6 +54,9 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
         if terminal_value is not None:
             raise NotImplementedError("ParticleTrajectoryEvaluator has no terminal term yet: a LearnedValueMLP closes the rollouts of "
                                       "DeterministicTrajectoryEvaluator only")
+        if termination is not None or float(discount) != 1.0:
+            raise NotImplementedError("ParticleTrajectoryEvaluator has no discounted or termination-aware return yet: discount / "
+                                      "termination shape the rollouts of DeterministicTrajectoryEvaluator only")
         super().__init__(reward_function, system_dynamics_handler, quirks=quirks)
         p = int(num_particles)
         if not 1 <= p <= 64:

@@ -33,7 +33,8 @@ class ModelEnvironment:
         nxt = self._ev.predict_next_state(self._state, actions)
         rew = self._ev.evaluate_next_reward(self._state, nxt, actions)
         self._state = nxt
-        return nxt.copy(), rew, False, {}
+        term = getattr(self._ev, "_termination", None)      # the evaluator's StateBoxTermination: done per agent
+        return nxt.copy(), rew, (term(nxt) if term is not None else False), {}
 
 
 def _sample(env, horizon, policy, episode_step, exploration_noise=False, tf_writer=None):

@@ -11,11 +11,15 @@ from ..dynamics_functions.deterministic_mlp import _ACT_NAME, _act_code
 from ..reward_functions.learned_reward_mlp import numpy_activation
 
 
-def value_targets(traj_obs, traj_rews, n_step, gamma=1.0, bootstrap=None):
+def value_targets(traj_obs, traj_rews, n_step, gamma=1.0, bootstrap=None, terminated=None):
     """n-step return targets of one episode: observations [T+1, A, S], rewards [T, A] -> (states [M, S], targets [M]) with
     M = (T - n_step + 1) * A rows, one per (t, agent) with t <= T - n_step (full windows only; none when n_step > T):
         y_t = sum_{k < n_step} gamma^k r_{t+k}  (+ gamma^n_step * bootstrap(s_{t+n_step}) when `bootstrap` is a callable
-    states [B, S] -> [B])."""
+    states [B, S] -> [B]).
+    terminated: bool [T, A] (or [T] for every agent), true where step t reached a terminal state.  A window then stops at
+    its first terminal step -- that step's reward counts, nothing behind it does -- and takes no bootstrap: what the shaped
+    returns of the planner do (bbmpc_set_return_shaping).  Rows whose own step lies behind an agent's first terminal step
+    are still returned: the caller decides what an episode is.  None reproduces the targets without it."""
     obs = np.asarray(traj_obs, np.float32)
     rews = np.asarray(traj_rews, np.float32)
     n_step = int(n_step)
@@ -30,11 +34,22 @@ def value_targets(traj_obs, traj_rews, n_step, gamma=1.0, bootstrap=None):
     if M <= 0:
         return np.zeros((0, S), np.float32), np.zeros((0,), np.float32)
     y = np.zeros((M, A), np.float64)
-    for k in range(n_step):
-        y += float(gamma) ** k * rews[k:k + M].astype(np.float64)
+    if terminated is None:
+        for k in range(n_step):
+            y += float(gamma) ** k * rews[k:k + M].astype(np.float64)
+        alive = None
+    else:
+        done = np.asarray(terminated, bool)
+        if done.shape not in ((T,), (T, A)):
+            raise ValueError("terminated must be [T] or [T, A] = [%d, %d], got %s" % (T, A, done.shape))
+        done = np.broadcast_to(done.reshape(T, -1), (T, A))
+        alive = np.ones((M, A), bool)                  # the window has not met a terminal step yet
+        for k in range(n_step):
+            y += np.where(alive, float(gamma) ** k * rews[k:k + M].astype(np.float64), 0.0)
+            alive = alive & ~done[k:k + M]
     if bootstrap is not None:
         tail = np.asarray(bootstrap(obs[n_step:n_step + M].reshape(M * A, S)), np.float64).reshape(M, A)
-        y += float(gamma) ** n_step * tail
+        y += float(gamma) ** n_step * tail if alive is None else np.where(alive, float(gamma) ** n_step * tail, 0.0)
     return obs[:M].reshape(M * A, S).copy(), y.reshape(M * A).astype(np.float32)
 
 
@@ -142,14 +157,21 @@ class LearnedValueMLP:
         self.train_loss, self.validation_loss = [float(v) for v in losses[0]], [float(v) for v in losses[1]]
         return losses
 
-    def train_on_rollouts(self, traj_obs, traj_rews, n_step, gamma=1.0, bootstrap=False, **train_args):
+    def train_on_rollouts(self, traj_obs, traj_rews, n_step, gamma=1.0, bootstrap=False, terminated=None, **train_args):
         """Add the episodes perform_rollouts returned (observations [T+1,A,S], rewards [T,A] each) to those collected so
         far and refit on the n-step targets of all of them.  bootstrap=True closes every window with the model's own
-        current prediction, gamma^n_step * V(s_{t+n_step}) (fitted n-step TD); False fits plain n-step returns."""
-        for obs, rews in zip(traj_obs, traj_rews):
-            self._episodes.append((np.asarray(obs, np.float32), np.asarray(rews, np.float32)))
+        current prediction, gamma^n_step * V(s_{t+n_step}) (fitted n-step TD); False fits plain n-step returns.
+        terminated: one bool [T,A] array per episode (value_targets' argument; e.g. StateBoxTermination(obs[1:])), so that
+        V and a planner with the same termination agree on where an episode ends."""
+        traj_obs, traj_rews = list(traj_obs), list(traj_rews)
+        dones = [None] * len(traj_obs) if terminated is None else list(terminated)
+        if len(dones) != len(traj_obs):
+            raise ValueError("terminated: one array per episode expected, got %d for %d episodes" % (len(dones), len(traj_obs)))
+        for obs, rews, done in zip(traj_obs, traj_rews, dones):
+            self._episodes.append((np.asarray(obs, np.float32), np.asarray(rews, np.float32)) if done is None else
+                                  (np.asarray(obs, np.float32), np.asarray(rews, np.float32), np.asarray(done, bool)))
         boot = self.__call__ if bootstrap else None
-        rows = [value_targets(o, r, n_step, gamma, boot) for o, r in self._episodes]
+        rows = [value_targets(e[0], e[1], n_step, gamma, boot, e[2] if len(e) > 2 else None) for e in self._episodes]
         states = np.concatenate([r[0] for r in rows], axis=0)
         targets = np.concatenate([r[1] for r in rows], axis=0)
         if states.shape[0] == 0:

@@ -236,6 +236,35 @@ int bbmpc_set_terminal_value_mlp(bbmpc_handle h, int32_t n_layers, const int32_t
 int bbmpc_evaluate_terminal_value(bbmpc_handle h, const float* states, int32_t batch, float* values);
 int bbmpc_evaluate_terminal_value_dev(bbmpc_handle h, const float* d_states, int32_t batch, float* d_values);
 
+/* Discounted, termination-aware returns of a learned-model handle (BBMPC_DYN_MLP with a built-in reward or BBMPC_REW_MLP;
+ * DESIGN.md section 8q).  state_lo / state_hi are each NULL or dim_s floats (-inf / +inf: unbounded in that direction).
+ * Per candidate, with s_0 the agent's state, s_1 .. s_H the model's states, a_t the clipped actions, r_t the step rewards:
+ *     outside(s) = any i: s[i] < state_lo[i] or s[i] > state_hi[i]        (false on NaN: a NaN state does not terminate)
+ *     g = 1; alive = true; R = 0; T = 0
+ *     for t = 0 .. H-1:   R += g * r_t
+ *                         if outside(s_{t+1}):  R += g * terminal_reward; alive = false; T = t + 1; stop
+ *                         g *= discount
+ *     if isnan(R): R = -1e6;   R += -(bound penalty)
+ *     if alive and a value network is installed:  R += g * terminal_weight * V(s_H), a NaN term -> R = -1e6
+ * The step that reaches a terminal state counts; nothing behind it is read into the score (a NaN there does not reach R).
+ * While shaping is on, bbmpc_evaluate[_dev] and the control steps of all six optimizers (agent and population shards
+ * included) record the trajectory and end in one more kernel that walks it: one launch sequence per iteration, no
+ * graph-replayed form.  The control step's record, bbmpc_predict_next_state, bbmpc_evaluate_next_reward,
+ * bbmpc_predict_trajectories and bbmpc_rollout_episode are unchanged.  discount == 1 with both bounds NULL switches shaping
+ * off and restores the handle's previous routing and scores bit for bit.  Refused before anything is allocated, the handle
+ * stays as it was -- BBMPC_E_UNSUPPORTED: analytic or BBMPC_DYN_USER dynamics, a BBMPC_REW_USER reward (HIP source or
+ * callback), an inverse target transform, particles on, gradient refinement on (and, the other way round,
+ * bbmpc_set_inverse_transform_source, bbmpc_set_particles (num_particles > 0) and bbmpc_set_grad_refine (steps > 0) on a
+ * handle with shaping on; bbmpc_plan_gradient[_dev] and bbmpc_refine_plans[_dev] are refused while it is on, their return
+ * is not the shaped one); BBMPC_E_INVALID: a discount outside (0, 1] or not finite, a NaN bound, state_lo[i] >
+ * state_hi[i], a non-finite terminal_reward. */
+int bbmpc_set_return_shaping(bbmpc_handle h, float discount, const float* state_lo, const float* state_hi, float terminal_reward);
+
+/* T of the most recent rollout (bbmpc_evaluate, or the last iteration of a control step): out [num_agents][n_pop] int32, the
+ * first terminal step in 1 .. H or 0 when the candidate never left the box; n = num_agents * n_pop.  BBMPC_E_STATE while
+ * shaping is off or before anything was rolled out. */
+int bbmpc_get_termination_steps(bbmpc_handle h, int32_t* out, int32_t n);
+
 /* Plan gradients: the derivative of the model return with respect to every action of a plan, through the learned dynamics
  * (BBMPC_DYN_MLP, bbmpc_set_mlp), the learned reward (BBMPC_REW_MLP, bbmpc_set_reward_mlp, any input_mask) and, when one is
  * installed, the learned terminal value.  For row b, s_0 = states[b] and a_0 .. a_{horizon-1} = seq[b]:
