@@ -202,6 +202,10 @@ Engine::Engine(const bbmpc_config& c) : cfg(c) {
         sw.refit_wgs = ival("BBMPC_REFIT_WGS", 0);
         sw.mlp_wave = ival("BBMPC_MLP_WAVE", 1);
         sw.linger_us = std::max(0, ival("BBMPC_LINGER_US", 200));
+        if (const char* fb = getenv("BBMPC_FUSED_BOUND")) {
+            sw.fused_bound = atoi(fb);
+            REQUIRE(sw.fused_bound == 512 || sw.fused_bound == 1024, BBMPC_E_INVALID, "BBMPC_FUSED_BOUND must be 512, 1024 or unset");
+        }
         linger_test_quit = ival("BBMPC_LINGER_TEST_QUIT", 0) - 1;
         host_seq = (uint32_t)ival("BBMPC_TEST_HOST_SEQ", 0);      // test hook: where the completion sequence numbers start (the 16-bit tag's wrap)
         sw.balance = ival("BBMPC_BALANCE", 0);      // accepted and ignored: pacing SIMD mates in the fused pendulum rollout measured slower and is gone

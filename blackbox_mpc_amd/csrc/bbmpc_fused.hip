@@ -32,26 +32,56 @@ bool Engine::use_fused() const {
     return (long)N <= 2048 || A >= 64;
 }
 
-static void note_inst(Engine& e, int opt, bool samples_lds, bool fastm, int inj, int ilp, bool linger) {
-    snprintf(e.dominant_inst, sizeof(e.dominant_inst), "k_fused_pendulum<%d, %s, %s, %d, %d, %s>", opt, samples_lds ? "true" : "false",
-             fastm ? "true" : "false", inj, ilp, linger ? "true" : "false");
+// how much LDS a samples-in-LDS instantiation may ask for
+static constexpr size_t fused_lds_limit() {
+#ifdef BBMPC_KERNEL_DBG
+    return 158 * 1024;   // the debug clocks live in static LDS
+#else
+    return 160 * 1024;   // all of a CU's LDS
+#endif
 }
 
+static void note_inst(Engine& e, int opt, bool samples_lds, bool fastm, int inj, int ilp, int maxt, bool linger) {
+    snprintf(e.dominant_inst, sizeof(e.dominant_inst), "k_fused_pendulum<%d, %s, %s, %d, %d, %d, %s>", opt, samples_lds ? "true" : "false",
+             fastm ? "true" : "false", inj, ilp, maxt, linger ? "true" : "false");
+}
+
+// Which instantiations exist with a launch bound of 512 threads (256 VGPRs a wave instead of 128): CEM with the samples in
+// LDS, on prefetched draws (the control step of DESIGN.md 9) and on the caller's injected draws (so that a test can put
+// designed populations through the same selection and tail).  Everything else has the 1024-thread form only.
+template <int OPT, int INJ, int ILP>
+constexpr bool fused_has_bound512() { return OPT == FOPT_CEM && (INJ == 2 || INJ == 1) && ILP == 1; }
+
+template <int OPT, bool FASTM, int INJ, int ILP, int MAXT>
+static void launch_fused5(Engine& e, FusedArgs& fa, int threads, size_t lds_base, size_t lds_samples);
+
+// THE selection point of the launch bound: the 512-thread form where it exists, the workgroup fits it and
+// BBMPC_FUSED_BOUND does not say 1024.  launch_fused5<.., MAXT> launches nothing but MAXT-bounded kernels with `threads`
+// threads (its samples-in-global branch, which has no 512 form, is reached with MAXT = 1024 only: see there).
 template <int OPT, bool FASTM, int INJ, int ILP>
 static void launch_fused4(Engine& e, FusedArgs& fa, int threads, size_t lds_base, size_t lds_samples) {
-#ifdef BBMPC_KERNEL_DBG
-    const size_t limit = 158 * 1024;   // the debug clocks live in static LDS
-#else
-    const size_t limit = 160 * 1024;   // all of a CU's LDS
-#endif
+    if constexpr (fused_has_bound512<OPT, INJ, ILP>()) {
+        if (threads <= 512 && e.sw.fused_bound != 1024 && lds_base + lds_samples <= fused_lds_limit()) {
+            REQUIRE(threads <= 512, BBMPC_E_HIP, "internal: a 512-bounded k_fused_pendulum launched with more threads");
+            launch_fused5<OPT, FASTM, INJ, ILP, 512>(e, fa, threads, lds_base, lds_samples);
+            return;
+        }
+    }
+    REQUIRE(threads <= 1024, BBMPC_E_HIP, "internal: k_fused_pendulum launched with more than 1024 threads");
+    launch_fused5<OPT, FASTM, INJ, ILP, 1024>(e, fa, threads, lds_base, lds_samples);
+}
+
+template <int OPT, bool FASTM, int INJ, int ILP, int MAXT>
+static void launch_fused5(Engine& e, FusedArgs& fa, int threads, size_t lds_base, size_t lds_samples) {
+    const size_t limit = fused_lds_limit();
     if (lds_base + lds_samples <= limit) {
         fa.test_quit_agent = -1;
         if constexpr (INJ == 2 && FASTM && ILP == 1) {
             if (e.linger_launch && e.subset_n == 0 && fa.done_flag && e.tail.event == nullptr) {
                 // the resident form: this launch serves the current call and then every workgroup waits for its agent's next
                 // request on its own (kernels_fused.hpp)
-                auto fl = k_fused_pendulum<OPT, true, FASTM, INJ, ILP, true>;
-                note_inst(e, OPT, true, FASTM, INJ, ILP, true);
+                auto fl = k_fused_pendulum<OPT, true, FASTM, INJ, ILP, MAXT, true>;
+                note_inst(e, OPT, true, FASTM, INJ, ILP, MAXT, true);
                 ensure_max_lds((const void*)fl, (int)limit);
                 // the completion lines carry the packed record itself: five floats in ten tagged half-words
                 if (e.rec != kCompletionRecordFloats) throw HipError(BBMPC_E_HIP, "internal: the resident pendulum kernel's record is not 5 floats");
@@ -83,8 +113,8 @@ static void launch_fused4(Engine& e, FusedArgs& fa, int threads, size_t lds_base
         }
         if (e.subset_n > 0) {
             // the agents whose resident workgroups had left when this control step was posted (Engine::resident_step)
-            auto fs = k_fused_pendulum<OPT, true, FASTM, INJ, ILP>;
-            note_inst(e, OPT, true, FASTM, INJ, ILP, false);
+            auto fs = k_fused_pendulum<OPT, true, FASTM, INJ, ILP, MAXT>;
+            note_inst(e, OPT, true, FASTM, INJ, ILP, MAXT, false);
             ensure_max_lds((const void*)fs, (int)limit);
             fa.amap = reinterpret_cast<const int*>(e.sync_dev(e.amap_host()));
             hipLaunchKernelGGL(fs, dim3(e.subset_n), dim3(threads), lds_base + lds_samples, e.stream, fa);
@@ -92,14 +122,17 @@ static void launch_fused4(Engine& e, FusedArgs& fa, int threads, size_t lds_base
             e.subset_n = 0;
             return;
         }
-        auto fn = k_fused_pendulum<OPT, true, FASTM, INJ, ILP>;
-        note_inst(e, OPT, true, FASTM, INJ, ILP, false);
+        auto fn = k_fused_pendulum<OPT, true, FASTM, INJ, ILP, MAXT>;
+        note_inst(e, OPT, true, FASTM, INJ, ILP, MAXT, false);
         ensure_max_lds((const void*)fn, (int)limit);
         launch_with_tail(e, fn, dim3(e.A), dim3(threads), lds_base + lds_samples, fa);
-    } else {
+    } else if constexpr (MAXT == 1024) {
         auto fn = k_fused_pendulum<OPT, false, FASTM, INJ, ILP>;
-        note_inst(e, OPT, false, FASTM, INJ, ILP, false);
+        note_inst(e, OPT, false, FASTM, INJ, ILP, 1024, false);
         launch_with_tail(e, fn, dim3(e.A), dim3(threads), lds_base, fa);
+    } else {
+        // (launch_fused4 picks 512 only where the samples fit LDS)
+        throw HipError(BBMPC_E_HIP, "internal: the samples-in-global k_fused_pendulum has no 512-thread form");
     }
     HIP_CHECK(hipGetLastError());
 }
@@ -244,6 +277,9 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
         }
     }
     const bool use_pf = pf_mode == 1 && fa.inj == nullptr && pf_nit > 0;
+    // k_noise_fill's rows hold Q = ceil(H*U / 4) blocks, and the kernel's consumers walk ceil(H / 4) of them per trajectory
+    // (the first-draws prefetch and the rollouts take the row stride from noise_block_index with that one Q): the same only at U == 1
+    REQUIRE(!use_pf || U == 1, BBMPC_E_HIP, "internal: prefetched draws need U == 1");
     if (use_pf) {
         const int64_t c = (int64_t)step / pf_steps;
         const int pb = (int)(c & 1), nb = pb ^ 1;

@@ -187,6 +187,8 @@ struct Engine {
         int refit_wgs = 0;                // BBMPC_REFIT_WGS=n: workgroups per agent in k_refit_cem_v2 (0 = by problem size)
         int mlp_wave = 1;                 // BBMPC_MLP_WAVE=0: never the one-wave-per-tile kernel for small networks
         int linger_us = 200;              // BBMPC_LINGER_US: how long a one-agent control-step kernel waits for the next call (0 = never)
+        int fused_bound = 0;              // BBMPC_FUSED_BOUND: 512 / 1024 = the launch bound of k_fused_pendulum where both forms exist (1024: the
+                                          // 1024-thread form at every size), 0 = unset: 512 wherever the workgroup fits it
         int balance = 0;               // BBMPC_BALANCE: parsed, ignored (the rollout's pacing of SIMD mates was taken out)
         int ilp = 1;                   // BBMPC_ILP
         bool refit_v1 = false;         // BBMPC_REFIT_V1

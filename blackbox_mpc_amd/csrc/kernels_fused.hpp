@@ -117,8 +117,16 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid, int nw)
 #ifndef BBMPC_FUSED_ACTIONS_AHEAD
 #define BBMPC_FUSED_ACTIONS_AHEAD 1
 #endif
-template <int OPT, bool SAMPLES_LDS, bool FASTM, int INJ, int ILP, bool LINGER = false>
-__global__ void k_fused_pendulum(FusedArgs p) {
+// 0: the 512-thread CEM form runs its tail behind the last statistics barrier like every other form (A/B builds)
+#ifndef BBMPC_FUSED_EARLY_TAIL
+#define BBMPC_FUSED_EARLY_TAIL 1
+#endif
+// MAXT: the largest workgroup an instantiation may be launched with (its launch bound, hence its register budget: 1024
+// threads leave a wave 128 VGPRs, 512 threads 256 at the same two waves per SIMD).  Engine::optimize_fused's launch_fused4
+// is the one place that picks it.
+template <int OPT, bool SAMPLES_LDS, bool FASTM, int INJ, int ILP, int MAXT = 1024, bool LINGER = false>
+__global__ __launch_bounds__(MAXT) void k_fused_pendulum(FusedArgs p) {
+    static_assert(MAXT == 512 || MAXT == 1024, "k_fused_pendulum: a launch bound of 512 or 1024 threads");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int a = p.amap ? p.amap[blockIdx.x] : (int)blockIdx.x;
     const int tid = threadIdx.x;
@@ -217,10 +225,20 @@ __global__ void k_fused_pendulum(FusedArgs p) {
     // of the sequence number; words 10..14 the tag alone, word 15 the whole sequence number.  The host accepts the line
     // when words 0..9 and 15 all name the call it waits for (completion_line.hpp), so neither the order in which the
     // words arrive nor how the fabric splits the store matters, and nothing has to be waited for in front of it.
+    // CEM at the 512-thread register budget: the tail runs IN FRONT of the last iteration's closing statistics barrier, from
+    // the row-0 mean thread 0 has just formed in a register (see the statistics below and the comment at the tail).  At 128
+    // registers the same code put spill reloads into the selection (profiles/control_step_tail.md).
+    constexpr bool EARLY_TAIL = BBMPC_FUSED_EARLY_TAIL && MAXT == 512 && OPT == FOPT_CEM;
     const bool tail_lanes = LINGER ? tid < 64 : tid == 0;
     auto tail = [&](float act_in) {
         BB_DBG(38);
         float s[3] = {s0, s1, s2};
+        // EARLY_TAIL puts this model step inside the iteration loop, where the state is loop-invariant: left alone, the
+        // compiler hoists sin(theta + pi) in front of the loop as +15 sin and forms acc = 3u - 15 sin here.  Equal for every
+        // finite value, but a NaN state then leaves the step with its sign bit set where the other forms' -15 sin + 3u
+        // leaves it clear.  The state is made opaque here so that the step is compiled in place, operation for operation
+        // as written (models.hpp), and the record's bits are the same in every form, NaNs included.
+        if constexpr (EARLY_TAIL) asm volatile("" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]));
         float act[1];
         act[0] = add_noise_s ? exploration_apply(act_in, noise_term(), lo, hi) : act_in;
         BB_DBG(35);
@@ -305,7 +323,9 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                     [[maybe_unused]] gvec4sp mine4 = nullptr;
                     [[maybe_unused]] gvec4s cur4 = {1.0f, 1.0f, 1.0f, 1.0f};
                     if constexpr (INJ == 2) {            // draws prefetched by k_noise_fill, one float4 per 4 steps
-                        mine4 = (gvec4sp)(reinterpret_cast<const float4*>(inj_s) + noise_block_index(it, p.A, a, p.Nst, n, nb4));   // (U == 1: nb4 == Q)
+                        // (the row stride is prefetch_first's Q, from which pf0 came; the host requires U == 1 for this layout,
+                        // Engine::optimize_fused, and then nb4 == Q blocks are walked)
+                        mine4 = (gvec4sp)(reinterpret_cast<const float4*>(inj_s) + noise_block_index(it, p.A, a, p.Nst, n, (p.HU + 3) >> 2));
                         if (n == tid) cur4 = pf0;                    // fetched while the previous iteration refitted
                         else cur4 = mine4[0];
                     }
@@ -608,6 +628,7 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                 int ei[EC];
 #pragma unroll
                 for (int i = 0; i < EC; ++i) ei[i] = (small_k && sub + 16 * i < p.k) ? eidx[sub + 16 * i] : -1;
+                [[maybe_unused]] float mean_row0 = 0.0f;      // EARLY_TAIL: thread 0's copy of the mean[0] it stores below
                 for (int j = tid >> 4; j < ((p.HU + 3) & ~3); j += nthr >> 4) {       // all 16 lanes of a row share j
                     const bool live = j < p.HU;
                     const float* row = samp + (size_t)(live ? j : 0) * p.Nst;
@@ -644,9 +665,19 @@ __global__ void k_fused_pendulum(FusedArgs p) {
                         mean[j] = m;
                         var[j] = v;
                         sigma[j] = cem_sigma(m, v, lo, hi);
+                        if constexpr (EARLY_TAIL) { if (j == 0) mean_row0 = m; }     // (row 0 is thread 0's, in its first trip)
                     }
                 }
                 if (it == 0) BB_DBG(33);
+                if constexpr (EARLY_TAIL) {
+                    // The last iteration: the caller needs mean[0] only, and thread 0 holds the very float it has just stored
+                    // there.  Wave 0 runs the tail from it and stores the completion line / the record without waiting for the
+                    // other rows' statistics; it then joins the barrier below like every wave (no barrier is skipped, so the
+                    // order of every LDS access on either side of it is what it was).
+                    if (it + 1 == p.iters && tail_lanes) {
+                        tail(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mean_row0))));   // (wave 0's first lane is thread 0)
+                    }
+                }
                 __syncthreads();
                 action0 = mean[0];                                                   // cem.py:135
             } else if (OPT == FOPT_PI2) {
@@ -730,10 +761,14 @@ __global__ void k_fused_pendulum(FusedArgs p) {
         // ---- OptimizerBase.__call__ tail (optimizer_base.py:82-94).  (Running it from thread 0's own row-0 mean in front of
         // CEM's last statistics barrier was built too: inlined into the iteration loop it put spill reloads into the
         // selection, profiles/control_step_tail.md.)
-        if (tail_lanes) tail(action0);
+        // The 512-thread CEM form (EARLY_TAIL) has run it already, in front of the last statistics barrier, from thread 0's
+        // register copy of mean[0] -- the float action0 holds here; only a control step without iterations comes by.
+        if (tail_lanes && !(EARLY_TAIL && p.iters > 0)) tail(action0);
         // ---- state carried to the next control step, BEHIND the publish: the caller waits for the record, not for these.
         // Invariant this rests on: nothing reads mean_out / var_out / prev_mean between the completion and the end of
-        // the kernel.  The host's readers (bbmpc_get_state, the traces, every entry point but bbmpc_optimize,
+        // the kernel -- with EARLY_TAIL the completion precedes the last statistics barrier as well, i.e. the other rows'
+        // mean[] / var[] / sigma[] are still being written in LDS when the caller has its record; nothing outside the
+        // workgroup reads LDS, and the global copies are stored below as before.  The host's readers (bbmpc_get_state, the traces, every entry point but bbmpc_optimize,
         // bbmpc_optimize_gather and bbmpc_gather_wait) settle the handle first -- Engine::settle ends a resident kernel and
         // joins the stream -- and the next control step is either a launch on the same stream or a resident pass, which
         // starts from the registers kept here (m_keep), or from the copies this very thread stores below.
@@ -785,6 +820,9 @@ __global__ void k_fused_pendulum(FusedArgs p) {
             // decoded part of its state from sample values: config 3 (PI2, 8 agents x 16 waves) gave other results in
             // a few of every ten 200-step runs, depending on nothing but timing.
             unsigned* mb = (unsigned*)(red + 16);
+            // (EARLY_TAIL: wave 0 left the last iteration's statistics early for the tail, but it took part in that
+            // iteration's closing barrier and takes part in this one like every wave, so its dist_init stores to mean[] /
+            // var[] / sigma[] below are still ordered behind every wave's last reads of them: the carry loop above.)
             __syncthreads();                                       // mean[] / ekeys / red have been read for the last time
             dist_init(keep_init);
             [[maybe_unused]] const float* inj_pred = nullptr;
