@@ -120,6 +120,12 @@ def _lib_fingerprint():
 
 
 def needs_build():
+    """True when build() has anything to do: the library or the _fastcall extension (each on its own stamp, so that build()
+    redoes only the one that is stale)."""
+    return library_needs_build() or fastcall_needs_build()
+
+
+def library_needs_build():
     """False when libbbmpc.so was linked from exactly the sources in the tree, by this link line and toolchain (on the GPU
     box: the .so and its stamp arrive with the snapshot, the object cache does not -- nothing is compiled there; the image,
     hence the toolchain, is the same).  Without a hipcc on the box only the sources are compared."""
@@ -155,12 +161,82 @@ def write_embedded_sources():
         os.replace(tmp, EMBED)
 
 
+# ---- the CPython extension of the host-in / host-out control step (csrc/pyfast.cpp -> _fastcall<EXT_SUFFIX>) ------------
+# Host code only, a build of its own: it does not link against libbbmpc.so and shares no header with it, so a kernel edit
+# does not rebuild it and an edit to it does not relink the library.  Its stamp travels with it like the library's.
+FASTCALL_SRC = os.path.join(CSRC, "pyfast.cpp")
+FASTCALL_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall"]
+
+
+def fastcall_path():
+    import sysconfig
+    return os.path.join(HERE, "_fastcall" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
+
+
+def _host_cxx():
+    """The host compiler as a command prefix: c++ / g++, else hipcc as a plain C++ compiler (no offload arch)."""
+    for cand in (os.environ.get("CXX"), "c++", "g++"):
+        if cand and shutil.which(cand):
+            return [shutil.which(cand)]
+    return [_hipcc(), "-x", "c++"]
+
+
+def _fastcall_fingerprint():
+    """(source, headers): the source text + the flags, and the Python / NumPy the extension was compiled against."""
+    import hashlib
+    import numpy
+    h = hashlib.sha256(" ".join(FASTCALL_FLAGS).encode())
+    h.update(open(FASTCALL_SRC, "rb").read())
+    return h.hexdigest(), "py%d.%d-numpy%s" % (sys.version_info[0], sys.version_info[1], numpy.__version__)
+
+
+def fastcall_needs_build():
+    path = fastcall_path()
+    if not (os.path.exists(path) and os.path.exists(path + ".sha")):
+        return True
+    return open(path + ".sha").read().strip() != "|".join(_fastcall_fingerprint())
+
+
+def build_fastcall(force=False, verbose=False):
+    """Compile csrc/pyfast.cpp; returns the extension's path, or None when it could not be built -- the compiler's message
+    goes to stderr and the package falls back to ctypes (engine.py), so this never raises."""
+    try:
+        if not force and not fastcall_needs_build():
+            return fastcall_path()
+        import sysconfig
+        import numpy
+        path = fastcall_path()
+        tmp = "%s.tmp.%d" % (path, os.getpid())            # several ranks may call build() at once
+        cmd = (_host_cxx() + FASTCALL_FLAGS + ["-I" + sysconfig.get_paths()["include"], "-I" + numpy.get_include(),
+                                               FASTCALL_SRC, "-o", tmp])
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise RuntimeError(res.stdout + res.stderr)
+        os.replace(tmp, path)
+        with open(path + ".sha", "w") as f:
+            f.write("|".join(_fastcall_fingerprint()))
+        return path
+    except Exception as ex:                                # noqa: BLE001
+        print("blackbox_mpc_amd: the _fastcall extension was not built (the ctypes path is used):\n%s" % ex, file=sys.stderr)
+        return None
+
+
 def build(force=False, verbose=False):
     """Compile the stale translation units side by side (objects are cached under csrc/_obj, so a kernel edit costs the
-    units that see it: 12-62 s instead of the whole library), link."""
+    units that see it: 12-62 s instead of the whole library), link; then the _fastcall extension, on its own stamp."""
+    lib = _build_library(force=force, verbose=verbose)
+    build_fastcall(force=force, verbose=verbose)
+    return lib
+
+
+def _build_library(force=False, verbose=False):
     write_embedded_sources()
     os.makedirs(OBJ_DIR, exist_ok=True)
-    if not force and not needs_build():
+    if not force and not library_needs_build():
         return LIB
     stale = list(SOURCES) if force else _stale_units()
     procs = []

@@ -260,6 +260,49 @@ def check(code):
         raise err
 
 
+# The CPython extension that marshals the host-in / host-out control step (csrc/pyfast.cpp, built by _build.py next to the
+# library).  It is an accelerator of the call, not of the computation: without it the same library entry points are called
+# through ctypes, so a missing or broken extension costs one warning per process and no call fails.
+def _fastcall_path():
+    import sysconfig
+    return os.path.join(HERE, "_fastcall" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
+
+
+FASTCALL_PATH = _fastcall_path()
+_fastcall_state = []                                      # [] = not tried yet, else [module or None]
+
+
+def fastcall():
+    """The _fastcall module loaded from FASTCALL_PATH, or None (warned about once)."""
+    if not _fastcall_state:
+        mod = None
+        try:
+            import importlib.util
+            if not os.path.exists(FASTCALL_PATH):
+                raise ImportError("%s is missing" % FASTCALL_PATH)
+            spec = importlib.util.spec_from_file_location(__package__ + "._fastcall", FASTCALL_PATH)
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+        except Exception as ex:                            # noqa: BLE001
+            import warnings
+            mod = None
+            warnings.warn("blackbox_mpc_amd: the _fastcall extension is not usable (%s: %s); control steps are called through "
+                          "ctypes, with more host time per call.  Build it with `python -m blackbox_mpc_amd._build`."
+                          % (type(ex).__name__, ex), RuntimeWarning, stacklevel=3)
+        _fastcall_state.append(mod)
+    return _fastcall_state[0]
+
+
+def fastcall_bind(library, handle, num_agents, dim_s, dim_u):
+    """One bound object (optimize / optimize_gather) for an engine handle of `library`, or None without the extension."""
+    mod = fastcall()
+    if mod is None:
+        return None
+    addr = lambda fn: ctypes.cast(fn, ctypes.c_void_p).value or 0
+    return mod.bind(handle or 0, addr(library.bbmpc_optimize), addr(library.bbmpc_optimize_gather),
+                    int(num_agents), int(dim_s), int(dim_u))
+
+
 def device_count():
     return lib.bbmpc_device_count()
 

@@ -1,6 +1,7 @@
 """Thin object wrapper over the C ABI handle (include/bbmpc.h).  NumPy in, NumPy
 out; device-pointer variants take integer addresses (e.g. torch `data_ptr()`)."""
 import ctypes
+import os
 
 import numpy as np
 
@@ -9,6 +10,9 @@ from . import _lib as L
 
 class Engine:
     risk = (L.RISK_MEAN_STD, 0)        # (kind, tail_count) of set_particle_risk: a new handle scores mean - kappa * std
+    _lib = L.lib                       # the library whose bbmpc_optimize / bbmpc_optimize_gather the hot path calls
+    _fastcall_on = True                # BBMPC_FASTCALL=0 at creation: the hot path stays on ctypes (A/B runs, parity tests)
+    _fast = None                       # the _fastcall object bound to this handle; None: not bound yet, False: ctypes path
 
     def __init__(self, optimizer, dynamics, reward, action_low, action_high, dim_s, num_agents,
                  planning_horizon, population_size=0, max_iterations=0, num_elite=0, seed=0, quirks=0,
@@ -17,6 +21,7 @@ class Engine:
                  spsa_alpha=0.602, spsa_gamma=0.101, spsa_a=0.01, spsa_c=0.3,
                  cma_alpha_cov=2.0, cma_h_sigma=1.0, population_offset=0, population_global=0):
         self._h = ctypes.c_void_p()
+        self._fastcall_on = os.environ.get("BBMPC_FASTCALL", "1") != "0"
         self._lo = L.f32c(np.asarray(action_low).reshape(-1))
         self._hi = L.f32c(np.asarray(action_high).reshape(-1))
         if self._lo.shape != self._hi.shape:
@@ -62,6 +67,7 @@ class Engine:
         if getattr(self, "_h", None) is not None and self._h.value:
             L.lib.bbmpc_destroy(self._h)
             self._h = ctypes.c_void_p()
+            self._fast = None                  # (it holds the handle's address)
 
     def __del__(self):
         try:
@@ -381,13 +387,22 @@ class Engine:
     def optimize_gather(self, state, d_gathered, slot, t=0, add_exploration_noise=False):
         """`optimize` for this rank's agents (NumPy in / out) + the device all-gather of their records into
         d_gathered (device address of [num_agents_global, U+S+1] floats), overlapped with the next control step."""
+        fast = self._fast
+        if fast is None:
+            fast = self._bind_fast()
+        if fast:
+            out = fast.optimize_gather(state, d_gathered, slot, t, add_exploration_noise)
+            if out.__class__ is tuple:
+                return out
+            if out is not NotImplemented:
+                L.check(out)
         io = self._io_buffers()
         st, action, nxt, rew, p_st, p_act, p_nxt, p_rew = io
         state = np.asarray(state)
         if state.shape != (self.A, self.S):
             raise ValueError("state must be [num_agents, dim_S] = [%d, %d], got %s" % (self.A, self.S, state.shape))
         np.copyto(st, state, casting="unsafe")
-        L.check(L.lib.bbmpc_optimize_gather(self._h, p_st, int(t), 1 if add_exploration_noise else 0, p_act, p_nxt,
+        L.check(self._lib.bbmpc_optimize_gather(self._h, p_st, int(t), 1 if add_exploration_noise else 0, p_act, p_nxt,
                                             p_rew, ctypes.c_void_p(d_gathered), int(slot)))
         return action.copy(), nxt.copy(), rew.copy()
 
@@ -399,6 +414,18 @@ class Engine:
 
     # -- hot path --------------------------------------------------------------------------
     def optimize(self, state, t=0, add_exploration_noise=False):
+        # One extension call (csrc/pyfast.cpp): the observation read in place, the results allocated before the library
+        # call and written by it.  It answers with the result tuple, with the library's error code, or with NotImplemented
+        # for anything but a C-contiguous float32 / float64 [A, S] array and an index-like t: the body below takes those.
+        fast = self._fast
+        if fast is None:
+            fast = self._bind_fast()
+        if fast:
+            out = fast.optimize(state, t, add_exploration_noise)
+            if out.__class__ is tuple:
+                return out
+            if out is not NotImplemented:
+                L.check(out)
         # persistent I/O buffers with cached ctypes pointers: building four `ndarray.ctypes` views per call costs more
         # host time (~15 us) than the H2D/D2H traffic of a control step
         st, action, nxt, rew, p_st, p_act, p_nxt, p_rew = self._io_buffers()
@@ -406,10 +433,17 @@ class Engine:
         if state.shape != (self.A, self.S):
             raise ValueError("state must be [num_agents, dim_S] = [%d, %d], got %s" % (self.A, self.S, state.shape))
         np.copyto(st, state, casting="unsafe")
-        code = L.lib.bbmpc_optimize(self._h, p_st, int(t), 1 if add_exploration_noise else 0, p_act, p_nxt, p_rew)
+        code = self._lib.bbmpc_optimize(self._h, p_st, int(t), 1 if add_exploration_noise else 0, p_act, p_nxt, p_rew)
         if code != 0:
             L.check(code)
         return action.copy(), nxt.copy(), rew.copy()
+
+    def _bind_fast(self):
+        """The _fastcall object of this handle (created at the first control step), or False: BBMPC_FASTCALL=0 when the
+        engine was created, or no usable extension (_lib.fastcall warns once per process)."""
+        fast = (L.fastcall_bind(self._lib, self._h.value, self.A, self.S, self.U) if self._fastcall_on else None) or False
+        self._fast = fast
+        return fast
 
     def _io_buffers(self):
         io = self.__dict__.get("_io")
