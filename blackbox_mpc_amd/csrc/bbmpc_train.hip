@@ -130,7 +130,6 @@ struct Trainer {
         q.idx = d_idx;
         q.row0 = 0;
         q.B = B;
-        q.gscale = (float)(2.0 / ((double)B * net.dims[net.L]));
         q.part = part.p;
         q.lossp = lossp.p;
         const int tiles = (B + TR_ROWS - 1) / TR_ROWS;
@@ -163,6 +162,7 @@ struct Trainer {
         u.pows = pows.p;
         u.parity = (int)(steps & 1);
         u.inv_count = (float)(1.0 / ((double)B * net.dims[net.L]));
+        u.gscale = (float)(2.0 / ((double)B * net.dims[net.L]));
         u.loss_acc = loss_slot;
         u.grads_out = grads_out;
         hipLaunchKernelGGL(k_train_update, dim3((net.n_params + 255) / 256), dim3(256), 0, stream, u);

@@ -3,11 +3,14 @@
 //
 //   k_train_fwd_bwd      grid ceil(B / 16): a workgroup owns 16 rows of the batch.  It gathers them through the epoch's
 //                        permutation, runs the forward stack with EVERY layer's output tile resident in LDS, forms
-//                        delta_{L-1} = act'(y_L) * 2 (y_L - t) / (B O) and sweeps backwards: per layer its share of
+//                        delta_{L-1} = act'(y_L) * (y_L - t) -- the factor 2 / (B O) is left to k_train_update, which
+//                        applies it ONCE to each summed gradient element -- and sweeps backwards: per layer its share of
 //                        dW_l = y_l^T delta_l (an MFMA product whose K extent is the tile's 16 rows), of
 //                        db_l = column sums of delta_l in row order, and g = delta_l W_l^T for the layer below.  Shares go
 //                        to part[tile][n_params], the tile's sum of squared errors to lossp[tile].  No atomics.
-//   k_train_update       one lane per parameter: adds the shares in ascending tile order, applies the rule (m, v and the
+//   k_train_update       one lane per parameter: adds the shares in ascending tile order, scales the sum by 2 / (B O)
+//                        (the only rounding of a gradient whose terms are exact, e.g. small integers; where B O is a
+//                        power of two the bits are those of scaling every delta), applies the rule (m, v and the
 //                        running powers b1^t, b2^t live on the device, the powers in double) and writes the parameter in
 //                        every layout the step kernel reads: the operand pack of W, the pack of W^T, the padded bias.
 //   k_train_forward_mse  forward only: per tile the squared error per output column and its sum (validation batches,
@@ -124,7 +127,6 @@ struct TrainStepArgs {
     const int* idx;                              // [B] dataset rows of this batch; null: rows row0 .. row0 + B - 1
     int row0;
     int B;
-    float gscale;                                // 2 / (B O)
     float* part;                                 // [tiles][n_params]
     float* lossp;                                // [tiles] sum of squared errors
 };
@@ -153,6 +155,7 @@ struct TrainUpdateArgs {
     double* pows;                                // [2][2]: (b1^t, b2^t) read at [parity], written at [parity ^ 1]
     int parity;
     float inv_count;                             // 1 / (B O)
+    float gscale;                                // 2 / (B O): the MSE gradient's factor, applied to the summed shares
     float* loss_acc;                             // += the batch loss (TR_RULE_NONE: = )
     float* grads_out;                            // TR_RULE_NONE: the summed gradient [n_params]
 };
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
     tr_load_input(n, q.din, q.idx, q.row0, n0, valid, tid, nthr);
     tr_forward(n, wave, lane);
 
-    // ---- delta_{L-1} = act'(y_L) * 2 (y_L - t) / (B O), in place; each thread's squared errors go to its word
+    // ---- delta_{L-1} = act'(y_L) * (y_L - t), in place (2 / (B O): k_train_update); each thread's squared errors go to its word
     {
         const int a = n.act[L - 1];
         const int r = rows[p];
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
                     const float z = n.zoff[L - 1] >= 0 ? smem[n.zoff[L - 1] + (t * 64 + lane) * 4 + c] : y;
                     const float diff = y - q.dout[(size_t)r * O + f];
                     sq = sq + diff * diff;
-                    d = train_act_grad(y, z, a) * (diff * q.gscale);
+                    d = train_act_grad(y, z, a) * diff;
                 }
                 yp[c] = d;
             }
@@ -417,6 +420,7 @@ __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     if (i >= n.n_params) return;
     float gsum = 0.0f;
     for (int t = 0; t < q.ntiles; ++t) gsum = gsum + q.part[(size_t)t * n.n_params + i];
+    gsum = gsum * q.gscale;
     if (q.rule == TR_RULE_NONE) {
         q.grads_out[i] = gsum;
         return;
