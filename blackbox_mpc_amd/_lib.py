@@ -106,6 +106,8 @@ SYMBOLS = [
     "bbmpc_refine_plans", "bbmpc_refine_plans_dev", "bbmpc_set_grad_refine", "bbmpc_get_grad_refine",
     "bbmpc_trainer_create", "bbmpc_trainer_destroy", "bbmpc_trainer_lds_bytes", "bbmpc_trainer_set_data", "bbmpc_trainer_fit",
     "bbmpc_trainer_get_params", "bbmpc_trainer_residual_rms", "bbmpc_trainer_gradients",
+    "bbmpc_trainer_create_ensemble", "bbmpc_trainer_set_member_rows", "bbmpc_trainer_fit_ensemble",
+    "bbmpc_trainer_get_member_params", "bbmpc_trainer_residual_rms_ensemble",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -236,6 +238,12 @@ def _load():
     lib.bbmpc_trainer_get_params.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     lib.bbmpc_trainer_residual_rms.argtypes = [vp, vp, vp, i32, vp]
     lib.bbmpc_trainer_gradients.argtypes = [vp, vp, i32, vp, vp]
+    lib.bbmpc_trainer_create_ensemble.argtypes = [ctypes.POINTER(vp), i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                                  ctypes.POINTER(vp), ctypes.POINTER(vp), i32, ctypes.c_float]
+    lib.bbmpc_trainer_set_member_rows.argtypes = [vp, vp]
+    lib.bbmpc_trainer_fit_ensemble.argtypes = [vp, i32, i32, vp, ctypes.c_uint64, vp, vp]
+    lib.bbmpc_trainer_get_member_params.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    lib.bbmpc_trainer_residual_rms_ensemble.argtypes = [vp, vp, vp, i32, vp]
     return lib
 
 

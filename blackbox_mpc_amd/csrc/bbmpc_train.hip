@@ -1,5 +1,7 @@
 // Training a Dense stack through the C ABI (bbmpc_trainer_*): the host side of kernels_train.hpp.
-// A trainer is independent of the planning handle: its own device, stream and buffers, no bbmpc_config.
+// A trainer is independent of the planning handle: its own device, stream and buffers, no bbmpc_config.  It holds E >= 1
+// equally shaped members (bbmpc_trainer_create: one; bbmpc_trainer_create_ensemble: up to 8) that step side by side, the
+// member index being the kernels' second grid dimension.
 #define BBMPC_TU_TRAIN
 #include <cmath>
 #include <limits>
@@ -35,58 +37,74 @@ static void train_describe(TrainNet& n, int32_t n_layers, const int32_t* dims, c
                 " bytes of LDS, over the 159 KiB limit");
 }
 
+// The seed member e draws its permutations from when bbmpc_trainer_fit_ensemble is given none (member 0: the seed itself).
+static inline uint64_t train_member_seed(uint64_t seed, int e) { return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)e); }
+
 struct Trainer {
     int device = 0;
+    int E = 1;                                   // members
     hipStream_t stream = nullptr;
-    TrainNet net;
+    TrainNet net;                                // wf / wr / bp: member 0's; member e's lie e * net.pstride floats further
     int rule = TR_RULE_ADAM;
     double lr = 1e-3;
-    DevBuf<float> theta, m, v, wf[TR_MAX_LAYERS], wr[TR_MAX_LAYERS], bp[TR_MAX_LAYERS];
-    DevBuf<double> pows;
-    long long steps = 0;
-    DevBuf<float> din, dout, vin, vout;
+    DevBuf<float> theta, m, v;                   // [E][n_params]
+    DevBuf<float> packs;                         // [E][pstride]: per member every layer's W pack, W^T pack, padded bias
+    DevBuf<double> pows;                         // [E][2][2]
+    long long steps = 0;                         // the members step together
+    DevBuf<float> din, dout, vin, vout;          // the dataset, once for all members
     int n_train = 0, n_val = 0;
     bool has_data = false;
+    std::vector<int32_t> member_rows;            // [E][n_train] training rows of each member; empty: identity
     DevBuf<float> part, lossp, loss_acc, val_loss, val_tiles, val_batch, grads, colsq, rms, rin, rout;
     DevBuf<int> perms, idx;
 
-    Trainer(const TrainNet& n, int dev, const float* const* weights, const float* const* biases, int rule_, double lr_)
-        : device(dev), net(n), rule(rule_), lr(lr_) {
+    // weights / biases: [E * L] host arrays, member major
+    Trainer(const TrainNet& n, int dev, int members, const float* const* weights, const float* const* biases, int rule_, double lr_)
+        : device(dev), E(members), net(n), rule(rule_), lr(lr_) {
         HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         const int L = net.L;
-        std::vector<float> h((size_t)net.n_params);
+        const size_t np = (size_t)net.n_params;
+        // one slab of operand packs per member: [wf_0 wr_0 bp_0 .. wf_{L-1} wr_{L-1} bp_{L-1}], every piece a multiple of 16 floats
+        size_t off_f[TR_MAX_LAYERS], off_r[TR_MAX_LAYERS], off_b[TR_MAX_LAYERS], slab = 0;
         for (int l = 0; l < L; ++l) {
-            memcpy(h.data() + net.woff[l], weights[l], sizeof(float) * net.dims[l] * net.dims[l + 1]);
-            memcpy(h.data() + net.boff[l], biases[l], sizeof(float) * net.dims[l + 1]);
+            const size_t pack = (size_t)net.tiles[l] * net.tiles[l + 1] * 256;
+            off_f[l] = slab; slab += pack;
+            off_r[l] = slab; slab += pack;
+            off_b[l] = slab; slab += (size_t)net.tiles[l + 1] * 16;
         }
+        net.pstride = (int)slab;
+        std::vector<float> h(np * E), s(slab * E, 0.0f);
+        for (int e = 0; e < E; ++e)
+            for (int l = 0; l < L; ++l) {
+                const int in = net.dims[l], out = net.dims[l + 1], IT = net.tiles[l], OT = net.tiles[l + 1];
+                const float* w = weights[(size_t)e * L + l];
+                const float* b = biases[(size_t)e * L + l];
+                memcpy(h.data() + e * np + net.woff[l], w, sizeof(float) * in * out);
+                memcpy(h.data() + e * np + net.boff[l], b, sizeof(float) * out);
+                float* f = s.data() + e * slab + off_f[l];
+                float* r = s.data() + e * slab + off_r[l];
+                for (int i = 0; i < in; ++i)
+                    for (int o = 0; o < out; ++o) {
+                        f[train_wf_index(IT, i, o)] = w[(size_t)i * out + o];
+                        r[train_wr_index(OT, i, o)] = w[(size_t)i * out + o];
+                    }
+                memcpy(s.data() + e * slab + off_b[l], b, sizeof(float) * out);
+            }
         theta.alloc(h.size());
         m.alloc(h.size());
         v.alloc(h.size());
-        pows.alloc(4);
+        pows.alloc((size_t)4 * E);
+        packs.alloc(s.size());
         HIP_CHECK(hipMemcpy(theta.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(m.p, 0, h.size() * sizeof(float)));
         HIP_CHECK(hipMemset(v.p, 0, h.size() * sizeof(float)));
-        const double ones[4] = {1.0, 1.0, 1.0, 1.0};
-        HIP_CHECK(hipMemcpy(pows.p, ones, sizeof(ones), hipMemcpyHostToDevice));
+        const std::vector<double> ones((size_t)4 * E, 1.0);
+        HIP_CHECK(hipMemcpy(pows.p, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(packs.p, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice));
         for (int l = 0; l < L; ++l) {
-            const int in = net.dims[l], out = net.dims[l + 1], IT = net.tiles[l], OT = net.tiles[l + 1];
-            std::vector<float> f((size_t)IT * OT * 256, 0.0f), r((size_t)IT * OT * 256, 0.0f), b((size_t)OT * 16, 0.0f);
-            for (int i = 0; i < in; ++i)
-                for (int o = 0; o < out; ++o) {
-                    const float w = weights[l][(size_t)i * out + o];
-                    f[train_wf_index(IT, i, o)] = w;
-                    r[train_wr_index(OT, i, o)] = w;
-                }
-            for (int o = 0; o < out; ++o) b[o] = biases[l][o];
-            wf[l].alloc(f.size());
-            wr[l].alloc(r.size());
-            bp[l].alloc(b.size());
-            HIP_CHECK(hipMemcpy(wf[l].p, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(wr[l].p, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(bp[l].p, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
-            net.wf[l] = wf[l].p;
-            net.wr[l] = wr[l].p;
-            net.bp[l] = bp[l].p;
+            net.wf[l] = packs.p + off_f[l];
+            net.wr[l] = packs.p + off_r[l];
+            net.bp[l] = packs.p + off_b[l];
         }
         const int bytes = net.lds_floats * 4;
         if (bytes > 64 * 1024) {
@@ -115,29 +133,49 @@ struct Trainer {
         n_train = nt;
         n_val = nv;
         has_data = true;
+        member_rows.clear();                     // the rows of another dataset
+    }
+
+    void set_member_rows(const int32_t* rows) {
+        REQUIRE(has_data, BBMPC_E_STATE, "trainer: bbmpc_trainer_set_member_rows before bbmpc_trainer_set_data");
+        if (!rows) {
+            member_rows.clear();
+            return;
+        }
+        const size_t count = (size_t)E * n_train;
+        for (size_t i = 0; i < count; ++i)
+            REQUIRE(rows[i] >= 0 && rows[i] < n_train, BBMPC_E_INVALID, "trainer: a member row outside [0, n_train)");
+        member_rows.assign(rows, rows + count);
+    }
+
+    // a single-member entry point on an ensemble
+    void require_single(const char* call, const char* instead) const {
+        REQUIRE(E == 1, BBMPC_E_STATE, std::string("trainer: ") + call + " on an ensemble of " + std::to_string(E) + " members; " + instead);
     }
 
     static void check_batch(int B) {
         REQUIRE(B >= 1 && B <= TR_MAX_BATCH, BBMPC_E_UNSUPPORTED, "trainer: batch_size must lie in [1, 4096]");
     }
 
-    // forward + backward of the batch idx[0 .. B-1] (device pointer) into part / lossp
-    void launch_step(const int* d_idx, int B) {
+    // forward + backward of every member's batch (member e: d_idx[e * idx_stride .. + B), device pointer) into part / lossp
+    void launch_step(const int* d_idx, long long idx_stride, int B) {
         TrainStepArgs q;
         q.n = net;
         q.din = din.p;
         q.dout = dout.p;
         q.idx = d_idx;
+        q.idx_stride = idx_stride;
         q.row0 = 0;
         q.B = B;
         q.part = part.p;
         q.lossp = lossp.p;
         const int tiles = (B + TR_ROWS - 1) / TR_ROWS;
-        hipLaunchKernelGGL(k_train_fwd_bwd, dim3(tiles), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        hipLaunchKernelGGL(k_train_fwd_bwd, dim3(tiles, E), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
         HIP_CHECK(hipGetLastError());
     }
 
-    void launch_update(int rule_, int B, float* loss_slot, float* grads_out) {
+    // member e's loss goes to loss_slot[e * loss_stride]
+    void launch_update(int rule_, int B, float* loss_slot, int loss_stride, float* grads_out) {
         TrainUpdateArgs u;
         u.n = net;
         u.theta = theta.p;
@@ -164,18 +202,20 @@ struct Trainer {
         u.inv_count = (float)(1.0 / ((double)B * net.dims[net.L]));
         u.gscale = (float)(2.0 / ((double)B * net.dims[net.L]));
         u.loss_acc = loss_slot;
+        u.loss_stride = loss_stride;
         u.grads_out = grads_out;
-        hipLaunchKernelGGL(k_train_update, dim3((net.n_params + 255) / 256), dim3(256), 0, stream, u);
+        hipLaunchKernelGGL(k_train_update, dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, u);
         HIP_CHECK(hipGetLastError());
         if (rule_ != TR_RULE_NONE) ++steps;
     }
 
     void ensure_step_buffers(int B) {
         const size_t tiles = (size_t)(B + TR_ROWS - 1) / TR_ROWS;
-        if (part.n < tiles * net.n_params) part.alloc(tiles * net.n_params);
-        if (lossp.n < tiles) lossp.alloc(tiles);
+        if (part.n < tiles * net.n_params * E) part.alloc(tiles * net.n_params * E);
+        if (lossp.n < tiles * E) lossp.alloc(tiles * E);
     }
 
+    // every member forward on the same rows: tile_loss [E][batches * tiles], colsq_out [E][batches * tiles][O]
     void launch_mse(const float* in, const float* out, int batches, int B, float* tile_loss, float* colsq_out) {
         TrainMseArgs q;
         q.n = net;
@@ -185,59 +225,76 @@ struct Trainer {
         q.tiles_per_batch = (B + TR_ROWS - 1) / TR_ROWS;
         q.tile_loss = tile_loss;
         q.colsq = colsq_out;
-        hipLaunchKernelGGL(k_train_forward_mse, dim3((unsigned)((size_t)batches * q.tiles_per_batch)), dim3(net.nw * 64),
+        hipLaunchKernelGGL(k_train_forward_mse, dim3((unsigned)((size_t)batches * q.tiles_per_batch), E), dim3(net.nw * 64),
                            (size_t)net.lds_floats * 4, stream, q);
         HIP_CHECK(hipGetLastError());
     }
 
-    void fit(int epochs, int B, const int32_t* perms_h, uint64_t seed, float* train_loss, float* val_loss_out) {
-        REQUIRE(has_data, BBMPC_E_STATE, "trainer: bbmpc_trainer_fit before bbmpc_trainer_set_data");
+    // Every member `epochs` epochs.  perms_h: [E][epochs][n_train] or null (member e then draws from train_member_seed(seed,
+    // e)); losses [E][epochs].  Batch rows of member e: member_rows[e][perm[e][epoch][pos + r]], composed here into one index
+    // array [E][epochs][n_train].  index_bound: what E * epochs * n_train has to stay below.
+    void fit(int epochs, int B, const int32_t* perms_h, uint64_t seed, float* train_loss, float* val_loss_out, long long index_bound) {
+        REQUIRE(has_data, BBMPC_E_STATE, "trainer: a fit before bbmpc_trainer_set_data");
         REQUIRE(epochs >= 1, BBMPC_E_INVALID, "trainer: epochs must be >= 1");
         check_batch(B);
         const int n = n_train, nb = n / B, nvb = n_val / B;
         const int tpb = (B + TR_ROWS - 1) / TR_ROWS;
-        REQUIRE((long long)nvb * tpb < (1ll << 31) && (long long)epochs * n < (1ll << 40), BBMPC_E_UNSUPPORTED, "trainer: dataset too large");
-        std::vector<int32_t> drawn;
+        const size_t en = (size_t)epochs * n;    // a member's stretch of the index array
+        REQUIRE((long long)nvb * tpb < (1ll << 31), BBMPC_E_UNSUPPORTED, "trainer: dataset too large");
+        REQUIRE((long long)E * epochs * n < index_bound, BBMPC_E_UNSUPPORTED,
+                "trainer: dataset too large: n_members * epochs * n_train = " + std::to_string((long long)E * epochs * n) +
+                    " index entries, the limit is below " + std::to_string(index_bound));
+        std::vector<int32_t> composed;
         if (nb > 0) {
-            if (perms_h) {
-                for (size_t i = 0; i < (size_t)epochs * n; ++i)
+            if (perms_h)
+                for (size_t i = 0; i < en * E; ++i)
                     REQUIRE(perms_h[i] >= 0 && perms_h[i] < n, BBMPC_E_INVALID, "trainer: a permutation entry outside [0, n_train)");
-            } else {
-                drawn.resize((size_t)epochs * n);
-                for (int e = 0; e < epochs; ++e) train_draw_permutation(seed, e, n, drawn.data() + (size_t)e * n);
-                perms_h = drawn.data();
+            if (!perms_h || !member_rows.empty()) {
+                composed.resize(en * E);
+                for (int e = 0; e < E; ++e) {
+                    int32_t* dst = composed.data() + e * en;
+                    if (perms_h) memcpy(dst, perms_h + e * en, en * sizeof(int32_t));
+                    else
+                        for (int k = 0; k < epochs; ++k) train_draw_permutation(train_member_seed(seed, e), k, n, dst + (size_t)k * n);
+                    if (!member_rows.empty()) {
+                        const int32_t* rows = member_rows.data() + (size_t)e * n;
+                        for (size_t i = 0; i < en; ++i) dst[i] = rows[dst[i]];
+                    }
+                }
+                perms_h = composed.data();
             }
             ensure_step_buffers(B);
-            if (perms.n < (size_t)epochs * n) perms.alloc((size_t)epochs * n);
-            HIP_CHECK(hipMemcpy(perms.p, perms_h, (size_t)epochs * n * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (perms.n < en * E) perms.alloc(en * E);
+            HIP_CHECK(hipMemcpy(perms.p, perms_h, en * E * sizeof(int32_t), hipMemcpyHostToDevice));
         }
-        if (loss_acc.n < (size_t)epochs) { loss_acc.alloc(epochs); val_loss.alloc(epochs); }
-        HIP_CHECK(hipMemsetAsync(loss_acc.p, 0, (size_t)epochs * sizeof(float), stream));
+        const size_t nl = (size_t)epochs * E;
+        if (loss_acc.n < nl) { loss_acc.alloc(nl); val_loss.alloc(nl); }
+        HIP_CHECK(hipMemsetAsync(loss_acc.p, 0, nl * sizeof(float), stream));
         if (nvb > 0) {
-            if (val_tiles.n < (size_t)nvb * tpb) val_tiles.alloc((size_t)nvb * tpb);
-            if (val_batch.n < (size_t)nvb) val_batch.alloc(nvb);
+            if (val_tiles.n < (size_t)nvb * tpb * E) val_tiles.alloc((size_t)nvb * tpb * E);
+            if (val_batch.n < (size_t)nvb * E) val_batch.alloc((size_t)nvb * E);
         }
-        // the epochs: nothing but launches on one stream
-        for (int e = 0; e < epochs; ++e) {
+        // the epochs: nothing but launches on one stream, each for all members
+        for (int k = 0; k < epochs; ++k) {
             for (int bi = 0; bi < nb; ++bi) {
-                launch_step(perms.p + (size_t)e * n + (size_t)bi * B, B);
-                launch_update(rule, B, loss_acc.p + e, nullptr);
+                launch_step(perms.p + (size_t)k * n + (size_t)bi * B, (long long)en, B);
+                launch_update(rule, B, loss_acc.p + k, epochs, nullptr);
             }
             if (nvb > 0) {
                 launch_mse(vin.p, vout.p, nvb, B, val_tiles.p, nullptr);
-                hipLaunchKernelGGL(k_train_val_reduce, dim3(1), dim3(256), 0, stream, (const float*)val_tiles.p, nvb, tpb,
-                                   (float)(1.0 / ((double)B * net.dims[net.L])), val_batch.p, val_loss.p + e);
+                hipLaunchKernelGGL(k_train_val_reduce, dim3(1, E), dim3(256), 0, stream, (const float*)val_tiles.p, nvb, tpb,
+                                   (float)(1.0 / ((double)B * net.dims[net.L])), val_batch.p, val_loss.p + k, epochs);
                 HIP_CHECK(hipGetLastError());
             }
         }
-        std::vector<float> tl(epochs), vl(epochs);
-        HIP_CHECK(hipMemcpyAsync(tl.data(), loss_acc.p, (size_t)epochs * sizeof(float), hipMemcpyDeviceToHost, stream));
-        if (nvb > 0) HIP_CHECK(hipMemcpyAsync(vl.data(), val_loss.p, (size_t)epochs * sizeof(float), hipMemcpyDeviceToHost, stream));
+        std::vector<float> tl(nl), vl(nl);
+        HIP_CHECK(hipMemcpyAsync(tl.data(), loss_acc.p, nl * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (nvb > 0) HIP_CHECK(hipMemcpyAsync(vl.data(), val_loss.p, nl * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         const float nan = std::numeric_limits<float>::quiet_NaN();
-        for (int e = 0; e < epochs; ++e) {
-            train_loss[e] = nb > 0 ? (float)((double)tl[e] / nb) : nan;
-            val_loss_out[e] = nvb > 0 ? vl[e] : nan;
+        for (size_t i = 0; i < nl; ++i) {
+            train_loss[i] = nb > 0 ? (float)((double)tl[i] / nb) : nan;
+            val_loss_out[i] = nvb > 0 ? vl[i] : nan;
         }
     }
 
@@ -249,8 +306,8 @@ struct Trainer {
         if (idx.n < (size_t)B) idx.alloc(B);
         if (grads.n < (size_t)net.n_params + 1) grads.alloc((size_t)net.n_params + 1);
         HIP_CHECK(hipMemcpy(idx.p, idx_h, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
-        launch_step(idx.p, B);
-        launch_update(TR_RULE_NONE, B, grads.p + net.n_params, grads.p);
+        launch_step(idx.p, 0, B);
+        launch_update(TR_RULE_NONE, B, grads.p + net.n_params, 0, grads.p);
         std::vector<float> h((size_t)net.n_params + 1);
         HIP_CHECK(hipMemcpyAsync(h.data(), grads.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -258,9 +315,9 @@ struct Trainer {
         *loss_out = h[net.n_params];
     }
 
-    void get_params(float* const* weights, float* const* biases) {
+    void get_params(int member, float* const* weights, float* const* biases) {
         std::vector<float> h((size_t)net.n_params);
-        HIP_CHECK(hipMemcpyAsync(h.data(), theta.p, h.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(h.data(), theta.p + (size_t)member * net.n_params, h.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         for (int l = 0; l < net.L; ++l) {
             memcpy(weights[l], h.data() + net.woff[l], sizeof(float) * net.dims[l] * net.dims[l + 1]);
@@ -268,18 +325,19 @@ struct Trainer {
         }
     }
 
+    // rms_out [E][O]: every member on the same n rows, uploaded once
     void residual_rms(const float* in, const float* out, int n, float* rms_out) {
         REQUIRE(n >= 1, BBMPC_E_INVALID, "trainer: residual_rms needs at least one row");
         const int D = net.dims[0], O = net.dims[net.L];
         const int tiles = (n + TR_ROWS - 1) / TR_ROWS;
         upload(rin, in, (size_t)n * D);
         upload(rout, out, (size_t)n * O);
-        if (colsq.n < (size_t)tiles * O) colsq.alloc((size_t)tiles * O);
-        if (rms.n < (size_t)O) rms.alloc(O);
+        if (colsq.n < (size_t)tiles * O * E) colsq.alloc((size_t)tiles * O * E);
+        if (rms.n < (size_t)O * E) rms.alloc((size_t)O * E);
         launch_mse(rin.p, rout.p, 1, n, nullptr, colsq.p);
-        hipLaunchKernelGGL(k_train_rms_reduce, dim3((O + 63) / 64), dim3(64), 0, stream, (const float*)colsq.p, tiles, O, (float)(1.0 / n), rms.p);
+        hipLaunchKernelGGL(k_train_rms_reduce, dim3((O + 63) / 64, E), dim3(64), 0, stream, (const float*)colsq.p, tiles, O, (float)(1.0 / n), rms.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(rms_out, rms.p, (size_t)O * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(rms_out, rms.p, (size_t)O * E * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
 };
@@ -296,6 +354,31 @@ struct bbmpc_trainer_s {
 #define CHECK_TRAINER(h)                                                       \
     if (!(h) || !(h)->t) throw HipError(BBMPC_E_INVALID, "null trainer");      \
     DeviceGuard _device_guard((h)->t->device)
+
+// what bbmpc_trainer_create and bbmpc_trainer_create_ensemble share; every refusal comes before a device is touched
+static void trainer_create(bbmpc_trainer* out, int32_t device, int32_t n_members, int32_t n_layers, const int32_t* dims,
+                           const int32_t* activations, const float* const* weights, const float* const* biases, int32_t rule,
+                           float learning_rate) {
+    REQUIRE(out, BBMPC_E_INVALID, "trainer: null output handle");
+    *out = nullptr;
+    REQUIRE(n_members >= 1 && n_members <= bbmpc::TR_MAX_MEMBERS, BBMPC_E_UNSUPPORTED,
+            "trainer: n_members must lie in [1, 8] (BBMPC_MAX_ENSEMBLE_MEMBERS)");
+    TrainNet n;
+    bbmpc::train_describe(n, n_layers, dims, activations);
+    REQUIRE(weights && biases, BBMPC_E_INVALID, "trainer: null weights / biases");
+    for (int i = 0; i < n_members * n_layers; ++i) REQUIRE(weights[i] && biases[i], BBMPC_E_INVALID, "trainer: a null weight or bias array");
+    REQUIRE(rule == BBMPC_TRAIN_ADAM || rule == BBMPC_TRAIN_SGD || rule == BBMPC_TRAIN_RMSPROP, BBMPC_E_INVALID, "trainer: unknown update rule");
+    REQUIRE(std::isfinite(learning_rate) && learning_rate > 0.0f, BBMPC_E_INVALID, "trainer: learning_rate must be finite and positive");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        throw HipError(BBMPC_E_NO_DEVICE, "no HIP device available: this library has no CPU fallback");
+    REQUIRE(device < ndev, BBMPC_E_NO_DEVICE, "trainer: device out of range");
+    int dev = device;
+    if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
+    DeviceGuard guard(dev);
+    Trainer* t = new Trainer(n, dev, n_members, weights, biases, rule, (double)learning_rate);
+    *out = new bbmpc_trainer_s{t};
+}
 
 extern "C" {
 
@@ -320,24 +403,15 @@ int bbmpc_trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t
 int bbmpc_trainer_create(bbmpc_trainer* out, int32_t device, int32_t n_layers, const int32_t* dims, const int32_t* activations,
                          const float* const* weights, const float* const* biases, int32_t rule, float learning_rate) {
     API_BEGIN
-    CHECK_PTR(out);
-    *out = nullptr;
-    TrainNet n;
-    bbmpc::train_describe(n, n_layers, dims, activations);
-    CHECK_PTR(weights);
-    CHECK_PTR(biases);
-    for (int l = 0; l < n_layers; ++l) REQUIRE(weights[l] && biases[l], BBMPC_E_INVALID, "trainer: a null weight or bias array");
-    REQUIRE(rule == BBMPC_TRAIN_ADAM || rule == BBMPC_TRAIN_SGD || rule == BBMPC_TRAIN_RMSPROP, BBMPC_E_INVALID, "trainer: unknown update rule");
-    REQUIRE(std::isfinite(learning_rate) && learning_rate > 0.0f, BBMPC_E_INVALID, "trainer: learning_rate must be finite and positive");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw HipError(BBMPC_E_NO_DEVICE, "no HIP device available: this library has no CPU fallback");
-    REQUIRE(device < ndev, BBMPC_E_NO_DEVICE, "trainer: device out of range");
-    int dev = device;
-    if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
-    DeviceGuard guard(dev);
-    Trainer* t = new Trainer(n, dev, weights, biases, rule, (double)learning_rate);
-    *out = new bbmpc_trainer_s{t};
+    trainer_create(out, device, 1, n_layers, dims, activations, weights, biases, rule, learning_rate);
+    API_END
+}
+
+int bbmpc_trainer_create_ensemble(bbmpc_trainer* out, int32_t device, int32_t n_members, int32_t n_layers, const int32_t* dims,
+                                  const int32_t* activations, const float* const* weights, const float* const* biases, int32_t rule,
+                                  float learning_rate) {
+    API_BEGIN
+    trainer_create(out, device, n_members, n_layers, dims, activations, weights, biases, rule, learning_rate);
     API_END
 }
 
@@ -364,13 +438,30 @@ int bbmpc_trainer_set_data(bbmpc_trainer t, const float* train_in, const float* 
     API_END
 }
 
+int bbmpc_trainer_set_member_rows(bbmpc_trainer t, const int32_t* rows) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    t->t->set_member_rows(rows);
+    API_END
+}
+
 int bbmpc_trainer_fit(bbmpc_trainer t, int32_t epochs, int32_t batch_size, const int32_t* perms, uint64_t seed, float* train_loss_out,
                       float* val_loss_out) {
     API_BEGIN
     CHECK_TRAINER(t);
     CHECK_PTR(train_loss_out);
     CHECK_PTR(val_loss_out);
-    t->t->fit(epochs, batch_size, perms, seed, train_loss_out, val_loss_out);
+    t->t->require_single("bbmpc_trainer_fit", "call bbmpc_trainer_fit_ensemble");
+    t->t->fit(epochs, batch_size, perms, seed, train_loss_out, val_loss_out, 1ll << 40);
+    API_END
+}
+
+int bbmpc_trainer_fit_ensemble(bbmpc_trainer t, int32_t epochs, int32_t batch_size, const int32_t* perms, uint64_t seed,
+                               float* train_loss_out, float* val_loss_out) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    REQUIRE(train_loss_out && val_loss_out, BBMPC_E_INVALID, "trainer: null loss outputs");
+    t->t->fit(epochs, batch_size, perms, seed, train_loss_out, val_loss_out, 1ll << 31);
     API_END
 }
 
@@ -379,8 +470,19 @@ int bbmpc_trainer_get_params(bbmpc_trainer t, float* const* weights, float* cons
     CHECK_TRAINER(t);
     CHECK_PTR(weights);
     CHECK_PTR(biases);
+    t->t->require_single("bbmpc_trainer_get_params", "call bbmpc_trainer_get_member_params");
     for (int l = 0; l < t->t->net.L; ++l) REQUIRE(weights[l] && biases[l], BBMPC_E_INVALID, "trainer: a null weight or bias array");
-    t->t->get_params(weights, biases);
+    t->t->get_params(0, weights, biases);
+    API_END
+}
+
+int bbmpc_trainer_get_member_params(bbmpc_trainer t, int32_t member, float* const* weights, float* const* biases) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    REQUIRE(weights && biases, BBMPC_E_INVALID, "trainer: null weights / biases");
+    REQUIRE(member >= 0 && member < t->t->E, BBMPC_E_INVALID, "trainer: member outside [0, n_members)");
+    for (int l = 0; l < t->t->net.L; ++l) REQUIRE(weights[l] && biases[l], BBMPC_E_INVALID, "trainer: a null weight or bias array");
+    t->t->get_params(member, weights, biases);
     API_END
 }
 
@@ -390,6 +492,15 @@ int bbmpc_trainer_residual_rms(bbmpc_trainer t, const float* in, const float* ou
     CHECK_PTR(in);
     CHECK_PTR(out);
     CHECK_PTR(rms_out);
+    t->t->require_single("bbmpc_trainer_residual_rms", "call bbmpc_trainer_residual_rms_ensemble");
+    t->t->residual_rms(in, out, n, rms_out);
+    API_END
+}
+
+int bbmpc_trainer_residual_rms_ensemble(bbmpc_trainer t, const float* in, const float* out, int32_t n, float* rms_out) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    REQUIRE(in && out && rms_out, BBMPC_E_INVALID, "trainer: null rows or output");
     t->t->residual_rms(in, out, n, rms_out);
     API_END
 }
@@ -400,6 +511,7 @@ int bbmpc_trainer_gradients(bbmpc_trainer t, const int32_t* idx, int32_t batch_s
     CHECK_PTR(idx);
     CHECK_PTR(grads_out);
     CHECK_PTR(loss_out);
+    t->t->require_single("bbmpc_trainer_gradients", "it is the single trainer's test window (bbmpc_trainer_fit_ensemble fits an ensemble)");
     t->t->gradients(idx, batch_size, grads_out, loss_out);
     API_END
 }

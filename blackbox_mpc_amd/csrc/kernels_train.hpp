@@ -28,6 +28,13 @@
 //
 // Rows >= B of the last tile are never read from the dataset, and their delta is set to zero in every layer: their
 // shares are exact zeros.  Nothing depends on timing or on the grid: equal calls give equal bits.
+//
+// Members.  Every kernel has a second grid dimension, blockIdx.y = e < E <= TR_MAX_MEMBERS: the members of an ensemble are
+// equally shaped networks fitted side by side.  A pointer below addresses member 0; member e's copy lies e member strides
+// further (TrainNet::pstride for the operand packs, n_params for theta / m / v / a gradient, the grid's x extent for the
+// share and loss buffers, the strides the argument structs name for the rest).  The dataset is shared; a member's own rows
+// are an index map (TrainStepArgs::idx).  e is uniform over the workgroup, so the offsets are scalar arithmetic.  A member
+// reads and writes nothing of another's and its arithmetic does not see E: E = 1 is the single trainer, bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,6 +48,7 @@ typedef float tr_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TR_MAX_LAYERS = 8;
 constexpr int TR_MAX_WIDTH = 512;
 constexpr int TR_MAX_BATCH = 4096;
+constexpr int TR_MAX_MEMBERS = 8;                   // BBMPC_MAX_ENSEMBLE_MEMBERS
 constexpr int TR_ROWS = 16;                      // batch rows per workgroup
 constexpr int TR_LDS_LIMIT = 159 * 1024;         // bytes, as the other kernels' carves
 constexpr int TR_SCRATCH = 64 + 1024;            // floats: 16 row indices (padded to 64) + one word per thread
@@ -66,6 +74,7 @@ struct TrainNet {
     float* wf[TR_MAX_LAYERS];                    // operand pack of W_l   [T_{l+1}][T_l][64][4]
     float* wr[TR_MAX_LAYERS];                    // operand pack of W_l^T [T_l][T_{l+1}][64][4]
     float* bp[TR_MAX_LAYERS];                    // b_l padded with zeros to 16 T_{l+1}
+    int pstride;                                 // floats from member e's wf / wr / bp to member e + 1's (one slab per member)
 };
 
 // LDS carve in floats:  256 * (sum_{l=0..L} T_l  +  sum over swish layers of T_{l+1}  +  max_l T_l) + TR_SCRATCH,
@@ -125,10 +134,11 @@ struct TrainStepArgs {
     const float* din;                            // [rows][dims[0]]
     const float* dout;                           // [rows][dims[L]]
     const int* idx;                              // [B] dataset rows of this batch; null: rows row0 .. row0 + B - 1
+    long long idx_stride;                        // ints from member e's idx to member e + 1's
     int row0;
     int B;
-    float* part;                                 // [tiles][n_params]
-    float* lossp;                                // [tiles] sum of squared errors
+    float* part;                                 // [E][tiles][n_params]
+    float* lossp;                                // [E][tiles] sum of squared errors
 };
 
 struct TrainMseArgs {
@@ -137,27 +147,28 @@ struct TrainMseArgs {
     const float* dout;
     int B;                                       // rows per batch; tile blockIdx.x = (batch, tile of the batch)
     int tiles_per_batch;
-    float* tile_loss;                            // [batches * tiles_per_batch] or null
-    float* colsq;                                // [batches * tiles_per_batch][O] or null
+    float* tile_loss;                            // [E][batches * tiles_per_batch] or null
+    float* colsq;                                // [E][batches * tiles_per_batch][O] or null
 };
 
 struct TrainUpdateArgs {
     TrainNet n;
-    float* theta;
+    float* theta;                                // [E][n_params], as m, v
     float* m;
     float* v;
-    const float* part;
-    const float* lossp;
+    const float* part;                           // [E][ntiles][n_params]
+    const float* lossp;                          // [E][ntiles]
     int ntiles;
     int rule;
     float lr, b1, b2, omb1, omb2, rho, omrho, eps;
     double lr_d, b1_d, b2_d;
-    double* pows;                                // [2][2]: (b1^t, b2^t) read at [parity], written at [parity ^ 1]
+    double* pows;                                // [E][2][2]: (b1^t, b2^t) read at [parity], written at [parity ^ 1]
     int parity;
     float inv_count;                             // 1 / (B O)
     float gscale;                                // 2 / (B O): the MSE gradient's factor, applied to the summed shares
     float* loss_acc;                             // += the batch loss (TR_RULE_NONE: = )
-    float* grads_out;                            // TR_RULE_NONE: the summed gradient [n_params]
+    int loss_stride;                             // floats from member e's loss_acc to member e + 1's
+    float* grads_out;                            // TR_RULE_NONE: the summed gradient [E][n_params]
 };
 
 #ifdef BBMPC_TU_TRAIN
@@ -211,14 +222,15 @@ __device__ __forceinline__ void tr_load_input(const TrainNet& n, const float* di
     __syncthreads();
 }
 
-// The forward stack: y_{l+1} = act(y_l W_l + b_l) for every layer, all resident.  Ends with a barrier.
-__device__ __forceinline__ void tr_forward(const TrainNet& n, int wave, int lane) {
+// The forward stack: y_{l+1} = act(y_l W_l + b_l) for every layer, all resident; mo: the member's offset into the operand
+// packs.  Ends with a barrier.
+__device__ __forceinline__ void tr_forward(const TrainNet& n, size_t mo, int wave, int lane) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     for (int l = 0; l < n.L; ++l) {
         const int IT = n.tiles[l], OT = n.tiles[l + 1], a = n.act[l];
-        const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wf[l]);
+        const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wf[l] + mo);
         for (int ot = wave; ot < OT; ot += n.nw) {
-            tr_f32x4 acc = *reinterpret_cast<const tr_f32x4*>(n.bp[l] + ot * 16 + (lane >> 4) * 4);     // the bias enters as C
+            tr_f32x4 acc = *reinterpret_cast<const tr_f32x4*>(n.bp[l] + mo + ot * 16 + (lane >> 4) * 4);     // the bias enters as C
             acc = tr_tile_product(W + (size_t)ot * IT * 64 + lane, n.yoff[l], IT, lane, acc);
             if (n.zoff[l] >= 0) *reinterpret_cast<tr_f32x4*>(smem + n.zoff[l] + (ot * 64 + lane) * 4) = acc;
             acc.x = apply_act(acc.x, a); acc.y = apply_act(acc.y, a); acc.z = apply_act(acc.z, a); acc.w = apply_act(acc.w, a);
@@ -238,10 +250,13 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
     const int p = lane & 15, g = lane >> 4;
     const int* rows = reinterpret_cast<const int*>(smem + n.soff);
     float* words = smem + n.soff + 64;                              // one word per thread
-    float* part = q.part + (size_t)blockIdx.x * n.n_params;
+    const int e = blockIdx.y;                                       // the member: uniform, so what follows is scalar arithmetic
+    const size_t mo = (size_t)e * n.pstride;
+    const size_t slot = (size_t)e * gridDim.x + blockIdx.x;         // (member, tile)
+    float* part = q.part + slot * n.n_params;
 
-    tr_load_input(n, q.din, q.idx, q.row0, n0, valid, tid, nthr);
-    tr_forward(n, wave, lane);
+    tr_load_input(n, q.din, q.idx ? q.idx + e * q.idx_stride : nullptr, q.row0, n0, valid, tid, nthr);
+    tr_forward(n, mo, wave, lane);
 
     // ---- delta_{L-1} = act'(y_L) * (y_L - t), in place (2 / (B O): k_train_update); each thread's squared errors go to its word
     {
@@ -275,7 +290,7 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
         const float rs = ((s0 + s1) + s2) + s3;
         float tot = 0.0f;
         for (int j = 0; j < TR_ROWS; ++j) tot = tot + __shfl(rs, j);
-        if (lane == 0) q.lossp[blockIdx.x] = tot;
+        if (lane == 0) q.lossp[slot] = tot;
     }
 
     // ---- backward sweep: delta_l sits in y_{l+1}'s tiles
@@ -309,7 +324,7 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
         if (l == 0) break;
         // g = delta_l W_l^T
         {
-            const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wr[l]);
+            const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wr[l] + mo);
             for (int ot = wave; ot < IT; ot += nw) {
                 tr_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
                 acc = tr_tile_product(W + (size_t)ot * OT * 64 + lane, n.yoff[l + 1], OT, lane, acc);
@@ -342,6 +357,7 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
 }
 
 // Forward only on rows b * B + 16 t .. of batch b (tile t of the batch): squared errors per output column, and their sum.
+// Grid (batches * tiles_per_batch, E): every member on the same rows.
 __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const TrainNet& n = q.n;
@@ -352,8 +368,9 @@ __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
     const int L = n.L, O = n.dims[L];
     const int* rows = reinterpret_cast<const int*>(smem + n.soff);
     float* words = smem + n.soff + 64;
+    const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;          // (member, tile)
     tr_load_input(n, q.din, nullptr, batch * q.B, n0, valid, tid, nthr);
-    tr_forward(n, wave, lane);
+    tr_forward(n, (size_t)blockIdx.y * n.pstride, wave, lane);
     for (int o = tid; o < 1024; o += nthr) {
         float s = 0.0f;
         if (o < O)
@@ -362,7 +379,7 @@ __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
                 s = s + d * d;
             }
         words[o] = s;
-        if (q.colsq && o < O) q.colsq[(size_t)blockIdx.x * O + o] = s;
+        if (q.colsq && o < O) q.colsq[slot * O + o] = s;
     }
     __syncthreads();
     if (wave == 0 && q.tile_loss) {
@@ -370,12 +387,18 @@ __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
         for (int o = lane; o < O; o += 64) s = s + words[o];
         float tot = 0.0f;
         for (int j = 0; j < 64; ++j) tot = tot + __shfl(s, j);
-        if (lane == 0) q.tile_loss[blockIdx.x] = tot;
+        if (lane == 0) q.tile_loss[slot] = tot;
     }
 }
 
-// val_out[0] = mean over the batches of (sum of the batch's tile losses in tile order) / (B O); NaN without a batch
-__global__ void k_train_val_reduce(const float* tile_loss, int batches, int tiles_per_batch, float inv_count, float* batch_mse, float* val_out) {
+// val_out[0] = mean over the batches of (sum of the batch's tile losses in tile order) / (B O); NaN without a batch.
+// Grid (1, E): member e reads tile_loss[e][..], uses batch_mse[e][batches] and writes val_out[e * val_stride].
+__global__ void k_train_val_reduce(const float* tile_loss, int batches, int tiles_per_batch, float inv_count, float* batch_mse, float* val_out,
+                                   int val_stride) {
+    const int e = blockIdx.y;
+    tile_loss += (size_t)e * batches * tiles_per_batch;
+    batch_mse += (size_t)e * batches;
+    val_out += (size_t)e * val_stride;
     for (int b = threadIdx.x; b < batches; b += blockDim.x) {
         float s = 0.0f;
         for (int t = 0; t < tiles_per_batch; ++t) s = s + tile_loss[(size_t)b * tiles_per_batch + t];
@@ -389,72 +412,84 @@ __global__ void k_train_val_reduce(const float* tile_loss, int batches, int tile
     }
 }
 
-// rms_out[o] = sqrt(sum over tiles (ascending) of colsq[tile][o] / rows)
+// rms_out[e][o] = sqrt(sum over tiles (ascending) of colsq[e][tile][o] / rows); grid (ceil(O / 64), E)
 __global__ void k_train_rms_reduce(const float* colsq, int tiles, int O, float inv_rows, float* rms_out) {
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= O) return;
+    colsq += (size_t)blockIdx.y * tiles * O;
+    rms_out += (size_t)blockIdx.y * O;
     float s = 0.0f;
     for (int t = 0; t < tiles; ++t) s = s + colsq[(size_t)t * O + o];
     rms_out[o] = sqrtf(s * inv_rows);
 }
 
+// Grid (ceil(n_params / 256), E).
 __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     const TrainNet& n = q.n;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int e = blockIdx.y;                                       // the member: every offset below is scalar
+    const size_t po = (size_t)e * n.n_params, mo = (size_t)e * n.pstride;
+    const float* lossp = q.lossp + (size_t)e * q.ntiles;
+    const float* part = q.part + po * q.ntiles;
+    double* pows = q.pows + e * 4;
+    float* loss_acc = q.loss_acc + (size_t)e * q.loss_stride;
+    float* theta = q.theta + po;
+    float* mm = q.m + po;
+    float* vv = q.v + po;
     if (i == 0) {
         float s = 0.0f;
-        for (int t = 0; t < q.ntiles; ++t) s = s + q.lossp[t];
+        for (int t = 0; t < q.ntiles; ++t) s = s + lossp[t];
         const float loss = s * q.inv_count;
-        if (q.rule == TR_RULE_NONE) q.loss_acc[0] = loss;
-        else q.loss_acc[0] = q.loss_acc[0] + loss;
+        if (q.rule == TR_RULE_NONE) loss_acc[0] = loss;
+        else loss_acc[0] = loss_acc[0] + loss;
     }
     double b1t = 1.0, b2t = 1.0;
     if (q.rule == TR_RULE_ADAM) {
-        b1t = q.pows[q.parity * 2 + 0] * q.b1_d;
-        b2t = q.pows[q.parity * 2 + 1] * q.b2_d;
+        b1t = pows[q.parity * 2 + 0] * q.b1_d;
+        b2t = pows[q.parity * 2 + 1] * q.b2_d;
         if (i == 0) {
-            q.pows[(q.parity ^ 1) * 2 + 0] = b1t;
-            q.pows[(q.parity ^ 1) * 2 + 1] = b2t;
+            pows[(q.parity ^ 1) * 2 + 0] = b1t;
+            pows[(q.parity ^ 1) * 2 + 1] = b2t;
         }
     }
     if (i >= n.n_params) return;
     float gsum = 0.0f;
-    for (int t = 0; t < q.ntiles; ++t) gsum = gsum + q.part[(size_t)t * n.n_params + i];
+    for (int t = 0; t < q.ntiles; ++t) gsum = gsum + part[(size_t)t * n.n_params + i];
     gsum = gsum * q.gscale;
     if (q.rule == TR_RULE_NONE) {
-        q.grads_out[i] = gsum;
+        q.grads_out[po + i] = gsum;
         return;
     }
-    float w = q.theta[i];
+    float w = theta[i];
     if (q.rule == TR_RULE_SGD) {
         w = w + (-q.lr) * gsum;
     } else if (q.rule == TR_RULE_RMSPROP) {
-        const float v = q.rho * q.v[i] + q.omrho * (gsum * gsum);
-        q.v[i] = v;
+        const float v = q.rho * vv[i] + q.omrho * (gsum * gsum);
+        vv[i] = v;
         w = w + (-q.lr) * (gsum / (sqrtf(v) + q.eps));
     } else {
         const float lr_t = (float)(q.lr_d * sqrt(1.0 - b2t) / (1.0 - b1t));
-        const float m = q.b1 * q.m[i] + q.omb1 * gsum;
-        const float v = q.b2 * q.v[i] + q.omb2 * (gsum * gsum);
-        q.m[i] = m;
-        q.v[i] = v;
+        const float m = q.b1 * mm[i] + q.omb1 * gsum;
+        const float v = q.b2 * vv[i] + q.omb2 * (gsum * gsum);
+        mm[i] = m;
+        vv[i] = v;
         w = w + (-lr_t) * (m / (sqrtf(v) + q.eps));
     }
-    q.theta[i] = w;
+    theta[i] = w;
     // every layout the step kernel reads
     const int L = n.L;
     if (i >= n.boff[0]) {
         int l = L - 1;
         while (i < n.boff[l]) --l;
-        n.bp[l][i - n.boff[l]] = w;
+        n.bp[l][mo + i - n.boff[l]] = w;
     } else {
         int l = L - 1;
         while (i < n.woff[l]) --l;
         const int out = n.dims[l + 1];
         const int k = i - n.woff[l];
         const int fi = k / out, fo = k - fi * out;
-        n.wf[l][train_wf_index(n.tiles[l], fi, fo)] = w;
-        n.wr[l][train_wr_index(n.tiles[l + 1], fi, fo)] = w;
+        n.wf[l][mo + train_wf_index(n.tiles[l], fi, fo)] = w;
+        n.wr[l][mo + train_wr_index(n.tiles[l + 1], fi, fo)] = w;
     }
 }
 

@@ -3,7 +3,8 @@ section 8p): `HipDenseTrainer` has `_train_torch.DenseTrainer`'s surface and sta
 mini-batches through one permutation per epoch, MSE, backprop, Keras TF-2.0 adam / sgd / rmsprop -- as two kernel launches
 per step: forward + backward of the batch in one, the update of every parameter in every layout the first one reads in the
 other.  The dataset, the permutations of all epochs, the optimizer state and the loss accumulators live on the device; the
-losses are read once per fit.
+losses are read once per fit.  `HipEnsembleTrainer` fits the equally shaped members of an ensemble side by side in the same
+two launches per step (the member index is a grid dimension), bit for bit what one `HipDenseTrainer` per member gives.
 
 Out of scope: a log-variance head (Gaussian NLL) -- ProbabilisticMLP and EnsembleMLP(probabilistic=True) train with the
 torch backend.  `dense_trainer(backend, ...)` is how every `train(..., backend=...)` of the package picks its trainer."""
@@ -177,6 +178,129 @@ class HipDenseTrainer:
         ws = [np.zeros_like(w) for w in self._w]
         bs = [np.zeros_like(b) for b in self._b]
         L.check(L.lib.bbmpc_trainer_get_params(self._t, _ptr_array(ws), _ptr_array(bs)))
+        return ws, bs
+
+
+def member_seed(seed, member):
+    """The seed member `member` of an ensemble draws its permutations from when bbmpc_trainer_fit_ensemble is given none:
+    seed ^ (0x9E3779B97F4A7C15 * member mod 2^64), so member 0 draws what bbmpc_trainer_fit draws from `seed`."""
+    mask = (1 << 64) - 1
+    return (int(seed) & mask) ^ ((0x9E3779B97F4A7C15 * int(member)) & mask)
+
+
+def check_index_bound(n_members, epochs, n_train):
+    """bbmpc_trainer_fit_ensemble's bound on the composed index array [n_members][epochs][n_train] (int32 offsets on the
+    device), restated: the same error the library raises, before anything is handed to it."""
+    count = int(n_members) * int(epochs) * int(n_train)
+    if count >= 1 << 31:
+        raise L.BBMPCError(L.E_UNSUPPORTED, "trainer: dataset too large: n_members * epochs * n_train = %d index entries, "
+                                            "the limit is below %d" % (count, 1 << 31))
+
+
+class HipEnsembleTrainer:
+    """E equally shaped Dense stacks fitted side by side (bbmpc_trainer_create_ensemble; DESIGN.md section 8p, "Members"): the
+    member index is a second grid dimension of the training kernels, the dataset is on the device once and a member's
+    bootstrap resample is an index map.  Member e's results are, bit for bit, those of a `HipDenseTrainer` fitted on
+    `train_in[member_rows[e]]` with member e's start weights and permutations."""
+    has_logvar_head = False
+
+    def __init__(self, weights_per_member, biases_per_member, act_codes, device=None, learning_rate=1e-3, rule="adam"):
+        if rule not in _RULES:
+            raise ValueError("unknown optimizer rule %r" % (rule,))
+        self._t = ctypes.c_void_p(None)
+        if len(weights_per_member) != len(biases_per_member):
+            raise ValueError("one list of biases per list of kernels")
+        self._w = [[np.ascontiguousarray(w, np.float32) for w in ws] for ws in weights_per_member]
+        self._b = [[np.ascontiguousarray(b, np.float32).reshape(-1) for b in bs] for bs in biases_per_member]
+        self.n_members = len(self._w)
+        self.acts = [int(a) for a in act_codes]
+        first = self._w[0] if self._w else []
+        self.dims = ([int(first[0].shape[0])] + [int(w.shape[1]) for w in first]) if first else []
+        for e, (ws, bs) in enumerate(zip(self._w, self._b)):
+            if len(ws) != len(self.acts) or len(bs) != len(ws):
+                raise ValueError("member %d: one activation code and one bias per kernel" % e)
+            for l, (w, b) in enumerate(zip(ws, bs)):
+                if w.shape != (self.dims[l], self.dims[l + 1]) or b.shape[0] != w.shape[1]:
+                    raise ValueError("member %d, layer %d: kernel %s / bias %s do not fit the members' shape %s"
+                                     % (e, l, w.shape, b.shape, self.dims))
+        self.rule = rule
+        dims = np.asarray(self.dims, np.int32)
+        acts = np.asarray(self.acts, np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        L.check(L.lib.bbmpc_trainer_create_ensemble(
+            ctypes.byref(self._t), _device_index(device), self.n_members, len(self.acts), dims.ctypes.data_as(i32p),
+            acts.ctypes.data_as(i32p), _ptr_array([w for ws in self._w for w in ws]), _ptr_array([b for bs in self._b for b in bs]),
+            _RULES[rule], float(learning_rate)))
+
+    member_seed = staticmethod(member_seed)
+
+    def close(self):
+        t, self._t = getattr(self, "_t", None), None
+        if t:
+            L.lib.bbmpc_trainer_destroy(t)
+
+    __del__ = close
+
+    def set_data(self, train_in, train_out, val_in, val_out, member_rows=None):
+        """The shared rows, and per member the training rows it is fitted on (`member_rows` [E][n_train], None: all of them
+        in order)."""
+        tin, tout = L.f32c(train_in), L.f32c(train_out)
+        vin, vout = L.f32c(val_in), L.f32c(val_out)
+        tin, tout = tin.reshape(tin.shape[0], -1), tout.reshape(tout.shape[0], -1)
+        vin, vout = vin.reshape(vin.shape[0], self.dims[0]), vout.reshape(vout.shape[0], self.dims[-1])
+        if tin.shape[1] != self.dims[0] or tout.shape[1] != self.dims[-1] or tin.shape[0] != tout.shape[0] \
+                or vin.shape[0] != vout.shape[0]:
+            raise ValueError("rows %s -> %s do not fit the network %s" % (tin.shape, tout.shape, self.dims))
+        rows = None
+        if member_rows is not None:
+            rows = np.ascontiguousarray(member_rows, np.int32)
+            if rows.shape != (self.n_members, tin.shape[0]):
+                raise ValueError("member_rows: [%d][%d] training rows, got %s" % (self.n_members, tin.shape[0], rows.shape))
+        self._n_train = tin.shape[0]
+        L.check(L.lib.bbmpc_trainer_set_data(self._t, L.ptr(tin), L.ptr(tout), tin.shape[0], L.ptr(vin), L.ptr(vout), vin.shape[0]))
+        if rows is not None:
+            L.check(L.lib.bbmpc_trainer_set_member_rows(self._t, L.ptr(rows)))
+
+    def fit(self, train_in, train_out, val_in, val_out, epochs, batch_size, member_rows=None, permutations=None, generator_seed=None):
+        """Returns (train_loss [E, epochs], val_loss [E, epochs]); fetch a member's weights with `numpy_params(member)`.
+        `permutations`: [E][epochs][n] (member e's index ITS rows: position pos of an epoch is training row
+        member_rows[e][permutations[e][epoch][pos]]) or [epochs][n], shared by the members; None: drawn by the library, member
+        e from `member_seed(generator_seed, e)`."""
+        self.set_data(train_in, train_out, val_in, val_out, member_rows)
+        return self.fit_resident(epochs, batch_size, permutations, generator_seed)
+
+    def fit_resident(self, epochs, batch_size, permutations=None, generator_seed=None):
+        """`fit` on the rows (and member rows) `set_data` left on the device."""
+        epochs, E, n = int(epochs), self.n_members, self._n_train
+        check_index_bound(E, epochs, n)
+        perms = None
+        if permutations is not None:
+            p = np.asarray(permutations)
+            if p.ndim == 2:                                            # shared by the members
+                p = np.broadcast_to(p[None, :epochs], (E, epochs, n))
+            elif p.ndim != 3 or p.shape[0] != E:
+                raise ValueError("permutations: [%d][epochs][%d] or [epochs][%d], got %s" % (E, n, n, p.shape))
+            perms = np.ascontiguousarray(p[:, :epochs], np.int32).reshape(E, epochs, n)
+        seed = int(generator_seed) if generator_seed is not None else int.from_bytes(os.urandom(8), "little")
+        tl, vl = np.zeros((E, epochs), np.float32), np.zeros((E, epochs), np.float32)
+        L.check(L.lib.bbmpc_trainer_fit_ensemble(self._t, epochs, int(batch_size), L.ptr(perms), ctypes.c_uint64(seed & ((1 << 64) - 1)),
+                                                 L.ptr(tl), L.ptr(vl)))
+        return tl.astype(np.float64), vl.astype(np.float64)
+
+    def residual_rms(self, val_in, val_out):
+        """Per member the per-output RMS of (target - prediction) on the given rows, [E, O]; None without rows."""
+        if len(val_in) == 0:
+            return None
+        vin, vout = L.f32c(val_in), L.f32c(val_out)
+        vin, vout = vin.reshape(vin.shape[0], self.dims[0]), vout.reshape(vout.shape[0], self.dims[-1])
+        out = np.zeros((self.n_members, self.dims[-1]), np.float32)
+        L.check(L.lib.bbmpc_trainer_residual_rms_ensemble(self._t, L.ptr(vin), L.ptr(vout), vin.shape[0], L.ptr(out)))
+        return out
+
+    def numpy_params(self, member):
+        ws = [np.zeros_like(w) for w in self._w[0]]
+        bs = [np.zeros_like(b) for b in self._b[0]]
+        L.check(L.lib.bbmpc_trainer_get_member_params(self._t, int(member), _ptr_array(ws), _ptr_array(bs)))
         return ws, bs
 
 

@@ -241,7 +241,8 @@ class SystemDynamicsHandler:
         negative log-likelihood: training_loss / validation_loss (and the member lists) then hold the NLL, while
         residual_std() stays the mean network's residual.  `backend`: "torch" (DenseTrainer, the default) or "hip"
         (dynamics_functions/_train_hip.HipDenseTrainer: the hand-written training kernels, GPU only, plain MSE models --
-        a model with a log-variance head is refused by name)."""
+        a model with a log-variance head is refused by name; the members of an EnsembleMLP are fitted by one
+        HipEnsembleTrainer, all of them in one launch sequence)."""
         from ..dynamics_functions._train_hip import check_backend, dense_trainer
         check_backend(backend)
         if self._is_true_model:
@@ -299,8 +300,8 @@ class SystemDynamicsHandler:
     def _train_ensemble(self, fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
                         bootstrap_indices, backend="torch"):
         """The members of an EnsembleMLP on the (normalised) rows train() prepared -- statistics, split and the
-        freeze-after-first rule are shared.  Member e is fitted by a fresh DenseTrainer on a bootstrap resample of the
-        training rows: n_train indices drawn with replacement, `bootstrap_indices[e]` when given, else from
+        freeze-after-first rule are shared.  Member e is fitted by a fresh trainer (backend "hip": all members by one
+        HipEnsembleTrainer, `_fit_members_hip`, with the same results) on a bootstrap resample of the training rows: n_train indices drawn with replacement, `bootstrap_indices[e]` when given, else from
         np.random.default_rng([seed, e]) -- which then also draws the member's epoch permutations.  Injected
         `permutations` are [E][epochs] (one list per member) or [epochs] (shared by the members).
         training_loss / validation_loss stay member 0's; the per-member lists go to member_training_loss /
@@ -317,26 +318,52 @@ class SystemDynamicsHandler:
         per_member = permutations is not None and len(permutations) > 0 and np.ndim(permutations[0]) >= 2
         if per_member and len(permutations) != len(members):
             raise ValueError("permutations needs one list per member (%d)" % len(members))
-        self.member_training_loss, self.member_validation_loss, rms = [], [], []
-        for e, member in enumerate(members):
+        draws = []                                                          # per member: (bootstrap rows, epoch permutations)
+        for e in range(len(members)):
             rng = np.random.default_rng([int(seed), e] if seed is not None else None)
             idx = bootstrap_indices[e] if bootstrap_indices is not None else rng.integers(0, n, size=n)
             if permutations is None:
                 perms = [rng.permutation(n) for _ in range(epochs)]
             else:
                 perms = permutations[e] if per_member else permutations
-            trainer = dense_trainer(backend, member.weights, member.biases, member.activation_codes, device,
-                                    learning_rate=learning_rate, rule=rule, logvar_head=_logvar_head(member))
-            tl, vl = trainer.fit(tin[idx], tout[idx], vin, vout, epochs, batch_size, permutations=perms, generator_seed=seed)
-            self.member_training_loss.append(tl)
-            self.member_validation_loss.append(vl)
-            rms.append(trainer.residual_rms(vin, vout))
-            member.set_weights(*trainer.numpy_params())                    # bumps the version: evaluators re-upload
-            if trainer.has_logvar_head:
-                member.set_logvar_head(*trainer.numpy_logvar_head())
+            draws.append((idx, perms))
+        if backend == "hip":
+            tl, vl, rms = self._fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed)
+        else:
+            tl, vl, rms = [], [], []
+            for member, (idx, perms) in zip(members, draws):
+                trainer = dense_trainer(backend, member.weights, member.biases, member.activation_codes, device,
+                                        learning_rate=learning_rate, rule=rule, logvar_head=_logvar_head(member))
+                tl_e, vl_e = trainer.fit(tin[idx], tout[idx], vin, vout, epochs, batch_size, permutations=perms, generator_seed=seed)
+                tl.append(tl_e)
+                vl.append(vl_e)
+                rms.append(trainer.residual_rms(vin, vout))
+                member.set_weights(*trainer.numpy_params())                # bumps the version: evaluators re-upload
+                if trainer.has_logvar_head:
+                    member.set_logvar_head(*trainer.numpy_logvar_head())
+        self.member_training_loss, self.member_validation_loss = tl, vl
         self.training_loss, self.validation_loss = self.member_training_loss[0], self.member_validation_loss[0]
         self._residual_rms = None if rms[0] is None else np.sqrt(np.mean(np.square(np.asarray(rms, np.float64)), axis=0)).astype(np.float32)
         self._trained = True
+
+    @staticmethod
+    def _fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed):
+        """`_train_ensemble`'s loop as ONE HipEnsembleTrainer and one fit ("Members"): the rows go to
+        the device once, member e's bootstrap resample is the index map `member_rows[e]`, and every step is one launch pair
+        for all members.  Bit for bit what a HipDenseTrainer per member on `tin[idx]` gives.  Returns the per-member lists
+        (training loss, validation loss, residual RMS)."""
+        from ..dynamics_functions._train_hip import HipEnsembleTrainer
+        trainer = HipEnsembleTrainer([m.weights for m in members], [m.biases for m in members], members[0].activation_codes,
+                                     device, learning_rate=learning_rate, rule=rule)
+        try:
+            tl, vl = trainer.fit(tin, tout, vin, vout, epochs, batch_size, member_rows=[idx for idx, _ in draws],
+                                 permutations=[np.asarray(perms)[:epochs] for _, perms in draws], generator_seed=seed)
+            rms = trainer.residual_rms(vin, vout)
+            for e, member in enumerate(members):
+                member.set_weights(*trainer.numpy_params(e))               # bumps the version: evaluators re-upload
+        finally:
+            trainer.close()
+        return list(tl), list(vl), ([None] * len(members) if rms is None else list(rms))
 
     def residual_std(self):
         """Per-dimension RMS of (target - prediction) in state units on the held-out validation rows of the last train():

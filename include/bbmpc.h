@@ -859,6 +859,41 @@ int bbmpc_trainer_residual_rms(bbmpc_trainer t, const float* in, const float* ou
  * b_{L-1}.  Refusals as bbmpc_trainer_fit; an index outside [0, n_train) is BBMPC_E_INVALID. */
 int bbmpc_trainer_gradients(bbmpc_trainer t, const int32_t* idx, int32_t batch_size, float* grads_out, float* loss_out);
 
+/* ---- training the members of an ensemble in one launch sequence -----------------------------------
+ * A trainer may hold n_members equally shaped networks, 1 <= n_members <= BBMPC_MAX_ENSEMBLE_MEMBERS (8).  They are fitted
+ * side by side: the member index is a second grid dimension of every training kernel, so a step of all members is the two
+ * launches a step of one member is.  Member e has its own parameters, optimizer state and losses and shares nothing but the
+ * dataset, which is on the device once; its arithmetic and summation order are the single trainer's, whatever n_members is
+ * and whatever the other members hold (NaN included): member e's results are, bit for bit, those of a bbmpc_trainer_create
+ * trainer given member e's start weights, rows and permutations.
+ *
+ * weights / biases: [n_members * n_layers] pointers, member major (member e's layer l at [e * n_layers + l]); the other
+ * arguments and refusals as bbmpc_trainer_create, and BBMPC_E_UNSUPPORTED for n_members outside [1, 8].  n_members = 1 is
+ * legal and is a bbmpc_trainer_create trainer.  bbmpc_trainer_set_data and bbmpc_trainer_destroy serve both kinds; on a
+ * trainer with n_members > 1 bbmpc_trainer_fit, _get_params, _residual_rms and _gradients are BBMPC_E_STATE, with a message
+ * that names the call to use. */
+int bbmpc_trainer_create_ensemble(bbmpc_trainer* out, int32_t device, int32_t n_members, int32_t n_layers, const int32_t* dims,
+                                  const int32_t* activations, const float* const* weights, const float* const* biases, int32_t rule,
+                                  float learning_rate);
+/* The members' training rows (a bootstrap resample is an index map, not a copy): rows [n_members][n_train] int32 into the
+ * training rows bbmpc_trainer_set_data uploaded -- member e trains as if its dataset were train[rows[e][0]], train[rows[e][1]],
+ * ...  NULL, or never called: the identity for every member.  A new bbmpc_trainer_set_data resets it.  BBMPC_E_STATE before
+ * bbmpc_trainer_set_data; BBMPC_E_INVALID: an entry outside [0, n_train) (the map then stays as it was). */
+int bbmpc_trainer_set_member_rows(bbmpc_trainer t, const int32_t* rows);
+/* bbmpc_trainer_fit for every member at once.  perms: [n_members][epochs][n_train] int32, member e's permutation of epoch k
+ * indexing ITS rows: position pos of the epoch is training row rows[e][perms[e][k][pos]] (the two maps are composed on the
+ * host into one index array [n_members][epochs][n_train]).  NULL: member e draws what bbmpc_trainer_fit draws from the seed
+ * seed ^ (0x9E3779B97F4A7C15 * e mod 2^64) -- member 0 from `seed` itself.  train_loss_out / val_loss_out:
+ * [n_members][epochs]; the validation rows are shared.  Per step two launches and per epoch the validation pair, each for
+ * all members; no host synchronisation inside the fit.  Refusals as bbmpc_trainer_fit, and BBMPC_E_UNSUPPORTED where
+ * n_members * epochs * n_train >= 2^31. */
+int bbmpc_trainer_fit_ensemble(bbmpc_trainer t, int32_t epochs, int32_t batch_size, const int32_t* perms, uint64_t seed,
+                               float* train_loss_out, float* val_loss_out);
+/* bbmpc_trainer_get_params of one member; BBMPC_E_INVALID: member outside [0, n_members). */
+int bbmpc_trainer_get_member_params(bbmpc_trainer t, int32_t member, float* const* weights, float* const* biases);
+/* bbmpc_trainer_residual_rms of every member on the same n >= 1 host rows (uploaded once): rms_out [n_members][dims[n_layers]]. */
+int bbmpc_trainer_residual_rms_ensemble(bbmpc_trainer t, const float* in, const float* out, int32_t n, float* rms_out);
+
 #ifdef __cplusplus
 }
 #endif
