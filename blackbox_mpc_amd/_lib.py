@@ -41,6 +41,7 @@ TRACE_CMA_B, TRACE_CMA_C, TRACE_CMA_D, TRACE_CMA_SVD_STATS = 6, 7, 8, 9
 TRACE_TOPK_PASSES = 10
 
 TRAIN_ADAM, TRAIN_SGD, TRAIN_RMSPROP = 1, 2, 3                # bbmpc_trainer_create: rule
+TRAIN_DECAY_L2, TRAIN_DECAY_DECOUPLED = 0, 1                  # bbmpc_trainer_set_weight_decay: mode
 TRAIN_MAX_LAYERS, TRAIN_MAX_WIDTH, TRAIN_MAX_BATCH, TRAIN_LDS_LIMIT = 8, 512, 4096, 159 * 1024
 
 E_INVALID, E_NO_DEVICE, E_HIP, E_STATE, E_UNSUPPORTED = -1, -2, -3, -4, -5
@@ -108,6 +109,7 @@ SYMBOLS = [
     "bbmpc_trainer_get_params", "bbmpc_trainer_residual_rms", "bbmpc_trainer_gradients",
     "bbmpc_trainer_create_ensemble", "bbmpc_trainer_set_member_rows", "bbmpc_trainer_fit_ensemble",
     "bbmpc_trainer_get_member_params", "bbmpc_trainer_residual_rms_ensemble",
+    "bbmpc_trainer_set_weight_decay", "bbmpc_trainer_set_early_stopping", "bbmpc_trainer_get_fit_report",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -244,6 +246,9 @@ def _load():
     lib.bbmpc_trainer_fit_ensemble.argtypes = [vp, i32, i32, vp, ctypes.c_uint64, vp, vp]
     lib.bbmpc_trainer_get_member_params.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     lib.bbmpc_trainer_residual_rms_ensemble.argtypes = [vp, vp, vp, i32, vp]
+    lib.bbmpc_trainer_set_weight_decay.argtypes = [vp, vp, i32]
+    lib.bbmpc_trainer_set_early_stopping.argtypes = [vp, i32, ctypes.c_float, i32]
+    lib.bbmpc_trainer_get_fit_report.argtypes = [vp, vp, vp, vp]
     return lib
 
 

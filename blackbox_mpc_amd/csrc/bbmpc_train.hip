@@ -57,6 +57,17 @@ struct Trainer {
     std::vector<int32_t> member_rows;            // [E][n_train] training rows of each member; empty: identity
     DevBuf<float> part, lossp, loss_acc, val_loss, val_tiles, val_batch, grads, colsq, rms, rin, rout;
     DevBuf<int> perms, idx;
+    // weight decay, early stopping, best-weights restore; they hold from fit to fit
+    float wd[TR_MAX_LAYERS] = {0};               // lambda_l; all zero: off
+    int wd_mode = TR_DECAY_L2;
+    int patience = 0;
+    float min_delta = 0.0f;
+    bool restore_best = false;
+    DevBuf<TrainMon> mon;                        // [E][2]
+    DevBuf<float> best_theta;                    // [E][n_params]
+    std::vector<TrainMon> mon_host;              // what a fit uploads to mon and reads back from it
+    std::vector<int32_t> rep_epochs, rep_best_epoch;      // the last fit's report, [E]
+    std::vector<float> rep_best_val;
 
     // weights / biases: [E * L] host arrays, member major
     Trainer(const TrainNet& n, int dev, int members, const float* const* weights, const float* const* biases, int rule_, double lr_)
@@ -108,8 +119,9 @@ struct Trainer {
         }
         const int bytes = net.lds_floats * 4;
         if (bytes > 64 * 1024) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_forward_mse), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+            for (const void* f : {reinterpret_cast<const void*>(k_train_fwd_bwd<false>), reinterpret_cast<const void*>(k_train_fwd_bwd<true>),
+                                  reinterpret_cast<const void*>(k_train_forward_mse<false>), reinterpret_cast<const void*>(k_train_forward_mse<true>)})
+                HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         }
     }
     ~Trainer() {
@@ -158,7 +170,8 @@ struct Trainer {
     }
 
     // forward + backward of every member's batch (member e: d_idx[e * idx_stride .. + B), device pointer) into part / lossp
-    void launch_step(const int* d_idx, long long idx_stride, int B) {
+    // stop: the early-stopping state the launch reads (mon.p + parity), null outside a monitored fit
+    void launch_step(const int* d_idx, long long idx_stride, int B, const TrainMon* stop = nullptr) {
         TrainStepArgs q;
         q.n = net;
         q.din = din.p;
@@ -169,13 +182,15 @@ struct Trainer {
         q.B = B;
         q.part = part.p;
         q.lossp = lossp.p;
+        q.stop = stop;
         const int tiles = (B + TR_ROWS - 1) / TR_ROWS;
-        hipLaunchKernelGGL(k_train_fwd_bwd, dim3(tiles, E), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        if (stop) hipLaunchKernelGGL((k_train_fwd_bwd<true>), dim3(tiles, E), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        else hipLaunchKernelGGL((k_train_fwd_bwd<false>), dim3(tiles, E), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
         HIP_CHECK(hipGetLastError());
     }
 
     // member e's loss goes to loss_slot[e * loss_stride]
-    void launch_update(int rule_, int B, float* loss_slot, int loss_stride, float* grads_out) {
+    void launch_update(int rule_, int B, float* loss_slot, int loss_stride, float* grads_out, const TrainMon* stop = nullptr) {
         TrainUpdateArgs u;
         u.n = net;
         u.theta = theta.p;
@@ -204,7 +219,16 @@ struct Trainer {
         u.loss_acc = loss_slot;
         u.loss_stride = loss_stride;
         u.grads_out = grads_out;
-        hipLaunchKernelGGL(k_train_update, dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, u);
+        u.wd_on = 0;
+        for (int l = 0; l < TR_MAX_LAYERS; ++l) {
+            u.wd[l] = wd[l];
+            u.lrwd[l] = u.lr * wd[l];
+            u.wd_on |= wd[l] != 0.0f;
+        }
+        u.wd_mode = wd_mode;
+        u.stop = stop;
+        if (stop || u.wd_on) hipLaunchKernelGGL((k_train_update<true>), dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, u);
+        else hipLaunchKernelGGL((k_train_update<false>), dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, u);
         HIP_CHECK(hipGetLastError());
         if (rule_ != TR_RULE_NONE) ++steps;
     }
@@ -216,7 +240,7 @@ struct Trainer {
     }
 
     // every member forward on the same rows: tile_loss [E][batches * tiles], colsq_out [E][batches * tiles][O]
-    void launch_mse(const float* in, const float* out, int batches, int B, float* tile_loss, float* colsq_out) {
+    void launch_mse(const float* in, const float* out, int batches, int B, float* tile_loss, float* colsq_out, const TrainMon* stop = nullptr) {
         TrainMseArgs q;
         q.n = net;
         q.din = in;
@@ -225,8 +249,10 @@ struct Trainer {
         q.tiles_per_batch = (B + TR_ROWS - 1) / TR_ROWS;
         q.tile_loss = tile_loss;
         q.colsq = colsq_out;
-        hipLaunchKernelGGL(k_train_forward_mse, dim3((unsigned)((size_t)batches * q.tiles_per_batch), E), dim3(net.nw * 64),
-                           (size_t)net.lds_floats * 4, stream, q);
+        q.stop = stop;
+        const dim3 grid((unsigned)((size_t)batches * q.tiles_per_batch), E);
+        if (stop) hipLaunchKernelGGL((k_train_forward_mse<true>), grid, dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        else hipLaunchKernelGGL((k_train_forward_mse<false>), grid, dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
         HIP_CHECK(hipGetLastError());
     }
 
@@ -244,6 +270,10 @@ struct Trainer {
         REQUIRE((long long)E * epochs * n < index_bound, BBMPC_E_UNSUPPORTED,
                 "trainer: dataset too large: n_members * epochs * n_train = " + std::to_string((long long)E * epochs * n) +
                     " index entries, the limit is below " + std::to_string(index_bound));
+        const bool monitor = patience > 0 || restore_best;
+        REQUIRE(!monitor || nvb > 0, BBMPC_E_STATE,
+                "trainer: early stopping / restore_best need a validation loss, and n_val = " + std::to_string(n_val) +
+                    " rows hold no full batch of " + std::to_string(B));
         std::vector<int32_t> composed;
         if (nb > 0) {
             if (perms_h)
@@ -274,28 +304,84 @@ struct Trainer {
             if (val_tiles.n < (size_t)nvb * tpb * E) val_tiles.alloc((size_t)nvb * tpb * E);
             if (val_batch.n < (size_t)nvb * E) val_batch.alloc((size_t)nvb * E);
         }
-        // the epochs: nothing but launches on one stream, each for all members
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        if (monitor) {
+            if (mon.n < (size_t)2 * E) mon.alloc((size_t)2 * E);
+            if (restore_best && best_theta.n < (size_t)net.n_params * E) best_theta.alloc((size_t)net.n_params * E);
+            mon_host.assign((size_t)2 * E, TrainMon{std::numeric_limits<float>::infinity(), -1, 0, 0});
+            HIP_CHECK(hipMemcpyAsync(mon.p, mon_host.data(), mon_host.size() * sizeof(TrainMon), hipMemcpyHostToDevice, stream));
+        }
+        // the epochs: nothing but launches on one stream, each for all members.  Every epoch is enqueued whatever the monitor
+        // will decide: a stopped member's workgroups return at once.
         for (int k = 0; k < epochs; ++k) {
+            const TrainMon* stop = monitor ? mon.p + (k & 1) : nullptr;
             for (int bi = 0; bi < nb; ++bi) {
-                launch_step(perms.p + (size_t)k * n + (size_t)bi * B, (long long)en, B);
-                launch_update(rule, B, loss_acc.p + k, epochs, nullptr);
+                launch_step(perms.p + (size_t)k * n + (size_t)bi * B, (long long)en, B, stop);
+                launch_update(rule, B, loss_acc.p + k, epochs, nullptr, stop);
             }
             if (nvb > 0) {
-                launch_mse(vin.p, vout.p, nvb, B, val_tiles.p, nullptr);
+                launch_mse(vin.p, vout.p, nvb, B, val_tiles.p, nullptr, stop);
                 hipLaunchKernelGGL(k_train_val_reduce, dim3(1, E), dim3(256), 0, stream, (const float*)val_tiles.p, nvb, tpb,
-                                   (float)(1.0 / ((double)B * net.dims[net.L])), val_batch.p, val_loss.p + k, epochs);
+                                   (float)(1.0 / ((double)B * net.dims[net.L])), val_batch.p, val_loss.p + k, epochs, stop);
                 HIP_CHECK(hipGetLastError());
             }
+            if (monitor) {
+                hipLaunchKernelGGL(k_train_monitor, dim3(restore_best ? (net.n_params + 255) / 256 : 1, E), dim3(256), 0, stream, mon.p,
+                                   (const float*)val_loss.p + k, epochs, k, patience, min_delta, (const float*)theta.p,
+                                   restore_best ? best_theta.p : (float*)nullptr, net.n_params);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        if (restore_best) {
+            hipLaunchKernelGGL(k_train_restore, dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, net,
+                               (const TrainMon*)mon.p + (epochs & 1), (const float*)best_theta.p, theta.p);
+            HIP_CHECK(hipGetLastError());
         }
         std::vector<float> tl(nl), vl(nl);
         HIP_CHECK(hipMemcpyAsync(tl.data(), loss_acc.p, nl * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (nvb > 0) HIP_CHECK(hipMemcpyAsync(vl.data(), val_loss.p, nl * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (monitor) HIP_CHECK(hipMemcpyAsync(mon_host.data(), mon.p, mon_host.size() * sizeof(TrainMon), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        const float nan = std::numeric_limits<float>::quiet_NaN();
-        for (size_t i = 0; i < nl; ++i) {
-            train_loss[i] = nb > 0 ? (float)((double)tl[i] / nb) : nan;
-            val_loss_out[i] = nvb > 0 ? vl[i] : nan;
+        // the report: without monitoring every member ran every epoch and nothing was tracked
+        rep_epochs.assign(E, epochs);
+        rep_best_epoch.assign(E, -1);
+        rep_best_val.assign(E, nan);
+        for (int e = 0; e < E && monitor; ++e) {
+            const TrainMon& s = mon_host[(size_t)2 * e + (epochs & 1)];
+            if (s.stopped) rep_epochs[e] = s.stopped;
+            rep_best_epoch[e] = s.best_epoch;
+            if (s.best_epoch >= 0) rep_best_val[e] = s.best;
         }
+        for (size_t i = 0; i < nl; ++i) {
+            const bool ran = (int)(i % epochs) < rep_epochs[i / epochs];       // a stopped member's later epochs: NaN
+            train_loss[i] = nb > 0 && ran ? (float)((double)tl[i] / nb) : nan;
+            val_loss_out[i] = nvb > 0 && ran ? vl[i] : nan;
+        }
+    }
+
+    void set_weight_decay(const float* decay, int mode) {
+        REQUIRE(mode == TR_DECAY_L2 || mode == TR_DECAY_DECOUPLED, BBMPC_E_INVALID,
+                "trainer: unknown weight decay mode " + std::to_string(mode) + " (BBMPC_TRAIN_DECAY_L2 or BBMPC_TRAIN_DECAY_DECOUPLED)");
+        for (int l = 0; decay && l < net.L; ++l)
+            REQUIRE(std::isfinite(decay[l]) && decay[l] >= 0.0f, BBMPC_E_INVALID,
+                    "trainer: weight decay of layer " + std::to_string(l) + " must be finite and >= 0");
+        for (int l = 0; l < TR_MAX_LAYERS; ++l) wd[l] = decay && l < net.L ? decay[l] : 0.0f;
+        wd_mode = mode;
+    }
+
+    void set_early_stopping(int patience_, float min_delta_, int restore) {
+        REQUIRE(patience_ >= 0, BBMPC_E_INVALID, "trainer: patience must be >= 0 (0: no early stopping)");
+        REQUIRE(std::isfinite(min_delta_) && min_delta_ >= 0.0f, BBMPC_E_INVALID, "trainer: min_delta must be finite and >= 0");
+        patience = patience_;
+        min_delta = min_delta_;
+        restore_best = restore != 0;
+    }
+
+    void get_fit_report(int32_t* epochs_run, int32_t* best_epoch, float* best_val) const {
+        REQUIRE(!rep_epochs.empty(), BBMPC_E_STATE, "trainer: bbmpc_trainer_get_fit_report before any fit");
+        memcpy(epochs_run, rep_epochs.data(), sizeof(int32_t) * E);
+        memcpy(best_epoch, rep_best_epoch.data(), sizeof(int32_t) * E);
+        memcpy(best_val, rep_best_val.data(), sizeof(float) * E);
     }
 
     void gradients(const int32_t* idx_h, int B, float* grads_out, float* loss_out) {
@@ -513,6 +599,28 @@ int bbmpc_trainer_gradients(bbmpc_trainer t, const int32_t* idx, int32_t batch_s
     CHECK_PTR(loss_out);
     t->t->require_single("bbmpc_trainer_gradients", "it is the single trainer's test window (bbmpc_trainer_fit_ensemble fits an ensemble)");
     t->t->gradients(idx, batch_size, grads_out, loss_out);
+    API_END
+}
+
+int bbmpc_trainer_set_weight_decay(bbmpc_trainer t, const float* decay, int32_t mode) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    t->t->set_weight_decay(decay, mode);
+    API_END
+}
+
+int bbmpc_trainer_set_early_stopping(bbmpc_trainer t, int32_t patience, float min_delta, int32_t restore_best) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    t->t->set_early_stopping(patience, min_delta, restore_best);
+    API_END
+}
+
+int bbmpc_trainer_get_fit_report(bbmpc_trainer t, int32_t* epochs_run, int32_t* best_epoch, float* best_val) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    REQUIRE(epochs_run && best_epoch && best_val, BBMPC_E_INVALID, "trainer: null report outputs");
+    t->t->get_fit_report(epochs_run, best_epoch, best_val);
     API_END
 }
 

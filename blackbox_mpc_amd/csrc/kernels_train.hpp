@@ -35,6 +35,27 @@
 // share and loss buffers, the strides the argument structs name for the rest).  The dataset is shared; a member's own rows
 // are an index map (TrainStepArgs::idx).  e is uniform over the workgroup, so the offsets are scalar arithmetic.  A member
 // reads and writes nothing of another's and its arithmetic does not see E: E = 1 is the single trainer, bit for bit.
+//
+// Weight decay, early stopping, best-weights restore.
+//   decay      k_train_update takes one lambda per layer and a mode by value; kernels only, never biases.  w0 is the value
+//              before the step, g the data gradient (2 / (B O) applied), every line one float32 operation:
+//                TR_DECAY_L2         g' = fma(lambda, w0, g), then the rule on g' exactly as on g
+//                TR_DECAY_DECOUPLED  w1 = the rule's result on g, then w = fma(-(lr lambda), w0, w1), lr lambda rounded to
+//                                    float32 once on the host; lr is the base rate, not Adam's lr_t
+//              Both lines sit behind `lambda != 0`: a zero decay adds no operation to the value chain.  The kernel has
+//              always found a parameter's layer to write the layouts; with a decay on, that lookup moves in front of the rule.
+//   monitor    k_train_monitor, one launch per epoch behind k_train_val_reduce, grid (ceil(n_params / 256), E).  A member's
+//              state (TrainMon: best, best_epoch, wait, stopped) is carried the way the Adam powers are: epoch k reads
+//              mon[e][k & 1] and writes mon[e][~k & 1].  Every workgroup of the launch therefore takes its decision from
+//              words no workgroup of the launch writes -- the decision is identical in all of them without a second launch
+//              (decision, then copy) per epoch, and launches are what this trainer's time is made of.  On an improvement
+//              the workgroups copy theta[e] to best_theta[e].  A stopped member's state is carried forward unchanged.
+//   early exit k_train_fwd_bwd, k_train_update, k_train_forward_mse and k_train_val_reduce are given the state epoch k reads
+//              (null: no monitoring) and return at once for a stopped member: uniform over the workgroup, nothing else
+//              touched -- but for the Adam powers, which a stopped member's k_train_update hands from [parity] to
+//              [parity ^ 1] unmultiplied, so that its step count stays its own when the trainer is fitted again.
+//   restore    k_train_restore, grid (ceil(n_params / 256), E), once at the end of a fit: best_theta -> theta and every
+//              layout the step kernel reads, for the members whose best_epoch >= 0.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,6 +74,15 @@ constexpr int TR_ROWS = 16;                      // batch rows per workgroup
 constexpr int TR_LDS_LIMIT = 159 * 1024;         // bytes, as the other kernels' carves
 constexpr int TR_SCRATCH = 64 + 1024;            // floats: 16 row indices (padded to 64) + one word per thread
 constexpr int TR_RULE_NONE = 0, TR_RULE_ADAM = 1, TR_RULE_SGD = 2, TR_RULE_RMSPROP = 3;      // BBMPC_TRAIN_*
+constexpr int TR_DECAY_L2 = 0, TR_DECAY_DECOUPLED = 1;                                        // BBMPC_TRAIN_DECAY_*
+
+// A member's early-stopping state, [E][2]: the epoch-k launches read [k & 1], k_train_monitor writes [~k & 1].
+struct TrainMon {
+    float best;                                  // the best validation loss so far; +inf before the first improvement
+    int best_epoch;                              // its epoch; -1 before
+    int wait;                                    // epochs since
+    int stopped;                                 // 0: running; else the number of epochs the member ran
+};
 
 // activations whose derivative needs the pre-activation (act_grad's x): the forward sweep keeps that tile
 __host__ __device__ inline bool train_needs_pre(int act) { return act == ACT_SWISH; }
@@ -139,6 +169,7 @@ struct TrainStepArgs {
     int B;
     float* part;                                 // [E][tiles][n_params]
     float* lossp;                                // [E][tiles] sum of squared errors
+    const TrainMon* stop;                        // member e's state at [2 e] (the parity is in the pointer); null: none
 };
 
 struct TrainMseArgs {
@@ -149,6 +180,7 @@ struct TrainMseArgs {
     int tiles_per_batch;
     float* tile_loss;                            // [E][batches * tiles_per_batch] or null
     float* colsq;                                // [E][batches * tiles_per_batch][O] or null
+    const TrainMon* stop;                        // as TrainStepArgs::stop
 };
 
 struct TrainUpdateArgs {
@@ -169,9 +201,42 @@ struct TrainUpdateArgs {
     float* loss_acc;                             // += the batch loss (TR_RULE_NONE: = )
     int loss_stride;                             // floats from member e's loss_acc to member e + 1's
     float* grads_out;                            // TR_RULE_NONE: the summed gradient [E][n_params]
+    float wd[TR_MAX_LAYERS];                     // lambda_l of W_l; all zero: no decay
+    float lrwd[TR_MAX_LAYERS];                   // float32 lr * lambda_l (TR_DECAY_DECOUPLED)
+    int wd_mode;                                 // TR_DECAY_*
+    int wd_on;                                   // is any lambda_l != 0?
+    const TrainMon* stop;                        // as TrainStepArgs::stop
 };
 
 #ifdef BBMPC_TU_TRAIN
+
+// has member e stopped?  (uniform over the workgroup: one scalar load)
+__device__ __forceinline__ bool tr_stopped(const TrainMon* stop, int e) { return stop && stop[2 * e].stopped != 0; }
+
+// The layer parameter i of theta belongs to; returns whether it is a bias.
+__device__ __forceinline__ bool tr_param_layer(const TrainNet& n, int i, int& l) {
+    const bool bias = i >= n.boff[0];
+    l = n.L - 1;
+    if (bias) {
+        while (i < n.boff[l]) --l;
+    } else {
+        while (i < n.woff[l]) --l;
+    }
+    return bias;
+}
+
+// Parameter i (layer l) = w in every layout the step kernel reads; mo: the member's offset into the operand packs.
+__device__ __forceinline__ void tr_write_layouts(const TrainNet& n, size_t mo, int i, int l, bool bias, float w) {
+    if (bias) {
+        n.bp[l][mo + i - n.boff[l]] = w;
+    } else {
+        const int out = n.dims[l + 1];
+        const int k = i - n.woff[l];
+        const int fi = k / out, fo = k - fi * out;
+        n.wf[l][mo + train_wf_index(n.tiles[l], fi, fo)] = w;
+        n.wr[l][mo + train_wr_index(n.tiles[l + 1], fi, fo)] = w;
+    }
+}
 
 __device__ __forceinline__ int tr_addr(int f, int p) {                   // feature f of row p in a tile array
     return (((f >> 4) * 64) + (((f & 15) >> 2) * 16 + p)) * 4 + (f & 3);
@@ -240,8 +305,11 @@ __device__ __forceinline__ void tr_forward(const TrainNet& n, size_t mo, int wav
     }
 }
 
+// MON: is the launch part of a monitored fit (q.stop set)?  The unmonitored instantiation carries no test of it.
+template <bool MON>
 __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (MON && tr_stopped(q.stop, blockIdx.y)) return;
     const TrainNet& n = q.n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = n.nw, nthr = nw * 64;
     const int n0 = blockIdx.x * TR_ROWS;
@@ -358,8 +426,10 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
 
 // Forward only on rows b * B + 16 t .. of batch b (tile t of the batch): squared errors per output column, and their sum.
 // Grid (batches * tiles_per_batch, E): every member on the same rows.
+template <bool MON>
 __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (MON && tr_stopped(q.stop, blockIdx.y)) return;
     const TrainNet& n = q.n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = n.nw * 64;
     const int batch = blockIdx.x / q.tiles_per_batch, tile = blockIdx.x - batch * q.tiles_per_batch;
@@ -394,8 +464,9 @@ __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
 // val_out[0] = mean over the batches of (sum of the batch's tile losses in tile order) / (B O); NaN without a batch.
 // Grid (1, E): member e reads tile_loss[e][..], uses batch_mse[e][batches] and writes val_out[e * val_stride].
 __global__ void k_train_val_reduce(const float* tile_loss, int batches, int tiles_per_batch, float inv_count, float* batch_mse, float* val_out,
-                                   int val_stride) {
+                                   int val_stride, const TrainMon* stop) {
     const int e = blockIdx.y;
+    if (tr_stopped(stop, e)) return;
     tile_loss += (size_t)e * batches * tiles_per_batch;
     batch_mse += (size_t)e * batches;
     val_out += (size_t)e * val_stride;
@@ -423,7 +494,10 @@ __global__ void k_train_rms_reduce(const float* colsq, int tiles, int O, float i
     rms_out[o] = sqrtf(s * inv_rows);
 }
 
-// Grid (ceil(n_params / 256), E).
+// Grid (ceil(n_params / 256), E).  REG: does the launch decay a kernel or belong to a monitored fit?  The instantiation
+// without either is the update as it has always been, instruction for instruction: an early test of q.stop in front of the
+// other arguments' loads cost a default fit 0.5 % when it was there (profiles/train_hip.md).
+template <bool REG>
 __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     const TrainNet& n = q.n;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -436,6 +510,13 @@ __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     float* theta = q.theta + po;
     float* mm = q.m + po;
     float* vv = q.v + po;
+    if (REG && tr_stopped(q.stop, e)) {                            // the powers keep their value and move to the parity the next step reads
+        if (q.rule == TR_RULE_ADAM && i == 0) {
+            pows[(q.parity ^ 1) * 2 + 0] = pows[q.parity * 2 + 0];
+            pows[(q.parity ^ 1) * 2 + 1] = pows[q.parity * 2 + 1];
+        }
+        return;
+    }
     if (i == 0) {
         float s = 0.0f;
         for (int t = 0; t < q.ntiles; ++t) s = s + lossp[t];
@@ -460,7 +541,19 @@ __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
         q.grads_out[po + i] = gsum;
         return;
     }
-    float w = theta[i];
+    // The parameter's layer is looked up before the rule where a decay needs it (wd_on, uniform) and behind the store of the
+    // parameter otherwise, where it has always been.
+    const bool decay = REG && q.wd_on;
+    int l = 0;
+    bool bias = false;
+    float lam = 0.0f;
+    if (decay) {
+        bias = tr_param_layer(n, i, l);
+        lam = bias ? 0.0f : q.wd[l];
+    }
+    const float w0 = theta[i];
+    float w = w0;
+    if (lam != 0.0f && q.wd_mode == TR_DECAY_L2) gsum = __fmaf_rn(lam, w0, gsum);
     if (q.rule == TR_RULE_SGD) {
         w = w + (-q.lr) * gsum;
     } else if (q.rule == TR_RULE_RMSPROP) {
@@ -475,22 +568,56 @@ __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
         vv[i] = v;
         w = w + (-lr_t) * (m / (sqrtf(v) + q.eps));
     }
+    if (lam != 0.0f && q.wd_mode == TR_DECAY_DECOUPLED) w = __fmaf_rn(-q.lrwd[l], w0, w);
     theta[i] = w;
-    // every layout the step kernel reads
-    const int L = n.L;
-    if (i >= n.boff[0]) {
-        int l = L - 1;
-        while (i < n.boff[l]) --l;
-        n.bp[l][mo + i - n.boff[l]] = w;
-    } else {
-        int l = L - 1;
-        while (i < n.woff[l]) --l;
-        const int out = n.dims[l + 1];
-        const int k = i - n.woff[l];
-        const int fi = k / out, fo = k - fi * out;
-        n.wf[l][mo + train_wf_index(n.tiles[l], fi, fo)] = w;
-        n.wr[l][mo + train_wr_index(n.tiles[l + 1], fi, fo)] = w;
+    if (!decay) bias = tr_param_layer(n, i, l);
+    tr_write_layouts(n, mo, i, l, bias, w);                         // every layout the step kernel reads
+}
+
+// Epoch k's decision for every member, behind k_train_val_reduce.  Grid (ceil(n_params / 256), E), or (1, E) with
+// best_theta null (nothing to restore later: no snapshot).  val: the epoch's validation loss of member 0, member e's
+// val_stride floats further.  v improves on best if v < best - min_delta in float32: NaN never does, and the first finite
+// (or -inf) v does, whatever min_delta is.
+__global__ __launch_bounds__(256) void k_train_monitor(TrainMon* mon, const float* val, int val_stride, int k, int patience, float min_delta,
+                                                       const float* theta, float* best_theta, int n_params) {
+    const int e = blockIdx.y;
+    const TrainMon s = mon[2 * e + (k & 1)];
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (s.stopped) {
+        if (first) mon[2 * e + ((k & 1) ^ 1)] = s;
+        return;
     }
+    const float v = val[(size_t)e * val_stride];
+    const bool better = v < s.best - min_delta;
+    if (first) {
+        TrainMon o = s;
+        if (better) {
+            o.best = v;
+            o.best_epoch = k;
+            o.wait = 0;
+        } else {
+            o.wait = s.wait + 1;
+        }
+        if (patience > 0 && o.wait >= patience) o.stopped = k + 1;
+        mon[2 * e + ((k & 1) ^ 1)] = o;
+    }
+    if (better && best_theta) {
+        const int i = blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < n_params) best_theta[(size_t)e * n_params + i] = theta[(size_t)e * n_params + i];
+    }
+}
+
+// best_theta -> theta and every layout, for the members with a best epoch; mon: the state after the last epoch.
+// Grid (ceil(n_params / 256), E).
+__global__ __launch_bounds__(256) void k_train_restore(TrainNet n, const TrainMon* mon, const float* best_theta, float* theta) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int e = blockIdx.y;
+    if (mon[2 * e].best_epoch < 0 || i >= n.n_params) return;
+    const float w = best_theta[(size_t)e * n.n_params + i];
+    theta[(size_t)e * n.n_params + i] = w;
+    int l;
+    const bool bias = tr_param_layer(n, i, l);
+    tr_write_layouts(n, (size_t)e * n.pstride, i, l, bias, w);
 }
 
 #endif  // BBMPC_TU_TRAIN

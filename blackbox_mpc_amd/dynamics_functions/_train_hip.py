@@ -14,9 +14,11 @@ import os
 import numpy as np
 
 from .. import _lib as L
+from . import _train_reg as R
 
 BACKENDS = ("torch", "hip")
 _RULES = {"adam": L.TRAIN_ADAM, "sgd": L.TRAIN_SGD, "rmsprop": L.TRAIN_RMSPROP}
+_DECAY_MODES = {"l2": L.TRAIN_DECAY_L2, "decoupled": L.TRAIN_DECAY_DECOUPLED}
 
 
 def check_backend(backend):
@@ -77,15 +79,59 @@ def _ptr_array(arrays):
     return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
 
 
-class HipDenseTrainer:
+class _Regularized:
+    """What HipDenseTrainer and HipEnsembleTrainer share of DESIGN.md section 8r: the settings (bbmpc_trainer_set_weight_decay,
+    bbmpc_trainer_set_early_stopping; checked here before the library is called, kept by the trainer from fit to fit) and the
+    last fit's report (bbmpc_trainer_get_fit_report)."""
+    patience, restore_best = 0, False
+    _n_val = None                                 # rows of the validation set on the device; None before set_data
+
+    def _require_validation(self, batch_size):
+        """Monitoring without a full validation batch is refused here as the library refuses it (a fit before set_data is the
+        library's to refuse)."""
+        if self._n_val is not None:
+            R.require_validation(self.patience, self.restore_best, self._n_val, batch_size)
+
+    def set_weight_decay(self, weight_decay=0.0, decay_mode="l2"):
+        """`weight_decay`: a scalar or one value per layer, on the kernels only; 0: off."""
+        decay = R.check_options(weight_decay, decay_mode, n_layers=len(self.acts))[0]
+        L.check(L.lib.bbmpc_trainer_set_weight_decay(self._t, L.ptr(decay), _DECAY_MODES[decay_mode]))
+
+    def set_early_stopping(self, patience=0, min_delta=0.0, restore_best=False):
+        _, _, patience, min_delta, restore_best = R.check_options(patience=patience, min_delta=min_delta, restore_best=restore_best)
+        L.check(L.lib.bbmpc_trainer_set_early_stopping(self._t, patience, min_delta, int(restore_best)))
+        self.patience, self.restore_best = patience, restore_best
+
+    def _configure(self, weight_decay, decay_mode, patience, min_delta, restore_best):
+        """The constructor's options: the library is told only what differs from its defaults."""
+        given = R.non_default(weight_decay, decay_mode, patience, min_delta, restore_best)
+        if "weight_decay" in given or "decay_mode" in given:
+            self.set_weight_decay(weight_decay, decay_mode)
+        if given.keys() & {"patience", "min_delta", "restore_best"}:
+            self.set_early_stopping(patience, min_delta, restore_best)
+
+    def _fit_report(self, members, epochs):
+        if not R.monitoring(self.patience, self.restore_best):      # nothing was tracked: no call into the library
+            return np.full((members,), epochs, np.int64), np.full((members,), -1, np.int64), np.full((members,), np.nan)
+        epochs_run, best_epoch = np.zeros((members,), np.int32), np.zeros((members,), np.int32)
+        best_val = np.zeros((members,), np.float32)
+        L.check(L.lib.bbmpc_trainer_get_fit_report(self._t, L.ptr(epochs_run), L.ptr(best_epoch), L.ptr(best_val)))
+        return epochs_run.astype(np.int64), best_epoch.astype(np.int64), best_val.astype(np.float64)
+
+
+class HipDenseTrainer(_Regularized):
     has_logvar_head = False
 
     def __init__(self, weights, biases, act_codes, device=None, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
-                 rule="adam", rho=0.9, logvar_head=None):
+                 rule="adam", rho=0.9, logvar_head=None, weight_decay=0.0, decay_mode="l2", patience=0, min_delta=0.0,
+                 restore_best=False):
         """DenseTrainer's arguments.  The Keras TF-2.0 defaults (beta_1 0.9, beta_2 0.999, epsilon 1e-7, rho 0.9) are the
-        only constants the kernels are built with."""
+        only constants the kernels are built with.  weight_decay .. restore_best: `_train_reg`'s options, decided on the
+        device (no host synchronisation inside a fit); after a fit `epochs_run`, `best_epoch` (-1: none, or no monitoring)
+        and `best_val` describe it."""
         if rule not in _RULES:
             raise ValueError("unknown optimizer rule %r" % (rule,))
+        R.check_options(weight_decay, decay_mode, patience, min_delta, restore_best, n_layers=len(weights))
         if logvar_head is not None:
             raise ValueError("the hip training backend fits plain Dense stacks (MSE); a log-variance head (Gaussian NLL) "
                              "trains with backend='torch'")
@@ -109,6 +155,8 @@ class HipDenseTrainer:
         L.check(L.lib.bbmpc_trainer_create(ctypes.byref(self._t), _device_index(device), len(self._w), dims.ctypes.data_as(i32p),
                                            acts.ctypes.data_as(i32p), _ptr_array(self._w), _ptr_array(self._b), _RULES[rule],
                                            float(learning_rate)))
+        self._configure(weight_decay, decay_mode, patience, min_delta, restore_best)
+        self.epochs_run, self.best_epoch, self.best_val = 0, -1, float("nan")
 
     def close(self):
         t, self._t = getattr(self, "_t", None), None
@@ -129,7 +177,7 @@ class HipDenseTrainer:
         if tin.shape[1] != self.dims[0] or tout.shape[1] != self.dims[-1] or tin.shape[0] != tout.shape[0] \
                 or vin.shape[0] != vout.shape[0]:
             raise ValueError("rows %s -> %s do not fit the network %s" % (tin.shape, tout.shape, self.dims))
-        self._n_train = tin.shape[0]
+        self._n_train, self._n_val = tin.shape[0], vin.shape[0]
         L.check(L.lib.bbmpc_trainer_set_data(self._t, L.ptr(tin), L.ptr(tout), tin.shape[0], L.ptr(vin), L.ptr(vout), vin.shape[0]))
 
     def fit(self, train_in, train_out, val_in, val_out, epochs, batch_size, permutations=None, generator_seed=None):
@@ -140,6 +188,7 @@ class HipDenseTrainer:
     def fit_resident(self, epochs, batch_size, permutations=None, generator_seed=None):
         """`fit` on the rows `set_data` left on the device."""
         epochs = int(epochs)
+        self._require_validation(batch_size)
         perms = None
         if permutations is not None:
             perms = np.ascontiguousarray(np.asarray(permutations)[:epochs], np.int32).reshape(epochs, self._n_train)
@@ -147,6 +196,8 @@ class HipDenseTrainer:
         tl, vl = np.zeros((epochs,), np.float32), np.zeros((epochs,), np.float32)
         L.check(L.lib.bbmpc_trainer_fit(self._t, epochs, int(batch_size), L.ptr(perms), ctypes.c_uint64(seed & ((1 << 64) - 1)),
                                         L.ptr(tl), L.ptr(vl)))
+        report = self._fit_report(1, epochs)
+        self.epochs_run, self.best_epoch, self.best_val = int(report[0][0]), int(report[1][0]), float(report[2][0])
         return tl.astype(np.float64), vl.astype(np.float64)
 
     def gradients(self, idx):
@@ -197,16 +248,20 @@ def check_index_bound(n_members, epochs, n_train):
                                             "the limit is below %d" % (count, 1 << 31))
 
 
-class HipEnsembleTrainer:
+class HipEnsembleTrainer(_Regularized):
     """E equally shaped Dense stacks fitted side by side (bbmpc_trainer_create_ensemble; DESIGN.md section 8p, "Members"): the
     member index is a second grid dimension of the training kernels, the dataset is on the device once and a member's
     bootstrap resample is an index map.  Member e's results are, bit for bit, those of a `HipDenseTrainer` fitted on
     `train_in[member_rows[e]]` with member e's start weights and permutations."""
     has_logvar_head = False
 
-    def __init__(self, weights_per_member, biases_per_member, act_codes, device=None, learning_rate=1e-3, rule="adam"):
+    def __init__(self, weights_per_member, biases_per_member, act_codes, device=None, learning_rate=1e-3, rule="adam",
+                 weight_decay=0.0, decay_mode="l2", patience=0, min_delta=0.0, restore_best=False):
+        """weight_decay .. restore_best: `_train_reg`'s options, the same for every member; the members monitor, stop and
+        restore independently, and after a fit `epochs_run`, `best_epoch`, `best_val` are arrays [E]."""
         if rule not in _RULES:
             raise ValueError("unknown optimizer rule %r" % (rule,))
+        R.check_options(weight_decay, decay_mode, patience, min_delta, restore_best, n_layers=len(act_codes))
         self._t = ctypes.c_void_p(None)
         if len(weights_per_member) != len(biases_per_member):
             raise ValueError("one list of biases per list of kernels")
@@ -231,6 +286,10 @@ class HipEnsembleTrainer:
             ctypes.byref(self._t), _device_index(device), self.n_members, len(self.acts), dims.ctypes.data_as(i32p),
             acts.ctypes.data_as(i32p), _ptr_array([w for ws in self._w for w in ws]), _ptr_array([b for bs in self._b for b in bs]),
             _RULES[rule], float(learning_rate)))
+        self._configure(weight_decay, decay_mode, patience, min_delta, restore_best)
+        self.epochs_run = np.zeros((self.n_members,), np.int64)
+        self.best_epoch = np.full((self.n_members,), -1, np.int64)
+        self.best_val = np.full((self.n_members,), np.nan)
 
     member_seed = staticmethod(member_seed)
 
@@ -256,7 +315,7 @@ class HipEnsembleTrainer:
             rows = np.ascontiguousarray(member_rows, np.int32)
             if rows.shape != (self.n_members, tin.shape[0]):
                 raise ValueError("member_rows: [%d][%d] training rows, got %s" % (self.n_members, tin.shape[0], rows.shape))
-        self._n_train = tin.shape[0]
+        self._n_train, self._n_val = tin.shape[0], vin.shape[0]
         L.check(L.lib.bbmpc_trainer_set_data(self._t, L.ptr(tin), L.ptr(tout), tin.shape[0], L.ptr(vin), L.ptr(vout), vin.shape[0]))
         if rows is not None:
             L.check(L.lib.bbmpc_trainer_set_member_rows(self._t, L.ptr(rows)))
@@ -273,6 +332,7 @@ class HipEnsembleTrainer:
         """`fit` on the rows (and member rows) `set_data` left on the device."""
         epochs, E, n = int(epochs), self.n_members, self._n_train
         check_index_bound(E, epochs, n)
+        self._require_validation(batch_size)
         perms = None
         if permutations is not None:
             p = np.asarray(permutations)
@@ -285,6 +345,7 @@ class HipEnsembleTrainer:
         tl, vl = np.zeros((E, epochs), np.float32), np.zeros((E, epochs), np.float32)
         L.check(L.lib.bbmpc_trainer_fit_ensemble(self._t, epochs, int(batch_size), L.ptr(perms), ctypes.c_uint64(seed & ((1 << 64) - 1)),
                                                  L.ptr(tl), L.ptr(vl)))
+        self.epochs_run, self.best_epoch, self.best_val = self._fit_report(E, epochs)
         return tl.astype(np.float64), vl.astype(np.float64)
 
     def residual_rms(self, val_in, val_out):

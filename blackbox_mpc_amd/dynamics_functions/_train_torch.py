@@ -85,7 +85,8 @@ def _act_grad(code, y, g, z=None):
 
 class DenseTrainer:
     def __init__(self, weights, biases, act_codes, device, learning_rate=1e-3, beta_1=0.9, beta_2=0.999,
-                 epsilon=1e-7, rule="adam", rho=0.9, logvar_head=None):
+                 epsilon=1e-7, rule="adam", rho=0.9, logvar_head=None, weight_decay=0.0, decay_mode="l2", patience=0,
+                 min_delta=0.0, restore_best=False):
         """rule: "adam" | "sgd" | "rmsprop" -- tf.keras.optimizers.{Adam, SGD, RMSprop}(learning_rate=lr) with their
         TF-2.0 defaults, which is how the reference instantiates `nn_optimizer` (system_dynamics_handler.py:261):
           sgd      w -= lr * g                                              (momentum 0)
@@ -95,9 +96,17 @@ class DenseTrainer:
           z = h W_v + b_v;  lv1 = max_lv - softplus(max_lv - z);  lv = min_lv + softplus(lv1 - min_lv)
           loss = mean over the batch's B * out elements of (mu - y)^2 exp(-lv) + lv
         with the backward pass written out like the Dense stack's (dlv/dz = sigmoid(lv1 - min_lv) sigmoid(max_lv - z));
-        W_v and b_v join `params`, so every update rule and the captured step cover them.  The bounds are fixed."""
+        W_v and b_v join `params`, so every update rule and the captured step cover them.  The bounds are fixed.
+        weight_decay / decay_mode / patience / min_delta / restore_best: `_train_reg`'s options.
+        Decay is part of the (captured) step; W_v is decayed like any kernel, with the last layer's lambda.  The monitor
+        runs on the host after each epoch's validation loss (the NLL with a log-variance head), which this trainer
+        reads per epoch anyway.  After a fit: `epochs_run`, `best_epoch` (-1: none, or no monitoring), `best_val`."""
         if rule not in ("adam", "sgd", "rmsprop"):
             raise ValueError("unknown optimizer rule %r" % (rule,))
+        from . import _train_reg as R
+        self.decay, self.decay_mode, self.patience, self.min_delta, self.restore_best = R.check_options(
+            weight_decay, decay_mode, patience, min_delta, restore_best, n_layers=len(weights))
+        self.epochs_run, self.best_epoch, self.best_val = 0, -1, float("nan")
         self.rule, self.rho = rule, float(rho)
         import torch
         self.torch = torch
@@ -120,6 +129,12 @@ class DenseTrainer:
             self.params = self.params + [self.wv, self.bv]
         self.m = [torch.zeros_like(p) for p in self.params]
         self.v = [torch.zeros_like(p) for p in self.params]
+        # (index into params / grads, lambda) of every decayed kernel
+        self._decayed = []
+        if self.decay is not None:
+            self._decayed = [(l, float(lam)) for l, lam in enumerate(self.decay) if lam > 0]
+            if self.has_logvar_head and self.decay[-1] > 0:
+                self._decayed.append((2 * len(self.w), float(self.decay[-1])))
         self.lr, self.b1, self.b2, self.eps = float(learning_rate), float(beta_1), float(beta_2), float(epsilon)
         # running powers b1^t, b2^t as device scalars so that the step is graph-capturable
         self.b1t = torch.ones((), device=self.dev, dtype=torch.float64)
@@ -188,6 +203,22 @@ class DenseTrainer:
                     g = g + gz @ self.wv.t()
         if gz is not None:
             grads = grads + [ys[n - 1].t() @ gz, gz.sum(dim=0)]
+        if self._decayed:
+            # both modes use the kernels as they are before the step
+            if self.decay_mode == "l2":
+                for i, lam in self._decayed:
+                    grads[i] = torch.add(grads[i], self.params[i], alpha=lam)
+                self._rule(grads)
+            else:
+                before = [self.params[i].clone() for i, _ in self._decayed]
+                self._rule(grads)
+                for (i, lam), w0 in zip(self._decayed, before):
+                    self.params[i].add_(w0, alpha=-(self.lr * lam))
+            return
+        self._rule(grads)
+
+    def _rule(self, grads):
+        torch = self.torch
         if self.rule == "sgd":
             torch._foreach_add_(self.params, grads, alpha=-self.lr)
             return
@@ -228,6 +259,10 @@ class DenseTrainer:
         vout = torch.as_tensor(np.ascontiguousarray(val_out, np.float32)).to(self.dev)
         n = self._din.shape[0]
         nb = n // batch_size                                    # drop_remainder=True (:201-202)
+        from . import _train_reg as R
+        R.require_validation(self.patience, self.restore_best, vin.shape[0], batch_size)
+        monitor = R.Monitor(self.patience, self.min_delta) if R.monitoring(self.patience, self.restore_best) else None
+        snapshot = None
         self._perm = torch.zeros((max(n, batch_size),), dtype=torch.int64, device=self.dev)
         self._ar = torch.arange(batch_size, dtype=torch.int64, device=self.dev)
         self._pos = torch.zeros((), dtype=torch.int64, device=self.dev)
@@ -255,6 +290,7 @@ class DenseTrainer:
             for t, c in zip(state, snap):
                 t.copy_(c)
         tl, vl = np.full((epochs,), np.nan), np.full((epochs,), np.nan)
+        self.epochs_run = epochs
         for e in range(epochs):
             if permutations is not None:
                 perm = torch.as_tensor(np.asarray(permutations[e], np.int64)).to(self.dev)
@@ -276,10 +312,21 @@ class DenseTrainer:
                     with torch.no_grad():
                         d = self.nll(vin[:nvb * batch_size], vout[:nvb * batch_size]).reshape(nvb, -1)
                     vl[e] = float(d.mean(dim=1).mean().item())      # mean of per-batch NLLs
-                    continue
-                pv = self.forward(vin[:nvb * batch_size])[-1]
-                d = (pv - vout[:nvb * batch_size]).reshape(nvb, -1)
-                vl[e] = float((d * d).mean(dim=1).mean().item())    # mean of per-batch MSEs (:276-284)
+                else:
+                    pv = self.forward(vin[:nvb * batch_size])[-1]
+                    d = (pv - vout[:nvb * batch_size]).reshape(nvb, -1)
+                    vl[e] = float((d * d).mean(dim=1).mean().item())    # mean of per-batch MSEs (:276-284)
+            if monitor is not None:
+                improved, stop = monitor.update(e, vl[e])
+                if improved and self.restore_best:
+                    snapshot = [p.clone() for p in self.params]
+                if stop:
+                    self.epochs_run = e + 1
+                    break
+        self.best_epoch, self.best_val = (monitor.best_epoch, monitor.best_val) if monitor is not None else (-1, float("nan"))
+        if snapshot is not None:                                # weights only: m, v and the powers stay
+            for p, s in zip(self.params, snapshot):
+                p.copy_(s)
         return tl, vl
 
     def residual_rms(self, val_in, val_out):

@@ -231,7 +231,8 @@ class SystemDynamicsHandler:
 
     def train(self, observations_trajectories, actions_trajectories, rewards_trajectories, validation_split=0.2,
               batch_size=128, learning_rate=1e-3, epochs=30, nn_optimizer=None, *, device=None, seed=None,
-              split_mask=None, permutations=None, bootstrap_indices=None, backend="torch"):
+              split_mask=None, permutations=None, bootstrap_indices=None, backend="torch", weight_decay=0.0, decay_mode="l2",
+              patience=0, min_delta=0.0, restore_best=False):
         """Reference signature (:163-166); `nn_optimizer`: None / "Adam" / "SGD" / "RMSprop" or a class of that name
         (the reference's callers only ever pass tf.keras.optimizers.Adam).  Keyword-only extras: `device` (default: the GPU -- training on the
         host has to be asked for explicitly with device="cpu"), and the injected random draws `split_mask`,
@@ -242,9 +243,16 @@ class SystemDynamicsHandler:
         residual_std() stays the mean network's residual.  `backend`: "torch" (DenseTrainer, the default) or "hip"
         (dynamics_functions/_train_hip.HipDenseTrainer: the hand-written training kernels, GPU only, plain MSE models --
         a model with a log-variance head is refused by name; the members of an EnsembleMLP are fitted by one
-        HipEnsembleTrainer, all of them in one launch sequence)."""
+        HipEnsembleTrainer, all of them in one launch sequence).
+        `weight_decay` (a scalar or one value per layer, kernels only) / `decay_mode` ("l2" | "decoupled"), `patience` /
+        `min_delta` (early stopping on the validation loss) and `restore_best` (the best epoch's weights are installed):
+        dynamics_functions/_train_reg.py; both backends, every member of an ensemble on its own.
+        They reach the trainer only where they differ from the defaults.  `epochs_run` / `best_epoch` (and
+        `member_epochs_run` / `member_best_epoch`) record the fit; residual_std() is that of the installed weights."""
         from ..dynamics_functions._train_hip import check_backend, dense_trainer
+        from ..dynamics_functions._train_reg import non_default
         check_backend(backend)
+        reg = non_default(weight_decay, decay_mode, patience, min_delta, restore_best)
         if self._is_true_model:
             raise Exception("the true model has nothing to train")
         # the reference instantiates `nn_optimizer(learning_rate=learning_rate)` (:261): a Keras optimizer CLASS (or its
@@ -274,14 +282,15 @@ class SystemDynamicsHandler:
         vin, vout = self._normalize_data(self._model_validation_in, self._model_validation_out)
         if hasattr(fn, "members"):
             self._train_ensemble(fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
-                                 bootstrap_indices, backend)
+                                 bootstrap_indices, backend, reg)
             return self._after_training()
         if bootstrap_indices is not None:
             raise ValueError("bootstrap_indices are the resamples of an EnsembleMLP's members")
         trainer = dense_trainer(backend, fn.weights, fn.biases, fn.activation_codes, device, learning_rate=learning_rate, rule=rule,
-                                logvar_head=_logvar_head(fn))              # fresh optimizer per call (:258)
+                                logvar_head=_logvar_head(fn), **reg)       # fresh optimizer per call (:258)
         self.training_loss, self.validation_loss = trainer.fit(tin, tout, vin, vout, epochs, batch_size,
                                                                permutations=permutations, generator_seed=seed)
+        self.epochs_run, self.best_epoch = getattr(trainer, "epochs_run", epochs), getattr(trainer, "best_epoch", -1)
         self._residual_rms = trainer.residual_rms(vin, vout)              # normalised target units; residual_std() scales it
         self._trained = True
         fn.set_weights(*trainer.numpy_params())                            # bumps the version: evaluators re-upload
@@ -298,15 +307,18 @@ class SystemDynamicsHandler:
         return
 
     def _train_ensemble(self, fn, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, permutations,
-                        bootstrap_indices, backend="torch"):
+                        bootstrap_indices, backend="torch", reg=None):
         """The members of an EnsembleMLP on the (normalised) rows train() prepared -- statistics, split and the
         freeze-after-first rule are shared.  Member e is fitted by a fresh trainer (backend "hip": all members by one
         HipEnsembleTrainer, `_fit_members_hip`, with the same results) on a bootstrap resample of the training rows: n_train indices drawn with replacement, `bootstrap_indices[e]` when given, else from
         np.random.default_rng([seed, e]) -- which then also draws the member's epoch permutations.  Injected
         `permutations` are [E][epochs] (one list per member) or [epochs] (shared by the members).
         training_loss / validation_loss stay member 0's; the per-member lists go to member_training_loss /
-        member_validation_loss, and residual_std() becomes the RMS over members of the members' validation residuals."""
+        member_validation_loss, and residual_std() becomes the RMS over members of the members' validation residuals.
+        `reg`: train()'s non-default regularisation options, for every member's trainer; member_epochs_run /
+        member_best_epoch record each member's fit, epochs_run / best_epoch member 0's."""
         from ..dynamics_functions._train_hip import dense_trainer
+        reg = dict(reg or {})
         n, members = tin.shape[0], fn.members
         if bootstrap_indices is not None:
             if len(bootstrap_indices) != len(members):
@@ -328,33 +340,39 @@ class SystemDynamicsHandler:
                 perms = permutations[e] if per_member else permutations
             draws.append((idx, perms))
         if backend == "hip":
-            tl, vl, rms = self._fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed)
+            tl, vl, rms, ran, best = self._fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule,
+                                                           device, seed, reg)
         else:
-            tl, vl, rms = [], [], []
+            tl, vl, rms, ran, best = [], [], [], [], []
             for member, (idx, perms) in zip(members, draws):
                 trainer = dense_trainer(backend, member.weights, member.biases, member.activation_codes, device,
-                                        learning_rate=learning_rate, rule=rule, logvar_head=_logvar_head(member))
+                                        learning_rate=learning_rate, rule=rule, logvar_head=_logvar_head(member), **reg)
                 tl_e, vl_e = trainer.fit(tin[idx], tout[idx], vin, vout, epochs, batch_size, permutations=perms, generator_seed=seed)
                 tl.append(tl_e)
                 vl.append(vl_e)
+                ran.append(getattr(trainer, "epochs_run", epochs))
+                best.append(getattr(trainer, "best_epoch", -1))
                 rms.append(trainer.residual_rms(vin, vout))
                 member.set_weights(*trainer.numpy_params())                # bumps the version: evaluators re-upload
                 if trainer.has_logvar_head:
                     member.set_logvar_head(*trainer.numpy_logvar_head())
         self.member_training_loss, self.member_validation_loss = tl, vl
         self.training_loss, self.validation_loss = self.member_training_loss[0], self.member_validation_loss[0]
+        self.member_epochs_run, self.member_best_epoch = [int(v) for v in ran], [int(v) for v in best]
+        self.epochs_run, self.best_epoch = self.member_epochs_run[0], self.member_best_epoch[0]
         self._residual_rms = None if rms[0] is None else np.sqrt(np.mean(np.square(np.asarray(rms, np.float64)), axis=0)).astype(np.float32)
         self._trained = True
 
     @staticmethod
-    def _fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed):
+    def _fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule, device, seed, reg=None):
         """`_train_ensemble`'s loop as ONE HipEnsembleTrainer and one fit ("Members"): the rows go to
         the device once, member e's bootstrap resample is the index map `member_rows[e]`, and every step is one launch pair
         for all members.  Bit for bit what a HipDenseTrainer per member on `tin[idx]` gives.  Returns the per-member lists
-        (training loss, validation loss, residual RMS)."""
+        (training loss, validation loss, residual RMS -- of the weights the fit leaves, restored ones included -- epochs run,
+        best epoch)."""
         from ..dynamics_functions._train_hip import HipEnsembleTrainer
         trainer = HipEnsembleTrainer([m.weights for m in members], [m.biases for m in members], members[0].activation_codes,
-                                     device, learning_rate=learning_rate, rule=rule)
+                                     device, learning_rate=learning_rate, rule=rule, **(reg or {}))
         try:
             tl, vl = trainer.fit(tin, tout, vin, vout, epochs, batch_size, member_rows=[idx for idx, _ in draws],
                                  permutations=[np.asarray(perms)[:epochs] for _, perms in draws], generator_seed=seed)
@@ -363,7 +381,9 @@ class SystemDynamicsHandler:
                 member.set_weights(*trainer.numpy_params(e))               # bumps the version: evaluators re-upload
         finally:
             trainer.close()
-        return list(tl), list(vl), ([None] * len(members) if rms is None else list(rms))
+        ran = getattr(trainer, "epochs_run", [epochs] * len(members))
+        best = getattr(trainer, "best_epoch", [-1] * len(members))
+        return list(tl), list(vl), ([None] * len(members) if rms is None else list(rms)), list(ran), list(best)
 
     def residual_std(self):
         """Per-dimension RMS of (target - prediction) in state units on the held-out validation rows of the last train():

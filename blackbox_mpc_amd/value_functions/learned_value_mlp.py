@@ -119,15 +119,21 @@ class LearnedValueMLP:
 
     # -- training -------------------------------------------------------------------------------------------------------
     def train(self, states, targets, epochs=30, batch_size=128, learning_rate=1e-3, validation_split=0.2, device=None,
-              seed=None, normalize=True, backend="torch"):
+              seed=None, normalize=True, backend="torch", *, weight_decay=0.0, decay_mode="l2",
+              patience=0, min_delta=0.0, restore_best=False):
         """Fit MSE on normalised targets with Keras-Adam (dynamics_functions/_train_torch.DenseTrainer, on `device`: the
         GPU when PyTorch sees one, else the CPU).  states [B, S], targets [B].  The statistics are refreshed from exactly
         these rows and the version is bumped, so every engine that holds the network uploads it again before its next
         computation.  Returns (train_loss [epochs], validation_loss [epochs]).
         backend: "torch" (the default) or "hip" -- the hand-written training kernels
-        (dynamics_functions/_train_hip.HipDenseTrainer; GPU only, permutations drawn by the library from `seed`)."""
+        (dynamics_functions/_train_hip.HipDenseTrainer; GPU only, permutations drawn by the library from `seed`).
+        weight_decay / decay_mode / patience / min_delta / restore_best (keyword-only): weight decay on the kernels, early
+        stopping on the validation loss and best-weights restore (dynamics_functions/_train_reg.py),
+        handed to the trainer only where they differ from the defaults; `epochs_run` / `best_epoch` record the fit."""
         from ..dynamics_functions._train_hip import check_backend, dense_trainer
+        from ..dynamics_functions._train_reg import non_default
         check_backend(backend)
+        reg = non_default(weight_decay, decay_mode, patience, min_delta, restore_best)
         x = np.asarray(states, np.float32).reshape(-1, self.dim_S)
         y = np.asarray(targets, np.float32).reshape(-1, 1)
         if x.shape[0] != y.shape[0]:
@@ -147,7 +153,7 @@ class LearnedValueMLP:
         if device is None and backend == "torch":
             import torch
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        tr = dense_trainer(backend, self.weights, self.biases, self.activation_codes, device, learning_rate=learning_rate)
+        tr = dense_trainer(backend, self.weights, self.biases, self.activation_codes, device, learning_rate=learning_rate, **reg)
         bs = max(1, min(int(batch_size), len(trn)))
         losses = tr.fit(xn[trn], yn[trn], xn[val], yn[val], int(epochs), bs,
                         generator_seed=None if seed is None else int(seed))
@@ -155,6 +161,7 @@ class LearnedValueMLP:
         self._stats = stats
         self.set_weights(ws, bs_)
         self.train_loss, self.validation_loss = [float(v) for v in losses[0]], [float(v) for v in losses[1]]
+        self.epochs_run, self.best_epoch = getattr(tr, "epochs_run", int(epochs)), getattr(tr, "best_epoch", -1)
         return losses
 
     def train_on_rollouts(self, traj_obs, traj_rews, n_step, gamma=1.0, bootstrap=False, terminated=None, **train_args):

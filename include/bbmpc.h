@@ -894,6 +894,42 @@ int bbmpc_trainer_get_member_params(bbmpc_trainer t, int32_t member, float* cons
 /* bbmpc_trainer_residual_rms of every member on the same n >= 1 host rows (uploaded once): rms_out [n_members][dims[n_layers]]. */
 int bbmpc_trainer_residual_rms_ensemble(bbmpc_trainer t, const float* in, const float* out, int32_t n, float* rms_out);
 
+/* ---- weight decay, early stopping, best-weights restore ---------------------------------------------
+ * Three settings of a trainer of either kind.  They hold from one fit to the next until they are set again; a trainer that
+ * never sets them, or sets them to (NULL, patience 0, restore_best 0), fits bit for bit as described above, with the same
+ * launches.  Reported losses stay the data term (MSE) and bbmpc_trainer_gradients the data gradient.
+ *
+ * Weight decay: one lambda_l >= 0 per layer, on the kernels W_l only, never on biases.  w0 is W_l before the step, g the
+ * data gradient; every line is one float32 operation:
+ *   BBMPC_TRAIN_DECAY_L2         g' = fma(lambda_l, w0, g); the rule then runs on g' exactly as it runs on g
+ *   BBMPC_TRAIN_DECAY_DECOUPLED  w1 = the rule's result on g; w = fma(-(lr lambda_l), w0, w1), lr the BASE rate (not Adam's
+ *                                lr_t), the product lr lambda_l rounded to float32 once (AdamW-style)
+ * A lambda_l of 0 adds no operation: that layer's bits are the undecayed ones.
+ *
+ * Monitoring is on with patience > 0 or restore_best != 0, and needs a validation loss: a fit whose n_val holds no full
+ * batch is then BBMPC_E_STATE, before anything runs.  Per member, after every epoch k, on the device:
+ *   v_k improves if v_k < best - min_delta (float32; best starts at +inf; a NaN v_k never improves)
+ *   improvement:  best = v_k, best_epoch = k, wait = 0, the member's parameters are copied to a snapshot
+ *   otherwise:    wait += 1
+ *   patience > 0 and wait >= patience: the member stops after epoch k
+ * A stopped member runs no further step (its launches are still enqueued: the workgroups return at once, and there is no host
+ * synchronisation inside the fit); its train_loss_out / val_loss_out entries of the epochs it did not run are NaN.  At the
+ * end of the fit, with restore_best and best_epoch >= 0, the member's parameters become the snapshot; m, v, the running
+ * powers and the step count stay as they are (Keras restore_best_weights restores weights only); with best_epoch = -1 the
+ * current parameters stay.  Members monitor, stop and restore independently of each other.
+ *
+ * bbmpc_trainer_set_weight_decay: decay [n_layers], NULL = off.  BBMPC_E_INVALID, the settings then as they were: an
+ * unknown mode, a negative or non-finite decay.
+ * bbmpc_trainer_set_early_stopping: BBMPC_E_INVALID for patience < 0 or a negative or non-finite min_delta.
+ * bbmpc_trainer_get_fit_report: the last fit, each array [n_members]: epochs_run (epochs, or fewer for a stopped member),
+ * best_epoch (-1: none, or no monitoring) and best_val (NaN then).  Host values kept from the fit's one read at its end.
+ * BBMPC_E_STATE before any fit; BBMPC_E_INVALID for a NULL array. */
+#define BBMPC_TRAIN_DECAY_L2        0
+#define BBMPC_TRAIN_DECAY_DECOUPLED 1
+int bbmpc_trainer_set_weight_decay(bbmpc_trainer t, const float* decay, int32_t mode);
+int bbmpc_trainer_set_early_stopping(bbmpc_trainer t, int32_t patience, float min_delta, int32_t restore_best);
+int bbmpc_trainer_get_fit_report(bbmpc_trainer t, int32_t* epochs_run, int32_t* best_epoch, float* best_val);
+
 #ifdef __cplusplus
 }
 #endif
