@@ -206,6 +206,8 @@ Engine::Engine(const bbmpc_config& c) : cfg(c) {
             sw.fused_bound = atoi(fb);
             REQUIRE(sw.fused_bound == 512 || sw.fused_bound == 1024, BBMPC_E_INVALID, "BBMPC_FUSED_BOUND must be 512, 1024 or unset");
         }
+        sw.cem_wave_select = ival("BBMPC_CEM_WAVE_SELECT", 1) != 0 ? 1 : 0;
+        sw.trace_select_only = flag("BBMPC_TRACE_SELECT_ONLY");
         linger_test_quit = ival("BBMPC_LINGER_TEST_QUIT", 0) - 1;
         host_seq = (uint32_t)ival("BBMPC_TEST_HOST_SEQ", 0);      // test hook: where the completion sequence numbers start (the 16-bit tag's wrap)
         sw.balance = ival("BBMPC_BALANCE", 0);      // accepted and ignored: pacing SIMD mates in the fused pendulum rollout measured slower and is gone

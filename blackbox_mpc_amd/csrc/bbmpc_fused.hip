@@ -63,6 +63,7 @@ static void launch_fused4(Engine& e, FusedArgs& fa, int threads, size_t lds_base
     if constexpr (fused_has_bound512<OPT, INJ, ILP>()) {
         if (threads <= 512 && e.sw.fused_bound != 1024 && lds_base + lds_samples <= fused_lds_limit()) {
             REQUIRE(threads <= 512, BBMPC_E_HIP, "internal: a 512-bounded k_fused_pendulum launched with more threads");
+            fa.wave_select = (BBMPC_CEM_WAVE_SELECT && e.sw.cem_wave_select) ? 1 : 0;      // (the all-wave selection: topk.hpp)
             launch_fused5<OPT, FASTM, INJ, ILP, 512>(e, fa, threads, lds_base, lds_samples);
             return;
         }
@@ -217,6 +218,7 @@ void Engine::optimize_fused(const float* d_state_in, int add_noise, float* d_rec
     if (trace_on) {
         ensure_trace();
         fa.t_rewards = t_rewards.p; fa.t_mean = t_mean.p; fa.t_var = t_var.p; fa.t_elites = t_elites.p; fa.t_passes = t_passes.p; fa.t_samples = t_samples.p;
+        if (sw.trace_select_only) fa.t_elites = nullptr;      // test hook: the selection runs as it does untraced (BBMPC_TRACE_ELITES stays empty)
         if (cfg.optimizer == BBMPC_OPT_SPSA) {
             if (!t_rewards2.p) t_rewards2.alloc((size_t)A * Nst * std::max(iters, 1));
             fa.t_rewards2 = t_rewards2.p;

@@ -189,6 +189,10 @@ struct Engine {
         int linger_us = 200;              // BBMPC_LINGER_US: how long a one-agent control-step kernel waits for the next call (0 = never)
         int fused_bound = 0;              // BBMPC_FUSED_BOUND: 512 / 1024 = the launch bound of k_fused_pendulum where both forms exist (1024: the
                                           // 1024-thread form at every size), 0 = unset: 512 wherever the workgroup fits it
+        int cem_wave_select = 1;          // BBMPC_CEM_WAVE_SELECT=0: the 512-thread CEM control step keeps the selection with wave 0's scan and the
+                                          // shared elite list (csrc/topk.hpp) where the all-wave route would run; read when the handle is created
+        bool trace_select_only = false;   // BBMPC_TRACE_SELECT_ONLY: test hook, bbmpc_set_trace leaves the persistent pendulum kernel's sorted-elites
+                                          // trace out, so that its selection takes the route it takes untraced (BBMPC_TRACE_TOPK_PASSES bit 8)
         int balance = 0;               // BBMPC_BALANCE: parsed, ignored (the rollout's pacing of SIMD mates was taken out)
         int ilp = 1;                   // BBMPC_ILP
         bool refit_v1 = false;         // BBMPC_REFIT_V1

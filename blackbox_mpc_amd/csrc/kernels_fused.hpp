@@ -77,6 +77,7 @@ struct FusedArgs {
     const float* pf_buf[2];
     unsigned long long pf_step_floats, pf_chunk_floats;      // floats per control step / per chunk buffer (0 = no prediction)
     int* t_passes;           // trace, with t_elites: [iters][A] radix passes of the elite selection (last: no other field moves)
+    int wave_select;         // 512-thread CEM form: the selection may take the all-wave route (BBMPC_CEM_WAVE_SELECT=0 at handle creation: 0)
 };
 
 // (noise_block_index: the float4 index of particle n's first Philox block in the layout k_noise_fill writes,
@@ -114,6 +115,11 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid, int nw)
 // With H a multiple of four the rollout reads one float4 past mean[HUp] and past sigma[HUp] -- here: var[0..3] and
 // eidx[0..3] (kp >= 4) -- and never uses it.  Whoever reorders the carve keeps a piece behind both, or pads them by a block
 // (and Engine::optimize_fused's lds_base with them).
+// 1: the 512-thread CEM form selects on the all-wave route where it applies (topk.hpp, block_topk_wave_select); 0 compiles
+// today's route only.
+#ifndef BBMPC_CEM_WAVE_SELECT
+#define BBMPC_CEM_WAVE_SELECT 1
+#endif
 #ifndef BBMPC_FUSED_ACTIONS_AHEAD
 #define BBMPC_FUSED_ACTIONS_AHEAD 1
 #endif
@@ -144,6 +150,12 @@ __global__ __launch_bounds__(MAXT) void k_fused_pendulum(FusedArgs p) {
     // (only CEM selects: the other optimizers keep the narrow words, i.e. the carve they always had)
     unsigned long long* ekeys = (unsigned long long*)(hist + (OPT == FOPT_CEM ? TOPK_HIST_WORDS : TOPK_HIST_WORDS_NARROW));
     float* samp = SAMPLES_LDS ? (float*)(ekeys + kp) : (p.samples_g + (size_t)a * p.HU * p.Nst);
+    // the all-wave selection: the 512-thread CEM form only.  Its prepass keeps the per-wave (kmin, bound) slots in red[0..8)
+    // and red[32..40), which the CEM form uses for nothing else (red[16..31]: the request's words, red[60..62]: the state),
+    // and zeroes the second histogram itself (topk.hpp).
+    constexpr bool WAVE_SEL = BBMPC_CEM_WAVE_SELECT && OPT == FOPT_CEM && MAXT == 512 && SAMPLES_LDS;
+    [[maybe_unused]] uint32_t* const slot_min = (uint32_t*)red;
+    [[maybe_unused]] uint32_t* const slot_bound = (uint32_t*)red + 32;
 #ifdef BBMPC_KERNEL_DBG
     __shared__ long long dbg_lds[48];
 #endif
@@ -584,7 +596,8 @@ __global__ __launch_bounds__(MAXT) void k_fused_pendulum(FusedArgs p) {
             // the selection's first part reads only the rewards this thread has just written: in front of the barrier the
             // rollout needs anyway instead of behind it with a barrier of its own (topk.hpp)
             if (it + 1 < p.iters) prefetch_first(inj_s, it + 1);
-            if (OPT == FOPT_CEM) block_topk_prepass(rew, p.N, p.k, hist, tid, nthr);
+            if constexpr (WAVE_SEL) block_topk_prepass<true, true>(rew, p.N, p.k, hist, tid, nthr, slot_min, slot_bound);
+            else if (OPT == FOPT_CEM) block_topk_prepass(rew, p.N, p.k, hist, tid, nthr);
             BB_DBG(2 + it * 4);
             __syncthreads();
             BB_DBG(3 + it * 4);
@@ -603,14 +616,28 @@ __global__ __launch_bounds__(MAXT) void k_fused_pendulum(FusedArgs p) {
                 // The refit needs the elite SET only, so the winners are listed in ascending index order (no ranking);
                 // the sorted list tf.nn.top_k returns is produced only for the parity trace.  The statistics below always
                 // run over the index-ordered list, so results do not depend on tracing.
-                const TopkSel sel = block_topk_select(rew, p.N, p.k, hist, tid, nthr, true);
-                if (p.t_passes && tid == 0) p.t_passes[(size_t)it * p.A + a] = sel.passes;      // (null unless traced)
-                if (p.t_elites) {
-                    block_topk_finish_sorted(rew, p.N, p.k, eidx, hist, ekeys, sel, tid, nthr);
-                    for (int e = tid; e < p.k; e += nthr) p.t_elites[((size_t)it * p.A + a) * p.k + e] = eidx[e];
-                    __syncthreads();
+                TopkSel sel;
+                [[maybe_unused]] int route = TOPK_ROUTE_OLD;
+                if constexpr (WAVE_SEL) {
+                    // the common case only: one element per thread, k <= 64, tracing off; every other case, and every
+                    // selection the route declines, runs today's code (uniform for the workgroup either way)
+                    if (p.wave_select && p.t_elites == nullptr && p.N <= nthr && p.k <= 64)
+                        route = block_topk_wave_select(rew, p.N, p.k, eidx, hist, slot_min, slot_bound, tid, nthr, sel);
+                    else
+                        sel = block_topk_select(rew, p.N, p.k, hist, tid, nthr, true, slot_min, slot_bound);
+                } else {
+                    sel = block_topk_select(rew, p.N, p.k, hist, tid, nthr, true);
                 }
-                block_topk_finish_indexed(rew, p.N, p.k, eidx, hist, sel, tid, nthr);
+                // (null unless traced; bit 8: the all-wave route listed the winners)
+                if (p.t_passes && tid == 0) p.t_passes[(size_t)it * p.A + a] = sel.passes | (route != TOPK_ROUTE_OLD ? 0x100 : 0);
+                if (route == TOPK_ROUTE_OLD) {
+                    if (p.t_elites) {
+                        block_topk_finish_sorted(rew, p.N, p.k, eidx, hist, ekeys, sel, tid, nthr);
+                        for (int e = tid; e < p.k; e += nthr) p.t_elites[((size_t)it * p.A + a) * p.k + e] = eidx[e];
+                        __syncthreads();
+                    }
+                    block_topk_finish_indexed(rew, p.N, p.k, eidx, hist, sel, tid, nthr);
+                }
                 BB_DBG(4 + it * 4);
 #ifdef BBMPC_KERNEL_DBG
                 if (p.dbg && tid == 0 && a == 0 && it == 1) for (int i = 0; i < 12; ++i) p.dbg[48 + i] = g_topk_dbg[i];

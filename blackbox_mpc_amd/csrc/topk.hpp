@@ -42,7 +42,10 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
 
 // vals[N] in LDS (left untouched); eidx[k] out; hist[TOPK_HIST_WORDS] and ekeys[k] are LDS scratch.
 // All threads of the workgroup must call (k <= nthr); ends with a barrier (eidx visible to everyone).
-// Barrier budget: 1 (key range) + 2 per radix pass (usually 1 pass) + 1 (compaction) + 2 (ranking).
+// Barrier budget: 1 (key range) + 2 per radix pass (usually 1 pass) + 1 (compaction) + 2 (ranking); the index-ordered
+// finish: 1 per round of nthr elements + 1.  The 512-thread CEM control step in its common case (one element per thread,
+// k <= 64, a first pass that takes the whole boundary bucket in: block_topk_wave_select): 1 (key range) + 1 (histogram)
+// + 2 (the list) -- every wave scans for itself, the scan's barrier is gone (profiles/cem_wave_select.md).
 #ifdef BBMPC_KERNEL_DBG
 __shared__ long long g_topk_dbg[16];
 #define TOPK_DBG(i) do { if (tid == 0) g_topk_dbg[(i)] = (long long)wall_clock64(); } while (0)
@@ -64,8 +67,13 @@ struct TopkSel {
 // First part of the selection, up to (not including) its first barrier: every thread reads only the elements
 // n = tid, tid + nthr, ... -- a caller whose threads have just WRITTEN exactly those elements (the persistent kernel's
 // rollout) runs it in front of the barrier it needs anyway and then calls block_topk_select(..., prepass_done = true).
-template <bool WIDE = true>
-__device__ __forceinline__ void block_topk_prepass(const float* vals, int N, int k, uint32_t* hist, int tid, int nthr) {
+// SPLIT (the all-wave route, block_topk_wave_select): the per-wave slots go to smin[wave] / sbound[wave], words of the
+// caller's outside hist[], and the second histogram and the compaction cursor are zeroed HERE, half a word per thread
+// at 512 threads -- that route has no scan phase in which idle waves could zero them.  INVARIANT: with SPLIT nothing in
+// hist[] is read between this zeroing and the barrier behind it, and the slots, read behind that barrier, are not in it.
+template <bool WIDE = true, bool SPLIT = false>
+__device__ __forceinline__ void block_topk_prepass(const float* vals, int N, int k, uint32_t* hist, int tid, int nthr,
+                                                   uint32_t* smin = nullptr, uint32_t* sbound = nullptr) {
     const int lane = tid & 63, wave = tid >> 6;
     uint32_t* hist2 = hist + TOPK_HIST2_OFF;     // second histogram; its first 32 words carry the per-wave slots first
     // ---- key range: digits are taken from the top of span = B - min, B an UPPER BOUND of the k-th smallest key.
@@ -109,7 +117,14 @@ __device__ __forceinline__ void block_topk_prepass(const float* vals, int N, int
     }
     // per-wave slots instead of atomics; the min of wave w goes to hist2[w], the bound to hist2[16+w]: the first pass
     // does not use that array, and it is zeroed for the second one behind the barrier all slots are read in front of
-    if (lane == 0) { hist2[wave] = kmin; hist2[16 + wave] = kmax; }
+    if constexpr (SPLIT) {
+        if (lane == 0) { smin[wave] = kmin; sbound[wave] = kmax; }
+        uint2* hz2 = reinterpret_cast<uint2*>(hist2);
+        for (int i = tid; i < TOPK_BINSN / 2; i += nthr) hz2[i] = make_uint2(0u, 0u);
+        if (tid == 0) hist[TOPK_CTRL_OFF + 3] = 0u;
+    } else {
+        if (lane == 0) { hist2[wave] = kmin; hist2[16 + wave] = kmax; }
+    }
     // the first pass histograms into the first histogram's 1024 words: two words per thread at 512 threads
     uint2* hz = reinterpret_cast<uint2*>(hist + TOPK_HIST1_OFF);
     for (int i = tid; i < (WIDE ? TOPK_BINS1 : TOPK_BINSN) / 2; i += nthr) hz[i] = make_uint2(0u, 0u);
@@ -147,39 +162,20 @@ __device__ __forceinline__ void topk_scan_first(const uint32_t* h, uint32_t* ctr
     }
 }
 
-// Selection only: pins the boundary bucket of the k-th key.  Ends with a barrier; ctrl[3] (compaction cursor) is 0.
+// The radix passes of a selection from pass `pass` on, with `top` low bits of the k-th offset key undecided, T its decided
+// high bits, `remaining` keys still wanted from the bucket T names and eq_total keys in it.  block_topk_select enters at
+// pass 0; the all-wave route (block_topk_wave_select) has run the first pass itself and enters at pass 1 when that did not
+// take the whole boundary bucket in -- with the second histogram and ctrl[3] zeroed, as the idle waves of pass 0 leave them.
+// Ends with a barrier whenever it ran a pass or pass == 0; ctrl[3] (compaction cursor) is 0.
 template <bool WIDE = true>
-__device__ __forceinline__ TopkSel block_topk_select(const float* vals, int N, int k, uint32_t* hist, int tid, int nthr,
-                                                     bool prepass_done = false) {
-    const int lane = tid & 63, nw = nthr >> 6;
-    TOPK_DBG(0);
+__device__ __forceinline__ TopkSel topk_select_passes(const float* vals, int N, uint32_t* hist, int tid, int nthr, uint32_t kmin,
+                                                      uint32_t span, int top, uint32_t T, uint32_t remaining, uint32_t eq_total,
+                                                      int pass) {
+    const int lane = tid & 63;
     uint32_t* ctrl = hist + TOPK_CTRL_OFF;       // [0] bucket [1] wanted [2] bucket size [3] compaction cursor
-    uint32_t* hist2 = hist + TOPK_HIST2_OFF;     // second histogram; its first 32 words carry the per-wave slots first
-    uint32_t* hist1 = hist + TOPK_HIST1_OFF;     // first histogram: 1024 words (WIDE) or 256
+    uint32_t* hist2 = hist + TOPK_HIST2_OFF;
+    uint32_t* hist1 = hist + TOPK_HIST1_OFF;
     constexpr int W1 = WIDE ? TOPK_W1 : TOPK_WN;
-    if (!prepass_done) {
-        block_topk_prepass<WIDE>(vals, N, k, hist, tid, nthr);
-        __syncthreads();
-    }
-    uint32_t kmin, kmax;
-    TOPK_DBG(1);
-    // combine the (<= 16) per-wave slots with ONE LDS round trip: lane w fetches wave w's pair, then a 16-lane DPP
-    // reduction (a serial loop over the slots costs one LDS latency per wave)
-    kmin = 0xFFFFFFFFu; kmax = 0u;
-    if (lane < nw) { kmin = hist2[lane]; kmax = hist2[16 + lane]; }
-#define BB_ROW_U32(op, v, ctrl) v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, 0xf, 0xf, false))
-    BB_ROW_U32(min, kmin, 0xB1); BB_ROW_U32(min, kmin, 0x4E); BB_ROW_U32(min, kmin, 0x141); BB_ROW_U32(min, kmin, 0x140);
-    BB_ROW_U32(max, kmax, 0xB1); BB_ROW_U32(max, kmax, 0x4E); BB_ROW_U32(max, kmax, 0x141); BB_ROW_U32(max, kmax, 0x140);
-#undef BB_ROW_U32
-    kmin = (uint32_t)__builtin_amdgcn_readlane((int)kmin, 0);
-    kmax = (uint32_t)__builtin_amdgcn_readlane((int)kmax, 0);
-    const TopkRange rg = topk_range(kmin, kmax);
-    const uint32_t span = rg.span;
-    int top = rg.top;                             // number of low bits of the k-th OFFSET key still undecided
-    uint32_t T = 0u;                              // its decided high bits
-    uint32_t remaining = (uint32_t)k;
-    uint32_t eq_total = (uint32_t)N;              // span == 0: at least k keys equal the smallest
-    int pass = 0;
     // The first pass uses the 1024-bin histogram (zeroed before the barrier; the slots read above are in hist2), the
     // second hist2, later ones alternate between the first 256 words of hist1 and hist2; the array for pass p+1 is zeroed
     // by the idle waves while wave 0 scans pass p.
@@ -243,6 +239,36 @@ __device__ __forceinline__ TopkSel block_topk_select(const float* vals, int N, i
     return TopkSel{kmin, T, topk_winner_limit(span, T, top), remaining, eq_total, pass};
 }
 
+// Selection only: pins the boundary bucket of the k-th key.  Ends with a barrier; ctrl[3] (compaction cursor) is 0.
+template <bool WIDE = true>
+__device__ __forceinline__ TopkSel block_topk_select(const float* vals, int N, int k, uint32_t* hist, int tid, int nthr,
+                                                     bool prepass_done = false, const uint32_t* smin = nullptr,
+                                                     const uint32_t* sbound = nullptr) {      // (slots of a SPLIT prepass)
+    const int lane = tid & 63, nw = nthr >> 6;
+    TOPK_DBG(0);
+    uint32_t* hist2 = hist + TOPK_HIST2_OFF;     // second histogram; its first 32 words carry the per-wave slots first
+    if (!prepass_done) {
+        block_topk_prepass<WIDE>(vals, N, k, hist, tid, nthr);
+        __syncthreads();
+    }
+    uint32_t kmin, kmax;
+    TOPK_DBG(1);
+    // combine the (<= 16) per-wave slots with ONE LDS round trip: lane w fetches wave w's pair, then a 16-lane DPP
+    // reduction (a serial loop over the slots costs one LDS latency per wave)
+    kmin = 0xFFFFFFFFu; kmax = 0u;
+    if (lane < nw) { kmin = smin ? smin[lane] : hist2[lane]; kmax = sbound ? sbound[lane] : hist2[16 + lane]; }
+#define BB_ROW_U32(op, v, ctrl) v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, 0xf, 0xf, false))
+    BB_ROW_U32(min, kmin, 0xB1); BB_ROW_U32(min, kmin, 0x4E); BB_ROW_U32(min, kmin, 0x141); BB_ROW_U32(min, kmin, 0x140);
+    BB_ROW_U32(max, kmax, 0xB1); BB_ROW_U32(max, kmax, 0x4E); BB_ROW_U32(max, kmax, 0x141); BB_ROW_U32(max, kmax, 0x140);
+#undef BB_ROW_U32
+    kmin = (uint32_t)__builtin_amdgcn_readlane((int)kmin, 0);
+    kmax = (uint32_t)__builtin_amdgcn_readlane((int)kmax, 0);
+    const TopkRange rg = topk_range(kmin, kmax);
+    // top: the number of low bits of the k-th OFFSET key still undecided; T = 0: its decided high bits;
+    // eq_total = N: span == 0 means at least k keys equal the smallest
+    return topk_select_passes<WIDE>(vals, N, hist, tid, nthr, kmin, rg.span, rg.top, 0u, (uint32_t)k, (uint32_t)N, 0);
+}
+
 // Winner test for element n given the selection (exact ties at the boundary: lowest indices win)
 __device__ __forceinline__ bool topk_is_winner(const float* vals, int n, const TopkSel& s) {
     const uint32_t kp = topk_offset_key(vals[n], s.kmin);
@@ -271,6 +297,7 @@ __device__ __forceinline__ void block_topk_finish_indexed(const float* vals, int
         uint32_t* wt = wtot + (round & 1) * 16;
         if (lane == 0) wt[wave] = (uint32_t)__popcll(bal);
         __syncthreads();
+        TOPK_DBG(8);      // (slots 8 / 9 are a fourth pass's too; the clocked runs never take one)
         // lane w fetches wave w's total (one LDS round trip), 16-lane DPP prefix scan, results through readlane
         int x = (lane < nw) ? (int)wt[lane] : 0;
         x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1
@@ -284,6 +311,98 @@ __device__ __forceinline__ void block_topk_finish_indexed(const float* vals, int
         base += tot;
     }
     __syncthreads();
+    TOPK_DBG(9);
+}
+
+// ---- The all-wave route of the 512-thread CEM control step (kernels_fused.hpp): behind the histogram's barrier EVERY
+// wave scans the first histogram -- what wave 0 handed the others across the scan's barrier (ctrl[]) is a pure function
+// of the first histogram, which every wave sees behind the histogram's barrier -- and, when the first pass took the whole
+// boundary bucket in, tests the offset key it kept in a register and lists the winners as block_topk_finish_indexed does.
+// Barrier budget of that case: 1 (key range; the caller's) + 1 (histogram) + 2 (the list).
+// Needs: one element per thread (N <= nthr <= 512), k <= 64, block_topk_prepass<true, true> done and its barrier passed.
+// Every case it declines -- span == 0, a first pass that leaves ties or a second pass to do -- runs today's code from
+// where it is detected; every wave computes the same scan, so the decision is uniform without communication.
+// Returns TOPK_ROUTE_OLD: `sel` is filled as block_topk_select fills it, the caller finishes (block_topk_finish_indexed);
+//         TOPK_ROUTE_LIST: eidx[0..k) written in ascending index order, closing barrier passed.
+// (Every wave listing all winners into a copy of its own, with no barrier up to the statistics, was built and measured
+// 1.6 us per control step SLOWER than this: profiles/cem_wave_select.md.)
+constexpr int TOPK_ROUTE_OLD = 0, TOPK_ROUTE_LIST = 1;
+
+struct TopkWavePick {
+    uint32_t bucket, wanted, cnt;
+};
+// topk_scan_first in every wave: the same reads and arithmetic, the pick broadcast from the one lane that holds it
+__device__ __forceinline__ TopkWavePick topk_scan_first_all(const uint32_t* h, uint32_t remaining, int lane) {
+    const uint4* hv = reinterpret_cast<const uint4*>(h);
+    const uint4 c0 = hv[lane], c1 = hv[64 + lane], c2 = hv[128 + lane], c3 = hv[192 + lane];
+    const uint32_t s0 = c0.x + c0.y + c0.z + c0.w, s1 = c1.x + c1.y + c1.z + c1.w;
+    const uint32_t s2 = c2.x + c2.y + c2.z + c2.w, s3 = c3.x + c3.y + c3.z + c3.w;
+    const uint32_t s = (s0 + s1) + (s2 + s3);
+    const uint32_t incl = wave_incl_scan(s, lane);
+    const uint32_t excl = incl - s;
+    const TopkPick pk = topk_pick16(TopkQuad{c0.x, c0.y, c0.z, c0.w}, TopkQuad{c1.x, c1.y, c1.z, c1.w}, TopkQuad{c2.x, c2.y, c2.z, c2.w},
+                                    TopkQuad{c3.x, c3.y, c3.z, c3.w}, excl, remaining);
+    const unsigned long long holder = __ballot(excl < remaining && remaining <= incl);      // exactly one lane
+    const int src = holder ? __builtin_ctzll(holder) : 0;
+    TopkWavePick r;
+    r.bucket = 16u * (uint32_t)src + (uint32_t)__builtin_amdgcn_readlane((int)pk.sub, src);
+    r.wanted = (uint32_t)__builtin_amdgcn_readlane((int)pk.wanted, src);
+    r.cnt = (uint32_t)__builtin_amdgcn_readlane((int)pk.cnt, src);
+    return r;
+}
+
+__device__ __forceinline__ int block_topk_wave_select(const float* vals, int N, int k, int* eidx, uint32_t* hist, const uint32_t* smin,
+                                                      const uint32_t* sbound, int tid, int nthr, TopkSel& sel) {
+    const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
+    uint32_t* hist1 = hist + TOPK_HIST1_OFF;
+    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
+    if (lane < nw) { kmin = smin[lane]; kmax = sbound[lane]; }
+#define BB_ROW_U32(op, v, ctrl) v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, 0xf, 0xf, false))
+    BB_ROW_U32(min, kmin, 0xB1); BB_ROW_U32(min, kmin, 0x4E); BB_ROW_U32(min, kmin, 0x141); BB_ROW_U32(min, kmin, 0x140);
+    BB_ROW_U32(max, kmax, 0xB1); BB_ROW_U32(max, kmax, 0x4E); BB_ROW_U32(max, kmax, 0x141); BB_ROW_U32(max, kmax, 0x140);
+#undef BB_ROW_U32
+    kmin = (uint32_t)__builtin_amdgcn_readlane((int)kmin, 0);
+    kmax = (uint32_t)__builtin_amdgcn_readlane((int)kmax, 0);
+    const TopkRange rg = topk_range(kmin, kmax);
+    const uint32_t span = rg.span;
+    if (rg.top == 0) {                           // min == bound: the exact tie path, today's code (no pass runs)
+        sel = topk_select_passes<true>(vals, N, hist, tid, nthr, kmin, span, 0, 0u, (uint32_t)k, (uint32_t)N, 0);
+        return TOPK_ROUTE_OLD;
+    }
+    // ---- the first pass's histogram; the thread keeps its offset key for the winner test
+    const int shift = topk_pass_shift(0, rg.top, TOPK_W1);
+    uint32_t kp = 0xFFFFFFFFu;
+    if (tid < N) {
+        kp = topk_offset_key(vals[tid], kmin);
+        if (topk_takes_part(kp, span, 0u, rg.top)) atomicAdd(&hist1[topk_first_slot(topk_digit(kp, 0, rg.top, TOPK_W1))], 1u);
+    }
+    __syncthreads();
+    TOPK_DBG(2);
+    const TopkWavePick pk = topk_scan_first_all(hist1, (uint32_t)k, lane);
+    const uint32_t T = pk.bucket << shift;
+    if (!topk_whole_bucket_in(pk.wanted, pk.cnt)) {      // ties at the boundary or a second pass: today's loop from pass 1
+        sel = topk_select_passes<true>(vals, N, hist, tid, nthr, kmin, span, shift, T, pk.wanted, pk.cnt, 1);
+        return TOPK_ROUTE_OLD;
+    }
+    const uint32_t lim = topk_winner_limit(span, T, shift);
+    sel = TopkSel{kmin, T, lim, pk.wanted, pk.cnt, 1};
+    // block_topk_finish_indexed's one round (N <= nthr) on the key the thread holds
+    uint32_t* wt = hist;                                     // [16] wave totals (hist2's first words, as there)
+    const bool take = tid < N && kp <= lim;
+    const unsigned long long bal = __ballot(take);
+    const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (lane == 0) wt[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    TOPK_DBG(3);
+    int x = (lane < nw) ? (int)wt[lane] : 0;
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);   // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);   // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);   // row_shr:8
+    const uint32_t incl_w = (uint32_t)__builtin_amdgcn_readlane(x, __builtin_amdgcn_readfirstlane(wave));
+    if (take) eidx[incl_w - (uint32_t)__popcll(bal) + pre] = tid;
+    __syncthreads();
+    return TOPK_ROUTE_LIST;
 }
 
 // Finish B: the k winners sorted (tf.nn.top_k(sorted=True)): atomic compaction + k x k ranking.

@@ -106,4 +106,38 @@ BBMPC_TOPK_HD uint32_t topk_winner_limit(uint32_t span, uint32_t T, int top) {
     return hi < span ? hi : span;
 }
 
+// ---- the arithmetic of the all-wave route (topk.hpp, block_topk_wave_select): every wave scans the first histogram.
+// Host-compilable like everything above (tests/topk_wave_list_check.cpp).
+struct TopkQuad {
+    uint32_t x, y, z, w;
+};
+struct TopkPick {
+    uint32_t sub;      // which of the lane's 16 consecutive bins holds the k-th key: 4 q + e
+    uint32_t wanted;   // how many keys of that bin are still wanted
+    uint32_t cnt;      // how many keys it holds
+};
+// The lane whose 16 bins (four quads c0..c3, `excl` keys in front of them) hold the `remaining`-th key picks the bin with
+// a two-level compare and select, operation for operation what topk_scan_first does in wave 0.
+BBMPC_TOPK_HD TopkPick topk_pick16(TopkQuad c0, TopkQuad c1, TopkQuad c2, TopkQuad c3, uint32_t excl, uint32_t remaining) {
+    const uint32_t s0 = c0.x + c0.y + c0.z + c0.w, s1 = c1.x + c1.y + c1.z + c1.w, s2 = c2.x + c2.y + c2.z + c2.w;
+    const uint32_t p1 = excl + s0, p2 = p1 + s1, p3 = p2 + s2;          // keys in front of quads 1, 2, 3
+    const bool g1 = remaining > p1, g2 = remaining > p2, g3 = remaining > p3;
+    const uint32_t q = (uint32_t)g1 + (uint32_t)g2 + (uint32_t)g3;
+    const uint32_t pq = g3 ? p3 : (g2 ? p2 : (g1 ? p1 : excl));
+    const uint32_t x = g3 ? c3.x : (g2 ? c2.x : (g1 ? c1.x : c0.x));
+    const uint32_t y = g3 ? c3.y : (g2 ? c2.y : (g1 ? c1.y : c0.y));
+    const uint32_t z = g3 ? c3.z : (g2 ? c2.z : (g1 ? c1.z : c0.z));
+    const uint32_t w = g3 ? c3.w : (g2 ? c2.w : (g1 ? c1.w : c0.w));
+    const uint32_t e1 = pq + x, e2 = e1 + y, e3 = e2 + z;               // keys in front of elements 1, 2, 3
+    const bool h1 = remaining > e1, h2 = remaining > e2, h3 = remaining > e3;
+    const uint32_t e = (uint32_t)h1 + (uint32_t)h2 + (uint32_t)h3;
+    const uint32_t cum = h3 ? e3 : (h2 ? e2 : (h1 ? e1 : pq));
+    const uint32_t cnt = h3 ? w : (h2 ? z : (h1 ? y : x));
+    return TopkPick{4u * q + e, remaining - cum, cnt};
+}
+
+// The all-wave route goes on only when the first pass took the whole boundary bucket in: every key of it is a winner, no
+// tie has to be counted and the undecided low bits do not matter (topk_winner_limit covers them).
+BBMPC_TOPK_HD bool topk_whole_bucket_in(uint32_t wanted, uint32_t cnt) { return wanted == cnt; }
+
 }  // namespace bbmpc

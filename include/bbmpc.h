@@ -115,7 +115,11 @@ extern "C" {
                                      * workgroup factorises, falls back and finishes in one kernel) records nothing: all zero. */
 #define BBMPC_TRACE_CMA_D   8   /* CMA-ES [G,n]   diag(D) = sqrt(eigenvalues) after the iteration (:197,205)   */
 #define BBMPC_TRACE_TOPK_PASSES 10 /* CEM int32 [A]: radix passes the iteration's elite selection took (csrc/topk.hpp); the persistent pendulum
-                                     * kernel and the per-iteration refit kernels record it, every other path leaves 0 */
+                                     * kernel and the per-iteration refit kernels record it, every other path leaves 0.  Bit 8
+                                     * (0x100) is set when the persistent kernel's all-wave route listed the winners; that
+                                     * route never runs while the sorted elites are traced, so the bit shows only under the
+                                     * test hook BBMPC_TRACE_SELECT_ONLY=1 (read when the handle is created), which leaves
+                                     * BBMPC_TRACE_ELITES of that kernel empty */
 
 typedef struct bbmpc_handle_s* bbmpc_handle;
 
