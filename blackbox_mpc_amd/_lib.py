@@ -110,6 +110,7 @@ SYMBOLS = [
     "bbmpc_trainer_create_ensemble", "bbmpc_trainer_set_member_rows", "bbmpc_trainer_fit_ensemble",
     "bbmpc_trainer_get_member_params", "bbmpc_trainer_residual_rms_ensemble",
     "bbmpc_trainer_set_weight_decay", "bbmpc_trainer_set_early_stopping", "bbmpc_trainer_get_fit_report",
+    "bbmpc_trainer_create_gaussian", "bbmpc_trainer_get_logvar_head", "bbmpc_trainer_lds_bytes_gaussian",
 ]
 COMM_ID_BYTES = 128
 # bbmpc_rows_callback (include/bbmpc.h): user, d_cur, d_actions, d_next, batch, d_out, hip_stream -> status
@@ -249,6 +250,11 @@ def _load():
     lib.bbmpc_trainer_set_weight_decay.argtypes = [vp, vp, i32]
     lib.bbmpc_trainer_set_early_stopping.argtypes = [vp, i32, ctypes.c_float, i32]
     lib.bbmpc_trainer_get_fit_report.argtypes = [vp, vp, vp, vp]
+    lib.bbmpc_trainer_create_gaussian.argtypes = [ctypes.POINTER(vp), i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                                  ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp,
+                                                  i32, ctypes.c_float]
+    lib.bbmpc_trainer_get_logvar_head.argtypes = [vp, i32, vp, vp]
+    lib.bbmpc_trainer_lds_bytes_gaussian.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64)]
     return lib
 
 

@@ -1,7 +1,8 @@
 // Training a Dense stack through the C ABI (bbmpc_trainer_*): the host side of kernels_train.hpp.
 // A trainer is independent of the planning handle: its own device, stream and buffers, no bbmpc_config.  It holds E >= 1
 // equally shaped members (bbmpc_trainer_create: one; bbmpc_trainer_create_ensemble: up to 8) that step side by side, the
-// member index being the kernels' second grid dimension.
+// member index being the kernels' second grid dimension.  bbmpc_trainer_create_gaussian: members with a log-variance head,
+// fitted on the Gaussian NLL by the kernels' NLL instantiations.
 #define BBMPC_TU_TRAIN
 #include <cmath>
 #include <limits>
@@ -37,6 +38,28 @@ static void train_describe(TrainNet& n, int32_t n_layers, const int32_t* dims, c
                 " bytes of LDS, over the 159 KiB limit");
 }
 
+// train_describe for a network with a log-variance head (bbmpc_trainer_create_gaussian): W_v and b_v
+// close theta, the head's z joins the carve, and the 159 KiB limit is checked on that carve -- before anything is allocated.
+static void train_describe_head(TrainNet& n, TrainHead& h) {
+    memset(&h, 0, sizeof(h));
+    const int hidden = n.dims[n.L - 1], O = n.dims[n.L];
+    h.woff = n.n_params;
+    h.boff = h.woff + hidden * O;
+    n.n_params = h.boff + O;
+    train_lds_layout_head(n, h);
+    REQUIRE((size_t)n.lds_floats * 4 <= (size_t)TR_LDS_LIMIT, BBMPC_E_UNSUPPORTED,
+            "trainer: the network's resident layer tiles and the log-variance head need " + std::to_string((size_t)n.lds_floats * 4) +
+                " bytes of LDS, over the 159 KiB limit");
+}
+
+// The bounds rule of bbmpc_set_mlp_logvar_head.
+static void train_check_logvar_bounds(const float* lo, const float* hi, int O) {
+    REQUIRE(lo && hi, BBMPC_E_INVALID, "trainer: null min_logvar / max_logvar");
+    for (int o = 0; o < O; ++o)
+        REQUIRE(std::isfinite(lo[o]) && std::isfinite(hi[o]) && std::fabs(lo[o]) <= 40.0f && std::fabs(hi[o]) <= 40.0f && lo[o] <= hi[o],
+                BBMPC_E_INVALID, "trainer: min_logvar / max_logvar must be finite, within [-40, 40], with min_logvar <= max_logvar");
+}
+
 // The seed member e draws its permutations from when bbmpc_trainer_fit_ensemble is given none (member 0: the seed itself).
 static inline uint64_t train_member_seed(uint64_t seed, int e) { return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)e); }
 
@@ -45,6 +68,9 @@ struct Trainer {
     int E = 1;                                   // members
     hipStream_t stream = nullptr;
     TrainNet net;                                // wf / wr / bp: member 0's; member e's lie e * net.pstride floats further
+    bool gauss = false;                          // a log-variance head: the NLL instantiations of the kernels
+    TrainHead head;                              // all zero without one
+    DevBuf<float> lvb;                           // [2][O]: min_logvar, max_logvar
     int rule = TR_RULE_ADAM;
     double lr = 1e-3;
     DevBuf<float> theta, m, v;                   // [E][n_params]
@@ -69,19 +95,26 @@ struct Trainer {
     std::vector<int32_t> rep_epochs, rep_best_epoch;      // the last fit's report, [E]
     std::vector<float> rep_best_val;
 
-    // weights / biases: [E * L] host arrays, member major
-    Trainer(const TrainNet& n, int dev, int members, const float* const* weights, const float* const* biases, int rule_, double lr_)
-        : device(dev), E(members), net(n), rule(rule_), lr(lr_) {
+    // weights / biases: [E * L] host arrays, member major.  hd (train_describe_head's, or null): the head, with head_w /
+    // head_b [E] host arrays and the bounds lo / hi [O].
+    Trainer(const TrainNet& n, int dev, int members, const float* const* weights, const float* const* biases, int rule_, double lr_,
+            const TrainHead* hd = nullptr, const float* const* head_w = nullptr, const float* const* head_b = nullptr,
+            const float* lo = nullptr, const float* hi = nullptr)
+        : device(dev), E(members), net(n), gauss(hd != nullptr), rule(rule_), lr(lr_) {
+        memset(&head, 0, sizeof(head));
+        if (hd) head = *hd;
         HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         const int L = net.L;
         const size_t np = (size_t)net.n_params;
-        // one slab of operand packs per member: [wf_0 wr_0 bp_0 .. wf_{L-1} wr_{L-1} bp_{L-1}], every piece a multiple of 16 floats
-        size_t off_f[TR_MAX_LAYERS], off_r[TR_MAX_LAYERS], off_b[TR_MAX_LAYERS], slab = 0;
-        for (int l = 0; l < L; ++l) {
-            const size_t pack = (size_t)net.tiles[l] * net.tiles[l + 1] * 256;
+        // one slab of operand packs per member: [wf_0 wr_0 bp_0 .. wf_{L-1} wr_{L-1} bp_{L-1}] and then the head's [wf_v wr_v
+        // bp_v], every piece a multiple of 16 floats
+        size_t off_f[TR_MAX_LAYERS + 1], off_r[TR_MAX_LAYERS + 1], off_b[TR_MAX_LAYERS + 1], slab = 0;
+        for (int l = 0; l < L + (gauss ? 1 : 0); ++l) {
+            const int ll = l < L ? l : L - 1;    // the head has the last layer's shape
+            const size_t pack = (size_t)net.tiles[ll] * net.tiles[ll + 1] * 256;
             off_f[l] = slab; slab += pack;
             off_r[l] = slab; slab += pack;
-            off_b[l] = slab; slab += (size_t)net.tiles[l + 1] * 16;
+            off_b[l] = slab; slab += (size_t)net.tiles[ll + 1] * 16;
         }
         net.pstride = (int)slab;
         std::vector<float> h(np * E), s(slab * E, 0.0f);
@@ -101,6 +134,19 @@ struct Trainer {
                     }
                 memcpy(s.data() + e * slab + off_b[l], b, sizeof(float) * out);
             }
+        for (int e = 0; e < E && gauss; ++e) {
+            const int in = net.dims[L - 1], out = net.dims[L], IT = net.tiles[L - 1], OT = net.tiles[L];
+            memcpy(h.data() + e * np + head.woff, head_w[e], sizeof(float) * in * out);
+            memcpy(h.data() + e * np + head.boff, head_b[e], sizeof(float) * out);
+            float* f = s.data() + e * slab + off_f[L];
+            float* r = s.data() + e * slab + off_r[L];
+            for (int i = 0; i < in; ++i)
+                for (int o = 0; o < out; ++o) {
+                    f[train_wf_index(IT, i, o)] = head_w[e][(size_t)i * out + o];
+                    r[train_wr_index(OT, i, o)] = head_w[e][(size_t)i * out + o];
+                }
+            memcpy(s.data() + e * slab + off_b[L], head_b[e], sizeof(float) * out);
+        }
         theta.alloc(h.size());
         m.alloc(h.size());
         v.alloc(h.size());
@@ -117,10 +163,29 @@ struct Trainer {
             net.wr[l] = packs.p + off_r[l];
             net.bp[l] = packs.p + off_b[l];
         }
+        if (gauss) {
+            const int O = net.dims[L];
+            std::vector<float> b(lo, lo + O);
+            b.insert(b.end(), hi, hi + O);
+            lvb.alloc(b.size());
+            HIP_CHECK(hipMemcpy(lvb.p, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
+            head.wf = packs.p + off_f[L];
+            head.wr = packs.p + off_r[L];
+            head.bp = packs.p + off_b[L];
+            head.min_lv = lvb.p;
+            head.max_lv = lvb.p + O;
+        }
         const int bytes = net.lds_floats * 4;
         if (bytes > 64 * 1024) {
-            for (const void* f : {reinterpret_cast<const void*>(k_train_fwd_bwd<false>), reinterpret_cast<const void*>(k_train_fwd_bwd<true>),
-                                  reinterpret_cast<const void*>(k_train_forward_mse<false>), reinterpret_cast<const void*>(k_train_forward_mse<true>)})
+            for (const void* f : {reinterpret_cast<const void*>(k_train_fwd_bwd<false, false>), reinterpret_cast<const void*>(k_train_fwd_bwd<true, false>),
+                                  reinterpret_cast<const void*>(k_train_forward_mse<false, false>),
+                                  reinterpret_cast<const void*>(k_train_forward_mse<true, false>)})
+                HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        }
+        if (bytes > 64 * 1024 && gauss) {        // besides: residual_rms is the mean network's, through the head-less forward
+            for (const void* f : {reinterpret_cast<const void*>(k_train_fwd_bwd<false, true>), reinterpret_cast<const void*>(k_train_fwd_bwd<true, true>),
+                                  reinterpret_cast<const void*>(k_train_forward_mse<false, true>),
+                                  reinterpret_cast<const void*>(k_train_forward_mse<true, true>)})
                 HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         }
     }
@@ -183,9 +248,15 @@ struct Trainer {
         q.part = part.p;
         q.lossp = lossp.p;
         q.stop = stop;
+        q.h = head;
         const int tiles = (B + TR_ROWS - 1) / TR_ROWS;
-        if (stop) hipLaunchKernelGGL((k_train_fwd_bwd<true>), dim3(tiles, E), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
-        else hipLaunchKernelGGL((k_train_fwd_bwd<false>), dim3(tiles, E), dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        const dim3 grid(tiles, E), block(net.nw * 64);
+        const size_t lds = (size_t)net.lds_floats * 4;
+        if (gauss) {
+            if (stop) hipLaunchKernelGGL((k_train_fwd_bwd<true, true>), grid, block, lds, stream, q);
+            else hipLaunchKernelGGL((k_train_fwd_bwd<false, true>), grid, block, lds, stream, q);
+        } else if (stop) hipLaunchKernelGGL((k_train_fwd_bwd<true, false>), grid, block, lds, stream, q);
+        else hipLaunchKernelGGL((k_train_fwd_bwd<false, false>), grid, block, lds, stream, q);
         HIP_CHECK(hipGetLastError());
     }
 
@@ -227,8 +298,13 @@ struct Trainer {
         }
         u.wd_mode = wd_mode;
         u.stop = stop;
-        if (stop || u.wd_on) hipLaunchKernelGGL((k_train_update<true>), dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, u);
-        else hipLaunchKernelGGL((k_train_update<false>), dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, u);
+        u.h = head;
+        const dim3 grid((net.n_params + 255) / 256, E);
+        if (gauss) {
+            if (stop || u.wd_on) hipLaunchKernelGGL((k_train_update<true, true>), grid, dim3(256), 0, stream, u);
+            else hipLaunchKernelGGL((k_train_update<false, true>), grid, dim3(256), 0, stream, u);
+        } else if (stop || u.wd_on) hipLaunchKernelGGL((k_train_update<true, false>), grid, dim3(256), 0, stream, u);
+        else hipLaunchKernelGGL((k_train_update<false, false>), grid, dim3(256), 0, stream, u);
         HIP_CHECK(hipGetLastError());
         if (rule_ != TR_RULE_NONE) ++steps;
     }
@@ -240,7 +316,9 @@ struct Trainer {
     }
 
     // every member forward on the same rows: tile_loss [E][batches * tiles], colsq_out [E][batches * tiles][O]
-    void launch_mse(const float* in, const float* out, int batches, int B, float* tile_loss, float* colsq_out, const TrainMon* stop = nullptr) {
+    // nll: the Gaussian form (per tile the sum of wsq + lv); false on a Gaussian trainer: the mean network's squared errors
+    void launch_mse(const float* in, const float* out, int batches, int B, float* tile_loss, float* colsq_out, const TrainMon* stop = nullptr,
+                    bool nll = false) {
         TrainMseArgs q;
         q.n = net;
         q.din = in;
@@ -250,9 +328,14 @@ struct Trainer {
         q.tile_loss = tile_loss;
         q.colsq = colsq_out;
         q.stop = stop;
-        const dim3 grid((unsigned)((size_t)batches * q.tiles_per_batch), E);
-        if (stop) hipLaunchKernelGGL((k_train_forward_mse<true>), grid, dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
-        else hipLaunchKernelGGL((k_train_forward_mse<false>), grid, dim3(net.nw * 64), (size_t)net.lds_floats * 4, stream, q);
+        q.h = head;
+        const dim3 grid((unsigned)((size_t)batches * q.tiles_per_batch), E), block(net.nw * 64);
+        const size_t lds = (size_t)net.lds_floats * 4;
+        if (nll) {
+            if (stop) hipLaunchKernelGGL((k_train_forward_mse<true, true>), grid, block, lds, stream, q);
+            else hipLaunchKernelGGL((k_train_forward_mse<false, true>), grid, block, lds, stream, q);
+        } else if (stop) hipLaunchKernelGGL((k_train_forward_mse<true, false>), grid, block, lds, stream, q);
+        else hipLaunchKernelGGL((k_train_forward_mse<false, false>), grid, block, lds, stream, q);
         HIP_CHECK(hipGetLastError());
     }
 
@@ -320,7 +403,7 @@ struct Trainer {
                 launch_update(rule, B, loss_acc.p + k, epochs, nullptr, stop);
             }
             if (nvb > 0) {
-                launch_mse(vin.p, vout.p, nvb, B, val_tiles.p, nullptr, stop);
+                launch_mse(vin.p, vout.p, nvb, B, val_tiles.p, nullptr, stop, gauss);
                 hipLaunchKernelGGL(k_train_val_reduce, dim3(1, E), dim3(256), 0, stream, (const float*)val_tiles.p, nvb, tpb,
                                    (float)(1.0 / ((double)B * net.dims[net.L])), val_batch.p, val_loss.p + k, epochs, stop);
                 HIP_CHECK(hipGetLastError());
@@ -333,8 +416,10 @@ struct Trainer {
             }
         }
         if (restore_best) {
-            hipLaunchKernelGGL(k_train_restore, dim3((net.n_params + 255) / 256, E), dim3(256), 0, stream, net,
-                               (const TrainMon*)mon.p + (epochs & 1), (const float*)best_theta.p, theta.p);
+            const dim3 grid((net.n_params + 255) / 256, E);
+            const TrainMon* last = mon.p + (epochs & 1);
+            if (gauss) hipLaunchKernelGGL(k_train_restore<true>, grid, dim3(256), 0, stream, net, last, (const float*)best_theta.p, theta.p, head);
+            else hipLaunchKernelGGL(k_train_restore<false>, grid, dim3(256), 0, stream, net, last, (const float*)best_theta.p, theta.p, head);
             HIP_CHECK(hipGetLastError());
         }
         std::vector<float> tl(nl), vl(nl);
@@ -411,6 +496,15 @@ struct Trainer {
         }
     }
 
+    void get_logvar_head(int member, float* w_out, float* b_out) {
+        const size_t count = (size_t)net.n_params - head.woff;     // W_v, then b_v
+        std::vector<float> h(count);
+        HIP_CHECK(hipMemcpyAsync(h.data(), theta.p + (size_t)member * net.n_params + head.woff, count * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        memcpy(w_out, h.data(), sizeof(float) * (head.boff - head.woff));
+        memcpy(b_out, h.data() + (head.boff - head.woff), sizeof(float) * net.dims[net.L]);
+    }
+
     // rms_out [E][O]: every member on the same n rows, uploaded once
     void residual_rms(const float* in, const float* out, int n, float* rms_out) {
         REQUIRE(n >= 1, BBMPC_E_INVALID, "trainer: residual_rms needs at least one row");
@@ -442,17 +536,27 @@ struct bbmpc_trainer_s {
     DeviceGuard _device_guard((h)->t->device)
 
 // what bbmpc_trainer_create and bbmpc_trainer_create_ensemble share; every refusal comes before a device is touched
+// gaussian: with a log-variance head (head_weights / head_biases [n_members], the bounds [dims[n_layers]])
 static void trainer_create(bbmpc_trainer* out, int32_t device, int32_t n_members, int32_t n_layers, const int32_t* dims,
                            const int32_t* activations, const float* const* weights, const float* const* biases, int32_t rule,
-                           float learning_rate) {
+                           float learning_rate, bool gaussian = false, const float* const* head_weights = nullptr,
+                           const float* const* head_biases = nullptr, const float* min_logvar = nullptr, const float* max_logvar = nullptr) {
     REQUIRE(out, BBMPC_E_INVALID, "trainer: null output handle");
     *out = nullptr;
     REQUIRE(n_members >= 1 && n_members <= bbmpc::TR_MAX_MEMBERS, BBMPC_E_UNSUPPORTED,
             "trainer: n_members must lie in [1, 8] (BBMPC_MAX_ENSEMBLE_MEMBERS)");
     TrainNet n;
+    bbmpc::TrainHead head;
     bbmpc::train_describe(n, n_layers, dims, activations);
+    if (gaussian) bbmpc::train_describe_head(n, head);
     REQUIRE(weights && biases, BBMPC_E_INVALID, "trainer: null weights / biases");
     for (int i = 0; i < n_members * n_layers; ++i) REQUIRE(weights[i] && biases[i], BBMPC_E_INVALID, "trainer: a null weight or bias array");
+    if (gaussian) {
+        REQUIRE(head_weights && head_biases, BBMPC_E_INVALID, "trainer: null head_weights / head_biases");
+        for (int e = 0; e < n_members; ++e)
+            REQUIRE(head_weights[e] && head_biases[e], BBMPC_E_INVALID, "trainer: a null log-variance head kernel or bias array");
+        bbmpc::train_check_logvar_bounds(min_logvar, max_logvar, n.dims[n.L]);
+    }
     REQUIRE(rule == BBMPC_TRAIN_ADAM || rule == BBMPC_TRAIN_SGD || rule == BBMPC_TRAIN_RMSPROP, BBMPC_E_INVALID, "trainer: unknown update rule");
     REQUIRE(std::isfinite(learning_rate) && learning_rate > 0.0f, BBMPC_E_INVALID, "trainer: learning_rate must be finite and positive");
     int ndev = 0;
@@ -462,16 +566,13 @@ static void trainer_create(bbmpc_trainer* out, int32_t device, int32_t n_members
     int dev = device;
     if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
     DeviceGuard guard(dev);
-    Trainer* t = new Trainer(n, dev, n_members, weights, biases, rule, (double)learning_rate);
+    Trainer* t = new Trainer(n, dev, n_members, weights, biases, rule, (double)learning_rate, gaussian ? &head : nullptr, head_weights,
+                             head_biases, min_logvar, max_logvar);
     *out = new bbmpc_trainer_s{t};
 }
 
-extern "C" {
-
-int bbmpc_trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t* activations, int64_t* bytes) {
-    API_BEGIN
-    CHECK_PTR(bytes);
-    *bytes = 0;
+// what bbmpc_trainer_lds_bytes and bbmpc_trainer_lds_bytes_gaussian share
+static int64_t trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t* activations, bool gaussian) {
     REQUIRE(n_layers >= 1 && n_layers <= bbmpc::TR_MAX_LAYERS && dims && activations, BBMPC_E_INVALID, "trainer: n_layers outside [1, 8] or null arrays");
     TrainNet n;
     memset(&n, 0, sizeof(n));
@@ -482,7 +583,48 @@ int bbmpc_trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t
     }
     for (int l = 0; l < n_layers; ++l) n.act[l] = activations[l];
     bbmpc::train_lds_layout(n);
-    *bytes = (int64_t)n.lds_floats * 4;
+    if (gaussian) {
+        bbmpc::TrainHead head;
+        bbmpc::train_lds_layout_head(n, head);
+    }
+    return (int64_t)n.lds_floats * 4;
+}
+
+extern "C" {
+
+int bbmpc_trainer_lds_bytes(int32_t n_layers, const int32_t* dims, const int32_t* activations, int64_t* bytes) {
+    API_BEGIN
+    CHECK_PTR(bytes);
+    *bytes = 0;
+    *bytes = trainer_lds_bytes(n_layers, dims, activations, false);
+    API_END
+}
+
+int bbmpc_trainer_lds_bytes_gaussian(int32_t n_layers, const int32_t* dims, const int32_t* activations, int64_t* bytes) {
+    API_BEGIN
+    CHECK_PTR(bytes);
+    *bytes = 0;
+    *bytes = trainer_lds_bytes(n_layers, dims, activations, true);
+    API_END
+}
+
+int bbmpc_trainer_create_gaussian(bbmpc_trainer* out, int32_t device, int32_t n_members, int32_t n_layers, const int32_t* dims,
+                                  const int32_t* activations, const float* const* weights, const float* const* biases,
+                                  const float* const* head_weights, const float* const* head_biases, const float* min_logvar,
+                                  const float* max_logvar, int32_t rule, float learning_rate) {
+    API_BEGIN
+    trainer_create(out, device, n_members, n_layers, dims, activations, weights, biases, rule, learning_rate, true, head_weights, head_biases,
+                   min_logvar, max_logvar);
+    API_END
+}
+
+int bbmpc_trainer_get_logvar_head(bbmpc_trainer t, int32_t member, float* head_weights_out, float* head_bias_out) {
+    API_BEGIN
+    CHECK_TRAINER(t);
+    REQUIRE(t->t->gauss, BBMPC_E_STATE, "trainer: bbmpc_trainer_get_logvar_head on a trainer without a log-variance head (bbmpc_trainer_create_gaussian makes one)");
+    REQUIRE(head_weights_out && head_bias_out, BBMPC_E_INVALID, "trainer: null log-variance head outputs");
+    REQUIRE(member >= 0 && member < t->t->E, BBMPC_E_INVALID, "trainer: member outside [0, n_members)");
+    t->t->get_logvar_head(member, head_weights_out, head_bias_out);
     API_END
 }
 

@@ -56,6 +56,26 @@
 //              [parity ^ 1] unmultiplied, so that its step count stays its own when the trainer is fitted again.
 //   restore    k_train_restore, grid (ceil(n_params / 256), E), once at the end of a fit: best_theta -> theta and every
 //              layout the step kernel reads, for the members whose best_epoch >= 0.
+//
+// Log-variance head, Gaussian NLL: the NLL instantiations, a second template bool next to MON / REG.
+// The head-less instantiations carry no test of it and are the code they were.
+//   parameters theta = W_0 .. W_{L-1}, b_0 .. b_{L-1}, W_v [dims[L-1]][O], b_v [O]: DenseTrainer.params' order, every
+//              head-less offset as it was.  The head's W pack, W^T pack and padded bias close the member's slab (TrainHead).
+//   forward    in the last layer the head's tile product z = h W_v + b_v runs next to the mean's, on the same input tiles,
+//              into a tile array of its own (TrainHead::zoff, T_L tiles between the adjoint scratch and the row / loss words).
+//   elementwise, per valid element (tr_logvar; accurate expf / log1pf, the stage touches B O values per step):
+//                lv1 = max_lv - softplus(max_lv - z);  lv = min_lv + softplus(lv1 - min_lv);  inv = exp(-lv)
+//                diff = mu - t;  wsq = diff diff inv;  the thread's loss word += wsq + lv
+//                delta_mu = act'(mu) (diff inv)                                        in place of y_L
+//                delta_z  = 0.5 (1 - wsq) sigmoid(lv1 - min_lv) sigmoid(max_lv - z)    in place of z
+//              The factor 0.5 is exact and lets k_train_update keep its ONE 2 / (B O) scaling of every summed gradient:
+//              d loss / d z = (1 - wsq) dlv/dz / (B O).
+//   backward   at layer L - 1: dW_v = h^T delta_z and db_v exactly as dW_{L-1} and db_{L-1}; g = delta_mu W_{L-1}^T +
+//              delta_z W_v^T is ONE accumulator per output tile -- the mean's k tiles first, ascending, then the head's,
+//              ascending (two tr_tile_product calls on the same acc).  Below that layer nothing changes.
+//   update     W_v decays with the last layer's lambda, b_v never; snapshot and restore cover the head (n_params does).
+//   validation k_train_forward_mse<., true> writes per tile the sum of wsq + lv: k_train_val_reduce and k_train_monitor work
+//              on the NLL unchanged.  residual_rms stays the mean network's, through the head-less forward.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -130,6 +150,27 @@ __host__ __device__ inline void train_lds_layout(TrainNet& n) {
     n.nw = tmax < 4 ? 4 : (tmax > 16 ? 16 : tmax);
 }
 
+// The log-variance head of a Gaussian trainer: a second last Dense layer on y_{L-1}, linear, with
+// fixed per-output bounds.  It closes every argument struct, behind what the head-less kernels read.
+struct TrainHead {
+    int woff, boff;                              // theta offsets of W_v [dims[L-1]][O] and b_v [O]: behind b_{L-1}
+    int zoff;                                    // LDS offset (floats) of the head's tile array [T_L][64][4]
+    int pad_;
+    float* wf;                                   // operand pack of W_v   [T_L][T_{L-1}][64][4]; member e's: + e * pstride
+    float* wr;                                   // operand pack of W_v^T [T_{L-1}][T_L][64][4]
+    float* bp;                                   // b_v padded with zeros to 16 T_L
+    const float* min_lv;                         // [O], shared by the members
+    const float* max_lv;
+};
+
+// The Gaussian carve: train_lds_layout's with T_L more tiles, the head's z, between the adjoint scratch and the words:
+// 256 * (sum_l T_l + swish pre-activations + max_l T_l + T_L) + TR_SCRATCH floats.  Call after train_lds_layout.
+__host__ __device__ inline void train_lds_layout_head(TrainNet& n, TrainHead& h) {
+    h.zoff = n.soff;
+    n.soff += n.tiles[n.L] * 256;
+    n.lds_floats += n.tiles[n.L] * 256;
+}
+
 // offsets of parameter (i, o) of layer l in the two packs
 __host__ __device__ inline size_t train_wf_index(int IT, int i, int o) {
     return (((size_t)(o >> 4) * IT + (i >> 4)) * 64 + (((i & 15) >> 2) * 16 + (o & 15))) * 4 + (i & 3);
@@ -170,6 +211,7 @@ struct TrainStepArgs {
     float* part;                                 // [E][tiles][n_params]
     float* lossp;                                // [E][tiles] sum of squared errors
     const TrainMon* stop;                        // member e's state at [2 e] (the parity is in the pointer); null: none
+    TrainHead h;                                 // read by the NLL instantiation only
 };
 
 struct TrainMseArgs {
@@ -181,6 +223,7 @@ struct TrainMseArgs {
     float* tile_loss;                            // [E][batches * tiles_per_batch] or null
     float* colsq;                                // [E][batches * tiles_per_batch][O] or null
     const TrainMon* stop;                        // as TrainStepArgs::stop
+    TrainHead h;                                 // read by the NLL instantiation only
 };
 
 struct TrainUpdateArgs {
@@ -206,6 +249,7 @@ struct TrainUpdateArgs {
     int wd_mode;                                 // TR_DECAY_*
     int wd_on;                                   // is any lambda_l != 0?
     const TrainMon* stop;                        // as TrainStepArgs::stop
+    TrainHead h;                                 // read by the NLL instantiation only
 };
 
 #ifdef BBMPC_TU_TRAIN
@@ -236,6 +280,53 @@ __device__ __forceinline__ void tr_write_layouts(const TrainNet& n, size_t mo, i
         n.wf[l][mo + train_wf_index(n.tiles[l], fi, fo)] = w;
         n.wr[l][mo + train_wr_index(n.tiles[l + 1], fi, fo)] = w;
     }
+}
+
+// tr_param_layer with the head: its parameters lie behind b_{L-1} and count as layer L - 1 (the decay W_v sees).
+template <bool NLL>
+__device__ __forceinline__ bool tr_locate(const TrainNet& n, const TrainHead& h, int i, int& l, bool& head) {
+    head = NLL && i >= h.woff;
+    if (head) {
+        l = n.L - 1;
+        return i >= h.boff;
+    }
+    return tr_param_layer(n, i, l);
+}
+
+// tr_write_layouts with the head: W_v is packed like W_{L-1} (same tile counts), b_v like b_{L-1}.
+template <bool NLL>
+__device__ __forceinline__ void tr_store_layouts(const TrainNet& n, const TrainHead& h, size_t mo, int i, int l, bool bias, bool head, float w) {
+    if (NLL && head) {
+        if (bias) {
+            h.bp[mo + i - h.boff] = w;
+        } else {
+            const int out = n.dims[n.L];
+            const int k = i - h.woff;
+            const int fi = k / out, fo = k - fi * out;
+            h.wf[mo + train_wf_index(n.tiles[n.L - 1], fi, fo)] = w;
+            h.wr[mo + train_wr_index(n.tiles[n.L], fi, fo)] = w;
+        }
+    } else {
+        tr_write_layouts(n, mo, i, l, bias, w);
+    }
+}
+
+// softplus and the logistic function in their accurate forms (expf / log1pf): DenseTrainer._softplus's max(x, 0) +
+// log1p(e^-|x|), and e^-|x| on either side of 0 so that neither tail cancels.
+__device__ __forceinline__ float tr_softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float tr_sigmoid(float x) {
+    const float e = expf(-fabsf(x));
+    const float d = 1.0f + e;
+    return x >= 0.0f ? 1.0f / d : e / d;
+}
+
+// The soft clamp of the head's output z between lo = min_lv and hi = max_lv: lv, and dlv / dz.
+__device__ __forceinline__ void tr_logvar(float z, float lo, float hi, float& lv, float& dlv) {
+    const float a = hi - z;
+    const float lv1 = hi - tr_softplus(a);
+    const float b = lv1 - lo;
+    lv = lo + tr_softplus(b);
+    dlv = tr_sigmoid(b) * tr_sigmoid(a);
 }
 
 __device__ __forceinline__ int tr_addr(int f, int p) {                   // feature f of row p in a tile array
@@ -288,8 +379,10 @@ __device__ __forceinline__ void tr_load_input(const TrainNet& n, const float* di
 }
 
 // The forward stack: y_{l+1} = act(y_l W_l + b_l) for every layer, all resident; mo: the member's offset into the operand
-// packs.  Ends with a barrier.
-__device__ __forceinline__ void tr_forward(const TrainNet& n, size_t mo, int wave, int lane) {
+// packs.  NLL: in the last layer the head's z = y_{L-1} W_v + b_v is formed next to the mean's tile, into h.zoff.  Ends with a
+// barrier.
+template <bool NLL>
+__device__ __forceinline__ void tr_forward(const TrainNet& n, const TrainHead& h, size_t mo, int wave, int lane) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     for (int l = 0; l < n.L; ++l) {
         const int IT = n.tiles[l], OT = n.tiles[l + 1], a = n.act[l];
@@ -300,13 +393,19 @@ __device__ __forceinline__ void tr_forward(const TrainNet& n, size_t mo, int wav
             if (n.zoff[l] >= 0) *reinterpret_cast<tr_f32x4*>(smem + n.zoff[l] + (ot * 64 + lane) * 4) = acc;
             acc.x = apply_act(acc.x, a); acc.y = apply_act(acc.y, a); acc.z = apply_act(acc.z, a); acc.w = apply_act(acc.w, a);
             *reinterpret_cast<tr_f32x4*>(smem + n.yoff[l + 1] + (ot * 64 + lane) * 4) = acc;
+            if (NLL && l == n.L - 1) {
+                tr_f32x4 zv = *reinterpret_cast<const tr_f32x4*>(h.bp + mo + ot * 16 + (lane >> 4) * 4);
+                zv = tr_tile_product(reinterpret_cast<const tr_f32x4*>(h.wf + mo) + (size_t)ot * IT * 64 + lane, n.yoff[l], IT, lane, zv);
+                *reinterpret_cast<tr_f32x4*>(smem + h.zoff + (ot * 64 + lane) * 4) = zv;
+            }
         }
         __syncthreads();
     }
 }
 
 // MON: is the launch part of a monitored fit (q.stop set)?  The unmonitored instantiation carries no test of it.
-template <bool MON>
+// NLL: does the network carry a log-variance head (q.h set; the loss is the Gaussian NLL)?  Likewise.
+template <bool MON, bool NLL>
 __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (MON && tr_stopped(q.stop, blockIdx.y)) return;
@@ -324,10 +423,40 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
     float* part = q.part + slot * n.n_params;
 
     tr_load_input(n, q.din, q.idx ? q.idx + e * q.idx_stride : nullptr, q.row0, n0, valid, tid, nthr);
-    tr_forward(n, mo, wave, lane);
+    tr_forward<NLL>(n, q.h, mo, wave, lane);
 
-    // ---- delta_{L-1} = act'(y_L) * (y_L - t), in place (2 / (B O): k_train_update); each thread's squared errors go to its word
-    {
+    if (NLL) {
+        // ---- delta_mu = act'(y_L) (diff inv) in place of y_L, delta_z = 0.5 (1 - wsq) dlv/dz in place of z; each thread's
+        // wsq + lv go to its word.  The exact 0.5 leaves k_train_update its single 2 / (B O) for every summed gradient.
+        const int a = n.act[L - 1];
+        const int r = rows[p];
+        float sq = 0.0f;
+        for (int t = wave; t < n.tiles[L]; t += nw) {
+            float* yp = smem + n.yoff[L] + (t * 64 + lane) * 4;
+            float* zp = smem + q.h.zoff + (t * 64 + lane) * 4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int f = 16 * t + 4 * g + c;
+                float d = 0.0f, dz = 0.0f;
+                if (r >= 0 && f < O) {
+                    const float y = yp[c];
+                    const float z = n.zoff[L - 1] >= 0 ? smem[n.zoff[L - 1] + (t * 64 + lane) * 4 + c] : y;
+                    const float diff = y - q.dout[(size_t)r * O + f];
+                    float lv, dlv;
+                    tr_logvar(zp[c], q.h.min_lv[f], q.h.max_lv[f], lv, dlv);
+                    const float inv = expf(-lv);
+                    const float wsq = diff * diff * inv;
+                    sq = sq + (wsq + lv);
+                    d = train_act_grad(y, z, a) * (diff * inv);
+                    dz = 0.5f * (1.0f - wsq) * dlv;
+                }
+                yp[c] = d;
+                zp[c] = dz;
+            }
+        }
+        words[tid] = sq;
+    } else {
+        // ---- delta_{L-1} = act'(y_L) * (y_L - t), in place (2 / (B O): k_train_update); each thread's squared errors go to its word
         const int a = n.act[L - 1];
         const int r = rows[p];
         float sq = 0.0f;
@@ -389,13 +518,41 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
             for (int r = 0; r < TR_ROWS; ++r) s = s + dp[r * 4];
             part[n.boff[l] + o] = s;
         }
+        if (NLL && l == L - 1) {
+            // dW_v = y_{L-1}^T delta_z and db_v: the two loops above on the head's tiles
+            for (int pr = wave; pr < IT * OT; pr += nw) {
+                const int it = pr / OT, ot = pr - it * OT;
+                const float* xa = smem + n.yoff[l] + (it * 64 + (p >> 2) * 16) * 4 + (p & 3);
+                const float* db = smem + q.h.zoff + (ot * 64 + (p >> 2) * 16) * 4 + (p & 3);
+                tr_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[(4 * s + g) * 4], db[(4 * s + g) * 4], acc, 0, 0, 0);
+                const int fo = 16 * ot + p;
+                if (fo < out) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int fi = 16 * it + 4 * g + c;
+                        if (fi < in) part[q.h.woff + (size_t)fi * out + fo] = acc[c];
+                    }
+                }
+            }
+            for (int o = tid; o < out; o += nthr) {
+                const float* dp = smem + q.h.zoff + tr_addr(o, 0);
+                float s = 0.0f;
+#pragma unroll
+                for (int r = 0; r < TR_ROWS; ++r) s = s + dp[r * 4];
+                part[q.h.boff + o] = s;
+            }
+        }
         if (l == 0) break;
-        // g = delta_l W_l^T
+        // g = delta_l W_l^T; NLL, at the last layer: + delta_z W_v^T on the same accumulator, the mean's k tiles first
         {
             const tr_f32x4* __restrict__ W = reinterpret_cast<const tr_f32x4*>(n.wr[l] + mo);
             for (int ot = wave; ot < IT; ot += nw) {
                 tr_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
                 acc = tr_tile_product(W + (size_t)ot * OT * 64 + lane, n.yoff[l + 1], OT, lane, acc);
+                if (NLL && l == L - 1)
+                    acc = tr_tile_product(reinterpret_cast<const tr_f32x4*>(q.h.wr + mo) + (size_t)ot * OT * 64 + lane, q.h.zoff, OT, lane, acc);
                 *reinterpret_cast<tr_f32x4*>(smem + n.goff + (ot * 64 + lane) * 4) = acc;
             }
         }
@@ -425,8 +582,8 @@ __global__ __launch_bounds__(1024) void k_train_fwd_bwd(TrainStepArgs q) {
 }
 
 // Forward only on rows b * B + 16 t .. of batch b (tile t of the batch): squared errors per output column, and their sum.
-// Grid (batches * tiles_per_batch, E): every member on the same rows.
-template <bool MON>
+// Grid (batches * tiles_per_batch, E): every member on the same rows.  NLL: per output column the sum of wsq + lv instead.
+template <bool MON, bool NLL>
 __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (MON && tr_stopped(q.stop, blockIdx.y)) return;
@@ -440,10 +597,20 @@ __global__ __launch_bounds__(1024) void k_train_forward_mse(TrainMseArgs q) {
     float* words = smem + n.soff + 64;
     const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;          // (member, tile)
     tr_load_input(n, q.din, nullptr, batch * q.B, n0, valid, tid, nthr);
-    tr_forward(n, (size_t)blockIdx.y * n.pstride, wave, lane);
+    tr_forward<NLL>(n, q.h, (size_t)blockIdx.y * n.pstride, wave, lane);
     for (int o = tid; o < 1024; o += nthr) {
         float s = 0.0f;
-        if (o < O)
+        if (NLL) {
+            if (o < O) {
+                const float lo = q.h.min_lv[o], hi = q.h.max_lv[o];
+                for (int r = 0; r < valid; ++r) {
+                    const float d = smem[n.yoff[L] + tr_addr(o, r)] - q.dout[(size_t)rows[r] * O + o];
+                    float lv, dlv;
+                    tr_logvar(smem[q.h.zoff + tr_addr(o, r)], lo, hi, lv, dlv);
+                    s = s + (d * d * expf(-lv) + lv);
+                }
+            }
+        } else if (o < O)
             for (int r = 0; r < valid; ++r) {
                 const float d = smem[n.yoff[L] + tr_addr(o, r)] - q.dout[(size_t)rows[r] * O + o];
                 s = s + d * d;
@@ -497,7 +664,8 @@ __global__ void k_train_rms_reduce(const float* colsq, int tiles, int O, float i
 // Grid (ceil(n_params / 256), E).  REG: does the launch decay a kernel or belong to a monitored fit?  The instantiation
 // without either is the update as it has always been, instruction for instruction: an early test of q.stop in front of the
 // other arguments' loads cost a default fit 0.5 % when it was there (profiles/train_hip.md).
-template <bool REG>
+// NLL: does theta end with a log-variance head (q.h set)?  W_v then decays with the last layer's lambda, b_v never.
+template <bool REG, bool NLL>
 __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     const TrainNet& n = q.n;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -545,10 +713,10 @@ __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     // parameter otherwise, where it has always been.
     const bool decay = REG && q.wd_on;
     int l = 0;
-    bool bias = false;
+    bool bias = false, head = false;
     float lam = 0.0f;
     if (decay) {
-        bias = tr_param_layer(n, i, l);
+        bias = tr_locate<NLL>(n, q.h, i, l, head);
         lam = bias ? 0.0f : q.wd[l];
     }
     const float w0 = theta[i];
@@ -570,8 +738,8 @@ __global__ __launch_bounds__(256) void k_train_update(TrainUpdateArgs q) {
     }
     if (lam != 0.0f && q.wd_mode == TR_DECAY_DECOUPLED) w = __fmaf_rn(-q.lrwd[l], w0, w);
     theta[i] = w;
-    if (!decay) bias = tr_param_layer(n, i, l);
-    tr_write_layouts(n, mo, i, l, bias, w);                         // every layout the step kernel reads
+    if (!decay) bias = tr_locate<NLL>(n, q.h, i, l, head);
+    tr_store_layouts<NLL>(n, q.h, mo, i, l, bias, head, w);         // every layout the step kernel reads
 }
 
 // Epoch k's decision for every member, behind k_train_val_reduce.  Grid (ceil(n_params / 256), E), or (1, E) with
@@ -608,16 +776,18 @@ __global__ __launch_bounds__(256) void k_train_monitor(TrainMon* mon, const floa
 }
 
 // best_theta -> theta and every layout, for the members with a best epoch; mon: the state after the last epoch.
-// Grid (ceil(n_params / 256), E).
-__global__ __launch_bounds__(256) void k_train_restore(TrainNet n, const TrainMon* mon, const float* best_theta, float* theta) {
+// Grid (ceil(n_params / 256), E).  NLL: the head's parameters and its three layouts too (h).
+template <bool NLL>
+__global__ __launch_bounds__(256) void k_train_restore(TrainNet n, const TrainMon* mon, const float* best_theta, float* theta, TrainHead h) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int e = blockIdx.y;
     if (mon[2 * e].best_epoch < 0 || i >= n.n_params) return;
     const float w = best_theta[(size_t)e * n.n_params + i];
     theta[(size_t)e * n.n_params + i] = w;
     int l;
-    const bool bias = tr_param_layer(n, i, l);
-    tr_write_layouts(n, (size_t)e * n.pstride, i, l, bias, w);
+    bool head;
+    const bool bias = tr_locate<NLL>(n, h, i, l, head);
+    tr_store_layouts<NLL>(n, h, (size_t)e * n.pstride, i, l, bias, head, w);
 }
 
 #endif  // BBMPC_TU_TRAIN

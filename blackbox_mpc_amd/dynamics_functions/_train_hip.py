@@ -6,8 +6,11 @@ other.  The dataset, the permutations of all epochs, the optimizer state and the
 losses are read once per fit.  `HipEnsembleTrainer` fits the equally shaped members of an ensemble side by side in the same
 two launches per step (the member index is a grid dimension), bit for bit what one `HipDenseTrainer` per member gives.
 
-Out of scope: a log-variance head (Gaussian NLL) -- ProbabilisticMLP and EnsembleMLP(probabilistic=True) train with the
-torch backend.  `dense_trainer(backend, ...)` is how every `train(..., backend=...)` of the package picks its trainer."""
+A log-variance head (Gaussian NLL: ProbabilisticMLP, EnsembleMLP(probabilistic=True)) is fitted by `HipGaussianTrainer` /
+`HipGaussianEnsembleTrainer` (bbmpc_trainer_create_gaussian) -- DenseTrainer(..., logvar_head=...)'s
+rule in the same kernels' NLL instantiations, W_v and b_v closing the parameter vector.  They are reached with the backend
+"hip_nll"; "hip" itself keeps refusing such models, and on a model without a head "hip_nll" is "hip": the same trainers,
+launches and bits.  `dense_trainer(backend, ...)` is how every `train(..., backend=...)` of the package picks its trainer."""
 import ctypes
 import os
 
@@ -16,14 +19,14 @@ import numpy as np
 from .. import _lib as L
 from . import _train_reg as R
 
-BACKENDS = ("torch", "hip")
+BACKENDS = ("torch", "hip", "hip_nll")
 _RULES = {"adam": L.TRAIN_ADAM, "sgd": L.TRAIN_SGD, "rmsprop": L.TRAIN_RMSPROP}
 _DECAY_MODES = {"l2": L.TRAIN_DECAY_L2, "decoupled": L.TRAIN_DECAY_DECOUPLED}
 
 
 def check_backend(backend):
     if backend not in BACKENDS:
-        raise ValueError("unknown training backend %r: 'torch' (default) or 'hip'" % (backend,))
+        raise ValueError("unknown training backend %r: 'torch' (default), 'hip' or 'hip_nll'" % (backend,))
     return backend
 
 
@@ -43,6 +46,22 @@ def lds_bytes_formula(dims, act_codes):
     t = [(int(d) + 15) // 16 for d in dims]
     pre = sum(t[l + 1] for l, a in enumerate(act_codes) if a == L.ACT_SWISH)
     return 4 * (256 * (sum(t) + pre + max(t)) + 1088)
+
+
+def lds_bytes_gaussian(dims, act_codes):
+    """The carve of the kernels' NLL instantiations in bytes (bbmpc_trainer_lds_bytes_gaussian; no device needed)."""
+    dims = np.ascontiguousarray(dims, np.int32)
+    acts = np.ascontiguousarray(act_codes, np.int32)
+    out = ctypes.c_int64(0)
+    L.check(L.lib.bbmpc_trainer_lds_bytes_gaussian(len(acts), dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                   acts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(out)))
+    return int(out.value)
+
+
+def lds_bytes_formula_gaussian(dims, act_codes):
+    """The same number from the formula DESIGN.md section 8s states: `lds_bytes_formula`'s with T_L more tiles, the head's z:
+    4 * (256 * (sum_l T_l + sum over swish layers of T_{l+1} + max_l T_l + T_L) + 1088)."""
+    return lds_bytes_formula(dims, act_codes) + 4 * 256 * ((int(dims[-1]) + 15) // 16)
 
 
 def draw_permutation(seed, epoch, n):
@@ -365,9 +384,148 @@ class HipEnsembleTrainer(_Regularized):
         return ws, bs
 
 
+def _head_arrays(logvar_head, hidden, out):
+    """DenseTrainer's `logvar_head` = (W_v, b_v, min_logvar, max_logvar) as float32 arrays: W_v [hidden][out], b_v [out], the
+    bounds [out] (scalars broadcast; the library checks their values)."""
+    wv, bv, lo, hi = logvar_head
+    wv = np.ascontiguousarray(wv, np.float32)
+    bv = np.ascontiguousarray(bv, np.float32).reshape(-1)
+    if wv.shape != (hidden, out) or bv.shape != (out,):
+        raise ValueError("logvar_head: kernel %s / bias %s do not sit on the last hidden layer (%d) with %d outputs"
+                         % (wv.shape, bv.shape, hidden, out))
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, np.float32), (out,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, np.float32), (out,)))
+    return wv, bv, lo, hi
+
+
+def _check_gaussian_options(rule, betas):
+    if rule not in _RULES:
+        raise ValueError("unknown optimizer rule %r" % (rule,))
+    if tuple(float(v) for v in betas) != (0.9, 0.999, 1e-7, 0.9):
+        raise ValueError("the hip training backend is built with the Keras TF-2.0 defaults "
+                         "(beta_1 0.9, beta_2 0.999, epsilon 1e-7, rho 0.9); use backend='torch' for others")
+
+
+class HipGaussianTrainer(HipDenseTrainer):
+    """HipDenseTrainer's surface for a Dense stack with a log-variance head (bbmpc_trainer_create_gaussian with one member;
+    DESIGN.md section 8s): DenseTrainer(..., logvar_head=...)'s rule.  Every loss is the Gaussian NLL, `residual_rms` stays the
+    mean network's residual."""
+    has_logvar_head = True
+
+    def __init__(self, weights, biases, act_codes, device=None, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+                 rule="adam", rho=0.9, logvar_head=None, weight_decay=0.0, decay_mode="l2", patience=0, min_delta=0.0,
+                 restore_best=False):
+        """logvar_head: (W_v [hidden, out], b_v [out], min_logvar, max_logvar), the bounds scalars or [out]; the other
+        arguments are HipDenseTrainer's.  weight_decay decays W_v with the last layer's value and never b_v."""
+        _check_gaussian_options(rule, (beta_1, beta_2, epsilon, rho))
+        R.check_options(weight_decay, decay_mode, patience, min_delta, restore_best, n_layers=len(weights))
+        if logvar_head is None:
+            raise ValueError("HipGaussianTrainer needs a logvar_head; HipDenseTrainer fits a network without one")
+        self._t = ctypes.c_void_p(None)
+        self._w = [np.ascontiguousarray(w, np.float32) for w in weights]
+        self._b = [np.ascontiguousarray(b, np.float32).reshape(-1) for b in biases]
+        self.acts = [int(a) for a in act_codes]
+        self.dims = [int(self._w[0].shape[0])] + [int(w.shape[1]) for w in self._w]
+        for l, (w, b) in enumerate(zip(self._w, self._b)):
+            if w.ndim != 2 or w.shape[0] != self.dims[l] or b.shape[0] != w.shape[1]:
+                raise ValueError("layer %d: kernel %s / bias %s do not chain" % (l, w.shape, b.shape))
+        if len(self.acts) != len(self._w) or len(self._b) != len(self._w):
+            raise ValueError("one activation code and one bias per kernel")
+        self._wv, self._bv, self._lo, self._hi = _head_arrays(logvar_head, self.dims[-2], self.dims[-1])
+        self.rule = rule
+        dims = np.asarray(self.dims, np.int32)
+        acts = np.asarray(self.acts, np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        L.check(L.lib.bbmpc_trainer_create_gaussian(
+            ctypes.byref(self._t), _device_index(device), 1, len(self._w), dims.ctypes.data_as(i32p), acts.ctypes.data_as(i32p),
+            _ptr_array(self._w), _ptr_array(self._b), _ptr_array([self._wv]), _ptr_array([self._bv]), L.ptr(self._lo), L.ptr(self._hi),
+            _RULES[rule], float(learning_rate)))
+        self._configure(weight_decay, decay_mode, patience, min_delta, restore_best)
+        self.epochs_run, self.best_epoch, self.best_val = 0, -1, float("nan")
+
+    @property
+    def n_params(self):
+        return sum(w.size for w in self._w) + sum(b.size for b in self._b) + self._wv.size + self._bv.size
+
+    def gradients(self, idx):
+        """(NLL, [dW_l], [db_l], dW_v, db_v) of the batch made of training rows `idx`, by the step's kernels, nothing
+        updated."""
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        g = np.zeros((self.n_params,), np.float32)
+        loss = ctypes.c_float(0.0)
+        L.check(L.lib.bbmpc_trainer_gradients(self._t, L.ptr(idx), idx.shape[0], L.ptr(g), ctypes.byref(loss)))
+        out, o = [], 0
+        for a in self._w + self._b + [self._wv, self._bv]:
+            out.append(g[o:o + a.size].reshape(a.shape))
+            o += a.size
+        n = len(self._w)
+        return float(loss.value), out[:n], out[n:2 * n], out[2 * n], out[2 * n + 1]
+
+    def numpy_logvar_head(self):
+        wv, bv = np.zeros_like(self._wv), np.zeros_like(self._bv)
+        L.check(L.lib.bbmpc_trainer_get_logvar_head(self._t, 0, L.ptr(wv), L.ptr(bv)))
+        return wv, bv
+
+
+class HipGaussianEnsembleTrainer(HipEnsembleTrainer):
+    """HipEnsembleTrainer's surface for E equally shaped Dense stacks with a log-variance head each
+    (bbmpc_trainer_create_gaussian): all members in one launch sequence, member e bit for bit the `HipGaussianTrainer` with its
+    start parameters, rows and permutations.  The bounds are shared by the members."""
+    has_logvar_head = True
+
+    def __init__(self, weights_per_member, biases_per_member, act_codes, device=None, learning_rate=1e-3, rule="adam",
+                 logvar_heads=None, min_logvar=-10.0, max_logvar=0.5, weight_decay=0.0, decay_mode="l2", patience=0, min_delta=0.0,
+                 restore_best=False, beta_1=0.9, beta_2=0.999, epsilon=1e-7, rho=0.9):
+        """logvar_heads: per member (W_v [hidden, out], b_v [out]); min_logvar / max_logvar: scalars or [out]."""
+        _check_gaussian_options(rule, (beta_1, beta_2, epsilon, rho))
+        R.check_options(weight_decay, decay_mode, patience, min_delta, restore_best, n_layers=len(act_codes))
+        self._t = ctypes.c_void_p(None)
+        if len(weights_per_member) != len(biases_per_member) or logvar_heads is None or len(logvar_heads) != len(weights_per_member):
+            raise ValueError("one list of biases and one entry of logvar_heads per list of kernels")
+        self._w = [[np.ascontiguousarray(w, np.float32) for w in ws] for ws in weights_per_member]
+        self._b = [[np.ascontiguousarray(b, np.float32).reshape(-1) for b in bs] for bs in biases_per_member]
+        self.n_members = len(self._w)
+        self.acts = [int(a) for a in act_codes]
+        first = self._w[0] if self._w else []
+        self.dims = ([int(first[0].shape[0])] + [int(w.shape[1]) for w in first]) if first else []
+        for e, (ws, bs) in enumerate(zip(self._w, self._b)):
+            if len(ws) != len(self.acts) or len(bs) != len(ws):
+                raise ValueError("member %d: one activation code and one bias per kernel" % e)
+            for l, (w, b) in enumerate(zip(ws, bs)):
+                if w.shape != (self.dims[l], self.dims[l + 1]) or b.shape[0] != w.shape[1]:
+                    raise ValueError("member %d, layer %d: kernel %s / bias %s do not fit the members' shape %s"
+                                     % (e, l, w.shape, b.shape, self.dims))
+        heads = [_head_arrays((wv, bv, min_logvar, max_logvar), self.dims[-2], self.dims[-1]) for wv, bv in logvar_heads] \
+            if self.dims else []
+        self._wv, self._bv = [h[0] for h in heads], [h[1] for h in heads]
+        lo = heads[0][2] if heads else np.zeros((0,), np.float32)
+        hi = heads[0][3] if heads else np.zeros((0,), np.float32)
+        self.rule = rule
+        dims = np.asarray(self.dims, np.int32)
+        acts = np.asarray(self.acts, np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        L.check(L.lib.bbmpc_trainer_create_gaussian(
+            ctypes.byref(self._t), _device_index(device), self.n_members, len(self.acts), dims.ctypes.data_as(i32p),
+            acts.ctypes.data_as(i32p), _ptr_array([w for ws in self._w for w in ws]), _ptr_array([b for bs in self._b for b in bs]),
+            _ptr_array(self._wv), _ptr_array(self._bv), L.ptr(lo), L.ptr(hi), _RULES[rule], float(learning_rate)))
+        self._configure(weight_decay, decay_mode, patience, min_delta, restore_best)
+        self.epochs_run = np.zeros((self.n_members,), np.int64)
+        self.best_epoch = np.full((self.n_members,), -1, np.int64)
+        self.best_val = np.full((self.n_members,), np.nan)
+
+    def numpy_logvar_head(self, member):
+        wv, bv = np.zeros_like(self._wv[0]), np.zeros_like(self._bv[0])
+        L.check(L.lib.bbmpc_trainer_get_logvar_head(self._t, int(member), L.ptr(wv), L.ptr(bv)))
+        return wv, bv
+
+
 def dense_trainer(backend, weights, biases, act_codes, device, **kwargs):
-    """The trainer behind every `train(..., backend=...)`: DenseTrainer for "torch", HipDenseTrainer for "hip"."""
-    if check_backend(backend) == "hip":
+    """The trainer behind every `train(..., backend=...)`: DenseTrainer for "torch", HipDenseTrainer for "hip" and for
+    "hip_nll" on a model without a log-variance head, HipGaussianTrainer for "hip_nll" on one with a head."""
+    backend = check_backend(backend)
+    if backend == "hip_nll" and kwargs.get("logvar_head") is not None:
+        return HipGaussianTrainer(weights, biases, act_codes, device, **kwargs)
+    if backend in ("hip", "hip_nll"):
         return HipDenseTrainer(weights, biases, act_codes, device, **kwargs)
     from ._train_torch import DenseTrainer
     return DenseTrainer(weights, biases, act_codes, device, **kwargs)

@@ -243,7 +243,10 @@ class SystemDynamicsHandler:
         residual_std() stays the mean network's residual.  `backend`: "torch" (DenseTrainer, the default) or "hip"
         (dynamics_functions/_train_hip.HipDenseTrainer: the hand-written training kernels, GPU only, plain MSE models --
         a model with a log-variance head is refused by name; the members of an EnsembleMLP are fitted by one
-        HipEnsembleTrainer, all of them in one launch sequence).
+        HipEnsembleTrainer, all of them in one launch sequence) or "hip_nll" ("hip" for a model without a log-variance head,
+        the same trainers and bits; a ProbabilisticMLP is fitted by a HipGaussianTrainer and the members of an
+        EnsembleMLP(probabilistic=True) by ONE HipGaussianEnsembleTrainer: the Gaussian NLL in the same kernels, DESIGN.md
+        section 8s).
         `weight_decay` (a scalar or one value per layer, kernels only) / `decay_mode` ("l2" | "decoupled"), `patience` /
         `min_delta` (early stopping on the validation loss) and `restore_best` (the best epoch's weights are installed):
         dynamics_functions/_train_reg.py; both backends, every member of an ensemble on its own.
@@ -265,7 +268,7 @@ class SystemDynamicsHandler:
             raise Exception("train() needs a DeterministicMLP dynamics function")
         if backend == "hip" and getattr(fn, "logvar_heads", None):
             raise ValueError("backend='hip' fits plain Dense stacks (MSE): %s has a log-variance head (Gaussian NLL) and "
-                             "trains with backend='torch'" % type(fn).__name__)
+                             "trains with backend='torch' or backend='hip_nll'" % type(fn).__name__)
         if device is None and backend == "torch":
             import torch
             if not torch.cuda.is_available():
@@ -339,7 +342,7 @@ class SystemDynamicsHandler:
             else:
                 perms = permutations[e] if per_member else permutations
             draws.append((idx, perms))
-        if backend == "hip":
+        if backend in ("hip", "hip_nll"):                                  # (train() refused "hip" on a probabilistic ensemble)
             tl, vl, rms, ran, best = self._fit_members_hip(members, draws, tin, tout, vin, vout, epochs, batch_size, learning_rate, rule,
                                                            device, seed, reg)
         else:
@@ -369,16 +372,26 @@ class SystemDynamicsHandler:
         the device once, member e's bootstrap resample is the index map `member_rows[e]`, and every step is one launch pair
         for all members.  Bit for bit what a HipDenseTrainer per member on `tin[idx]` gives.  Returns the per-member lists
         (training loss, validation loss, residual RMS -- of the weights the fit leaves, restored ones included -- epochs run,
-        best epoch)."""
-        from ..dynamics_functions._train_hip import HipEnsembleTrainer
-        trainer = HipEnsembleTrainer([m.weights for m in members], [m.biases for m in members], members[0].activation_codes,
-                                     device, learning_rate=learning_rate, rule=rule, **(reg or {}))
+        best epoch).  Members with a log-variance head (backend "hip_nll" on a probabilistic ensemble) are fitted the same way
+        by ONE HipGaussianEnsembleTrainer: the losses are then the NLL, the residual stays the mean network's, and the heads
+        are installed with the weights."""
+        from ..dynamics_functions import _train_hip as T
+        if _logvar_head(members[0]) is None:
+            trainer = T.HipEnsembleTrainer([m.weights for m in members], [m.biases for m in members], members[0].activation_codes,
+                                           device, learning_rate=learning_rate, rule=rule, **(reg or {}))
+        else:
+            trainer = T.HipGaussianEnsembleTrainer(
+                [m.weights for m in members], [m.biases for m in members], members[0].activation_codes, device,
+                learning_rate=learning_rate, rule=rule, logvar_heads=[(m.logvar_weights, m.logvar_bias) for m in members],
+                min_logvar=members[0].min_logvar, max_logvar=members[0].max_logvar, **(reg or {}))
         try:
             tl, vl = trainer.fit(tin, tout, vin, vout, epochs, batch_size, member_rows=[idx for idx, _ in draws],
                                  permutations=[np.asarray(perms)[:epochs] for _, perms in draws], generator_seed=seed)
             rms = trainer.residual_rms(vin, vout)
             for e, member in enumerate(members):
                 member.set_weights(*trainer.numpy_params(e))               # bumps the version: evaluators re-upload
+                if getattr(trainer, "has_logvar_head", False):
+                    member.set_logvar_head(*trainer.numpy_logvar_head(e))
         finally:
             trainer.close()
         ran = getattr(trainer, "epochs_run", [epochs] * len(members))

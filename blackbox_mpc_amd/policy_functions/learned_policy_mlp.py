@@ -84,7 +84,7 @@ class LearnedPolicyMLP:
         GPU when PyTorch sees one, else the CPU).  states [B, S], actions [B, U].  The statistics are refreshed from exactly
         these rows and the version is bumped, so every engine that holds the network uploads it again before its next
         computation.  Returns (train_loss [epochs], validation_loss [epochs]).
-        backend: "torch" (the default) or "hip" -- the hand-written training kernels
+        backend: "torch" (the default), "hip" or "hip_nll" (here the same as "hip") -- the hand-written training kernels
         (dynamics_functions/_train_hip.HipDenseTrainer; GPU only, permutations drawn by the library from `seed`).
         weight_decay / decay_mode / patience / min_delta / restore_best (keyword-only): weight decay on the kernels, early
         stopping on the validation loss and best-weights restore (dynamics_functions/_train_reg.py),

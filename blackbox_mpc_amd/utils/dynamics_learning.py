@@ -11,7 +11,7 @@ def learn_dynamics_from_policy(env, policy, number_of_rollouts, task_horizon, dy
                                start_episode=0, multistep_horizon=None, reward_model=None, reward_train_args=None,
                                value_model=None, value_n_step=10, value_train_args=None, policy_model=None, policy_train_args=None,
                                **train_args):
-    """Same arguments as the reference; `train_args` (device=, seed=, backend="torch" | "hip", ...) are forwarded to `train`.
+    """Same arguments as the reference; `train_args` (device=, seed=, backend="torch" | "hip" | "hip_nll", ...) are forwarded to `train`.
     `multistep_horizon`: when set, the fit is followed by one SystemDynamicsHandler.multistep_error call over that many
     steps on the episodes just collected (the train / validation split is per transition, so there is no held-out
     episode to use instead); the result stays on the handler as `multistep_rmse` -- a TRAINING-set figure, optimistic

@@ -21,8 +21,8 @@ def learn_dynamics_iteratively_w_mpc(env, number_of_initial_rollouts, number_of_
                                      reward_model=None, reward_train_args=None, value_model=None, value_n_step=10,
                                      value_train_args=None, policy_model=None, policy_train_args=None, **optimizer_args):
     """Same arguments as the reference (+ `train_args`, a dict forwarded to SystemDynamicsHandler.train -- device=, seed=,
-    backend="torch" | "hip" (the hand-written training kernels), ...; the reward / value / policy models take theirs
-    through `reward_train_args` / `value_train_args` / `policy_train_args` -- and
+    backend="torch" | "hip" | "hip_nll" (the hand-written training kernels; "hip_nll" also fits log-variance heads), ...;
+    the reward / value / policy models take theirs through `reward_train_args` / `value_train_args` / `policy_train_args` -- and
     `multistep_horizon`: every fit is followed by the open-loop error over that many steps, kept as
     `handler.multistep_rmse`; None = not computed; and `reward_model`, a LearnedRewardMLP refitted in every iteration from
     the rewards the rollouts collect -- pass the same object as `reward_function` to plan with it; and `value_model`, a

@@ -825,7 +825,7 @@ int bbmpc_comm_destroy(bbmpc_handle h);
  * m, v and t belong to the trainer and go on from one bbmpc_trainer_fit to the next.  train_loss_out[e] = mean of epoch e's
  * batch losses (NaN without a full batch); val_loss_out[e] = mean of the per-batch MSEs over the floor(n_val / B) full batches
  * val[0 .. B), val[B .. 2B), ... after the epoch (NaN without one).  Equal calls from equal starts give equal bits.
- * Out of scope: log-variance heads / Gaussian NLL.
+ * Log-variance heads / Gaussian NLL: bbmpc_trainer_create_gaussian, below.
  *
  * Layouts as bbmpc_set_mlp: Dense kernels [in, out] row-major, biases [out], dims has n_layers + 1 entries (so the widths
  * chain by construction), any BBMPC_ACT_* code per layer.  device: HIP ordinal, -1 = current.
@@ -933,6 +933,40 @@ int bbmpc_trainer_residual_rms_ensemble(bbmpc_trainer t, const float* in, const 
 int bbmpc_trainer_set_weight_decay(bbmpc_trainer t, const float* decay, int32_t mode);
 int bbmpc_trainer_set_early_stopping(bbmpc_trainer t, int32_t patience, float min_delta, int32_t restore_best);
 int bbmpc_trainer_get_fit_report(bbmpc_trainer t, int32_t* epochs_run, int32_t* best_epoch, float* best_val);
+
+/* ---- log-variance heads: the Gaussian negative log-likelihood ---------------------------------------
+ * A trainer whose members carry a second last Dense layer on the last hidden activation h = y_{L-1} (the input when n_layers
+ * = 1), the log-variance head of ProbabilisticMLP / EnsembleMLP(probabilistic=True) (bbmpc_set_mlp_logvar_head), fitted
+ * together with the mean network on
+ *   mu = act_{L-1}(h W_{L-1} + b_{L-1});   z = h W_v + b_v
+ *   lv1 = max_lv - softplus(max_lv - z);   lv = min_lv + softplus(lv1 - min_lv)
+ *   loss = mean over the batch's B * O elements of (mu - y)^2 exp(-lv) + lv,   O = dims[n_layers]
+ *   d loss / d mu = 2 (mu - y) exp(-lv) / (B O)
+ *   d loss / d z  = (1 - (mu - y)^2 exp(-lv)) sigmoid(lv1 - min_lv) sigmoid(max_lv - z) / (B O)
+ * W_v [dims[n_layers - 1]][O] and b_v [O] are parameters like any other (same update rules, m, v, powers); in the parameter
+ * vector they follow b_{L-1}.  Weight decay treats W_v as a kernel with the last layer's lambda and b_v as a bias.  The bounds
+ * are fixed.  softplus, exp and the logistic function are evaluated in their accurate float32 forms.
+ *
+ * weights / biases: [n_members * n_layers] pointers, member major; head_weights / head_biases: [n_members] pointers;
+ * min_logvar / max_logvar: [O], shared by the members.  n_members = 1 is the single model.  Refusals as
+ * bbmpc_trainer_create_ensemble, the LDS limit on bbmpc_trainer_lds_bytes_gaussian; BBMPC_E_INVALID also for a NULL head
+ * array and for bounds that are not finite, not inside [-40, 40] or have min_logvar > max_logvar.
+ *
+ * On such a trainer every other bbmpc_trainer_* call works as described above (the single-member ones with n_members = 1), and
+ * every loss is the NLL: train_loss_out, val_loss_out (mean of the per-batch NLLs), what the monitor compares, best_val, and
+ * bbmpc_trainer_gradients' loss, whose grads_out holds n_params = the mean network's + dims[n_layers - 1] * O + O floats, W_v
+ * and b_v last.  bbmpc_trainer_residual_rms(_ensemble) stays the mean network's residual.  Member e of n_members is, bit for
+ * bit, the single Gaussian trainer with its start parameters, rows and permutations. */
+int bbmpc_trainer_create_gaussian(bbmpc_trainer* out, int32_t device, int32_t n_members, int32_t n_layers, const int32_t* dims,
+                                  const int32_t* activations, const float* const* weights, const float* const* biases,
+                                  const float* const* head_weights, const float* const* head_biases, const float* min_logvar,
+                                  const float* max_logvar, int32_t rule, float learning_rate);
+/* Member `member`'s current head: head_weights_out [dims[n_layers - 1]][O], head_bias_out [O].  BBMPC_E_STATE on a trainer
+ * without a head; BBMPC_E_INVALID: NULL outputs, member outside [0, n_members). */
+int bbmpc_trainer_get_logvar_head(bbmpc_trainer t, int32_t member, float* head_weights_out, float* head_bias_out);
+/* bbmpc_trainer_lds_bytes with the head's tile array: 4 * (256 * (sum_{l=0..L} T_l + sum over swish layers of T_{l+1} +
+ * max_l T_l + T_L) + 1088).  Host arithmetic only: no device needed. */
+int bbmpc_trainer_lds_bytes_gaussian(int32_t n_layers, const int32_t* dims, const int32_t* activations, int64_t* bytes);
 
 #ifdef __cplusplus
 }
