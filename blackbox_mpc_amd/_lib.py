@@ -101,6 +101,7 @@ SYMBOLS = [
     "bbmpc_set_reward_mlp",
     "bbmpc_set_terminal_value_mlp", "bbmpc_evaluate_terminal_value", "bbmpc_evaluate_terminal_value_dev",
     "bbmpc_set_return_shaping", "bbmpc_get_termination_steps",
+    "bbmpc_set_chance_constraint", "bbmpc_get_constraint_violations",
     "bbmpc_set_policy_prior_mlp", "bbmpc_get_policy_prior", "bbmpc_evaluate_policy_prior", "bbmpc_evaluate_policy_prior_dev",
     "bbmpc_predict_policy_rollouts", "bbmpc_predict_policy_rollouts_dev",
     "bbmpc_plan_gradient", "bbmpc_plan_gradient_dev",
@@ -224,6 +225,8 @@ def _load():
     lib.bbmpc_predict_trajectory_particles.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.bbmpc_predict_trajectory_particles_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.bbmpc_set_particle_risk.argtypes = [vp, i32, i32]
+    lib.bbmpc_set_chance_constraint.argtypes = [vp, vp, vp, ctypes.c_float, ctypes.c_float]
+    lib.bbmpc_get_constraint_violations.argtypes = [vp, i32, vp, vp]
     lib.bbmpc_predict_trajectory_quantiles.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.bbmpc_predict_trajectory_quantiles_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.bbmpc_set_sampling_correlation.argtypes = [vp, vp, i64]

@@ -1537,6 +1537,7 @@ void Engine::get_state(const std::string& name, float* out, int64_t count) {
         HIP_CHECK(hipMemcpy(out, d_samples.p, (size_t)count * 4, hipMemcpyDeviceToHost));
         return;
     }
+    if (constraint_raw_state(name, out, nullptr, count)) return;       // the chance constraint's buffers (bbmpc_particles.hip)
     if (name == "shaping_n_pop") {                            // candidates of the most recent shaped rollout (bbmpc_get_termination_steps' n / A); 0: none yet
         REQUIRE(count == 1, BBMPC_E_INVALID, "shaping_n_pop has one element");
         out[0] = (float)sh_last_npop;
@@ -1609,6 +1610,7 @@ void Engine::set_state(const std::string& name, const float* data, int64_t count
         HIP_CHECK(hipMemcpy(d_samples.p, data, (size_t)count * 4, hipMemcpyHostToDevice));
         return;
     }
+    if (name != "constraint_shape" && constraint_raw_state(name, nullptr, data, count)) return;      // (tests: a sentinel in the padding)
     if (name == "prev_mean") dst = d_prev_mean.p;
     else if (name == "C" && cfg.optimizer == BBMPC_OPT_CMAES) { dst = c_C.p; nm = (size_t)cma_G * cma_n * cma_n; }   // (tests: a covariance at another scale)
     else if (name == "var0") { dst = d_var0.p; pi2_dist_ready = false; }

@@ -5,6 +5,7 @@
 
 #include "abi_util.hpp"
 #include "kernels_particles.hpp"
+#include "kernels_particle_constraint.hpp"
 
 namespace bbmpc {
 
@@ -14,6 +15,11 @@ void Engine::set_particles(int num_particles, const float* sigma, float kappa) {
     if (num_particles == 0) {
         part_P = 0;
         pnoise_valid = false;
+        if (cc_on) {                                                   // the chance constraint lives on the particles
+            HIP_CHECK(hipStreamSynchronize(stream));
+            cc_on = false;
+            cc_last_npop = cc_last_Nst = cc_last_RS = cc_last_P = 0;
+        }
         return;
     }
     REQUIRE(sigma != nullptr, BBMPC_E_INVALID, "null pointer argument: sigma");
@@ -109,11 +115,12 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
     const bool user_rew = particle_user_reward();          // a HIP-source reward over the learned model: TRAJ rollout + scorer
     REQUIRE(!user_path() || user_rew, BBMPC_E_UNSUPPORTED, "particles with user-supplied dynamics or an inverse target transform");
     const int P = part_P;
+    const bool boxed = cc_on && cfg.dynamics == BBMPC_DYN_MLP;      // bbmpc_set_chance_constraint: the TRAJ form whatever the reward
     if (user_rew) {                                        // refused before anything is allocated, drawn or launched
         require_particle_user_reward();
         (void)user_reward_params_dev();                    // (declared but not set: BBMPC_E_STATE)
-        require_particle_traj_fits(d_returns ? returns_stride : (long)ra.Nst * P);
     }
+    if (user_rew || boxed) require_particle_traj_fits(d_returns ? returns_stride : (long)ra.Nst * P);
     if (!d_returns) {
         returns_stride = ra.Nst * P;
         if (d_preturns.n < (size_t)A * returns_stride) d_preturns.alloc((size_t)A * returns_stride);
@@ -137,18 +144,33 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
     q.rewards = ra.rewards;
     q.penalty_out = ra.penalty_out;
     REQUIRE(ra.H == H, BBMPC_E_INVALID, "internal: particle rollout horizon");
-    if (user_rew) {
+    if (user_rew || boxed) {
         const size_t need = (size_t)ra.H * A * S * returns_stride;
         if (d_ptraj.n < need) d_ptraj.alloc(need);
         q.traj = d_ptraj.p;
     }
+    if (boxed) {
+        if (d_cc_first.n < (size_t)A * returns_stride) d_cc_first.alloc((size_t)A * returns_stride);
+        if (d_cc_viol.n < (size_t)A * ra.Nst) d_cc_viol.alloc((size_t)A * ra.Nst);
+    }
     const long rows = (long)ra.n_pop * P;
+    ParticleConstraintArgs cq;
+    memset(&cq, 0, sizeof(cq));
     dominant_inst[0] = 0;
     prof_begin();
     if (cfg.dynamics == BBMPC_DYN_MLP) {
         dominant_kernel = lv_heads > 0 ? "k_rollout_mlp_particles_gauss" : ens_E > 0 ? "k_rollout_mlp_particles_ens" : "k_rollout_mlp_particles";
         launch_rollout_mlp_particles(q);
         if (user_rew) score_particles_user(q);             // inside the profiled span, under the kind's name
+        if (boxed) {                                       // the box scan; a built-in reward's returns come from it too
+            cq.p = q;
+            cq.box = d_cc_box.p; cq.first = d_cc_first.p; cq.viol = d_cc_viol.p;
+            cq.delta = cc_delta; cq.lambda = cc_lambda;
+            const dim3 sgrid((unsigned)((rows + PCS_LANES - 1) / PCS_LANES), A), sblock(PCS_LANES);
+            if (user_rew) hipLaunchKernelGGL(k_particle_box_scan<false>, sgrid, sblock, 0, stream, cq);
+            else hipLaunchKernelGGL(k_particle_box_scan<true>, sgrid, sblock, (size_t)particle_box_scan_lds_floats(S, U) * sizeof(float), stream, cq);
+            HIP_CHECK(hipGetLastError());
+        }
     } else {
         dominant_kernel = "k_rollout_pendulum_particles";
         // few rows -> one wave per workgroup so every wave gets its own SIMD; many -> 256-thread workgroups
@@ -156,13 +178,19 @@ void Engine::rollout_particles(int mode, bool pen, RolloutArgs& ra, float* d_ret
         hipLaunchKernelGGL(k_rollout_pendulum_particles, dim3((unsigned)((rows + bs - 1) / bs), A), dim3(bs), 0, stream, q);
         HIP_CHECK(hipGetLastError());
     }
-    prof_end();
+    if (!boxed) prof_end();
     if (part_risk == BBMPC_RISK_CVAR)
         hipLaunchKernelGGL(k_particle_aggregate_cvar, dim3((ra.n_pop + CVAR_WAVES - 1) / CVAR_WAVES, A), dim3(CVAR_WAVES * 64), 0, stream, q,
                            part_tail);
     else
         hipLaunchKernelGGL(k_particle_aggregate, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, q, part_kappa);
     HIP_CHECK(hipGetLastError());
+    if (boxed) {                                           // behind the unchanged aggregate; the profiled span closes behind it
+        hipLaunchKernelGGL(k_particle_constraint_apply, dim3((ra.n_pop + 255) / 256, A), dim3(256), 0, stream, cq);
+        HIP_CHECK(hipGetLastError());
+        prof_end();
+        cc_last_npop = ra.n_pop; cc_last_Nst = ra.Nst; cc_last_RS = returns_stride; cc_last_P = P;
+    }
 }
 
 // returns [A][RS] from the states the TRAJ rollout left in pa.traj: one lane per (candidate, particle) row, grid.y = agent
@@ -187,7 +215,93 @@ void Engine::score_particles_user(const ParticleArgs& pa) {
 // the TRAJ rollout's buffer [H][A][S][RS] is addressed with 32-bit offsets
 void Engine::require_particle_traj_fits(long returns_stride) const {
     REQUIRE((long)H * A * S * returns_stride < (1L << 31), BBMPC_E_UNSUPPORTED,
-            "particles with a HIP-source reward: horizon * num_agents * dim_s * (candidates * num_particles) reaches 2^31 trajectory elements");
+            "particles with a HIP-source reward or a chance constraint: horizon * num_agents * dim_s * (candidates * num_particles) reaches 2^31 trajectory elements");
+}
+
+// Chance constraint.  Everything is checked before the handle is touched, so a refusal leaves it as
+// it was.  lo == hi == NULL removes it: the handle's launches and scores are then what they were before it was installed.
+void Engine::set_chance_constraint(const float* lo, const float* hi, float max_violation, float weight) {
+    REQUIRE((lo == nullptr) == (hi == nullptr), BBMPC_E_INVALID, "chance constraint: lo and hi must both be given, or both be NULL (remove)");
+    if (!lo) {
+        if (!cc_on) return;
+        invalidate_step_graph();
+        HIP_CHECK(hipStreamSynchronize(stream));
+        cc_on = false;
+        cc_last_npop = cc_last_Nst = cc_last_RS = cc_last_P = 0;
+        return;
+    }
+    for (int i = 0; i < S; ++i) {
+        REQUIRE(lo[i] == lo[i] && hi[i] == hi[i], BBMPC_E_INVALID,
+                "chance constraint: state bound " + std::to_string(i) + " is NaN (use -inf / +inf for unbounded)");
+        REQUIRE(lo[i] <= hi[i], BBMPC_E_INVALID, "chance constraint: lo[" + std::to_string(i) + "] exceeds hi[" + std::to_string(i) + "]");
+    }
+    REQUIRE(std::isfinite(max_violation) && max_violation >= 0.0f && max_violation < 1.0f, BBMPC_E_INVALID,
+            "chance constraint: max_violation must be in [0, 1)");
+    REQUIRE(std::isfinite(weight) && weight >= 0.0f, BBMPC_E_INVALID, "chance constraint: weight must be finite and >= 0");
+    REQUIRE(cfg.dynamics == BBMPC_DYN_MLP, BBMPC_E_UNSUPPORTED,
+            "chance constraint: the box is tested on the recorded particle rollouts of a learned model: the handle needs BBMPC_DYN_MLP, not "
+            "analytic or user dynamics");
+    REQUIRE(particles_on(), BBMPC_E_STATE, "chance constraint: particles are off: call bbmpc_set_particles first");
+    REQUIRE(!(cfg.reward == BBMPC_REW_USER && user_reward.cb), BBMPC_E_UNSUPPORTED,
+            "chance constraint with a callback reward: the particle evaluator needs a built-in or HIP-source reward (bbmpc_set_reward_source)");
+    std::vector<float> box((size_t)2 * S);
+    for (int i = 0; i < S; ++i) {
+        box[i] = lo[i];
+        box[S + i] = hi[i];
+    }
+    invalidate_step_graph();
+    HIP_CHECK(hipStreamSynchronize(stream));               // (nothing in flight reads the box that is replaced)
+    cc_on = false;
+    if (d_cc_box.n < box.size()) d_cc_box.alloc(box.size());
+    HIP_CHECK(hipMemcpy(d_cc_box.p, box.data(), box.size() * 4, hipMemcpyHostToDevice));
+    cc_delta = max_violation;
+    cc_lambda = weight;
+    cc_last_npop = cc_last_Nst = cc_last_RS = cc_last_P = 0;
+    cc_on = true;
+}
+
+// v [n_pop, A] and first [n_pop, P, A] of the most recent particle rollout, in the layouts of bbmpc_evaluate_particles
+void Engine::constraint_violations(int n_pop, float* prob_out, int32_t* first_out) {
+    REQUIRE(constraint_on(), BBMPC_E_STATE, "constraint violations: no chance constraint is installed (bbmpc_set_chance_constraint)");
+    REQUIRE(cc_last_npop > 0, BBMPC_E_STATE, "constraint violations: nothing has been rolled out since the chance constraint was installed");
+    REQUIRE(prob_out != nullptr, BBMPC_E_INVALID, "null pointer argument: prob_out");
+    REQUIRE(n_pop == cc_last_npop, BBMPC_E_INVALID,
+            "constraint violations: n_pop must be the candidates of the most recent rollout = " + std::to_string(cc_last_npop));
+    const int P = cc_last_P;
+    std::vector<float> v((size_t)A * n_pop);
+    std::vector<int32_t> f(first_out ? (size_t)A * n_pop * P : 0);
+    HIP_CHECK(hipMemcpy2DAsync(v.data(), (size_t)n_pop * 4, d_cc_viol.p, (size_t)cc_last_Nst * 4, (size_t)n_pop * 4, A, hipMemcpyDeviceToHost, stream));
+    if (first_out)
+        HIP_CHECK(hipMemcpy2DAsync(f.data(), (size_t)n_pop * P * 4, d_cc_first.p, (size_t)cc_last_RS * 4, (size_t)n_pop * P * 4, A,
+                                   hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (int a = 0; a < A; ++a)
+        for (int n = 0; n < n_pop; ++n) {
+            prob_out[(size_t)n * A + a] = v[(size_t)a * n_pop + n];
+            if (first_out)
+                for (int p = 0; p < P; ++p) first_out[((size_t)n * P + p) * A + a] = f[((size_t)a * n_pop + n) * P + p];
+        }
+}
+
+// bbmpc_get_state / bbmpc_set_state names of the constraint's tests: the buffers of the most recent rollout as they lie in
+// HBM, padding included ("constraint_first_raw" carries int32 bits).  true: the name was one of them.
+bool Engine::constraint_raw_state(const std::string& name, float* out, const float* in, int64_t count) {
+    if (name == "constraint_shape") {                     // (n_pop, Nst, RS, P) of the most recent constrained rollout; zeros: none
+        REQUIRE(out && count == 4, BBMPC_E_INVALID, "constraint_shape has four elements and cannot be set");
+        out[0] = (float)cc_last_npop; out[1] = (float)cc_last_Nst; out[2] = (float)cc_last_RS; out[3] = (float)cc_last_P;
+        return true;
+    }
+    void* buf = nullptr;
+    size_t n = 0;
+    if (name == "constraint_first_raw") { buf = d_cc_first.p; n = (size_t)A * cc_last_RS; }
+    else if (name == "constraint_viol_raw") { buf = d_cc_viol.p; n = (size_t)A * cc_last_Nst; }
+    else if (name == "particle_returns_raw") { buf = d_preturns.p; n = (size_t)A * cc_last_RS; }
+    else return false;
+    REQUIRE(cc_last_npop > 0 && buf, BBMPC_E_STATE, name + ": nothing has been rolled out under a chance constraint");
+    REQUIRE(count == (int64_t)n, BBMPC_E_INVALID, name + " has num_agents * stride elements (bbmpc_get_state \"constraint_shape\")");
+    if (out) HIP_CHECK(hipMemcpy(out, buf, n * 4, hipMemcpyDeviceToHost));
+    else HIP_CHECK(hipMemcpy(buf, in, n * 4, hipMemcpyHostToDevice));
+    return true;
 }
 
 // scores [n_pop, A] and (optional) returns [n_pop, P, A] in the reference's layouts, from the caller's sequences
@@ -197,7 +311,7 @@ void Engine::evaluate_particles_dev(const float* d_state_in, const float* d_seq,
     REQUIRE((long)n_pop * part_P <= (1L << 24), BBMPC_E_UNSUPPORTED, "particles: n_pop * num_particles must not exceed 2^24 per call");
     const int P = part_P;
     const int st = ((n_pop + 63) / 64) * 64;
-    if (particle_user_reward()) require_particle_traj_fits((long)st * P);
+    if (particle_user_reward() || constraint_on()) require_particle_traj_fits((long)st * P);
     if (d_eval_rew.n < (size_t)A * st) d_eval_rew.alloc((size_t)A * st);
     RolloutArgs ra;
     memset(&ra, 0, sizeof(ra));
@@ -239,6 +353,20 @@ int bbmpc_set_particle_risk(bbmpc_handle h, int32_t kind, int32_t tail_count) {
     API_END
 }
 
+int bbmpc_set_chance_constraint(bbmpc_handle h, const float* lo, const float* hi, float max_violation, float weight) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->set_chance_constraint(lo, hi, max_violation, weight);
+    API_END
+}
+
+int bbmpc_get_constraint_violations(bbmpc_handle h, int32_t n_pop, float* prob_out, int32_t* first_step_out) {
+    API_BEGIN
+    CHECK_HANDLE(h);
+    h->e->constraint_violations(n_pop, prob_out, first_step_out);
+    API_END
+}
+
 int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const float* d_seq, int32_t n_pop, float* d_scores,
                                  float* d_returns) {
     API_BEGIN
@@ -259,7 +387,8 @@ int bbmpc_evaluate_particles(bbmpc_handle h, const float* state, const float* se
     Engine& e = *h->e;
     if (!e.particles_on()) throw HipError(BBMPC_E_STATE, "particles are off: call bbmpc_set_particles first");
     if (n_pop < 1) throw HipError(BBMPC_E_INVALID, "n_pop must be >= 1");
-    if (e.particle_user_reward()) e.require_particle_traj_fits((((long)n_pop + 63) / 64) * 64 * e.part_P);     // before the staging buffer
+    if (e.particle_user_reward() || e.constraint_on())
+        e.require_particle_traj_fits((((long)n_pop + 63) / 64) * 64 * e.part_P);     // before the staging buffer
     const size_t nsc = (size_t)n_pop * e.A;
     HostStage st(e);
     const int q = st.in(seq, nsc * e.HU), sc = st.out(scores, nsc), ret = st.out(returns, nsc * e.part_P);

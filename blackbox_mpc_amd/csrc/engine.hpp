@@ -595,6 +595,20 @@ struct Engine {
     void score_particles_user(const ParticleArgs& pa);                        // bbmpc_particles.hip
     void require_particle_traj_fits(long returns_stride) const;               // H * A * S * RS < 2^31, before anything is allocated
     void score_traj_particles_user(const TrajParticleArgs& pa);               // bbmpc_user.hip
+    // chance constraint (bbmpc_set_chance_constraint; bbmpc_particles.hip, kernels_particle_constraint.hpp, DESIGN.md section
+    // 8t): a state box over the noisy states of the learned model's particle rollouts.  While it is installed the rollout
+    // takes the TRAJ form whatever the reward, k_particle_box_scan finds every row's first step outside the box (and, for a
+    // built-in reward, the row's return) and k_particle_constraint_apply subtracts weight * max(0, v - max_violation) from
+    // the aggregate's score.  Removed by bbmpc_set_particles(0).
+    bool cc_on = false;
+    float cc_delta = 0.0f, cc_lambda = 0.0f;
+    DevBuf<float> d_cc_box, d_cc_viol;                  // [2][S] lo | hi; [A][Nst] v of the most recent rollout ...
+    DevBuf<int> d_cc_first;                             // ... and its first steps [A][RS]
+    int cc_last_npop = 0, cc_last_Nst = 0, cc_last_RS = 0, cc_last_P = 0;      // its shape (0: nothing rolled out since the install)
+    bool constraint_on() const { return cc_on; }
+    void set_chance_constraint(const float* lo, const float* hi, float max_violation, float weight);
+    void constraint_violations(int n_pop, float* prob_out, int32_t* first_out);
+    bool constraint_raw_state(const std::string& name, float* out, const float* in, int64_t count);   // get_state / set_state names of tests
     // model ensemble for the particle rollouts (bbmpc_set_mlp_ensemble; bbmpc_mlp.hip, kernels_mlp_particles.hpp): particle p
     // follows member p % ens_E.  Every deterministic path keeps the model of bbmpc_set_mlp.
     int ens_E = 0;

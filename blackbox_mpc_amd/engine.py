@@ -511,6 +511,35 @@ class Engine:
         L.check(L.lib.bbmpc_set_particle_risk(self._h, int(kind), int(tail_count)))
         self.risk = (int(kind), int(tail_count))
 
+    def set_chance_constraint(self, lo, hi, max_violation=0.0, weight=1e3):
+        """Chance constraint of the particle evaluator (bbmpc_set_chance_constraint): a state box [lo, hi] ([dim_S] each,
+        -inf / +inf = unbounded) that does not end a rollout; a candidate's score loses
+        weight * max(0, v - max_violation), v the share of its particles that ever leave the box.  Needs a DYN_MLP handle
+        with particles on and a built-in or HIP-source reward.  lo = hi = None removes it."""
+        bounds = []
+        for b in (lo, hi):
+            if b is not None:
+                b = L.f32c(np.asarray(b, np.float32).reshape(-1))
+                if b.shape != (self.S,):         # the C side reads dim_S floats from this buffer
+                    raise ValueError("a state bound must be [%d], got %s" % (self.S, b.shape))
+            bounds.append(b)
+        L.check(L.lib.bbmpc_set_chance_constraint(self._h, L.ptr(bounds[0]), L.ptr(bounds[1]), ctypes.c_float(float(max_violation)),
+                                                  ctypes.c_float(float(weight))))
+
+    def clear_chance_constraint(self):
+        L.check(L.lib.bbmpc_set_chance_constraint(self._h, None, None, ctypes.c_float(0.0), ctypes.c_float(0.0)))
+
+    def constraint_violations(self, n_pop=None, first_steps=False):
+        """v of the most recent particle rollout (bbmpc_get_constraint_violations): float32 [n_pop, A], the share of each
+        candidate's particles that left the box; with first_steps also int32 [n_pop, P, A], the first step in 1 .. H
+        outside the box, 0 = never.  n_pop: the candidates of that rollout -- by default what the handle says it rolled
+        out (bbmpc_get_state "constraint_shape")."""
+        n = int(n_pop if n_pop is not None else self.get_state("constraint_shape", (4,))[0])
+        prob = np.empty((max(n, 0), self.A), np.float32)
+        first = np.empty((max(n, 0), max(int(getattr(self, "P", 0)), 1), self.A), np.int32) if first_steps else None
+        L.check(L.lib.bbmpc_get_constraint_violations(self._h, n, L.ptr(prob), L.ptr(first)))
+        return (prob, first) if first_steps else prob
+
     def evaluate_particles(self, state, action_sequences, want_returns=True):
         """(scores [n, A], per-particle returns [n, P, A] or None) -- bbmpc_evaluate_particles."""
         state = L.f32c(state)

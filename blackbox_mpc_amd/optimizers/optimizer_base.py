@@ -64,6 +64,10 @@ class OptimizerBase:
         if term is not None and eng.__dict__.get("_shaping_version", (0, 0, 0))[2] != term._version:
             from ..trajectory_evaluators.deterministic import configure_return_shaping
             configure_return_shaping(eng, self._trajectory_evaluator)
+        box = getattr(self._trajectory_evaluator, "_constraint", None)            # a chance constraint that was changed, likewise
+        if box is not None and eng.__dict__.get("_constraint_version", (0, 0))[1] != box._version:
+            from ..trajectory_evaluators.particle import configure_constraint
+            configure_constraint(eng, self._trajectory_evaluator)
         prior = getattr(self, "_policy_prior", None)                              # a refitted policy prior, likewise
         if prior is not None and eng.__dict__.get("_prior_version") != getattr(prior[0], "_version", 0):
             self._configure_policy_prior(eng)
@@ -177,6 +181,8 @@ class OptimizerBase:
             risk = getattr(trajectory_evaluator, "risk_settings", (L.RISK_MEAN_STD, 0))
             if risk[0] != L.RISK_MEAN_STD:            # (the engine is new: mean - kappa * std is what it starts with)
                 self._engine.set_particle_risk(*risk)
+            from ..trajectory_evaluators.particle import configure_constraint
+            configure_constraint(self._engine, trajectory_evaluator)      # a StateBoxConstraint (constraint=), behind set_particles
         mix = getattr(self, "_sampling_mix", None)    # CEM / PI2 with noise_beta / sampling_correlation
         if mix is not None:
             self._engine.set_sampling_correlation(mix)

@@ -20,8 +20,11 @@ class MPCPolicy(ModelBasedBasePolicy):
                  reward_function=None, env_action_space=None, env_observation_space=None,
                  dynamics_function=None, dynamics_handler=None, true_model=False, optimizer_name=None,
                  num_agents=None, save_model_frequency=1, saved_model_dir=None, terminal_value=None, terminal_weight=1.0,
-                 refine_steps=0, refine_lr=0.05, refine_device=False, discount=1.0, termination=None, **optimizer_args):
-        """terminal_value / terminal_weight: a LearnedValueMLP that closes the planning horizon (handed to the
+                 refine_steps=0, refine_lr=0.05, refine_device=False, discount=1.0, termination=None, constraint=None, **optimizer_args):
+        """constraint: the utils.constraints.StateBoxConstraint of the ParticleTrajectoryEvaluator passed in (it must carry
+        this very object: a chance constraint is a statement about particles, and the evaluator this constructor builds is
+        deterministic); `plan_violation` then reports the plan's violation probability.
+        terminal_value / terminal_weight: a LearnedValueMLP that closes the planning horizon (handed to the
         DeterministicTrajectoryEvaluator this constructor builds; an evaluator passed in takes them itself).
         discount / termination: a discount in (0, 1] and a utils.termination.StateBoxTermination, handed to that evaluator
         likewise: plans score sum_t discount^t r_t up to the first state outside the box (bbmpc_set_return_shaping); not
@@ -51,6 +54,11 @@ class MPCPolicy(ModelBasedBasePolicy):
                                  "(DeterministicMLP) and a learned reward (LearnedRewardMLP), got %s and %s"
                                  % (type(df).__name__, type(rf).__name__))
         self._refined_plan = self._unrefined_plan = None
+        if constraint is not None and (trajectory_evaluator is None or getattr(trajectory_evaluator, "particle_settings", None) is None
+                                       or getattr(trajectory_evaluator, "_constraint", None) is not constraint):
+            raise ValueError("constraint needs a ParticleTrajectoryEvaluator that carries it: construct "
+                             "ParticleTrajectoryEvaluator(..., constraint=constraint) and pass it as trajectory_evaluator (the "
+                             "evaluator MPCPolicy builds itself is deterministic and has no particles)")
         if trajectory_evaluator is not None and terminal_value is not None:
             raise ValueError("terminal_value goes to the trajectory evaluator: construct it with terminal_value=, "
                              "or leave trajectory_evaluator to MPCPolicy")
@@ -161,6 +169,21 @@ class MPCPolicy(ModelBasedBasePolicy):
         if observations.ndim == 1:
             return tuple(o[0] for o in out)
         return out
+
+    def plan_violation(self, observations):
+        """v [A] of the plan the last `act` took its action from (a scalar for a 1-D observation): the share of the
+        ParticleTrajectoryEvaluator's particles that leave its StateBoxConstraint when the plan is rolled out from
+        `observations` (violation_probability of the plan `plan` returns).  Needs keep_plan(True) before that `act`."""
+        ev = self._trajectory_evaluator
+        if getattr(ev, "_constraint", None) is None:
+            raise ValueError("plan_violation() needs a ParticleTrajectoryEvaluator constructed with constraint=")
+        observations = np.asarray(observations)
+        batched = observations
+        if observations.ndim == 1:
+            batched = np.tile(observations[None], (self._optimizer._num_agents, 1))
+        actions = self._optimizer.plan(batched)[0]
+        v = ev.violation_probability(np.asarray(batched, np.float32), actions[None])[0]
+        return v[0] if observations.ndim == 1 else v
 
     def reset(self):
         self._optimizer.reset()

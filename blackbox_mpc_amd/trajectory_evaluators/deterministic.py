@@ -207,13 +207,19 @@ _SHAPED_GRADIENT = ("%s beside discount / termination: the differentiated return
 
 class DeterministicTrajectoryEvaluator(EvaluatorBase):
     def __init__(self, reward_function, system_dynamics_handler, quirks=0, terminal_value=None, terminal_weight=1.0,
-                 discount=1.0, termination=None):
-        """terminal_value: a LearnedValueMLP V -- candidates then score sum_t r_t + terminal_weight * V(s_H) (learned
+                 discount=1.0, termination=None, constraint=None):
+        """constraint: refused here -- a utils.constraints.StateBoxConstraint is a statement about the particles of
+        ParticleTrajectoryEvaluator.
+        terminal_value: a LearnedValueMLP V -- candidates then score sum_t r_t + terminal_weight * V(s_H) (learned
         dynamics only; bbmpc_set_terminal_value_mlp).  The one-step calls and predict_trajectories do not read it.
         discount in (0, 1] / termination: a utils.termination.StateBoxTermination -- candidates then score
         sum_t discount^t r_t up to the first state outside the box, where they collect discount^T * terminal_reward and no
         terminal value; candidates that stay inside close with discount^H * terminal_weight * V(s_H) (learned dynamics with
         a built-in reward or a LearnedRewardMLP; bbmpc_set_return_shaping)."""
+        if constraint is not None:
+            raise NotImplementedError("DeterministicTrajectoryEvaluator has no chance constraint: a StateBoxConstraint limits the share "
+                                      "of PARTICLES that leave the box, and one noise-free rollout has none (use "
+                                      "ParticleTrajectoryEvaluator(..., constraint=))")
         super().__init__(reward_function=reward_function, system_dynamics_handler=system_dynamics_handler, name=None)
         self._quirks = int(quirks)
         self._terminal_value = terminal_value

@@ -41,13 +41,36 @@ def quantile_rank(tau, num_particles):
     return min(p - 1, max(0, math.ceil(t * p - 1e-9) - 1))
 
 
+def _constraint_version(evaluator):
+    c = getattr(evaluator, "_constraint", None)
+    return (id(c), getattr(c, "_version", 0))
+
+
+def configure_constraint(engine, evaluator):
+    """Upload the evaluator's StateBoxConstraint (constraint=) behind set_particles; nothing to do without one."""
+    c = getattr(evaluator, "_constraint", None)
+    if c is None:
+        return
+    lo, hi = c.bounds(engine.S)
+    engine.set_chance_constraint(lo, hi, c.max_violation, c.weight)
+    engine._constraint_version = _constraint_version(evaluator)
+
+
+def constraint_stale(engine, evaluator):
+    """A box whose bounds, limit or weight changed since they were uploaded (or that was never uploaded to this engine)."""
+    return getattr(evaluator, "_constraint", None) is not None and engine.__dict__.get("_constraint_version") != _constraint_version(evaluator)
+
+
 class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
     def __init__(self, reward_function, system_dynamics_handler, num_particles, process_noise_std, risk_kappa=0.0,
-                 quirks=0, risk_alpha=None, terminal_value=None, terminal_weight=1.0, discount=1.0, termination=None):
+                 quirks=0, risk_alpha=None, terminal_value=None, terminal_weight=1.0, discount=1.0, termination=None,
+                 constraint=None):
         """process_noise_std: a scalar or [dim_S], >= 0 -- for a learned model SystemDynamicsHandler.residual_std() is
         the natural choice.  risk_kappa > 0 prefers candidates whose return varies little over the particles.
         risk_alpha in (0, 1] scores the mean of the ceil(risk_alpha * num_particles) worst returns instead (CVaR; not
-        together with risk_kappa != 0)."""
+        together with risk_kappa != 0).  constraint: a utils.constraints.StateBoxConstraint -- a candidate's score then
+        loses weight * max(0, v - max_violation), v the share of its particles whose noisy state ever leaves the box
+        (learned dynamics with a built-in or HIP-source reward; bbmpc_set_chance_constraint)."""
         if getattr(reward_function, "_bbmpc_reward_kind", None) == L.REW_MLP:
             raise NotImplementedError("ParticleTrajectoryEvaluator does not score a LearnedRewardMLP yet: the particle rollouts take "
                                       "built-in and HIP-source rewards (use DeterministicTrajectoryEvaluator with a learned reward)")
@@ -78,6 +101,15 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
                 raise ValueError("risk_alpha (CVaR) and risk_kappa != 0 (mean - kappa * std) are two scoring rules: give one")
             self._risk = (L.RISK_CVAR, cvar_tail_count(risk_alpha, p))
         self._num_particles, self._process_noise_std, self._risk_kappa = p, sg, float(risk_kappa)
+        if constraint is not None:
+            if not (callable(getattr(constraint, "bounds", None)) and hasattr(constraint, "max_violation") and hasattr(constraint, "weight")):
+                raise ValueError("constraint must be a StateBoxConstraint, got %r" % (constraint,))
+            if getattr(system_dynamics_handler._dynamics_function, "_bbmpc_dynamics_kind", None) != L.DYN_MLP:
+                raise NotImplementedError("a StateBoxConstraint is tested on the particle rollouts of a learned model "
+                                          "(DeterministicMLP, EnsembleMLP, ProbabilisticMLP), not of %s"
+                                          % type(system_dynamics_handler._dynamics_function).__name__)
+            constraint.bounds(dim_s)                       # (a box of another length is refused here)
+        self._constraint = constraint
 
     @property
     def risk_settings(self):
@@ -110,7 +142,27 @@ class ParticleTrajectoryEvaluator(DeterministicTrajectoryEvaluator):
             eng.set_particles(*self.particle_settings)
             eng.set_particle_risk(*self.risk_settings)         # (also resets a CVaR another evaluator left behind)
             eng._particle_settings = self
+            eng.__dict__.pop("_constraint_version", None)       # (set_particles(0) in between would have removed the box)
+        if constraint_stale(eng, self):
+            configure_constraint(eng, self)
         return eng
+
+    def _violations(self, current_states, action_sequences, first_steps):
+        if self._constraint is None:
+            raise ValueError("this ParticleTrajectoryEvaluator has no constraint (construct it with constraint=StateBoxConstraint(...))")
+        seq = np.asarray(action_sequences, np.float32)
+        eng = self._particle_engine(seq)
+        eng.evaluate_particles(current_states, seq, want_returns=False)
+        return eng.constraint_violations(seq.shape[0], first_steps=first_steps)
+
+    def violation_probability(self, current_states, action_sequences):
+        """current_states [A,S], action_sequences [N,A,H,U] -> v [N,A]: the share of each sequence's particles whose noisy
+        state leaves the constraint's box at some step of the horizon."""
+        return self._violations(current_states, action_sequences, False)
+
+    def first_violation_steps(self, current_states, action_sequences):
+        """... -> int32 [N,P,A]: per particle the first step in 1 .. H outside the box, 0 = never."""
+        return self._violations(current_states, action_sequences, True)[1]
 
     def predict_trajectory_distribution(self, current_states, action_sequences, eps=None, return_particles=False, quantiles=None):
         """current_states [B,S], action_sequences [B,Hq,U] -> (state_mean [B,Hq,S], state_std [B,Hq,S], reward_mean [B,Hq],

@@ -500,6 +500,32 @@ int bbmpc_evaluate_particles_dev(bbmpc_handle h, const float* d_state, const flo
 #define BBMPC_RISK_CVAR     1
 int bbmpc_set_particle_risk(bbmpc_handle h, int32_t kind, int32_t tail_count);
 
+/* Chance constraint of the particle evaluator: a state box [lo, hi] ([dim_S] each, -inf / +inf =
+ * unbounded in that feature) that does NOT end a rollout.  The share of a candidate's particles that ever leave the box
+ * becomes a penalty on its score; per agent a, candidate n, particle p, with s_1 .. s_H the noisy next states of the
+ * particle recurrence above (s_0 is given and not tested):
+ *     out(s)       = any i: s[i] < lo[i] or s[i] > hi[i]     (both false on NaN: a NaN state violates nothing)
+ *     first[n,p,a] = the smallest t in 1 .. H with out(s_t), else 0
+ *     v[n,a]       = (float)#{p : first[n,p,a] != 0} / (float)P
+ *     score'[n,a]  = score[n,a] - weight * max(0, v[n,a] - max_violation)          (fp32, in this order)
+ * score is what the handle computes without the constraint (mean - kappa * std or CVaR, minus the bound penalty); the
+ * per-particle returns are not changed.  All six optimizers then plan on score', bbmpc_evaluate[_particles] returns it.
+ * Needs BBMPC_DYN_MLP dynamics (plain, ensemble or log-variance heads), particles on, and a built-in or HIP-source reward.
+ * lo == hi == NULL removes the constraint: the handle then launches and scores what it did before, bit for bit.
+ * bbmpc_set_particles(h, 0, ..) removes it as well; another num_particles keeps it.  Installing or removing it
+ * invalidates a captured step graph.  The record of a control step, the one-step calls, bbmpc_predict_trajectory_particles /
+ * _quantiles and every deterministic path never read it.
+ * BBMPC_E_INVALID: exactly one of lo / hi NULL, a NaN bound, lo[i] > hi[i], max_violation outside [0, 1) or not finite,
+ * weight negative or not finite.  BBMPC_E_UNSUPPORTED: dynamics other than BBMPC_DYN_MLP, a callback reward.
+ * BBMPC_E_STATE: particles are off.  With it installed, horizon * num_agents * dim_s * (candidates rounded up to 64 *
+ * num_particles) must stay below 2^31 per rollout (BBMPC_E_UNSUPPORTED from the computing call).  A refused call leaves the
+ * handle as it was.
+ * bbmpc_get_constraint_violations: v of the handle's most recent particle rollout as prob_out [n_pop, A] and, when
+ * first_step_out is not NULL, first as [n_pop, P, A].  Synchronous.  BBMPC_E_STATE: no constraint installed, or nothing
+ * rolled out since it was.  BBMPC_E_INVALID: prob_out NULL, n_pop different from that rollout's. */
+int bbmpc_set_chance_constraint(bbmpc_handle h, const float* lo, const float* hi, float max_violation, float weight);
+int bbmpc_get_constraint_violations(bbmpc_handle h, int32_t n_pop, float* prob_out, int32_t* first_step_out);
+
 /* Model ensemble with trajectory sampling for the particle evaluator (PETS, TS-infinity): num_members networks of the shape,
  * activations and six normalisation statistics of the model that bbmpc_set_mlp installed, e.g. fitted on bootstrap
  * resamples of the training rows.  weights / biases: num_members x n_layers pointers, member-major (entry e * n_layers + l),
